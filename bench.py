@@ -3,7 +3,8 @@
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 launched as
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one rank per GPU,
-RCCL).  Rank 0 prints ONE JSON line.
+RCCL).  Rank 0 prints ONE JSON line; its `ms_per_step` is the wall time of one of the K timed steps.  `--dump-outputs DIR`
+also writes what the last timed step returned (DIR/segments.npy) so that two builds can be compared on the same seeded input.
 
 Workloads
   segmenter (default at EVERY --gpus N)  the configuration the metric is quoted on, below: one recording per rank (weak scaling,
@@ -914,6 +915,28 @@ def timed_steps(step, k, comm, sync):
     return dt, out, dt_own
 
 
+DUMP_LIMIT_BYTES = (64 << 20) - (64 << 10)          # 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each (rows, ...) array -> <out_dir>/<name>.npy in float64.  When the arrays exceed DUMP_LIMIT_BYTES in
+    all, every array keeps the same fraction of its rows, drawn with a fixed seed (kept in order), and the indices of the kept
+    rows go to <name>_rows.npy.  -> {name: shape written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(a, np.float64) for k, a in arrays.items()}
+    full = sum(a.nbytes for a in arrays.values())
+    with_index = sum(a.nbytes + 8 * len(a) for a in arrays.values())
+    out = {}
+    for name, a in arrays.items():
+        if full > DUMP_LIMIT_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(len(a), int(len(a) * DUMP_LIMIT_BYTES / with_index), replace=False))
+            np.save(os.path.join(out_dir, name + '_rows.npy'), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        out[name] = list(a.shape)
+    return out
+
+
 def main_fake_device(args, rank, world):
     """Tests only (`--fake-device module:factory`): the launcher / rank / communicator / timing / line-assembly code of an N-rank
     run with the Segmenter replaced by `factory(rank)` (an object with segment_device_pcm(ptr, n, dense=...)), so that the N > 1
@@ -927,16 +950,20 @@ def main_fake_device(args, rank, world):
     for _ in range(args.warmup):
         step()
     dt, (lseg, rows), dt_local = timed_steps(step, args.steps, comm, lambda: None)
+    dumped = dump_outputs(args.dump_outputs, {'segments': rows}) if args.dump_outputs and rank == 0 else None
     dt_min = -comm.max_over_ranks(-dt_local) if comm else dt_local
     if comm:
         comm.barrier()
     if rank == 0:
-        print(json.dumps({"metric": "SELF-TEST of bench.py's N-rank path on a fake device (no audio was segmented)", "value": None,
-                          "unit": None, "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-                          "data": "fake-device", "scaling": "weak",
-                          "config": {"parallelism": f"x{world}: {comm_kind}", "rows_gathered": int(len(rows)),
-                                     "files_seen": sorted({int(r[0]) for r in rows})},
-                          "ranks": {"ms_per_step_min": dt_min / args.steps * 1e3, "ms_per_step_max": dt / args.steps * 1e3}}))
+        line = {"metric": "SELF-TEST of bench.py's N-rank path on a fake device (no audio was segmented)", "value": None,
+                "unit": None, "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+                "data": "fake-device", "scaling": "weak",
+                "config": {"parallelism": f"x{world}: {comm_kind}", "rows_gathered": int(len(rows)),
+                           "files_seen": sorted({int(r[0]) for r in rows})},
+                "ranks": {"ms_per_step_min": dt_min / args.steps * 1e3, "ms_per_step_max": dt / args.steps * 1e3}}
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
+        print(json.dumps(line))
 
 
 def main():
@@ -974,8 +1001,17 @@ def main():
                          "multi-GPU data path -- a failed rendezvous is an error, there is no fallback); torch = a torch.distributed nccl "
                          "group, asked for explicitly; gloo = host-memory group, which also lets the N ranks SHARE the visible GPUs "
                          "(single-GPU rehearsal of the N-rank code path; the line is labelled, it is not a scaling result)")
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='segmenter workload: after the timed steps, write the segment table the last timed step returned as '
+                         'DIR/segments.npy, float64 rows (rank, label id in inaspeechsegmenter_amd.sharding.LABELS, start slot, '
+                         'stop slot) in 20 ms slots, every rank\'s rows; the inputs are seeded, so runs with the same arguments compare '
+                         'row for row')
     ap.add_argument('--fake-device', default='', help=argparse.SUPPRESS)      # tests only: 'module:factory' replacing the Segmenter
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.workload != 'segmenter':
+        ap.error('--dump-outputs: the segmenter workload only')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:             # no launcher: become one (the driver's own command line)
         raise SystemExit(self_spawn(args.gpus, sys.argv[1:]))
@@ -1042,6 +1078,7 @@ def main():
         return timed_steps(lambda: step(dense), k, comm, sync)
 
     dt, (lseg, rows), dt_local = timed(args.steps, True)
+    dumped = dump_outputs(args.dump_outputs, {'segments': rows}) if args.dump_outputs and rank == 0 else None
     value = world * args.steps * hours / dt
     dt_min = -comm.max_over_ranks(-dt_local) if comm else dt_local
     rccl = comm_audit(comm, comm_kind, rank, world) if comm else None
@@ -1209,6 +1246,8 @@ def main():
                                            "split mode or, failing that, to exact f32 (north star: within 1e-3)"}
         if companions:
             line["companions"] = companions
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line))
     seg.close()
 

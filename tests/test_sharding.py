@@ -204,3 +204,39 @@ def test_bench_has_no_silent_comm_fallback():
     assert bench.make_comm(NoRccl(), 0, 1, None, 'rccl') == (None, None)
     r, lines = _run_bench(['--gpus', '2', '--steps', '1', '--warmup', '0', '--minutes', '1', '--fake-device', 'tests.fake_bench_device:make'])
     assert r.returncode != 0 and not lines and 'no fallback' in r.stderr, r.stdout + r.stderr       # default --comm rccl, no device
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` writes the segment table the last timed step returned as DIR/segments.npy (float64 rows: rank, label id,
+    start slot, stop slot); the same arguments give the same file; `--steps` is the number of timed steps and must be >= 1."""
+    from tests.fake_bench_device import make
+    want = sh.pack_segments(0, make(0).segment_device_pcm(0, 60 * 16000))
+    got = []
+    for d in ('a', 'b'):
+        r, lines = _run_bench(['--gpus', '1', '--steps', '4', '--warmup', '1', '--minutes', '1', '--dump-outputs', str(tmp_path / d),
+                               '--fake-device', 'tests.fake_bench_device:make'])
+        assert r.returncode == 0 and len(lines) == 1, r.stdout + r.stderr
+        assert lines[0]['steps'] == 4 and lines[0]['ms_per_step'] >= 10.0        # the fake device sleeps 10 ms per step on rank 0
+        assert lines[0]['dumped_outputs'] == {'segments': [len(want), 4]}
+        assert sorted(os.listdir(tmp_path / d)) == ['segments.npy']
+        got.append(np.load(tmp_path / d / 'segments.npy'))
+    assert got[0].dtype == np.float64 and np.array_equal(got[0], want) and np.array_equal(got[0], got[1])
+    r, lines = _run_bench(['--gpus', '1', '--steps', '0', '--fake-device', 'tests.fake_bench_device:make'])
+    assert r.returncode != 0 and not lines and '--steps' in r.stderr
+    r, lines = _run_bench(['--workload', 'vbx', '--dump-outputs', str(tmp_path / 'c'), '--fake-device', 'tests.fake_bench_device:make'])
+    assert r.returncode != 0 and not lines and '--dump-outputs' in r.stderr
+
+
+def test_bench_dump_outputs_samples_above_the_limit(tmp_path, monkeypatch):
+    """Outputs larger than the dump limit keep a fixed, seeded sample of their rows (in order) with the row indices beside them."""
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 4096)
+    big = np.arange(1000 * 4, dtype=np.int32).reshape(1000, 4)
+    for d in ('a', 'b'):
+        shapes = bench.dump_outputs(str(tmp_path / d), {'segments': big})
+        rows = np.load(tmp_path / d / 'segments_rows.npy')
+        seg = np.load(tmp_path / d / 'segments.npy')
+        assert shapes == {'segments': list(seg.shape)} and 0 < len(seg) < 1000
+        assert seg.nbytes + rows.nbytes <= 4096 and rows.dtype == np.float64
+        assert np.all(np.diff(rows) > 0) and np.array_equal(seg, big[rows.astype(np.int64)].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / 'a' / 'segments.npy'), np.load(tmp_path / 'b' / 'segments.npy'))

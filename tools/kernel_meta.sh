@@ -1,9 +1,9 @@
 #!/bin/bash
 # Registers / LDS / spills of the kernels of one csrc/*.hip unit (device-only compile, no GPU needed) and its gfx950 disassembly:
-#   bash tools/kernel_meta.sh cnn.hip [name filter]      -> table on stdout, /tmp/iss_meta/<unit>.s
+#   bash tools/kernel_meta.sh cnn.hip [name filter]      -> table on stdout, $ISS_META_DIR/<unit>.s (default /tmp/iss_meta)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 U=${1:-cnn.hip}; F=${2:-.}
-B=$(basename $U .hip); O=/tmp/iss_meta; mkdir -p $O
+B=$(basename $U .hip); O=$(mkdir -p "${ISS_META_DIR:-/tmp/iss_meta}" && cd "${ISS_META_DIR:-/tmp/iss_meta}" && pwd) || exit 1
 LL=/opt/rocm/lib/llvm/bin
 cd $ROOT/inaspeechsegmenter_amd/csrc
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Wno-unused-function -mllvm -pragma-unroll-threshold=100000 \
