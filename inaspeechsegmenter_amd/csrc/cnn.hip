@@ -1263,11 +1263,27 @@ extern "C" int iss_cnn_set_net_precision(iss_ctx* c, int id, int mode) {
     return ISS_OK;
 }
 
+// A patch network (iss_cnn_probs) reads mspec windows through its first conv; iss_cnn_forward and iss_vbx_embed run every other kind.
+static bool net_reads_patches(const IssNet& n) {
+    for (int r = 0; r < n.nrows; ++r)
+        if (n.prog[(size_t)r * ISS_PROG_COLS + ISS_C_OP] == ISS_OP_CONV && n.prog[(size_t)r * ISS_PROG_COLS + ISS_C_INMODE] == 1) return true;
+    return false;
+}
+
+// The arithmetic a network actually runs in.  fp16 operand halves overflow on an activation beyond 65504, and only the precision
+// guard's probe (iss_cnn_probs) can see that happen: ISS_PREC_F16X3 takes them on patch networks whose parameters are inside
+// fp16's range, every other network runs ISS_PREC_BF16X3 (the same MFMA count, f32's range).
+static int effective_precision(const iss_ctx* c, const IssNet& n) {
+    const int prec = n.prec_override >= 0 ? n.prec_override : c->precision;
+    if (prec == ISS_PREC_F16X3 && !(n.f16_ok && n.d_wh16 != nullptr && net_reads_patches(n))) return ISS_PREC_BF16X3;
+    return prec;
+}
+
 extern "C" int iss_cnn_precision_info(iss_ctx* c, int id, int32_t* mode, float* max_dlogp, int32_t* slots, int32_t* state, float* dlogp_in_use) {
     if (!c || id < 0 || id >= ISS_MAX_NETS) return ISS_EINVAL;
     const IssNet& n = c->nets[id];
     if (!n.loaded) return iss_fail(c, ISS_ESTATE, "net %d not loaded", id);
-    if (mode) *mode = n.prec_override >= 0 ? n.prec_override : c->precision;
+    if (mode) *mode = effective_precision(c, n);
     if (max_dlogp) *max_dlogp = n.guard_dlogp;
     if (slots) *slots = n.guard_slots;
     if (state) *state = n.guard_state;
@@ -1348,13 +1364,13 @@ int footprint_pixels(const ConvArgs& a, int TM = BM) {      // largest pixel spa
 int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const float* d_stats,
                 const uint8_t* d_fin, const float* d_input, float** result, int rmin = 0, int rmax = -1,
                 bool share_first = false) {
-    const int prec = n.prec_override >= 0 ? n.prec_override : c->precision;          // (precision guard: one network may run exact f32)
+    const int prec = effective_precision(c, n);                 // (precision guard: one network may run another mode)
     const bool x3mode = prec != ISS_PREC_F32;                    // a split-operand mode (bf16 or fp16 halves)
     // ISS_PREC_F16X3: the launches with an fp16 instantiation (the one-wave-per-SIMD conv2 / conv3 / conv4 kernels and the long-K
     // dense kernel: > 99.9 % of the segmenter nets' arithmetic) take fp16 operand halves; a SMALL layer without one runs in exact
     // f32 (conv_igemm_kernel: tests/precision_emulation.py -- the last dense layers in bf16 halves would undo most of the gain),
     // anything else keeps bf16 halves
-    const bool f16mode = prec == ISS_PREC_F16X3 && n.f16_ok && n.d_wh16 != nullptr;
+    const bool f16mode = prec == ISS_PREC_F16X3;
     double net_flops = 0.0;
     if (f16mode)
         for (int q = 0; q < n.nrows; ++q) {
@@ -2244,7 +2260,7 @@ static int cnn_probs_impl(iss_ctx* c, int id, const int32_t* win_row, int32_t ns
 // layer needs overlapping windows) -- are evaluated in both arithmetic modes; max |d log p| decides.
 static int precision_guard(iss_ctx* c, int id, const int32_t* win_row, int32_t nslots) {
     IssNet& n = c->nets[id];
-    const int eff = n.prec_override >= 0 ? n.prec_override : c->precision;
+    const int eff = effective_precision(c, n);
     if (eff == ISS_PREC_F32) { n.guard_state = ISS_GUARD_FIXED; return ISS_OK; }
     if (!(c->guard_threshold > 0.f)) return ISS_OK;               // guard off: stays pending
     const int runs = nslots >= 256 ? 4 : 1, per = nslots >= 256 ? 64 : nslots;
@@ -2296,6 +2312,7 @@ static int precision_guard(iss_ctx* c, int id, const int32_t* win_row, int32_t n
     c->in_guard = false;
     n.prec_override = -1;
     if (rc != ISS_OK) return rc;
+    if (compared == 0) { n.guard_slots = 0; return ISS_OK; }    // no window finite in both modes: no evidence, stays pending (the next call probes)
     n.guard_dlogp = (float)std::min(first, 1e30); n.guard_slots = compared;
     n.guard_dlogp_chosen = chosen == eff ? n.guard_dlogp : (chosen == ISS_PREC_F32 ? 0.f : (float)worst);
     if (chosen != eff) { n.prec_override = chosen; n.guard_state = ISS_GUARD_ESCALATED; }
@@ -2394,9 +2411,7 @@ extern "C" int iss_cnn_forward(iss_ctx* c, int id, const float* x, int32_t nsamp
         return iss_fail(c, ISS_EINVAL, "iss_cnn_forward: bad argument");
     IssNet& n = c->nets[id];
     if (!n.loaded) return iss_fail(c, ISS_ESTATE, "iss_cnn_forward: net %d not loaded", id);
-    for (int r = 0; r < n.nrows; ++r)
-        if (n.prog[(size_t)r * ISS_PROG_COLS + ISS_C_OP] == ISS_OP_CONV && n.prog[(size_t)r * ISS_PROG_COLS + ISS_C_INMODE] == 1)
-            return iss_fail(c, ISS_EINVAL, "iss_cnn_forward: net %d reads mspec patches; use iss_cnn_probs", id);
+    if (net_reads_patches(n)) return iss_fail(c, ISS_EINVAL, "iss_cnn_forward: net %d reads mspec patches; use iss_cnn_probs", id);
     if (nsamp == 0) return ISS_OK;
     ISS_HIP(c, hipSetDevice(c->device));
     const size_t in_elems = (size_t)n.in_h * n.in_w * n.in_c;

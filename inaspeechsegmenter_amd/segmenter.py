@@ -128,6 +128,12 @@ def locate_model(model_fname):
         "construct Segmenter(..., models='synthetic') for seeded stand-in weights.")
 
 
+def _guard_on(ctx):
+    """Is the library's precision guard probing on this context?  (guard_threshold None: the library default, 5e-4, on.)"""
+    thr = getattr(ctx, 'guard_threshold', None)
+    return thr is None or thr > 0
+
+
 class DnnSegmenter:
     """Mirror of segmenter.py:111-179.  Child classes define outlabels / model_fname / inlabel /
     nmel / viterbi_arg exactly as the reference does (:182-204)."""
@@ -174,9 +180,13 @@ class DnnSegmenter:
                 if st['mode'] is None:
                     out = run()
                     info = ctx.cnn_precision_info(self.net_id)
-                    # 'pending' after a call = guard off: nothing to agree on
-                    st['mode'] = -1 if info['state'] == 'pending' else self._MODES[info['mode']]
-                    st['told'].add(id(ctx))
+                    if info['state'] != 'pending':
+                        st['mode'] = self._MODES[info['mode']]
+                        st['told'].add(id(ctx))
+                    elif not _guard_on(ctx):
+                        st['mode'] = -1                        # guard off: nothing to agree on
+                    # (else the guard is on but compared no window -- e.g. all over -inf mel rows --: the decision stays open,
+                    # the next call anywhere probes and decides for every context, this one included)
                     return out
         if st['mode'] >= 0 and id(ctx) not in st['told']:
             with st['lock']:

@@ -189,9 +189,13 @@ int iss_cnn_forward(iss_ctx* ctx, int net_id, const float* x, int32_t n, float* 
  *   ISS_PREC_F16X3   (default since round 6) fp16 halves, 11 + 11 mantissa bits, v_mfma_f32_32x32x16_f16, in the kernels that carry the
  *                    segmenter nets' arithmetic (conv_x3_wq_kernel, conv_x3_wq3h_kernel, conv_x3_pw_kernel); exact f32 for their
  *                    small trailing layers; bf16 halves in every kernel without an fp16 instantiation.  Needs parameters and
- *                    activations inside fp16's range (|x| < 65504): parameters are checked at load (a network with a larger one
- *                    runs ISS_PREC_BF16X3), activations by the precision guard's probe.  max |d log p| against exact f32 on the
- *                    stand-ins: 4.7e-5 (profiles/r06_f16_ab.txt), the speed of ISS_PREC_BF16X3 within 1 %;
+ *                    activations inside fp16's range (|x| < 65504; beyond it a result is NaN).  Parameters are checked at load, and
+ *                    activations can only be checked by the precision guard's probe, which runs on iss_cnn_probs /
+ *                    iss_cnn_probs_async: so fp16 halves are taken by PATCH networks with every parameter in range, run through
+ *                    those two calls, and by nothing else.  A network with a larger parameter, and every network run through
+ *                    iss_cnn_forward or iss_vbx_embed (the x-vector ResNet among them), runs ISS_PREC_BF16X3 in this mode, and
+ *                    iss_cnn_precision_info reports that.  max |d log p| against exact f32 on the stand-ins: 4.7e-5
+ *                    (profiles/r06_f16_ab.txt), the speed of ISS_PREC_BF16X3 within 1 %;
  *   ISS_PREC_BF16X3  bf16 halves, 8 + 8 mantissa bits, v_mfma_f32_32x32x16_bf16, in every GEMM kernel: operand error 2^-16 relative,
  *                    max |d log p| 2.9e-4 on the same data (the default of rounds 1-5);
  *   ISS_PREC_F32     v_mfma_f32_32x32x2_f32, bit-wise an fmaf chain (reference-grade, ~3 x slower).                          */
@@ -207,10 +211,12 @@ int iss_set_precision(iss_ctx* ctx, int mode);
  * (four runs of consecutive slots spread over the list) in that mode and in exact f32, records max |log p_split - log p_f32| over
  * every class of every finite window, and -- when that exceeds `threshold` (default 5e-4, half the bound; a NaN, i.e. an activation
  * beyond fp16's range, always does) -- switches THIS network for the rest of its life: to the other split mode if that one passes
- * the same probe (the same speed), else to ISS_PREC_F32.
+ * the same probe (the same speed), else to ISS_PREC_F32.  A call none of whose probed windows is finite (e.g. all over -inf mel rows)
+ * gives the probe nothing to compare: the network stays ISS_GUARD_PENDING (0 windows compared) and its next call probes again.
  * iss_set_precision_guard: threshold <= 0 disables the probe (networks loaded later are not probed; already decided ones keep their mode).
- * iss_cnn_precision_info: mode in use for the network (ISS_PREC_*), the probe's figure for the mode that was asked for (-1 if not
- * probed), the windows it compared, ISS_GUARD_* state, and the figure of the mode in use (0 for exact f32).
+ * iss_cnn_precision_info: mode in use for the network (ISS_PREC_*, the one it actually runs: see ISS_PREC_F16X3), the probe's figure
+ * for the mode that was asked for (-1 if not probed), the windows it compared, ISS_GUARD_* state, and the figure of the mode in use
+ * (0 for exact f32).
  * iss_cnn_set_net_precision: caller's override for one network (-1 = follow the context again); marks it decided. */
 #define ISS_GUARD_PENDING   0   /* not probed yet                                              */
 #define ISS_GUARD_PASSED    1   /* probed: within the threshold, mode kept                     */

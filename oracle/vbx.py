@@ -147,19 +147,21 @@ def resnet101_random_params(seed=0):
     return params
 
 
-def resnet101_forward(params, fea_bft, eps=1e-5):
-    """fea_bft: (B, 64, T) float32 (feature-major, vbx_segmenter.py:265) -> (B,256).
-    torch-CPU functional restatement of resnet.py:115-130."""
+def resnet101_forward(params, fea_bft, eps=1e-5, dtype=np.float32, pooled=False):
+    """fea_bft: (B, 64, T) float32 (feature-major, vbx_segmenter.py:265) -> (B,256) of `dtype`.
+    torch-CPU functional restatement of resnet.py:115-130; dtype=np.float64 runs the same graph in double (the
+    high-precision reference the x-vector tests measure the device against).  pooled=True: the (B, 16384) statistics
+    vector the embedding layer reads instead of the embedding."""
     import torch
     import torch.nn.functional as F
-    P = {k: torch.from_numpy(np.asarray(v)) for k, v in params.items()}
+    P = {k: torch.from_numpy(np.asarray(v, dtype=dtype)) for k, v in params.items()}
 
     def bn(x, p):
         return F.batch_norm(x, P[p + '.running_mean'], P[p + '.running_var'], P[p + '.weight'], P[p + '.bias'],
                             False, 0.0, eps)
 
     with torch.no_grad():
-        x = torch.from_numpy(np.ascontiguousarray(fea_bft, dtype=np.float32)).unsqueeze(1)
+        x = torch.from_numpy(np.ascontiguousarray(fea_bft, dtype=dtype)).unsqueeze(1)
         out = F.relu(bn(F.conv2d(x, P['conv1.weight'], padding=1), 'bn1'))
         in_planes = 32
         for li, (planes, nblocks, stride) in enumerate(zip((32, 64, 128, 256), (3, 4, 23, 3), (1, 2, 2, 2)), 1):
@@ -178,4 +180,6 @@ def resnet101_forward(params, fea_bft, eps=1e-5):
         meansq = torch.mean(out * out, dim=-1)
         std = torch.sqrt(meansq - mean ** 2 + 1e-10)
         v = torch.cat((torch.flatten(mean, start_dim=1), torch.flatten(std, start_dim=1)), 1)
+        if pooled:
+            return v.numpy()
         return F.linear(v, P['embedding.weight'], P['embedding.bias']).numpy()

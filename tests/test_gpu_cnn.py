@@ -610,3 +610,36 @@ def test_first_dense_layer_wider_than_one_column_tile(ctx, prec, width):
             if prec == 'bf16x3':
                 assert any(k.startswith('conv_x3_pw_kernel') for k in used_f32), (width, T, sorted(used_f32))
                 assert np.array_equal(p_new, p_f32), (width, T, np.abs(p_new - p_f32).max())
+
+
+def test_precision_guard_decides_nothing_without_evidence(ctx):
+    """The probe compares windows that are finite in both modes.  A first call whose windows all cover -inf mel rows (a file that
+    starts in digital silence) gives it none: the network must stay 'pending' with 0 windows compared -- not 'passed' on a
+    figure of 0 -- and the next call, on finite windows, probes and decides."""
+    rng = np.random.default_rng(31)
+    T = 900
+    mspec = _mspec(rng, T)
+    mspec[:200] = -np.inf
+    ctx.set_mspec(mspec)
+    rows = S._window_rows(T)
+    blind, live = rows[rows < 200], rows[rows >= 200]
+    layers, shp = KM.synthetic_ina_like(21, 3, seed=1)
+    ctx.set_precision(_native.PREC_F16X3)                                # the library default
+    ctx.set_precision_guard(5e-4)
+    try:
+        ctx.cnn_load(3, KM.compile_layers(layers, shp))
+        p0, f0 = ctx.cnn_probs(3, blind)
+        info0 = ctx.cnn_precision_info(3)
+        print('no finite window:', info0)
+        assert not f0.any() and np.all(p0 == 0.5)
+        assert info0['state'] == 'pending' and info0['slots'] == 0 and info0['max_dlogp'] is None, info0
+        p1, f1 = ctx.cnn_probs(3, live)
+        info1 = ctx.cnn_precision_info(3)
+        print('finite windows:', info1)
+        assert f1.all()
+        assert info1['state'] in ('passed', 'escalated') and info1['slots'] > 100 and info1['max_dlogp'] >= 0, info1
+        ref, rfin = _oracle_probs(layers, mspec, 21, live)
+        assert rfin.all() and np.abs(p1 - ref).max() < 1e-4, np.abs(p1 - ref).max()
+    finally:
+        ctx.set_precision_guard(0)
+        ctx.set_precision(_native.PREC_BF16X3)

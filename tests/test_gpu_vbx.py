@@ -10,10 +10,40 @@ import pytest
 
 from inaspeechsegmenter_amd import vbx as V, keras_model as KM
 from oracle import vbx as ovbx
-from conftest import GOLDEN
+from conftest import GOLDEN, synth_pcm
 
 pytestmark = pytest.mark.gpu
 FEA_TOL = 2e-5
+
+
+def _fresh_context():
+    """A device context with the library's defaults (ISS_PREC_F16X3, 24 GiB workspace, guard on) and the front-end tables
+    loaded the way conftest.ctx loads them -- not the shared context, which runs split bf16 under a smaller workspace limit."""
+    from inaspeechsegmenter_amd import _native, tables
+    c = _native.Context(0)
+    c.sidekit_tables(tables.sidekit_window(), tables.sidekit_melbank())
+    c.vbx_tables(tables.vbx_window(), tables.vbx_melbank())
+    return c
+
+
+def _f16_instance(name):
+    """Kernel instantiations that take fp16 operand halves (their F16 template argument true)."""
+    return (name == 'conv_x3_pw_kernel<true>' or name.startswith('conv_dhl_kernel<true,') or
+            (name.startswith(('conv_x3_wq_kernel<', 'conv_x3_wq3h_kernel<')) and name.endswith(',true>')))
+
+
+def _launches(c, run):
+    c.prof_enable(True)
+    c.prof_reset()
+    try:
+        out = run()
+        return out, {e['kernel']: e['launches'] for e in c.prof_instances()}
+    finally:
+        c.prof_enable(False)
+
+
+def _oracle64(params, fea, a, b):
+    return ovbx.resnet101_forward(params, fea[a:b].T[None], dtype=np.float64)[0]
 
 
 @pytest.fixture(scope='module')
@@ -209,3 +239,113 @@ def test_final_onnx_file_through_the_product_loader(ctx, tmp_path, monkeypatch):
     got = ex.get_embeddings(fea, starts, 144)
     want = ovbx.resnet101_forward(params, np.stack([fea[s:s + 144].T for s in starts]))
     assert np.abs(got - want).max() <= 1e-4 * max(1.0, np.abs(want).max())
+
+
+def test_vbx_one_hour_production_passes():
+    """1 h of audio through the product's x-vector path (FeatureExtractor -> VBxExtractor: resident features, iss_vbx_embed) on a
+    context with the library's defaults.  plan_chunk sizes the passes from the 24 GiB workspace and the 2^31-float cap on the
+    largest activation buffer (1 179 648 floats per window): floor((2^31 - 1) / 1 179 648) = 1820, down to a multiple of 8 = 1816
+    windows per pass, 9 passes for the 14 994 full windows; that buffer then holds 2 142 240 768 floats (8.6 GB, byte offsets far
+    beyond 2^32), where the 8-window tests above stay below 10^7.  Checked: the window list, no window dropped for NaN, the pass
+    count, no fp16-halves launch (the x-vector net runs bf16 halves under ISS_PREC_F16X3: no probe can see its activations), the
+    x-vectors of the first and last window of every pass, 20 seeded random windows and the last window (a separate call after the
+    hop loop; at exactly 360 000 frames it spans the last 144 of them) against the float64 oracle
+    at 1e-4 of the embedding scale (measured 1e-5), and pass-size independence: the same windows in 256-window passes give
+    bit-identical x-vectors (every pass size launches the same kernel instances, and no kernel's arithmetic per window depends
+    on how many windows share its launch)."""
+    c = _fresh_context()
+    try:
+        params = KM.synthetic_resnet101(0)
+        n = 3600 * 16000
+        fe = V.FeatureExtractor(c)
+        fea = fe(synth_pcm(11, n))                                    # host copy; the features also stay resident
+        T = len(fea)
+        wins = ovbx.window_list(T)
+        full = list(range(0, T - V.WINLEN, V.STEP))                   # the hop loop; then the last window (:234-243)
+        assert len(full) == 14994 and len(wins) == len(full) + 1 and wins[:-1] == [(s, s + V.WINLEN) for s in full], (T, wins[-1])
+        ex = V.VBxExtractor(c, params)
+        _, small = _launches(c, lambda: ex.get_embeddings(fea, full[:8], V.WINLEN))
+        emb, big = _launches(c, lambda: ex.get_embeddings(fea, full, V.WINLEN))
+        per = sum(KM.compile_resnet101(params, V.FEAT_DIM, V.WINLEN, window_input=True).buf_elems)
+        emax = max(KM.compile_resnet101(params, V.FEAT_DIM, V.WINLEN, window_input=True).buf_elems)
+        bc = min((24 << 30) // (per * 4), ((1 << 31) - 1) // emax)
+        bc -= bc % 8
+        passes = -(-len(full) // bc)
+        print(f'{len(full)} full windows, {bc} per pass, {passes} passes; largest buffer {bc * emax} floats')
+        print('8-window call:', sorted(small))
+        print('production passes:', sorted(big))
+        print('only at production size:', sorted(set(big) - set(small)), ' only at 8 windows:', sorted(set(small) - set(big)))
+        assert bc == 1816 and passes == 9
+        dual = sum(v for k, v in big.items() if 'dual' in k)
+        assert dual == 4 * passes, big
+        assert not [k for k in big if _f16_instance(k)] and not [k for k in small if _f16_instance(k)], big
+        assert c.cnn_precision_info(ex._net_for(V.WINLEN, window=True))['mode'] == 'bf16x3'
+
+        got = ex('utt', fea, n / 16000.0)                              # the product's call: keys, NaN filter, tail window
+        assert [k for k, _, _ in got] == [f'utt_{a:08}-{b:08}' for a, b in wins]
+        assert np.array_equal(np.stack([x for _, _, x in got[:len(full)]]), emb * 10)
+
+        rng = np.random.default_rng(2024)
+        edges = sorted({i for p in range(passes) for i in (p * bc, min(p * bc + bc, len(full)) - 1)})
+        sample = sorted(set(edges) | set(rng.choice(len(full), 20, replace=False).tolist()))
+        ref = np.stack([_oracle64(params, fea, full[i], full[i] + V.WINLEN) for i in sample])
+        a, b = wins[-1]
+        ref_tail = _oracle64(params, fea, a, b)
+        scale = max(np.abs(ref).max(), np.abs(ref_tail).max())
+        err = np.abs(emb[sample] - ref).max()
+        err_tail = np.abs(got[-1][2] / 10 - ref_tail).max()
+        print(f'{len(sample)} windows at 1816-window passes vs float64: max abs err {err:.3e} = {err / scale:.2e} of the scale '
+              f'{scale:.2f}; last window ({b - a} frames) {err_tail / scale:.2e}')
+        assert err <= 1e-4 * scale and err_tail <= 1e-4 * scale
+
+        c.set_workspace_limit(256 * per * 4)                          # ~256-window passes on the same context
+        emb2, mid = _launches(c, lambda: ex.get_embeddings(fea, full, V.WINLEN))
+        assert sum(v for k, v in mid.items() if 'dual' in k) == 4 * -(-len(full) // 256), mid
+        d = np.abs(emb2 - emb).max()
+        print(f'256- vs 1816-window passes: max abs diff {d:.3e} = {d / scale:.2e} of the scale, '
+              f'{np.mean(emb2 == emb) * 100:.2f} % bit-identical')
+        assert np.array_equal(emb2, emb)
+    finally:
+        c.close()
+
+
+def test_default_precision_survives_activations_beyond_fp16_range():
+    """Under the library's default ISS_PREC_F16X3, a network whose statistics-pooling output (the embedding layer's input) leaves
+    fp16's range -- layer4's last BatchNorm scaled 2048 x: up to ~1.8e5 here, above 65 504 in every window -- while every
+    parameter stays inside it (so the net is not excluded at load).  fp16 operand halves would turn those activations into inf and
+    the x-vectors into NaN, which VBxExtractor drops; no probe covers iss_cnn_forward / iss_vbx_embed.  Both entry points must give
+    finite x-vectors within 1e-4 of the float64 oracle's scale, drop no window, and report the arithmetic they ran (bf16x3)."""
+    params = KM.synthetic_resnet101(0)
+    for k in ('layer4.2.bn3.weight', 'layer4.2.bn3.bias'):
+        params[k] = params[k] * np.float32(2048)
+    for frames, window in ((V.WINLEN, False), (V.WINLEN, True)):
+        blob = KM.compile_resnet101(params, V.FEAT_DIM, frames, window_input=window).blob
+        assert np.abs(blob).max() < 65504, np.abs(blob).max()          # still f16_ok: the net reaches the fp16 path
+    c = _fresh_context()
+    try:
+        pcm = synth_pcm(3, 16000 * 8)
+        fea = V.FeatureExtractor(c)(pcm)
+        starts = list(range(0, len(fea) - V.WINLEN, V.STEP))
+        x = np.stack([fea[s:s + V.WINLEN].T for s in starts])
+        pooled = ovbx.resnet101_forward(params, x, dtype=np.float64, pooled=True)
+        ref = ovbx.resnet101_forward(params, x, dtype=np.float64)
+        scale = np.abs(ref).max()
+        print(f'embedding input: max {np.abs(pooled).max():.4g}, windows with a value beyond 65504: '
+              f'{int((np.abs(pooled) > 65504).any(axis=1).sum())} / {len(starts)}')
+        assert np.abs(pooled).max() > 2 * 65504 and (np.abs(pooled) > 65504).any(axis=1).all()
+        ex = V.VBxExtractor(c, params)
+        host, inst_h = _launches(c, lambda: ex.get_embeddings(fea.copy(), starts, V.WINLEN))      # iss_cnn_forward
+        dev, inst_d = _launches(c, lambda: ex.get_embeddings(fea, starts, V.WINLEN))              # iss_vbx_embed
+        for name, emb, inst in (('iss_cnn_forward', host, inst_h), ('iss_vbx_embed', dev, inst_d)):
+            f16 = sorted(k for k in inst if _f16_instance(k))
+            bad = int((~np.isfinite(emb)).any(axis=1).sum())
+            err = np.abs(emb - ref).max() if not bad else float('nan')
+            print(f'{name}: {bad} / {len(starts)} windows not finite, max abs err {err:.3e} = {err / scale:.2e} of the scale '
+                  f'{scale:.4g}; fp16-halves instances {f16}')
+            assert bad == 0 and err <= 1e-4 * scale, name
+        got = ex('utt', fea, len(pcm) / 16000.0)
+        assert len(got) == len(ovbx.window_list(len(fea)))
+        for window in (False, True):
+            assert c.cnn_precision_info(ex._net_for(V.WINLEN, window=window))['mode'] == 'bf16x3'
+    finally:
+        c.close()

@@ -784,17 +784,22 @@ def test_every_diag_switch_of_the_abi_has_its_python_name():
 def test_one_arithmetic_decision_per_network_across_device_contexts():
     """The precision guard (include/iss.h) decides a network's arithmetic at its first call PER CONTEXT; `DnnSegmenter.probs`
     makes the first call anywhere decide for every device context of the Segmenter (its own and the pipeline workers'): later
-    contexts are told the outcome before their first call and are never probed; with the guard off nothing is touched."""
+    contexts are told the outcome before their first call and are never probed; with the guard off nothing is touched; a first
+    call that gave the probe no finite window to compare leaves the decision open, and the next call anywhere decides for all."""
     from inaspeechsegmenter_amd import segmenter as S
 
     class Ctx:
-        def __init__(self, outcome):
+        def __init__(self, outcome, blind_calls=0, guard_threshold=None):
             self.outcome, self.state, self.mode, self.calls, self.told = outcome, 'pending', 'f16x3', 0, []
+            self.blind_calls, self.guard_threshold = blind_calls, guard_threshold
 
         def cnn_probs(self, net_id, rows):
             self.calls += 1
             if self.state == 'pending' and self.outcome is not None:
-                self.state, self.mode = self.outcome
+                if self.blind_calls:                     # no window finite in both modes: the library leaves the net pending
+                    self.blind_calls -= 1
+                else:
+                    self.state, self.mode = self.outcome
             return np.zeros((len(rows), 2), np.float32), np.ones(len(rows), np.uint8)
 
         def cnn_precision_info(self, net_id):
@@ -812,6 +817,20 @@ def test_one_arithmetic_decision_per_network_across_device_contexts():
     assert a.told == [] and b.told == [_native.PREC_BF16X3] and c.told == [_native.PREC_BF16X3]
     assert (a.mode, b.mode, c.mode) == ('bf16x3', 'bf16x3', 'bf16x3') and (a.calls, b.calls, c.calls) == (2, 2, 1)
     off = S.DnnSegmenter.__new__(S.Gender)               # guard off: the state stays 'pending', nobody is told anything
-    d, e = Ctx(None), Ctx(None)
+    d, e = Ctx(None, guard_threshold=0.0), Ctx(None, guard_threshold=0.0)
     off.probs(d, rows); off.probs(e, rows); off.probs(d, rows)
     assert d.told == [] and e.told == [] and d.calls == 2 and e.calls == 1
+    # the guard on, but the first call's windows all over -inf mel rows: 'pending' is no decision; the second call (on another
+    # context) probes and decides, and the first context is told that outcome before its next call
+    late = S.DnnSegmenter.__new__(S.Gender)
+    f, g, h = Ctx(('escalated', 'bf16x3'), blind_calls=1), Ctx(('passed', 'f16x3')), Ctx(('escalated', 'f32'))
+    late.probs(f, rows)
+    assert f.state == 'pending' and late._mode_state['mode'] is None and f.told == []
+    late.probs(g, rows); late.probs(f, rows); late.probs(h, rows); late.probs(g, rows)
+    assert g.told == [] and f.told == [_native.PREC_F16X3] and h.told == [_native.PREC_F16X3]
+    assert (f.mode, g.mode, h.mode) == ('f16x3', 'f16x3', 'f16x3') and (f.calls, g.calls, h.calls) == (2, 2, 1)
+    # ... or on the same context: its own second call probes, and the other contexts are told
+    again = S.DnnSegmenter.__new__(S.Gender)
+    k, m = Ctx(('escalated', 'f32'), blind_calls=1), Ctx(('passed', 'f16x3'))
+    again.probs(k, rows); again.probs(k, rows); again.probs(m, rows)
+    assert k.told == [] and k.state == 'escalated' and m.told == [_native.PREC_F32] and m.mode == 'f32'
