@@ -77,6 +77,7 @@ def lib():
         'iss_get_mspec': (C.c_int, [vp, pf]),
         'iss_set_mspec': (C.c_int, [vp, pf, i32]),
         'iss_cnn_load': (C.c_int, [vp, C.c_int, pi32, i32, pf, i64, i32, pi64, i32, i32, i32, i32]),
+        'iss_cnn_load_shared': (C.c_int, [vp, C.c_int, C.c_int, pi32, i32, i32, pi64, i32, i32, i32, i32]),
         'iss_cnn_probs': (C.c_int, [vp, C.c_int, pi32, i32, pf, pu8]),
         'iss_cnn_forward': (C.c_int, [vp, C.c_int, pf, i32, pf]),
         'iss_cnn_flops': (C.c_int, [vp, C.c_int, pd]),
@@ -88,6 +89,7 @@ def lib():
         'iss_vbx_features': (C.c_int, [vp, pi32, pd, i64, pf, pi32]),
         'iss_vbx_set_dither': (C.c_int, [vp, pd, i64]),
         'iss_vbx_features_pcm16': (C.c_int, [vp, pi16, i64, pf, pi32]),
+        'iss_vbx_features_batch_pcm16': (C.c_int, [vp, pi16, pi64, i32, pi32, pf]),
         'iss_vbx_embed': (C.c_int, [vp, C.c_int, pi32, i32, pf]),
         'iss_prof_enable': (C.c_int, [vp, C.c_int]),
         'iss_prof_get': (C.c_int, [vp, C.c_int, pd, pi64, pd]),
@@ -301,6 +303,16 @@ class Context:
                  'iss_cnn_load')
         self._net_out[net_id] = compiled.out_dim
 
+    def cnn_load_shared(self, net_id, src_id, compiled):
+        """Load `compiled` (keras_model.CompiledNet) on the device parameters of net `src_id`: its blob must be byte-identical
+        to the one src_id was loaded with -- the caller's check, the blob is not sent (include/iss.h)."""
+        prog = np.ascontiguousarray(compiled.prog, dtype=np.int32)
+        be = np.ascontiguousarray(compiled.buf_elems, dtype=np.int64)
+        h, w, c = compiled.in_shape
+        self._ck(self._L.iss_cnn_load_shared(self._h, net_id, src_id, _ptr(prog, C.c_int32), prog.shape[0], be.size,
+                                             _ptr(be, C.c_int64), h, w, c, compiled.out_dim), 'iss_cnn_load_shared')
+        self._net_out[net_id] = compiled.out_dim
+
     def cnn_probs(self, net_id, win_row):
         wr = np.ascontiguousarray(win_row, dtype=np.int32)
         n = wr.size
@@ -472,6 +484,22 @@ class Context:
                  'iss_vbx_features_pcm16')
         assert t.value == T
         return out
+
+    def vbx_features_batch_pcm16(self, pcms, to_host=True):
+        """Many PCM16 files in one call (iss_vbx_features_batch_pcm16; the cached dither stream must cover the longest).
+        -> (frame_off, fea): frame_off = (F + 1,) int32 first arena row of every file, fea = the (frame_off[-1], 64) float32
+        arena, or None with to_host=False (it stays resident for vbx_embed, whose window starts are then arena rows)."""
+        pcms = [np.asarray(p, dtype=np.int16) for p in pcms]
+        soff = np.zeros(len(pcms) + 1, dtype=np.int64)
+        soff[1:] = np.cumsum([p.size for p in pcms])
+        s = np.ascontiguousarray(np.concatenate(pcms) if pcms else np.zeros(0, np.int16))
+        foff = np.zeros(len(pcms) + 1, dtype=np.int32)
+        T = int(sum((p.size + 320 - 400) // 160 + 1 for p in pcms))
+        out = np.empty((T, 64), dtype=np.float32) if to_host else None
+        self._ck(self._L.iss_vbx_features_batch_pcm16(self._h, _ptr(s, C.c_int16), _ptr(soff, C.c_int64), len(pcms),
+                                                      _ptr(foff, C.c_int32), _ptr(out, C.c_float) if to_host else None),
+                 'iss_vbx_features_batch_pcm16')
+        return foff, out
 
     def vbx_embed(self, net_id, starts):
         st = np.ascontiguousarray(starts, dtype=np.int32)

@@ -1046,39 +1046,43 @@ inline void fused_pool_of(const int32_t* R, int& ph, int& pw) {
 }  // namespace
 
 // ============================================================================ host side
+IssParamArrays::~IssParamArrays() {
+    for (void* p : {(void*)blob, (void*)wh, (void*)wl, (void*)wh16, (void*)wl16}) if (p) (void)hipFree(p);
+}
+
 int iss_cnn_free(iss_ctx* c, int id) {
     if (!c || id < 0 || id >= ISS_MAX_NETS) return ISS_EINVAL;
     IssNet& n = c->nets[id];
-    if (n.d_blob) (void)hipFree(n.d_blob);
-    if (n.d_wh) (void)hipFree(n.d_wh);
-    if (n.d_wl) (void)hipFree(n.d_wl);
+    if (n.shared_params) {
+        n.shared_params.reset();           // shared with another net (iss_cnn_load_shared): freed with the last of them
+    } else {
+        if (n.d_blob) (void)hipFree(n.d_blob);
+        if (n.d_wh) (void)hipFree(n.d_wh);
+        if (n.d_wl) (void)hipFree(n.d_wl);
+        if (n.d_wh16) (void)hipFree(n.d_wh16);
+        if (n.d_wl16) (void)hipFree(n.d_wl16);
+    }
     for (auto& kv : n.dhl_wp) if (kv.second) (void)hipFree(kv.second);
-    if (n.d_wh16) (void)hipFree(n.d_wh16);
-    if (n.d_wl16) (void)hipFree(n.d_wl16);
     if (n.d_wsum) (void)hipFree(n.d_wsum);
     if (n.d_ktab) (void)hipFree(n.d_ktab);
     n = IssNet();
     return ISS_OK;
 }
 
-extern "C" int iss_cnn_load(iss_ctx* c, int id, const int32_t* prog, int32_t nrows, const float* blob,
-                            int64_t blob_floats, int32_t nbuf, const int64_t* buf_elems, int32_t in_h, int32_t in_w,
-                            int32_t in_c, int32_t out_dim) {
-    if (!c) return ISS_EINVAL;
-    if (id < 0 || id >= ISS_MAX_NETS || !prog || nrows <= 0 || !blob || blob_floats <= 0 || nbuf <= 0 || !buf_elems)
-        return iss_fail(c, ISS_EINVAL, "iss_cnn_load: bad argument");
-    ISS_HIP(c, hipSetDevice(c->device));
-    iss_cnn_free(c, id);
-    IssNet& n = c->nets[id];
+namespace {
+// The op program of a load (iss_cnn_load / iss_cnn_load_shared): rows validated against a blob of blob_floats floats, the
+// im2col tables built into ktab.
+int cnn_set_program(iss_ctx* c, IssNet& n, const char* who, const int32_t* prog, int32_t nrows, int64_t blob_floats,
+                    int32_t nbuf, const int64_t* buf_elems, int32_t in_h, int32_t in_w, int32_t in_c, int32_t out_dim,
+                    std::vector<int32_t>& ktab) {
     n.prog.assign(prog, prog + (size_t)nrows * ISS_PROG_COLS);
     n.nrows = nrows; n.nbuf = nbuf; n.buf_elems.assign(buf_elems, buf_elems + nbuf);
     n.in_h = in_h; n.in_w = in_w; n.in_c = in_c; n.out_dim = out_dim;
     n.kpad.assign(nrows, 0); n.ktab_off.assign(nrows, -1);
-    std::vector<int32_t> ktab;
     double flops = 0;
     for (int r = 0; r < nrows; ++r) {
         const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
-        auto bad = [&](const char* what) { return iss_fail(c, ISS_EINVAL, "iss_cnn_load: row %d: %s", r, what); };
+        auto bad = [&](const char* what) { return iss_fail(c, ISS_EINVAL, "%s: row %d: %s", who, r, what); };
         if (R[ISS_C_IN] != ISS_BUF_INPUT && (R[ISS_C_IN] < 0 || R[ISS_C_IN] >= nbuf)) return bad("IN buffer id");
         if (R[ISS_C_OUT] < 0 || R[ISS_C_OUT] >= nbuf) return bad("OUT buffer id");
         if (R[ISS_C_OP] == ISS_OP_CONV) {
@@ -1169,6 +1173,76 @@ extern "C" int iss_cnn_load(iss_ctx* c, int id, const int32_t* prog, int32_t nro
         }
     }
     n.flops_per_sample = flops; n.blob_floats = blob_floats;
+    return ISS_OK;
+}
+
+// Per-program device tables of a load whose parameters are already on the device (n.d_blob): the weight sums of the
+// patch-mode first layers (from the host blob when there is one, else from the device copy) and the im2col tables.
+int cnn_upload_tables(iss_ctx* c, IssNet& n, const float* blob, const std::vector<int32_t>& ktab) {
+    const int nrows = n.nrows;
+    {   // per-channel weight sums of the patch-mode first layers (ConvArgs::f_wsum)
+        std::vector<float> wsum;
+        n.wsum_off.assign(nrows, -1);
+        n.wsumx_off.assign(nrows, -1);
+        std::vector<float> wdev;
+        for (int r = 0; r < nrows; ++r) {
+            const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
+            if (R[ISS_C_OP] != ISS_OP_CONV || R[ISS_C_INMODE] != 1) continue;
+            const int K = R[ISS_C_KH] * R[ISS_C_KW] * R[ISS_C_CIN];
+            const float* w = blob ? blob + R[ISS_C_WOFF] : nullptr;     // this row's [Cout][Kpad] weights
+            if (!w) {
+                wdev.resize((size_t)R[ISS_C_COUT] * n.kpad[r]);
+                ISS_HIP(c, hipMemcpy(wdev.data(), n.d_blob + R[ISS_C_WOFF], wdev.size() * sizeof(float), hipMemcpyDeviceToHost));
+                w = wdev.data();
+            }
+            n.wsum_off[r] = (int64_t)wsum.size();
+            for (int co = 0; co < R[ISS_C_COUT]; ++co) {
+                double acc = 0.0;
+                for (int k = 0; k < K; ++k) acc += (double)w[(int64_t)co * n.kpad[r] + k];
+                wsum.push_back((float)acc);
+            }
+            while (wsum.size() % 8) wsum.push_back(0.f);         // float4-aligned rows
+            // zero-padded first layer: S[x][co] = sum over all filter rows and the filter columns that see data at column x
+            // (conv_x3_ws_kernel<..., FS>, first_layer_edge_kernel)
+            if ((R[ISS_C_PT] != 0 || R[ISS_C_PL] != 0 || R[ISS_C_WO] == R[ISS_C_W]) && R[ISS_C_CIN] == 1 && R[ISS_C_SW] == 1) {
+                n.wsumx_off[r] = (int64_t)wsum.size();
+                const int W = R[ISS_C_W], kh = R[ISS_C_KH], kw = R[ISS_C_KW], pl = R[ISS_C_PL];
+                for (int x = 0; x < W; ++x)
+                    for (int co = 0; co < R[ISS_C_COUT]; ++co) {
+                        double acc = 0.0;
+                        for (int ky = 0; ky < kh; ++ky)
+                            for (int kx = 0; kx < kw; ++kx)
+                                if (x - pl + kx >= 0 && x - pl + kx < W) acc += (double)w[(int64_t)co * n.kpad[r] + ky * kw + kx];
+                        wsum.push_back((float)acc);
+                    }
+                while (wsum.size() % 8) wsum.push_back(0.f);
+            }
+        }
+        if (!wsum.empty()) {
+            ISS_HIP(c, hipMalloc((void**)&n.d_wsum, wsum.size() * sizeof(float)));
+            ISS_HIP(c, hipMemcpy(n.d_wsum, wsum.data(), wsum.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+    }
+    if (!ktab.empty()) {
+        ISS_HIP(c, hipMalloc((void**)&n.d_ktab, ktab.size() * sizeof(int32_t)));
+        ISS_HIP(c, hipMemcpy(n.d_ktab, ktab.data(), ktab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    return ISS_OK;
+}
+}  // namespace
+
+extern "C" int iss_cnn_load(iss_ctx* c, int id, const int32_t* prog, int32_t nrows, const float* blob,
+                            int64_t blob_floats, int32_t nbuf, const int64_t* buf_elems, int32_t in_h, int32_t in_w,
+                            int32_t in_c, int32_t out_dim) {
+    if (!c) return ISS_EINVAL;
+    if (id < 0 || id >= ISS_MAX_NETS || !prog || nrows <= 0 || !blob || blob_floats <= 0 || nbuf <= 0 || !buf_elems)
+        return iss_fail(c, ISS_EINVAL, "iss_cnn_load: bad argument");
+    ISS_HIP(c, hipSetDevice(c->device));
+    iss_cnn_free(c, id);
+    IssNet& n = c->nets[id];
+    std::vector<int32_t> ktab;
+    int rc = cnn_set_program(c, n, "iss_cnn_load", prog, nrows, blob_floats, nbuf, buf_elems, in_h, in_w, in_c, out_dim, ktab);
+    if (rc) return rc;
     ISS_HIP(c, hipMalloc((void**)&n.d_blob, (size_t)blob_floats * sizeof(float)));
     ISS_HIP(c, hipMemcpy(n.d_blob, blob, (size_t)blob_floats * sizeof(float), hipMemcpyHostToDevice));
     {   // bf16 hi / lo parts of every parameter, same offsets as the f32 blob (conv_x3_kernel operands)
@@ -1196,46 +1270,34 @@ extern "C" int iss_cnn_load(iss_ctx* c, int id, const int32_t* prog, int32_t nro
         ISS_HIP(c, hipMemcpy(n.d_wh, hi.data(), (size_t)blob_floats * 2, hipMemcpyHostToDevice));
         ISS_HIP(c, hipMemcpy(n.d_wl, lo.data(), (size_t)blob_floats * 2, hipMemcpyHostToDevice));
     }
-    {   // per-channel weight sums of the patch-mode first layers (ConvArgs::f_wsum)
-        std::vector<float> wsum;
-        n.wsum_off.assign(nrows, -1);
-        n.wsumx_off.assign(nrows, -1);
-        for (int r = 0; r < nrows; ++r) {
-            const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
-            if (R[ISS_C_OP] != ISS_OP_CONV || R[ISS_C_INMODE] != 1) continue;
-            const int K = R[ISS_C_KH] * R[ISS_C_KW] * R[ISS_C_CIN];
-            n.wsum_off[r] = (int64_t)wsum.size();
-            for (int co = 0; co < R[ISS_C_COUT]; ++co) {
-                double acc = 0.0;
-                for (int k = 0; k < K; ++k) acc += (double)blob[R[ISS_C_WOFF] + (int64_t)co * n.kpad[r] + k];
-                wsum.push_back((float)acc);
-            }
-            while (wsum.size() % 8) wsum.push_back(0.f);         // float4-aligned rows
-            // zero-padded first layer: S[x][co] = sum over all filter rows and the filter columns that see data at column x
-            // (conv_x3_ws_kernel<..., FS>, first_layer_edge_kernel)
-            if ((R[ISS_C_PT] != 0 || R[ISS_C_PL] != 0 || R[ISS_C_WO] == R[ISS_C_W]) && R[ISS_C_CIN] == 1 && R[ISS_C_SW] == 1) {
-                n.wsumx_off[r] = (int64_t)wsum.size();
-                const int W = R[ISS_C_W], kh = R[ISS_C_KH], kw = R[ISS_C_KW], pl = R[ISS_C_PL];
-                for (int x = 0; x < W; ++x)
-                    for (int co = 0; co < R[ISS_C_COUT]; ++co) {
-                        double acc = 0.0;
-                        for (int ky = 0; ky < kh; ++ky)
-                            for (int kx = 0; kx < kw; ++kx)
-                                if (x - pl + kx >= 0 && x - pl + kx < W) acc += (double)blob[R[ISS_C_WOFF] + (int64_t)co * n.kpad[r] + ky * kw + kx];
-                        wsum.push_back((float)acc);
-                    }
-                while (wsum.size() % 8) wsum.push_back(0.f);
-            }
-        }
-        if (!wsum.empty()) {
-            ISS_HIP(c, hipMalloc((void**)&n.d_wsum, wsum.size() * sizeof(float)));
-            ISS_HIP(c, hipMemcpy(n.d_wsum, wsum.data(), wsum.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
+    if ((rc = cnn_upload_tables(c, n, blob, ktab))) return rc;
+    n.loaded = true;
+    return ISS_OK;
+}
+
+extern "C" int iss_cnn_load_shared(iss_ctx* c, int id, int src, const int32_t* prog, int32_t nrows, int32_t nbuf,
+                                   const int64_t* buf_elems, int32_t in_h, int32_t in_w, int32_t in_c, int32_t out_dim) {
+    if (!c) return ISS_EINVAL;
+    if (id < 0 || id >= ISS_MAX_NETS || src < 0 || src >= ISS_MAX_NETS || src == id || !prog || nrows <= 0 || nbuf <= 0 || !buf_elems)
+        return iss_fail(c, ISS_EINVAL, "iss_cnn_load_shared: bad argument");
+    if (!c->nets[src].loaded || !c->nets[src].d_blob)
+        return iss_fail(c, ISS_ESTATE, "iss_cnn_load_shared: source net %d not loaded", src);
+    ISS_HIP(c, hipSetDevice(c->device));
+    iss_cnn_free(c, id);                                  // (id != src: the source's arrays stay)
+    IssNet& s = c->nets[src];
+    IssNet& n = c->nets[id];
+    std::vector<int32_t> ktab;
+    int rc = cnn_set_program(c, n, "iss_cnn_load_shared", prog, nrows, s.blob_floats, nbuf, buf_elems, in_h, in_w, in_c, out_dim, ktab);
+    if (rc) return rc;
+    if (!s.shared_params) {                               // first alias: the source's arrays become reference-counted
+        s.shared_params = std::make_shared<IssParamArrays>();
+        IssParamArrays& a = *s.shared_params;
+        a.blob = s.d_blob; a.wh = s.d_wh; a.wl = s.d_wl; a.wh16 = s.d_wh16; a.wl16 = s.d_wl16;
     }
-    if (!ktab.empty()) {
-        ISS_HIP(c, hipMalloc((void**)&n.d_ktab, ktab.size() * sizeof(int32_t)));
-        ISS_HIP(c, hipMemcpy(n.d_ktab, ktab.data(), ktab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
+    n.shared_params = s.shared_params;
+    n.d_blob = s.d_blob; n.d_wh = s.d_wh; n.d_wl = s.d_wl; n.d_wh16 = s.d_wh16; n.d_wl16 = s.d_wl16;
+    n.f16_ok = s.f16_ok;
+    if ((rc = cnn_upload_tables(c, n, nullptr, ktab))) return rc;
     n.loaded = true;
     return ISS_OK;
 }

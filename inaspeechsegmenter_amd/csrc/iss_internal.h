@@ -8,6 +8,7 @@
 #include <vector>
 #include <unordered_map>
 #include <map>
+#include <memory>
 #include "../../include/iss.h"
 
 struct DevBuf {
@@ -16,6 +17,13 @@ struct DevBuf {
 };
 
 struct ConvOp;   // cnn.hip
+
+// A network's device parameter arrays once another net shares them (iss_cnn_load_shared): freed with their last user.
+struct IssParamArrays {
+    float* blob = nullptr;
+    uint16_t *wh = nullptr, *wl = nullptr, *wh16 = nullptr, *wl16 = nullptr;
+    ~IssParamArrays();                    // cnn.hip
+};
 
 struct IssNet {
     bool loaded = false;
@@ -27,6 +35,7 @@ struct IssNet {
     uint16_t* d_wh16 = nullptr;           // fp16 hi / lo parts (ISS_PREC_F16X3)
     uint16_t* d_wl16 = nullptr;
     bool f16_ok = false;                  // every parameter is inside fp16's range
+    std::shared_ptr<IssParamArrays> shared_params;   // set once the five arrays above are shared with another net: freed with the last holder
     std::map<std::pair<int, int>, uint16_t*> dhl_wp;   // (row, fp16?) -> the dense layer's weights packed for conv_dhl_kernel (built at first use)
     float* d_wsum = nullptr;              // patch-mode first layers: sum_k w[c][k] per output channel (shared first layer)
     std::vector<int64_t> wsum_off;        // per row: offset into d_wsum, -1 = none
@@ -89,6 +98,7 @@ struct iss_ctx {
     double* d_vbx_melw = nullptr;
     int32_t* d_vbx_mellim = nullptr;
     DevBuf vbx_sig, vbx_dither, vbx_fb, vbx_out;
+    DevBuf vbx_meta;                       // batch front end: per-file sample offsets (int64) then frame offsets (int32)
     int32_t vbx_T = 0;
     int64_t vbx_dither_n = 0;              // length of the dither stream cached in vbx_dither (0 = none)
 

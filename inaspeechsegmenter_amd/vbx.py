@@ -9,6 +9,7 @@ Mirrors, for the hot path only:
                                                                    one onnxruntime call per window.
 The VAD filtering / MLP scoring tail of VoiceFemininityScoring (:129-202) lives in vfs.py.
 """
+import hashlib
 import logging
 import os
 
@@ -31,6 +32,56 @@ def dither_stream(n, seed=3):
     """`np.random.seed(3)` + `np.random.rand(n)` (vbx_segmenter.py:84, features_vbx.py:127-128):
     an MT19937 stream, generated on the host and uploaded."""
     return np.random.RandomState(seed).rand(n)
+
+
+def pcm16_of(signal):
+    """The PCM16 samples FeatureExtractor derives from `signal` ((signal * 2**15).astype(int), vbx_segmenter.py:85), or None
+    when they leave int16's range (the general int32 path)."""
+    signal = np.asarray(signal)
+    if signal.dtype == np.int16:
+        return signal
+    sig_i = (np.asarray(signal, dtype=np.float64) * 2 ** 15).astype(int)
+    return sig_i.astype(np.int16) if sig_i.size and -32768 <= sig_i.min() and sig_i.max() <= 32767 else None
+
+
+def frame_count(nsamples):
+    """Frames get_features makes of `nsamples` samples (iss_vbx_features*)."""
+    return (nsamples + 320 - 400) // 160 + 1
+
+
+def plan_windows(frame_counts, durations, basenames, keep=None):
+    """The windows VBxExtractor.__call__ (vbx_segmenter.py:217-246) takes from every file of a batch whose features lie back
+    to back in one arena (iss_vbx_features_batch_pcm16: file f = arena rows frame_off[f] .. frame_off[f + 1]).
+
+    keep(f, (t0, t1)) -> bool, optional: windows it rejects are left out, the ResNet never sees them.
+    Returns (frame_off, files, full_starts, tails):
+      files[f]     [(key, (t0, t1), slot)] in __call__'s order, keys and times as it makes them; slot = row of full_starts
+                   (an int) or (width, j) = row j of tails[width]
+      full_starts  int32 arena starts of the WINLEN-frame windows of the whole batch (one iss_vbx_embed)
+      tails        {width: int32 arena starts of the shorter last windows of that width} (one program, one call per width)
+    No window straddles two files: every start is a start of __call__ inside its own file."""
+    frame_off = np.zeros(len(frame_counts) + 1, dtype=np.int64)
+    frame_off[1:] = np.cumsum(np.asarray(frame_counts, dtype=np.int64))
+    files, full, tails = [], [], {}
+    for f, (T, duration, basename) in enumerate(zip(frame_counts, durations, basenames)):
+        T, base, wins = int(T), int(frame_off[f]), []
+        starts = range(0, T - WINLEN, STEP)
+        start = starts[-1] if starts else 0
+        for s in starts:
+            times = (round(s / 100.0, 3), round(s / 100.0 + WINLEN / 100.0, 3))
+            if keep is None or keep(f, times):
+                wins.append((f'{basename}_{s:08}-{(s + WINLEN):08}', times, len(full)))
+                full.append(base + s)
+        if T - start - STEP >= 10:                                       # last, shorter window (:234-243)
+            width = T - start - STEP
+            times = (round((start + STEP) / 100.0, 3), round(duration, 3))
+            if keep is None or keep(f, times):
+                group = tails.setdefault(width, [])
+                wins.append((f'{basename}_{(start + STEP):08}-{T:08}', times, (width, len(group))))
+                group.append(base + start + STEP)
+        files.append(wins)
+    return (frame_off, files, np.asarray(full, dtype=np.int32),
+            {w: np.asarray(st, dtype=np.int32) for w, st in tails.items()})
 
 
 class ResidentFeatures:
@@ -87,6 +138,7 @@ class VBxExtractor:
     params: state_dict-like mapping of resnet.py's ResNet101 (conv OIHW, BN weight / bias /
     running_mean / running_var, embedding.weight / bias) as numpy arrays."""
     _NET_BASE = 4            # net ids 4.. are used for the per-length programs
+    _BATCH_TAIL_NET = 2      # embed_batch: the tail-width program on the parameters of net _NET_BASE + 1 (iss_cnn_load_shared)
 
     def __init__(self, ctx, params, batch_windows=256):
         self.ctx = ctx
@@ -94,6 +146,9 @@ class VBxExtractor:
         self.batch_windows = batch_windows
         self._nets = {}      # (frames, device-window input) -> net_id
         self._lru = []       # keys of the two tail-length slots, oldest first
+        self._tail_progs = {}    # embed_batch: width -> (compiled program, shares the full-width blob)
+        self._src_digest = None  # digest of the full-width window program's blob
+        self._batch_tail = None  # width of the program in _BATCH_TAIL_NET
 
     def _net_for(self, frames, window=False):
         """Engine program for this window length.  The full-length programs keep fixed slots (4: host input, 5: device
@@ -159,3 +214,59 @@ class VBxExtractor:
             else:
                 xvectors.append((key, (round((start + STEP) / 100.0, 3), round(duration, 3)), xvector * 10))
         return xvectors
+
+    def _tail_net(self, frames):
+        """_BATCH_TAIL_NET holding the `frames`-wide window program.  compile_resnet101's blob does not depend on the width,
+        so the program is loaded on the device parameters of the full-width one (net _NET_BASE + 1): no upload.  Each width
+        is compiled once per extractor and its blob compared with the full-width one then; a width whose blob differed would
+        be loaded in full."""
+        src = self._net_for(WINLEN, window=True)
+        if self._batch_tail == frames:
+            return self._BATCH_TAIL_NET
+        if frames not in self._tail_progs:
+            if self._src_digest is None:
+                self._src_digest = _digest(keras_model.compile_resnet101(self.params, FEAT_DIM, WINLEN, window_input=True).blob)
+            comp = keras_model.compile_resnet101(self.params, FEAT_DIM, frames, window_input=True)
+            shared = _digest(comp.blob) == self._src_digest
+            if shared:
+                comp.blob = None                                          # the device already holds it
+            else:
+                logger.warning(f'ResNet program of width {frames}: parameter blob differs from the full-width one, loaded in full')
+            self._tail_progs[frames] = (comp, shared)
+        comp, shared = self._tail_progs[frames]
+        self._batch_tail = None
+        if shared:
+            self.ctx.cnn_load_shared(self._BATCH_TAIL_NET, src, comp)
+        else:
+            self.ctx.cnn_load(self._BATCH_TAIL_NET, comp)
+        self._batch_tail = frames
+        return self._BATCH_TAIL_NET
+
+    def embed_batch(self, plan):
+        """x-vectors of a plan_windows plan on the resident batch arena: one iss_vbx_embed over the full windows of every file
+        (the engine fills its passes across file boundaries), one program and one call per tail width.  -> per file, the
+        [(key, (t0, t1), x-vector * 10)] list __call__ returns for that file (the same NaN rule; a window's result does not
+        depend on which other windows share its pass)."""
+        _, files, full, tails = plan
+        emb = self.ctx.vbx_embed(self._net_for(WINLEN, window=True), full) if full.size else np.zeros((0, EMBED_DIM), np.float32)
+        groups = {w: self.ctx.vbx_embed(self._tail_net(w), st) for w, st in sorted(tails.items())}
+        bad, emb10 = np.isnan(emb).any(axis=1), emb * 10
+        out = []
+        for wins in files:
+            xvectors = []
+            for key, times, slot in wins:
+                if isinstance(slot, tuple):
+                    x = groups[slot[0]][slot[1]]
+                    nan, x10 = np.isnan(x).any(), x * 10
+                else:
+                    nan, x10 = bad[slot], emb10[slot]
+                if nan:
+                    logger.warning(f'NaN found, not processing: {key}{os.linesep}')
+                else:
+                    xvectors.append((key, times, x10))
+            out.append(xvectors)
+        return out
+
+
+def _digest(blob):
+    return hashlib.blake2b(np.ascontiguousarray(blob).view(np.uint8), digest_size=32).digest()

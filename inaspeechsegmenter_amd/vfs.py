@@ -18,13 +18,14 @@ Known divergence: add_needed_vectors (:40-52) reads `s.stop` on a pyannote Segme
 the branch would raise in the reference; here it does what the code evidently intends (append (key, (start, end), x)).
 """
 import os
+import time
 
 import numpy as np
 
 from . import _native, keras_model
-from .io import media2sig16kmono
+from .io import decode_pcm, media2sig16kmono
 from .segmenter import Segmenter, locate_model
-from .vbx import FeatureExtractor, VBxExtractor, SR
+from .vbx import FeatureExtractor, VBxExtractor, SR, frame_count, pcm16_of, plan_windows
 
 _MLP_NET = 3          # engine net id of the gender MLP (0/1: VAD / gender CNNs, 4..: ResNet programs)
 
@@ -213,3 +214,93 @@ class VoiceFemininityScoring:
         pred = self.gender_predict(np.asarray([x for _, _, x in x_vectors])).reshape(len(x_vectors), -1)[:, 0]
         g = [(seg[0], seg[1], p) for (_, seg, _), p in zip(x_vectors, pred)]
         return get_femininity_score(g), speech_dur, len(g)
+
+    def _score(self, x_vectors, speech, speech_dur):
+        """The tail of __call__ (vbx_segmenter.py:181-202) on one file's x-vectors."""
+        x_vectors = apply_vad(x_vectors, speech, self.vad_thresh)
+        if not x_vectors:
+            return None, speech_dur, 0
+        pred = self.gender_predict(np.asarray([x for _, _, x in x_vectors])).reshape(len(x_vectors), -1)[:, 0]
+        g = [(seg[0], seg[1], p) for (_, seg, _), p in zip(x_vectors, pred)]
+        return get_femininity_score(g), speech_dur, len(g)
+
+    def _decode(self, fpath, nbtry, trydelay):
+        for itry in range(nbtry):
+            try:
+                return decode_pcm(fpath, ffmpeg=self.ffmpeg)
+            except _native.NativeError:
+                raise
+            except Exception:
+                if itry + 1 == nbtry:
+                    raise
+                time.sleep(trydelay)
+
+    def _score_batch(self, batch):
+        """batch: [(index, basename, pcm16, duration, speech, speech_dur)] -> {index: result}.  One front-end call for all
+        files, the windows whose midpoint is not in speech left out before the ResNet (apply_vad and add_needed_vectors only
+        read mid-speech windows, in list order: vbx_segmenter.py:28-52, 129-145), then __call__'s tail per file."""
+        self.features._ensure_dither(max(len(b[2]) for b in batch))
+        self.ctx.vbx_features_batch_pcm16([b[2] for b in batch], to_host=False)
+        self.ctx._vbx_resident = None                     # the single-file arena is gone
+        speeches = [b[4] for b in batch]
+        plan = plan_windows([frame_count(len(b[2])) for b in batch], [b[3] for b in batch], [b[1] for b in batch],
+                            keep=lambda f, t: is_mid_speech(t[0], t[1], speeches[f]))
+        xv = self.xvector_model.embed_batch(plan)
+        return {b[0]: self._score(x, b[4], b[5]) for b, x in zip(batch, xv)}
+
+    def batch_process(self, linput, output_csv=None, batch_seconds=3600, nbtry=1, trydelay=2., verbose=False):
+        """__call__ on many files -> [(score, speech_duration, nb_vectors) or an error message] in `linput` order, the same
+        results as __call__ on each file.  Every file is decoded once (to PCM16): the VAD and the x-vector front end read the
+        same array.  Files with speech are gathered into batches of at most `batch_seconds` of audio (a longer file makes a
+        batch of its own): per batch, one front-end call (iss_vbx_features_batch_pcm16), one ResNet call over all full
+        windows, one per distinct last-window width on the parameters already on the device.  A file that cannot be decoded
+        (`nbtry` attempts, `trydelay` s apart) or is too short for the VAD gets an error message and the batch goes on;
+        device failures raise.  output_csv: also write a TSV `path score speech_duration nb_vectors` (header line first;
+        a failed file's row carries its message)."""
+        linput = list(linput)
+        results = [None] * len(linput)
+        batch, held = [], 0.0
+
+        def flush():
+            if batch:
+                for i, r in self._score_batch(batch).items():
+                    results[i] = r
+                if verbose:
+                    print('%d/%d scored' % (sum(r is not None for r in results), len(linput)))
+                batch.clear()
+
+        for i, fpath in enumerate(linput):
+            try:
+                a = self._decode(fpath, nbtry, trydelay)
+                vad = self.vad.segment_signal(a)
+            except _native.NativeError:
+                raise
+            except Exception as exc:
+                results[i] = f'{type(exc).__name__}: {exc}'
+                if verbose:
+                    print(fpath, results[i])
+                continue
+            speech = speech_intervals(vad)
+            speech_dur = speech_duration(speech)
+            if not speech_dur:
+                results[i] = (None, speech_dur, 0)
+                continue
+            basename = os.path.splitext(os.path.basename(fpath))[0]
+            duration = len(a) / SR
+            pcm = pcm16_of(a)
+            if pcm is None:                               # samples beyond int16 (float source): the single-file front end
+                feats = self.features(np.asarray(a, dtype=np.float64))     # = media2sig16kmono(fpath) of __call__
+                results[i] = self._score(self.xvector_model(basename, feats, duration), speech, speech_dur)
+                continue
+            if batch and held + duration > batch_seconds:
+                flush()
+                held = 0.0
+            batch.append((i, basename, pcm, duration, speech, speech_dur))
+            held += duration
+        flush()
+        if output_csv is not None:
+            with open(output_csv, 'w') as fh:
+                fh.write('path\tscore\tspeech_duration\tnb_vectors\n')
+                for fpath, r in zip(linput, results):
+                    fh.write('\t'.join([fpath] + ([str(v) for v in r] if isinstance(r, tuple) else [r])) + '\n')
+        return results

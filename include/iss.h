@@ -158,6 +158,15 @@ int iss_cnn_load(iss_ctx* ctx, int net_id, const int32_t* prog, int32_t nrows,
                  const float* blob, int64_t blob_floats,
                  int32_t nbuf, const int64_t* buf_elems,
                  int32_t in_h, int32_t in_w, int32_t in_c, int32_t out_dim);
+/* Load a program whose parameter blob is byte-identical to net src_id's (e.g. the same ResNet compiled for another window
+ * width): iss_cnn_load minus the blob.  No parameter upload and no hi / lo split: the device parameter arrays (f32 and the
+ * bf16 / fp16 halves) are shared and reference-counted, so unloading either net leaves the other valid.  The rows are
+ * validated against the source's blob size; f16 eligibility is the source's; the precision state starts as a fresh load's.
+ * Per-program state (im2col tables, weight sums, packed dense weights, buffer plan) is the new net's own.  Replaces, for the
+ * shorter last window of every file (vbx_segmenter.py:234-243), a full reload of the same ResNet-101 parameters.       */
+int iss_cnn_load_shared(iss_ctx* ctx, int net_id, int src_id, const int32_t* prog, int32_t nrows,
+                        int32_t nbuf, const int64_t* buf_elems,
+                        int32_t in_h, int32_t in_w, int32_t in_c, int32_t out_dim);
 
 /* Class probabilities of n 20 ms slots.  win_row[i] = first mspec row of the 68-frame
  * window feeding slot i (the host applies the 17-left/16(+1)-right edge replication of
@@ -272,6 +281,15 @@ int iss_vbx_features(iss_ctx* ctx, const int32_t* sig_i32, const double* dither_
 int iss_vbx_set_dither(iss_ctx* ctx, const double* dither_u, int64_t n);
 int iss_vbx_features_pcm16(iss_ctx* ctx, const int16_t* pcm, int64_t n,
                            float* fea_out /* T*64 or NULL */, int32_t* T_out);
+/* F files of PCM16 concatenated (file f = pcm[sample_off[f] .. sample_off[f+1]), F+1 offsets), each >= 200 samples; dither =
+ * the cached stream (iss_vbx_set_dither), long enough for the LONGEST file: every file restarts at u[0] (vbx_segmenter.py:84).
+ * Leaves ONE resident (sum T_f, 64) f32 arena for iss_vbx_embed (window starts are arena rows); frame_off_out[f] = first
+ * frame of file f (F+1 entries).  The frames of file f are bit-identical to iss_vbx_features_pcm16 on that file alone.
+ * Three launches per batch (fbank over all frames, one cumsum wavefront per file, one ragged CMN), where a loop over
+ * iss_vbx_features_pcm16 makes three per file.  ISS_EINVAL: a file under 200 samples or over the per-file limit, or more than
+ * 2^31 - 8192 frames in all.  Replaces a per-file loop over get_features (vbx_segmenter.py:72-89).                      */
+int iss_vbx_features_batch_pcm16(iss_ctx* ctx, const int16_t* pcm, const int64_t* sample_off, int32_t nfiles,
+                                 int32_t* frame_off_out, float* fea_out /* (sum T_f)*64, or NULL: stay resident */);
 /* x-vectors of n windows [starts[i], starts[i] + frames) of the RESIDENT features (frames = the loaded network's input
  * width; its first conv must be a window-mode conv, ISS_C_INMODE 2): replaces the window loop of
  * vbx_segmenter.py:222-231 + get_embedding (:262-266) without copying windows through the host.                        */
