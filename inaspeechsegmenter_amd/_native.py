@@ -20,6 +20,10 @@ PREC_BF16X3, PREC_F32, PREC_F16X3 = 0, 1, 2
 K_ALIGN = 32          # conv weight rows are padded to a multiple of this many k
 BUF_INPUT = -2
 MAX_NETS = 8
+# iss_resample_job (include/iss.h) and the ISS_RS_* format of each stored sample dtype
+RS_JOB = np.dtype([('src_offset', '<i8'), ('frames_in', '<i8'), ('channels', '<i4'), ('format', '<i4'), ('filter', '<i4'),
+                   ('reserved', '<i4'), ('dst_offset', '<i8'), ('frames_out', '<i8')])
+RS_FORMAT = {np.dtype(np.uint8): 0, np.dtype('<i2'): 1, np.dtype('<i4'): 2, np.dtype('<f4'): 3, np.dtype('<f8'): 4}
 
 
 class NativeError(RuntimeError):
@@ -62,6 +66,10 @@ def lib():
         'iss_signal_f32': (C.c_int, [vp, pf, i64]),
         'iss_signal_pcm16_device': (C.c_int, [vp, vp, i64]),
         'iss_signal_pcm16_device_stream': (C.c_int, [vp, vp, i64, vp]),
+        'iss_resample_filter': (C.c_int, [vp, i32, i32, pd, i64, pi32]),
+        'iss_resample_pcm16': (C.c_int, [vp, vp, i64, vp, i32, i64]),
+        'iss_get_signal_pcm16': (C.c_int, [vp, pi16, i64, i64]),
+        'iss_resample_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_host_alloc': (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
         'iss_host_free': (C.c_int, [vp, vp]),
         'iss_cnn_probs_async': (C.c_int, [vp, C.c_int, pi32, i32, pf, pu8, pi64]),
@@ -251,6 +259,49 @@ class Context:
         self._ck(self._L.iss_signal_pcm16_device_stream(self._h, C.c_void_p(int(dev_ptr)), int(n),
                                                         C.c_void_p(int(producer_stream)) if producer_stream else None),
                  'iss_signal_pcm16_device')
+
+    # ---- resampler (iss_resample_*): WAV sources at other rates / channel counts -> resident 16 kHz mono PCM16
+    def resample_filter(self, sr):
+        """Register the filter of source rate `sr` (resample.plan; cached by the library) -> (filter id, up, down)."""
+        from . import resample
+        up, down, h = resample.plan(sr)
+        fid = C.c_int32()
+        self._ck(self._L.iss_resample_filter(self._h, up, down, _ptr(h, C.c_double), h.size, C.byref(fid)), 'iss_resample_filter')
+        return fid.value, up, down
+
+    def resample_job(self, x, sr, src_offset, dst_offset):
+        """One iss_resample_job row for stored samples x ((n,) or (n, C)) placed at byte `src_offset` of the source buffer."""
+        fid, up, down = self.resample_filter(sr)
+        n = x.shape[0]
+        return (src_offset, n, 1 if x.ndim == 1 else x.shape[1], RS_FORMAT[x.dtype], fid, 0, dst_offset, -(-n * up // down))
+
+    def resample(self, src, jobs, n_signal=-1):
+        """iss_resample_pcm16: src = 1-D uint8 array of the stored samples of every job, jobs = rows of RS_JOB; one H2D copy,
+        one launch.  n_signal >= 0: a new resident signal of that many samples; < 0: into the signal of the last set_signal."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        jb = np.ascontiguousarray(np.array(jobs, dtype=RS_JOB))
+        self._ck(self._L.iss_resample_pcm16(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
+                                            jb.size, int(n_signal)), 'iss_resample_pcm16')
+        self._keep_rs = src         # the async H2D copy reads it until the next sync
+
+    def resample_signal(self, x, sr):
+        """A single source resampled on its own: the resident signal becomes its 16 kHz mono PCM16 -> its length."""
+        x = np.ascontiguousarray(x)
+        job = self.resample_job(x, sr, 0, 0)
+        self.resample(x.reshape(-1).view(np.uint8), [job], n_signal=job[-1])
+        return job[-1]
+
+    def get_signal_pcm16(self, offset, n):
+        """Samples [offset, offset + n) of the resident PCM16 signal (e.g. what `resample` wrote)."""
+        out = np.empty(int(n), dtype=np.int16)
+        self._ck(self._L.iss_get_signal_pcm16(self._h, _ptr(out, C.c_int16), int(offset), int(n)), 'iss_get_signal_pcm16')
+        return out
+
+    def resample_stats(self):
+        """(resample launches, resample jobs) since the context was created."""
+        a, b = C.c_int64(), C.c_int64()
+        self._ck(self._L.iss_resample_stats(self._h, C.byref(a), C.byref(b)), 'iss_resample_stats')
+        return a.value, b.value
 
     # ---- page-locked host arrays
     def pinned_empty(self, shape, dtype):

@@ -77,9 +77,10 @@ extern "C" void iss_destroy(iss_ctx* c) {
     void* singles[] = {c->d_window, c->d_melw, c->d_mellim, c->d_tw, c->d_vbx_window, c->d_vbx_melw, c->d_vbx_mellim};
     for (void* p : singles) if (p) (void)hipFree(p);
     DevBuf* bufs[] = {&c->sig, &c->mspec, &c->loge, &c->d_winrow, &c->d_stats, &c->d_finite, &c->d_out, &c->d_in, &c->raw1,
-                      &c->vbx_sig, &c->vbx_dither, &c->vbx_fb, &c->vbx_out, &c->vbx_meta};
+                      &c->vbx_sig, &c->vbx_dither, &c->vbx_fb, &c->vbx_out, &c->vbx_meta, &c->rs_src, &c->rs_jobs};
     for (DevBuf* b : bufs) free_buf(*b);
     for (auto& b : c->act) free_buf(b);
+    for (auto& f : c->rs_filters) if (f.d_taps) (void)hipFree(f.d_taps);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& e : c->ev_pool) (void)hipEventDestroy(e);
     for (auto& e : c->ticket_ev) (void)hipEventDestroy(e);
@@ -175,6 +176,17 @@ extern "C" int iss_signal_pcm16_device_stream(iss_ctx* c, const void* dev, int64
 }
 extern "C" int iss_signal_pcm16_device(iss_ctx* c, const void* dev, int64_t n) {
     return iss_signal_pcm16_device_stream(c, dev, n, nullptr);
+}
+extern "C" int iss_get_signal_pcm16(iss_ctx* c, int16_t* out, int64_t offset, int64_t n) {
+    if (!c || (!out && n > 0) || offset < 0 || n < 0) return iss_fail(c, ISS_EINVAL, "iss_get_signal_pcm16: bad argument");
+    if (c->sig_kind != 1) return iss_fail(c, ISS_ESTATE, "iss_get_signal_pcm16: no resident PCM16 signal");
+    if (offset + n > c->sig_n)
+        return iss_fail(c, ISS_EINVAL, "iss_get_signal_pcm16: [%lld, %lld) outside the %lld-sample signal", (long long)offset,
+                        (long long)(offset + n), (long long)c->sig_n);
+    ISS_HIP(c, hipSetDevice(c->device));
+    if (n > 0) ISS_HIP(c, hipMemcpyAsync(out, (const int16_t*)c->sig_ptr + offset, (size_t)n * 2, hipMemcpyDeviceToHost, c->stream));
+    ISS_HIP(c, hipStreamSynchronize(c->stream));
+    return ISS_OK;
 }
 
 // ---------------------------------------------------------------- pinned host memory

@@ -76,6 +76,13 @@ struct iss_ctx {
     int sig_kind = 0;                     // 0 none, 1 pcm16, 2 f32
     int64_t sig_n = 0;
 
+    // resampler (resample.hip): filters per (up, down), the raw-source and job buffers of the last call
+    struct RsFilter { int32_t up = 1, down = 1, hl = 0; int64_t ntaps = 1; double* d_taps = nullptr; };
+    std::vector<RsFilter> rs_filters;
+    std::map<std::pair<int32_t, int32_t>, int32_t> rs_filter_id;
+    DevBuf rs_src, rs_jobs;
+    int64_t rs_launches = 0, rs_jobs_done = 0;
+
     // resident features
     DevBuf mspec, loge;
     int32_t T = 0;

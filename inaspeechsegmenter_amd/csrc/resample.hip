@@ -1,0 +1,243 @@
+// Downmix + polyphase low-pass resampling + PCM16 quantisation of WAV sources at any rate, for gfx950 (float64).
+//
+// Replaces the 16 kHz-only assertion of the ffmpeg-free read (io.py:53-55): iss_resample_pcm16 turns the stored samples of
+// many files (one H2D copy) into 16 kHz mono PCM16 in the resident signal, in ONE launch of resample_kernel.  The
+// arithmetic is inaspeechsegmenter_amd/resample.py's `resample_ref` to the bit (include/iss.h states it).
+//
+// Grid: ragged over (job, output tile).  Job k owns tiles [tile_base_k, tile_base_k + ceil(frames_out / tile_k)), a prefix
+// sum built on the host; a workgroup finds its job by binary search.  A tile is 256 * R consecutive outputs (R = 4, 2 or 1:
+// the largest whose input span fits 64 KiB).  Per workgroup:
+//   1. the filter table (2*hl+1 float64) goes into LDS when it fits next to the span (160 KiB per workgroup on gfx950);
+//      larger tables (e.g. 44 056 Hz: 110 141 taps) are read through L1/L2
+//   2. the input span s0 = floor((i0*down - hl)/up) .. floor((i_last*down + hl)/up) is staged in LDS, each frame's channels
+//      converted and averaged to float64 on the way; frames outside [0, frames_in) are 0 (a job never reads another's bytes)
+//   3. thread t computes outputs i0 + t + 256*r: first input j0 = ceil((i*down - hl)/up), its tap i*down + hl - j0*up, then
+//      every `up`-th tap down to 0, summed in ascending j with separate multiply and add, then rint * 32768 and saturation
+// All index arithmetic is 64-bit: i*down passes 2^31 after ~5 minutes of 44.1 kHz output.
+#include "iss_internal.h"
+#include <algorithm>
+#include <cstring>
+
+namespace {
+
+constexpr int RS_THREADS = 256;
+constexpr int64_t RS_LDS_MAX = 160 * 1024;         // bytes of LDS one workgroup may use on gfx950
+constexpr int64_t RS_SPAN_MAX = 64 * 1024;         // a tile's input span (float64) is kept under this when R > 1
+
+struct RsJobDev {
+    int64_t src_off, n_in, dst_off, n_out, tile_base;
+    const double* taps;
+    int32_t ch, fmt, up, down, hl, tile, lds_tab, pad;
+};
+
+__device__ __forceinline__ double to_f64(uint8_t x) { return __ddiv_rn(__dsub_rn((double)x, 128.0), 128.0); }
+__device__ __forceinline__ double to_f64(int16_t x) { return __ddiv_rn((double)x, 32768.0); }
+__device__ __forceinline__ double to_f64(int32_t x) { return __ddiv_rn((double)x, 2147483648.0); }
+__device__ __forceinline__ double to_f64(float x) { return (double)x; }
+__device__ __forceinline__ double to_f64(double x) { return x; }
+
+// frames s0 .. s0+len-1 of one source, downmixed to float64 (channels summed in order, divided by their count)
+template <typename T>
+__device__ __forceinline__ void stage_span(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
+                                           double* __restrict__ span) {
+    const T* p = reinterpret_cast<const T*>(src);
+    for (int k = threadIdx.x; k < len; k += RS_THREADS) {
+        const int64_t j = s0 + k;
+        double v = 0.0;
+        if (j >= 0 && j < n_in) {
+            const T* q = p + j * ch;
+            v = to_f64(q[0]);
+            for (int c = 1; c < ch; ++c) v = __dadd_rn(v, to_f64(q[c]));
+            if (ch > 1) v = __ddiv_rn(v, (double)ch);
+        }
+        span[k] = v;
+    }
+}
+
+__device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) {      // b > 0
+    return a >= 0 ? a / b : -((-a + b - 1) / b);
+}
+
+__device__ __forceinline__ void compute_tile(const RsJobDev& J, const double* __restrict__ tab, const double* __restrict__ span,
+                                             int64_t s0, int64_t i0, int64_t i_end, int16_t* __restrict__ dst) {
+    const int64_t up = J.up, down = J.down, hl = J.hl;
+    for (int64_t i = i0 + threadIdx.x; i < i_end; i += RS_THREADS) {
+        const int64_t j0 = -floor_div(hl - i * down, up);                  // ceil((i*down - hl) / up)
+        int t = (int)(i * down + hl - j0 * up);                             // in (2*hl - up, 2*hl]
+        const double* sp = span + (j0 - s0);
+        double acc = 0.0;
+        for (; t >= 0; t -= (int)up, ++sp) acc = __dadd_rn(acc, __dmul_rn(tab[t], *sp));
+        const double q = fmin(fmax(rint(__dmul_rn(acc, 32768.0)), -32768.0), 32767.0);
+        dst[J.dst_off + i] = (int16_t)q;
+    }
+}
+
+__global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __restrict__ src, const RsJobDev* __restrict__ jobs,
+                                                              int njobs, int16_t* __restrict__ dst) {
+    extern __shared__ __attribute__((aligned(16))) double rs_smem[];
+    const int64_t b = blockIdx.x;
+    int lo = 0, hi = njobs - 1;                                             // last job whose tile_base <= b
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].tile_base <= b) lo = mid; else hi = mid - 1;
+    }
+    const RsJobDev J = jobs[lo];
+    const int64_t i0 = (b - J.tile_base) * J.tile;
+    const int64_t i_end = min(i0 + (int64_t)J.tile, J.n_out);
+    const int64_t s0 = floor_div(i0 * J.down - J.hl, J.up);
+    const int64_t s1 = floor_div((i_end - 1) * J.down + J.hl, J.up);
+    const int len = (int)(s1 - s0 + 1);
+    const int ntaps = 2 * J.hl + 1;
+    double* span = rs_smem + (J.lds_tab ? ((ntaps + 1) & ~1) : 0);        // 16-byte aligned carve
+    if (J.lds_tab)
+        for (int k = threadIdx.x; k < ntaps; k += RS_THREADS) rs_smem[k] = J.taps[k];
+    const uint8_t* s = src + J.src_off;
+    switch (J.fmt) {
+        case ISS_RS_U8:  stage_span<uint8_t>(s, J.n_in, J.ch, s0, len, span); break;
+        case ISS_RS_I16: stage_span<int16_t>(s, J.n_in, J.ch, s0, len, span); break;
+        case ISS_RS_I32: stage_span<int32_t>(s, J.n_in, J.ch, s0, len, span); break;
+        case ISS_RS_F32: stage_span<float>(s, J.n_in, J.ch, s0, len, span); break;
+        default:         stage_span<double>(s, J.n_in, J.ch, s0, len, span); break;
+    }
+    __syncthreads();
+    if (J.lds_tab) compute_tile(J, rs_smem, span, s0, i0, i_end, dst);
+    else           compute_tile(J, J.taps, span, s0, i0, i_end, dst);
+}
+
+const int kFmtBytes[5] = {1, 2, 4, 4, 8};
+
+// longest input span of a tile of `tile` outputs: floor(((tile-1)*down + 2*hl) / up) + 2 frames
+int64_t span_frames(const iss_ctx::RsFilter& f, int64_t tile) {
+    return ((tile - 1) * f.down + 2 * (int64_t)f.hl) / f.up + 2;
+}
+
+}  // namespace
+
+extern "C" int iss_resample_filter(iss_ctx* c, int32_t up, int32_t down, const double* taps, int64_t ntaps, int32_t* id_out) {
+    if (!c || !taps || !id_out) return iss_fail(c, ISS_EINVAL, "iss_resample_filter: NULL argument");
+    if (up < 1 || down < 1 || up > 384000 || down > 384000)
+        return iss_fail(c, ISS_EINVAL, "iss_resample_filter: up %d / down %d out of range", up, down);
+    const int64_t want = up == 1 && down == 1 ? 1 : 20 * (int64_t)std::max(up, down) + 1;
+    if (ntaps != want)
+        return iss_fail(c, ISS_EINVAL, "iss_resample_filter: %lld taps for %d/%d, expected %lld", (long long)ntaps, up, down,
+                        (long long)want);
+    auto it = c->rs_filter_id.find({up, down});
+    if (it != c->rs_filter_id.end()) { *id_out = it->second; return ISS_OK; }
+    ISS_HIP(c, hipSetDevice(c->device));
+    iss_ctx::RsFilter f;
+    f.up = up; f.down = down; f.hl = (int32_t)((ntaps - 1) / 2); f.ntaps = ntaps;
+    ISS_HIP(c, hipMalloc((void**)&f.d_taps, (size_t)ntaps * sizeof(double)));
+    hipError_t e = hipMemcpy(f.d_taps, taps, (size_t)ntaps * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(f.d_taps);
+        return iss_fail(c, ISS_EHIP, "iss_resample_filter: hipMemcpy: %s", hipGetErrorString(e));
+    }
+    const int32_t id = (int32_t)c->rs_filters.size();
+    c->rs_filters.push_back(f);
+    c->rs_filter_id[{up, down}] = id;
+    *id_out = id;
+    return ISS_OK;
+}
+
+extern "C" int iss_resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
+                                  int64_t n_signal) {
+    if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0))
+        return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: bad argument");
+    ISS_HIP(c, hipSetDevice(c->device));
+    int64_t nsig = n_signal;
+    if (n_signal < 0) {
+        if (c->sig_kind != 1 || c->sig_ptr != c->sig.p)
+            return iss_fail(c, ISS_ESTATE, "iss_resample_pcm16: n_signal < 0 needs a PCM16 signal uploaded by iss_signal_pcm16");
+        nsig = c->sig_n;
+    }
+    // validate every job, build the device descriptors and the tile prefix sum
+    std::vector<RsJobDev> dj((size_t)njobs);
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    int64_t tiles = 0, lds = 0;
+    for (int32_t k = 0; k < njobs; ++k) {
+        const iss_resample_job& J = jobs[k];
+        if (J.format < ISS_RS_U8 || J.format > ISS_RS_F64)
+            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: bad format %d", k, J.format);
+        if (J.channels < 1 || J.channels > 1024)
+            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: %d channels", k, J.channels);
+        if (J.filter < 0 || J.filter >= (int32_t)c->rs_filters.size())
+            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: unknown filter %d", k, J.filter);
+        const iss_ctx::RsFilter& f = c->rs_filters[(size_t)J.filter];
+        const int64_t esz = kFmtBytes[J.format];
+        if (J.frames_in < 1 || J.frames_in > (int64_t(1) << 40) / (esz * J.channels))
+            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: %lld frames", k, (long long)J.frames_in);
+        const int64_t nbytes = J.frames_in * J.channels * esz;
+        if (J.src_offset < 0 || J.src_offset % esz != 0 || J.src_offset > src_bytes - nbytes)
+            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: source bytes [%lld, %lld) outside the %lld-byte buffer or "
+                            "not aligned to %lld", k, (long long)J.src_offset, (long long)(J.src_offset + nbytes),
+                            (long long)src_bytes, (long long)esz);
+        const int64_t nout = (J.frames_in * f.up + f.down - 1) / f.down;
+        if (J.frames_out != nout)
+            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: frames_out %lld, ceil(%lld * %d / %d) = %lld", k,
+                            (long long)J.frames_out, (long long)J.frames_in, f.up, f.down, (long long)nout);
+        if (J.dst_offset < 0 || J.dst_offset > nsig - nout)
+            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: output [%lld, %lld) outside the %lld-sample signal", k,
+                            (long long)J.dst_offset, (long long)(J.dst_offset + nout), (long long)nsig);
+        ranges.push_back({J.dst_offset, J.dst_offset + nout});
+        int64_t tile = RS_THREADS * 4;
+        while (tile > RS_THREADS && span_frames(f, tile) * 8 > RS_SPAN_MAX) tile /= 2;
+        const int64_t span_b = span_frames(f, tile) * 8;
+        const int64_t tab_b = ((f.ntaps + 1) & ~int64_t(1)) * 8;
+        const bool lds_tab = span_b + tab_b <= RS_LDS_MAX;
+        lds = std::max(lds, span_b + (lds_tab ? tab_b : 0));
+        RsJobDev& d = dj[(size_t)k];
+        d.src_off = J.src_offset; d.n_in = J.frames_in; d.dst_off = J.dst_offset; d.n_out = nout; d.tile_base = tiles;
+        d.taps = f.d_taps; d.ch = J.channels; d.fmt = J.format; d.up = f.up; d.down = f.down; d.hl = f.hl;
+        d.tile = (int32_t)tile; d.lds_tab = lds_tab ? 1 : 0; d.pad = 0;
+        tiles += (nout + tile - 1) / tile;
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t k = 1; k < ranges.size(); ++k)
+        if (ranges[k].first < ranges[k - 1].second)
+            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: output ranges [%lld, %lld) and [%lld, %lld) overlap",
+                            (long long)ranges[k - 1].first, (long long)ranges[k - 1].second, (long long)ranges[k].first,
+                            (long long)ranges[k].second);
+    if (tiles > 0x7fffffffLL) return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: %lld tiles in one call", (long long)tiles);
+    if (n_signal >= 0) {                                   // a signal of its own, zero wherever no job writes
+        int rc = iss_reserve(c, c->sig, (size_t)nsig * 2 + 16);
+        if (rc) return rc;
+        if (nsig > 0) ISS_HIP(c, hipMemsetAsync(c->sig.p, 0, (size_t)nsig * 2, c->stream));
+        c->sig_ptr = c->sig.p; c->sig_kind = 1; c->sig_n = nsig;
+    }
+    c->have_feats = false;
+    if (njobs == 0) return ISS_OK;
+    int rc = iss_reserve(c, c->rs_src, (size_t)std::max<int64_t>(src_bytes, 16));
+    if (rc) return rc;
+    rc = iss_reserve(c, c->rs_jobs, dj.size() * sizeof(RsJobDev));
+    if (rc) return rc;
+    iss_prof_begin(c, ISS_PROF_OTHER, 0.0);
+    iss_prof_inst(c, "resample_h2d(%lld B)", (long long)src_bytes);
+    if (src_bytes > 0) ISS_HIP(c, hipMemcpyAsync(c->rs_src.p, src, (size_t)src_bytes, hipMemcpyHostToDevice, c->stream));
+    iss_prof_end(c);
+    void* pinned = nullptr;
+    int slot = -1;
+    rc = iss_stage_host(c, dj.data(), dj.size() * sizeof(RsJobDev), &pinned, &slot);
+    if (rc) return rc;
+    ISS_HIP(c, hipMemcpyAsync(c->rs_jobs.p, pinned, dj.size() * sizeof(RsJobDev), hipMemcpyHostToDevice, c->stream));
+    iss_stage_mark(c, slot);
+    if (lds > 64 * 1024)
+        ISS_HIP(c, hipFuncSetAttribute((const void*)resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    double flops = 0;
+    for (const RsJobDev& d : dj) flops += 2.0 * (double)d.n_out * (2.0 * d.hl + 1) / d.up;
+    iss_prof_begin(c, ISS_PROF_FRONTEND, flops);
+    iss_prof_inst(c, "resample_kernel");
+    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)tiles), dim3(RS_THREADS), (size_t)lds, c->stream,
+                       (const uint8_t*)c->rs_src.p, (const RsJobDev*)c->rs_jobs.p, (int)njobs, (int16_t*)c->sig.p);
+    ISS_HIP(c, hipGetLastError());
+    iss_prof_end(c);
+    c->rs_launches += 1;
+    c->rs_jobs_done += njobs;
+    return ISS_OK;
+}
+
+extern "C" int iss_resample_stats(iss_ctx* c, int64_t* launches, int64_t* jobs) {
+    if (!c) return ISS_EINVAL;
+    if (launches) *launches = c->rs_launches;
+    if (jobs) *jobs = c->rs_jobs_done;
+    return ISS_OK;
+}

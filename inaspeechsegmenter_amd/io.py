@@ -120,6 +120,13 @@ def decode_pcm(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg'):
     return np.ascontiguousarray(_to_float(a, np.float32))
 
 
+def decode_source(medianame):
+    """ffmpeg-free read of any WAV (Segmenter(ffmpeg=None, resample=True)): -> (samples as stored, (n,) or (n, C), sr).
+    Nothing is converted: the device downmixes, resamples and quantises (inaspeechsegmenter_amd/resample.py)."""
+    with open(medianame, 'rb') as f:
+        return _parse_wav(f.read(), medianame)
+
+
 def media2sig16kmono(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg', dtype='float64'):
     """Reference-compatible signature and result (float array of `dtype`)."""
     a = decode_pcm(medianame, start_sec, stop_sec, ffmpeg)

@@ -5,11 +5,13 @@ main thread runs the two Keras `predict` calls, the Viterbi smoothing and the ex
 (segmenter.py:297-335, medialist2feats :338-374).  On an MI355X a 5-minute file is ~14 ms of device work, so per-file
 launches, copies and Python bookkeeping become the limit.  Here files are processed in SUPER-BATCHES:
 
-  decode threads   N files  ->  int16 PCM (RIFF parse, or the ffmpeg pipe)
+  decode threads   N files  ->  int16 PCM (RIFF parse, or the ffmpeg pipe); with Segmenter(resample=True) WAVs at other
+                   rates / channel counts are handed on as stored (segmenter.RawSource)
   packer           the PCM of a super-batch (default <= 32 files / ~40 min of audio) is laid end to end in ONE page-locked
                    buffer, every file starting on a multiple of 160 samples: frame t of file f is then frame
                    off_f / 160 + t of the concatenation, and the frames that straddle two files are simply never used
-  device worker    ONE H2D copy, ONE sidekit launch, one log-energy read-back; per-file energy Viterbi (compiled);
+                   (room is left for the resampled files, whose stored bytes go into a second page-locked buffer)
+  device worker    ONE H2D copy, ONE resample launch for all resampled files (one more H2D copy), ONE sidekit launch, one log-energy read-back; per-file energy Viterbi (compiled);
                    ONE iss_cnn_probs call for the VAD windows of all files, per-segment Viterbi; ONE call for the
                    gender windows, Viterbi; hand the segment lists to the exporter
   exporter         CSV / TextGrid writers
@@ -27,7 +29,6 @@ import warnings
 import numpy as np
 
 from . import _native
-from .io import decode_pcm
 
 FRAME_HOP = 160
 MIN_SAMPLES = 400 + FRAME_HOP * 67                  # 68 frames: shorter media take the single-file path (mspec padding)
@@ -39,8 +40,14 @@ class _Batch:
     def __init__(self):
         self.idx, self.sigs, self.names = [], [], []
 
-    def samples(self):
+    def samples(self):                               # 16 kHz samples (a RawSource's size is its resampled length)
         return sum(-(-s.size // FRAME_HOP) * FRAME_HOP for s in self.sigs)
+
+
+def _held(sig):
+    """What a decoded source holds, in 16-bit sample units: its samples, or a stored source's bytes / 2 when larger."""
+    x = getattr(sig, 'x', None)
+    return sig.size if x is None else max(sig.size, x.nbytes // 2)
 
 
 class _AudioBudget:
@@ -63,9 +70,10 @@ class _AudioBudget:
             self.cv.notify_all()
 
 
-def _decode_stage(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None):
+def _decode_stage(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None, resample=False):
     """items: [(index, src)].  Puts (index, src, sig | None, errtext | None) on out_q in completion order, then None."""
     import random
+    from . import segmenter as S
     in_q = queue.Queue()
     for it in items:
         in_q.put(it)
@@ -79,14 +87,14 @@ def _decode_stage(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None):
             sig, err, itry = None, None, 0
             while sig is None and itry < nbtry:
                 try:
-                    sig = decode_pcm(src, None, None, ffmpeg)
+                    sig = S._load_source(src, None, None, ffmpeg, resample)
                 except:                                            # noqa: E722  (reference semantics, segmenter.py:364-370)
                     itry += 1
                     err = 'error: ' + str(sys.exc_info()[0])
                     if itry != nbtry:
                         time.sleep(random.random() * trydelay)
             if budget is not None and sig is not None:
-                budget.acquire(sig.size)
+                budget.acquire(_held(sig))
             out_q.put((i, src, sig, err))
 
     ths = [threading.Thread(target=work, daemon=True) for _ in range(max(1, nthreads))]
@@ -117,6 +125,7 @@ class _Worker:
             self.owned = False
         self.ctx = ctx
         self.pin = None
+        self.rpin = None                             # stored bytes of the resampled files of a pass
         # wall seconds this worker spent per phase since the last reset (bench.py reports them: where a step's host time goes)
         self.stats = {k: 0.0 for k in ('pack', 'features', 'energy_host', 'cnn_device', 'smooth_host', 'batches', 'files')}
 
@@ -130,6 +139,13 @@ class _Worker:
                 self.ctx.pinned_free(self.pin)
             self.pin = self.ctx.pinned_empty((int(nsamples * 1.25) + 4096,), np.int16)
         return self.pin
+
+    def raw_pinned(self, nbytes):
+        if self.rpin is None or self.rpin.size < nbytes:
+            if self.rpin is not None:
+                self.ctx.pinned_free(self.rpin)
+            self.rpin = self.ctx.pinned_empty((int(nbytes * 1.25) + 4096,), np.uint8)
+        return self.rpin
 
     def sync_settings(self):
         """Arithmetic mode and workspace cap follow the Segmenter's own context (they may have changed since this
@@ -148,14 +164,27 @@ class _Worker:
             offs.append(pos)
             pos += -(-s.size // FRAME_HOP) * FRAME_HOP
         buf = self.pinned(pos)
+        raws = []
         for s, o in zip(batch.sigs, offs):
-            if s.dtype == np.int16:
+            if isinstance(s, S.RawSource):           # written by the resample kernel
+                buf[o:o + s.size] = 0
+                raws.append((s, o))
+            elif s.dtype == np.int16:
                 buf[o:o + s.size] = s
             else:                                    # float sources: what libsndfile's float32 read holds, re-quantised is NOT exact
                 raise TypeError('float media take the single-file path')
             buf[o + s.size:o + -(-s.size // FRAME_HOP) * FRAME_HOP] = 0
+        if raws:                                     # stored bytes end to end, each source on a 16-byte boundary
+            rb = self.raw_pinned(sum(-(-s.x.nbytes // 16) * 16 for s, _ in raws))
+            jobs, rpos = [], 0
+            for s, o in raws:
+                rb[rpos:rpos + s.x.nbytes] = s.x.reshape(-1).view(np.uint8)
+                jobs.append(ctx.resample_job(s.x, s.sr, rpos, o))
+                rpos += -(-s.x.nbytes // 16) * 16
         st['pack'] += time.perf_counter() - t_; t_ = time.perf_counter()
         ctx.set_signal(buf[:pos])
+        if raws:
+            ctx.resample(rb[:rpos], jobs)            # one launch for every resampled file of the pass, into the signal above
         ctx.sidekit()
         loge = ctx.get_loge()
         st['features'] += time.perf_counter() - t_; t_ = time.perf_counter()
@@ -259,7 +288,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
     items = [(i, src) for i, src in enumerate(linput) if not (skip and i in skip)]
     dec_q = queue.Queue(maxsize=4 * batch_files)
     budget = _AudioBudget(2 * batch_seconds * 16000)        # decoded audio waiting for the packer: <= 2 super-batches
-    _decode_stage(items, seg.ffmpeg, nbtry, trydelay, dec_q, decode_threads, budget)
+    _decode_stage(items, seg.ffmpeg, nbtry, trydelay, dec_q, decode_threads, budget, getattr(seg, 'resample', False))
     batch_q = queue.Queue(maxsize=max(2, workers))
     lock = threading.Lock()
     failure = []
@@ -276,7 +305,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                     break
                 i, src, sig, err = it
                 if sig is not None:
-                    budget.release(sig.size)
+                    budget.release(_held(sig))
                 if failure:                                        # a worker failed: drain the decoders, pack nothing more
                     continue
                 if sig is None:
@@ -286,7 +315,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                     except BaseException as exc:                   # noqa: B902
                         failure.append(exc)
                     continue
-                if sig.dtype != np.int16 or sig.size < MIN_SAMPLES:
+                if (not isinstance(sig, S.RawSource) and sig.dtype != np.int16) or sig.size < MIN_SAMPLES:
                     batch_q.put(('single', i, src, sig))
                     continue
                 cur.idx.append(i); cur.sigs.append(sig); cur.names.append(src)
@@ -308,7 +337,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                 if it is None:
                     break
                 if it[2] is not None:
-                    budget.release(it[2].size)
+                    budget.release(_held(it[2]))
         finally:
             for _ in range(workers):
                 batch_q.put(None)

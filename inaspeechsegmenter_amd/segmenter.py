@@ -24,7 +24,7 @@ import numpy as np
 from . import _native
 from . import tables
 from . import keras_model
-from .io import decode_pcm
+from .io import decode_pcm, decode_source, _check_no_ffmpeg, _to_float
 from .export_funcs import seg2csv, seg2textgrid
 
 _MODEL_DIRS = ('/root/.keras/inaSpeechSegmenter/', os.path.expanduser('~/.keras/inaSpeechSegmenter/'))
@@ -284,19 +284,48 @@ def _ensure_resident(ctx, mspec):
     return m.shape[0]
 
 
-def _media2feats(medianame, start_sec, stop_sec, ffmpeg, ctx=None):
+class RawSource:
+    """A WAV at another rate or channel count, as stored, for the device resampler (Segmenter(ffmpeg=None, resample=True)).
+    `size` is its length once resampled to 16 kHz, so it stands where a decoded signal's `size` is read."""
+    __slots__ = ('x', 'sr', 'size')
+
+    def __init__(self, x, sr):
+        from . import resample
+        self.x, self.sr = np.ascontiguousarray(x), sr
+        self.size = resample.out_len(x.shape[0], sr)
+
+
+def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False):
+    """decode_pcm's 16 kHz mono samples; with `resample` (ffmpeg=None only) a WAV at another rate or with several channels
+    comes back as a RawSource instead of failing (16 kHz mono files are read exactly as decode_pcm reads them)."""
+    if not resample:
+        return decode_pcm(medianame, start_sec, stop_sec, ffmpeg)
+    from . import resample as R
+    _check_no_ffmpeg(medianame, start_sec, stop_sec)
+    x, sr = decode_source(medianame)
+    if sr == R.SR_OUT and x.ndim == 1:
+        return np.ascontiguousarray(x) if x.dtype == np.int16 else np.ascontiguousarray(_to_float(x, np.float32))
+    R.check_rate(sr)
+    return RawSource(x, sr)
+
+
+def _media2feats(medianame, start_sec, stop_sec, ffmpeg, ctx=None, resample=False):
     """segmenter.py:53-67 on the device: returns (mspec, loge, difflen) where mspec is a
     `_Resident` handle when a context is given (the (T,24) array stays in HBM)."""
     if ctx is None:
         raise _native.NativeError("feature extraction needs a device context (no CPU path)")
-    sig = decode_pcm(medianame, start_sec, stop_sec, ffmpeg)
+    sig = _load_source(medianame, start_sec, stop_sec, ffmpeg, resample)
     return _sig2feats(ctx, sig, medianame)
 
 
 def _sig2feats(ctx, sig, medianame='<signal>'):
+    """sig: 16 kHz mono samples (uploaded), or a RawSource (resampled on the device into the resident signal)."""
     if sig.size < 400:
         raise ValueError(f"media {medianame}: {sig.size} samples, less than one 25 ms analysis window")
-    ctx.set_signal(sig)
+    if isinstance(sig, RawSource):
+        ctx.resample_signal(sig.x, sig.sr)
+    else:
+        ctx.set_signal(sig)
     nframes = ctx.sidekit()
     loge = ctx.get_loge()
     difflen = 0
@@ -312,14 +341,21 @@ def _sig2feats(ctx, sig, medianame='<signal>'):
 
 class Segmenter:
     def __init__(self, vad_engine='smn', detect_gender=True, ffmpeg='ffmpeg', batch_size=32, energy_ratio=0.03,
-                 device=0, models=None):
+                 device=0, models=None, resample=False):
         """Load the networks onto one MI355X.
 
         vad_engine / detect_gender / ffmpeg / batch_size / energy_ratio: as segmenter.py:208-247
         (same assertions, same "ffmpeg program not found" exception).
         device: HIP device ordinal.  models: None -> Keras files from ~/.keras/inaSpeechSegmenter
         (remote_utils.py search path); 'synthetic' -> seeded stand-in weights; or a dict
-        {model_fname: (layers, in_shape)}."""
+        {model_fname: (layers, in_shape)}.
+        resample (extension, ffmpeg=None only): WAV files at other integer rates (4 000 - 384 000 Hz) or with several
+        channels are downmixed, resampled to 16 kHz and quantised to PCM16 on the device (resample.py states the
+        arithmetic) instead of failing; 16 kHz mono files are read as without it."""
+        if resample and ffmpeg is not None:
+            raise ValueError(f'resample=True reads WAV files without ffmpeg: pass ffmpeg=None (ffmpeg={ffmpeg!r} already '
+                             f'resamples)')
+        self.resample = bool(resample)
         if ffmpeg is not None:
             if shutil.which(ffmpeg) is None:
                 raise (Exception("""ffmpeg program not found"""))
@@ -406,9 +442,17 @@ class Segmenter:
         mspec, loge, difflen = _sig2feats(self.ctx, np.ascontiguousarray(sig))
         return self.segment_feats(mspec, loge, difflen, start_sec)
 
+    def load_pcm(self, medianame):
+        """The 16 kHz mono samples the front end reads for `medianame` (decode_pcm's int16 or float32 array); with
+        resample=True a WAV at another rate or channel count is resampled on the device and its PCM16 copied back."""
+        sig = _load_source(medianame, None, None, self.ffmpeg, self.resample)
+        if isinstance(sig, RawSource):
+            return self.ctx.get_signal_pcm16(0, self.ctx.resample_signal(sig.x, sig.sr))
+        return sig
+
     def __call__(self, medianame, start_sec=None, stop_sec=None):
         """segmenter.py:279-294."""
-        mspec, loge, difflen = _media2feats(medianame, start_sec, stop_sec, self.ffmpeg, self.ctx)
+        mspec, loge, difflen = _media2feats(medianame, start_sec, stop_sec, self.ffmpeg, self.ctx, self.resample)
         if start_sec is None:
             start_sec = 0
         return self.segment_feats(mspec, loge, difflen, start_sec)

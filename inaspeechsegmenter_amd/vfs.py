@@ -23,7 +23,7 @@ import time
 import numpy as np
 
 from . import _native, keras_model
-from .io import decode_pcm, media2sig16kmono
+from .io import decode_pcm, media2sig16kmono, _to_float
 from .segmenter import Segmenter, locate_model
 from .vbx import FeatureExtractor, VBxExtractor, SR, frame_count, pcm16_of, plan_windows
 
@@ -142,11 +142,13 @@ def _load_resnet_params(path):
 
 
 class VoiceFemininityScoring:
-    def __init__(self, gd_model_criteria='bgc', backend='onnx', ffmpeg='ffmpeg', device=0, models=None):
+    def __init__(self, gd_model_criteria='bgc', backend='onnx', ffmpeg='ffmpeg', device=0, models=None, resample=False):
         """gd_model_criteria / backend: as vbx_segmenter.py:97-127.  models: None -> files from the
         remote_utils search path (final.onnx for the x-vector net, read by onnx_reader.py; raw_81.pth if only that exists);
         'synthetic' -> seeded stand-ins; or a dict {'resnet': state_dict-like, 'mlp': (layers, in_shape),
-        'vad': the `models` argument of the inner Segmenter (optional; default = its Keras files)}."""
+        'vad': the `models` argument of the inner Segmenter (optional; default = its Keras files)}.
+        resample: passed on to the inner Segmenter (ffmpeg=None only): WAVs at other rates / channel counts are turned into
+        16 kHz mono PCM16 on the device and scored as if ffmpeg had produced that PCM."""
         assert backend in ['onnx'], "Backend should be 'onnx' (or 'pytorch' if uncommented)."
         assert gd_model_criteria in ['bgc', 'vfp'], "Gender detection model Criteria must be 'bgc' (default) or 'vfp'"
         gd_model, self.vad_thresh = ('interspeech2023_all.hdf5', 0.7) if gd_model_criteria == 'bgc' else ('interspeech2023_cvfr.hdf5', 0.62)
@@ -157,7 +159,9 @@ class VoiceFemininityScoring:
             vad_models = models.get('vad')                # {'keras_speech_music_noise_cnn.hdf5': (layers, in_shape)} or 'synthetic'
         else:
             vad_models = None
-        self.vad = Segmenter(vad_engine='smn', detect_gender=False, ffmpeg=ffmpeg, device=device, models=vad_models)
+        self.vad = Segmenter(vad_engine='smn', detect_gender=False, ffmpeg=ffmpeg, device=device, models=vad_models,
+                             resample=resample)
+        self.resample = self.vad.resample
         self.ctx = self.vad.ctx
         if models == 'synthetic':
             rng = np.random.default_rng(23)
@@ -200,9 +204,15 @@ class VoiceFemininityScoring:
     def __call__(self, fpath):
         """-> (score, speech_duration, nb_vectors)  (vbx_segmenter.py:147-202)."""
         basename = os.path.splitext(os.path.basename(fpath))[0]
-        signal = media2sig16kmono(fpath, ffmpeg=self.ffmpeg, dtype='float64')
+        if self.resample:                                 # one device decode: the VAD and the front end read the same PCM
+            a = self.vad.load_pcm(fpath)
+            signal = _to_float(a, np.float64) if a.dtype == np.int16 else a.astype(np.float64)   # = media2sig16kmono
+            vad = self.vad.segment_signal(a)
+        else:
+            signal = media2sig16kmono(fpath, ffmpeg=self.ffmpeg, dtype='float64')
+            vad = None
         duration = len(signal) / SR
-        speech = speech_intervals(self.vad(fpath))
+        speech = speech_intervals(self.vad(fpath) if vad is None else vad)
         speech_dur = speech_duration(speech)
         if not speech_dur:
             return None, speech_dur, 0
@@ -227,7 +237,7 @@ class VoiceFemininityScoring:
     def _decode(self, fpath, nbtry, trydelay):
         for itry in range(nbtry):
             try:
-                return decode_pcm(fpath, ffmpeg=self.ffmpeg)
+                return self.vad.load_pcm(fpath) if self.resample else decode_pcm(fpath, ffmpeg=self.ffmpeg)
             except _native.NativeError:
                 raise
             except Exception:

@@ -76,6 +76,49 @@ int iss_signal_f32(iss_ctx* ctx, const float* sig, int64_t n);
 int iss_signal_pcm16_device(iss_ctx* ctx, const void* dev_pcm, int64_t n);
 int iss_signal_pcm16_device_stream(iss_ctx* ctx, const void* dev_pcm, int64_t n, void* producer_stream);
 
+/* WAV sources at other rates / channel counts without ffmpeg: replaces the 16 kHz-only assertion of the ffmpeg-free
+ * read (io.py:53-55) with what `ffmpeg -ac 1 -ar 16000 -acodec pcm_s16le` is asked for, on the device:
+ *   m[j] = mean over channels of the stored sample scaled like libsndfile (u8 (x-128)/128, i16 x/2^15, i32 x/2^31,
+ *          f32 / f64 as stored), float64, channels summed in order then divided by their count;
+ *   y[i] = sum over ascending j of taps[i*down + hl - j*up] * m[j]   (taps in [0, 2*hl], j in [0, frames_in), float64,
+ *          no fused multiply-add), i < frames_out = ceil(frames_in*up/down): scipy.signal.resample_poly(m, up, down);
+ *   pcm  = clip(rint(y * 32768), -32768, 32767)   (round half to even, saturate: ffmpeg's pcm_s16le).
+ * The filter of a (up, down) pair is registered once per context: `taps` = 2*hl+1 float64, hl = (ntaps-1)/2
+ * (inaspeechsegmenter_amd/resample.py designs it); a second registration of the same pair returns the same id and
+ * copies nothing.  ntaps 1 with up = down = 1 is the identity (16 kHz sources with several channels).               */
+#define ISS_RS_U8   0
+#define ISS_RS_I16  1
+#define ISS_RS_I32  2     /* 32-bit PCM, and 24-bit PCM widened to x << 8 */
+#define ISS_RS_F32  3
+#define ISS_RS_F64  4
+typedef struct {
+    int64_t src_offset;   /* byte offset of the job's first stored sample in `src` (a multiple of the sample size)   */
+    int64_t frames_in;    /* frames (samples per channel) of the source, >= 1                                        */
+    int32_t channels;     /* interleaved channels, 1 .. 1024                                                         */
+    int32_t format;       /* ISS_RS_*                                                                                */
+    int32_t filter;       /* id returned by iss_resample_filter                                                      */
+    int32_t reserved;     /* 0                                                                                       */
+    int64_t dst_offset;   /* first output sample in the resident signal                                              */
+    int64_t frames_out;   /* must be ceil(frames_in * up / down)                                                     */
+} iss_resample_job;
+int iss_resample_filter(iss_ctx* ctx, int32_t up, int32_t down, const double* taps, int64_t ntaps, int32_t* id_out);
+/* One H2D copy of `src` (src_bytes bytes: the stored samples of every job) and ONE kernel launch for all jobs, the
+ * PCM16 output written into the resident signal at each job's dst_offset.
+ *   n_signal >= 0: the resident signal becomes a new zero-filled PCM16 signal of n_signal samples first (a call on its own);
+ *   n_signal <  0: the jobs write into the PCM16 signal uploaded by the last iss_signal_pcm16 (a packed batch with room
+ *                  left for the resampled files); every sample outside the jobs' ranges stays as uploaded.
+ * Then iss_sidekit runs as on any uploaded signal.  `src` is read asynchronously: from page-locked memory
+ * (iss_host_alloc) it must stay unchanged until the next synchronising call (iss_get_loge, iss_synchronize, ...).
+ * ISS_EINVAL: bad format or channel count, unknown filter, frames_out not ceil(frames_in*up/down), a source range outside
+ * `src` or misaligned, a destination range outside the signal, or two destination ranges that overlap.
+ * ISS_ESTATE: n_signal < 0 without a resident PCM16 signal of the context's own (iss_signal_pcm16).                  */
+int iss_resample_pcm16(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
+                       int64_t n_signal);
+/* Samples [offset, offset + n) of the resident PCM16 signal back to the host (e.g. the output of iss_resample_pcm16).  */
+int iss_get_signal_pcm16(iss_ctx* ctx, int16_t* out, int64_t offset, int64_t n);
+/* Resample kernel launches and jobs since the context was created.                                                   */
+int iss_resample_stats(iss_ctx* ctx, int64_t* launches, int64_t* jobs);
+
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */
 int iss_host_alloc(iss_ctx* ctx, size_t bytes, void** out);

@@ -3,7 +3,8 @@
 
 Same options as the reference's scripts/ina_speech_segmenter.py (-i -o -s -d -g -b -e -r, :45-53) and the
 same output naming (<basename>.<format> inside the output directory, :80-84).  Extra: --models synthetic
-(seeded stand-in weights, for machines without the Keras release assets) and multi-GPU operation: start it
+(seeded stand-in weights, for machines without the Keras release assets), --resample (with -b None: WAV at any rate /
+channel count, downmixed and resampled to 16 kHz on the GPU) and multi-GPU operation: start it
 under `python -m torch.distributed.run --nproc-per-node N` and the inputs are dealt to the N GPUs.
 """
 import argparse
@@ -37,14 +38,19 @@ def build_parser():
     ap.add_argument('-e', '--export_format', choices=['csv', 'textgrid'], default='csv')
     ap.add_argument('-r', '--energy_ratio', type=float, default=0.03)
     ap.add_argument('--models', default=None, help="'synthetic' = seeded stand-in weights")
+    ap.add_argument('--resample', action='store_true',
+                    help='with -b None: downmix and resample WAV files of other rates / channel counts to 16 kHz mono on the GPU')
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     ffmpeg = None if args.ffmpeg_binary.lower() in ('none', '') else args.ffmpeg_binary
+    if args.resample and ffmpeg is not None:
+        build_parser().error('--resample needs -b None (ffmpeg already resamples)')
     if ffmpeg is None:
-        print('Disabling ffmpeg. Make sure your audio files are already sampled at 16kHz.')
+        print('Disabling ffmpeg. ' + ('WAV files at other rates or with several channels are resampled on the GPU.' if args.resample
+                                      else 'Make sure your audio files are already sampled at 16kHz.'))
     inputs = []
     for pat in args.input:
         inputs += [pat] if pat.startswith('http') else sorted(glob.glob(pat))
@@ -57,7 +63,7 @@ def main(argv=None):
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     from inaspeechsegmenter_amd import Segmenter
     seg = Segmenter(vad_engine=args.vad_engine, detect_gender=args.detect_gender, ffmpeg=ffmpeg, batch_size=args.batch_size,
-                    energy_ratio=args.energy_ratio, device=local_rank, models=args.models)
+                    energy_ratio=args.energy_ratio, device=local_rank, models=args.models, resample=args.resample)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         if world == 1:

@@ -3,7 +3,8 @@
 
 Scores every input file and writes one TSV: path, score, speech duration, number of x-vectors (a file that could not be
 read gets its error message instead).  Argument handling as scripts/ina_speech_segmenter_amd.py: -i takes paths or glob
-patterns, -b None reads 16 kHz mono WAV directly, --models synthetic runs seeded stand-in weights.
+patterns, -b None reads 16 kHz mono WAV directly (with --resample: WAV at any rate / channel count, resampled on the GPU),
+--models synthetic runs seeded stand-in weights.
 """
 import argparse
 import glob
@@ -24,6 +25,8 @@ def build_parser():
     ap.add_argument('-b', '--ffmpeg_binary', default='ffmpeg', help="ffmpeg binary; 'None' reads 16 kHz mono WAV directly")
     ap.add_argument('--batch_seconds', type=float, default=3600, help='audio held on the device per batch (seconds)')
     ap.add_argument('--models', default=None, help="'synthetic' = seeded stand-in weights")
+    ap.add_argument('--resample', action='store_true',
+                    help='with -b None: downmix and resample WAV files of other rates / channel counts to 16 kHz mono on the GPU')
     return ap
 
 
@@ -37,14 +40,17 @@ def expand_inputs(patterns):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     ffmpeg = None if args.ffmpeg_binary.lower() in ('none', '') else args.ffmpeg_binary
+    if args.resample and ffmpeg is not None:
+        build_parser().error('--resample needs -b None (ffmpeg already resamples)')
     if ffmpeg is None:
-        print('Disabling ffmpeg. Make sure your audio files are already sampled at 16kHz.')
+        print('Disabling ffmpeg. ' + ('WAV files at other rates or with several channels are resampled on the GPU.' if args.resample
+                                      else 'Make sure your audio files are already sampled at 16kHz.'))
     inputs = expand_inputs(args.input)
     assert len(inputs) > 0, 'No media selected for analysis! Bad values provided to -i (%s)' % args.input
     odir = os.path.dirname(os.path.abspath(args.output))
     assert os.access(odir, os.W_OK), 'Directory %s is not writable!' % odir
     from inaspeechsegmenter_amd.vfs import VoiceFemininityScoring
-    vfs = VoiceFemininityScoring(gd_model_criteria=args.criteria, ffmpeg=ffmpeg, models=args.models)
+    vfs = VoiceFemininityScoring(gd_model_criteria=args.criteria, ffmpeg=ffmpeg, models=args.models, resample=args.resample)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         res = vfs.batch_process(inputs, output_csv=args.output, batch_seconds=args.batch_seconds, verbose=True)
