@@ -22,6 +22,7 @@
 //   softmax_kernel       softmax over channels
 //   statpool_kernel      mean || std over time                           (resnet.py:123-127)
 #include <map>
+#include <numeric>
 #include "conv_common.h"
 #include "conv_ws.h"
 #include "conv_wq.h"
@@ -1391,12 +1392,13 @@ inline bool fp_shape_compiled(int kh, int kw) {
 }
 
 // Host replica of the device's row mapping / footprint arithmetic: does every 128-row tile of this
-// launch touch at most FPIX pixels?  The pattern is periodic in the sample index (period <= BM
-// samples), so tiles covering the first BM + 2 samples decide.
-int footprint_pixels(const ConvArgs& a, int TM = BM) {      // largest pixel span of a TM-row tile of this launch (INT_MAX: irregular)
+// layer touch at most FPIX pixels?  Tiles start at multiples of TM and the pattern repeats every sample, so the tiles
+// starting in the first lcm(rows per sample, TM) rows decide.  The answer is that of a launch over any number of samples:
+// the call's own count (a.M) is not used, so a call of a few windows, whose only tile ends early, takes the kernel a large
+// call takes, and a window's result does not depend on how many windows share its pass.
+int footprint_pixels(const ConvArgs& a, int TM = BM) {      // largest pixel span of a TM-row tile of this layer (INT_MAX: irregular)
     const long long rows_per_sample = (long long)a.Hq * a.Wq * a.pp;
-    const long long samples = a.M / rows_per_sample;
-    const long long lim_rows = std::min<long long>(a.M, rows_per_sample * std::min<long long>(samples, TM + 2));
+    const long long lim_rows = std::lcm(rows_per_sample, (long long)TM);
     auto pix_of = [&](long long m, int ky, int kx) {
         long long q = m;
         int dy = 0, dx = 0;
@@ -1410,7 +1412,7 @@ int footprint_pixels(const ConvArgs& a, int TM = BM) {      // largest pixel spa
     };
     long long worst = 0;
     for (long long m0 = 0; m0 < lim_rows; m0 += TM) {
-        const long long m_last = std::min<long long>(m0 + TM, a.M) - 1;
+        const long long m_last = m0 + TM - 1;
         const long long lo = pix_of(m0, 0, 0), hi = pix_of(m_last, a.H_k - 1, a.kw - 1);
         worst = std::max<long long>(worst, hi - lo + 1);
         // rows inside the tile never reach below lo / above hi (row-major or pool-window-major order); check anyway
@@ -1547,7 +1549,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
             a.Cin % F2_CH != 0 || a.Cin < 2 * F2_CH || a.M >= (1ll << 31) || (long long)bc * a.img_stride * 4 >= (1ll << 32)) return -1;
         if (R[ISS_C_BOFF] < 0 || a.act != 1 || R[ISS_C_PSOFF] >= 0 || !ws_recip_exact(a.W, issk::WQ3_PIX + a.W)) return -1;
         {
-            const long long key = ((long long)q << 32) | (unsigned)bc | (1ll << 60);
+            const long long key = ((long long)q << 32) | (1ll << 60);
             auto it = n.fp_pix.find(key);
             if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
             if (it->second > WS_PIX2) return -1;
@@ -1556,7 +1558,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
         if (a.pp == 1 && a.M * (long long)a.Cout * 4 < 0xFFF00000ll) kind = 0;
         else if (a.pp == 2 && a.ph == 2 && a.poolkind == 0 && (a.M / 2) * (long long)a.Cout * 4 < 0xFFF00000ll) kind = 1;
         if (kind < 0) return -1;
-        const long long key = ((long long)q << 32) | (unsigned)bc | (1ll << 58);
+        const long long key = ((long long)q << 32) | (1ll << 58);
         auto it = n.fp_pix.find(key);
         if (it == n.fp_pix.end()) {
             int tmr = 0;
@@ -1736,7 +1738,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
         }
         bool fp = false;                               // LDS-footprint kernel usable
         if (x3 && a.mode == 0 && fp_shape_compiled(a.H_k, a.kw) && a.M < (1ll << 31)) {
-            const long long key = ((long long)r << 32) | (unsigned)bc;
+            const long long key = ((long long)r << 32);
             auto it = n.fp_pix.find(key);
             if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a)).first;
             fp = it->second <= FPIX;
@@ -1751,7 +1753,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
         const bool pool1 = ph1 * pw1 != 1;
         if (!no_ws && fp && pend >= 0 && a.H_k * a.kw >= 8 && a.H_k * a.kw <= WS_MAXNT && ws_shape_compiled(a.H_k, a.kw) &&
             a.Cin % F2_CH == 0 && a.H * a.W >= WS_PIX + 64 + (a.pt_ + 1) * a.W && ws_recip_exact(a.W, a.H * a.W + WS_PIX + a.W)) {
-            const long long key = ((long long)r << 32) | (unsigned)bc | (1ll << 62);
+            const long long key = ((long long)r << 32) | (1ll << 62);
             auto it = n.fp_pix.find(key);
             if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
             ws = it->second <= WS_PIX && n.prog[(size_t)pend * ISS_PROG_COLS + ISS_C_PSOFF] < 0;     // (a post-activation affine of the
@@ -1764,7 +1766,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
             ws_recip_exact(a.W, a.H * a.W + WS_PIX2 + a.W) && n.prog[(size_t)pend * ISS_PROG_COLS + ISS_C_PSOFF] < 0) {
             // rows per tile: the largest multiple of 4 (<= 512, >= 320) whose footprint fits the 1024 pixels -- a 512-row tile of a
             // pooled 59 x 14 output under a 7-row filter spans 1036 pixels, 496 rows 1002 (ConvArgs::tmr; the rest of the tile idles)
-            const long long key = ((long long)r << 32) | (unsigned)bc | (1ll << 57);
+            const long long key = ((long long)r << 32) | (1ll << 57);
             auto it = n.fp_pix.find(key);
             if (it == n.fp_pix.end()) {
                 // ... and reaches into at most ONE following window (the fetch decomposes a footprint position into two windows)
@@ -1787,7 +1789,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
             a.sh == 1 && a.sw == 1 && issk::epi_is_pool_relu(a) && a.Cin % F2_CH == 0 && a.Cin >= 2 * F2_CH && a.M < (1ll << 31) &&
             a.H * a.W >= WS_PIX + 64 + a.W && ws_recip_exact(a.W, a.H * a.W + WS_PIX + a.W) &&
             n.prog[(size_t)pend * ISS_PROG_COLS + ISS_C_PSOFF] < 0) {
-            const long long key = ((long long)r << 32) | (unsigned)bc | (1ll << 62);
+            const long long key = ((long long)r << 32) | (1ll << 62);
             auto it = n.fp_pix.find(key);
             if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
             ws_f32 = it->second <= WS_PIX;
@@ -1812,7 +1814,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
         if (!no_ws && !no_ws3 && pend < 0 && (x3 || nh2_f32) && a.mode == 0 && (!padded || nh2_pad_ok) && a.sh == 1 && a.sw == 1 && !a.res && a.Cout % (2 * BN) == 0 &&
             issk::iss_ws_nh2_compiled(a.H_k, a.kw) && a.Cin % F2_CH == 0 && a.M < (1ll << 31) &&
             (long long)bc * a.img_stride * 4 < (1ll << 32)) {
-            const long long key = ((long long)r << 32) | (unsigned)bc | (1ll << 60);
+            const long long key = ((long long)r << 32) | (1ll << 60);
             auto it = n.fp_pix.find(key);
             if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
             ws_nh2 = it->second <= WS_PIX2;
@@ -1822,7 +1824,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
         if (!no_ws && !fp && pend < 0 && x3 && a.mode == 0 && padded && a.sh == 1 && a.sw == 1 && a.pp == 1 && a.Cout % 4 == 0 &&
             !a.res && issk::iss_ws_plain_compiled(a.H_k, a.kw) && a.Cin % F2_CH == 0 && a.M < (1ll << 31) &&
             (long long)bc * a.img_stride * 4 < (1ll << 32)) {
-            const long long key = ((long long)r << 32) | (unsigned)bc | (1ll << 61);
+            const long long key = ((long long)r << 32) | (1ll << 61);
             auto it = n.fp_pix.find(key);
             if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
             ws_plain = it->second <= WS_PIX;
@@ -1834,7 +1836,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
             issk::iss_ws_plain_compiled(a.H_k, a.kw) && a.Cin % F2_CH == 0 && a.Cin >= 2 * F2_CH && a.M < (1ll << 31) &&
             (long long)bc * a.img_stride * 4 < (1ll << 32) &&
             ((a.pp == 1 && a.Cout % 4 == 0 && issk::epi_is_simple_tr(a)) || (a.pp > 1 && issk::epi_is_pool_relu(a)))) {
-            const long long key = ((long long)r << 32) | (unsigned)bc | (1ll << 56);
+            const long long key = ((long long)r << 32) | (1ll << 56);
             auto it = n.fp_pix.find(key);
             if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
             ws_plain_u = it->second <= WS_PIX;
@@ -1991,7 +1993,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
                 else if (a.pp == 2 && a.ph == 2 && a.poolkind == 0 && (a.M / 2) * (long long)a.Cout * 4 < 0xFFF00000ll) wq3_kind = 1;
             }
             if (wq3_kind >= 0) {
-                const long long key = ((long long)r << 32) | (unsigned)bc | (1ll << 58);
+                const long long key = ((long long)r << 32) | (1ll << 58);
                 auto it = n.fp_pix.find(key);
                 if (it == n.fp_pix.end()) {
                     int tmr = 0;
@@ -2069,7 +2071,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
                 issk::iss_wq_compiled(a.H_k, a.kw) && a.sh == 1 && a.sw == 1 && a.Cin >= 2 * F2_CH && a.M % 4 == 0 &&
                 (a.M / 4) * (long long)a.Cout * 4 < 0xFFF00000ll && a.Cout <= 256) {
                 // rows per tile: the largest multiple of 4 (<= 512) whose footprint fits the kernel's 800 pixels
-                const long long key = ((long long)r << 32) | (unsigned)bc | (1ll << 59);
+                const long long key = ((long long)r << 32) | (1ll << 59);
                 auto it = n.fp_pix.find(key);
                 if (it == n.fp_pix.end()) {
                     int tmr = 0;

@@ -49,7 +49,7 @@ struct IssNet {
     std::vector<int64_t> buf_elems;
     int in_h = 0, in_w = 0, in_c = 0, out_dim = 0;
     double flops_per_sample = 0;
-    std::unordered_map<long long, int> fp_pix;   // (row << 32 | samples) -> pixels a 128-row tile's LDS footprint spans
+    std::unordered_map<long long, int> fp_pix;   // (row << 32 | kernel family bit) -> largest LDS footprint of a tile (or its rows)
     // precision guard (iss_set_precision_guard / iss_cnn_precision_info)
     int prec_override = -1;               // -1: the context's mode; else ISS_PREC_* for this network only
     int guard_state = 0;                  // ISS_GUARD_*
