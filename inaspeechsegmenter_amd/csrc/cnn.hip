@@ -1306,7 +1306,17 @@ extern "C" int iss_cnn_load_shared(iss_ctx* c, int id, int src, const int32_t* p
 extern "C" int iss_set_precision(iss_ctx* c, int mode) {
     if (!c) return ISS_EINVAL;
     if (mode != ISS_PREC_BF16X3 && mode != ISS_PREC_F32 && mode != ISS_PREC_F16X3) return iss_fail(c, ISS_EINVAL, "iss_set_precision: unknown mode %d", mode);
+    if (mode == c->precision) return ISS_OK;
     c->precision = mode;
+    // the guard's decision (or its FIXED for a first call in exact f32) was about the old mode: every network the caller has not
+    // pinned follows the new one and is probed again on its next iss_cnn_probs call
+    for (IssNet& n : c->nets) {
+        if (!n.loaded || n.prec_by_caller) continue;
+        n.prec_override = -1;
+        n.guard_state = ISS_GUARD_PENDING;
+        n.guard_dlogp = n.guard_dlogp_chosen = -1.f;
+        n.guard_slots = 0;
+    }
     return ISS_OK;
 }
 
@@ -1322,6 +1332,7 @@ extern "C" int iss_cnn_set_net_precision(iss_ctx* c, int id, int mode) {
     if (mode != -1 && mode != ISS_PREC_BF16X3 && mode != ISS_PREC_F32 && mode != ISS_PREC_F16X3) return iss_fail(c, ISS_EINVAL, "iss_cnn_set_net_precision: unknown mode %d", mode);
     if (!c->nets[id].loaded) return iss_fail(c, ISS_ESTATE, "net %d not loaded", id);
     c->nets[id].prec_override = mode;
+    c->nets[id].prec_by_caller = mode != -1;
     c->nets[id].guard_state = mode == -1 ? ISS_GUARD_PENDING : ISS_GUARD_FIXED;
     return ISS_OK;
 }
@@ -1527,8 +1538,27 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
     int hl_out_row = -1;                                         // the row conv_row has just launched with a CHL output ...
     unsigned hl_out_np = 0;                                      // ... and its plane size
     const bool no_hl = (c->diag & ISS_DIAG_NO_HL) != 0;
+    // (fp16 mode) a small layer -- under 0.5 % of the network's arithmetic -- that no fp16 kernel takes: exact f32.  conv_row(r, pend, ..)
+    // launches by it, and wq3_plan asks it too: a producer must not hand the CHL layout to a row that then runs an f32 kernel
+    auto small_row_of = [&](int r, int pend, bool* f16_dense_pw_out) -> bool {
+        const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
+        const double row_flops = 2.0 * R[ISS_C_KH] * R[ISS_C_KW] * R[ISS_C_CIN] * (double)R[ISS_C_COUT] * R[ISS_C_HO] * R[ISS_C_WO];
+        const bool small_cand = f16mode && pend < 0 && row_flops < 0.005 * net_flops && row_flops < 2e6 &&     // (and small in absolute terms: a
+                                R[ISS_C_INMODE] == 0 && !can_defer(r);                                        //  ResNet-101 has 105 layers under 1 %)
+        // ... unless it is a dense layer of some width (a 512 -> 512 head: 0.5 MFLOP per window, 66 TFLOP/s on conv_igemm_kernel, 5 % of
+        // such a net's step): conv_x3_pw_kernel has an fp16 form for any K, so it takes the layer instead of the streaming kernels
+        int ph, pw;
+        fused_pool_of(R, ph, pw);
+        const bool f16_dense_pw = small_cand && row_flops >= 2.5e5 && R[ISS_C_KH] == 1 && R[ISS_C_KW] == 1 && R[ISS_C_H] == 1 && R[ISS_C_W] == 1 &&
+                                  R[ISS_C_HO] == 1 && R[ISS_C_WO] == 1 && ph * pw == 1 && R[ISS_C_SH] == 1 && R[ISS_C_SW] == 1 && R[ISS_C_PT] == 0 &&
+                                  R[ISS_C_PL] == 0 && R[ISS_C_COUT] % 4 == 0 && R[ISS_C_CIN] % XBK == 0 && n.kpad[r] == R[ISS_C_CIN] && R[ISS_C_RES] < 0 &&
+                                  (c->diag & ISS_DIAG_NO_PW) == 0;
+        if (f16_dense_pw_out) *f16_dense_pw_out = f16_dense_pw;
+        return small_cand && !f16_dense_pw;
+    };
     auto wq3_plan = [&](int q, int* tmr_out) -> int {            // -1, or the kind (0: bias + relu, 1: relu + 2 x 1 max-pool)
         if (q < 0 || q >= n.nrows || !x3mode) return -1;
+        if (small_row_of(q, -1, nullptr)) return -1;             // (a CHL consumer has no deferred first layer in front: pend = -1)
         if (c->diag & (ISS_DIAG_NO_WS | ISS_DIAG_NO_WS3 | ISS_DIAG_NO_WQ)) return -1;
         const int32_t* R = &n.prog[(size_t)q * ISS_PROG_COLS];
         if (R[ISS_C_OP] != ISS_OP_CONV || R[ISS_C_INMODE] != 0 || R[ISS_C_IN] == ISS_BUF_INPUT || R[ISS_C_RES] >= 0 || R[ISS_C_DUALW] != 0) return -1;
@@ -1638,17 +1668,8 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
         a.act = R[ISS_C_ACT]; a.Kpad = n.kpad[r];
         a.M = (long long)bc * a.Hq * a.Wq * a.pp;
         const bool patch = R[ISS_C_INMODE] == 1;
-        // (fp16 mode) a small layer -- under 0.5 % of the network's arithmetic -- that no fp16 kernel takes: exact f32
-        const double row_flops = 2.0 * R[ISS_C_KH] * R[ISS_C_KW] * R[ISS_C_CIN] * (double)R[ISS_C_COUT] * R[ISS_C_HO] * R[ISS_C_WO];
-        const bool small_cand = f16mode && pend < 0 && row_flops < 0.005 * net_flops && row_flops < 2e6 &&     // (and small in absolute terms: a
-                                R[ISS_C_INMODE] == 0 && !can_defer(r);                                        //  ResNet-101 has 105 layers under 1 %)
-        // ... unless it is a dense layer of some width (a 512 -> 512 head: 0.5 MFLOP per window, 66 TFLOP/s on conv_igemm_kernel, 5 % of
-        // such a net's step): conv_x3_pw_kernel has an fp16 form for any K, so it takes the layer instead of the streaming kernels
-        const bool f16_dense_pw = small_cand && row_flops >= 2.5e5 && a.H_k == 1 && a.kw == 1 && a.H == 1 && a.W == 1 && R[ISS_C_HO] == 1 &&
-                                  R[ISS_C_WO] == 1 && a.pp == 1 && a.sh == 1 && a.sw == 1 && a.pt_ == 0 && a.pl_ == 0 && a.Cout % 4 == 0 && a.Cin % XBK == 0 &&
-                                  a.Kpad == a.Cin && !a.res &&
-                                  (c->diag & ISS_DIAG_NO_PW) == 0;
-        const bool small_row = small_cand && !f16_dense_pw;
+        bool f16_dense_pw = false;
+        const bool small_row = small_row_of(r, pend, &f16_dense_pw);
         const bool x3 = x3mode && !small_row;
         bool row_f16 = f16mode;                                  // cleared below where the launch has no fp16 form
         const bool in_is_hl = R[ISS_C_IN] != ISS_BUF_INPUT && hl_np.count(R[ISS_C_IN]) != 0;     // (only conv_x3_wq3h_kernel reads that layout)

@@ -52,6 +52,7 @@ struct IssNet {
     std::unordered_map<long long, int> fp_pix;   // (row << 32 | kernel family bit) -> largest LDS footprint of a tile (or its rows)
     // precision guard (iss_set_precision_guard / iss_cnn_precision_info)
     int prec_override = -1;               // -1: the context's mode; else ISS_PREC_* for this network only
+    bool prec_by_caller = false;          // prec_override came from iss_cnn_set_net_precision (else from the guard: iss_set_precision re-arms)
     int guard_state = 0;                  // ISS_GUARD_*
     float guard_dlogp = -1.f;             // max |log p(mode asked for) - log p(exact f32)| of the probe, -1 = never probed
     float guard_dlogp_chosen = -1.f;      // the same figure for the mode the network runs in after the probe

@@ -19,6 +19,7 @@ import shutil
 import warnings
 
 import threading
+import weakref
 import numpy as np
 
 from . import _native
@@ -167,24 +168,40 @@ class DnnSegmenter:
         """iss_cnn_probs (or, with async_out = (probs, finite) page-locked arrays, iss_cnn_probs_async) of this network on `ctx`.
         The library's precision guard (include/iss.h) decides a network's arithmetic at its first call PER CONTEXT; the device
         contexts of one Segmenter (its own and the pipeline workers') must not decide differently, so the first call anywhere
-        decides for all of them: it runs under a lock, and every other context is told the outcome before its first call."""
+        decides for all of them: it runs under a lock, and every other context is told the outcome before its first call.
+        The decision is about the mode the Segmenter's own context was asked for (its `precision`): when that changes, the decision
+        is dropped, every context that was told it follows its own mode again, and the next call anywhere decides anew.  Only a
+        probe's outcome ('passed' / 'escalated') is passed on; a 'fixed' first call (exact f32, or a caller's per-network
+        override) is nothing to agree on.  A change of the guard threshold alone does not reopen a decision."""
         def run():
             if async_out is None:
                 return ctx.cnn_probs(self.net_id, win_rows)
             return ctx.cnn_probs_async(self.net_id, win_rows, *async_out)
-        st = self.__dict__.setdefault('_mode_state', {'lock': threading.Lock(), 'mode': None, 'told': set()})
+        st = self.__dict__.setdefault('_mode_state', {'lock': threading.Lock(), 'mode': None, 'told': set(), 'asked': None,
+                                                      'pinned': weakref.WeakValueDictionary()})
         if not hasattr(ctx, 'cnn_precision_info'):             # (a test double of the device context)
             return run()
+        asked = getattr(self.__dict__.get('ctx') or ctx, 'precision', None)
+        asked = _native.PREC_F16X3 if asked is None else asked      # (None: never set, the library default)
+        if st['asked'] != asked:
+            with st['lock']:
+                if st['asked'] != asked:
+                    for c in list(st['pinned'].values()):      # (a context this method pinned follows its own mode again)
+                        if getattr(c, '_h', True) is not None:  # (a closed context: nothing to undo)
+                            c.cnn_set_net_precision(self.net_id, -1)
+                    st['pinned'].clear()
+                    st['told'].clear()
+                    st['mode'], st['asked'] = None, asked
         if st['mode'] is None:
             with st['lock']:
                 if st['mode'] is None:
                     out = run()
                     info = ctx.cnn_precision_info(self.net_id)
-                    if info['state'] != 'pending':
+                    if info['state'] in ('passed', 'escalated'):
                         st['mode'] = self._MODES[info['mode']]
                         st['told'].add(id(ctx))
-                    elif not _guard_on(ctx):
-                        st['mode'] = -1                        # guard off: nothing to agree on
+                    elif info['state'] == 'fixed' or not _guard_on(ctx):
+                        st['mode'] = -1                        # exact f32, the caller's own override, or the guard off: nothing to agree on
                     # (else the guard is on but compared no window -- e.g. all over -inf mel rows --: the decision stays open,
                     # the next call anywhere probes and decides for every context, this one included)
                     return out
@@ -193,6 +210,7 @@ class DnnSegmenter:
                 if id(ctx) not in st['told']:
                     if ctx.cnn_precision_info(self.net_id)['state'] == 'pending':
                         ctx.cnn_set_net_precision(self.net_id, st['mode'])
+                        st['pinned'][id(ctx)] = ctx
                     st['told'].add(id(ctx))
         return run()
 

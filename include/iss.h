@@ -262,18 +262,23 @@ int iss_set_precision(iss_ctx* ctx, int mode);
  * iss_cnn_probs / iss_cnn_probs_async call of a patch network in a split mode first runs up to 256 of the call's own windows
  * (four runs of consecutive slots spread over the list) in that mode and in exact f32, records max |log p_split - log p_f32| over
  * every class of every finite window, and -- when that exceeds `threshold` (default 5e-4, half the bound; a NaN, i.e. an activation
- * beyond fp16's range, always does) -- switches THIS network for the rest of its life: to the other split mode if that one passes
- * the same probe (the same speed), else to ISS_PREC_F32.  A call none of whose probed windows is finite (e.g. all over -inf mel rows)
- * gives the probe nothing to compare: the network stays ISS_GUARD_PENDING (0 windows compared) and its next call probes again.
- * iss_set_precision_guard: threshold <= 0 disables the probe (networks loaded later are not probed; already decided ones keep their mode).
+ * beyond fp16's range, always does) -- switches THIS network until the context's mode changes: to the other split mode if that one
+ * passes the same probe (the same speed), else to ISS_PREC_F32.  A call none of whose probed windows is finite (e.g. all over -inf
+ * mel rows) gives the probe nothing to compare: the network stays ISS_GUARD_PENDING (0 windows compared) and its next call probes again.
+ * iss_set_precision with a mode other than the context's current one re-arms every loaded network the caller has not pinned with
+ * iss_cnn_set_net_precision: the guard's decision is dropped (ISS_GUARD_PENDING, probe figures -1 / 0 windows), the network runs the
+ * new mode, and its next iss_cnn_probs call probes it again (a network whose first call ran in exact f32 included).
+ * iss_set_precision_guard: threshold <= 0 disables the probe (networks loaded later are not probed; already decided ones keep their
+ * mode).  A threshold change is not a mode change: it re-arms nothing.
  * iss_cnn_precision_info: mode in use for the network (ISS_PREC_*, the one it actually runs: see ISS_PREC_F16X3), the probe's figure
  * for the mode that was asked for (-1 if not probed), the windows it compared, ISS_GUARD_* state, and the figure of the mode in use
  * (0 for exact f32).
- * iss_cnn_set_net_precision: caller's override for one network (-1 = follow the context again); marks it decided. */
+ * iss_cnn_set_net_precision: caller's override for one network (-1 = follow the context again); marks it decided, and the override
+ * survives iss_set_precision (it is never probed). */
 #define ISS_GUARD_PENDING   0   /* not probed yet                                              */
 #define ISS_GUARD_PASSED    1   /* probed: within the threshold, mode kept                     */
 #define ISS_GUARD_ESCALATED 2   /* probed: above the threshold, the network runs another mode  */
-#define ISS_GUARD_FIXED     3   /* mode set by the caller (iss_cnn_set_net_precision) or the context is in exact-f32 mode anyway */
+#define ISS_GUARD_FIXED     3   /* mode set by the caller (iss_cnn_set_net_precision) or the context was in exact-f32 mode at the first call */
 int iss_set_precision_guard(iss_ctx* ctx, float threshold);
 int iss_cnn_precision_info(iss_ctx* ctx, int id, int32_t* mode, float* max_dlogp, int32_t* slots, int32_t* state, float* dlogp_in_use);
 int iss_cnn_set_net_precision(iss_ctx* ctx, int id, int mode);

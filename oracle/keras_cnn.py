@@ -9,7 +9,10 @@ the TF rule (extra pad goes bottom/right), BatchNormalization inference form
 gamma*(x-mean)/sqrt(var+eps)+beta, Flatten in (H,W,C) order, Dropout=identity,
 softmax over the last axis.  Two independent implementations are kept so they
 can check each other: `forward` (torch-CPU functional, fast enough to be the
-CPU baseline) and `forward_naive` (pure numpy loops, tiny cases only).
+CPU baseline) and `forward_naive` (pure numpy loops, tiny cases only).  Both take `dtype`: np.float32 (the default, the
+arithmetic of the Keras models) or np.float64, in which parameters, activations, the BatchNorm folding and the softmax are all
+float64 -- the reference the device's arithmetic modes are measured against.  `forward(..., log=True)` returns the log of a
+softmax-terminated network's output as a log-softmax (compare log p, not p: the softmax squashes errors).
 
 A model is a list of plain dicts (same vocabulary as
 inaspeechsegmenter_amd/keras_model.py produces, but this file does not import it):
@@ -36,23 +39,23 @@ def same_pads(size, k, s):
 _ALPHA = {'elu': 1.0, 'leaky_relu': 0.3}          # keras.activations.elu / keras.layers.LeakyReLU defaults
 
 
-def _act_np(x, fn, alpha=None):
+def _act_np(x, fn, alpha=None, dt=np.float32):
     alpha = _ALPHA.get(fn, 0.0) if alpha is None else alpha
     if fn in (None, 'linear'):
         return x
     if fn == 'relu':
         return np.maximum(x, 0)
     if fn == 'relu_general':                       # keras.layers.ReLU(max_value, negative_slope, threshold); alpha = (slope, max, thr)
-        sl, mv, th = (np.float32(v) for v in alpha)
-        return np.where(x > th, np.minimum(x, mv), sl * (x - th)).astype(np.float32)
+        sl, mv, th = (dt(v) for v in alpha)
+        return np.where(x > th, np.minimum(x, mv), sl * (x - th)).astype(dt)
     if fn == 'relu_max':                           # keras.layers.ReLU(max_value=alpha): min(max(x, 0), alpha)
-        return np.minimum(np.maximum(x, 0), np.float32(alpha))
+        return np.minimum(np.maximum(x, 0), dt(alpha))
     if fn == 'elu':                                # keras.activations.elu: x if x > 0 else alpha * (exp(x) - 1)
-        return np.where(x > 0, x, np.float32(alpha) * (np.exp(np.minimum(x, 0)) - 1))
+        return np.where(x > 0, x, dt(alpha) * (np.exp(np.minimum(x, 0)) - 1))
     if fn == 'leaky_relu':                         # keras.layers.LeakyReLU: x if x > 0 else alpha * x
-        return np.where(x > 0, x, np.float32(alpha) * x)
+        return np.where(x > 0, x, dt(alpha) * x)
     if fn == 'selu':                               # scale * elu(x, alpha) with the fixed SELU constants
-        return np.float32(1.05070098) * np.where(x > 0, x, np.float32(1.67326324) * (np.exp(np.minimum(x, 0)) - 1))
+        return dt(1.05070098) * np.where(x > 0, x, dt(1.67326324) * (np.exp(np.minimum(x, 0)) - 1))
     if fn == 'softplus':
         return np.logaddexp(x, 0)
     if fn == 'sigmoid':
@@ -65,12 +68,18 @@ def _act_np(x, fn, alpha=None):
     raise ValueError(fn)
 
 
-def forward(layers, x, batch_size=1024, threads=None):
-    """x: (N,H,W,C) float32 -> (N,classes) float32, torch-CPU."""
+def forward(layers, x, batch_size=1024, threads=None, dtype=np.float32, log=False):
+    """x: (N,H,W,C) -> (N,classes) in `dtype` (float32: the Keras arithmetic; float64: the reference), torch-CPU.
+    log=True: log p of a network whose last layer is a softmax, computed as a log-softmax."""
     import torch
     import torch.nn.functional as F
     if threads:
         torch.set_num_threads(threads)
+    f32 = np.dtype(dtype) == np.float32
+    assert f32 or np.dtype(dtype) == np.float64, dtype
+
+    def P(a):                                      # a parameter array as a tensor of the working type (float32: as stored)
+        return torch.from_numpy(np.ascontiguousarray(a) if f32 else np.ascontiguousarray(a, dtype=np.float64))
 
     def act(t, fn, alpha=None):
         alpha = _ALPHA.get(fn, 0.0) if alpha is None else alpha
@@ -97,6 +106,8 @@ def forward(layers, x, batch_size=1024, threads=None):
             return torch.tanh(t)
         if fn == 'softmax':
             return torch.softmax(t, dim=-1)
+        if fn == 'log_softmax':
+            return torch.log_softmax(t, dim=-1)
         raise ValueError(fn)
 
     def step(L, t, flat):
@@ -107,12 +118,12 @@ def forward(layers, x, batch_size=1024, threads=None):
             # dilation_rate: taps (dy, dx) apart; 'same' pads for the EFFECTIVE kernel size (k - 1) * d + 1
             if ty == 'depthwise':
                 kh, kw, cin, mult = L['W'].shape
-                w = torch.from_numpy(np.ascontiguousarray(L['W'].transpose(2, 3, 0, 1).reshape(cin * mult, 1, kh, kw)))
+                w = P(L['W'].transpose(2, 3, 0, 1).reshape(cin * mult, 1, kh, kw))
                 groups = cin
             else:
-                w = torch.from_numpy(np.ascontiguousarray(L['W'].transpose(3, 2, 0, 1)))
+                w = P(L['W'].transpose(3, 2, 0, 1))
                 groups = 1
-            b = None if L.get('b') is None else torch.from_numpy(L['b'])
+            b = None if L.get('b') is None else P(L['b'])
             kh, kw = L['W'].shape[:2]
             sh, sw = L.get('strides', (1, 1))
             dy, dx = L.get('dilation', (1, 1))
@@ -125,10 +136,15 @@ def forward(layers, x, batch_size=1024, threads=None):
                 t = F.pad(t, (pl, pr, pt, pb))
             t = act_nchw(F.conv2d(t, w, b, stride=(sh, sw), dilation=(dy, dx), groups=groups), L.get('activation'), act, L.get('alpha'))
         elif ty == 'batchnorm':
-            sc = L['gamma'] / np.sqrt(L['var'] + np.float32(L['eps']))
-            sh_ = L['beta'] - L['mean'] * sc
-            sc_t = torch.from_numpy(sc.astype(np.float32))
-            sh_t = torch.from_numpy(sh_.astype(np.float32))
+            if f32:
+                sc = L['gamma'] / np.sqrt(L['var'] + np.float32(L['eps']))
+                sh_ = L['beta'] - L['mean'] * sc
+                sc_t = torch.from_numpy(sc.astype(np.float32))
+                sh_t = torch.from_numpy(sh_.astype(np.float32))
+            else:
+                g, v, be, mu = (np.asarray(L[k], np.float64) for k in ('gamma', 'var', 'beta', 'mean'))
+                sc = g / np.sqrt(v + np.float64(L['eps']))
+                sc_t, sh_t = torch.from_numpy(sc), torch.from_numpy(be - mu * sc)
             if flat:
                 t = t * sc_t + sh_t
             else:
@@ -157,9 +173,9 @@ def forward(layers, x, batch_size=1024, threads=None):
             t = t.permute(0, 2, 3, 1).reshape(t.shape[0], -1); flat = True
         elif ty == 'dense':
             assert flat, "dense on un-flattened input"
-            t = t @ torch.from_numpy(L['W'])
+            t = t @ P(L['W'])
             if L.get('b') is not None:
-                t = t + torch.from_numpy(L['b'])
+                t = t + P(L['b'])
             t = act(t, L.get('activation'), L.get('alpha'))
         elif ty == 'dropout':
             pass
@@ -197,10 +213,19 @@ def forward(layers, x, batch_size=1024, threads=None):
         return (r / np.float32(len(ts)) if ty == 'average' else r), flat
 
     graph = any('inputs' in L for L in layers)
+    if log:                                        # the sink's softmax becomes a log-softmax
+        names = [L.get('name') for L in layers]
+        read = {nm for L in layers for nm in (L.get('inputs') or [])}
+        k = next(i for i in range(len(layers) - 1, -1, -1) if not graph or names[i] not in read)
+        key = 'fn' if layers[k]['type'] == 'activation' else 'activation'
+        if layers[k].get(key) != 'softmax':
+            raise ValueError("log=True needs a network whose output layer is a softmax")
+        layers = list(layers)
+        layers[k] = dict(layers[k], **{key: 'log_softmax'})
     outs = []
     with torch.no_grad():
         for s in range(0, len(x), batch_size):
-            t = torch.from_numpy(np.ascontiguousarray(x[s:s + batch_size], dtype=np.float32))
+            t = torch.from_numpy(np.ascontiguousarray(x[s:s + batch_size], dtype=np.float32 if f32 else np.float64))
             t = t.permute(0, 3, 1, 2)                      # NCHW internally
             flat = False
             if not graph:
@@ -209,7 +234,7 @@ def forward(layers, x, batch_size=1024, threads=None):
             else:
                 t, flat = _run_graph(layers, (t, flat), lambda L, v: step(L, v[0], v[1]), merge)
             outs.append(t.numpy())
-    return np.concatenate(outs) if outs else np.zeros((0, 0), np.float32)
+    return np.concatenate(outs) if outs else np.zeros((0, 0), dtype)
 
 
 _MERGE_TYPES = ('add', 'subtract', 'multiply', 'average', 'maximum', 'minimum', 'concatenate')
@@ -236,14 +261,15 @@ def _run_graph(layers, x, step, merge):
 
 
 def act_nchw(t, fn, act, alpha=None):
-    if fn == 'softmax':
+    if fn in ('softmax', 'log_softmax'):
         return act(t.permute(0, 2, 3, 1), fn).permute(0, 3, 1, 2)
     return act(t, fn, alpha)
 
 
-def forward_naive(layers, x):
-    """Pure-numpy NHWC loops, float32, for tiny shapes: independent check of `forward`."""
-    t = np.asarray(x, dtype=np.float32)
+def forward_naive(layers, x, dtype=np.float32):
+    """Pure-numpy NHWC loops, float32 (or float64: parameters cast), for tiny shapes: independent check of `forward`."""
+    dt = np.float32 if np.dtype(dtype) == np.float32 else np.float64
+    t = np.asarray(x, dtype=dt)
     if any('inputs' in L for L in layers):
         def merge(L, ts):
             if L['type'] == 'concatenate':
@@ -254,12 +280,14 @@ def forward_naive(layers, x):
             r = ts[0]
             for u in ts[1:]:
                 r = f(r, u)
-            return (r / np.float32(len(ts)) if L['type'] == 'average' else r).astype(np.float32)
-        return _run_graph(layers, t, lambda L, v: _naive_chain([L], v), merge)
-    return _naive_chain(layers, t)
+            return (r / dt(len(ts)) if L['type'] == 'average' else r).astype(dt)
+        return _run_graph(layers, t, lambda L, v: _naive_chain([L], v, dt), merge)
+    return _naive_chain(layers, t, dt)
 
 
-def _naive_chain(layers, t):
+def _naive_chain(layers, t, dt=np.float32):
+    def P(k, L):                                   # (float32: the stored array itself)
+        return L.get(k) if dt is np.float32 or L.get(k) is None else np.asarray(L[k], dt)
     for L in layers:
         ty = L['type']
         if ty == 'reshape':
@@ -267,7 +295,7 @@ def _naive_chain(layers, t):
         elif ty == 'permute':
             t = t.transpose((0,) + tuple(int(v) + 1 for v in L['perm']))
         elif ty == 'conv2d':
-            W = L['W']; kh, kw, cin, cout = W.shape
+            W = P('W', L); kh, kw, cin, cout = W.shape
             sh, sw = L.get('strides', (1, 1))
             if L.get('pad'):
                 zt, zb, zl, zr = L['pad']
@@ -277,19 +305,19 @@ def _naive_chain(layers, t):
                 t = np.pad(t, ((0, 0), (pt, pb), (pl, pr), (0, 0)))
             n, H, Wd, _ = t.shape
             ho, wo = (H - kh) // sh + 1, (Wd - kw) // sw + 1
-            o = np.zeros((n, ho, wo, cout), np.float32)
+            o = np.zeros((n, ho, wo, cout), dt)
             for y in range(ho):
                 for xx in range(wo):
                     patch = t[:, y * sh:y * sh + kh, xx * sw:xx * sw + kw, :].reshape(n, -1)
                     o[:, y, xx, :] = patch @ W.reshape(-1, cout)
             if L.get('b') is not None:
-                o = o + L['b']
-            t = _act_np(o, L.get('activation'), L.get('alpha')).astype(np.float32)
+                o = o + P('b', L)
+            t = _act_np(o, L.get('activation'), L.get('alpha'), dt).astype(dt)
         elif ty == 'batchnorm':
-            sc = L['gamma'] / np.sqrt(L['var'] + np.float32(L['eps']))
-            t = (t * sc + (L['beta'] - L['mean'] * sc)).astype(np.float32)
+            sc = P('gamma', L) / np.sqrt(P('var', L) + dt(L['eps']))
+            t = (t * sc + (P('beta', L) - P('mean', L) * sc)).astype(dt)
         elif ty == 'activation':
-            t = _act_np(t, L['fn'], L.get('alpha')).astype(np.float32)
+            t = _act_np(t, L['fn'], L.get('alpha'), dt).astype(dt)
         elif ty in ('maxpool', 'avgpool'):
             ph, pw = L['pool']; sh, sw = L.get('strides') or L['pool']
             if L.get('padding', 'valid') == 'same':
@@ -297,7 +325,7 @@ def _naive_chain(layers, t):
                 t = np.pad(t, ((0, 0), (pt, pb), (pl, pr), (0, 0)), constant_values=-np.inf if ty == 'maxpool' else np.nan)
             n, H, Wd, c = t.shape
             ho, wo = (H - ph) // sh + 1, (Wd - pw) // sw + 1
-            o = np.zeros((n, ho, wo, c), np.float32)
+            o = np.zeros((n, ho, wo, c), dt)
             for y in range(ho):
                 for xx in range(wo):
                     win = t[:, y * sh:y * sh + ph, xx * sw:xx * sw + pw, :]
@@ -310,10 +338,10 @@ def _naive_chain(layers, t):
         elif ty == 'flatten':
             t = t.reshape(t.shape[0], -1)
         elif ty == 'dense':
-            t = t @ L['W']
+            t = t @ P('W', L)
             if L.get('b') is not None:
-                t = t + L['b']
-            t = _act_np(t, L.get('activation'), L.get('alpha')).astype(np.float32)
+                t = t + P('b', L)
+            t = _act_np(t, L.get('activation'), L.get('alpha'), dt).astype(dt)
         elif ty == 'dropout':
             pass
         else:

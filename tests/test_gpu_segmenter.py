@@ -152,7 +152,10 @@ def test_batch_process_contract(seg, tmp_path):
 
 def test_pipeline_workers_follow_the_segmenters_settings(tmp_path):
     """The extra device contexts of the multi-file pipeline take over the arithmetic mode and workspace cap of seg.ctx, at
-    creation and again on every call (they are cached): f32 batch_process with two workers == per-file f32 calls."""
+    creation and again on every call (they are cached): f32 batch_process with two workers == per-file f32 calls.  Every context
+    reports the mode asked for after every leg (iss_cnn_precision_info): a first decision at the defaults does not survive a later
+    request for exact f32 (and a worker's f32 rows are bit-identical to seg.ctx's, within float32 rounding of float64), nor does
+    f32 survive the switch back."""
     from inaspeechsegmenter_amd import _native
     s2 = Segmenter(vad_engine='smn', detect_gender=True, ffmpeg=None, models='synthetic')
     lin = []
@@ -173,7 +176,59 @@ def test_pipeline_workers_follow_the_segmenters_settings(tmp_path):
             assert filecmp.cmp(dst, ref, shallow=False)
         secs = [float(m[2].split()[1]) for m in lmsg]
         assert all(0.0 < v < t for v in secs) and sum(secs) < 2.5 * t          # per-file figures, not time since batch start
+        modes = _modes_in_use(s2)
+        print('modes in use after the', prec, 'leg:', modes)
+        if prec == _native.PREC_F32:
+            assert set(modes.values()) == {'f32'}, modes
+        else:                                                                   # one decision for every context
+            assert len(set(modes.values())) == 1 and set(modes.values()) <= {'bf16x3', 'f16x3'}, modes
+    # the library defaults, then exact f32 asked for after the first decision, then the defaults again: every context runs the
+    # mode asked for -- none stays on the decision of the earlier mode
+    s2.ctx.set_precision(_native.PREC_F16X3)
+    s2.ctx.set_workspace_limit(24 << 30)
+    lout = [str(tmp_path / f'od_{i}.csv') for i in range(4)]
+    assert s2.batch_process(lin, lout, batch_files=1, workers=2)[1] == 4
+    modes = _modes_in_use(s2)
+    assert len(set(modes.values())) == 1, modes
+    s2.ctx.set_precision(_native.PREC_F32)
+    assert s2.batch_process(lin, lout, batch_files=1, workers=2)[1] == 4
+    modes = _modes_in_use(s2)
+    print('defaults, then f32:', modes)
+    assert set(modes.values()) == {'f32'}, modes
+    from inaspeechsegmenter_amd import segmenter as S
+    w = next(w for w in s2.__dict__['_pipeline_workers'] if w.ctx is not s2.ctx)
+    s2.ctx.set_signal(synth_pcm(44, 16000 * 20))
+    T = s2.ctx.sidekit()
+    mspec = s2.ctx.get_mspec()
+    w.ctx.set_mspec(mspec)
+    rows = S._window_rows(T)
+    sub = rows[np.random.default_rng(5).choice(len(rows), 120, replace=False)]
+    for net in (s2.vad, s2.gender):
+        pa, fa = net.probs(s2.ctx, rows)
+        pw, fw = net.probs(w.ctx, rows)
+        assert np.array_equal(pa, pw) and np.array_equal(fa, fw)
+        patches = np.stack([mspec[r:r + 68, :net.nmel] for r in sub]).astype(np.float64).reshape(len(sub), -1)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            z = ((patches - patches.mean(1, keepdims=True)) / patches.std(1, keepdims=True)).reshape(len(sub), 68, net.nmel, 1)
+        fin = np.all(np.isfinite(z.reshape(len(sub), -1)), axis=1)
+        lp64 = ocnn.forward(net.layers, np.where(fin[:, None, None, None], z, 0), dtype=np.float64, log=True)
+        pi = np.searchsorted(rows, sub)                                 # (rows is sorted: the first slot of each window)
+        assert np.array_equal(fa[pi].astype(bool), fin) and fin.sum() > 60
+        err = np.abs(np.log(pa[pi].astype(np.float64)) - lp64)[fin[:, None] & (lp64 > np.log(1e-30))].max()
+        print(f'{type(net).__name__}: f32 on seg.ctx == on a worker; max |d log p| vs float64 {err:.2e}')
+        assert err < 5e-5
+    s2.ctx.set_precision(_native.PREC_F16X3)
+    assert s2.batch_process(lin, lout, batch_files=1, workers=2)[1] == 4
+    modes = _modes_in_use(s2)
+    print('back to the defaults:', modes)
+    assert 'f32' not in set(modes.values()) and len(set(modes.values())) == 1, modes
     s2.close()
+
+
+def _modes_in_use(seg):
+    """{(context, net): the mode iss_cnn_precision_info reports} over seg.ctx and every pipeline worker's context."""
+    ctxs = [('seg', seg.ctx)] + [(f'w{i}', w.ctx) for i, w in enumerate(seg.__dict__['_pipeline_workers'])]
+    return {(k, type(net).__name__): c.cnn_precision_info(net.net_id)['mode'] for k, c in ctxs for net in (seg.vad, seg.gender)}
 
 
 def test_constructor_contract():

@@ -785,7 +785,10 @@ def test_one_arithmetic_decision_per_network_across_device_contexts():
     """The precision guard (include/iss.h) decides a network's arithmetic at its first call PER CONTEXT; `DnnSegmenter.probs`
     makes the first call anywhere decide for every device context of the Segmenter (its own and the pipeline workers'): later
     contexts are told the outcome before their first call and are never probed; with the guard off nothing is touched; a first
-    call that gave the probe no finite window to compare leaves the decision open, and the next call anywhere decides for all."""
+    call that gave the probe no finite window to compare leaves the decision open, and the next call anywhere decides for all.
+    The decision is about the mode the Segmenter's own context was asked for: when that changes, every context that was told
+    follows its own mode again and the next call decides anew; a 'fixed' outcome (exact f32) is never passed on; a change of the
+    guard threshold alone reopens nothing."""
     from inaspeechsegmenter_amd import segmenter as S
 
     class Ctx:
@@ -834,3 +837,75 @@ def test_one_arithmetic_decision_per_network_across_device_contexts():
     k, m = Ctx(('escalated', 'f32'), blind_calls=1), Ctx(('passed', 'f16x3'))
     again.probs(k, rows); again.probs(k, rows); again.probs(m, rows)
     assert k.told == [] and k.state == 'escalated' and m.told == [_native.PREC_F32] and m.mode == 'f32'
+
+    names = {_native.PREC_BF16X3: 'bf16x3', _native.PREC_F32: 'f32', _native.PREC_F16X3: 'f16x3'}
+
+    class Lib(Ctx):
+        """... with the library's mode switch (include/iss.h): the guard's outcome depends on the mode asked for (exact f32: 'fixed'),
+        iss_set_precision re-arms a network the caller has not pinned, iss_cnn_set_net_precision(-1) unpins it."""
+        def __init__(self, outcomes, precision=None, guard_threshold=None):
+            super().__init__(None, guard_threshold=guard_threshold)
+            self.outcomes, self.precision, self.pinned = outcomes, precision, False
+            self.mode = names[_native.PREC_F16X3 if precision is None else precision]
+
+        def cnn_probs(self, net_id, rows):
+            self.calls += 1
+            prec = _native.PREC_F16X3 if self.precision is None else self.precision
+            if self.state == 'pending' and (prec == _native.PREC_F32 or S._guard_on(self)):
+                self.state, self.mode = ('fixed', 'f32') if prec == _native.PREC_F32 else self.outcomes[prec]
+            return np.zeros((len(rows), 2), np.float32), np.ones(len(rows), np.uint8)
+
+        def cnn_set_net_precision(self, net_id, mode):
+            self.told.append(mode)
+            self.pinned = mode != -1
+            self.state = 'fixed' if self.pinned else 'pending'
+            self.mode = names[mode if self.pinned else (_native.PREC_F16X3 if self.precision is None else self.precision)]
+
+        def set_precision(self, mode):
+            if mode != (_native.PREC_F16X3 if self.precision is None else self.precision) and not self.pinned:
+                self.state, self.mode = 'pending', names[mode]
+            self.precision = mode
+
+        def set_precision_guard(self, threshold):
+            self.guard_threshold = threshold
+
+    outcomes = {_native.PREC_F16X3: ('escalated', 'bf16x3'), _native.PREC_BF16X3: ('passed', 'bf16x3')}
+    # the requested precision changes after a decision: the told worker is released (-1) and runs the new mode, like the
+    # Segmenter's own context (re-armed by the library itself: its decision was the guard's, not a pin); exact f32 is passed on to nobody; back in the default mode the next call decides for all again
+    seg = S.DnnSegmenter.__new__(S.Gender)
+    own, wk = Lib(outcomes), Lib(outcomes)
+    seg.ctx = own
+    seg.probs(own, rows); seg.probs(wk, rows)
+    assert (own.state, own.mode, wk.state, wk.mode, wk.told) == ('escalated', 'bf16x3', 'fixed', 'bf16x3', [_native.PREC_BF16X3])
+    for c_ in (own, wk):                                 # Segmenter.ctx.set_precision, then the workers' mirror_settings
+        c_.set_precision(_native.PREC_F32)
+    seg.probs(wk, rows); seg.probs(own, rows); seg.probs(wk, rows)
+    assert (own.mode, wk.mode) == ('f32', 'f32') and (own.state, wk.state) == ('fixed', 'fixed')
+    assert wk.told == [_native.PREC_BF16X3, -1] and own.told == [] and seg._mode_state['mode'] == -1
+    for c_ in (own, wk):
+        c_.set_precision(_native.PREC_F16X3)
+    seg.probs(own, rows); seg.probs(wk, rows)
+    assert (own.state, own.mode, wk.state, wk.mode) == ('escalated', 'bf16x3', 'fixed', 'bf16x3')
+    assert wk.told == [_native.PREC_BF16X3, -1, _native.PREC_BF16X3] and own.told == []
+    # a 'fixed' first call (the context in exact f32): nothing to agree on, nobody is told f32; after the switch to the default
+    # mode the first call anywhere probes and decides for the others
+    fx = S.DnnSegmenter.__new__(S.Gender)
+    own, wk = Lib(outcomes, precision=_native.PREC_F32), Lib(outcomes, precision=_native.PREC_F32)
+    fx.ctx = own
+    fx.probs(own, rows); fx.probs(wk, rows)
+    assert (own.state, wk.state, own.told, wk.told) == ('fixed', 'fixed', [], []) and fx._mode_state['mode'] == -1
+    for c_ in (own, wk):
+        c_.set_precision(_native.PREC_F16X3)
+    fx.probs(wk, rows); fx.probs(own, rows)
+    assert (wk.state, wk.mode, own.state, own.mode, own.told) == ('escalated', 'bf16x3', 'fixed', 'bf16x3', [_native.PREC_BF16X3])
+    # a guard-threshold change is not a mode change: the decision stands, nobody is released or told again
+    gd = S.DnnSegmenter.__new__(S.Gender)
+    own, wk = Lib(outcomes), Lib(outcomes)
+    gd.ctx = own
+    gd.probs(own, rows); gd.probs(wk, rows)
+    for thr in (1e-3, 0.0):
+        for c_ in (own, wk):
+            c_.set_precision_guard(thr)
+        gd.probs(wk, rows); gd.probs(own, rows)
+        assert wk.told == [_native.PREC_BF16X3] and own.told == [] and (own.mode, wk.mode) == ('bf16x3', 'bf16x3')
+    assert gd._mode_state['mode'] == _native.PREC_BF16X3
