@@ -16,8 +16,11 @@ Workloads
                                      archive.segment_archive, ONE RCCL all-gather of the segment tables per step (C-ABI
                                      iss_allgather_segments); --files-per-gpu of them per rank (weak scaling)
   vbx                                BASELINE.json configs[4]
-The default line carries the other single-GPU configurations as driver-timed `companions`: `archive` at every N (so that the
-file-based configs[3] path has a 1 -> N curve of its own), `batch` and `vbx` at N = 1 (--no-companions skips them).
+A plain run does only what the headline needs: set up, warm up, time the K steps, dump (--dump-outputs), print the line.
+`--full` adds everything else, after the timed steps: the per-kernel roofline (one profiled step), and for the segmenter workload the
+reference-semantics rate, the exact-f32 companion step, the CPU baseline with its parity check (N = 1), and the other single-GPU
+configurations as driver-timed `companions`: `archive` at every N (so that the file-based configs[3] path has a 1 -> N curve of its
+own), `batch` and `vbx` at N = 1; for vbx, its CPU baseline.  --no-companions, --no-f32-companion and --no-cpu-baseline drop parts of it.
 
 segmenter workload (BASELINE.json configs[1] input, with the metric's smn + gender nets): every rank holds
 ONE 1 h synthetic 16 kHz mono PCM16 recording, already resident in HBM when the timed region
@@ -597,13 +600,15 @@ def self_spawn(n, argv):
 
 
 def bench_files(args, torch, dev, local_rank, rank, world, kind, seg=None, comm=None, comm_kind=None, steps=None, warmup=None,
-                per_gpu=None, dense=None):
+                per_gpu=None, dense=None, full=None):
     """`batch` (configs[2], one GPU) and `archive` (configs[3] shape, file-parallel + one all-gather) workloads.
-    -> the JSON line as a dict on rank 0 (None elsewhere).  seg / comm: reuse the caller's (companion runs)."""
+    -> the JSON line as a dict on rank 0 (None elsewhere).  seg / comm: reuse the caller's (companion runs).  full (default
+    --full): also the roofline of one extra profiled step."""
     from inaspeechsegmenter_amd import Segmenter, _native, sharding
     from inaspeechsegmenter_amd.archive import segment_archive
     steps = steps or args.steps
     warmup = max(args.warmup if warmup is None else warmup, 1)
+    full = args.full if full is None else full
     own_seg = seg is None
     if own_seg:
         seg = Segmenter(vad_engine='smn', detect_gender=True, ffmpeg=None, models='synthetic', device=local_rank)
@@ -690,21 +695,9 @@ def bench_files(args, torch, dev, local_rank, rank, world, kind, seg=None, comm=
             for w in seg.__dict__.get('_pipeline_workers', [])]
     if comm:
         dt = comm.max_over_ranks(dt)
-    # roofline of the conv/dense GEMM launches, live: HIP events on the library's streams around every launch of ONE extra
-    # step (all ranks run it -- the step holds the collective; rank 0's device contexts are read)
+    # (--full) roofline of the conv/dense GEMM launches, live: ONE extra step, all ranks (the step holds the collective)
     ctxs = [w.ctx for w in seg.__dict__.get('_pipeline_workers', [])] or [seg.ctx]
-    for c in ctxs:
-        c.prof_enable(True)
-        c.prof_reset()
-    step()
-    conv_ms = conv_fl = 0.0
-    conv_n = 0
-    for c in ctxs:
-        ms, nl, fl = c.prof_get(0)
-        conv_ms += ms; conv_n += nl; conv_fl += fl
-    ktab, kdom = gemm_kernel_table(ctxs, MFMA_BF16_PEAK_TF if x3 else MFMA_F32_PEAK_TF, _pmc_static())
-    for c in ctxs:
-        c.prof_enable(False)
+    roofline = files_roofline(ctxs, step, x3, dt / steps) if full else None
     # audit trail of the multi-GPU run: what RCCL reports for the communicator, and the spread of the ranks' own step times
     rccl = None
     dt_min = dt_max = dt_local
@@ -715,20 +708,6 @@ def bench_files(args, torch, dev, local_rank, rank, world, kind, seg=None, comm=
     line = None
     if rank == 0:
         value = steps * hours / dt
-        peak_tf = MFMA_BF16_PEAK_TF if x3 else MFMA_F32_PEAK_TF
-        step_s = dt / steps
-        ach = conv_fl / step_s / 1e12                # whole-step figure: the two device contexts' launches overlap on the GPU,
-        ach_ev = conv_fl / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0     # so per-launch event durations are stretched
-        roofline = {"bound": "mfma", "kernel": "conv/dense implicit-GEMM launches of rank 0's device contexts (see the segmenter workload's line)",
-                    "achieved": ach, "peak": peak_tf, "unit": "TFLOP/s", "frac": ach / peak_tf, "traffic": None,
-                    "launches_per_step": conv_n, "flops_per_launch": conv_fl / max(conv_n, 1),
-                    "event_based": {"achieved": ach_ev, "frac": ach_ev / peak_tf, "kernel_ms_per_step": conv_ms,
-                                    "avg_launch_ms": conv_ms / max(conv_n, 1)},
-                    "dominant": kdom, "kernels": ktab,
-                    "note": "achieved = algorithmic flops of rank 0's GEMM launches in one step / the step's WALL time (decode, copies, "
-                            "host Viterbi and export included): launches of the two device contexts run concurrently, so the sum of "
-                            "their HIP-event durations (event_based) counts shared time twice; the segmenter workload's line has the "
-                            "kernel-only figure.  Reference semantics: VAD net on energy slots, gender net on speech slots"}
         line = {
             "metric": "hours-of-audio segmented/sec (smn+gender, 16 kHz mono)",
             "value": value, "unit": "hours-of-audio/s", "n_gpus": world, "steps": steps, "warmup": warmup,
@@ -749,7 +728,6 @@ def bench_files(args, torch, dev, local_rank, rank, world, kind, seg=None, comm=
                                   "(tests/golden/make_standin_heads.py); the real Keras files are un-vendored release assets",
                        "parallelism": (f"file-parallel x{world}: files dealt by size (LPT), no data-path collective, ONE all-gather of int32 segment "
                                        f"tables per step: {comm_kind}") if world > 1 else "single GPU"},
-            "roofline": roofline,
             "pipeline_workers_ms_per_step": {"workers": pipe,
                                              "what": "wall ms per step each device worker thread spent packing PCM into its page-locked buffer, in "
                                                      "H2D + sidekit + log-energy read-back, in the host energy detector, blocked in iss_cnn_probs, "
@@ -761,12 +739,45 @@ def bench_files(args, torch, dev, local_rank, rank, world, kind, seg=None, comm=
             "ranks": {"ms_per_step_min": dt_min / steps * 1e3, "ms_per_step_max": dt_max / steps * 1e3,
                       "what": "each rank's own wall time for the timed steps (barrier to barrier), min / max over the ranks"},
         }
+        if roofline is not None:
+            line["roofline"] = roofline
         if rccl is not None:
             line["rccl"] = rccl
     barrier()
     if own_seg:
         seg.close()
     return line
+
+
+def files_roofline(ctxs, step, x3, step_s):
+    """Roofline of the conv/dense GEMM launches of the file workloads, live: HIP events on the library's streams around every
+    launch of ONE extra `step()` (every rank runs it: the step holds the collective; `ctxs` = this rank's device contexts, rank 0's
+    are the ones reported).  step_s: wall seconds of one timed step.  -> the line's `roofline` object."""
+    for c in ctxs:
+        c.prof_enable(True)
+        c.prof_reset()
+    step()
+    conv_ms = conv_fl = 0.0
+    conv_n = 0
+    for c in ctxs:
+        ms, nl, fl = c.prof_get(0)
+        conv_ms += ms; conv_n += nl; conv_fl += fl
+    ktab, kdom = gemm_kernel_table(ctxs, MFMA_BF16_PEAK_TF if x3 else MFMA_F32_PEAK_TF, _pmc_static())
+    for c in ctxs:
+        c.prof_enable(False)
+    peak_tf = MFMA_BF16_PEAK_TF if x3 else MFMA_F32_PEAK_TF
+    ach = conv_fl / step_s / 1e12                    # whole-step figure: the two device contexts' launches overlap on the GPU,
+    ach_ev = conv_fl / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0     # so per-launch event durations are stretched
+    return {"bound": "mfma", "kernel": "conv/dense implicit-GEMM launches of rank 0's device contexts (see the segmenter workload's line)",
+            "achieved": ach, "peak": peak_tf, "unit": "TFLOP/s", "frac": ach / peak_tf, "traffic": None,
+            "launches_per_step": conv_n, "flops_per_launch": conv_fl / max(conv_n, 1),
+            "event_based": {"achieved": ach_ev, "frac": ach_ev / peak_tf, "kernel_ms_per_step": conv_ms,
+                            "avg_launch_ms": conv_ms / max(conv_n, 1)},
+            "dominant": kdom, "kernels": ktab,
+            "note": "achieved = algorithmic flops of rank 0's GEMM launches in one step / the step's WALL time (decode, copies, "
+                    "host Viterbi and export included): launches of the two device contexts run concurrently, so the sum of "
+                    "their HIP-event durations (event_based) counts shared time twice; the segmenter workload's line has the "
+                    "kernel-only figure.  Reference semantics: VAD net on energy slots, gender net on speech slots"}
 
 
 def comm_audit(comm, comm_kind, rank, world):
@@ -784,13 +795,43 @@ def comm_audit(comm, comm_kind, rank, world):
     return out
 
 
-def bench_vbx(args, torch, dev, local_rank, rank, world, steps=None, warmup=None, cpu_leg=True):
+def vbx_roofline(ctx, step, precision, n, stage_s):
+    """Roofline of the vbx workload, live: HIP events on the library's stream around every launch of ONE extra `step()` --
+    the GEMM launches against the MFMA peak and the fbank kernel against HBM.  stage_s: the timed steps' wall seconds per step in
+    the feature stage.  -> the line's `roofline` object."""
+    ctx.prof_enable(True)
+    ctx.prof_reset()
+    step()
+    conv_ms, conv_launches, conv_flops = ctx.prof_get(0)
+    fb_ms, _, _ = ctx.prof_get(1)                    # vbx_fbank_kernel alone (HIP events on the library's stream)
+    ktab, kdom = gemm_kernel_table([ctx], MFMA_BF16_PEAK_TF if precision != 'f32' else MFMA_F32_PEAK_TF, _pmc_static())
+    ctx.prof_enable(False)
+    # feature stage: algorithmic bytes = PCM16 in + the cached dither stream (f64) + (T, 64) f32 out
+    T = n // 160
+    fea_bytes = n * 2 + n * 8 + T * 64 * 4
+    return {"bound": "mfma", "achieved": conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms else 0.0, "peak": MFMA_BF16_PEAK_TF,
+            "frac": (conv_flops / (conv_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TF) if conv_ms else 0.0,
+            "unit": "TFLOP/s", "kernel_ms_per_step": conv_ms, "launches_per_step": conv_launches, "flops_per_step": conv_flops,
+            "dominant": kdom, "kernels": ktab,
+            "secondary": {"kernel": "vbx_fbank_kernel + vbx_cumsum_kernel + vbx_cmn_kernel (PCM16 + dither -> 64-band fbank, CMN)",
+                          "bound": "hbm", "algorithmic_bytes": fea_bytes, "stage_ms_per_step": stage_s * 1e3,
+                          "fbank_kernel_ms": fb_ms,
+                          "achieved": fea_bytes / (fb_ms * 1e-3) / 1e9 if fb_ms > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": (fea_bytes / (fb_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if fb_ms > 0 else 0.0,
+                          "note": "achieved = algorithmic bytes of the stage / vbx_fbank_kernel time (f64 FFT per frame: "
+                                  "latency- and f64-VALU-bound, not HBM-bound); stage_ms is wall time incl. the PCIe copy of "
+                                  "the PCM16 (2 B/sample), the sequential CMN cumsum and launch overheads"}}
+
+
+def bench_vbx(args, torch, dev, local_rank, rank, world, steps=None, warmup=None, cpu_leg=True, full=None):
     """BASELINE.json configs[4]: 1 h of 16 kHz audio through get_features (VBx 64-band fbank + CMN) and the
-    ResNet-101 x-vector network (144-frame windows, hop 24) -- not the headline metric.  -> the JSON line as a dict."""
+    ResNet-101 x-vector network (144-frame windows, hop 24) -- not the headline metric.  -> the JSON line as a dict.
+    full (default --full): also the roofline of one extra profiled step and (cpu_leg) the CPU baseline."""
     from inaspeechsegmenter_amd import _native, vbx as V
     from inaspeechsegmenter_amd import keras_model as KM
     steps = steps or args.steps
     warmup = args.warmup if warmup is None else warmup
+    full = args.full if full is None else full
     ctx = _native.Context(local_rank)
     ctx.set_precision({'bf16x3': _native.PREC_BF16X3, 'f16x3': _native.PREC_F16X3, 'f32': _native.PREC_F32}[args.precision])
     if args.workspace_mb:
@@ -822,18 +863,9 @@ def bench_vbx(args, torch, dev, local_rank, rank, world, steps=None, warmup=None
         tx += b_
     ctx.synchronize()
     dt = time.perf_counter() - t0
-    ctx.prof_enable(True)
-    ctx.prof_reset()
-    step()
-    conv_ms, conv_launches, conv_flops = ctx.prof_get(0)
-    fb_ms, _, _ = ctx.prof_get(1)                    # vbx_fbank_kernel alone (HIP events on the library's stream)
-    ktab, kdom = gemm_kernel_table([ctx], MFMA_BF16_PEAK_TF if args.precision != 'f32' else MFMA_F32_PEAK_TF, _pmc_static())
-    ctx.prof_enable(False)
-    # feature stage: algorithmic bytes = PCM16 in + the cached dither stream (f64) + (T, 64) f32 out
-    T = n // 160
-    fea_bytes = n * 2 + n * 8 + T * 64 * 4
+    roofline = vbx_roofline(ctx, step, args.precision, n, tf / steps) if full else None
     cpu = None
-    if cpu_leg and not args.no_cpu_baseline:
+    if cpu_leg and full and not args.no_cpu_baseline:
         import torch as _t
         from oracle import vbx as ovbx
         threads = min(os.cpu_count() or 1, 64)
@@ -864,23 +896,76 @@ def bench_vbx(args, torch, dev, local_rank, rank, world, steps=None, warmup=None
             "higher_is_better": True, "dtype": f"f32 ({args.precision} split-operand MFMA; f64 fbank front end)", "data": "synthetic",
             "config": {"workload": f"BASELINE.json configs[4]: {args.minutes:g} min synthetic audio, get_features + ResNet-101 on "
                                    f"{nwin} windows (seeded stand-in weights); PCM16 in page-locked host memory -> device, features stay in HBM",
-                       "features_ms_per_step": tf / steps * 1e3, "xvectors_ms_per_step": tx / steps * 1e3},
-            "roofline": {"bound": "mfma", "achieved": conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms else 0.0, "peak": MFMA_BF16_PEAK_TF,
-                         "frac": (conv_flops / (conv_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TF) if conv_ms else 0.0,
-                         "unit": "TFLOP/s", "kernel_ms_per_step": conv_ms, "launches_per_step": conv_launches, "flops_per_step": conv_flops,
-                         "dominant": kdom, "kernels": ktab,
-                         "secondary": {"kernel": "vbx_fbank_kernel + vbx_cumsum_kernel + vbx_cmn_kernel (PCM16 + dither -> 64-band fbank, CMN)",
-                                       "bound": "hbm", "algorithmic_bytes": fea_bytes, "stage_ms_per_step": tf / steps * 1e3,
-                                       "fbank_kernel_ms": fb_ms,
-                                       "achieved": fea_bytes / (fb_ms * 1e-3) / 1e9 if fb_ms > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                       "frac": (fea_bytes / (fb_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if fb_ms > 0 else 0.0,
-                                       "note": "achieved = algorithmic bytes of the stage / vbx_fbank_kernel time (f64 FFT per frame: "
-                                               "latency- and f64-VALU-bound, not HBM-bound); stage_ms is wall time incl. the PCIe copy of "
-                                               "the PCM16 (2 B/sample), the sequential CMN cumsum and launch overheads"}}}
+                       "features_ms_per_step": tf / steps * 1e3, "xvectors_ms_per_step": tx / steps * 1e3}}
+    if roofline is not None:
+        line["roofline"] = roofline
     if cpu:
         line["cpu_baseline"] = cpu
     ctx.close()
     return line
+
+
+def segmenter_roofline(seg, step, args, n):
+    """Roofline of the segmenter workload, measured live with HIP events on the library's own stream around every launch of
+    ONE extra dense `step(True)` (rank 0's context is read): the dominant GEMM instantiation against the MFMA peak, every
+    instantiation, and the sidekit front end against HBM.  n: samples of the recording.  -> the line's `roofline` object."""
+    x3 = args.precision != 'f32'
+    pj = _pmc_static()
+    seg.ctx.prof_enable(True)
+    seg.ctx.prof_reset()
+    step(True)
+    conv_ms, conv_launches, conv_flops = seg.ctx.prof_get(0)
+    sk_ms, sk_launches, _ = seg.ctx.prof_get(1)
+    other_ms, other_launches, _ = seg.ctx.prof_get(2)
+    peak_tf = MFMA_BF16_PEAK_TF if x3 else MFMA_F32_PEAK_TF
+    ktab, kdom = gemm_kernel_table([seg.ctx], peak_tf, pj)
+    seg.ctx.prof_enable(False)
+    all_tf = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+    sk_bytes = n * 2 + seg.ctx.T * 25 * 4                # PCM16 in + (24 mel + 1 loge) f32 out
+    kd = kdom or {"kernel": None, "achieved": 0.0, "frac": 0.0, "flops_per_launch": 0.0, "avg_launch_ms": 0.0, "launches": 0, "ms_per_step": 0.0}
+    traffic_src = ("static_from_profiles: profiles/pmc_latest.json = rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes (separate runs) of "
+                   + str(pj.get('source', 'bench.py --minutes 20 --steps 1 --warmup 0 of the round-3 build'))
+                   + "; per launch of THIS instantiation, 2 x FETCH_SIZE + WRITE_SIZE (the guide's gfx950 correction for 16-byte-per-lane "
+                     "reads); PMC counters cannot be collected inside a bench run, and rocprofv3 --pmc crashes on the 1 h recording "
+                     "(profiles/r05_pmc_1h_attempt.txt): the PMC run's bytes per launch are scaled by this run's / the PMC run's algorithmic "
+                     "flops per launch of the same instantiation (traffic_scale_to_this_run; same pass geometry, other mix of full and "
+                     "remainder passes)")
+    roofline = {"bound": "mfma",
+                "kernel": kd["kernel"],
+                "achieved": kd["achieved"], "peak": peak_tf, "unit": "TFLOP/s", "frac": kd["frac"],
+                "traffic": kd.get("traffic_per_launch_static"), "traffic_source": traffic_src,
+                "traffic_pmc_run_mean_launch": kd.get("traffic_per_launch_pmc_run"), "traffic_scale_to_this_run": kd.get("traffic_scale_to_this_run"),
+                "frac_own_flops": kd["frac"] * _own_flops_share(seg, kd["kernel"]),
+                "flops_per_launch": kd["flops_per_launch"], "avg_launch_ms": kd["avg_launch_ms"],
+                "launches_per_step": kd["launches"], "kernel_ms_per_step": kd["ms_per_step"],
+                "mfma_executed_tflops": kd["achieved"] * (3 if x3 else 1),
+                # what the matrix pipe SUSTAINS under the chip's power cap on register-resident operands with every CU busy
+                # (tools/microbench/mfma_power_cap.hip, profiles/r06_mfma_power_cap.txt; static: measured once per round, on one box)
+                "sustained_mfma_ceiling": ({"f16_relu_data_tflops": 1620.0, "bf16_relu_data_tflops": 1715.0, "zeros_tflops": 2440.0,
+                                            "frac_of_ceiling": kd["achieved"] * 3 / (1620.0 if args.precision == 'f16x3' else 1715.0),
+                                            "what": "v_mfma_f32_32x32x16 with nothing else in the loop, 0.4-1.3 s per case: random-normal "
+                                                    "operands with relu'd A 1.62 PF (f16) / 1.72 PF (bf16) of the 2.5 PF dense peak, zeros "
+                                                    "2.44 PF -- the clock follows the power the operands' bit activity costs; frac_of_ceiling = "
+                                                    "this kernel's EXECUTED MFMA rate over that figure (profiles/r06_mfma_power_cap.txt)"}
+                                           if x3 else None),
+                "what": ("the kernel INSTANTIATION with the most HIP-event time in one dense step (template arguments spelled out: "
+                         "<KH,KW,PADDED,TR,FUSED,NH,EPI>); achieved = its algorithmic flops per launch / its average launch duration. "
+                         "split modes (f16x3 / bf16x3): three v_mfma_f32_32x32x16_{f16,bf16} per k-step on 16-bit hi/lo operand halves -- the "
+                         "matrix pipe executes 3 x the algorithmic flops, so frac <= 1/3 by construction; the first layer of a fused launch "
+                         "(2.5 % of its flops) is counted as the reference computes it (once per window) although it runs once per log-mel "
+                         "row: frac_own_flops leaves that credit out")
+                        if x3 else "conv_igemm_kernel (conv2d/dense implicit GEMM on v_mfma_f32_32x32x2_f32)",
+                "kernels": ktab,
+                "all_gemm_launches": {"achieved": all_tf, "frac": all_tf / peak_tf, "kernel_ms_per_step": conv_ms, "launches_per_step": conv_launches,
+                                      "flops_per_step": conv_flops,
+                                      "traffic_per_launch_static": pj.get('conv_hbm_bytes_per_launch_corrected_' + args.precision),
+                                      "traffic_per_launch_static_raw": pj.get('conv_hbm_bytes_per_launch_' + args.precision)},
+                "secondary": {"kernel": "sidekit_kernel (PCM16 -> log-energy + 24-band log-mel)", "bound": "hbm",
+                              "achieved": sk_bytes / (sk_ms * 1e-3) / 1e9 if sk_ms > 0 else 0.0, "peak": HBM_PEAK_GBS,
+                              "unit": "GB/s", "frac": (sk_bytes / (sk_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if sk_ms > 0 else 0.0,
+                              "kernel_ms_per_step": sk_ms, "algorithmic_bytes": sk_bytes},
+                "other_kernels_ms_per_step": other_ms}
+    return roofline
 
 
 def make_step(segment, rank, comm):
@@ -978,18 +1063,22 @@ def main():
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--minutes', type=float, default=60.0, help='length of each rank\'s recording')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure and check everything besides the headline: the per-kernel roofline '
+                         '(one profiled step); segmenter workload: the reference-semantics rate, the exact-f32 companion, the CPU '
+                         'baseline and parity check (N = 1) and the archive / batch / vbx companions; vbx: its CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline (and the parity check)')
     ap.add_argument('--workload', choices=['segmenter', 'batch', 'archive', 'vbx'], default='segmenter',
-                    help="segmenter = the metric's workload (default at every --gpus N, with the other configurations as "
+                    help="segmenter = the metric's workload (default at every --gpus N; --full adds the other configurations as "
                          "`companions`); archive = file-parallel configs[3] shape; batch = configs[2]; vbx = configs[4] (x-vector path)")
     ap.add_argument('--timing-only', action='store_true', help='experiment builds of the library that compute wrong results on purpose: no consistency assert')
-    ap.add_argument('--no-companions', action='store_true', help='segmenter workload: skip the archive / batch / vbx companion runs')
+    ap.add_argument('--no-companions', action='store_true', help='--full, segmenter workload: skip the archive / batch / vbx companion runs')
     ap.add_argument('--companion-files-per-gpu', type=int, default=64, help='files per GPU of the archive companion (3 min each)')
     ap.add_argument('--files-per-gpu', type=int, default=0, help='batch / archive: files per GPU and step (default 128)')
     ap.add_argument('--file-minutes', type=float, default=0.0, help='batch / archive: minutes per file (default 5 / 3)')
     ap.add_argument('--dir', default='/dev/shm/iss_bench', help='batch / archive: where the synthetic WAV files live')
     ap.add_argument('--dense-files', action='store_true', help='batch / archive: both networks on every slot of every file (Segmenter.dense_batches)')
-    ap.add_argument('--no-f32-companion', action='store_true', help='skip the exact-f32 (ISS_PREC_F32) companion step')
+    ap.add_argument('--no-f32-companion', action='store_true', help='--full: skip the exact-f32 (ISS_PREC_F32) companion step')
     ap.add_argument('--batch-files', type=int, default=0, help='batch / archive: files per device pass at most (0 = library default, 32)')
     ap.add_argument('--batch-seconds', type=float, default=0, help='batch / archive: audio per device pass at most (0 = library default, 2400 s)')
     ap.add_argument('--workers', type=int, default=0, help='batch / archive: device contexts taking super-batches in turn (0 = library default, 4)')
@@ -1083,76 +1172,23 @@ def main():
     dt_min = -comm.max_over_ranks(-dt_local) if comm else dt_local
     rccl = comm_audit(comm, comm_kind, rank, world) if comm else None
 
-    # reference-semantics rate (VAD on energy slots, gender on speech slots), one step, for the record
-    step(False)
-    dt_ref, (lseg_ref, _), _ = timed(1, False)
-    assert lseg_ref == lseg or args.timing_only, "dense and reference-semantics passes disagree"
+    # (--full) reference-semantics rate (VAD on energy slots, gender on speech slots), one step, for the record
+    dt_ref = None
+    if args.full:
+        step(False)
+        dt_ref, (lseg_ref, _), _ = timed(1, False)
+        assert lseg_ref == lseg or args.timing_only, "dense and reference-semantics passes disagree"
     P = (seg.ctx.T + 1) // 2
     slots = {lab: 0 for lab in ('noEnergy', 'music', 'noise', 'female', 'male')}
     for lab, a, b in lseg:
         slots[lab] = slots.get(lab, 0) + (b - a)
 
-    # ---- roofline, measured live with HIP events on the library's own stream around every launch of one extra dense step
-    # (every rank runs it: the step holds the collective; rank 0's context is read)
-    pj = _pmc_static()
-    seg.ctx.prof_enable(True)
-    seg.ctx.prof_reset()
-    step(True)
-    conv_ms, conv_launches, conv_flops = seg.ctx.prof_get(0)
-    sk_ms, sk_launches, _ = seg.ctx.prof_get(1)
-    other_ms, other_launches, _ = seg.ctx.prof_get(2)
-    peak_tf = MFMA_BF16_PEAK_TF if x3 else MFMA_F32_PEAK_TF
-    ktab, kdom = gemm_kernel_table([seg.ctx], peak_tf, pj)
-    seg.ctx.prof_enable(False)
-    all_tf = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    sk_bytes = n * 2 + seg.ctx.T * 25 * 4                # PCM16 in + (24 mel + 1 loge) f32 out
-    kd = kdom or {"kernel": None, "achieved": 0.0, "frac": 0.0, "flops_per_launch": 0.0, "avg_launch_ms": 0.0, "launches": 0, "ms_per_step": 0.0}
-    traffic_src = ("static_from_profiles: profiles/pmc_latest.json = rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes (separate runs) of "
-                   + str(pj.get('source', 'bench.py --minutes 20 --steps 1 --warmup 0 of the round-3 build'))
-                   + "; per launch of THIS instantiation, 2 x FETCH_SIZE + WRITE_SIZE (the guide's gfx950 correction for 16-byte-per-lane "
-                     "reads); PMC counters cannot be collected inside a bench run, and rocprofv3 --pmc crashes on the 1 h recording "
-                     "(profiles/r05_pmc_1h_attempt.txt): the PMC run's bytes per launch are scaled by this run's / the PMC run's algorithmic "
-                     "flops per launch of the same instantiation (traffic_scale_to_this_run; same pass geometry, other mix of full and "
-                     "remainder passes)")
-    roofline = {"bound": "mfma",
-                "kernel": kd["kernel"],
-                "achieved": kd["achieved"], "peak": peak_tf, "unit": "TFLOP/s", "frac": kd["frac"],
-                "traffic": kd.get("traffic_per_launch_static"), "traffic_source": traffic_src,
-                "traffic_pmc_run_mean_launch": kd.get("traffic_per_launch_pmc_run"), "traffic_scale_to_this_run": kd.get("traffic_scale_to_this_run"),
-                "frac_own_flops": kd["frac"] * _own_flops_share(seg, kd["kernel"]),
-                "flops_per_launch": kd["flops_per_launch"], "avg_launch_ms": kd["avg_launch_ms"],
-                "launches_per_step": kd["launches"], "kernel_ms_per_step": kd["ms_per_step"],
-                "mfma_executed_tflops": kd["achieved"] * (3 if x3 else 1),
-                # what the matrix pipe SUSTAINS under the chip's power cap on register-resident operands with every CU busy
-                # (tools/microbench/mfma_power_cap.hip, profiles/r06_mfma_power_cap.txt; static: measured once per round, on one box)
-                "sustained_mfma_ceiling": ({"f16_relu_data_tflops": 1620.0, "bf16_relu_data_tflops": 1715.0, "zeros_tflops": 2440.0,
-                                            "frac_of_ceiling": kd["achieved"] * 3 / (1620.0 if args.precision == 'f16x3' else 1715.0),
-                                            "what": "v_mfma_f32_32x32x16 with nothing else in the loop, 0.4-1.3 s per case: random-normal "
-                                                    "operands with relu'd A 1.62 PF (f16) / 1.72 PF (bf16) of the 2.5 PF dense peak, zeros "
-                                                    "2.44 PF -- the clock follows the power the operands' bit activity costs; frac_of_ceiling = "
-                                                    "this kernel's EXECUTED MFMA rate over that figure (profiles/r06_mfma_power_cap.txt)"}
-                                           if x3 else None),
-                "what": ("the kernel INSTANTIATION with the most HIP-event time in one dense step (template arguments spelled out: "
-                         "<KH,KW,PADDED,TR,FUSED,NH,EPI>); achieved = its algorithmic flops per launch / its average launch duration. "
-                         "split modes (f16x3 / bf16x3): three v_mfma_f32_32x32x16_{f16,bf16} per k-step on 16-bit hi/lo operand halves -- the "
-                         "matrix pipe executes 3 x the algorithmic flops, so frac <= 1/3 by construction; the first layer of a fused launch "
-                         "(2.5 % of its flops) is counted as the reference computes it (once per window) although it runs once per log-mel "
-                         "row: frac_own_flops leaves that credit out")
-                        if x3 else "conv_igemm_kernel (conv2d/dense implicit GEMM on v_mfma_f32_32x32x2_f32)",
-                "kernels": ktab,
-                "all_gemm_launches": {"achieved": all_tf, "frac": all_tf / peak_tf, "kernel_ms_per_step": conv_ms, "launches_per_step": conv_launches,
-                                      "flops_per_step": conv_flops,
-                                      "traffic_per_launch_static": pj.get('conv_hbm_bytes_per_launch_corrected_' + args.precision),
-                                      "traffic_per_launch_static_raw": pj.get('conv_hbm_bytes_per_launch_' + args.precision)},
-                "secondary": {"kernel": "sidekit_kernel (PCM16 -> log-energy + 24-band log-mel)", "bound": "hbm",
-                              "achieved": sk_bytes / (sk_ms * 1e-3) / 1e9 if sk_ms > 0 else 0.0, "peak": HBM_PEAK_GBS,
-                              "unit": "GB/s", "frac": (sk_bytes / (sk_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if sk_ms > 0 else 0.0,
-                              "kernel_ms_per_step": sk_ms, "algorithmic_bytes": sk_bytes},
-                "other_kernels_ms_per_step": other_ms}
+    # ---- (--full) roofline, measured live on one extra dense step (every rank runs it: the step holds the collective)
+    roofline = segmenter_roofline(seg, step, args, n) if args.full else None
 
-    # ---- exact-f32 companion (ISS_PREC_F32: v_mfma_f32_32x32x2_f32, bit-wise an fmaf chain), one timed dense step
+    # ---- (--full) exact-f32 companion (ISS_PREC_F32: v_mfma_f32_32x32x2_f32, bit-wise an fmaf chain), one timed dense step
     f32c = None
-    if x3 and not args.no_f32_companion:
+    if args.full and x3 and not args.no_f32_companion:
         seg.ctx.set_precision(_native.PREC_F32)
         step(True)
         dt32, (lseg32, _), _ = timed(1, True)
@@ -1168,15 +1204,15 @@ def main():
                 "dtype": "f32 (v_mfma_f32_32x32x2_f32, exact f32 products and accumulation)"}
 
     cpu = par = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         host = pcm[:min(n, 660 * FS)].cpu().numpy()
         cpu, nsec, det = cpu_baseline(seg, host)
         par = parity_check(seg, host, nsec, det)
 
-    # ---- companions: the other configurations, driver-timed in the same line.  archive (configs[3] shape) at every N -- the
+    # ---- (--full) companions: the other configurations, driver-timed in the same line.  archive (configs[3] shape) at every N -- the
     # file-based path gets its own 1 -> N curve --, batch (configs[2]) and vbx (configs[4]) on one GPU.
     companions = None
-    if not args.no_companions:
+    if args.full and not args.no_companions:
         del pcm
         torch.cuda.empty_cache()
         companions = {}
@@ -1216,15 +1252,17 @@ def main():
                        "vad_flops_per_slot": vad_f, "gender_flops_per_slot": gen_f,
                        "parallelism": (f"file-parallel x{world} (one recording per rank, no data-path collective), one all-gather of int32 "
                                        f"segment tables per step: {comm_kind}") if world > 1 else "single GPU",
-                       "segments": len(lseg), "label_slots": slots, "cnn_driven_boundaries": cnn_driven_boundaries(lseg),
-                       "reference_semantics": {"value": world * hours / dt_ref, "unit": "hours-of-audio/s",
-                                               "ms_per_step": dt_ref * 1e3,
-                                               "vad_slot_frac": 1.0 - slots['noEnergy'] / P,
-                                               "gender_slot_frac": (slots['female'] + slots['male']) / P}},
-            "roofline": roofline,
+                       "segments": len(lseg), "label_slots": slots, "cnn_driven_boundaries": cnn_driven_boundaries(lseg)},
             "ranks": {"ms_per_step_min": dt_min / args.steps * 1e3, "ms_per_step_max": dt / args.steps * 1e3,
                       "what": "each rank's own wall time for the timed steps (barrier to barrier), min / max over the ranks"},
         }
+        if dt_ref is not None:
+            line["config"]["reference_semantics"] = {"value": world * hours / dt_ref, "unit": "hours-of-audio/s",
+                                                     "ms_per_step": dt_ref * 1e3,
+                                                     "vad_slot_frac": 1.0 - slots['noEnergy'] / P,
+                                                     "gender_slot_frac": (slots['female'] + slots['male']) / P}
+        if roofline is not None:
+            line["roofline"] = roofline
         if rccl is not None:
             line["rccl"] = rccl
         if args.comm == 'gloo' and world > 1:

@@ -227,6 +227,15 @@ def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
     assert r.returncode != 0 and not lines and '--dump-outputs' in r.stderr
 
 
+def test_bench_accepts_full():
+    """`--full` (everything besides the headline, after the timed steps) is an option of the command line: a run given it prints
+    its one line with the timed steps' figures."""
+    r, lines = _run_bench(['--gpus', '1', '--steps', '2', '--warmup', '0', '--minutes', '1', '--full',
+                           '--fake-device', 'tests.fake_bench_device:make'])
+    assert r.returncode == 0 and len(lines) == 1, r.stdout + r.stderr
+    assert lines[0]['steps'] == 2 and lines[0]['ms_per_step'] >= 10.0
+
+
 def test_bench_dump_outputs_samples_above_the_limit(tmp_path, monkeypatch):
     """Outputs larger than the dump limit keep a fixed, seeded sample of their rows (in order) with the row indices beside them."""
     import bench

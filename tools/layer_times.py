@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-layer kernel times of the ResNet-101 (vbx) program from a rocprofv3 --kernel-trace result (rocpd SQLite), joined
 with each layer's algorithmic flops and activation bytes:  python tools/layer_times.py <results.db> [batch_windows]
-Run on the GPU box right after:  rocprofv3 --kernel-trace -d D -o r -- python bench.py --workload vbx --steps 1 --warmup 0 --no-cpu-baseline"""
+Run on the GPU right after:  rocprofv3 --kernel-trace -d D -o r -- python bench.py --workload vbx --full --steps 1 --warmup 0 --no-cpu-baseline"""
 import os
 import sqlite3
 import sys
