@@ -24,6 +24,19 @@ MAX_NETS = 8
 RS_JOB = np.dtype([('src_offset', '<i8'), ('frames_in', '<i8'), ('channels', '<i4'), ('format', '<i4'), ('filter', '<i4'),
                    ('reserved', '<i4'), ('dst_offset', '<i8'), ('frames_out', '<i8')])
 RS_FORMAT = {np.dtype(np.uint8): 0, np.dtype('<i2'): 1, np.dtype('<i4'): 2, np.dtype('<f4'): 3, np.dtype('<f8'): 4}
+# iss_flac_info / iss_flac_frame / iss_flac_job (include/iss.h)
+FLAC_INFO = np.dtype([('sample_rate', '<i4'), ('channels', '<i4'), ('bps', '<i4'), ('min_block', '<i4'), ('max_block', '<i4'),
+                      ('reserved', '<i4'), ('total_samples', '<i8')])
+FLAC_FRAME = np.dtype([('offset', '<i8'), ('length', '<i8'), ('first_sample', '<i8'), ('block_size', '<i4'),
+                       ('channel_mode', '<i4'), ('bps', '<i4'), ('header_bytes', '<i4')])
+FLAC_JOB = np.dtype([('src_offset', '<i8'), ('frame_begin', '<i8'), ('nframes', '<i8'), ('frames_total', '<i8'), ('channels', '<i4'),
+                     ('bps', '<i4'), ('output', '<i4'), ('filter', '<i4'), ('dst_offset', '<i8'), ('frames_out', '<i8')])
+FLAC_TO_SIGNAL, FLAC_TO_STAGE = 0, 1
+# ISS_FLAC_* frame status codes -> reason
+FLAC_STATUS = {1: 'reserved subframe type', 2: 'subframe header padding bit set', 3: 'wasted bits exceed the sample size',
+               4: 'reserved residual coding method', 5: 'residual partition order does not fit the block',
+               6: 'invalid LPC precision', 7: 'negative LPC shift', 8: 'residual overruns the frame',
+               9: 'nonzero padding before the footer', 10: 'subframes end before the footer', 11: 'CRC-16 mismatch'}
 
 
 class NativeError(RuntimeError):
@@ -70,6 +83,12 @@ def lib():
         'iss_resample_pcm16': (C.c_int, [vp, vp, i64, vp, i32, i64]),
         'iss_get_signal_pcm16': (C.c_int, [vp, pi16, i64, i64]),
         'iss_resample_stats': (C.c_int, [vp, pi64, pi64]),
+        'iss_flac_index': (C.c_int, [vp, i64, i64, vp, vp, i64, pi64, pi64, C.c_char_p, i32]),
+        'iss_flac_crc': (C.c_int, [vp, i64, pi32, pi32]),
+        'iss_flac_decode_host': (C.c_int, [vp, i64, vp, i64, i32, i32, i64, vp, pi32]),
+        'iss_flac_decode': (C.c_int, [vp, vp, i64, vp, i64, vp, i32, i64, pi32]),
+        'iss_flac_get_stage': (C.c_int, [vp, i32, vp, i64]),
+        'iss_flac_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_host_alloc': (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
         'iss_host_free': (C.c_int, [vp, vp]),
         'iss_cnn_probs_async': (C.c_int, [vp, C.c_int, pi32, i32, pf, pu8, pi64]),
@@ -188,6 +207,48 @@ def energy_viterbi(loge, threshold, transition):
     return out
 
 
+def flac_crc(buf):
+    """(CRC-8, CRC-16) of `buf` as the FLAC frame header / footer computes them (iss_flac_crc)."""
+    b = np.frombuffer(bytes(buf), dtype=np.uint8)
+    c8, c16 = C.c_int32(), C.c_int32()
+    if lib().iss_flac_crc(C.c_void_p(b.ctypes.data), b.size, C.byref(c8), C.byref(c16)) != 0:
+        raise NativeError('iss_flac_crc failed')
+    return c8.value, c16.value
+
+
+def flac_index(buf, first_frame, info):
+    """iss_flac_index: buf = uint8 array of the whole stream, info = one FLAC_INFO record -> FLAC_FRAME rows.
+    Raises ValueError(offset, reason) for a malformed stream."""
+    L = lib()
+    inf = np.ascontiguousarray(np.array(info, dtype=FLAC_INFO).reshape(1))
+    cap = max(16, int(inf['total_samples'][0]) // max(1, int(inf['min_block'][0]) or 1) + 2) if inf['total_samples'][0] > 0 \
+        else buf.size // 64 + 16
+    err = C.create_string_buffer(256)
+    n, off = C.c_int64(), C.c_int64()
+    for _ in range(2):
+        rows = np.zeros(cap, dtype=FLAC_FRAME)
+        rc = L.iss_flac_index(C.c_void_p(buf.ctypes.data), buf.size, int(first_frame), C.c_void_p(inf.ctypes.data),
+                              C.c_void_p(rows.ctypes.data), cap, C.byref(n), C.byref(off), err, 256)
+        if rc != -5:                                   # ISS_ENOMEM: more frames than room
+            break
+        cap = buf.size // 9 + 16                       # a frame is at least 9 bytes
+    if rc != 0:
+        raise ValueError(off.value, err.value.decode())
+    return rows[:n.value].copy()
+
+
+def flac_decode_host(buf, frames, channels, bps, frames_total):
+    """iss_flac_decode_host -> (stored samples (n,) or (n, channels) int16 / int32, per-frame ISS_FLAC_* status)."""
+    fr = np.ascontiguousarray(frames, dtype=FLAC_FRAME)
+    out = np.empty((int(frames_total), int(channels)), dtype=np.int32 if bps > 16 else np.int16)
+    st = np.zeros(len(fr), dtype=np.int32)
+    rc = lib().iss_flac_decode_host(C.c_void_p(buf.ctypes.data), buf.size, C.c_void_p(fr.ctypes.data), len(fr), int(channels),
+                                    int(bps), int(frames_total), C.c_void_p(out.ctypes.data), _ptr(st, C.c_int32))
+    if rc != 0:
+        raise NativeError(f'iss_flac_decode_host failed ({rc}): bad frame rows')
+    return (out[:, 0] if channels == 1 else out), st
+
+
 class Context:
     """One device context (stream + resident signal/features + loaded networks)."""
 
@@ -304,6 +365,37 @@ class Context:
         return a.value, b.value
 
     # ---- page-locked host arrays
+    # ---- FLAC decoder (iss_flac_*): compressed frames -> resident signal (PCM16), staging buffer, or resampled
+    def flac_decode(self, src, frames, jobs, n_signal=-1):
+        """iss_flac_decode: src = 1-D uint8 array of the compressed bytes of every job, frames = FLAC_FRAME rows, jobs = rows
+        of FLAC_JOB; one H2D copy, one decode launch (+ one resample launch).  -> the per-frame status array (page-locked,
+        this context's): valid after the next synchronising call (get_loge, flac_get_stage, synchronize)."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        fr = np.ascontiguousarray(frames, dtype=FLAC_FRAME)
+        jb = np.ascontiguousarray(np.array(jobs, dtype=FLAC_JOB).reshape(-1))
+        st = self.__dict__.get('_flac_status')
+        if st is None or st.size < max(len(fr), 1):
+            if st is not None:
+                self.pinned_free(st)
+            st = self._flac_status = self.pinned_empty((int(max(len(fr), 1) * 1.25) + 256,), np.int32)
+        self._ck(self._L.iss_flac_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data), len(fr),
+                                         C.c_void_p(jb.ctypes.data), jb.size, int(n_signal), _ptr(st, C.c_int32)),
+                 'iss_flac_decode')
+        self._keep_flac = (src, fr)    # the async H2D copy reads them until the next sync
+        return st[:len(fr)]
+
+    def flac_get_stage(self, job, frames_total, channels, bps):
+        """Stored-format samples of staged job `job` of the last flac_decode: (n,) or (n, channels) int16 / int32."""
+        out = np.empty((int(frames_total), int(channels)), dtype=np.int32 if bps > 16 else np.int16)
+        self._ck(self._L.iss_flac_get_stage(self._h, int(job), C.c_void_p(out.ctypes.data), out.nbytes), 'iss_flac_get_stage')
+        return out[:, 0] if channels == 1 else out
+
+    def flac_stats(self):
+        """(FLAC decode launches, frames decoded) since the context was created."""
+        a, b = C.c_int64(), C.c_int64()
+        self._ck(self._L.iss_flac_stats(self._h, C.byref(a), C.byref(b)), 'iss_flac_stats')
+        return a.value, b.value
+
     def pinned_empty(self, shape, dtype):
         """numpy array backed by hipHostMalloc memory (freed with the context, or by `pinned_free`)."""
         dt = np.dtype(dtype)

@@ -84,6 +84,11 @@ struct iss_ctx {
     DevBuf rs_src, rs_jobs;
     int64_t rs_launches = 0, rs_jobs_done = 0;
 
+    // FLAC decoder (flac.hip): compressed bytes, frame rows, per-frame status and the staging buffer of the last call
+    DevBuf flac_src, flac_frames, flac_status, flac_stage;
+    std::vector<int64_t> flac_stage_off, flac_stage_bytes;   // per job of the last call (-1: not staged)
+    int64_t flac_launches = 0, flac_frames_done = 0;
+
     // resident features
     DevBuf mspec, loge;
     int32_t T = 0;
@@ -158,6 +163,21 @@ void iss_prof_row(iss_ctx* c, int row);      // op-program row of the launch bra
 void iss_prof_inst(iss_ctx* c, const char* fmt, ...);   // kernel instantiation of the launch bracketed last (printf-style name)
 void iss_prof_end(iss_ctx* c);
 void iss_prof_collect(iss_ctx* c);
+
+// resample.hip: a validated set of resample jobs (device descriptors, tiles, LDS), launched from any device source
+struct RsJobDev {
+    int64_t src_off, n_in, dst_off, n_out, tile_base;
+    const double* taps;
+    int32_t ch, fmt, up, down, hl, tile, lds_tab, pad;
+};
+struct IssRsPlan {
+    std::vector<RsJobDev> dj;
+    int64_t tiles = 0, lds = 0;
+};
+// `ranges`: destination ranges of other writers of the same call, checked for overlap with the jobs' (error texts start with `who`)
+int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, int32_t njobs, int64_t src_bytes, int64_t nsig,
+                      std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan);
+int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& plan);
 
 // implemented in the .hip files
 int iss_launch_sidekit(iss_ctx* c);

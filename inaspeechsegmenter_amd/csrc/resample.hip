@@ -24,12 +24,6 @@ constexpr int RS_THREADS = 256;
 constexpr int64_t RS_LDS_MAX = 160 * 1024;         // bytes of LDS one workgroup may use on gfx950
 constexpr int64_t RS_SPAN_MAX = 64 * 1024;         // a tile's input span (float64) is kept under this when R > 1
 
-struct RsJobDev {
-    int64_t src_off, n_in, dst_off, n_out, tile_base;
-    const double* taps;
-    int32_t ch, fmt, up, down, hl, tile, lds_tab, pad;
-};
-
 __device__ __forceinline__ double to_f64(uint8_t x) { return __ddiv_rn(__dsub_rn((double)x, 128.0), 128.0); }
 __device__ __forceinline__ double to_f64(int16_t x) { return __ddiv_rn((double)x, 32768.0); }
 __device__ __forceinline__ double to_f64(int32_t x) { return __ddiv_rn((double)x, 2147483648.0); }
@@ -139,44 +133,35 @@ extern "C" int iss_resample_filter(iss_ctx* c, int32_t up, int32_t down, const d
     return ISS_OK;
 }
 
-extern "C" int iss_resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
-                                  int64_t n_signal) {
-    if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0))
-        return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: bad argument");
-    ISS_HIP(c, hipSetDevice(c->device));
-    int64_t nsig = n_signal;
-    if (n_signal < 0) {
-        if (c->sig_kind != 1 || c->sig_ptr != c->sig.p)
-            return iss_fail(c, ISS_ESTATE, "iss_resample_pcm16: n_signal < 0 needs a PCM16 signal uploaded by iss_signal_pcm16");
-        nsig = c->sig_n;
-    }
+int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, int32_t njobs, int64_t src_bytes, int64_t nsig,
+                      std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan) {
     // validate every job, build the device descriptors and the tile prefix sum
-    std::vector<RsJobDev> dj((size_t)njobs);
-    std::vector<std::pair<int64_t, int64_t>> ranges;
+    std::vector<RsJobDev>& dj = plan.dj;
+    dj.assign((size_t)njobs, RsJobDev{});
     int64_t tiles = 0, lds = 0;
     for (int32_t k = 0; k < njobs; ++k) {
         const iss_resample_job& J = jobs[k];
         if (J.format < ISS_RS_U8 || J.format > ISS_RS_F64)
-            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: bad format %d", k, J.format);
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: bad format %d", who, k, J.format);
         if (J.channels < 1 || J.channels > 1024)
-            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: %d channels", k, J.channels);
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: %d channels", who, k, J.channels);
         if (J.filter < 0 || J.filter >= (int32_t)c->rs_filters.size())
-            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: unknown filter %d", k, J.filter);
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: unknown filter %d", who, k, J.filter);
         const iss_ctx::RsFilter& f = c->rs_filters[(size_t)J.filter];
         const int64_t esz = kFmtBytes[J.format];
         if (J.frames_in < 1 || J.frames_in > (int64_t(1) << 40) / (esz * J.channels))
-            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: %lld frames", k, (long long)J.frames_in);
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: %lld frames", who, k, (long long)J.frames_in);
         const int64_t nbytes = J.frames_in * J.channels * esz;
         if (J.src_offset < 0 || J.src_offset % esz != 0 || J.src_offset > src_bytes - nbytes)
-            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: source bytes [%lld, %lld) outside the %lld-byte buffer or "
-                            "not aligned to %lld", k, (long long)J.src_offset, (long long)(J.src_offset + nbytes),
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: source bytes [%lld, %lld) outside the %lld-byte buffer or "
+                            "not aligned to %lld", who, k, (long long)J.src_offset, (long long)(J.src_offset + nbytes),
                             (long long)src_bytes, (long long)esz);
         const int64_t nout = (J.frames_in * f.up + f.down - 1) / f.down;
         if (J.frames_out != nout)
-            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: frames_out %lld, ceil(%lld * %d / %d) = %lld", k,
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: frames_out %lld, ceil(%lld * %d / %d) = %lld", who, k,
                             (long long)J.frames_out, (long long)J.frames_in, f.up, f.down, (long long)nout);
         if (J.dst_offset < 0 || J.dst_offset > nsig - nout)
-            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: job %d: output [%lld, %lld) outside the %lld-sample signal", k,
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: output [%lld, %lld) outside the %lld-sample signal", who, k,
                             (long long)J.dst_offset, (long long)(J.dst_offset + nout), (long long)nsig);
         ranges.push_back({J.dst_offset, J.dst_offset + nout});
         int64_t tile = RS_THREADS * 4;
@@ -194,45 +179,70 @@ extern "C" int iss_resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes
     std::sort(ranges.begin(), ranges.end());
     for (size_t k = 1; k < ranges.size(); ++k)
         if (ranges[k].first < ranges[k - 1].second)
-            return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: output ranges [%lld, %lld) and [%lld, %lld) overlap",
+            return iss_fail(c, ISS_EINVAL, "%s: output ranges [%lld, %lld) and [%lld, %lld) overlap", who,
                             (long long)ranges[k - 1].first, (long long)ranges[k - 1].second, (long long)ranges[k].first,
                             (long long)ranges[k].second);
-    if (tiles > 0x7fffffffLL) return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: %lld tiles in one call", (long long)tiles);
-    if (n_signal >= 0) {                                   // a signal of its own, zero wherever no job writes
-        int rc = iss_reserve(c, c->sig, (size_t)nsig * 2 + 16);
-        if (rc) return rc;
-        if (nsig > 0) ISS_HIP(c, hipMemsetAsync(c->sig.p, 0, (size_t)nsig * 2, c->stream));
-        c->sig_ptr = c->sig.p; c->sig_kind = 1; c->sig_n = nsig;
-    }
-    c->have_feats = false;
-    if (njobs == 0) return ISS_OK;
-    int rc = iss_reserve(c, c->rs_src, (size_t)std::max<int64_t>(src_bytes, 16));
+    if (tiles > 0x7fffffffLL) return iss_fail(c, ISS_EINVAL, "%s: %lld tiles in one call", who, (long long)tiles);
+    plan.tiles = tiles;
+    plan.lds = lds;
+    return ISS_OK;
+}
+
+int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& plan) {
+    const std::vector<RsJobDev>& dj = plan.dj;
+    if (dj.empty()) return ISS_OK;
+    int rc = iss_reserve(c, c->rs_jobs, dj.size() * sizeof(RsJobDev));
     if (rc) return rc;
-    rc = iss_reserve(c, c->rs_jobs, dj.size() * sizeof(RsJobDev));
-    if (rc) return rc;
-    iss_prof_begin(c, ISS_PROF_OTHER, 0.0);
-    iss_prof_inst(c, "resample_h2d(%lld B)", (long long)src_bytes);
-    if (src_bytes > 0) ISS_HIP(c, hipMemcpyAsync(c->rs_src.p, src, (size_t)src_bytes, hipMemcpyHostToDevice, c->stream));
-    iss_prof_end(c);
     void* pinned = nullptr;
     int slot = -1;
     rc = iss_stage_host(c, dj.data(), dj.size() * sizeof(RsJobDev), &pinned, &slot);
     if (rc) return rc;
     ISS_HIP(c, hipMemcpyAsync(c->rs_jobs.p, pinned, dj.size() * sizeof(RsJobDev), hipMemcpyHostToDevice, c->stream));
     iss_stage_mark(c, slot);
-    if (lds > 64 * 1024)
-        ISS_HIP(c, hipFuncSetAttribute((const void*)resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (plan.lds > 64 * 1024)
+        ISS_HIP(c, hipFuncSetAttribute((const void*)resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
     double flops = 0;
     for (const RsJobDev& d : dj) flops += 2.0 * (double)d.n_out * (2.0 * d.hl + 1) / d.up;
     iss_prof_begin(c, ISS_PROF_FRONTEND, flops);
     iss_prof_inst(c, "resample_kernel");
-    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)tiles), dim3(RS_THREADS), (size_t)lds, c->stream,
-                       (const uint8_t*)c->rs_src.p, (const RsJobDev*)c->rs_jobs.p, (int)njobs, (int16_t*)c->sig.p);
+    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)plan.tiles), dim3(RS_THREADS), (size_t)plan.lds, c->stream,
+                       dev_src, (const RsJobDev*)c->rs_jobs.p, (int)dj.size(), (int16_t*)c->sig.p);
     ISS_HIP(c, hipGetLastError());
     iss_prof_end(c);
     c->rs_launches += 1;
-    c->rs_jobs_done += njobs;
+    c->rs_jobs_done += (int64_t)dj.size();
     return ISS_OK;
+}
+
+extern "C" int iss_resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
+                                  int64_t n_signal) {
+    if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0))
+        return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: bad argument");
+    ISS_HIP(c, hipSetDevice(c->device));
+    int64_t nsig = n_signal;
+    if (n_signal < 0) {
+        if (c->sig_kind != 1 || c->sig_ptr != c->sig.p)
+            return iss_fail(c, ISS_ESTATE, "iss_resample_pcm16: n_signal < 0 needs a PCM16 signal uploaded by iss_signal_pcm16");
+        nsig = c->sig_n;
+    }
+    IssRsPlan plan;
+    int rc = iss_resample_plan(c, jobs, njobs, src_bytes, nsig, {}, "iss_resample_pcm16", plan);
+    if (rc) return rc;
+    if (n_signal >= 0) {                                   // a signal of its own, zero wherever no job writes
+        rc = iss_reserve(c, c->sig, (size_t)nsig * 2 + 16);
+        if (rc) return rc;
+        if (nsig > 0) ISS_HIP(c, hipMemsetAsync(c->sig.p, 0, (size_t)nsig * 2, c->stream));
+        c->sig_ptr = c->sig.p; c->sig_kind = 1; c->sig_n = nsig;
+    }
+    c->have_feats = false;
+    if (njobs == 0) return ISS_OK;
+    rc = iss_reserve(c, c->rs_src, (size_t)std::max<int64_t>(src_bytes, 16));
+    if (rc) return rc;
+    iss_prof_begin(c, ISS_PROF_OTHER, 0.0);
+    iss_prof_inst(c, "resample_h2d(%lld B)", (long long)src_bytes);
+    if (src_bytes > 0) ISS_HIP(c, hipMemcpyAsync(c->rs_src.p, src, (size_t)src_bytes, hipMemcpyHostToDevice, c->stream));
+    iss_prof_end(c);
+    return iss_resample_launch(c, (const uint8_t*)c->rs_src.p, plan);
 }
 
 extern "C" int iss_resample_stats(iss_ctx* c, int64_t* launches, int64_t* jobs) {

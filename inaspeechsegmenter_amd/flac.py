@@ -1,0 +1,170 @@
+"""FLAC without ffmpeg: the container, the frame index and the sources the device decodes.
+
+The reference's ffmpeg-free read is `soundfile.read` (io.py:36-55), and libsndfile decodes FLAC.  Here a FLAC file (bytes
+starting with `fLaC`, optionally behind an ID3v2 tag) reads exactly like its WAV twin -- the PCM WAV of the same samples,
+rate and channels, 16 bits for 8/16-bit streams and 24 bits for 24-bit streams.  This module parses the metadata blocks
+(STREAMINFO used; PADDING, APPLICATION, SEEKTABLE, VORBIS_COMMENT, CUESHEET, PICTURE and reserved types skipped) and has the
+compiled host code index the frames (iss_flac_index); the samples are decoded by flac_decode_kernel on the device
+(`FlacSource`, Segmenter / pipeline) or by the host build of the same decoder (`read_host`, io.py).
+"""
+import struct
+
+import numpy as np
+
+from . import _native
+
+MAGIC = b'fLaC'
+# benchmark switch (tools/bench_flac.py), not a user option: True makes the ffmpeg-free read decode FLAC on the host
+# (iss_flac_decode_host in the decode threads) instead of handing the compressed frames to the device
+_HOST_DECODE = False
+_METADATA = {0: 'STREAMINFO', 1: 'PADDING', 2: 'APPLICATION', 3: 'SEEKTABLE', 4: 'VORBIS_COMMENT', 5: 'CUESHEET', 6: 'PICTURE'}
+
+
+def _id3_end(buf):
+    """Offset after a leading ID3v2 tag (0 if there is none)."""
+    if len(buf) >= 10 and buf[:3] == b'ID3':
+        size = 0
+        for b in buf[6:10]:
+            size = (size << 7) | (b & 0x7F)
+        return 10 + size + (10 if buf[5] & 0x10 else 0)          # footer flag
+    return 0
+
+
+def is_flac(buf):
+    """Do these (leading) bytes start a native FLAC stream?"""
+    p = _id3_end(buf)
+    return buf[p:p + 4] == MAGIC
+
+
+def is_ogg_flac(buf):
+    return buf[:4] == b'OggS' and b'\x7fFLAC' in buf[:128]
+
+
+def sniff(path):
+    """Is the file at `path` a FLAC stream (by its bytes, whatever its name)?"""
+    with open(path, 'rb') as f:
+        head = f.read(10)
+        p = _id3_end(head)
+        f.seek(p)
+        return f.read(4) == MAGIC
+
+
+class FlacStream:
+    """A parsed FLAC file: STREAMINFO, and the frames indexed by iss_flac_index (offsets relative to `audio`)."""
+    __slots__ = ('name', 'audio', 'base', 'frames', 'sr', 'ch', 'bps', 'n')
+
+    def __init__(self, buf, name='<buffer>'):
+        buf = bytes(buf)
+        p = _id3_end(buf)
+        if buf[p:p + 4] != MAGIC:
+            raise ValueError(f'{name}: not a FLAC stream')
+        p += 4
+        info, first = None, True
+        while True:
+            if p + 4 > len(buf):
+                raise ValueError(f'{name}: truncated metadata at byte {p}')
+            hdr = buf[p]
+            typ, size = hdr & 0x7F, int.from_bytes(buf[p + 1:p + 4], 'big')
+            if typ == 127:
+                raise ValueError(f'{name}: invalid metadata block type 127 at byte {p}')
+            if first and typ != 0:
+                raise ValueError(f'{name}: the first metadata block at byte {p} is {_METADATA.get(typ, typ)}, not STREAMINFO')
+            if p + 4 + size > len(buf):
+                raise ValueError(f'{name}: truncated metadata block at byte {p}')
+            if typ == 0:
+                if size != 34 or not first:
+                    raise ValueError(f'{name}: bad STREAMINFO block at byte {p}')
+                b = buf[p + 4:p + 4 + 34]
+                minb, maxb = struct.unpack('>HH', b[:4])
+                v = int.from_bytes(b[10:18], 'big')
+                sr, ch, bps, total = v >> 44, ((v >> 41) & 7) + 1, ((v >> 36) & 31) + 1, v & ((1 << 36) - 1)
+                info = (sr, ch, bps, minb, maxb, 0, total)
+            first = False
+            p += 4 + size
+            if hdr & 0x80:
+                break
+        sr, ch, bps = info[0], info[1], info[2]
+        if bps not in (8, 16, 24):
+            raise ValueError(f'{name}: {bps}-bit FLAC is not supported without ffmpeg (8, 16 and 24 bits are)')
+        if sr < 1:
+            raise ValueError(f'{name}: STREAMINFO sample rate {sr}')
+        arr = np.frombuffer(buf, dtype=np.uint8)
+        try:
+            frames = _native.flac_index(arr, p, info)
+        except ValueError as exc:
+            off, why = exc.args
+            raise ValueError(f'{name}: frame at byte {off}: {why}') from None
+        frames['offset'] -= p
+        self.name, self.audio, self.base, self.frames = name, arr[p:], p, frames
+        self.sr, self.ch, self.bps = sr, ch, bps
+        self.n = int(frames['first_sample'][-1] + frames['block_size'][-1])
+
+    def check(self, status):
+        """Raise ValueError for the first frame whose decode status (ISS_FLAC_*) is not 0."""
+        bad = np.flatnonzero(np.asarray(status))
+        if bad.size:
+            k = int(bad[0])
+            why = _native.FLAC_STATUS.get(int(status[k]), f'status {int(status[k])}')
+            raise ValueError(f'{self.name}: frame at byte {self.base + int(self.frames["offset"][k])}: {why}')
+
+    def decode_host(self):
+        """The stored samples ((n,) or (n, ch) int16 / int32 << 8) by the host build of the decoder."""
+        x, st = _native.flac_decode_host(self.audio, self.frames, self.ch, self.bps, self.n)
+        self.check(st)
+        return x
+
+
+class FlacSource:
+    """A FLAC file for the device decoder.  `size` is its 16 kHz length (resampled when `resample`), so it stands where a
+    decoded signal's `size` is read, like segmenter.RawSource.  kind: 'pcm' (mono 8/16-bit at 16 kHz: PCM16 straight into
+    the signal), 'float' (mono 24-bit at 16 kHz: the float path of a 24-bit WAV), 'resample' (downmixed and resampled)."""
+    __slots__ = ('s', 'kind', 'size', 'nbytes')
+
+    def __init__(self, stream, kind):
+        from . import resample
+        self.s, self.kind = stream, kind
+        self.size = resample.out_len(stream.n, stream.sr) if kind == 'resample' else stream.n
+        self.nbytes = stream.audio.nbytes
+
+    def job(self, ctx, src_offset, frame_begin, dst_offset):
+        """Its FLAC_JOB row: into the signal at dst_offset ('pcm'), resampled to dst_offset ('resample'), or staged ('float')."""
+        s = self.s
+        if self.kind == 'pcm':
+            return (src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_SIGNAL, -1, dst_offset, 0)
+        if self.kind == 'resample':
+            fid, _, _ = ctx.resample_filter(s.sr)
+            return (src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_STAGE, fid, dst_offset, self.size)
+        return (src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_STAGE, -1, 0, 0)
+
+
+def source(stream, resample=False):
+    """The FlacSource of a parsed stream under the WAV-twin rules of the ffmpeg-free read: without `resample`, a rate other
+    than 16 kHz is the WAV path's AssertionError and several channels its ValueError; 16 kHz mono reads the same either way."""
+    from . import resample as R
+    if stream.sr == R.SR_OUT and stream.ch == 1:
+        return FlacSource(stream, 'float' if stream.bps > 16 else 'pcm')
+    if not resample:
+        assert stream.sr == 16_000, \
+            f'Without ffmpeg, inaSpeechSegmenter can only take files sampled ' \
+            f'at 16000 Hz. The file {stream.name} is sampled at {stream.sr} Hz.'
+        raise ValueError(f'{stream.name}: {stream.ch} channels; without ffmpeg only mono files are supported')
+    R.check_rate(stream.sr)
+    return FlacSource(stream, 'resample')
+
+
+def decode_on(ctx, src):
+    """One file on its own.  'pcm' / 'resample': the resident signal becomes its 16 kHz PCM16 -> the per-frame status, valid
+    after the context's next synchronising call (check it with src.s.check).  'float': -> the stored int32 samples (checked)."""
+    s = src.s
+    st = ctx.flac_decode(s.audio, s.frames, [src.job(ctx, 0, 0, 0)], n_signal=0 if src.kind == 'float' else src.size)
+    if src.kind == 'float':
+        x = ctx.flac_get_stage(0, s.n, s.ch, s.bps)
+        s.check(st)
+        return x
+    return st
+
+
+def read_host(buf, name='<buffer>'):
+    """ffmpeg-free host read: -> (stored samples, (n,) or (n, C), sr), the arrays io._parse_wav returns for the WAV twin."""
+    stream = FlacStream(buf, name)
+    return stream.decode_host(), stream.sr

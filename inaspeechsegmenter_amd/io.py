@@ -8,7 +8,8 @@ Mirrors io.py:32-79 `media2sig16kmono(medianame, start_sec, stop_sec, ffmpeg, dt
     with the reference's wording (io.py:37-50); the file must already be 16 kHz (io.py:53-55).
 Decode stays on the host (north star); soundfile/libsndfile is not available in the target
 image, so RIFF/WAVE is parsed here with libsndfile's conversion rules (PCM16 -> x/32768,
-unknown chunks skipped).  `decode_pcm` is the entry the native pipeline uses: it keeps
+unknown chunks skipped).  FLAC (flac.py) reads exactly like its WAV twin, decoded here by the host build of the
+device's frame decoder.  `decode_pcm` is the entry the native pipeline uses: it keeps
 PCM16 as int16 so the device does the x/32768 scaling (2 B/sample over PCIe, not 4).
 """
 import os
@@ -62,6 +63,18 @@ def _parse_wav(buf, name='<buffer>'):
     return a, sr
 
 
+def _read_nofmpeg(medianame):
+    """ffmpeg-free read of a WAV or FLAC file -> (samples as stored, sr) as _parse_wav returns them."""
+    from . import flac
+    with open(medianame, 'rb') as f:
+        buf = f.read()
+    if flac.is_flac(buf):
+        return flac.read_host(buf, medianame)
+    if flac.is_ogg_flac(buf):
+        raise ValueError(f'{medianame}: Ogg-FLAC (FLAC in an Ogg container) is not supported without ffmpeg')
+    return _parse_wav(buf, medianame)
+
+
 def _to_float(a, dtype):
     """libsndfile's integer -> float scaling."""
     if a.dtype == np.int16:
@@ -106,8 +119,7 @@ def decode_pcm(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg'):
     ffmpeg), else float32 holding exactly what soundfile's float32 read would return."""
     if ffmpeg is None:
         _check_no_ffmpeg(medianame, start_sec, stop_sec)
-        with open(medianame, 'rb') as f:
-            a, sr = _parse_wav(f.read(), medianame)
+        a, sr = _read_nofmpeg(medianame)
         assert sr == 16_000, \
             f'Without ffmpeg, inaSpeechSegmenter can only take files sampled ' \
             f'at 16000 Hz. The file {medianame} is sampled at {sr} Hz.'
@@ -121,10 +133,9 @@ def decode_pcm(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg'):
 
 
 def decode_source(medianame):
-    """ffmpeg-free read of any WAV (Segmenter(ffmpeg=None, resample=True)): -> (samples as stored, (n,) or (n, C), sr).
-    Nothing is converted: the device downmixes, resamples and quantises (inaspeechsegmenter_amd/resample.py)."""
-    with open(medianame, 'rb') as f:
-        return _parse_wav(f.read(), medianame)
+    """ffmpeg-free read of any WAV or FLAC (Segmenter(ffmpeg=None, resample=True)): -> (samples as stored, (n,) or (n, C),
+    sr).  Nothing is converted: the device downmixes, resamples and quantises (inaspeechsegmenter_amd/resample.py)."""
+    return _read_nofmpeg(medianame)
 
 
 def media2sig16kmono(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg', dtype='float64'):

@@ -6,12 +6,15 @@ main thread runs the two Keras `predict` calls, the Viterbi smoothing and the ex
 launches, copies and Python bookkeeping become the limit.  Here files are processed in SUPER-BATCHES:
 
   decode threads   N files  ->  int16 PCM (RIFF parse, or the ffmpeg pipe); with Segmenter(resample=True) WAVs at other
-                   rates / channel counts are handed on as stored (segmenter.RawSource)
+                   rates / channel counts are handed on as stored (segmenter.RawSource); without ffmpeg FLAC files are
+                   handed on compressed, their frames indexed (flac.FlacSource)
   packer           the PCM of a super-batch (default <= 32 files / ~40 min of audio) is laid end to end in ONE page-locked
                    buffer, every file starting on a multiple of 160 samples: frame t of file f is then frame
                    off_f / 160 + t of the concatenation, and the frames that straddle two files are simply never used
                    (room is left for the resampled files, whose stored bytes go into a second page-locked buffer)
-  device worker    ONE H2D copy, ONE resample launch for all resampled files (one more H2D copy), ONE sidekit launch, one log-energy read-back; per-file energy Viterbi (compiled);
+  device worker    ONE H2D copy, ONE resample launch for all resampled files (one more H2D copy), ONE FLAC decode launch for
+                   all FLAC files (one more H2D copy of their compressed bytes; the resampled ones add one resample launch),
+                   ONE sidekit launch, one log-energy read-back (with the FLAC frame status); per-file energy Viterbi (compiled);
                    ONE iss_cnn_probs call for the VAD windows of all files, per-segment Viterbi; ONE call for the
                    gender windows, Viterbi; hand the segment lists to the exporter
   exporter         CSV / TextGrid writers
@@ -35,17 +38,21 @@ MIN_SAMPLES = 400 + FRAME_HOP * 67                  # 68 frames: shorter media t
 
 
 class _Batch:
-    __slots__ = ('idx', 'sigs', 'names')
+    __slots__ = ('idx', 'sigs', 'names', 'errs')
 
     def __init__(self):
-        self.idx, self.sigs, self.names = [], [], []
+        self.idx, self.sigs, self.names, self.errs = [], [], [], {}
 
     def samples(self):                               # 16 kHz samples (a RawSource's size is its resampled length)
         return sum(-(-s.size // FRAME_HOP) * FRAME_HOP for s in self.sigs)
 
 
 def _held(sig):
-    """What a decoded source holds, in 16-bit sample units: its samples, or a stored source's bytes / 2 when larger."""
+    """What a decoded source holds, in 16-bit sample units: its samples, or a stored source's bytes / 2 when larger; a FLAC
+    source holds its compressed bytes."""
+    from . import flac
+    if isinstance(sig, flac.FlacSource):
+        return max(1, sig.nbytes // 2)
     x = getattr(sig, 'x', None)
     return sig.size if x is None else max(sig.size, x.nbytes // 2)
 
@@ -126,6 +133,7 @@ class _Worker:
         self.ctx = ctx
         self.pin = None
         self.rpin = None                             # stored bytes of the resampled files of a pass
+        self.fpin = None                             # compressed bytes of the FLAC files of a pass
         # wall seconds this worker spent per phase since the last reset (bench.py reports them: where a step's host time goes)
         self.stats = {k: 0.0 for k in ('pack', 'features', 'energy_host', 'cnn_device', 'smooth_host', 'batches', 'files')}
 
@@ -147,6 +155,13 @@ class _Worker:
             self.rpin = self.ctx.pinned_empty((int(nbytes * 1.25) + 4096,), np.uint8)
         return self.rpin
 
+    def flac_pinned(self, nbytes):
+        if self.fpin is None or self.fpin.size < nbytes:
+            if self.fpin is not None:
+                self.ctx.pinned_free(self.fpin)
+            self.fpin = self.ctx.pinned_empty((int(nbytes * 1.25) + 4096,), np.uint8)
+        return self.fpin
+
     def sync_settings(self):
         """Arithmetic mode and workspace cap follow the Segmenter's own context (they may have changed since this
         worker was created: the workers are cached between calls)."""
@@ -154,8 +169,10 @@ class _Worker:
             self.ctx.mirror_settings(self.seg.ctx)
 
     def run(self, batch):
-        """-> [ [(label, start_slot, stop_slot)] per file of the batch ]"""
+        """-> [ [(label, start_slot, stop_slot)] per file of the batch ]; None for a FLAC file whose frames the device found
+        malformed (its message in batch.errs)"""
         from . import segmenter as S
+        from . import flac
         seg, ctx = self.seg, self.ctx
         st = self.stats
         t_ = time.perf_counter()
@@ -164,11 +181,14 @@ class _Worker:
             offs.append(pos)
             pos += -(-s.size // FRAME_HOP) * FRAME_HOP
         buf = self.pinned(pos)
-        raws = []
-        for s, o in zip(batch.sigs, offs):
+        raws, flacs = [], []
+        for f, (s, o) in enumerate(zip(batch.sigs, offs)):
             if isinstance(s, S.RawSource):           # written by the resample kernel
                 buf[o:o + s.size] = 0
                 raws.append((s, o))
+            elif isinstance(s, flac.FlacSource):     # written by the FLAC decode kernel (and the resample kernel)
+                buf[o:o + s.size] = 0
+                flacs.append((f, s, o))
             elif s.dtype == np.int16:
                 buf[o:o + s.size] = s
             else:                                    # float sources: what libsndfile's float32 read holds, re-quantised is NOT exact
@@ -181,18 +201,40 @@ class _Worker:
                 rb[rpos:rpos + s.x.nbytes] = s.x.reshape(-1).view(np.uint8)
                 jobs.append(ctx.resample_job(s.x, s.sr, rpos, o))
                 rpos += -(-s.x.nbytes // 16) * 16
+        if flacs:                                    # compressed frames end to end, each file on a 16-byte boundary
+            fb = self.flac_pinned(sum(-(-s.nbytes // 16) * 16 for _, s, _ in flacs))
+            fjobs, fpos, fbeg = [], 0, 0
+            for _, s, o in flacs:
+                fb[fpos:fpos + s.nbytes] = s.s.audio
+                fjobs.append(s.job(ctx, fpos, fbeg, o))
+                fpos += -(-s.nbytes // 16) * 16
+                fbeg += len(s.s.frames)
+            frames = np.concatenate([s.s.frames for _, s, _ in flacs])
         st['pack'] += time.perf_counter() - t_; t_ = time.perf_counter()
         ctx.set_signal(buf[:pos])
         if raws:
             ctx.resample(rb[:rpos], jobs)            # one launch for every resampled file of the pass, into the signal above
+        if flacs:
+            fstat = ctx.flac_decode(fb[:fpos], frames, fjobs)   # one decode launch for every FLAC file of the pass
         ctx.sidekit()
         loge = ctx.get_loge()
+        if flacs:                                    # the frame status came back with the log-energy
+            fbeg = 0
+            for f, s, _ in flacs:
+                try:
+                    s.s.check(fstat[fbeg:fbeg + len(s.s.frames)])
+                except ValueError as exc:
+                    batch.errs[f] = 'error: %s %s' % (type(exc), exc)
+                fbeg += len(s.s.frames)
         st['features'] += time.perf_counter() - t_; t_ = time.perf_counter()
         g0 = [o // FRAME_HOP for o in offs]
         nfr = [(s.size - 400) // FRAME_HOP + 1 for s in batch.sigs]
         # energy segmentation per file (segmenter.py:261-267)
         lsegs = []
         for f in range(len(batch.sigs)):
+            if f in batch.errs:                      # a malformed FLAC file: no segments, no network rows
+                lsegs.append([])
+                continue
             le = loge[g0[f]:g0[f] + nfr[f]]
             lseg = []
             for lab, start, stop in S._binidx2seglist(S._energy_activity(le, seg.energy_ratio)[::2]):
@@ -263,7 +305,7 @@ class _Worker:
             st['smooth_host'] += time.perf_counter() - t_
         st['batches'] += 1
         st['files'] += len(batch.sigs)
-        return lsegs
+        return [None if f in batch.errs else l for f, l in enumerate(lsegs)]
 
 
 DEFAULT_BATCH_FILES = 32          # files per device pass at most ...
@@ -282,6 +324,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
     skip: set of indices not to process.  Device failures (NativeError) and exceptions raised by on_result (unwritable
     outputs) propagate to the caller: the first one is re-raised here once every stage has drained."""
     from . import segmenter as S
+    from . import flac
     batch_files = batch_files or DEFAULT_BATCH_FILES
     batch_seconds = batch_seconds or DEFAULT_BATCH_SECONDS
     workers = workers or DEFAULT_WORKERS
@@ -315,7 +358,13 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                     except BaseException as exc:                   # noqa: B902
                         failure.append(exc)
                     continue
-                if (not isinstance(sig, S.RawSource) and sig.dtype != np.int16) or sig.size < MIN_SAMPLES:
+                if isinstance(sig, S.RawSource):
+                    single = False
+                elif isinstance(sig, flac.FlacSource):
+                    single = sig.kind == 'float'             # 24-bit: the float path, as a 24-bit WAV takes
+                else:
+                    single = sig.dtype != np.int16
+                if single or sig.size < MIN_SAMPLES:
                     batch_q.put(('single', i, src, sig))
                     continue
                 cur.idx.append(i); cur.sigs.append(sig); cur.names.append(src)
@@ -371,8 +420,11 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                 lsegs = w.run(b)
                 share = (time.time() - t0) / max(len(b.idx), 1)
                 with lock:
-                    for i, src, lseg in zip(b.idx, b.names, lsegs):
-                        on_result(i, src, [(lab, a * .02, c * .02) for lab, a, c in lseg], None, share)
+                    for f, (i, src, lseg) in enumerate(zip(b.idx, b.names, lsegs)):
+                        if lseg is None:
+                            on_result(i, src, None, b.errs[f], share)
+                        else:
+                            on_result(i, src, [(lab, a * .02, c * .02) for lab, a, c in lseg], None, share)
             except BaseException as exc:                           # noqa: B902  propagate to the caller's thread
                 failure.append(exc)
 

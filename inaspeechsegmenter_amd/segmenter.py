@@ -25,6 +25,7 @@ import numpy as np
 from . import _native
 from . import tables
 from . import keras_model
+from . import flac
 from .io import decode_pcm, decode_source, _check_no_ffmpeg, _to_float
 from .export_funcs import seg2csv, seg2textgrid
 
@@ -315,7 +316,13 @@ class RawSource:
 
 def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False):
     """decode_pcm's 16 kHz mono samples; with `resample` (ffmpeg=None only) a WAV at another rate or with several channels
-    comes back as a RawSource instead of failing (16 kHz mono files are read exactly as decode_pcm reads them)."""
+    comes back as a RawSource instead of failing (16 kHz mono files are read exactly as decode_pcm reads them).  Without
+    ffmpeg a FLAC file comes back as a flac.FlacSource (compressed frames, decoded on the device like its WAV twin reads)."""
+    if ffmpeg is None:
+        _check_no_ffmpeg(medianame, start_sec, stop_sec)
+        if flac.sniff(medianame) and not flac._HOST_DECODE:
+            with open(medianame, 'rb') as f:
+                return flac.source(flac.FlacStream(f.read(), medianame), resample)
     if not resample:
         return decode_pcm(medianame, start_sec, stop_sec, ffmpeg)
     from . import resample as R
@@ -337,15 +344,24 @@ def _media2feats(medianame, start_sec, stop_sec, ffmpeg, ctx=None, resample=Fals
 
 
 def _sig2feats(ctx, sig, medianame='<signal>'):
-    """sig: 16 kHz mono samples (uploaded), or a RawSource (resampled on the device into the resident signal)."""
+    """sig: 16 kHz mono samples (uploaded), a RawSource (resampled on the device into the resident signal), or a FlacSource
+    (decoded on the device: into the signal, resampled, or -- 24-bit -- back to the host for the float path)."""
     if sig.size < 400:
         raise ValueError(f"media {medianame}: {sig.size} samples, less than one 25 ms analysis window")
+    status = None
     if isinstance(sig, RawSource):
         ctx.resample_signal(sig.x, sig.sr)
+    elif isinstance(sig, flac.FlacSource):
+        if sig.kind == 'float':
+            ctx.set_signal(_to_float(flac.decode_on(ctx, sig), np.float32))
+        else:
+            status = flac.decode_on(ctx, sig)
     else:
         ctx.set_signal(sig)
     nframes = ctx.sidekit()
     loge = ctx.get_loge()
+    if status is not None:                                      # read back with the log-energy
+        sig.s.check(status)
     difflen = 0
     if nframes < 68:                                            # segmenter.py:61-65
         difflen = 68 - nframes
@@ -462,8 +478,16 @@ class Segmenter:
 
     def load_pcm(self, medianame):
         """The 16 kHz mono samples the front end reads for `medianame` (decode_pcm's int16 or float32 array); with
-        resample=True a WAV at another rate or channel count is resampled on the device and its PCM16 copied back."""
+        resample=True a WAV at another rate or channel count is resampled on the device and its PCM16 copied back.  Without
+        ffmpeg a FLAC file is decoded on the device and its samples copied back (what decode_pcm gives for its WAV twin)."""
         sig = _load_source(medianame, None, None, self.ffmpeg, self.resample)
+        if isinstance(sig, flac.FlacSource):
+            if sig.kind == 'float':
+                return _to_float(flac.decode_on(self.ctx, sig), np.float32)
+            status = flac.decode_on(self.ctx, sig)
+            out = self.ctx.get_signal_pcm16(0, sig.size)
+            sig.s.check(status)
+            return out
         if isinstance(sig, RawSource):
             return self.ctx.get_signal_pcm16(0, self.ctx.resample_signal(sig.x, sig.sr))
         return sig

@@ -119,6 +119,88 @@ int iss_get_signal_pcm16(iss_ctx* ctx, int16_t* out, int64_t offset, int64_t n);
 /* Resample kernel launches and jobs since the context was created.                                                   */
 int iss_resample_stats(iss_ctx* ctx, int64_t* launches, int64_t* jobs);
 
+/* FLAC sources without ffmpeg (the reference reads them with soundfile.read, io.py:36-55).  The decode contract: every
+ * sample of a frame is what RFC 9639 defines (subframes CONSTANT / VERBATIM / FIXED 0-4 / LPC 1-32 with wasted bits, Rice /
+ * Rice2 residuals with escapes, left/side, side/right and mid/side decorrelation), written in the stored format of the
+ * file's WAV twin: int16 for 8- and 16-bit streams (8-bit widened x << 8), int32 x << 8 for 24-bit streams, channels
+ * interleaved.  12/20/32-bit streams are not decoded.
+ * iss_flac_index (host, no context): the frames of one stream.  buf[first_frame] is the first frame's sync code (after the
+ * metadata blocks, which the caller parses into `info`); a frame is a sync code whose header parses, passes its CRC-8, matches
+ * STREAMINFO (rate, channels, sample size, block size <= max_block) and continues the frame / sample numbering; it runs to
+ * the next such frame or to the end of `buf`.  A sync pattern inside frame data is rejected by the numbering; the CRC-16 of
+ * the decode is the final word.  -> ISS_OK with *nframes rows; ISS_EINVAL with the frame's byte offset in *err_offset and
+ * the reason in err (bad header, CRC-8, frame-sequence break, truncated frame, a nonzero STREAMINFO total that differs from
+ * the frames' sum); ISS_ENOMEM when more than `cap` frames were found (*nframes = cap: call again with more room).       */
+typedef struct {
+    int32_t sample_rate, channels, bps;   /* STREAMINFO                                                                 */
+    int32_t min_block, max_block;         /* STREAMINFO block sizes (max_block 0: not checked)                          */
+    int32_t reserved;                     /* 0                                                                          */
+    int64_t total_samples;                /* samples per channel, 0 = unknown                                           */
+} iss_flac_info;
+typedef struct {
+    int64_t offset;        /* byte offset of the frame's sync code                                                      */
+    int64_t length;        /* bytes, CRC-16 footer included                                                            */
+    int64_t first_sample;  /* per channel: the frames of a stream tile [0, total) in order                             */
+    int32_t block_size;    /* samples per channel                                                                       */
+    int32_t channel_mode;  /* 0..7: channel_mode + 1 independent channels; 8 left/side, 9 side/right, 10 mid/side      */
+    int32_t bps;           /* 8, 16 or 24 (12, 20, 32 are indexed but not decoded)                                     */
+    int32_t header_bytes;  /* frame header, CRC-8 included: the first subframe starts after it                         */
+} iss_flac_frame;
+int iss_flac_index(const uint8_t* buf, int64_t len, int64_t first_frame, const iss_flac_info* info, iss_flac_frame* frames,
+                   int64_t cap, int64_t* nframes, int64_t* err_offset, char* err, int32_t err_len);
+/* CRC-8 (poly 0x07) and CRC-16 (poly 0x8005), both init 0, unreflected, of buf[0, n) (host, no context).              */
+int iss_flac_crc(const uint8_t* buf, int64_t n, int32_t* crc8_out, int32_t* crc16_out);
+/* Frame status codes (status_out of the decoders): 0 = decoded and CRC-16 verified, else the first violation met.     */
+#define ISS_FLAC_OK               0
+#define ISS_FLAC_SUBFRAME_TYPE    1   /* reserved subframe type (or FIXED order > 4)                                   */
+#define ISS_FLAC_PAD_BIT          2   /* subframe header's zero bit set                                                */
+#define ISS_FLAC_WASTED           3   /* wasted bits >= the subframe's sample size                                     */
+#define ISS_FLAC_RESIDUAL_METHOD  4   /* reserved residual coding method                                               */
+#define ISS_FLAC_PARTITION        5   /* partition order does not divide the block, or predictor order > partition 0  */
+#define ISS_FLAC_LPC_PRECISION    6   /* LPC coefficient precision code 1111                                           */
+#define ISS_FLAC_LPC_SHIFT        7   /* negative LPC shift                                                            */
+#define ISS_FLAC_OVERRUN          8   /* subframes run past the CRC-16 footer                                          */
+#define ISS_FLAC_PADDING          9   /* nonzero byte-alignment padding                                                */
+#define ISS_FLAC_FOOTER          10   /* subframes end before the CRC-16 footer                                        */
+#define ISS_FLAC_CRC16           11   /* CRC-16 mismatch                                                               */
+/* The host build of the decoder: every row of one stream (rows of iss_flac_index, offsets into buf) into `out`
+ * (frames_total * channels samples of the stored format above), status_out[k] = ISS_FLAC_* of row k.  ISS_EINVAL (nothing
+ * decoded) when a row lies outside buf, the rows do not tile [0, frames_total), or their channels / bps differ.          */
+int iss_flac_decode_host(const uint8_t* buf, int64_t len, const iss_flac_frame* frames, int64_t nframes, int32_t channels,
+                         int32_t bps, int64_t frames_total, void* out, int32_t* status_out);
+#define ISS_FLAC_TO_SIGNAL  0   /* mono 8/16-bit at 16 kHz: PCM16 straight into the resident signal at dst_offset        */
+#define ISS_FLAC_TO_STAGE   1   /* stored-format samples into the context's staging buffer (iss_flac_get_stage), and with
+                                   filter >= 0 resampled from there into the resident signal like an iss_resample_job    */
+typedef struct {
+    int64_t src_offset;    /* byte offset in `src` that the job's frame offsets are relative to                        */
+    int64_t frame_begin;   /* the job's rows of `frames`: [frame_begin, frame_begin + nframes)                         */
+    int64_t nframes;
+    int64_t frames_total;  /* samples per channel                                                                       */
+    int32_t channels;      /* 1 .. 8                                                                                     */
+    int32_t bps;           /* 8, 16 or 24                                                                                */
+    int32_t output;        /* ISS_FLAC_TO_SIGNAL / ISS_FLAC_TO_STAGE                                                     */
+    int32_t filter;        /* TO_STAGE: iss_resample_filter id, or -1 (decode only)                                     */
+    int64_t dst_offset;    /* TO_SIGNAL, or TO_STAGE with a filter: first output sample in the resident signal          */
+    int64_t frames_out;    /* TO_STAGE with a filter: ceil(frames_total * up / down)                                    */
+} iss_flac_job;
+/* One H2D copy of `src` (the compressed frames of every job), ONE launch of flac_decode_kernel (one lane per frame, every
+ * frame of every job), and when some TO_STAGE job has a filter ONE launch of the resample kernel reading the staging
+ * buffer.  n_signal as for iss_resample_pcm16 (>= 0: a new zero-filled signal; < 0: into the last iss_signal_pcm16 upload,
+ * every sample outside the jobs' ranges stays as uploaded).  The staging buffer holds the TO_STAGE jobs in job order, each
+ * at a multiple of 16 bytes.  status_out[k] (nframes int32, page-locked memory recommended) receives the ISS_FLAC_* code
+ * of row k asynchronously: it is valid after the next synchronising call (iss_get_loge, iss_flac_get_stage,
+ * iss_synchronize, ...), so a pass reads it with its log-energy.  A frame with a nonzero status leaves garbage in its own
+ * output range only.  ISS_EINVAL (nothing launched): rows outside `src` or not tiling [0, frames_total) in order, a row in
+ * no job or in two, bad channels / bps / output, a TO_SIGNAL job that is not mono 8/16-bit, destination ranges outside the
+ * signal or overlapping, a resample job that iss_resample_pcm16 would refuse.  ISS_ESTATE: as iss_resample_pcm16.     */
+int iss_flac_decode(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
+                    const iss_flac_job* jobs, int32_t njobs, int64_t n_signal, int32_t* status_out);
+/* The stored-format samples of TO_STAGE job `job` of the last iss_flac_decode (bytes = frames_total * channels * 2 or 4)
+ * back to the host; synchronises.                                                                                       */
+int iss_flac_get_stage(iss_ctx* ctx, int32_t job, void* out, int64_t bytes);
+/* FLAC decode launches and frames since the context was created.                                                     */
+int iss_flac_stats(iss_ctx* ctx, int64_t* launches, int64_t* frames);
+
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */
 int iss_host_alloc(iss_ctx* ctx, size_t bytes, void** out);

@@ -3,7 +3,8 @@
 
 Scores every input file and writes one TSV: path, score, speech duration, number of x-vectors (a file that could not be
 read gets its error message instead).  Argument handling as scripts/ina_speech_segmenter_amd.py: -i takes paths or glob
-patterns, -b None reads 16 kHz mono WAV directly (with --resample: WAV at any rate / channel count, resampled on the GPU),
+patterns, -b None reads 16 kHz mono WAV or FLAC directly (with --resample: WAV / FLAC at any rate / channel count, resampled on
+the GPU),
 --models synthetic runs seeded stand-in weights.
 """
 import argparse
@@ -22,11 +23,11 @@ def build_parser():
     ap.add_argument('-i', '--input', nargs='+', required=True, help='media paths or glob patterns')
     ap.add_argument('-o', '--output', required=True, help='TSV file receiving path, score, speech_duration, nb_vectors')
     ap.add_argument('-c', '--criteria', choices=['bgc', 'vfp'], default='bgc', help='gender detection model criteria')
-    ap.add_argument('-b', '--ffmpeg_binary', default='ffmpeg', help="ffmpeg binary; 'None' reads 16 kHz mono WAV directly")
+    ap.add_argument('-b', '--ffmpeg_binary', default='ffmpeg', help="ffmpeg binary; 'None' reads 16 kHz mono WAV or FLAC directly (FLAC decoded on the GPU)")
     ap.add_argument('--batch_seconds', type=float, default=3600, help='audio held on the device per batch (seconds)')
     ap.add_argument('--models', default=None, help="'synthetic' = seeded stand-in weights")
     ap.add_argument('--resample', action='store_true',
-                    help='with -b None: downmix and resample WAV files of other rates / channel counts to 16 kHz mono on the GPU')
+                    help='with -b None: downmix and resample WAV / FLAC files of other rates / channel counts to 16 kHz mono on the GPU')
     return ap
 
 
