@@ -24,6 +24,13 @@ MAX_NETS = 8
 RS_JOB = np.dtype([('src_offset', '<i8'), ('frames_in', '<i8'), ('channels', '<i4'), ('format', '<i4'), ('filter', '<i4'),
                    ('reserved', '<i4'), ('dst_offset', '<i8'), ('frames_out', '<i8')])
 RS_FORMAT = {np.dtype(np.uint8): 0, np.dtype('<i2'): 1, np.dtype('<i4'): 2, np.dtype('<f4'): 3, np.dtype('<f8'): 4}
+# formats a dtype does not tell: signed 8-bit, G.711 mu-law / A-law bytes, and the big-endian flag of the 2/4/8-byte formats
+RS_I8, RS_ULAW, RS_ALAW, RS_SWAP = 8, 9, 10, 0x100
+# iss_adpcm_job (include/iss.h) and the ISS_ADPCM_* block status codes
+ADPCM_JOB = np.dtype([('src_offset', '<i8'), ('block_begin', '<i8'), ('nblocks', '<i8'), ('frames_total', '<i8'), ('channels', '<i4'),
+                      ('block_align', '<i4'), ('output', '<i4'), ('filter', '<i4'), ('dst_offset', '<i8'), ('frames_out', '<i8')])
+ADPCM_TO_SIGNAL, ADPCM_TO_STAGE = 0, 1
+ADPCM_STATUS = {1: 'step index above 88'}
 # iss_flac_info / iss_flac_frame / iss_flac_job (include/iss.h)
 FLAC_INFO = np.dtype([('sample_rate', '<i4'), ('channels', '<i4'), ('bps', '<i4'), ('min_block', '<i4'), ('max_block', '<i4'),
                       ('reserved', '<i4'), ('total_samples', '<i8')])
@@ -89,6 +96,10 @@ def lib():
         'iss_flac_decode': (C.c_int, [vp, vp, i64, vp, i64, vp, i32, i64, pi32]),
         'iss_flac_get_stage': (C.c_int, [vp, i32, vp, i64]),
         'iss_flac_stats': (C.c_int, [vp, pi64, pi64]),
+        'iss_adpcm_decode_host': (C.c_int, [vp, i64, i64, i32, i32, i64, pi16, pi32]),
+        'iss_adpcm_decode': (C.c_int, [vp, vp, i64, vp, i32, i64, i64, pi32]),
+        'iss_adpcm_get_stage': (C.c_int, [vp, i32, vp, i64]),
+        'iss_adpcm_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_host_alloc': (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
         'iss_host_free': (C.c_int, [vp, vp]),
         'iss_cnn_probs_async': (C.c_int, [vp, C.c_int, pi32, i32, pf, pu8, pi64]),
@@ -249,6 +260,18 @@ def flac_decode_host(buf, frames, channels, bps, frames_total):
     return (out[:, 0] if channels == 1 else out), st
 
 
+def adpcm_decode_host(buf, nblocks, channels, block_align, frames_total):
+    """iss_adpcm_decode_host -> (PCM16 samples (n,) or (n, channels), per-block ISS_ADPCM_* status)."""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    out = np.empty((int(frames_total), int(channels)), dtype=np.int16)
+    st = np.zeros(int(nblocks), dtype=np.int32)
+    rc = lib().iss_adpcm_decode_host(C.c_void_p(buf.ctypes.data), buf.size, int(nblocks), int(channels), int(block_align),
+                                     int(frames_total), _ptr(out, C.c_int16), _ptr(st, C.c_int32))
+    if rc != 0:
+        raise NativeError(f'iss_adpcm_decode_host failed ({rc}): bad block geometry')
+    return (out[:, 0] if channels == 1 else out), st
+
+
 class Context:
     """One device context (stream + resident signal/features + loaded networks)."""
 
@@ -330,11 +353,13 @@ class Context:
         self._ck(self._L.iss_resample_filter(self._h, up, down, _ptr(h, C.c_double), h.size, C.byref(fid)), 'iss_resample_filter')
         return fid.value, up, down
 
-    def resample_job(self, x, sr, src_offset, dst_offset):
-        """One iss_resample_job row for stored samples x ((n,) or (n, C)) placed at byte `src_offset` of the source buffer."""
+    def resample_job(self, x, sr, src_offset, dst_offset, fmt=None):
+        """One iss_resample_job row for stored samples x ((n,) or (n, C)) placed at byte `src_offset` of the source buffer.
+        fmt: the ISS_RS_* format code where the dtype does not tell it (RS_I8 / RS_ULAW / RS_ALAW bytes, | RS_SWAP)."""
         fid, up, down = self.resample_filter(sr)
         n = x.shape[0]
-        return (src_offset, n, 1 if x.ndim == 1 else x.shape[1], RS_FORMAT[x.dtype], fid, 0, dst_offset, -(-n * up // down))
+        return (src_offset, n, 1 if x.ndim == 1 else x.shape[1], RS_FORMAT[x.dtype] if fmt is None else int(fmt), fid, 0,
+                dst_offset, -(-n * up // down))
 
     def resample(self, src, jobs, n_signal=-1):
         """iss_resample_pcm16: src = 1-D uint8 array of the stored samples of every job, jobs = rows of RS_JOB; one H2D copy,
@@ -345,10 +370,10 @@ class Context:
                                             jb.size, int(n_signal)), 'iss_resample_pcm16')
         self._keep_rs = src         # the async H2D copy reads it until the next sync
 
-    def resample_signal(self, x, sr):
+    def resample_signal(self, x, sr, fmt=None):
         """A single source resampled on its own: the resident signal becomes its 16 kHz mono PCM16 -> its length."""
         x = np.ascontiguousarray(x)
-        job = self.resample_job(x, sr, 0, 0)
+        job = self.resample_job(x, sr, 0, 0, fmt)
         self.resample(x.reshape(-1).view(np.uint8), [job], n_signal=job[-1])
         return job[-1]
 
@@ -394,6 +419,35 @@ class Context:
         """(FLAC decode launches, frames decoded) since the context was created."""
         a, b = C.c_int64(), C.c_int64()
         self._ck(self._L.iss_flac_stats(self._h, C.byref(a), C.byref(b)), 'iss_flac_stats')
+        return a.value, b.value
+
+    # ---- IMA ADPCM decoder (iss_adpcm_*): stored blocks -> resident signal (PCM16), staging buffer, or resampled
+    def adpcm_decode(self, src, jobs, nblocks, n_signal=-1):
+        """iss_adpcm_decode: src = 1-D uint8 array of the blocks of every job, jobs = rows of ADPCM_JOB, nblocks = their
+        sum; one H2D copy, one decode launch (+ one resample launch).  -> the per-block status array (page-locked, this
+        context's): valid after the next synchronising call (get_loge, adpcm_get_stage, synchronize)."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        jb = np.ascontiguousarray(np.array(jobs, dtype=ADPCM_JOB).reshape(-1))
+        st = self.__dict__.get('_adpcm_status')
+        if st is None or st.size < max(nblocks, 1):
+            if st is not None:
+                self.pinned_free(st)
+            st = self._adpcm_status = self.pinned_empty((int(max(nblocks, 1) * 1.25) + 256,), np.int32)
+        self._ck(self._L.iss_adpcm_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data), jb.size,
+                                          int(nblocks), int(n_signal), _ptr(st, C.c_int32)), 'iss_adpcm_decode')
+        self._keep_adpcm = src         # the async H2D copy reads it until the next sync
+        return st[:int(nblocks)]
+
+    def adpcm_get_stage(self, job, frames_total, channels):
+        """PCM16 samples of staged job `job` of the last adpcm_decode: (n,) or (n, channels) int16."""
+        out = np.empty((int(frames_total), int(channels)), dtype=np.int16)
+        self._ck(self._L.iss_adpcm_get_stage(self._h, int(job), C.c_void_p(out.ctypes.data), out.nbytes), 'iss_adpcm_get_stage')
+        return out[:, 0] if channels == 1 else out
+
+    def adpcm_stats(self):
+        """(ADPCM decode launches, blocks decoded) since the context was created."""
+        a, b = C.c_int64(), C.c_int64()
+        self._ck(self._L.iss_adpcm_stats(self._h, C.byref(a), C.byref(b)), 'iss_adpcm_stats')
         return a.value, b.value
 
     def pinned_empty(self, shape, dtype):

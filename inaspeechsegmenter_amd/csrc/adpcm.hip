@@ -1,0 +1,248 @@
+// IMA ADPCM (WAV format tag 0x11) decoding for the ffmpeg-free read, on gfx950 and on the host from one source.
+//
+// ima_decode_block walks ONE channel of ONE block: the 4-byte channel header (predictor = first sample, step index), then
+// that channel's 4-byte words, 8 nibbles each, low nibble first (include/iss.h states the step).  It is __host__ __device__:
+// iss_adpcm_decode_host runs it on the CPU, adpcm_decode_kernel on the device.
+//
+// Grid: ragged over (job, block), one 64-lane workgroup (a wave) per block; job k owns blocks [block_base_k, +nblocks_k), a
+// prefix sum built on the host, found by binary search as the resample kernel finds its tile's job.  The predictor chain of
+// a channel is serial, so lane c walks channel c (c, c + 64, ... for wide files) and writes its samples interleaved into
+// LDS; after a barrier the whole wave copies the block's samples to global memory, consecutive lanes to consecutive 16-bit
+// samples (a lane per block would store 16-bit samples a block apart: one cache line per store).  All offsets are 64-bit.
+#include "iss_internal.h"
+#include <algorithm>
+#include <cstring>
+
+namespace {
+
+constexpr int AD_THREADS = 64;
+constexpr int AD_MAX_ALIGN = 32768;               // bytes per block at most: its samples (< 4 bytes each stored byte) fit LDS
+
+constexpr int16_t kStep[89] = {
+    7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97, 107, 118,
+    130, 143, 157, 173, 190, 209, 230, 253, 279, 307, 337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060,
+    1166, 1282, 1411, 1552, 1707, 1878, 2066, 2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132,
+    7845, 8630, 9493, 10442, 11487, 12635, 13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767};
+
+__host__ __device__ inline int ima_step(int idx) { return kStep[idx]; }
+
+__host__ __device__ inline uint32_t load_le32(const uint8_t* p) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return *reinterpret_cast<const uint32_t*>(p);                     // blocks start on 4-byte boundaries (checked on the host)
+#else
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+#endif
+}
+
+// Channel `c` of the block at `blk` (`ch` channels): samples 0 .. n-1 to out[s * stride].  -> ISS_ADPCM_* of the header.
+__host__ __device__ inline int ima_decode_block(const uint8_t* blk, int ch, int c, int n, int16_t* out, int64_t stride) {
+    const uint32_t hdr = load_le32(blk + 4 * c);
+    int pred = (int16_t)(hdr & 0xFFFFu);
+    int idx = (int)((hdr >> 16) & 0xFFu);
+    int status = ISS_ADPCM_OK;
+    if (idx > 88) { idx = 88; status = ISS_ADPCM_STEP_INDEX; }
+    if (n > 0) out[0] = (int16_t)pred;
+    const uint8_t* words = blk + 4 * (int64_t)ch + 4 * c;
+    for (int s = 1; s < n; s += 8, words += 4 * (int64_t)ch) {
+        uint32_t w = load_le32(words);
+        const int m = n - s < 8 ? n - s : 8;
+        for (int k = 0; k < m; ++k, w >>= 4) {
+            const int nib = (int)(w & 15u);
+            const int step = ima_step(idx);
+            int d = step >> 3;
+            if (nib & 1) d += step >> 2;
+            if (nib & 2) d += step >> 1;
+            if (nib & 4) d += step;
+            pred = (nib & 8) ? pred - d : pred + d;
+            pred = pred < -32768 ? -32768 : (pred > 32767 ? 32767 : pred);
+            idx += (nib & 4) ? 2 * (nib & 3) + 2 : -1;                 // {-1,-1,-1,-1,2,4,6,8}[nib & 7]
+            idx = idx < 0 ? 0 : (idx > 88 ? 88 : idx);
+            out[(int64_t)(s + k) * stride] = (int16_t)pred;
+        }
+    }
+    return status;
+}
+
+struct AdJobDev {
+    int64_t src_off, block_base, nblocks, frames_total, dst_byte;   // dst_byte: into the signal (to_sig) or the staging buffer
+    int32_t ch, block_align, spb, to_sig;
+};
+
+__global__ __launch_bounds__(AD_THREADS) void adpcm_decode_kernel(const uint8_t* __restrict__ src, const AdJobDev* __restrict__ jobs,
+                                                                  int njobs, int16_t* __restrict__ sig, uint8_t* __restrict__ stage,
+                                                                  int32_t* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) int16_t ad_smem[];
+    const int64_t b = blockIdx.x;
+    int lo = 0, hi = njobs - 1;                                          // last job whose block_base <= b
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].block_base <= b) lo = mid; else hi = mid - 1;
+    }
+    const AdJobDev J = jobs[lo];
+    const int64_t kb = b - J.block_base;
+    if (kb >= J.nblocks) return;                                         // (never: the grid is the sum of the jobs' blocks)
+    const int64_t first = kb * J.spb;
+    const int n = (int)min((int64_t)J.spb, J.frames_total - first);      // a `fact` count may cut the last block
+    const uint8_t* blk = src + J.src_off + kb * (int64_t)J.block_align;
+    int st = ISS_ADPCM_OK;
+    for (int c = threadIdx.x; c < J.ch; c += AD_THREADS) st |= ima_decode_block(blk, J.ch, c, n, ad_smem + c, J.ch);
+    st = __syncthreads_or(st) ? ISS_ADPCM_STEP_INDEX : ISS_ADPCM_OK;   // (the barrier tells zero from non-zero only: the one code there is;
+                                                                        //  a second status code needs the value itself reduced)
+    if (threadIdx.x == 0) status[b] = st;
+    int16_t* dst = reinterpret_cast<int16_t*>((J.to_sig ? reinterpret_cast<uint8_t*>(sig) : stage) + J.dst_byte) + first * J.ch;
+    const int total = n * J.ch;
+    for (int i = threadIdx.x; i < total; i += AD_THREADS) dst[i] = ad_smem[i];
+}
+
+int samples_per_block(int32_t block_align, int32_t ch) { return (block_align / ch - 4) * 2 + 1; }
+
+bool geometry_ok(int64_t nblocks, int32_t ch, int32_t block_align, int64_t frames_total) {
+    if (ch < 1 || ch > 64 || block_align <= 4 * ch || block_align % (4 * ch) != 0 || block_align > AD_MAX_ALIGN) return false;
+    if (nblocks < 1 || nblocks > ((int64_t)1 << 40) / block_align) return false;
+    const int64_t spb = samples_per_block(block_align, ch);
+    return frames_total > (nblocks - 1) * spb && frames_total <= nblocks * spb;
+}
+
+}  // namespace
+
+extern "C" int iss_adpcm_decode_host(const uint8_t* buf, int64_t len, int64_t nblocks, int32_t channels, int32_t block_align,
+                                     int64_t frames_total, int16_t* out, int32_t* status_out) {
+    if (!buf || !out || !status_out || len < 0 || !geometry_ok(nblocks, channels, block_align, frames_total) ||
+        nblocks * (int64_t)block_align > len)
+        return ISS_EINVAL;
+    const int64_t spb = samples_per_block(block_align, channels);
+    for (int64_t k = 0; k < nblocks; ++k) {
+        const int n = (int)std::min<int64_t>(spb, frames_total - k * spb);
+        int st = ISS_ADPCM_OK;
+        for (int c = 0; c < channels; ++c)
+            st |= ima_decode_block(buf + k * block_align, channels, c, n, out + k * spb * channels + c, channels);
+        status_out[k] = st;
+    }
+    return ISS_OK;
+}
+
+extern "C" int iss_adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, int32_t njobs,
+                                int64_t nblocks_total, int64_t n_signal, int32_t* status_out) {
+    if (!c || njobs < 0 || (njobs > 0 && (!jobs || !status_out)) || src_bytes < 0 || (!src && src_bytes > 0) || nblocks_total < 0)
+        return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: bad argument");
+    ISS_HIP(c, hipSetDevice(c->device));
+    int64_t nsig = n_signal;
+    if (n_signal < 0) {
+        if (c->sig_kind != 1 || c->sig_ptr != c->sig.p)
+            return iss_fail(c, ISS_ESTATE, "iss_adpcm_decode: n_signal < 0 needs a PCM16 signal uploaded by iss_signal_pcm16");
+        nsig = c->sig_n;
+    }
+    std::vector<AdJobDev> dev((size_t)njobs);
+    std::vector<iss_resample_job> rjobs;
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    std::vector<int64_t> stage_off((size_t)njobs, -1), stage_bytes((size_t)njobs, 0);
+    int64_t stage = 0, blocks = 0, lds = 0;
+    for (int32_t j = 0; j < njobs; ++j) {
+        const iss_adpcm_job& J = jobs[j];
+        if (!geometry_ok(J.nblocks, J.channels, J.block_align, J.frames_total))
+            return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: %lld blocks of %d bytes, %d channels, %lld samples", j,
+                            (long long)J.nblocks, J.block_align, J.channels, (long long)J.frames_total);
+        if (J.block_begin != blocks)
+            return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: status rows start at %lld, expected %lld", j,
+                            (long long)J.block_begin, (long long)blocks);
+        const int64_t nbytes = J.nblocks * J.block_align;
+        if (J.src_offset < 0 || J.src_offset % 4 != 0 || J.src_offset > src_bytes - nbytes)
+            return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: source bytes [%lld, %lld) outside the %lld-byte buffer or "
+                            "not aligned to 4", j, (long long)J.src_offset, (long long)(J.src_offset + nbytes), (long long)src_bytes);
+        AdJobDev& d = dev[(size_t)j];
+        d.src_off = J.src_offset; d.block_base = blocks; d.nblocks = J.nblocks; d.frames_total = J.frames_total;
+        d.ch = J.channels; d.block_align = J.block_align; d.spb = samples_per_block(J.block_align, J.channels);
+        if (J.output == ISS_ADPCM_TO_SIGNAL) {
+            if (J.channels != 1)
+                return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: only mono sources go to the signal", j);
+            if (J.dst_offset < 0 || J.dst_offset > nsig - J.frames_total)
+                return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: output [%lld, %lld) outside the %lld-sample signal", j,
+                                (long long)J.dst_offset, (long long)(J.dst_offset + J.frames_total), (long long)nsig);
+            ranges.push_back({J.dst_offset, J.dst_offset + J.frames_total});
+            d.to_sig = 1;
+            d.dst_byte = J.dst_offset * 2;
+        } else if (J.output == ISS_ADPCM_TO_STAGE) {
+            d.to_sig = 0;
+            d.dst_byte = stage;
+            stage_off[(size_t)j] = stage;
+            stage_bytes[(size_t)j] = J.frames_total * J.channels * 2;
+            if (J.filter >= 0) {
+                iss_resample_job r{};
+                r.src_offset = stage; r.frames_in = J.frames_total; r.channels = J.channels; r.format = ISS_RS_I16;
+                r.filter = J.filter; r.dst_offset = J.dst_offset; r.frames_out = J.frames_out;
+                rjobs.push_back(r);
+            }
+            stage += (stage_bytes[(size_t)j] + 15) / 16 * 16;
+        } else {
+            return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: bad output %d", j, J.output);
+        }
+        lds = std::max<int64_t>(lds, (int64_t)d.spb * d.ch * 2);
+        blocks += J.nblocks;
+    }
+    if (blocks != nblocks_total)
+        return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: the jobs hold %lld blocks, not %lld", (long long)blocks,
+                        (long long)nblocks_total);
+    if (blocks > 0x7fffffffLL) return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: %lld blocks in one call", (long long)blocks);
+    IssRsPlan plan;
+    int rc = iss_resample_plan(c, rjobs.data(), (int32_t)rjobs.size(), stage, nsig, ranges, "iss_adpcm_decode", plan);
+    if (rc) return rc;
+    if (n_signal >= 0) {
+        rc = iss_reserve(c, c->sig, (size_t)nsig * 2 + 16);
+        if (rc) return rc;
+        if (nsig > 0) ISS_HIP(c, hipMemsetAsync(c->sig.p, 0, (size_t)nsig * 2, c->stream));
+        c->sig_ptr = c->sig.p; c->sig_kind = 1; c->sig_n = nsig;
+    }
+    c->have_feats = false;
+    c->ad_stage_off = stage_off;
+    c->ad_stage_bytes = stage_bytes;
+    if (blocks == 0) return ISS_OK;
+    if ((rc = iss_reserve(c, c->ad_src, (size_t)std::max<int64_t>(src_bytes, 16)))) return rc;
+    if ((rc = iss_reserve(c, c->ad_jobs, dev.size() * sizeof(AdJobDev)))) return rc;
+    if ((rc = iss_reserve(c, c->ad_status, (size_t)blocks * 4))) return rc;
+    if ((rc = iss_reserve(c, c->ad_stage, (size_t)std::max<int64_t>(stage, 16)))) return rc;
+    iss_prof_begin(c, ISS_PROF_OTHER, 0.0);
+    iss_prof_inst(c, "adpcm_h2d(%lld B)", (long long)src_bytes);
+    ISS_HIP(c, hipMemcpyAsync(c->ad_src.p, src, (size_t)src_bytes, hipMemcpyHostToDevice, c->stream));
+    iss_prof_end(c);
+    void* pinned = nullptr;
+    int slot = -1;
+    if ((rc = iss_stage_host(c, dev.data(), dev.size() * sizeof(AdJobDev), &pinned, &slot))) return rc;
+    ISS_HIP(c, hipMemcpyAsync(c->ad_jobs.p, pinned, dev.size() * sizeof(AdJobDev), hipMemcpyHostToDevice, c->stream));
+    iss_stage_mark(c, slot);
+    if (lds + 1024 > 64 * 1024)                        // (the kernel's static LDS, 256 bytes, counts towards the 64 KiB default)
+        ISS_HIP(c, hipFuncSetAttribute((const void*)adpcm_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    iss_prof_begin(c, ISS_PROF_FRONTEND, 0.0);
+    iss_prof_inst(c, "adpcm_decode_kernel");
+    hipLaunchKernelGGL(adpcm_decode_kernel, dim3((unsigned)blocks), dim3(AD_THREADS), (size_t)lds, c->stream,
+                       (const uint8_t*)c->ad_src.p, (const AdJobDev*)c->ad_jobs.p, (int)dev.size(), (int16_t*)c->sig.p,
+                       (uint8_t*)c->ad_stage.p, (int32_t*)c->ad_status.p);
+    ISS_HIP(c, hipGetLastError());
+    iss_prof_end(c);
+    ISS_HIP(c, hipMemcpyAsync(status_out, c->ad_status.p, (size_t)blocks * 4, hipMemcpyDeviceToHost, c->stream));
+    c->ad_launches += 1;
+    c->ad_blocks_done += blocks;
+    if (!rjobs.empty()) return iss_resample_launch(c, (const uint8_t*)c->ad_stage.p, plan);
+    return ISS_OK;
+}
+
+extern "C" int iss_adpcm_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {
+    if (!c || (!out && bytes > 0)) return iss_fail(c, ISS_EINVAL, "iss_adpcm_get_stage: bad argument");
+    if (job < 0 || job >= (int32_t)c->ad_stage_off.size() || c->ad_stage_off[(size_t)job] < 0)
+        return iss_fail(c, ISS_EINVAL, "iss_adpcm_get_stage: job %d of the last iss_adpcm_decode did not go to the staging buffer", job);
+    if (bytes != c->ad_stage_bytes[(size_t)job])
+        return iss_fail(c, ISS_EINVAL, "iss_adpcm_get_stage: job %d holds %lld bytes, not %lld", job,
+                        (long long)c->ad_stage_bytes[(size_t)job], (long long)bytes);
+    ISS_HIP(c, hipSetDevice(c->device));
+    if (bytes > 0)
+        ISS_HIP(c, hipMemcpyAsync(out, (const uint8_t*)c->ad_stage.p + c->ad_stage_off[(size_t)job], (size_t)bytes,
+                                  hipMemcpyDeviceToHost, c->stream));
+    ISS_HIP(c, hipStreamSynchronize(c->stream));
+    return ISS_OK;
+}
+
+extern "C" int iss_adpcm_stats(iss_ctx* c, int64_t* launches, int64_t* blocks) {
+    if (!c) return ISS_EINVAL;
+    if (launches) *launches = c->ad_launches;
+    if (blocks) *blocks = c->ad_blocks_done;
+    return ISS_OK;
+}

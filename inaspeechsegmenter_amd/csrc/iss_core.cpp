@@ -78,7 +78,8 @@ extern "C" void iss_destroy(iss_ctx* c) {
     for (void* p : singles) if (p) (void)hipFree(p);
     DevBuf* bufs[] = {&c->sig, &c->mspec, &c->loge, &c->d_winrow, &c->d_stats, &c->d_finite, &c->d_out, &c->d_in, &c->raw1,
                       &c->vbx_sig, &c->vbx_dither, &c->vbx_fb, &c->vbx_out, &c->vbx_meta, &c->rs_src, &c->rs_jobs,
-                      &c->flac_src, &c->flac_frames, &c->flac_status, &c->flac_stage};
+                      &c->flac_src, &c->flac_frames, &c->flac_status, &c->flac_stage,
+                      &c->ad_src, &c->ad_jobs, &c->ad_status, &c->ad_stage};
     for (DevBuf* b : bufs) free_buf(*b);
     for (auto& b : c->act) free_buf(b);
     for (auto& f : c->rs_filters) if (f.d_taps) (void)hipFree(f.d_taps);

@@ -89,6 +89,11 @@ struct iss_ctx {
     std::vector<int64_t> flac_stage_off, flac_stage_bytes;   // per job of the last call (-1: not staged)
     int64_t flac_launches = 0, flac_frames_done = 0;
 
+    // IMA ADPCM decoder (adpcm.hip): stored blocks, job rows, per-block status and the staging buffer of the last call
+    DevBuf ad_src, ad_jobs, ad_status, ad_stage;
+    std::vector<int64_t> ad_stage_off, ad_stage_bytes;       // per job of the last call (-1: not staged)
+    int64_t ad_launches = 0, ad_blocks_done = 0;
+
     // resident features
     DevBuf mspec, loge;
     int32_t T = 0;

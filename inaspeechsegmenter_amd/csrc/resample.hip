@@ -1,4 +1,5 @@
-// Downmix + polyphase low-pass resampling + PCM16 quantisation of WAV sources at any rate, for gfx950 (float64).
+// Downmix + polyphase low-pass resampling + PCM16 quantisation of stored samples at any rate, for gfx950 (float64).
+// Stored: WAV's little-endian PCM / float, signed 8-bit, G.711 mu-law / A-law bytes, big-endian 16/32/64-bit (ISS_RS_SWAP).
 //
 // Replaces the 16 kHz-only assertion of the ffmpeg-free read (io.py:53-55): iss_resample_pcm16 turns the stored samples of
 // many files (one H2D copy) into 16 kHz mono PCM16 in the resident signal, in ONE launch of resample_kernel.  The
@@ -25,23 +26,71 @@ constexpr int64_t RS_LDS_MAX = 160 * 1024;         // bytes of LDS one workgroup
 constexpr int64_t RS_SPAN_MAX = 64 * 1024;         // a tile's input span (float64) is kept under this when R > 1
 
 __device__ __forceinline__ double to_f64(uint8_t x) { return __ddiv_rn(__dsub_rn((double)x, 128.0), 128.0); }
+__device__ __forceinline__ double to_f64(int8_t x) { return __ddiv_rn((double)x, 128.0); }     // = the u8 twin x + 128
 __device__ __forceinline__ double to_f64(int16_t x) { return __ddiv_rn((double)x, 32768.0); }
 __device__ __forceinline__ double to_f64(int32_t x) { return __ddiv_rn((double)x, 2147483648.0); }
 __device__ __forceinline__ double to_f64(float x) { return (double)x; }
 __device__ __forceinline__ double to_f64(double x) { return x; }
 
+// G.711 expansion (include/iss.h states both): the decoded 16-bit value of a stored byte
+__device__ __forceinline__ int ulaw_value(uint32_t b) {
+    const uint32_t u = ~b & 0xFFu;
+    const int t = (int)((((u & 15u) << 3) + 0x84u) << ((u >> 4) & 7u));
+    return (u & 0x80u) ? 0x84 - t : t - 0x84;
+}
+__device__ __forceinline__ int alaw_value(uint32_t b) {
+    const uint32_t a = (b ^ 0x55u) & 0xFFu;
+    int t = (int)((a & 15u) << 4);
+    const int s = (int)((a >> 4) & 7u);
+    if (s == 0) t += 8;
+    else if (s == 1) t += 0x108;
+    else t = (t + 0x108) << (s - 1);
+    return (a & 0x80u) ? t : -t;
+}
+
+// one stored sample -> float64 with libsndfile's scaling: as stored, G.711, or byte-swapped (big-endian sources)
+template <typename T> struct LdPlain {
+    using type = T;
+    static __device__ __forceinline__ double get(const T* q) { return to_f64(*q); }
+};
+struct LdUlaw {
+    using type = uint8_t;
+    static __device__ __forceinline__ double get(const uint8_t* q) { return to_f64((int16_t)ulaw_value(*q)); }
+};
+struct LdAlaw {
+    using type = uint8_t;
+    static __device__ __forceinline__ double get(const uint8_t* q) { return to_f64((int16_t)alaw_value(*q)); }
+};
+struct LdSwapI16 {
+    using type = uint16_t;
+    static __device__ __forceinline__ double get(const uint16_t* q) { return to_f64((int16_t)__builtin_bswap16(*q)); }
+};
+struct LdSwapI32 {
+    using type = uint32_t;
+    static __device__ __forceinline__ double get(const uint32_t* q) { return to_f64((int32_t)__builtin_bswap32(*q)); }
+};
+struct LdSwapF32 {
+    using type = uint32_t;
+    static __device__ __forceinline__ double get(const uint32_t* q) { return (double)__uint_as_float(__builtin_bswap32(*q)); }
+};
+struct LdSwapF64 {
+    using type = uint64_t;
+    static __device__ __forceinline__ double get(const uint64_t* q) { return __longlong_as_double((long long)__builtin_bswap64(*q)); }
+};
+
 // frames s0 .. s0+len-1 of one source, downmixed to float64 (channels summed in order, divided by their count)
-template <typename T>
+template <typename L>
 __device__ __forceinline__ void stage_span(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
                                            double* __restrict__ span) {
+    using T = typename L::type;
     const T* p = reinterpret_cast<const T*>(src);
     for (int k = threadIdx.x; k < len; k += RS_THREADS) {
         const int64_t j = s0 + k;
         double v = 0.0;
         if (j >= 0 && j < n_in) {
             const T* q = p + j * ch;
-            v = to_f64(q[0]);
-            for (int c = 1; c < ch; ++c) v = __dadd_rn(v, to_f64(q[c]));
+            v = L::get(q);
+            for (int c = 1; c < ch; ++c) v = __dadd_rn(v, L::get(q + c));
             if (ch > 1) v = __ddiv_rn(v, (double)ch);
         }
         span[k] = v;
@@ -66,6 +115,9 @@ __device__ __forceinline__ void compute_tile(const RsJobDev& J, const double* __
     }
 }
 
+// EXT = false: the five little-endian WAV formats only, the instantiation every call without a newer format launches (its
+// switch, and so its code, is what it was before the newer formats existed); EXT = true adds them behind the default case.
+template <bool EXT>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __restrict__ src, const RsJobDev* __restrict__ jobs,
                                                               int njobs, int16_t* __restrict__ dst) {
     extern __shared__ __attribute__((aligned(16))) double rs_smem[];
@@ -87,18 +139,33 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __r
         for (int k = threadIdx.x; k < ntaps; k += RS_THREADS) rs_smem[k] = J.taps[k];
     const uint8_t* s = src + J.src_off;
     switch (J.fmt) {
-        case ISS_RS_U8:  stage_span<uint8_t>(s, J.n_in, J.ch, s0, len, span); break;
-        case ISS_RS_I16: stage_span<int16_t>(s, J.n_in, J.ch, s0, len, span); break;
-        case ISS_RS_I32: stage_span<int32_t>(s, J.n_in, J.ch, s0, len, span); break;
-        case ISS_RS_F32: stage_span<float>(s, J.n_in, J.ch, s0, len, span); break;
-        default:         stage_span<double>(s, J.n_in, J.ch, s0, len, span); break;
+        case ISS_RS_U8:  stage_span<LdPlain<uint8_t>>(s, J.n_in, J.ch, s0, len, span); break;
+        case ISS_RS_I16: stage_span<LdPlain<int16_t>>(s, J.n_in, J.ch, s0, len, span); break;
+        case ISS_RS_I32: stage_span<LdPlain<int32_t>>(s, J.n_in, J.ch, s0, len, span); break;
+        case ISS_RS_F32: stage_span<LdPlain<float>>(s, J.n_in, J.ch, s0, len, span); break;
+        default:
+            if constexpr (!EXT) {
+                stage_span<LdPlain<double>>(s, J.n_in, J.ch, s0, len, span);
+            } else {
+                switch (J.fmt) {
+                    case ISS_RS_F64:  stage_span<LdPlain<double>>(s, J.n_in, J.ch, s0, len, span); break;
+                    case ISS_RS_I8:   stage_span<LdPlain<int8_t>>(s, J.n_in, J.ch, s0, len, span); break;
+                    case ISS_RS_ULAW: stage_span<LdUlaw>(s, J.n_in, J.ch, s0, len, span); break;
+                    case ISS_RS_ALAW: stage_span<LdAlaw>(s, J.n_in, J.ch, s0, len, span); break;
+                    case ISS_RS_I16 | ISS_RS_SWAP: stage_span<LdSwapI16>(s, J.n_in, J.ch, s0, len, span); break;
+                    case ISS_RS_I32 | ISS_RS_SWAP: stage_span<LdSwapI32>(s, J.n_in, J.ch, s0, len, span); break;
+                    case ISS_RS_F32 | ISS_RS_SWAP: stage_span<LdSwapF32>(s, J.n_in, J.ch, s0, len, span); break;
+                    default:          stage_span<LdSwapF64>(s, J.n_in, J.ch, s0, len, span); break;      // ISS_RS_F64 | ISS_RS_SWAP
+                }
+            }
+            break;
     }
     __syncthreads();
     if (J.lds_tab) compute_tile(J, rs_smem, span, s0, i0, i_end, dst);
     else           compute_tile(J, J.taps, span, s0, i0, i_end, dst);
 }
 
-const int kFmtBytes[5] = {1, 2, 4, 4, 8};
+const int kFmtBytes[11] = {1, 2, 4, 4, 8, 0, 0, 0, 1, 1, 1};      // bytes per stored sample of ISS_RS_* (0: not a format)
 
 // longest input span of a tile of `tile` outputs: floor(((tile-1)*down + 2*hl) / up) + 2 frames
 int64_t span_frames(const iss_ctx::RsFilter& f, int64_t tile) {
@@ -141,14 +208,15 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, int32_t njobs, i
     int64_t tiles = 0, lds = 0;
     for (int32_t k = 0; k < njobs; ++k) {
         const iss_resample_job& J = jobs[k];
-        if (J.format < ISS_RS_U8 || J.format > ISS_RS_F64)
+        const int32_t code = J.format & ~ISS_RS_SWAP;
+        if (J.format < 0 || code > ISS_RS_ALAW || kFmtBytes[code] == 0 || ((J.format & ISS_RS_SWAP) && kFmtBytes[code] < 2))
             return iss_fail(c, ISS_EINVAL, "%s: job %d: bad format %d", who, k, J.format);
         if (J.channels < 1 || J.channels > 1024)
             return iss_fail(c, ISS_EINVAL, "%s: job %d: %d channels", who, k, J.channels);
         if (J.filter < 0 || J.filter >= (int32_t)c->rs_filters.size())
             return iss_fail(c, ISS_EINVAL, "%s: job %d: unknown filter %d", who, k, J.filter);
         const iss_ctx::RsFilter& f = c->rs_filters[(size_t)J.filter];
-        const int64_t esz = kFmtBytes[J.format];
+        const int64_t esz = kFmtBytes[code];
         if (J.frames_in < 1 || J.frames_in > (int64_t(1) << 40) / (esz * J.channels))
             return iss_fail(c, ISS_EINVAL, "%s: job %d: %lld frames", who, k, (long long)J.frames_in);
         const int64_t nbytes = J.frames_in * J.channels * esz;
@@ -199,13 +267,16 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     if (rc) return rc;
     ISS_HIP(c, hipMemcpyAsync(c->rs_jobs.p, pinned, dj.size() * sizeof(RsJobDev), hipMemcpyHostToDevice, c->stream));
     iss_stage_mark(c, slot);
+    bool ext = false;                                  // a format newer than the WAV five: the instantiation that reads them all
+    for (const RsJobDev& d : dj) ext = ext || d.fmt > ISS_RS_F64;
+    auto kernel = ext ? resample_kernel<true> : resample_kernel<false>;
     if (plan.lds > 64 * 1024)
-        ISS_HIP(c, hipFuncSetAttribute((const void*)resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+        ISS_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
     double flops = 0;
     for (const RsJobDev& d : dj) flops += 2.0 * (double)d.n_out * (2.0 * d.hl + 1) / d.up;
     iss_prof_begin(c, ISS_PROF_FRONTEND, flops);
     iss_prof_inst(c, "resample_kernel");
-    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)plan.tiles), dim3(RS_THREADS), (size_t)plan.lds, c->stream,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)plan.tiles), dim3(RS_THREADS), (size_t)plan.lds, c->stream,
                        dev_src, (const RsJobDev*)c->rs_jobs.p, (int)dj.size(), (int16_t*)c->sig.p);
     ISS_HIP(c, hipGetLastError());
     iss_prof_end(c);

@@ -9,7 +9,8 @@ Mirrors io.py:32-79 `media2sig16kmono(medianame, start_sec, stop_sec, ffmpeg, dt
 Decode stays on the host (north star); soundfile/libsndfile is not available in the target
 image, so RIFF/WAVE is parsed here with libsndfile's conversion rules (PCM16 -> x/32768,
 unknown chunks skipped).  FLAC (flac.py) reads exactly like its WAV twin, decoded here by the host build of the
-device's frame decoder.  `decode_pcm` is the entry the native pipeline uses: it keeps
+device's frame decoder; so do G.711 and IMA ADPCM in WAV, RF64 / BW64, Wave64, AIFF / AIFF-C, AU and CAF (sndfmt.py: numpy
+tables, byte swaps and the host build of the device's IMA decoder).  `decode_pcm` is the entry the native pipeline uses: it keeps
 PCM16 as int16 so the device does the x/32768 scaling (2 B/sample over PCIe, not 4).
 """
 import os
@@ -64,7 +65,7 @@ def _parse_wav(buf, name='<buffer>'):
 
 
 def _read_nofmpeg(medianame):
-    """ffmpeg-free read of a WAV or FLAC file -> (samples as stored, sr) as _parse_wav returns them."""
+    """ffmpeg-free read of a WAV, FLAC or sndfmt.py file -> (samples as stored, sr) as _parse_wav returns them (for the WAV twin)."""
     from . import flac
     with open(medianame, 'rb') as f:
         buf = f.read()
@@ -72,6 +73,10 @@ def _read_nofmpeg(medianame):
         return flac.read_host(buf, medianame)
     if flac.is_ogg_flac(buf):
         raise ValueError(f'{medianame}: Ogg-FLAC (FLAC in an Ogg container) is not supported without ffmpeg')
+    from . import sndfmt
+    snd = sndfmt.parse(buf, medianame)               # G.711 / IMA ADPCM WAV, RF64, Wave64, AIFF, AU, CAF: expanded to the twin's array
+    if snd is not None:
+        return snd.stored(), snd.sr
     return _parse_wav(buf, medianame)
 
 

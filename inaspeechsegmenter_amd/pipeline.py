@@ -7,13 +7,15 @@ launches, copies and Python bookkeeping become the limit.  Here files are proces
 
   decode threads   N files  ->  int16 PCM (RIFF parse, or the ffmpeg pipe); with Segmenter(resample=True) WAVs at other
                    rates / channel counts are handed on as stored (segmenter.RawSource); without ffmpeg FLAC files are
-                   handed on compressed, their frames indexed (flac.FlacSource)
+                   handed on compressed, their frames indexed (flac.FlacSource); G.711, big-endian and IMA ADPCM files
+                   (sndfmt.py) are handed on as stored too (RawSource with its format, sndfmt.AdpcmSource)
   packer           the PCM of a super-batch (default <= 32 files / ~40 min of audio) is laid end to end in ONE page-locked
                    buffer, every file starting on a multiple of 160 samples: frame t of file f is then frame
                    off_f / 160 + t of the concatenation, and the frames that straddle two files are simply never used
                    (room is left for the resampled files, whose stored bytes go into a second page-locked buffer)
   device worker    ONE H2D copy, ONE resample launch for all resampled files (one more H2D copy), ONE FLAC decode launch for
                    all FLAC files (one more H2D copy of their compressed bytes; the resampled ones add one resample launch),
+                   likewise ONE ADPCM decode launch for all IMA ADPCM files (one more H2D copy, at most one resample launch),
                    ONE sidekit launch, one log-energy read-back (with the FLAC frame status); per-file energy Viterbi (compiled);
                    ONE iss_cnn_probs call for the VAD windows of all files, per-segment Viterbi; ONE call for the
                    gender windows, Viterbi; hand the segment lists to the exporter
@@ -49,9 +51,9 @@ class _Batch:
 
 def _held(sig):
     """What a decoded source holds, in 16-bit sample units: its samples, or a stored source's bytes / 2 when larger; a FLAC
-    source holds its compressed bytes."""
-    from . import flac
-    if isinstance(sig, flac.FlacSource):
+    or IMA ADPCM source holds its compressed bytes."""
+    from . import flac, sndfmt
+    if isinstance(sig, (flac.FlacSource, sndfmt.AdpcmSource)):
         return max(1, sig.nbytes // 2)
     x = getattr(sig, 'x', None)
     return sig.size if x is None else max(sig.size, x.nbytes // 2)
@@ -134,6 +136,7 @@ class _Worker:
         self.pin = None
         self.rpin = None                             # stored bytes of the resampled files of a pass
         self.fpin = None                             # compressed bytes of the FLAC files of a pass
+        self.apin = None                             # blocks of the IMA ADPCM files of a pass
         # wall seconds this worker spent per phase since the last reset (bench.py reports them: where a step's host time goes)
         self.stats = {k: 0.0 for k in ('pack', 'features', 'energy_host', 'cnn_device', 'smooth_host', 'batches', 'files')}
 
@@ -162,6 +165,13 @@ class _Worker:
             self.fpin = self.ctx.pinned_empty((int(nbytes * 1.25) + 4096,), np.uint8)
         return self.fpin
 
+    def adpcm_pinned(self, nbytes):
+        if self.apin is None or self.apin.size < nbytes:
+            if self.apin is not None:
+                self.ctx.pinned_free(self.apin)
+            self.apin = self.ctx.pinned_empty((int(nbytes * 1.25) + 4096,), np.uint8)
+        return self.apin
+
     def sync_settings(self):
         """Arithmetic mode and workspace cap follow the Segmenter's own context (they may have changed since this
         worker was created: the workers are cached between calls)."""
@@ -169,10 +179,10 @@ class _Worker:
             self.ctx.mirror_settings(self.seg.ctx)
 
     def run(self, batch):
-        """-> [ [(label, start_slot, stop_slot)] per file of the batch ]; None for a FLAC file whose frames the device found
-        malformed (its message in batch.errs)"""
+        """-> [ [(label, start_slot, stop_slot)] per file of the batch ]; None for a FLAC / IMA ADPCM file whose frames / blocks
+        the device found malformed (its message in batch.errs)"""
         from . import segmenter as S
-        from . import flac
+        from . import flac, sndfmt
         seg, ctx = self.seg, self.ctx
         st = self.stats
         t_ = time.perf_counter()
@@ -181,7 +191,7 @@ class _Worker:
             offs.append(pos)
             pos += -(-s.size // FRAME_HOP) * FRAME_HOP
         buf = self.pinned(pos)
-        raws, flacs = [], []
+        raws, flacs, adpcms = [], [], []
         for f, (s, o) in enumerate(zip(batch.sigs, offs)):
             if isinstance(s, S.RawSource):           # written by the resample kernel
                 buf[o:o + s.size] = 0
@@ -189,6 +199,9 @@ class _Worker:
             elif isinstance(s, flac.FlacSource):     # written by the FLAC decode kernel (and the resample kernel)
                 buf[o:o + s.size] = 0
                 flacs.append((f, s, o))
+            elif isinstance(s, sndfmt.AdpcmSource):  # written by the ADPCM decode kernel (and the resample kernel)
+                buf[o:o + s.size] = 0
+                adpcms.append((f, s, o))
             elif s.dtype == np.int16:
                 buf[o:o + s.size] = s
             else:                                    # float sources: what libsndfile's float32 read holds, re-quantised is NOT exact
@@ -199,7 +212,7 @@ class _Worker:
             jobs, rpos = [], 0
             for s, o in raws:
                 rb[rpos:rpos + s.x.nbytes] = s.x.reshape(-1).view(np.uint8)
-                jobs.append(ctx.resample_job(s.x, s.sr, rpos, o))
+                jobs.append(ctx.resample_job(s.x, s.sr, rpos, o, s.fmt))
                 rpos += -(-s.x.nbytes // 16) * 16
         if flacs:                                    # compressed frames end to end, each file on a 16-byte boundary
             fb = self.flac_pinned(sum(-(-s.nbytes // 16) * 16 for _, s, _ in flacs))
@@ -210,14 +223,32 @@ class _Worker:
                 fpos += -(-s.nbytes // 16) * 16
                 fbeg += len(s.s.frames)
             frames = np.concatenate([s.s.frames for _, s, _ in flacs])
+        if adpcms:                                   # stored blocks end to end, each file on a 16-byte boundary
+            ab = self.adpcm_pinned(sum(-(-s.nbytes // 16) * 16 for _, s, _ in adpcms))
+            ajobs, apos, abeg = [], 0, 0
+            for _, s, o in adpcms:
+                ab[apos:apos + s.nbytes] = s.s.data
+                ajobs.append(s.job(ctx, apos, abeg, o))
+                apos += -(-s.nbytes // 16) * 16
+                abeg += s.s.nblocks
         st['pack'] += time.perf_counter() - t_; t_ = time.perf_counter()
         ctx.set_signal(buf[:pos])
         if raws:
             ctx.resample(rb[:rpos], jobs)            # one launch for every resampled file of the pass, into the signal above
         if flacs:
             fstat = ctx.flac_decode(fb[:fpos], frames, fjobs)   # one decode launch for every FLAC file of the pass
+        if adpcms:
+            astat = ctx.adpcm_decode(ab[:apos], ajobs, abeg)    # one decode launch for every ADPCM file of the pass
         ctx.sidekit()
         loge = ctx.get_loge()
+        if adpcms:                                   # the block status came back with the log-energy
+            abeg = 0
+            for f, s, _ in adpcms:
+                try:
+                    s.s.check(astat[abeg:abeg + s.s.nblocks])
+                except ValueError as exc:
+                    batch.errs[f] = 'error: %s %s' % (type(exc), exc)
+                abeg += s.s.nblocks
         if flacs:                                    # the frame status came back with the log-energy
             fbeg = 0
             for f, s, _ in flacs:
@@ -232,7 +263,7 @@ class _Worker:
         # energy segmentation per file (segmenter.py:261-267)
         lsegs = []
         for f in range(len(batch.sigs)):
-            if f in batch.errs:                      # a malformed FLAC file: no segments, no network rows
+            if f in batch.errs:                      # a malformed FLAC / ADPCM file: no segments, no network rows
                 lsegs.append([])
                 continue
             le = loge[g0[f]:g0[f] + nfr[f]]
@@ -324,7 +355,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
     skip: set of indices not to process.  Device failures (NativeError) and exceptions raised by on_result (unwritable
     outputs) propagate to the caller: the first one is re-raised here once every stage has drained."""
     from . import segmenter as S
-    from . import flac
+    from . import flac, sndfmt
     batch_files = batch_files or DEFAULT_BATCH_FILES
     batch_seconds = batch_seconds or DEFAULT_BATCH_SECONDS
     workers = workers or DEFAULT_WORKERS
@@ -358,7 +389,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                     except BaseException as exc:                   # noqa: B902
                         failure.append(exc)
                     continue
-                if isinstance(sig, S.RawSource):
+                if isinstance(sig, (S.RawSource, sndfmt.AdpcmSource)):
                     single = False
                 elif isinstance(sig, flac.FlacSource):
                     single = sig.kind == 'float'             # 24-bit: the float path, as a 24-bit WAV takes

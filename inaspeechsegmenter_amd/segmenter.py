@@ -26,6 +26,7 @@ from . import _native
 from . import tables
 from . import keras_model
 from . import flac
+from . import sndfmt
 from .io import decode_pcm, decode_source, _check_no_ffmpeg, _to_float
 from .export_funcs import seg2csv, seg2textgrid
 
@@ -304,25 +305,35 @@ def _ensure_resident(ctx, mspec):
 
 
 class RawSource:
-    """A WAV at another rate or channel count, as stored, for the device resampler (Segmenter(ffmpeg=None, resample=True)).
-    `size` is its length once resampled to 16 kHz, so it stands where a decoded signal's `size` is read."""
-    __slots__ = ('x', 'sr', 'size')
+    """Samples at another rate or channel count, as stored, for the device resampler (Segmenter(ffmpeg=None, resample=True)).
+    `size` is its length once resampled to 16 kHz, so it stands where a decoded signal's `size` is read.  `fmt` is the
+    ISS_RS_* format of the stored bytes: the dtype's by default; explicit for signed bytes, G.711 and big-endian samples."""
+    __slots__ = ('x', 'sr', 'size', 'fmt')
 
-    def __init__(self, x, sr):
+    def __init__(self, x, sr, fmt=None):
         from . import resample
         self.x, self.sr = np.ascontiguousarray(x), sr
+        self.fmt = _native.RS_FORMAT[self.x.dtype] if fmt is None else int(fmt)
         self.size = resample.out_len(x.shape[0], sr)
 
 
 def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False):
     """decode_pcm's 16 kHz mono samples; with `resample` (ffmpeg=None only) a WAV at another rate or with several channels
     comes back as a RawSource instead of failing (16 kHz mono files are read exactly as decode_pcm reads them).  Without
-    ffmpeg a FLAC file comes back as a flac.FlacSource (compressed frames, decoded on the device like its WAV twin reads)."""
+    ffmpeg a FLAC file comes back as a flac.FlacSource (compressed frames, decoded on the device like its WAV twin reads),
+    and a file of sndfmt.py as what sndfmt.source makes of it: stored bytes for the device (a RawSource with its format, a
+    sndfmt.AdpcmSource), or the twin's 16 kHz mono array."""
     if ffmpeg is None:
         _check_no_ffmpeg(medianame, start_sec, stop_sec)
-        if flac.sniff(medianame) and not flac._HOST_DECODE:
+        what = sndfmt.device_decoded(medianame)                  # one look at the file's first bytes
+        if what == 'flac' and not flac._HOST_DECODE:
             with open(medianame, 'rb') as f:
                 return flac.source(flac.FlacStream(f.read(), medianame), resample)
+        if what == 'snd':
+            with open(medianame, 'rb') as f:
+                snd = sndfmt.parse(f.read(), medianame)
+            if snd is not None:
+                return sndfmt.source(snd, resample)
     if not resample:
         return decode_pcm(medianame, start_sec, stop_sec, ffmpeg)
     from . import resample as R
@@ -344,13 +355,16 @@ def _media2feats(medianame, start_sec, stop_sec, ffmpeg, ctx=None, resample=Fals
 
 
 def _sig2feats(ctx, sig, medianame='<signal>'):
-    """sig: 16 kHz mono samples (uploaded), a RawSource (resampled on the device into the resident signal), or a FlacSource
-    (decoded on the device: into the signal, resampled, or -- 24-bit -- back to the host for the float path)."""
+    """sig: 16 kHz mono samples (uploaded), a RawSource (resampled on the device into the resident signal), a FlacSource
+    (decoded on the device: into the signal, resampled, or -- 24-bit -- back to the host for the float path), or an
+    AdpcmSource (decoded on the device into the signal, or staged and resampled)."""
     if sig.size < 400:
         raise ValueError(f"media {medianame}: {sig.size} samples, less than one 25 ms analysis window")
     status = None
     if isinstance(sig, RawSource):
-        ctx.resample_signal(sig.x, sig.sr)
+        ctx.resample_signal(sig.x, sig.sr, sig.fmt)
+    elif isinstance(sig, sndfmt.AdpcmSource):
+        status = sndfmt.decode_on(ctx, sig)
     elif isinstance(sig, flac.FlacSource):
         if sig.kind == 'float':
             ctx.set_signal(_to_float(flac.decode_on(ctx, sig), np.float32))
@@ -383,7 +397,7 @@ class Segmenter:
         device: HIP device ordinal.  models: None -> Keras files from ~/.keras/inaSpeechSegmenter
         (remote_utils.py search path); 'synthetic' -> seeded stand-in weights; or a dict
         {model_fname: (layers, in_shape)}.
-        resample (extension, ffmpeg=None only): WAV files at other integer rates (4 000 - 384 000 Hz) or with several
+        resample (extension, ffmpeg=None only): files (WAV, FLAC, G.711 / IMA ADPCM, AIFF, AU, CAF, Wave64) at other integer rates (4 000 - 384 000 Hz) or with several
         channels are downmixed, resampled to 16 kHz and quantised to PCM16 on the device (resample.py states the
         arithmetic) instead of failing; 16 kHz mono files are read as without it."""
         if resample and ffmpeg is not None:
@@ -479,7 +493,8 @@ class Segmenter:
     def load_pcm(self, medianame):
         """The 16 kHz mono samples the front end reads for `medianame` (decode_pcm's int16 or float32 array); with
         resample=True a WAV at another rate or channel count is resampled on the device and its PCM16 copied back.  Without
-        ffmpeg a FLAC file is decoded on the device and its samples copied back (what decode_pcm gives for its WAV twin)."""
+        ffmpeg a FLAC file is decoded on the device and its samples copied back (what decode_pcm gives for its WAV twin),
+        and so is an IMA ADPCM file; G.711 and big-endian files at other rates or channel counts go to the resampler as stored."""
         sig = _load_source(medianame, None, None, self.ffmpeg, self.resample)
         if isinstance(sig, flac.FlacSource):
             if sig.kind == 'float':
@@ -488,8 +503,13 @@ class Segmenter:
             out = self.ctx.get_signal_pcm16(0, sig.size)
             sig.s.check(status)
             return out
+        if isinstance(sig, sndfmt.AdpcmSource):
+            status = sndfmt.decode_on(self.ctx, sig)
+            out = self.ctx.get_signal_pcm16(0, sig.size)
+            sig.s.check(status)
+            return out
         if isinstance(sig, RawSource):
-            return self.ctx.get_signal_pcm16(0, self.ctx.resample_signal(sig.x, sig.sr))
+            return self.ctx.get_signal_pcm16(0, self.ctx.resample_signal(sig.x, sig.sr, sig.fmt))
         return sig
 
     def __call__(self, medianame, start_sec=None, stop_sec=None):

@@ -24,7 +24,7 @@ import numpy as np
 
 from . import _native, keras_model
 from .io import decode_pcm, media2sig16kmono, _to_float
-from . import flac
+from . import sndfmt
 from .segmenter import Segmenter, locate_model
 from .vbx import FeatureExtractor, VBxExtractor, SR, frame_count, pcm16_of, plan_windows
 
@@ -205,7 +205,7 @@ class VoiceFemininityScoring:
     def __call__(self, fpath):
         """-> (score, speech_duration, nb_vectors)  (vbx_segmenter.py:147-202)."""
         basename = os.path.splitext(os.path.basename(fpath))[0]
-        if self.resample or self._reads_flac(fpath):     # one device decode: the VAD and the front end read the same PCM
+        if self.resample or self._decoded_on_device(fpath):     # one device decode: the VAD and the front end read the same PCM
             a = self.vad.load_pcm(fpath)
             signal = _to_float(a, np.float64) if a.dtype == np.int16 else a.astype(np.float64)   # = media2sig16kmono
             vad = self.vad.segment_signal(a)
@@ -226,12 +226,13 @@ class VoiceFemininityScoring:
         g = [(seg[0], seg[1], p) for (_, seg, _), p in zip(x_vectors, pred)]
         return get_femininity_score(g), speech_dur, len(g)
 
-    def _reads_flac(self, fpath):
-        """A FLAC file read without ffmpeg: decoded once on the device (Segmenter.load_pcm), like a resampled WAV."""
+    def _decoded_on_device(self, fpath):
+        """Is the file decoded on the device when read without ffmpeg (FLAC, or a file of sndfmt.py)?  Then it is decoded
+        once (Segmenter.load_pcm), like a resampled WAV."""
         if self.ffmpeg is not None:
             return False
         try:
-            return flac.sniff(fpath)
+            return sndfmt.device_decoded(fpath) is not None
         except OSError:                                   # (missing file, URL: the decode raises as before)
             return False
 
@@ -247,7 +248,7 @@ class VoiceFemininityScoring:
     def _decode(self, fpath, nbtry, trydelay):
         for itry in range(nbtry):
             try:
-                if self.resample or self._reads_flac(fpath):
+                if self.resample or self._decoded_on_device(fpath):
                     return self.vad.load_pcm(fpath)
                 return decode_pcm(fpath, ffmpeg=self.ffmpeg)
             except _native.NativeError:

@@ -91,11 +91,18 @@ int iss_signal_pcm16_device_stream(iss_ctx* ctx, const void* dev_pcm, int64_t n,
 #define ISS_RS_I32  2     /* 32-bit PCM, and 24-bit PCM widened to x << 8 */
 #define ISS_RS_F32  3
 #define ISS_RS_F64  4
+/* (5 .. 7 are not formats: refused)                                                                                  */
+#define ISS_RS_I8   8     /* signed 8-bit (AIFF, AU, CAF): reads like the unsigned 8-bit WAV holding x + 128               */
+#define ISS_RS_ULAW 9     /* G.711 mu-law byte b: u = ~b & 0xFF, t = (((u & 15) << 3) + 0x84) << ((u >> 4) & 7),
+                             value 0x84 - t if u & 0x80 else t - 0x84; reads like the PCM16 WAV holding the value         */
+#define ISS_RS_ALAW 10    /* G.711 A-law byte b: a = b ^ 0x55, t = (a & 15) << 4, s = (a >> 4) & 7; s == 0: t += 8,
+                             s == 1: t += 0x108, s > 1: t = (t + 0x108) << (s - 1); value t if a & 0x80 else -t           */
+#define ISS_RS_SWAP 0x100 /* or-ed onto a 2-, 4- or 8-byte format: the samples are stored big-endian (AIFF, AU, CAF)      */
 typedef struct {
     int64_t src_offset;   /* byte offset of the job's first stored sample in `src` (a multiple of the sample size)   */
     int64_t frames_in;    /* frames (samples per channel) of the source, >= 1                                        */
     int32_t channels;     /* interleaved channels, 1 .. 1024                                                         */
-    int32_t format;       /* ISS_RS_*                                                                                */
+    int32_t format;       /* ISS_RS_*, | ISS_RS_SWAP for big-endian samples                                          */
     int32_t filter;       /* id returned by iss_resample_filter                                                      */
     int32_t reserved;     /* 0                                                                                       */
     int64_t dst_offset;   /* first output sample in the resident signal                                              */
@@ -109,7 +116,7 @@ int iss_resample_filter(iss_ctx* ctx, int32_t up, int32_t down, const double* ta
  *                  left for the resampled files); every sample outside the jobs' ranges stays as uploaded.
  * Then iss_sidekit runs as on any uploaded signal.  `src` is read asynchronously: from page-locked memory
  * (iss_host_alloc) it must stay unchanged until the next synchronising call (iss_get_loge, iss_synchronize, ...).
- * ISS_EINVAL: bad format or channel count, unknown filter, frames_out not ceil(frames_in*up/down), a source range outside
+ * ISS_EINVAL: bad format (ISS_RS_SWAP on a one-byte format included) or channel count, unknown filter, frames_out not ceil(frames_in*up/down), a source range outside
  * `src` or misaligned, a destination range outside the signal, or two destination ranges that overlap.
  * ISS_ESTATE: n_signal < 0 without a resident PCM16 signal of the context's own (iss_signal_pcm16).                  */
 int iss_resample_pcm16(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
@@ -200,6 +207,49 @@ int iss_flac_decode(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_
 int iss_flac_get_stage(iss_ctx* ctx, int32_t job, void* out, int64_t bytes);
 /* FLAC decode launches and frames since the context was created.                                                     */
 int iss_flac_stats(iss_ctx* ctx, int64_t* launches, int64_t* frames);
+
+/* IMA ADPCM in WAV (format tag 0x11) without ffmpeg.  A block of `block_align` bytes holds, per channel, a 4-byte header
+ * (int16 predictor = the block's first sample, uint8 step index <= 88, one reserved byte) and then 4-byte words interleaved
+ * by channel, 8 nibbles each, low nibble first: samples_per_block = (block_align / channels - 4) * 2 + 1.  A nibble n moves
+ * the state by the standard 89-entry step table:  step = table[idx]; d = step >> 3; n&1: d += step >> 2; n&2: d += step >> 1;
+ * n&4: d += step; pred = clamp16(n&8 ? pred - d : pred + d); idx = clamp(idx + {-1,-1,-1,-1,2,4,6,8}[n&7], 0, 88).  The
+ * decoded samples are PCM16, channels interleaved: the file reads like the PCM16 WAV holding them.                       */
+#define ISS_ADPCM_OK          0
+#define ISS_ADPCM_STEP_INDEX  1   /* a channel header's step index is above 88 (decoded from 88: garbage in that block only) */
+#define ISS_ADPCM_TO_SIGNAL   0   /* mono at 16 kHz: PCM16 straight into the resident signal at dst_offset                  */
+#define ISS_ADPCM_TO_STAGE    1   /* interleaved PCM16 into the context's staging buffer (iss_adpcm_get_stage), and with
+                                     filter >= 0 resampled from there into the resident signal like an iss_resample_job    */
+typedef struct {
+    int64_t src_offset;    /* byte offset of the job's first block in `src`, a multiple of 4                             */
+    int64_t block_begin;   /* the job's rows of the status array: [block_begin, block_begin + nblocks)                   */
+    int64_t nblocks;       /* whole blocks, >= 1                                                                          */
+    int64_t frames_total;  /* samples per channel, in ((nblocks - 1) * samples_per_block, nblocks * samples_per_block]     */
+    int32_t channels;      /* 1 .. 64                                                                                     */
+    int32_t block_align;   /* bytes per block: a multiple of 4 * channels, > 4 * channels, at most 32768                  */
+    int32_t output;        /* ISS_ADPCM_TO_SIGNAL / ISS_ADPCM_TO_STAGE                                                    */
+    int32_t filter;        /* TO_STAGE: iss_resample_filter id, or -1 (decode only)                                      */
+    int64_t dst_offset;    /* TO_SIGNAL, or TO_STAGE with a filter: first output sample in the resident signal           */
+    int64_t frames_out;    /* TO_STAGE with a filter: ceil(frames_total * up / down)                                     */
+} iss_adpcm_job;
+/* The host build of the decoder (no context): the blocks of one stream into out (frames_total * channels int16),
+ * status_out[k] = ISS_ADPCM_* of block k.  ISS_EINVAL (nothing decoded): blocks outside buf or a bad geometry.           */
+int iss_adpcm_decode_host(const uint8_t* buf, int64_t len, int64_t nblocks, int32_t channels, int32_t block_align,
+                          int64_t frames_total, int16_t* out, int32_t* status_out);
+/* One H2D copy of `src` (the blocks of every job), ONE launch of adpcm_decode_kernel over the blocks of every job (a wave
+ * per block: lane c walks channel c's predictor chain into LDS, the wave then stores the block's interleaved samples
+ * coalesced), and when some TO_STAGE job has a filter ONE launch of the resample kernel reading the staging buffer.
+ * n_signal as for iss_resample_pcm16.  The staging buffer holds the TO_STAGE jobs in job order, each at a multiple of 16
+ * bytes.  The jobs' status rows must tile [0, nblocks_total) in job order.  status_out (nblocks_total int32, page-locked
+ * memory recommended) is written asynchronously: valid after the next synchronising call (iss_get_loge,
+ * iss_adpcm_get_stage, iss_synchronize, ...).  ISS_EINVAL (nothing launched): a bad geometry, blocks outside `src`,
+ * status rows that do not tile, a TO_SIGNAL job that is not mono, destination ranges outside the signal or overlapping, a
+ * resample job that iss_resample_pcm16 would refuse.  ISS_ESTATE: as iss_resample_pcm16.                               */
+int iss_adpcm_decode(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, int32_t njobs,
+                     int64_t nblocks_total, int64_t n_signal, int32_t* status_out);
+/* The PCM16 samples of TO_STAGE job `job` of the last iss_adpcm_decode (bytes = frames_total * channels * 2); synchronises. */
+int iss_adpcm_get_stage(iss_ctx* ctx, int32_t job, void* out, int64_t bytes);
+/* ADPCM decode launches and blocks since the context was created.                                                    */
+int iss_adpcm_stats(iss_ctx* ctx, int64_t* launches, int64_t* blocks);
 
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */

@@ -34,12 +34,14 @@ def build_parser():
     ap.add_argument('-s', '--batch_size', type=int, default=32, help='accepted for compatibility (the engine sizes its own passes)')
     ap.add_argument('-d', '--vad_engine', choices=['sm', 'smn'], default='smn')
     ap.add_argument('-g', '--detect_gender', type=_truthy, default=True, metavar='{true,false}')
-    ap.add_argument('-b', '--ffmpeg_binary', default='ffmpeg', help="ffmpeg binary; 'None' reads 16 kHz mono WAV or FLAC directly (FLAC decoded on the GPU)")
+    ap.add_argument('-b', '--ffmpeg_binary', default='ffmpeg', help="ffmpeg binary; 'None' reads 16 kHz mono WAV, FLAC, G.711 / IMA ADPCM WAV, AIFF, AU, CAF, Wave64 and RF64 directly "
+                                                                      "(FLAC and IMA ADPCM decoded on the GPU)")
     ap.add_argument('-e', '--export_format', choices=['csv', 'textgrid'], default='csv')
     ap.add_argument('-r', '--energy_ratio', type=float, default=0.03)
     ap.add_argument('--models', default=None, help="'synthetic' = seeded stand-in weights")
     ap.add_argument('--resample', action='store_true',
-                    help='with -b None: downmix and resample WAV / FLAC files of other rates / channel counts to 16 kHz mono on the GPU')
+                    help='with -b None: downmix and resample files of other rates / channel counts (8 kHz G.711 telephony, 44.1 kHz AIFF ...) to '
+                         '16 kHz mono on the GPU')
     return ap
 
 

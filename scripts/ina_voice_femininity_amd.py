@@ -23,11 +23,13 @@ def build_parser():
     ap.add_argument('-i', '--input', nargs='+', required=True, help='media paths or glob patterns')
     ap.add_argument('-o', '--output', required=True, help='TSV file receiving path, score, speech_duration, nb_vectors')
     ap.add_argument('-c', '--criteria', choices=['bgc', 'vfp'], default='bgc', help='gender detection model criteria')
-    ap.add_argument('-b', '--ffmpeg_binary', default='ffmpeg', help="ffmpeg binary; 'None' reads 16 kHz mono WAV or FLAC directly (FLAC decoded on the GPU)")
+    ap.add_argument('-b', '--ffmpeg_binary', default='ffmpeg', help="ffmpeg binary; 'None' reads 16 kHz mono WAV, FLAC, G.711 / IMA ADPCM WAV, AIFF, AU, CAF, Wave64 and RF64 directly "
+                                                                      "(FLAC and IMA ADPCM decoded on the GPU)")
     ap.add_argument('--batch_seconds', type=float, default=3600, help='audio held on the device per batch (seconds)')
     ap.add_argument('--models', default=None, help="'synthetic' = seeded stand-in weights")
     ap.add_argument('--resample', action='store_true',
-                    help='with -b None: downmix and resample WAV / FLAC files of other rates / channel counts to 16 kHz mono on the GPU')
+                    help='with -b None: downmix and resample files of other rates / channel counts (8 kHz G.711 telephony, 44.1 kHz AIFF ...) to '
+                         '16 kHz mono on the GPU')
     return ap
 
 
