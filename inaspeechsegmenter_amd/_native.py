@@ -103,6 +103,7 @@ def lib():
         'iss_host_alloc': (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
         'iss_host_free': (C.c_int, [vp, vp]),
         'iss_cnn_probs_async': (C.c_int, [vp, C.c_int, pi32, i32, pf, pu8, pi64]),
+        'iss_cnn_dead_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_wait': (C.c_int, [vp, i64]),
         'iss_comm_unique_id': (C.c_int, [vp, pu8]),
         'iss_comm_init': (C.c_int, [vp, pu8, i32, i32]),
@@ -151,7 +152,8 @@ def lib():
 
 DIAG_BITS = {'no_shared_first': 0x001, 'no_flrows': 0x002, 'no_ws': 0x004, 'no_ws3': 0x008, 'no_direct1': 0x010,
              'no_nh2': 0x020, 'no_tr': 0x040, 'no_pw': 0x080, 'no_pws': 0x100, 'no_pws2': 0x200, 'no_wq': 0x400,
-             'no_dual': 0x800, 'no_chain': 0x1000, 'no_ring': 0x2000, 'no_fsame': 0x4000, 'no_f32ws': 0x8000, 'no_ncb1': 0x10000, 'no_wsu3': 0x20000, 'no_gfused': 0x40000, 'no_hl': 0x80000}                                                                                         # include/iss.h ISS_DIAG_*
+             'no_dual': 0x800, 'no_chain': 0x1000, 'no_ring': 0x2000, 'no_fsame': 0x4000, 'no_f32ws': 0x8000, 'no_ncb1': 0x10000, 'no_wsu3': 0x20000, 'no_gfused': 0x40000, 'no_hl': 0x80000,
+             'no_skip_dead': 0x100000}                                                                                         # include/iss.h ISS_DIAG_*
 
 
 def diag_flags(names):
@@ -533,6 +535,13 @@ class Context:
         self._ck(self._L.iss_cnn_probs_async(self._h, net_id, _ptr(wr, C.c_int32), n, _ptr(probs_out, C.c_float),
                                              _ptr(finite_out, C.c_uint8), C.byref(t)), 'iss_cnn_probs_async')
         return t.value, probs_out, finite_out
+
+    def cnn_dead_stats(self):
+        """{'windows', 'dead'}: windows cnn_probs / cnn_probs_async were given since the context was created, and how many of them
+        were left out of the passes because they hold a non-finite log-mel value (include/iss.h)."""
+        w, d = C.c_int64(0), C.c_int64(0)
+        self._ck(self._L.iss_cnn_dead_stats(self._h, C.byref(w), C.byref(d)), 'iss_cnn_dead_stats')
+        return {'windows': w.value, 'dead': d.value}
 
     def wait(self, ticket=-1):
         self._ck(self._L.iss_wait(self._h, int(ticket)), 'iss_wait')

@@ -192,7 +192,7 @@ extern "C" int iss_adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, 
         if (nsig > 0) ISS_HIP(c, hipMemsetAsync(c->sig.p, 0, (size_t)nsig * 2, c->stream));
         c->sig_ptr = c->sig.p; c->sig_kind = 1; c->sig_n = nsig;
     }
-    c->have_feats = false;
+    c->have_feats = false; ++c->feat_epoch;
     c->ad_stage_off = stage_off;
     c->ad_stage_bytes = stage_bytes;
     if (blocks == 0) return ISS_OK;

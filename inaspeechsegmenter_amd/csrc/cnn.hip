@@ -1023,6 +1023,31 @@ __global__ void mask_probs_kernel(float* probs, const uint8_t* finite, long long
     if (i < n * C && !finite[i / C]) probs[i] = 0.5f;
 }
 
+// One thread per resident log-mel row: the lowest column that holds a non-finite value, 24 if none.  A window of width w over
+// rows [r, r + 68) with such a flag < w has a non-finite mean (patch_stats_kernel) and so is certainly not finite.
+__global__ __launch_bounds__(256) void row_flags_kernel(const float* __restrict__ mspec, int T, uint8_t* __restrict__ flag) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    float v[24];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) *reinterpret_cast<float4*>(v + 4 * k) = reinterpret_cast<const float4*>(mspec + (size_t)t * 24)[k];
+    flag[t] = (uint8_t)iss_row_flag(v);
+}
+
+// The rows of one pass over the live windows to the caller's slots: out[map[i]] = res[i], or 0.5 where the window did not
+// normalise to finite values (segmenter.py:175); finite[map[i]] = the device's flag.  The dead slots were filled before.
+__global__ void scatter_probs_kernel(const float* __restrict__ res, const uint8_t* __restrict__ lfinite, const int32_t* __restrict__ map,
+                                     long long n, int C, float* __restrict__ out, uint8_t* __restrict__ finite) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * C) return;
+    const long long r = i / C;
+    const int k = (int)(i - r * C);
+    const long long m = map[r];
+    const uint8_t f = lfinite[r];
+    out[m * C + k] = f ? res[i] : 0.5f;
+    if (k == 0) finite[m] = f;
+}
+
 inline int roundup(int a, int b) { return (a + b - 1) / b * b; }
 
 // float -> bf16, round to nearest even (what v_cvt_pk_bf16_f32 does); weights are finite
@@ -2405,6 +2430,43 @@ static int precision_guard(iss_ctx* c, int id, const int32_t* win_row, int32_t n
     return ISS_OK;
 }
 
+// The row flags of the resident features (row_flags_kernel), on the host: computed at the first call after the features changed,
+// with one short wait -- in every caller the stream then holds only the feature kernels (iss_get_loge has just synchronised).
+static int ensure_row_flags(iss_ctx* c) {
+    if (c->flags_epoch == c->feat_epoch) return ISS_OK;
+    int rc;
+    if ((rc = iss_reserve(c, c->d_rowflag, (size_t)c->T))) return rc;
+    if ((rc = iss_rowflag_host(c, (size_t)c->T))) return rc;
+    iss_prof_begin(c, 2, 0);
+    hipLaunchKernelGGL(row_flags_kernel, dim3((c->T + 255) / 256), dim3(256), 0, c->stream, (const float*)c->mspec.p, (int)c->T,
+                       (uint8_t*)c->d_rowflag.p);
+    iss_prof_end(c);
+    ISS_HIP(c, hipGetLastError());
+    ISS_HIP(c, hipMemcpyAsync(c->h_rowflag, c->d_rowflag.p, (size_t)c->T, hipMemcpyDeviceToHost, c->stream));
+    ISS_HIP(c, hipStreamSynchronize(c->stream));
+    c->bad_prefix.clear();
+    c->flags_epoch = c->feat_epoch;
+    return ISS_OK;
+}
+
+// P[t] = rows below t with a non-finite value in their first w columns: the window at row r is dead iff P[r + 68] != P[r]
+static const std::vector<int32_t>& bad_prefix(iss_ctx* c, int w) {
+    std::vector<int32_t>& P = c->bad_prefix[w];
+    if (P.size() != (size_t)c->T + 1) {
+        P.resize((size_t)c->T + 1);
+        P[0] = 0;
+        for (int32_t t = 0; t < c->T; ++t) P[t + 1] = P[t] + (c->h_rowflag[t] < w ? 1 : 0);
+    }
+    return P;
+}
+
+extern "C" int iss_cnn_dead_stats(iss_ctx* c, int64_t* windows, int64_t* dead) {
+    if (!c) return ISS_EINVAL;
+    if (windows) *windows = c->win_total;
+    if (dead) *dead = c->win_dead;
+    return ISS_OK;
+}
+
 static int cnn_probs_impl(iss_ctx* c, int id, const int32_t* win_row, int32_t nslots, float* probs_out,
                           uint8_t* finite_out, bool async, int64_t* ticket_out) {
     if (!c) return ISS_EINVAL;
@@ -2421,49 +2483,97 @@ static int cnn_probs_impl(iss_ctx* c, int id, const int32_t* win_row, int32_t ns
             return iss_fail(c, ISS_EINVAL, "iss_cnn_probs: window %d (row %d) outside the %d resident frames", i, win_row[i], c->T);
     ISS_HIP(c, hipSetDevice(c->device));
     int rc;
-    if (!c->in_guard && n.guard_state == ISS_GUARD_PENDING && (rc = precision_guard(c, id, win_row, nslots))) return rc;
-    if ((rc = iss_reserve(c, c->d_winrow, (size_t)nslots * 4))) return rc;
+    // Dead windows -- a non-finite log-mel value inside (digital silence: whole -inf rows) -- come back as 0.5 / not finite whatever
+    // the network computes, so they are left out of the passes: a pure function of (features, list, width).  `lm` = the live
+    // windows' rows, then their slots; empty when no window is dead, and the call then runs exactly as without this step.
+    // Windows of finite values that do not normalise (std = 0, overflow) stay in: the device's flag decides them as before.
+    std::vector<int32_t> lm;
+    int nlive = nslots;
+    if (!(c->diag & ISS_DIAG_NO_SKIP_DEAD)) {
+        if ((rc = ensure_row_flags(c))) return rc;
+        const std::vector<int32_t>& P = bad_prefix(c, n.in_w);
+        int dead = 0;
+        for (int i = 0; i < nslots; ++i) dead += P[win_row[i] + 68] != P[win_row[i]];
+        if (dead) {
+            nlive = nslots - dead;
+            lm.resize(2 * (size_t)nlive);
+            for (int i = 0, j = 0; i < nslots; ++i)
+                if (P[win_row[i] + 68] == P[win_row[i]]) { lm[j] = win_row[i]; lm[(size_t)nlive + j] = i; ++j; }
+        }
+        if (!c->in_guard) c->win_dead += dead;
+    }
+    if (!c->in_guard) c->win_total += nslots;
+    const bool compact = nlive < nslots;
+    const int32_t* rows = compact ? lm.data() : win_row;          // the list the network runs on
+    if (!c->in_guard && n.guard_state == ISS_GUARD_PENDING && nlive > 0 && (rc = precision_guard(c, id, rows, nlive))) return rc;
+    const size_t nup = compact ? 2 * (size_t)nlive : (size_t)nslots;
+    if ((rc = iss_reserve(c, c->d_winrow, (nup ? nup : 1) * 4))) return rc;
     if ((rc = iss_reserve(c, c->d_stats, (size_t)nslots * 8))) return rc;
     if ((rc = iss_reserve(c, c->d_finite, (size_t)nslots))) return rc;
+    if (compact && (rc = iss_reserve(c, c->d_lfinite, (size_t)(nlive ? nlive : 1)))) return rc;
     if ((rc = iss_reserve(c, c->d_out, (size_t)nslots * n.out_dim * 4))) return rc;
     int bc = 0;
-    if ((rc = plan_chunk(c, n, nslots, &bc))) return rc;
-    if (async) {                                     // the caller may reuse win_row as soon as we return: stage it (pinned)
+    if (nlive > 0 && (rc = plan_chunk(c, n, nlive, &bc))) return rc;
+    // (the device buffers above are shared by calls in flight: one stream orders them, and iss_reserve waits before it frees)
+    if (nup == 0) {                                  // every window is dead: nothing to upload, no CNN launch
+    } else if (async || compact) {                   // the caller may reuse win_row as soon as we return, and lm ends with this call: stage (pinned)
         void* pinned; int slot;
-        if ((rc = iss_stage_host(c, win_row, (size_t)nslots * 4, &pinned, &slot))) return rc;
-        ISS_HIP(c, hipMemcpyAsync(c->d_winrow.p, pinned, (size_t)nslots * 4, hipMemcpyHostToDevice, c->stream));
+        if ((rc = iss_stage_host(c, rows, nup * 4, &pinned, &slot))) return rc;
+        ISS_HIP(c, hipMemcpyAsync(c->d_winrow.p, pinned, nup * 4, hipMemcpyHostToDevice, c->stream));
         iss_stage_mark(c, slot);
     } else {
         ISS_HIP(c, hipMemcpyAsync(c->d_winrow.p, win_row, (size_t)nslots * 4, hipMemcpyHostToDevice, c->stream));
     }
-    iss_prof_begin(c, 2, 0);
-    hipLaunchKernelGGL(patch_stats_kernel, dim3((nslots + 3) / 4), dim3(256), 0, c->stream, (const float*)c->mspec.p,
-                       (const int32_t*)c->d_winrow.p, nslots, n.in_w, (float*)c->d_stats.p, (uint8_t*)c->d_finite.p);
-    iss_prof_end(c);
-    ISS_HIP(c, hipGetLastError());
+    const int32_t* d_map = (const int32_t*)c->d_winrow.p + nlive;
+    uint8_t* d_fin = compact ? (uint8_t*)c->d_lfinite.p : (uint8_t*)c->d_finite.p;
+    const long long tot = (long long)nslots * n.out_dim;
+    if (compact) {                                   // the dead slots (the live ones are overwritten by the scatter)
+        iss_prof_begin(c, 2, 0);
+        hipLaunchKernelGGL(fill_half_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, (float*)c->d_out.p, tot);
+        iss_prof_end(c);
+        ISS_HIP(c, hipGetLastError());
+        ISS_HIP(c, hipMemsetAsync(c->d_finite.p, 0, (size_t)nslots, c->stream));
+    }
+    if (nlive > 0) {
+        iss_prof_begin(c, 2, 0);
+        hipLaunchKernelGGL(patch_stats_kernel, dim3((nlive + 3) / 4), dim3(256), 0, c->stream, (const float*)c->mspec.p,
+                           (const int32_t*)c->d_winrow.p, nlive, n.in_w, (float*)c->d_stats.p, d_fin);
+        iss_prof_end(c);
+        ISS_HIP(c, hipGetLastError());
+    }
     // Shared first layer (ConvArgs::f_*): decided per call from the whole window list, not per chunk, so that the result
     // does not depend on the workspace limit: on when the windows overlap at least 4-fold on average.
     bool share = !(c->diag & ISS_DIAG_NO_SHARED_FIRST);
-    {
-        int gmin = win_row[0], gmax = win_row[0];
-        for (int i = 1; i < nslots; ++i) { gmin = std::min(gmin, win_row[i]); gmax = std::max(gmax, win_row[i]); }
-        if ((long long)(gmax - gmin + 68) * 4 > (long long)nslots * 68) share = false;
+    if (nlive > 0) {
+        int gmin = rows[0], gmax = rows[0];
+        for (int i = 1; i < nlive; ++i) { gmin = std::min(gmin, rows[i]); gmax = std::max(gmax, rows[i]); }
+        if ((long long)(gmax - gmin + 68) * 4 > (long long)nlive * 68) share = false;
     }
-    for (int s0 = 0; s0 < nslots; s0 += bc) {
-        const int cur = std::min(bc, nslots - s0);
+    for (int s0 = 0; s0 < nlive; s0 += bc) {
+        const int cur = std::min(bc, nlive - s0);
         float* res = nullptr;
-        int rmin = win_row[s0], rmax = win_row[s0];
-        for (int i = s0 + 1; i < s0 + cur; ++i) { rmin = std::min(rmin, win_row[i]); rmax = std::max(rmax, win_row[i]); }
+        int rmin = rows[s0], rmax = rows[s0];
+        for (int i = s0 + 1; i < s0 + cur; ++i) { rmin = std::min(rmin, rows[i]); rmax = std::max(rmax, rows[i]); }
         rc = run_program(c, n, cur, (const int32_t*)c->d_winrow.p + s0, (const float*)c->d_stats.p + 2 * (size_t)s0,
-                         (const uint8_t*)c->d_finite.p + s0, nullptr, &res, rmin, rmax, share);
+                         (const uint8_t*)d_fin + s0, nullptr, &res, rmin, rmax, share);
         if (rc) return rc;
-        ISS_HIP(c, hipMemcpyAsync((float*)c->d_out.p + (size_t)s0 * n.out_dim, res, (size_t)cur * n.out_dim * 4,
-                                  hipMemcpyDeviceToDevice, c->stream));
+        if (compact) {
+            const long long ct = (long long)cur * n.out_dim;
+            iss_prof_begin(c, 2, 0);
+            hipLaunchKernelGGL(scatter_probs_kernel, dim3((unsigned)((ct + 255) / 256)), dim3(256), 0, c->stream, (const float*)res,
+                               (const uint8_t*)d_fin + s0, d_map + s0, (long long)cur, n.out_dim, (float*)c->d_out.p, (uint8_t*)c->d_finite.p);
+            iss_prof_end(c);
+            ISS_HIP(c, hipGetLastError());
+        } else {
+            ISS_HIP(c, hipMemcpyAsync((float*)c->d_out.p + (size_t)s0 * n.out_dim, res, (size_t)cur * n.out_dim * 4,
+                                      hipMemcpyDeviceToDevice, c->stream));
+        }
     }
-    const long long tot = (long long)nslots * n.out_dim;
-    hipLaunchKernelGGL(mask_probs_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream,
-                       (float*)c->d_out.p, (const uint8_t*)c->d_finite.p, (long long)nslots, n.out_dim);
-    ISS_HIP(c, hipGetLastError());
+    if (!compact) {
+        hipLaunchKernelGGL(mask_probs_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream,
+                           (float*)c->d_out.p, (const uint8_t*)c->d_finite.p, (long long)nslots, n.out_dim);
+        ISS_HIP(c, hipGetLastError());
+    }
     ISS_HIP(c, hipMemcpyAsync(probs_out, c->d_out.p, (size_t)tot * 4, hipMemcpyDeviceToHost, c->stream));
     ISS_HIP(c, hipMemcpyAsync(finite_out, c->d_finite.p, (size_t)nslots, hipMemcpyDeviceToHost, c->stream));
     if (async) {

@@ -588,7 +588,7 @@ extern "C" int iss_flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, c
         if (nsig > 0) ISS_HIP(c, hipMemsetAsync(c->sig.p, 0, (size_t)nsig * 2, c->stream));
         c->sig_ptr = c->sig.p; c->sig_kind = 1; c->sig_n = nsig;
     }
-    c->have_feats = false;
+    c->have_feats = false; ++c->feat_epoch;
     c->flac_stage_off = stage_off;
     c->flac_stage_bytes = stage_bytes;
     if (nframes == 0) return ISS_OK;

@@ -76,7 +76,7 @@ extern "C" void iss_destroy(iss_ctx* c) {
     for (int i = 0; i < ISS_MAX_NETS; ++i) iss_cnn_free(c, i);
     void* singles[] = {c->d_window, c->d_melw, c->d_mellim, c->d_tw, c->d_vbx_window, c->d_vbx_melw, c->d_vbx_mellim};
     for (void* p : singles) if (p) (void)hipFree(p);
-    DevBuf* bufs[] = {&c->sig, &c->mspec, &c->loge, &c->d_winrow, &c->d_stats, &c->d_finite, &c->d_out, &c->d_in, &c->raw1,
+    DevBuf* bufs[] = {&c->sig, &c->mspec, &c->loge, &c->d_winrow, &c->d_stats, &c->d_finite, &c->d_out, &c->d_in, &c->raw1, &c->d_rowflag, &c->d_lfinite,
                       &c->vbx_sig, &c->vbx_dither, &c->vbx_fb, &c->vbx_out, &c->vbx_meta, &c->rs_src, &c->rs_jobs,
                       &c->flac_src, &c->flac_frames, &c->flac_status, &c->flac_stage,
                       &c->ad_src, &c->ad_jobs, &c->ad_status, &c->ad_stage};
@@ -88,6 +88,7 @@ extern "C" void iss_destroy(iss_ctx* c) {
     for (auto& e : c->ticket_ev) (void)hipEventDestroy(e);
     for (auto& s : c->staging) { if (s.p) (void)hipHostFree(s.p); if (s.done) (void)hipEventDestroy(s.done); }
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
+    if (c->h_rowflag) (void)hipHostFree(c->h_rowflag);
     iss_comm_destroy(c);
     free_buf(c->comm_send); free_buf(c->comm_recv);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -150,7 +151,7 @@ static int put_signal(iss_ctx* c, const void* host, int64_t n, size_t esz, int k
     int rc = iss_reserve(c, c->sig, (size_t)n * esz + 16);
     if (rc) return rc;
     if (n > 0) ISS_HIP(c, hipMemcpyAsync(c->sig.p, host, (size_t)n * esz, hipMemcpyHostToDevice, c->stream));
-    c->sig_ptr = c->sig.p; c->sig_kind = kind; c->sig_n = n; c->have_feats = false;
+    c->sig_ptr = c->sig.p; c->sig_kind = kind; c->sig_n = n; c->have_feats = false; ++c->feat_epoch;
     return ISS_OK;
 }
 extern "C" int iss_signal_pcm16(iss_ctx* c, const int16_t* pcm, int64_t n) { return put_signal(c, pcm, n, 2, 1); }
@@ -173,7 +174,7 @@ extern "C" int iss_signal_pcm16_device_stream(iss_ctx* c, const void* dev, int64
     if (!c->order_ev) ISS_HIP(c, hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming));
     ISS_HIP(c, hipEventRecord(c->order_ev, (hipStream_t)producer_stream));
     ISS_HIP(c, hipStreamWaitEvent(c->stream, c->order_ev, 0));
-    c->sig_ptr = dev; c->sig_kind = 1; c->sig_n = n; c->have_feats = false;
+    c->sig_ptr = dev; c->sig_kind = 1; c->sig_n = n; c->have_feats = false; ++c->feat_epoch;
     return ISS_OK;
 }
 extern "C" int iss_signal_pcm16_device(iss_ctx* c, const void* dev, int64_t n) {
@@ -236,6 +237,15 @@ int iss_stage_host(iss_ctx* c, const void* src, size_t bytes, void** pinned_out,
     *slot_out = slot;
     return ISS_OK;
 }
+int iss_rowflag_host(iss_ctx* c, size_t rows) {
+    if (rows <= c->h_rowflag_cap) return ISS_OK;
+    if (c->h_rowflag) { ISS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(c->h_rowflag); c->h_rowflag = nullptr; c->h_rowflag_cap = 0; }
+    const size_t want = rows + (rows >> 2) + 4096;
+    hipError_t e = hipHostMalloc((void**)&c->h_rowflag, want, hipHostMallocDefault);
+    if (e != hipSuccess) { c->h_rowflag = nullptr; return iss_fail(c, ISS_ENOMEM, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e)); }
+    c->h_rowflag_cap = want;
+    return ISS_OK;
+}
 void iss_stage_mark(iss_ctx* c, int slot) {
     auto& s = c->staging[slot];
     (void)hipEventRecord(s.done, c->stream);
@@ -273,7 +283,7 @@ extern "C" int iss_sidekit(iss_ctx* c, int32_t* T_out) {
     rc = iss_reserve(c, c->loge, (size_t)(T > 0 ? T : 1) * sizeof(float));
     if (rc) return rc;
     if (T > 0) { rc = iss_launch_sidekit(c); if (rc) return rc; }
-    c->have_feats = true;
+    c->have_feats = true; ++c->feat_epoch;
     if (T_out) *T_out = (int32_t)T;
     return ISS_OK;
 }
@@ -305,7 +315,12 @@ extern "C" int iss_set_mspec(iss_ctx* c, const float* mspec, int32_t T) {
     if (rc) return rc;
     ISS_HIP(c, hipMemcpyAsync(c->mspec.p, mspec, (size_t)T * 24 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     ISS_HIP(c, hipStreamSynchronize(c->stream));   // caller may free `mspec` right after
-    c->T = T; c->have_feats = true;
+    c->T = T; c->have_feats = true; ++c->feat_epoch;
+    // the rows are here on the host: their flags (cnn.hip, dead windows) without a launch and a read-back
+    if ((rc = iss_rowflag_host(c, (size_t)T))) return rc;
+    for (int32_t t = 0; t < T; ++t) c->h_rowflag[t] = (uint8_t)iss_row_flag(mspec + (size_t)t * 24);
+    c->bad_prefix.clear();
+    c->flags_epoch = c->feat_epoch;
     return ISS_OK;
 }
 

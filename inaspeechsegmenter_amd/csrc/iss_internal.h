@@ -98,6 +98,17 @@ struct iss_ctx {
     DevBuf mspec, loge;
     int32_t T = 0;
     bool have_feats = false;
+    uint64_t feat_epoch = 1;              // bumped wherever have_feats, sig_* or T is set: what was derived from the features is stale
+
+    // dead windows (cnn.hip, cnn_probs_impl): per resident log-mel row the lowest column holding a non-finite value (24: none),
+    // read back once per feature set, and per network width w the prefix count of rows whose flag is < w
+    uint64_t flags_epoch = 0;             // feat_epoch the row flags belong to
+    DevBuf d_rowflag;
+    uint8_t* h_rowflag = nullptr;         // page-locked, grow-only
+    size_t h_rowflag_cap = 0;
+    std::map<int, std::vector<int32_t>> bad_prefix;
+    DevBuf d_lfinite;                     // finite flags of the compacted (live) window list; d_finite holds the caller's slots
+    int64_t win_total = 0, win_dead = 0;  // iss_cnn_dead_stats
 
     // CNN engine
     IssNet nets[ISS_MAX_NETS];
@@ -152,6 +163,16 @@ int iss_fail(iss_ctx* c, int code, const char* fmt, ...);
 int iss_reserve(iss_ctx* c, DevBuf& b, size_t bytes);
 int iss_stage_host(iss_ctx* c, const void* src, size_t bytes, void** pinned_out, int* slot_out);   // copy into a pinned staging buffer
 void iss_stage_mark(iss_ctx* c, int slot);                                                       // record 'consumed' on the stream
+int iss_rowflag_host(iss_ctx* c, size_t rows);                                                   // page-locked h_rowflag of >= rows bytes
+
+// the lowest column of one 24-column log-mel row that holds a non-finite value, 24 if none (host and device)
+__host__ __device__ inline int iss_row_flag(const float* row) {
+    for (int k = 0; k < 24; ++k) {
+        const float v = row[k];
+        if (!(v - v == 0.f)) return k;            // inf - inf and nan - nan are NaN
+    }
+    return 24;
+}
 
 #define ISS_HIP(c, call)                                                                  \
     do {                                                                                  \

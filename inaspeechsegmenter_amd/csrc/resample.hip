@@ -305,7 +305,7 @@ extern "C" int iss_resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes
         if (nsig > 0) ISS_HIP(c, hipMemsetAsync(c->sig.p, 0, (size_t)nsig * 2, c->stream));
         c->sig_ptr = c->sig.p; c->sig_kind = 1; c->sig_n = nsig;
     }
-    c->have_feats = false;
+    c->have_feats = false; ++c->feat_epoch;
     if (njobs == 0) return ISS_OK;
     rc = iss_reserve(c, c->rs_src, (size_t)std::max<int64_t>(src_bytes, 16));
     if (rc) return rc;

@@ -357,9 +357,22 @@ int iss_cnn_probs(iss_ctx* ctx, int net_id, const int32_t* win_row, int32_t n,
  * iss_host_alloc if the copy is to overlap host work) are valid after iss_wait(ctx, ticket)
  * (or any other call that synchronises the context).  The resident mel spectrogram must not
  * be replaced before iss_wait.  Lets the host run the Viterbi of one network
- * (segmenter.py:176) while the device already evaluates the next one.                  */
+ * (segmenter.py:176) while the device already evaluates the next one.
+ *
+ * Dead windows.  A window that holds a non-finite log-mel value (digital silence gives whole -inf rows) is certainly not finite:
+ * its mean is non-finite.  Both calls leave such windows out of the network's passes and write their 0.5 / finite = 0 rows directly; the
+ * live windows run as a shorter list in the caller's order (their arithmetic is unchanged; tile boundaries move as they do with
+ * the pass size, and the shared-first-layer decision is taken on the live list, so a list with many dead windows may run the
+ * per-window first layer where compute-then-mask shares it: the same values to float32 rounding), and a call without a dead window runs exactly as before.  Windows of finite values that do not normalise
+ * (std = 0, overflow) stay in the list and are decided on the device as ever.  Which windows are dead is known on the host from
+ * one byte per log-mel row (row_flags_kernel; iss_set_mspec scans its argument instead), fetched at the FIRST of these calls
+ * after the resident features changed, with ONE wait for the stream: in every caller the stream then holds only the feature
+ * kernels (iss_get_loge has just synchronised), so the asynchronous form still returns before its own work runs.  The
+ * precision guard probes the live list.  ISS_DIAG_NO_SKIP_DEAD restores compute-then-mask.  iss_cnn_dead_stats: windows
+ * these calls were given, and how many of them were left out, since the context was created (0 left out under the switch). */
 int iss_cnn_probs_async(iss_ctx* ctx, int net_id, const int32_t* win_row, int32_t n,
                         float* probs_out /* n*out_dim */, uint8_t* finite_out /* n */, int64_t* ticket_out);
+int iss_cnn_dead_stats(iss_ctx* ctx, int64_t* windows, int64_t* dead);
 /* Block until the work of `ticket` (and everything enqueued before it) is complete; ticket < 0 = the whole stream. */
 int iss_wait(iss_ctx* ctx, int64_t ticket);
 
@@ -439,7 +452,8 @@ int iss_cnn_set_net_precision(iss_ctx* ctx, int id, int mode);
 #define ISS_DIAG_NO_WSU3         0x20000u /* unpadded 3x3 layers with 64 / 96 output channels on conv_x3_fp_kernel                      */
 #define ISS_DIAG_NO_GFUSED       0x40000u /* the generic gather kernel never reads the shared first-layer rows (per-window first layer)  */
 #define ISS_DIAG_NO_HL           0x80000u /* f32 NHWC activations between the footprint kernels (no CHL layout: conv_x3_wq3_kernel instead of conv_x3_wq3h_kernel) */
-#define ISS_DIAG_ALL             0xfffffu
+#define ISS_DIAG_NO_SKIP_DEAD    0x100000u /* windows over non-finite log-mel values run through the network and are masked afterwards   */
+#define ISS_DIAG_ALL             0x1fffffu
 int iss_set_diag(iss_ctx* ctx, uint32_t flags);
 
 /* FLOPs (2*MAC of the conv/dense outputs actually computed) per sample of a loaded network. */
