@@ -136,6 +136,7 @@ def lib():
         'iss_prof_get_row': (C.c_int, [vp, C.c_int, pd, pi64]),
         'iss_prof_get_instance': (C.c_int, [vp, C.c_int, C.c_char_p, i32, pd, pi64, pd]),
         'iss_set_diag': (C.c_int, [vp, C.c_uint32]),
+        'iss_scribble': (C.c_int, [vp, C.c_uint32]),
         'iss_viterbi_f64': (C.c_int, [pd, i64, i32, pd, pi32]),
         'iss_viterbi_f32': (C.c_int, [pf, i64, i32, pd, pi32]),
         'iss_energy_viterbi': (C.c_int, [pf, i64, C.c_double, C.c_double, C.c_double, pd, pi32]),
@@ -647,6 +648,11 @@ class Context:
         flags = diag_flags(flags) if isinstance(flags, str) else int(flags)
         self._ck(self._L.iss_set_diag(self._h, flags), 'iss_set_diag')
         self.diag = flags
+
+    def scribble(self, word):
+        """Test aid: fill every scratch buffer of the context (capacity, slack included) with the 32-bit `word`; resident
+        signal, features, tables and parameters are left alone (include/iss.h iss_scribble)."""
+        self._ck(self._L.iss_scribble(self._h, int(word) & 0xFFFFFFFF), 'iss_scribble')
 
     def synchronize(self):
         self._ck(self._L.iss_synchronize(self._h), 'iss_synchronize')

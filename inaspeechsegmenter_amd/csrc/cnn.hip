@@ -469,7 +469,11 @@ __global__ __launch_bounds__(256, 3) void conv_x3_pw_kernel(const ConvArgs p) {
 //     the persistent workgroup walks its range of tiles: 12 MFMAs + the fused epilogue per tile.
 // TR: operands swapped (C^T = W . A^T): a lane then holds 4 CONSECUTIVE channels of one pixel per register group and
 // the epilogue stores float4 (8 x 16-byte stores per lane and tile instead of 32 x 4-byte ones); needs pp == 1.
-template <bool TR>
+// F16 (ISS_PREC_F16X3): fp16 halves of the normalised window and of the weights (p.wh / p.wl are then the fp16 split).  With bf16
+// halves here the first layer's 2^-16 operand rounding carried the error of a call on scattered windows in that mode (gender
+// stand-in, 333 rows: max |d log p| 1.08e-4 against float64, over the mode's 1e-4; overlapping lists take the exact-f32 shared
+// first layer and never met it).
+template <bool TR, bool F16>
 __global__ __launch_bounds__(256, 2) void conv1_patch_x3_kernel(const ConvArgs p) {
     __shared__ int s_delta[XBK];                     // k -> ty * 24 + tx  (or -1 for the K padding)
     __shared__ int s_tap[XBK];                       // k -> (ty << 16) | tx
@@ -528,9 +532,15 @@ __global__ __launch_bounds__(256, 2) void conv1_patch_x3_kernel(const ConvArgs p
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float v = x[ks * 8 + e];
-                const __bf16 h = (__bf16)v;
-                ah[ks][e] = h;
-                al[ks][e] = (__bf16)(v - (float)h);
+                if constexpr (F16) {
+                    const _Float16 h = (_Float16)v;
+                    ah[ks][e] = __builtin_bit_cast(__bf16, h);
+                    al[ks][e] = __builtin_bit_cast(__bf16, (_Float16)(v - (float)h));
+                } else {
+                    const __bf16 h = (__bf16)v;
+                    ah[ks][e] = h;
+                    al[ks][e] = (__bf16)(v - (float)h);
+                }
             }
         }
         floatx16 acc0, acc1;
@@ -539,24 +549,24 @@ __global__ __launch_bounds__(256, 2) void conv1_patch_x3_kernel(const ConvArgs p
         if (!TR) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ks], b0h[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ks], b1h[ks], acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks], b0l[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks], b1l[ks], acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks], b0h[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks], b1h[ks], acc1, 0, 0, 0);
+                acc0 = mfma_x3<F16>(al[ks], b0h[ks], acc0);
+                acc1 = mfma_x3<F16>(al[ks], b1h[ks], acc1);
+                acc0 = mfma_x3<F16>(ah[ks], b0l[ks], acc0);
+                acc1 = mfma_x3<F16>(ah[ks], b1l[ks], acc1);
+                acc0 = mfma_x3<F16>(ah[ks], b0h[ks], acc0);
+                acc1 = mfma_x3<F16>(ah[ks], b1h[ks], acc1);
             }
             epilogue_tile(p, acc0, (long long)tile * BM + wv * 32, n0 + li, lh);
             epilogue_tile(p, acc1, (long long)tile * BM + wv * 32, n0 + 32 + li, lh);
         } else {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {             // rows = channels (weight fragment), columns = pixels
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0h[ks], al[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1h[ks], al[ks], acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0l[ks], ah[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1l[ks], ah[ks], acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0h[ks], ah[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1h[ks], ah[ks], acc1, 0, 0, 0);
+                acc0 = mfma_x3<F16>(b0h[ks], al[ks], acc0);
+                acc1 = mfma_x3<F16>(b1h[ks], al[ks], acc1);
+                acc0 = mfma_x3<F16>(b0l[ks], ah[ks], acc0);
+                acc1 = mfma_x3<F16>(b1l[ks], ah[ks], acc1);
+                acc0 = mfma_x3<F16>(b0h[ks], ah[ks], acc0);
+                acc1 = mfma_x3<F16>(b1h[ks], ah[ks], acc1);
             }
             epilogue_tr(p, acc0, acc1, m, n0, lh);
         }
@@ -2161,10 +2171,15 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
         } else if (x3 && patch && a.H_k * a.kw <= XBK && a.M < (1ll << 31)) {
             const dim3 pgrid(std::min<unsigned>(a.nblk, 512u), grid.y);     // persistent, no barriers: 2 workgroups per CU
             iss_prof_tag(c, ISS_PROF_PATCH1);
-            iss_prof_inst(c, "conv1_patch_x3_kernel<%s>", (a.pp == 1 && a.Cout % 4 == 0 && !a.res) ? "true" : "false");
+            const bool ptr = a.pp == 1 && a.Cout % 4 == 0 && !a.res;
+            // fp16 mode: fp16 halves of the normalised window and of the weights here too (|z| <= sqrt(68 * 24), far inside fp16's range)
+            if (row_f16) { a.f16 = 1; a.wh = n.d_wh16 + R[ISS_C_WOFF]; a.wl = n.d_wl16 + R[ISS_C_WOFF]; }
+            iss_prof_inst(c, "conv1_patch_x3_kernel<%s,%s>", ptr ? "true" : "false", a.f16 ? "true" : "false");   // <TR,F16>
             // blob offsets are multiples of 8 floats, so the float4 loads of bias / scale / shift are aligned
-            if (a.pp == 1 && a.Cout % 4 == 0 && !a.res) hipLaunchKernelGGL(conv1_patch_x3_kernel<true>, pgrid, dim3(256), 0, c->stream, a);
-            else hipLaunchKernelGGL(conv1_patch_x3_kernel<false>, pgrid, dim3(256), 0, c->stream, a);
+            if (ptr && a.f16) hipLaunchKernelGGL((conv1_patch_x3_kernel<true, true>), pgrid, dim3(256), 0, c->stream, a);
+            else if (ptr) hipLaunchKernelGGL((conv1_patch_x3_kernel<true, false>), pgrid, dim3(256), 0, c->stream, a);
+            else if (a.f16) hipLaunchKernelGGL((conv1_patch_x3_kernel<false, true>), pgrid, dim3(256), 0, c->stream, a);
+            else hipLaunchKernelGGL((conv1_patch_x3_kernel<false, false>), pgrid, dim3(256), 0, c->stream, a);
         } else if (x3) {
             const bool tr = a.pp == 1 && a.Cout % 4 == 0;     // float4 epilogue on transposed accumulators
             // wider N tiles for wide layers (A staged once per 128 / 256 output channels); 1-D XCD-aware grid

@@ -109,6 +109,27 @@ extern "C" int iss_synchronize(iss_ctx* c) {
     return ISS_OK;
 }
 
+// Test aid (iss.h): every scratch buffer, over its whole capacity, holds `word` afterwards; state is left alone.
+extern "C" int iss_scribble(iss_ctx* c, uint32_t word) {
+    if (!c) return ISS_EINVAL;
+    ISS_HIP(c, hipSetDevice(c->device));
+    ISS_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<DevBuf*> bufs = {&c->raw1, &c->d_stats, &c->d_finite, &c->d_lfinite, &c->d_out, &c->d_in, &c->d_winrow, &c->d_rowflag,
+                                 &c->vbx_fb, &c->vbx_meta, &c->vbx_sig, &c->rs_src, &c->rs_jobs,
+                                 &c->flac_src, &c->flac_frames, &c->flac_status, &c->flac_stage,
+                                 &c->ad_src, &c->ad_jobs, &c->ad_status, &c->ad_stage};
+    for (auto& b : c->act) bufs.push_back(&b);
+    for (DevBuf* b : bufs) {
+        if (!b->p) continue;
+        if (b->cap >= 4) ISS_HIP(c, hipMemsetD32Async((hipDeviceptr_t)b->p, (int)word, b->cap / 4, c->stream));
+        for (size_t i = b->cap & ~(size_t)3; i < b->cap; ++i)      // a capacity need not be a multiple of 4: the word's leading bytes
+            ISS_HIP(c, hipMemsetD8Async((hipDeviceptr_t)((char*)b->p + i), (unsigned char)(word >> (8 * (i & 3))), 1, c->stream));
+    }
+    c->flags_epoch = 0;                    // feat_epoch starts at 1: the row flags are computed again
+    c->bad_prefix.clear();
+    return ISS_OK;
+}
+
 // ---------------------------------------------------------------- sidekit tables
 extern "C" int iss_sidekit_tables(iss_ctx* c, const double* window400, const float* bank) {
     if (!c || !window400 || !bank) return iss_fail(c, ISS_EINVAL, "iss_sidekit_tables: NULL argument");

@@ -384,7 +384,8 @@ int iss_cnn_forward(iss_ctx* ctx, int net_id, const float* x, int32_t n, float* 
 /* Arithmetic mode of the conv/dense GEMMs.  gfx950 has no xf32 / TF32 and its f32-input MFMA runs at 1/16 of the 16-bit rate, so
  * both operands are split x = hi + lo into 16-bit halves and every k-step issues three MFMAs (lo.hi + hi.lo + hi.hi, f32 accumulate):
  *   ISS_PREC_F16X3   (default since round 6) fp16 halves, 11 + 11 mantissa bits, v_mfma_f32_32x32x16_f16, in the kernels that carry the
- *                    segmenter nets' arithmetic (conv_x3_wq_kernel, conv_x3_wq3h_kernel, conv_x3_pw_kernel); exact f32 for their
+ *                    segmenter nets' arithmetic (conv_x3_wq_kernel, conv_x3_wq3h_kernel, conv_x3_pw_kernel, and the per-window first
+ *                    layer of scattered window lists, conv1_patch_x3_kernel); exact f32 for their
  *                    small trailing layers; bf16 halves in every kernel without an fp16 instantiation.  Needs parameters and
  *                    activations inside fp16's range (|x| < 65504; beyond it a result is NaN).  Parameters are checked at load, and
  *                    activations can only be checked by the precision guard's probe, which runs on iss_cnn_probs /
@@ -544,6 +545,18 @@ int iss_prof_get_row(iss_ctx* ctx, int row, double* ms, int64_t* launches);
  * "conv_x3_ws_kernel<5,3,false,false,true,1,1>"), accumulated HIP-event time, launches and algorithmic flops.  This is what
  * bench.py's roofline.dominant is computed from.                                                                        */
 int iss_prof_get_instance(iss_ctx* ctx, int index, char* name_out, int32_t name_len, double* ms, int64_t* launches, double* flops);
+
+/* ------------------------------------------------------------------ test aid
+ * Overwrites scratch, not state.  After a stream sync, fills the full CAPACITY (not the used size) of every device
+ * buffer of the context that holds no state with the 32-bit `word`: the activation buffers with their slack, the shared
+ * first-layer rows, statistics, finite flags, window lists, row flags, the CNN input / output staging, the x-vector
+ * front end's sample / filter-bank / offset buffers, and the source, job, status and staging buffers of the resampler
+ * and the decoders.  Untouched: the resident signal and features (log-mel, log-energy, x-vector features), the cached
+ * dither stream, every table and every network's parameters.  The row flags of the resident features are recomputed at
+ * the next call that needs them.  A result of the library is a function of its inputs, parameters, mode and switches
+ * only, so no call made afterwards may return anything else than before: the tests use this entry with NaN, -inf, 0 and
+ * FLT_MAX to hold that.  What iss_flac_get_stage / iss_adpcm_get_stage would return is gone.  Not for production.     */
+int iss_scribble(iss_ctx* ctx, uint32_t word);
 
 /* ------------------------------------------------------------------ host only
  * Viterbi smoothing, replaces pyannote_viterbi.py:118-224 `viterbi_decoding` on the

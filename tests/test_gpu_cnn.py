@@ -298,26 +298,35 @@ def _pw_program(rng, n, h, w, cin, specs):
     return B.finish((h, w, cin), int(np.prod(shape)), False), x, vals[src].reshape(n, -1)
 
 
+# _pw_program arguments (n, h, w, cin, specs) of test_pointwise_streaming_kernels' cases (tests/screen_jobs.py reads two of them)
+PW_CASES = {
+    # M = 5 * 7 * 11 = 385: three full row tiles + one of a single row
+    'bottleneck_odd_channels': (5, 7, 11, 64, [(96, 1, False, 1, False), (32, 1, False, 1, False), (96, 1, True, 1, False),
+                                               (100, 3, False, 1, False)]),
+    # (8, 10) -> (4, 5): M = 9 * 20 = 180 rows spanning several samples per tile
+    'strided_projection': (9, 8, 10, 64, [(128, 0, False, 2, False), (256, 1, False, 1, False), (128, 1, False, 1, False),
+                                          (256, 1, True, 1, False)]),
+    'post_affine_and_sigmoid': (3, 9, 15, 32, [(64, 1, False, 1, True), (128, 2, False, 1, True), (64, 1, True, 1, True),
+                                               (36, 0, False, 1, False)]),
+    # 8 x 18 maps of ResNet-101's last stage: K = 1024 (32 k-steps), 4 x 128 columns
+    'k1024_n256': (4, 8, 18, 1024, [(256, 1, False, 1, False), (1024, 1, False, 1, False)]),
+    # the segmenter nets' dense head: 301 rows (64-row tiles, last one of 45), K = 4992 -> 192 -> 128 -> tanh 192
+    'dense_192': (301, 1, 1, 4992, [(192, 1, False, 1, False), (128, 1, False, 1, False), (192, 3, False, 1, True)]),
+}
+
+
+def _pw_case(case):
+    """(CompiledNet, x, float64 reference) of one PW_CASES entry, drawn from the case's own seed."""
+    n, h, w, cin, specs = PW_CASES[case]
+    return _pw_program(np.random.default_rng(sum(map(ord, case))), n, h, w, cin, specs)
+
+
 @pytest.mark.parametrize('case', ['bottleneck_odd_channels', 'strided_projection', 'post_affine_and_sigmoid', 'k1024_n256', 'dense_192'])
 def test_pointwise_streaming_kernels(ctx, prec, case):
     """conv_x3_pws_kernel / conv_x3_pws2_kernel (conv_pw.h): partial row tiles (M % 128 != 0), partial column tiles
     (Cout % 64 != 0), in-place residuals, the generic epilogue (sigmoid / tanh / post-activation affine), strided
     1x1 projections and deep K, against a float64 reference of the same GEMM chain."""
-    rng = np.random.default_rng(sum(map(ord, case)))
-    if case == 'bottleneck_odd_channels':       # M = 5 * 7 * 11 = 385: three full row tiles + one of a single row
-        comp, x, ref = _pw_program(rng, 5, 7, 11, 64, [(96, 1, False, 1, False), (32, 1, False, 1, False),
-                                                        (96, 1, True, 1, False), (100, 3, False, 1, False)])
-    elif case == 'strided_projection':          # (8, 10) -> (4, 5): M = 9 * 20 = 180 rows spanning several samples per tile
-        comp, x, ref = _pw_program(rng, 9, 8, 10, 64, [(128, 0, False, 2, False), (256, 1, False, 1, False),
-                                                       (128, 1, False, 1, False), (256, 1, True, 1, False)])
-    elif case == 'post_affine_and_sigmoid':
-        comp, x, ref = _pw_program(rng, 3, 9, 15, 32, [(64, 1, False, 1, True), (128, 2, False, 1, True),
-                                                       (64, 1, True, 1, True), (36, 0, False, 1, False)])
-    elif case == 'dense_192':                   # the segmenter nets' dense head: 301 rows (64-row tiles, last one of 45), K = 4992 -> 192 -> 128 -> tanh 192
-        comp, x, ref = _pw_program(rng, 301, 1, 1, 4992, [(192, 1, False, 1, False), (128, 1, False, 1, False),
-                                                          (192, 3, False, 1, True)])
-    else:                                       # 8 x 18 maps of ResNet-101's last stage: K = 1024 (32 k-steps), 4 x 128 columns
-        comp, x, ref = _pw_program(rng, 4, 8, 18, 1024, [(256, 1, False, 1, False), (1024, 1, False, 1, False)])
+    comp, x, ref = _pw_case(case)
     ctx.cnn_load(5, comp)
     out = ctx.cnn_forward(5, x)
     scale = max(1.0, np.abs(ref).max())
