@@ -21,16 +21,7 @@
 //   pool_kernel          max / average pooling, NHWC (pools that cannot be fused)
 //   softmax_kernel       softmax over channels
 //   statpool_kernel      mean || std over time                           (resnet.py:123-127)
-#include <map>
-#include <numeric>
-#include "conv_common.h"
-#include "conv_ws.h"
-#include "conv_wq.h"
-#include "conv_wq3.h"
-#include "conv_wq3h.h"
-#include "conv_dhl.h"
-#include "conv_pwc.h"
-#include "conv_pw.h"
+#include "conv_select.h"      // kernel selection (and, through it, the kernel headers)
 
 using namespace issk;
 
@@ -1073,11 +1064,6 @@ inline float bf16_to_f32(uint16_t h) {
     memcpy(&x, &u, 4);
     return x;
 }
-// fused-pool window of a conv row (1,1 when absent)
-inline void fused_pool_of(const int32_t* R, int& ph, int& pw) {
-    ph = R[ISS_C_FPOOLH] > 1 ? R[ISS_C_FPOOLH] : 1;
-    pw = R[ISS_C_FPOOLW] > 1 ? R[ISS_C_FPOOLW] : 1;
-}
 
 }  // namespace
 
@@ -1416,56 +1402,272 @@ extern "C" int iss_cnn_flops(iss_ctx* c, int id, double* f) {
 
 namespace {
 
-// Kernel shapes conv_x3_fp_kernel is instantiated for (the tap loop is unrolled at compile time);
-// other shapes run on conv_x3_kernel.
-// conv_x3_ws_kernel decomposes a flattened window pixel p < limit as p / W == (p * ceil(2^16 / W)) >> 16: exact iff
-// limit * (ceil(2^16 / W) * W - 2^16) < 2^16
-inline bool ws_recip_exact(int W, long long limit) {
-    const long long m = (65536 + W - 1) / W;
-    return limit * (m * W - 65536) < 65536 && limit * m < (1ll << 31);
-}
-inline bool ws_shape_compiled(int kh, int kw) {
-#define ISS_WS_HAS(KH_, KW_) if (kh == KH_ && kw == KW_) return true;
-    ISS_WS_SHAPES(ISS_WS_HAS)
-#undef ISS_WS_HAS
-    return false;
-}
-inline bool fp_shape_compiled(int kh, int kw) {
-#define ISS_FP_HAS(KH_, KW_) if (kh == KH_ && kw == KW_) return true;
-    ISS_FP_SHAPES(ISS_FP_HAS)
-#undef ISS_FP_HAS
-    return false;
+// what a pass reads: PATCH / window mode (d_winrow + s0, stats, finite), else an NHWC batch
+struct PassIo { const int32_t* d_winrow; const float* d_stats; const uint8_t* d_fin; const float* d_input; };
+
+// ConvArgs of the launch `ch`: the geometry selection saw, and the pointers, tables and tile counts it did not look at
+int conv_args(iss_ctx* c, IssNet& n, const PassIo& io, int bc, const ConvChoice& ch, ConvArgs& a) {
+    const int r = ch.row;
+    const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
+    memset(&a, 0, sizeof(a));
+    fill_geometry(a, R, bc);
+    a.in = R[ISS_C_IN] == ISS_BUF_INPUT ? io.d_input : (const float*)c->act[R[ISS_C_IN]].p;
+    a.w = n.d_blob + R[ISS_C_WOFF];
+    a.bias = R[ISS_C_BOFF] >= 0 ? n.d_blob + R[ISS_C_BOFF] : nullptr;
+    a.ps = R[ISS_C_PSOFF] >= 0 ? n.d_blob + R[ISS_C_PSOFF] : nullptr;
+    a.pt = R[ISS_C_PTOFF] >= 0 ? n.d_blob + R[ISS_C_PTOFF] : nullptr;
+    a.res = R[ISS_C_RES] >= 0 ? (const float*)c->act[R[ISS_C_RES]].p : nullptr;
+    a.out = (float*)c->act[R[ISS_C_OUT]].p;
+    a.ktab = n.d_ktab + n.ktab_off[r];
+    a.wh = n.d_wh + R[ISS_C_WOFF]; a.wl = n.d_wl + R[ISS_C_WOFF];
+    a.Kpad = n.kpad[r]; a.mode = ch.mode; a.tmr = ch.tmr;
+    if (ch.kernel == ConvKernel::Dhl) return ISS_OK;
+    if (R[ISS_C_INMODE] == 1) {
+        if (!io.d_winrow) return iss_fail(c, ISS_ESTATE, "patch-mode network run without a window list");
+        a.in = (const float*)c->mspec.p; a.win_row = io.d_winrow; a.stats = io.d_stats; a.finite = io.d_fin;
+    } else if (R[ISS_C_INMODE] == 2) {
+        if (!io.d_winrow || !c->vbx_out.p) return iss_fail(c, ISS_ESTATE, "window-mode network run without resident vbx features");
+        a.in = (const float*)c->vbx_out.p; a.win_row = io.d_winrow;
+    } else if (!a.in) return iss_fail(c, ISS_ESTATE, "network input missing");
+    a.nblk = (unsigned)((a.M + BM - 1) / BM);
+    set_fast_div(a, 0, a.pp); set_fast_div(a, 1, a.pw); set_fast_div(a, 2, a.Hq * a.Wq); set_fast_div(a, 3, a.Wq);
+#ifdef ISS_EXPERIMENTS
+    { static const int dbg = getenv("ISS_DBG") ? atoi(getenv("ISS_DBG")) : 0; a.dbg = dbg; }     // timing-only experiment bits (never in a release build)
+#endif
+    a.nblk_n = (unsigned)((a.Cout + BN - 1) / BN);
+    if (ch.kernel == ConvKernel::Pwc) {
+        const int32_t* Q = &n.prog[(size_t)ch.partner * ISS_PROG_COLS];
+        a.wh2 = n.d_wh + Q[ISS_C_WOFF]; a.wl2 = n.d_wl + Q[ISS_C_WOFF];
+        a.bias2 = Q[ISS_C_BOFF] >= 0 ? n.d_blob + Q[ISS_C_BOFF] : nullptr;
+        a.out2 = (float*)c->act[Q[ISS_C_OUT]].p;
+        a.act2 = Q[ISS_C_ACT]; a.Cout2 = Q[ISS_C_COUT];
+    } else if (ch.kernel == ConvKernel::Pws2Dual) {
+        const int32_t* P = &n.prog[(size_t)ch.partner * ISS_PROG_COLS];
+        a.in2 = P[ISS_C_IN] == ISS_BUF_INPUT ? io.d_input : (const float*)c->act[P[ISS_C_IN]].p;
+        a.Cin2 = P[ISS_C_CIN]; a.H2 = P[ISS_C_H]; a.W2 = P[ISS_C_W]; a.sh2 = P[ISS_C_SH]; a.sw2 = P[ISS_C_SW];
+        const int64_t wo = (int64_t)R[ISS_C_DUALW] - 1;
+        a.w = n.d_blob + wo; a.wh = n.d_wh + wo; a.wl = n.d_wl + wo;
+        a.bias = n.d_blob + (R[ISS_C_DUALB] - 1); a.res = nullptr;
+        a.Kpad = a.Cin + a.Cin2;
+    }
+    if (ch.f16) { a.f16 = 1; a.wh = n.d_wh16 + R[ISS_C_WOFF]; a.wl = n.d_wl16 + R[ISS_C_WOFF]; }       // fp16 operand halves
+    if (ch.kernel == ConvKernel::Wq3h) { a.in_hl = 1; a.in_np = ch.in_np; }
+    if (ch.out != OutLayout::F32) { a.out_hl = 1; a.out_np = ch.out_np; a.out_f16 = ch.generic_out && ch.out_f16 ? 1 : 0; }
+    return ISS_OK;
 }
 
-// Host replica of the device's row mapping / footprint arithmetic: does every 128-row tile of this
-// layer touch at most FPIX pixels?  Tiles start at multiples of TM and the pattern repeats every sample, so the tiles
-// starting in the first lcm(rows per sample, TM) rows decide.  The answer is that of a launch over any number of samples:
-// the call's own count (a.M) is not used, so a call of a few windows, whose only tile ends early, takes the kernel a large
-// call takes, and a window's result does not depend on how many windows share its pass.
-int footprint_pixels(const ConvArgs& a, int TM = BM) {      // largest pixel span of a TM-row tile of this layer (INT_MAX: irregular)
-    const long long rows_per_sample = (long long)a.Hq * a.Wq * a.pp;
-    const long long lim_rows = std::lcm(rows_per_sample, (long long)TM);
-    auto pix_of = [&](long long m, int ky, int kx) {
-        long long q = m;
-        int dy = 0, dx = 0;
-        if (a.pp > 1) { q = m / a.pp; const int j = (int)(m - q * a.pp); dy = j / a.pw; dx = j - dy * a.pw; }
-        const int hw = a.Hq * a.Wq;
-        const long long b = q / hw;
-        const int rem = (int)(q - b * hw);
-        const int qy = rem / a.Wq, qx = rem - qy * a.Wq;
-        const int oy = qy * a.ph + dy, ox = qx * a.pw + dx;
-        return (b * a.H + (oy * a.sh - a.pt_ + ky)) * a.W + (ox * a.sw - a.pl_ + kx);
-    };
-    long long worst = 0;
-    for (long long m0 = 0; m0 < lim_rows; m0 += TM) {
-        const long long m_last = m0 + TM - 1;
-        const long long lo = pix_of(m0, 0, 0), hi = pix_of(m_last, a.H_k - 1, a.kw - 1);
-        worst = std::max<long long>(worst, hi - lo + 1);
-        // rows inside the tile never reach below lo / above hi (row-major or pool-window-major order); check anyway
-        for (long long m = m0; m <= m_last; ++m)
-            if (pix_of(m, 0, 0) < lo || pix_of(m, a.H_k - 1, a.kw - 1) > hi) return 0x7fffffff;
+// The shared first layer `pend` of this pass, into c->raw1: the raw convolution once per log-mel row (zero-padded: the shared rows and
+// the per-window edge rows behind them), its fused max-pool where it has one, and the second conv's arguments (ConvArgs::f_*, in,
+// win_row) pointed at the result.  *fl gains the first layer's flops.
+int launch_shared_first_layer(iss_ctx* c, IssNet& n, const PassIo& io, int pend, int bc, int rmin, int rmax, ConvArgs& a, double* fl) {
+    const int32_t* R1 = &n.prog[(size_t)pend * ISS_PROG_COLS];
+    const bool fs1 = R1[ISS_C_HO] == R1[ISS_C_H];                        // zero-padded ('same')
+    int ph1, pw1;
+    fused_pool_of(R1, ph1, pw1);
+    const bool pool1 = ph1 * pw1 != 1;
+    const long long rrows = (long long)(rmax - rmin) + R1[ISS_C_HO];     // R: rows rmin .. rmax + H1 - 1
+    const long long rtot = rrows * R1[ISS_C_WO] * (R1[ISS_C_COUT] / 4);
+    const int f_ne = fs1 ? R1[ISS_C_KH] - 1 : 0;                         // zero-padded first layer: edge rows per window
+    const long long etot = (long long)bc * f_ne * R1[ISS_C_WO] * (R1[ISS_C_COUT] / 4);
+    // pooled planes (ph1 of them) + the transformed window list behind R (see pool_rows_kernel)
+    const int plane_rows = pool1 ? (int)(rrows / ph1) + 2 : 0;
+    const long long ptot = pool1 ? (long long)ph1 * plane_rows * (R1[ISS_C_WO] / pw1) * (R1[ISS_C_COUT] / 4) : 0;
+    { const int rc = iss_reserve(c, c->raw1, (size_t)(rtot + etot + ptot) * 16 + (pool1 ? (size_t)bc * 4 + 16 : 0)); if (rc) return rc; }
+    float* Rraw = (float*)c->raw1.p;
+    const float* mspec = (const float*)c->mspec.p;
+    const float* w1 = n.d_blob + R1[ISS_C_WOFF];
+    const size_t lds1 = (size_t)R1[ISS_C_KH] * R1[ISS_C_KW] * R1[ISS_C_COUT] * 4;
+    iss_prof_begin(c, 2, 0);
+    if (fs1) {
+        // shared rows (all filter rows, the filter columns that see data) + the per-window edge rows behind them
+        const int pt1 = R1[ISS_C_PT], pl1 = R1[ISS_C_PL], pb1 = R1[ISS_C_KH] - 1 - pt1;
+        const float* S = n.d_wsum + n.wsumx_off[pend];
+        if (rtot >= (1ll << 31) || etot >= (1ll << 31)) return iss_fail(c, ISS_EINVAL, "internal: shared first layer over %lld + %lld items", rtot, etot);
+        hipLaunchKernelGGL(first_layer_same_kernel, dim3((unsigned)std::min<long long>((rtot + 255) / 256, 4096)), dim3(256), lds1, c->stream,
+                           mspec, (int)c->T, rmin, rtot, R1[ISS_C_WO], R1[ISS_C_COUT], R1[ISS_C_KH], R1[ISS_C_KW], pt1, pl1, w1, n.kpad[pend], Rraw);
+        if (etot > 0)
+            hipLaunchKernelGGL(first_layer_edge_kernel, dim3((unsigned)std::min<long long>((etot + 255) / 256, 8192)), dim3(256), lds1, c->stream,
+                               mspec, io.d_winrow, io.d_stats, etot, R1[ISS_C_H], R1[ISS_C_WO], R1[ISS_C_COUT], R1[ISS_C_KH],
+                               R1[ISS_C_KW], pt1, pb1, pl1, w1, n.kpad[pend], S, Rraw + (size_t)rtot * 4);
+        a.f_padt = pt1; a.f_padb = pb1; a.f_erow0 = (int)rrows;
+    } else {
+        const dim3 rgrid((unsigned)std::min<long long>((rtot + 255) / 256, 4096));
+        const bool no_rows = (c->diag & ISS_DIAG_NO_FLROWS) != 0;             // diagnostic: the per-output kernel
+        // compiled for the two input widths of the reference's nets: 21 bands (smn / sm) -> 17 positions, 24 (gender) -> 20
+        const bool rows_ok = !no_rows && R1[ISS_C_KH] == 4 && R1[ISS_C_KW] == 5 && (R1[ISS_C_WO] == 17 || R1[ISS_C_WO] == 20) &&
+                             rrows * (R1[ISS_C_COUT] / 4) < (1ll << 31);
+        const dim3 rowgrid((unsigned)std::min<long long>((rrows * (R1[ISS_C_COUT] / 4) + 255) / 256, 4096));
+        if (rows_ok && R1[ISS_C_WO] == 17)
+            hipLaunchKernelGGL((first_layer_rows_kernel<4, 5, 17>), rowgrid, dim3(256), lds1, c->stream, mspec, rmin, (int)rrows, R1[ISS_C_COUT], w1, n.kpad[pend], Rraw);
+        else if (rows_ok)
+            hipLaunchKernelGGL((first_layer_rows_kernel<4, 5, 20>), rowgrid, dim3(256), lds1, c->stream, mspec, rmin, (int)rrows, R1[ISS_C_COUT], w1, n.kpad[pend], Rraw);
+        else if (R1[ISS_C_KH] == 4 && R1[ISS_C_KW] == 5)
+            hipLaunchKernelGGL((first_layer_raw_kernel<4, 5>), rgrid, dim3(256), lds1, c->stream, mspec, rmin, rtot, R1[ISS_C_WO], R1[ISS_C_COUT], 4, 5, w1, n.kpad[pend], Rraw);
+        else
+            hipLaunchKernelGGL((first_layer_raw_kernel<0, 0>), rgrid, dim3(256), lds1, c->stream, mspec, rmin, rtot, R1[ISS_C_WO], R1[ISS_C_COUT],
+                               R1[ISS_C_KH], R1[ISS_C_KW], w1, n.kpad[pend], Rraw);
     }
-    return (int)std::min<long long>(worst, 0x7fffffff);
+    a.in = Rraw; a.win_row = io.d_winrow; a.f_rmin = rmin;
+    if (pool1) {
+        if (ptot >= (1ll << 40)) return iss_fail(c, ISS_EINVAL, "internal: pooled first layer over %lld items", ptot);
+        float* P = Rraw + (size_t)(rtot + etot) * 4;
+        int32_t* wr2 = reinterpret_cast<int32_t*>(P + (size_t)ptot * 4);
+        hipLaunchKernelGGL(pool_rows_kernel, dim3((unsigned)std::min<long long>((ptot + 255) / 256, 8192)), dim3(256), 0, c->stream,
+                           (const float*)Rraw, P, ptot, (int)rrows, R1[ISS_C_WO], R1[ISS_C_COUT], ph1, pw1, plane_rows);
+        hipLaunchKernelGGL(winrow_pool_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, c->stream, io.d_winrow, wr2, bc, rmin, ph1, plane_rows);
+        a.in = P; a.win_row = wr2; a.f_rmin = 0;
+    }
+    iss_prof_end(c);
+    a.stats = io.d_stats; a.finite = io.d_fin;
+    a.f_bias = n.d_blob + R1[ISS_C_BOFF];
+    a.f_wsum = fs1 ? n.d_wsum + n.wsumx_off[pend] : n.d_wsum + n.wsum_off[pend];
+    a.f_ps = R1[ISS_C_PSOFF] >= 0 ? n.d_blob + R1[ISS_C_PSOFF] : nullptr;
+    a.f_pt = R1[ISS_C_PTOFF] >= 0 ? n.d_blob + R1[ISS_C_PTOFF] : nullptr;
+    a.f_act = R1[ISS_C_ACT];
+    *fl += 2.0 * R1[ISS_C_KH] * R1[ISS_C_KW] * (double)R1[ISS_C_COUT] * (double)bc * R1[ISS_C_HO] * R1[ISS_C_WO];
+    return ISS_OK;
+}
+
+// One launch, as selected: per kernel its grid and its launcher, with the template arguments inst_name spells.
+int launch_conv(iss_ctx* c, IssNet& n, const ConvChoice& ch, ConvArgs& a, double fl) {
+    const int r = ch.row;
+    const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
+    const bool padded = ch.padded, tr = ch.tr, fused = ch.fused;
+    const int nh = ch.nh;
+    const dim3 grid(a.nblk, a.nblk_n);
+    const unsigned ny = (unsigned)std::max(1, a.Cout / (2 * BN));                                             // NH = 2: column pairs
+    const unsigned tiles = (unsigned)((a.M + WS_TM - 1) / WS_TM);                                             // 512-row tiles
+    const unsigned groups = (unsigned)((a.M + (long long)WS_TM * WS_G - 1) / ((long long)WS_TM * WS_G));      // ... and groups of WS_G of them
+    const unsigned qtiles = ch.tmr > 0 ? (unsigned)((a.M + ch.tmr - 1) / ch.tmr) : 0;                         // tiles of tmr rows
+    iss_prof_begin(c, 0, fl);
+    iss_prof_tag(c, ch.tag), iss_prof_row(c, r), iss_prof_inst(c, "%s", inst_name(ch).c_str());
+    switch (ch.kernel) {
+    case ConvKernel::Dhl: {
+        const int K = R[ISS_C_CIN];
+        uint16_t*& wp = n.dhl_wp[{r, ch.f16 ? 1 : 0}];
+        if (!wp) {
+            ISS_HIP(c, hipMalloc((void**)&wp, dhl_packed_elems(K, R[ISS_C_COUT]) * 2));
+            iss_dhl_pack((ch.f16 ? n.d_wh16 : n.d_wh) + R[ISS_C_WOFF], (ch.f16 ? n.d_wl16 : n.d_wl) + R[ISS_C_WOFF], wp, R[ISS_C_COUT], n.kpad[r], K, c->stream);
+        }
+        DhlArgs d;
+        d.a = reinterpret_cast<const uint16_t*>(a.in); d.wp = wp; d.bias = a.bias; d.out = a.out;
+        d.np = ch.in_np; d.M = (int)a.M; d.K = K; d.Cout = R[ISS_C_COUT]; d.act = R[ISS_C_ACT];       // (a dense row: one GEMM row per window)
+        iss_dhl_launch(d, c->stream, ch.f16);
+        break;
+    }
+    case ConvKernel::Pwc: iss_pwc_launch(a, c->stream); break;
+    case ConvKernel::Pws2Dual: iss_pws2_launch(a, c->stream, false, true); break;
+    case ConvKernel::Direct1: {
+        const long long items = (long long)(a.M / ((long long)a.H * a.W)) * ((a.H + 7) / 8) * a.W * (a.Cout / 4);
+        if (items >= (1ll << 32)) return iss_fail(c, ISS_EINVAL, "internal: direct first layer over %lld work items", items);
+        const dim3 dgrid((unsigned)std::min<long long>((items + 255) / 256, 8192));
+        const size_t dlds = (size_t)9 * a.Cout * sizeof(float);
+        if (ch.window) hipLaunchKernelGGL(conv1_direct3x3_kernel<true>, dgrid, dim3(256), dlds, c->stream, a);
+        else hipLaunchKernelGGL(conv1_direct3x3_kernel<false>, dgrid, dim3(256), dlds, c->stream, a);
+        break;
+    }
+    case ConvKernel::WsNh2F32: iss_ws_launch_f32_nh2_3x3(a, dim3(std::min<unsigned>(tiles, std::max(1u, 256u / ny)), ny), c->stream, tr); break;
+    case ConvKernel::WsNh2: {                            // one 512-row tile per group
+        const dim3 g2(std::min<unsigned>(tiles, std::max(1u, 256u / ny)), ny);
+        if (padded && !tr) iss_ws_launch_nh2_3x3_padded_pool(a, g2, c->stream);
+        else if (padded) iss_ws_launch_nh2_3x3_padded(a, g2, c->stream);
+        else iss_ws_launch_nh2_3x3(a, g2, c->stream, tr);
+        break;
+    }
+    case ConvKernel::Wq3: case ConvKernel::Wq3h: {
+        const dim3 qgrid(std::min<unsigned>((qtiles + 1) / 2, std::max(1u, 256u / ny)), ny);
+        if (ch.kernel == ConvKernel::Wq3h) iss_wq3h_launch(a, qgrid, c->stream, ch.kind);
+        else iss_wq3_launch(a, qgrid, c->stream, ch.kind);
+        break;
+    }
+    case ConvKernel::WsPlainU: iss_ws_launch_plain_3x3_unpadded(a, dim3(std::min<unsigned>(groups, std::max(1u, 256u / grid.y)), grid.y), c->stream, tr); break;
+    case ConvKernel::WsPlain: iss_ws_launch_plain_3x3(a, dim3(std::min<unsigned>(groups, std::max(1u, 256u / grid.y)), grid.y), c->stream); break;   // one 512-thread workgroup per CU in total
+    case ConvKernel::WsF32Fused: iss_ws_launch_f32_fused_5x3(a, dim3(std::min<unsigned>(groups, 256u), grid.y), c->stream); break;
+    case ConvKernel::WsRing: iss_ws_launch_ring(a, dim3(std::min<unsigned>(qtiles, 256u), grid.y), c->stream, padded); break;   // one tile of tmr rows per group
+    case ConvKernel::WsFs: {                             // FS: one tile per group (conv_ws.h G)
+        const dim3 wgrid(std::min<unsigned>(tiles, 256u), grid.y);
+        if (tr) iss_ws_launch_fs_5x3_tr(a, wgrid, c->stream);
+        else if (a.H_k == 5) iss_ws_launch_fs_5x3(a, wgrid, c->stream, padded);
+        else iss_ws_launch_fs_3x3(a, wgrid, c->stream, padded);
+        break;
+    }
+    case ConvKernel::WsNcb1: iss_ws_launch_ncb1_5x3(a, dim3(std::min<unsigned>(groups, 256u), grid.y), c->stream); break;
+    case ConvKernel::Wq: iss_wq_launch_5x3(a, dim3(std::min<unsigned>((qtiles + 1) / 2, 256u), grid.y), c->stream); break;   // persistent: one 256-thread workgroup per CU
+    case ConvKernel::Ws: {
+        const dim3 wgrid(std::min<unsigned>(groups, 256u), grid.y);         // persistent: one 512-thread workgroup per CU
+#define ISS_WS_CASE(KH_, KW_) if (a.H_k == KH_ && a.kw == KW_) iss_ws_launch_##KH_##x##KW_(a, wgrid, c->stream, padded, tr, fused); else
+        ISS_WS_SHAPES(ISS_WS_CASE) { return iss_fail(c, ISS_EINVAL, "internal: no weight-stationary kernel for %dx%d", a.H_k, a.kw); }
+#undef ISS_WS_CASE
+        break;
+    }
+    case ConvKernel::Fp: {
+        const dim3 pgrid(std::min<unsigned>(a.nblk, 512u), grid.y / nh);     // persistent: 2 workgroups per CU
+#define ISS_FP_CASE(KH_, KW_) if (a.H_k == KH_ && a.kw == KW_) iss_fp_launch_##KH_##x##KW_(a, pgrid, c->stream, padded, tr, fused, nh); else
+        ISS_FP_SHAPES(ISS_FP_CASE) { return iss_fail(c, ISS_EINVAL, "internal: no footprint kernel for %dx%d", a.H_k, a.kw); }
+#undef ISS_FP_CASE
+        break;
+    }
+    case ConvKernel::Patch1: {
+        const dim3 pgrid(std::min<unsigned>(a.nblk, 512u), grid.y);     // persistent, no barriers: 2 workgroups per CU
+        // blob offsets are multiples of 8 floats, so the float4 loads of bias / scale / shift are aligned
+        if (tr && ch.f16) hipLaunchKernelGGL((conv1_patch_x3_kernel<true, true>), pgrid, dim3(256), 0, c->stream, a);
+        else if (tr) hipLaunchKernelGGL((conv1_patch_x3_kernel<true, false>), pgrid, dim3(256), 0, c->stream, a);
+        else if (ch.f16) hipLaunchKernelGGL((conv1_patch_x3_kernel<false, true>), pgrid, dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL((conv1_patch_x3_kernel<false, false>), pgrid, dim3(256), 0, c->stream, a);
+        break;
+    }
+    case ConvKernel::Gather: case ConvKernel::X3: {
+        // wider N tiles for wide layers (A staged once per 128 / 256 output channels); 1-D XCD-aware grid
+        // NTN = 4 (128 x 128 tiles) is compiled but not selected: with the XCD-aware order the A tile is re-read from
+        // L2, not from HBM, and the wider tiles (fewer, fatter workgroups) measured 6 % SLOWER on ResNet-101
+        constexpr int ntn = 2;
+        a.nblk_n = (unsigned)((a.Cout + 32 * ntn - 1) / (32 * ntn));
+        const dim3 gridw(a.nblk * a.nblk_n);
+        if (a.mode == 4 && tr) hipLaunchKernelGGL((conv_x3_kernel<4, true, 2>), gridw, dim3(256), 0, c->stream, a);
+        else if (a.mode == 4) hipLaunchKernelGGL((conv_x3_kernel<4, false, 2>), gridw, dim3(256), 0, c->stream, a);
+        else if (a.mode == 3 && tr) hipLaunchKernelGGL((conv_x3_kernel<3, true, 2>), gridw, dim3(256), 0, c->stream, a);
+        else if (a.mode == 3) hipLaunchKernelGGL((conv_x3_kernel<3, false, 2>), gridw, dim3(256), 0, c->stream, a);
+        else if (a.mode == 0 && tr) hipLaunchKernelGGL((conv_x3_kernel<0, true, 2>), gridw, dim3(256), 0, c->stream, a);
+        else if (a.mode == 0) hipLaunchKernelGGL((conv_x3_kernel<0, false, 2>), gridw, dim3(256), 0, c->stream, a);
+        else if (a.mode == 1 && tr) hipLaunchKernelGGL((conv_x3_kernel<1, true, 2>), gridw, dim3(256), 0, c->stream, a);
+        else if (a.mode == 1) hipLaunchKernelGGL((conv_x3_kernel<1, false, 2>), gridw, dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL((conv_x3_kernel<2, false, 2>), gridw, dim3(256), 0, c->stream, a);
+        break;
+    }
+    case ConvKernel::Pws2Strided: case ConvKernel::Pws2: case ConvKernel::Pws: case ConvKernel::Pw: {
+        if (ch.kernel == ConvKernel::Pws2Strided) iss_pws2_launch(a, c->stream, true);
+        else if (ch.kernel == ConvKernel::Pws2) iss_pws2_launch(a, c->stream);
+        else if (ch.kernel == ConvKernel::Pws) iss_pws_launch(a, dim3(std::min<unsigned>(a.nblk * a.nblk_n, 512u)), c->stream);
+        else if (ch.f16) hipLaunchKernelGGL(conv_x3_pw_kernel<true>, dim3(std::min<unsigned>(a.nblk * a.nblk_n, 768u)), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL(conv_x3_pw_kernel<false>, dim3(std::min<unsigned>(a.nblk * a.nblk_n, 768u)), dim3(256), 0, c->stream, a);
+        break;
+    }
+    case ConvKernel::Igemm: {                            // generic kernels: 1-D, XCD-aware (gemm_tile_of_block)
+        const dim3 grid1(a.nblk * a.nblk_n);
+        if (a.mode == 0) hipLaunchKernelGGL(conv_igemm_kernel<0>, grid1, dim3(256), 0, c->stream, a);
+        else if (a.mode == 1) hipLaunchKernelGGL(conv_igemm_kernel<1>, grid1, dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL(conv_igemm_kernel<2>, grid1, dim3(256), 0, c->stream, a);
+        break;
+    }
+    case ConvKernel::Declined: return iss_fail(c, ISS_EINVAL, "internal: row %d has no kernel", r);
+    }
+    iss_prof_end(c);
+    return ISS_OK;
+}
+
+// One selected launch with what goes in front of it: its arguments, the shared first layer where a kernel reads it, the launch.
+int run_conv(iss_ctx* c, IssNet& n, const ConvEnv& env, const PassIo& io, const ConvChoice& ch, int pend) {
+    const int32_t* R = &n.prog[(size_t)ch.row * ISS_PROG_COLS];
+    ConvArgs a;
+    int rc = conv_args(c, n, io, env.bc, ch, a);
+    if (rc) return rc;
+    double fl = conv_flops(R, (double)a.M);
+    if (ch.kernel == ConvKernel::Dhl) fl = 2.0 * R[ISS_C_CIN] * (double)R[ISS_C_COUT] * (double)env.bc;
+    if (ch.kernel == ConvKernel::Pwc) fl += 2.0 * a.Cout * (double)a.Cout2 * (double)a.M;
+    if (ch.kernel == ConvKernel::Pws2Dual) fl += 2.0 * a.Cin2 * (double)a.Cout * (double)a.M;
+    if (ch.first == FirstLayer::Fused || ch.first == FirstLayer::Gather)
+        if ((rc = launch_shared_first_layer(c, n, io, pend, env.bc, env.rmin, env.rmax, a, &fl))) return rc;
+    return launch_conv(c, n, ch, a, fl);
 }
 
 // Run the op program on `bc` samples.  src: PATCH mode uses (d_winrow + s0, stats, finite),
@@ -1474,824 +1676,37 @@ int footprint_pixels(const ConvArgs& a, int TM = BM) {      // largest pixel spa
 int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const float* d_stats,
                 const uint8_t* d_fin, const float* d_input, float** result, int rmin = 0, int rmax = -1,
                 bool share_first = false) {
-    const int prec = effective_precision(c, n);                 // (precision guard: one network may run another mode)
-    const bool x3mode = prec != ISS_PREC_F32;                    // a split-operand mode (bf16 or fp16 halves)
-    // ISS_PREC_F16X3: the launches with an fp16 instantiation (the one-wave-per-SIMD conv2 / conv3 / conv4 kernels and the long-K
-    // dense kernel: > 99.9 % of the segmenter nets' arithmetic) take fp16 operand halves; a SMALL layer without one runs in exact
-    // f32 (conv_igemm_kernel: tests/precision_emulation.py -- the last dense layers in bf16 halves would undo most of the gain),
-    // anything else keeps bf16 halves
-    const bool f16mode = prec == ISS_PREC_F16X3;
-    double net_flops = 0.0;
-    if (f16mode)
-        for (int q = 0; q < n.nrows; ++q) {
-            const int32_t* Q = &n.prog[(size_t)q * ISS_PROG_COLS];
-            if (Q[ISS_C_OP] == ISS_OP_CONV) net_flops += 2.0 * Q[ISS_C_KH] * Q[ISS_C_KW] * Q[ISS_C_CIN] * (double)Q[ISS_C_COUT] * Q[ISS_C_HO] * Q[ISS_C_WO];
-        }
-    // A PATCH first layer directly in front of a footprint-kernel conv is not launched per window: it is computed once
-    // per log-mel row and the second conv normalises it per window while staging its LDS footprint (ConvArgs::f_*,
-    // conv_fp.h FUSED).  Static part of the test; the footprint-capacity part is decided when the second row is reached
-    // (the first layer is then launched per window after all).
-    auto can_defer = [&](int r) {
-        if (r + 1 >= n.nrows || !share_first || rmax < rmin) return false;
-        // exact-f32 mode: only the shape the F32 form of the weight-stationary kernel is instantiated for (conv_ws.h F32, cnn_ws_h.hip)
-        const bool f32defer = !x3mode;
-        if (f32defer && (c->diag & (ISS_DIAG_NO_WS | ISS_DIAG_NO_F32WS))) return false;
-        const int32_t* R1 = &n.prog[(size_t)r * ISS_PROG_COLS];
-        const int32_t* R2 = &n.prog[(size_t)(r + 1) * ISS_PROG_COLS];
-        int ph, pw;
-        fused_pool_of(R1, ph, pw);
-        const bool pool1 = ph * pw != 1;                 // fused non-overlapping pool behind the first layer: max only, gather path only
-        if (R1[ISS_C_OP] != ISS_OP_CONV || R1[ISS_C_INMODE] != 1 || R1[ISS_C_RES] >= 0 || R1[ISS_C_ACT] > 1) return false;
-        if (pool1 && (R1[ISS_C_POOLKIND] != 0 || !x3mode || (c->diag & ISS_DIAG_NO_GFUSED))) return false;
-        if (R1[ISS_C_CIN] != 1 || R1[ISS_C_SH] != 1 || R1[ISS_C_SW] != 1) return false;
-        const bool valid1 = R1[ISS_C_PT] == 0 && R1[ISS_C_PL] == 0 && R1[ISS_C_HO] == R1[ISS_C_H] - R1[ISS_C_KH] + 1 &&
-                            R1[ISS_C_WO] == R1[ISS_C_W] - R1[ISS_C_KW] + 1;                                                     // 'valid'
-        // 'same' (zero-padded, output = input size): shared through conv_x3_ws_kernel<..., FS> (S table + per-window edge rows)
-        const bool same_geo = !valid1 && R1[ISS_C_HO] == R1[ISS_C_H] && R1[ISS_C_WO] == R1[ISS_C_W] && R1[ISS_C_PT] <= R1[ISS_C_KH] - 1 &&
-                              R1[ISS_C_PL] <= R1[ISS_C_KW] - 1 && R1[ISS_C_KH] <= R1[ISS_C_H] && n.wsumx_off[r] >= 0 && R1[ISS_C_PSOFF] < 0 &&
-                              !(c->diag & ISS_DIAG_NO_FSAME);
-        const bool same_ws = same_geo && R1[ISS_C_W] * R1[ISS_C_COUT] * 4 <= issk::WS_STAB && !(c->diag & ISS_DIAG_NO_WS) &&
-                             issk::iss_ws_fs_compiled(R2[ISS_C_KH], R2[ISS_C_KW]);
-        // ... or through the generic gather kernel (conv_x3_kernel<4>: any second conv)
-        const bool same1 = same_ws || (same_geo && x3mode && !(c->diag & ISS_DIAG_NO_GFUSED));
-        if (!valid1 && !same1) return false;
-        if (pool1 && !valid1) return false;
-        if (f32defer && (!valid1 || !issk::iss_ws_f32_fused_compiled(R2[ISS_C_KH], R2[ISS_C_KW]) || R2[ISS_C_SH] != 1 || R2[ISS_C_SW] != 1 ||
-                         R2[ISS_C_PT] != 0 || R2[ISS_C_PL] != 0 || R1[ISS_C_PSOFF] >= 0)) return false;
-        if (R1[ISS_C_KH] * R1[ISS_C_KW] * R1[ISS_C_COUT] * 4 > 48 * 1024) return false;        // first_layer_raw_kernel's LDS weights
-        if (R1[ISS_C_BOFF] < 0 || (R1[ISS_C_PSOFF] >= 0) != (R1[ISS_C_PTOFF] >= 0) || R1[ISS_C_COUT] % 4 != 0 || n.wsum_off[r] < 0) return false;
-        if (R2[ISS_C_OP] != ISS_OP_CONV || R2[ISS_C_INMODE] != 0 || R2[ISS_C_IN] != R1[ISS_C_OUT] || R2[ISS_C_RES] >= 0) return false;
-        if (R2[ISS_C_CIN] != R1[ISS_C_COUT] || R2[ISS_C_CIN] % XBK != 0 || R2[ISS_C_H] != R1[ISS_C_HO] / ph || R2[ISS_C_W] != R1[ISS_C_WO] / pw) return false;
-        const bool ring2 = valid1 && issk::iss_ws_ring_compiled(R2[ISS_C_KH], R2[ISS_C_KW]) && !(c->diag & (ISS_DIAG_NO_RING | ISS_DIAG_NO_WS));
-        // a footprint kernel can take it: (a zero-padded second conv is fused by the weight-stationary kernel only; conv_row decides);
-        // the footprint may touch two windows at most, and the x / W trick of the kernel needs a small W
-        const bool foot2 = R2[ISS_C_KH] * R2[ISS_C_KW] >= 8 && (fp_shape_compiled(R2[ISS_C_KH], R2[ISS_C_KW]) || ring2) &&   // (>= 12 unless the weight-stationary kernel takes it, see conv_row)
-                           R2[ISS_C_H] * R2[ISS_C_W] >= FPIX + 32 && R2[ISS_C_W] <= 128 && (valid1 || same_ws) && !pool1;
-        // ... or the generic gather kernel reads the shared rows itself (conv_x3_kernel<3>): any second conv, 'valid' first layer
-        const bool gath2 = x3mode && (valid1 || same_geo) && R1[ISS_C_PSOFF] < 0 && !(c->diag & ISS_DIAG_NO_GFUSED);
-        if (!foot2 && !gath2) return false;
-        for (int q = r + 2; q < n.nrows; ++q) {                  // nobody else may read the first layer's output
-            const int32_t* Q = &n.prog[(size_t)q * ISS_PROG_COLS];
-            if (Q[ISS_C_IN] == R1[ISS_C_OUT] || Q[ISS_C_RES] == R1[ISS_C_OUT]) return false;
-            if (Q[ISS_C_OUT] == R1[ISS_C_OUT]) break;
-        }
-        return true;
-    };
-    // rows r, r + 1: an in-place 1x1 stride-1 expansion with identity residual and relu, then a plain 1x1 stride-1 convolution to
-    // 32 / 64 / 128 channels that reads it (the next Bottleneck's reduction, resnet.py:48-58) -- the pair conv_x3_pwc_kernel computes
-    auto chain_pair = [&](int r) {
-        if (r + 1 >= n.nrows) return false;
-        const int32_t* R1 = &n.prog[(size_t)r * ISS_PROG_COLS];
-        const int32_t* R2 = &n.prog[(size_t)(r + 1) * ISS_PROG_COLS];
-        int ph, pw, ph2, pw2;
-        fused_pool_of(R1, ph, pw);
-        fused_pool_of(R2, ph2, pw2);
-        auto plain1x1 = [](const int32_t* R) {
-            return R[ISS_C_OP] == ISS_OP_CONV && R[ISS_C_KH] == 1 && R[ISS_C_KW] == 1 && R[ISS_C_SH] == 1 && R[ISS_C_SW] == 1 &&
-                   R[ISS_C_PT] == 0 && R[ISS_C_PL] == 0 && R[ISS_C_INMODE] == 0 && R[ISS_C_PSOFF] < 0 && R[ISS_C_BOFF] >= 0 &&
-                   R[ISS_C_HO] == R[ISS_C_H] && R[ISS_C_WO] == R[ISS_C_W];
-        };
-        return plain1x1(R1) && plain1x1(R2) && ph * pw == 1 && ph2 * pw2 == 1 && R1[ISS_C_DUALW] == 0 &&
-               R1[ISS_C_RES] >= 0 && R1[ISS_C_RES] == R1[ISS_C_OUT] && R1[ISS_C_IN] != R1[ISS_C_OUT] && R1[ISS_C_IN] != ISS_BUF_INPUT &&
-               R1[ISS_C_ACT] == 1 && R2[ISS_C_IN] == R1[ISS_C_OUT] && R2[ISS_C_RES] < 0 && R2[ISS_C_OUT] != R1[ISS_C_OUT] &&
-               R2[ISS_C_OUT] != R1[ISS_C_IN] && R2[ISS_C_ACT] <= 1 && R2[ISS_C_CIN] == R1[ISS_C_COUT] && issk::pwc_compiled(R1[ISS_C_CIN], R2[ISS_C_COUT]) &&
-               R2[ISS_C_H] == R1[ISS_C_HO] && R2[ISS_C_W] == R1[ISS_C_WO] && n.kpad[r] == R1[ISS_C_CIN] && n.kpad[r + 1] == R2[ISS_C_CIN];
-    };
-#ifdef ISS_PW_NO_ASM_RING                            // build-time escape (Makefile): none of the asm-load kernels of conv_pw.h / conv_pwc.h
-    constexpr bool asm_ring_ok = false;
-#else
-    constexpr bool asm_ring_ok = true;
-#endif
-    // ---- CHL hand-over between footprint kernels (conv_common.h, round 6).  hl_np[buffer] = pixels per plane while the tensor in
-    // that activation buffer is in the CHL layout (absent: f32 NHWC).  A producer writes CHL only when the NEXT row is the tensor's
-    // only reader and runs on conv_x3_wq3h_kernel (wq3_plan: the conditions conv_row launches conv_x3_wq3_kernel under).
-    std::map<int, unsigned> hl_np;
-    std::map<int, bool> hl_f16;                                  // ... and holds fp16 (not bf16) planes
-    std::map<int, bool> hl_dense;                                // ... and is the flattened-feature CHL tensor of a dense layer (conv_dhl.h)
-    bool hl_out_dense = false;
-    bool hl_out_f16 = false;
-    int hl_out_row = -1;                                         // the row conv_row has just launched with a CHL output ...
-    unsigned hl_out_np = 0;                                      // ... and its plane size
-    const bool no_hl = (c->diag & ISS_DIAG_NO_HL) != 0;
-    // (fp16 mode) a small layer -- under 0.5 % of the network's arithmetic -- that no fp16 kernel takes: exact f32.  conv_row(r, pend, ..)
-    // launches by it, and wq3_plan asks it too: a producer must not hand the CHL layout to a row that then runs an f32 kernel
-    auto small_row_of = [&](int r, int pend, bool* f16_dense_pw_out) -> bool {
-        const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
-        const double row_flops = 2.0 * R[ISS_C_KH] * R[ISS_C_KW] * R[ISS_C_CIN] * (double)R[ISS_C_COUT] * R[ISS_C_HO] * R[ISS_C_WO];
-        const bool small_cand = f16mode && pend < 0 && row_flops < 0.005 * net_flops && row_flops < 2e6 &&     // (and small in absolute terms: a
-                                R[ISS_C_INMODE] == 0 && !can_defer(r);                                        //  ResNet-101 has 105 layers under 1 %)
-        // ... unless it is a dense layer of some width (a 512 -> 512 head: 0.5 MFLOP per window, 66 TFLOP/s on conv_igemm_kernel, 5 % of
-        // such a net's step): conv_x3_pw_kernel has an fp16 form for any K, so it takes the layer instead of the streaming kernels
-        int ph, pw;
-        fused_pool_of(R, ph, pw);
-        const bool f16_dense_pw = small_cand && row_flops >= 2.5e5 && R[ISS_C_KH] == 1 && R[ISS_C_KW] == 1 && R[ISS_C_H] == 1 && R[ISS_C_W] == 1 &&
-                                  R[ISS_C_HO] == 1 && R[ISS_C_WO] == 1 && ph * pw == 1 && R[ISS_C_SH] == 1 && R[ISS_C_SW] == 1 && R[ISS_C_PT] == 0 &&
-                                  R[ISS_C_PL] == 0 && R[ISS_C_COUT] % 4 == 0 && R[ISS_C_CIN] % XBK == 0 && n.kpad[r] == R[ISS_C_CIN] && R[ISS_C_RES] < 0 &&
-                                  (c->diag & ISS_DIAG_NO_PW) == 0;
-        if (f16_dense_pw_out) *f16_dense_pw_out = f16_dense_pw;
-        return small_cand && !f16_dense_pw;
-    };
-    auto wq3_plan = [&](int q, int* tmr_out) -> int {            // -1, or the kind (0: bias + relu, 1: relu + 2 x 1 max-pool)
-        if (q < 0 || q >= n.nrows || !x3mode) return -1;
-        if (small_row_of(q, -1, nullptr)) return -1;             // (a CHL consumer has no deferred first layer in front: pend = -1)
-        if (c->diag & (ISS_DIAG_NO_WS | ISS_DIAG_NO_WS3 | ISS_DIAG_NO_WQ)) return -1;
-        const int32_t* R = &n.prog[(size_t)q * ISS_PROG_COLS];
-        if (R[ISS_C_OP] != ISS_OP_CONV || R[ISS_C_INMODE] != 0 || R[ISS_C_IN] == ISS_BUF_INPUT || R[ISS_C_RES] >= 0 || R[ISS_C_DUALW] != 0) return -1;
-        ConvArgs a;
-        memset(&a, 0, sizeof(a));
-        a.H = R[ISS_C_H]; a.W = R[ISS_C_W]; a.Cin = R[ISS_C_CIN]; a.Cout = R[ISS_C_COUT];
-        fused_pool_of(R, a.ph, a.pw);
-        a.pp = a.ph * a.pw;
-        a.poolkind = R[ISS_C_POOLKIND];
-        a.Hq = R[ISS_C_HO] / a.ph; a.Wq = R[ISS_C_WO] / a.pw;
-        a.H_k = R[ISS_C_KH]; a.kw = R[ISS_C_KW];
-        a.sh = R[ISS_C_SH]; a.sw = R[ISS_C_SW]; a.pt_ = R[ISS_C_PT]; a.pl_ = R[ISS_C_PL];
-        a.act = R[ISS_C_ACT];
-        a.M = (long long)bc * a.Hq * a.Wq * a.pp;
-        a.img_stride = (long long)a.H * a.W * a.Cin;
-        const bool padded = a.pt_ != 0 || a.pl_ != 0 || (R[ISS_C_HO] - 1) * a.sh - a.pt_ + a.H_k > a.H || (R[ISS_C_WO] - 1) * a.sw - a.pl_ + a.kw > a.W;
-        if (a.Cin % XBK != 0 || padded || a.sh != 1 || a.sw != 1 || a.Cout % (2 * BN) != 0 || !issk::iss_ws_nh2_compiled(a.H_k, a.kw) || a.H_k != 3 || a.kw != 3 ||
-            a.Cin % F2_CH != 0 || a.Cin < 2 * F2_CH || a.M >= (1ll << 31) || (long long)bc * a.img_stride * 4 >= (1ll << 32)) return -1;
-        if (R[ISS_C_BOFF] < 0 || a.act != 1 || R[ISS_C_PSOFF] >= 0 || !ws_recip_exact(a.W, issk::WQ3_PIX + a.W)) return -1;
-        {
-            const long long key = ((long long)q << 32) | (1ll << 60);
-            auto it = n.fp_pix.find(key);
-            if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
-            if (it->second > WS_PIX2) return -1;
-        }
-        int kind = -1;
-        if (a.pp == 1 && a.M * (long long)a.Cout * 4 < 0xFFF00000ll) kind = 0;
-        else if (a.pp == 2 && a.ph == 2 && a.poolkind == 0 && (a.M / 2) * (long long)a.Cout * 4 < 0xFFF00000ll) kind = 1;
-        if (kind < 0) return -1;
-        const long long key = ((long long)q << 32) | (1ll << 58);
-        auto it = n.fp_pix.find(key);
-        if (it == n.fp_pix.end()) {
-            int tmr = 0;
-            for (int cand = issk::WQ3_TM; cand >= issk::WQ3_TM - 64 && !tmr; cand -= 4)
-                if (footprint_pixels(a, cand) <= issk::WQ3_PIX) tmr = cand;
-            it = n.fp_pix.emplace(key, tmr).first;
-        }
-        if (it->second <= 0) return -1;
-        if (tmr_out) *tmr_out = it->second;
-        return kind;
-    };
-    // row r's output (Cout channels, `npix` pixels for this call) may be written in the CHL layout: row r + 1 is a conv_x3_wq3h_kernel
-    // launch that reads it, and nobody else does before the buffer is written again
-    auto want_hl_out = [&](int r, long long npix) -> bool {
-        if (no_hl || r + 1 >= n.nrows) return false;
-        const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
-        const int32_t* Q = &n.prog[(size_t)(r + 1) * ISS_PROG_COLS];
-        const int ob = R[ISS_C_OUT];
-        if (Q[ISS_C_IN] != ob || Q[ISS_C_OUT] == ob || Q[ISS_C_CIN] != R[ISS_C_COUT] || R[ISS_C_COUT] % (2 * BN) != 0 && R[ISS_C_COUT] != BN) return false;
-        if (npix != (long long)bc * Q[ISS_C_H] * Q[ISS_C_W] || !issk::chl_fits(npix, R[ISS_C_COUT])) return false;
-        if (wq3_plan(r + 1, nullptr) < 0) return false;
-        for (int t = r + 2; t < n.nrows; ++t) {
-            const int32_t* T = &n.prog[(size_t)t * ISS_PROG_COLS];
-            if (T[ISS_C_IN] == ob || T[ISS_C_RES] == ob) return false;
-            if (T[ISS_C_OUT] == ob) break;
-        }
-        return true;
-    };
-    // row r is a pooled conv launch (conv_x3_wq3h_kernel<1, ..>) whose output, flattened, is read by the dense layer of row r + 1 and by
-    // nobody else: it may write the CHL tensor conv_dhl_kernel fetches by LDS-DMA (window = "pixel", feature = "channel")
-    auto want_dhl_out = [&](int r, int hq, int wq) -> bool {
-        if (no_hl || r + 1 >= n.nrows || !x3mode) return false;
-        const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
-        const int32_t* Q = &n.prog[(size_t)(r + 1) * ISS_PROG_COLS];
-        const int ob = R[ISS_C_OUT];
-        const long long K = (long long)hq * wq * R[ISS_C_COUT];
-        int qph, qpw;
-        fused_pool_of(Q, qph, qpw);
-        if (Q[ISS_C_OP] != ISS_OP_CONV || Q[ISS_C_IN] != ob || Q[ISS_C_OUT] == ob || Q[ISS_C_INMODE] != 0 || Q[ISS_C_RES] >= 0 || Q[ISS_C_DUALW] != 0) return false;
-        if (Q[ISS_C_KH] != 1 || Q[ISS_C_KW] != 1 || Q[ISS_C_H] != 1 || Q[ISS_C_W] != 1 || Q[ISS_C_HO] != 1 || Q[ISS_C_WO] != 1 || qph * qpw != 1) return false;
-        if (Q[ISS_C_CIN] != K || n.kpad[r + 1] != K || hq * wq < 2 || R[ISS_C_COUT] % 8 != 0) return false;
-        if (!issk::dhl_supported((int)K, Q[ISS_C_COUT], Q[ISS_C_ACT], Q[ISS_C_PSOFF] >= 0, false)) return false;
-        const size_t bytes = (size_t)issk::dhl_npad(bc) * (size_t)K * 4;
-        if (bytes > (size_t)bc * K * 4 + issk::ISS_ACT_SLACK || bytes >= 0xFFF00000ull || (long long)bc * hq * wq * (hq * wq) >= (1ll << 32)) return false;
-        if ((long long)bc * Q[ISS_C_COUT] * 4 >= (1ll << 32)) return false;
-        for (int t = r + 2; t < n.nrows; ++t) {
-            const int32_t* T = &n.prog[(size_t)t * ISS_PROG_COLS];
-            if (T[ISS_C_IN] == ob || T[ISS_C_RES] == ob) return false;
-            if (T[ISS_C_OUT] == ob) break;
-        }
-        return true;
-    };
-    constexpr int kDualDeclined = -12345;                        // conv_row(r, -1, r - 1): the two-source launch is not possible for this call
-    std::function<int(int, int, int, int)> conv_row = [&](int r, int pend, int dual, int chain) -> int {
-        const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
-        const float* in = R[ISS_C_IN] == ISS_BUF_INPUT ? d_input : (const float*)c->act[R[ISS_C_IN]].p;
-        float* out = (float*)c->act[R[ISS_C_OUT]].p;
-        ConvArgs a;
-        memset(&a, 0, sizeof(a));
-        a.in = in;
-        a.w = n.d_blob + R[ISS_C_WOFF];
-        a.bias = R[ISS_C_BOFF] >= 0 ? n.d_blob + R[ISS_C_BOFF] : nullptr;
-        a.ps = R[ISS_C_PSOFF] >= 0 ? n.d_blob + R[ISS_C_PSOFF] : nullptr;
-        a.pt = R[ISS_C_PTOFF] >= 0 ? n.d_blob + R[ISS_C_PTOFF] : nullptr;
-        a.res = R[ISS_C_RES] >= 0 ? (const float*)c->act[R[ISS_C_RES]].p : nullptr;
-        a.out = out;
-        a.ktab = n.d_ktab + n.ktab_off[r];
-        a.wh = n.d_wh + R[ISS_C_WOFF];
-        a.wl = n.d_wl + R[ISS_C_WOFF];
-        a.H = R[ISS_C_H]; a.W = R[ISS_C_W]; a.Cin = R[ISS_C_CIN]; a.Cout = R[ISS_C_COUT];
-        fused_pool_of(R, a.ph, a.pw);
-        a.pp = a.ph * a.pw;
-        a.poolkind = R[ISS_C_POOLKIND];
-        a.Hq = R[ISS_C_HO] / a.ph; a.Wq = R[ISS_C_WO] / a.pw;
-        a.H_k = R[ISS_C_KH]; a.kw = R[ISS_C_KW];
-        a.sh = R[ISS_C_SH]; a.sw = R[ISS_C_SW]; a.pt_ = R[ISS_C_PT]; a.pl_ = R[ISS_C_PL];
-        a.act = R[ISS_C_ACT]; a.Kpad = n.kpad[r];
-        a.M = (long long)bc * a.Hq * a.Wq * a.pp;
-        const bool patch = R[ISS_C_INMODE] == 1;
-        bool f16_dense_pw = false;
-        const bool small_row = small_row_of(r, pend, &f16_dense_pw);
-        const bool x3 = x3mode && !small_row;
-        bool row_f16 = f16mode;                                  // cleared below where the launch has no fp16 form
-        const bool in_is_hl = R[ISS_C_IN] != ISS_BUF_INPUT && hl_np.count(R[ISS_C_IN]) != 0;     // (only conv_x3_wq3h_kernel reads that layout)
-        bool in_hl_taken = false;
-        if (in_is_hl && hl_dense.count(R[ISS_C_IN])) {
-            // the first dense layer on the flattened-feature CHL tensor conv4 wrote for it (want_dhl_out): both operands by LDS-DMA
-            const bool f16 = hl_f16.count(R[ISS_C_IN]) != 0;
-            const int K = R[ISS_C_CIN];
-            uint16_t*& wp = n.dhl_wp[{r, f16 ? 1 : 0}];
-            if (!wp) {
-                ISS_HIP(c, hipMalloc((void**)&wp, issk::dhl_packed_elems(K, R[ISS_C_COUT]) * 2));
-                issk::iss_dhl_pack((f16 ? n.d_wh16 : n.d_wh) + R[ISS_C_WOFF], (f16 ? n.d_wl16 : n.d_wl) + R[ISS_C_WOFF], wp, R[ISS_C_COUT], n.kpad[r], K, c->stream);
-            }
-            issk::DhlArgs d;
-            d.a = reinterpret_cast<const uint16_t*>(in); d.wp = wp; d.bias = a.bias; d.out = out;
-            d.np = hl_np[R[ISS_C_IN]]; d.M = bc; d.K = K; d.Cout = R[ISS_C_COUT]; d.act = R[ISS_C_ACT];
-            iss_prof_begin(c, 0, 2.0 * K * (double)R[ISS_C_COUT] * (double)bc);
-            iss_prof_tag(c, ISS_PROF_PW);
-            iss_prof_row(c, r);
-            iss_prof_inst(c, "conv_dhl_kernel<%s,%d>", f16 ? "true" : "false", ISS_DHL_NW);       // <F16,NW>
-            issk::iss_dhl_launch(d, c->stream, f16);
-            iss_prof_end(c);
-            return ISS_OK;
-        }
-        a.mode = patch ? 2 : ((a.Cin % (x3 ? XBK : 4) == 0) ? 0 : 1);
-        const bool window = R[ISS_C_INMODE] == 2;
-        if (patch) {
-            if (!d_winrow) return iss_fail(c, ISS_ESTATE, "patch-mode network run without a window list");
-            a.in = (const float*)c->mspec.p; a.win_row = d_winrow; a.stats = d_stats; a.finite = d_fin;
-            a.row_stride = 24; a.pix_stride = 1; a.img_stride = 0;
-        } else if (window) {
-            if (!d_winrow || !c->vbx_out.p) return iss_fail(c, ISS_ESTATE, "window-mode network run without resident vbx features");
-            a.in = (const float*)c->vbx_out.p; a.win_row = d_winrow;
-            a.row_stride = 1; a.pix_stride = a.H; a.img_stride = 0;
-            a.mode = 1;
-        } else {
-            if (!in) return iss_fail(c, ISS_ESTATE, "network input missing");
-            a.row_stride = a.W * a.Cin; a.pix_stride = a.Cin; a.img_stride = (long long)a.H * a.W * a.Cin;
-        }
-        a.nblk = (unsigned)((a.M + BM - 1) / BM);
-        set_fast_div(a, 0, a.pp); set_fast_div(a, 1, a.pw); set_fast_div(a, 2, a.Hq * a.Wq); set_fast_div(a, 3, a.Wq);
-#ifdef ISS_EXPERIMENTS
-        { static const int dbg = getenv("ISS_DBG") ? atoi(getenv("ISS_DBG")) : 0; a.dbg = dbg; }     // timing-only experiment bits (never in a release build)
-#endif
-        a.nblk_n = (unsigned)((a.Cout + BN - 1) / BN);
-        dim3 grid(a.nblk, a.nblk_n);
-        const dim3 grid1(a.nblk * a.nblk_n);          // generic kernels: 1-D, XCD-aware (gemm_tile_of_block)
-        double fl = 2.0 * R[ISS_C_KH] * R[ISS_C_KW] * a.Cin * (double)a.Cout * (double)a.M;
-        if (chain >= 0) {
-            // row r (in-place 1x1 expansion + identity residual + relu) and row `chain` = r + 1 (the next Bottleneck's 1x1 reduction
-            // to 128 channels, which reads row r's output) as ONE launch: the reduction consumes x' out of LDS (conv_pwc.h)
-            const int32_t* Q = &n.prog[(size_t)chain * ISS_PROG_COLS];
-            a.wh2 = n.d_wh + Q[ISS_C_WOFF]; a.wl2 = n.d_wl + Q[ISS_C_WOFF];
-            a.bias2 = Q[ISS_C_BOFF] >= 0 ? n.d_blob + Q[ISS_C_BOFF] : nullptr;
-            a.out2 = (float*)c->act[Q[ISS_C_OUT]].p;
-            a.act2 = Q[ISS_C_ACT]; a.Cout2 = Q[ISS_C_COUT];
-            if (!x3 || a.mode != 0 || !in || !issk::pwc_supported(a)) return kDualDeclined;
-            fl += 2.0 * Q[ISS_C_CIN] * (double)Q[ISS_C_COUT] * (double)a.M;
-            iss_prof_begin(c, 0, fl);
-            iss_prof_tag(c, ISS_PROF_PW);
-            iss_prof_row(c, r);
-            iss_prof_inst(c, "conv_x3_pwc_kernel<%d,%d>", a.Cin / 32, a.Cout2 / 32);
-            issk::iss_pwc_launch(a, c->stream);
-            iss_prof_end(c);
-            return ISS_OK;
-        }
-        if (dual >= 0) {
-            // rows `dual` (a linear 1x1 projection, any stride) and r (the in-place 1x1 expansion it is added to) as ONE GEMM over
-            // both inputs on the concatenated weights (ISS_C_DUALW; validated by iss_cnn_load): row `dual`'s output never exists
-            const int32_t* P = &n.prog[(size_t)dual * ISS_PROG_COLS];
-            a.in2 = P[ISS_C_IN] == ISS_BUF_INPUT ? d_input : (const float*)c->act[P[ISS_C_IN]].p;
-            a.Cin2 = P[ISS_C_CIN]; a.H2 = P[ISS_C_H]; a.W2 = P[ISS_C_W]; a.sh2 = P[ISS_C_SH]; a.sw2 = P[ISS_C_SW];
-            const int64_t wo = (int64_t)R[ISS_C_DUALW] - 1;
-            a.w = n.d_blob + wo; a.wh = n.d_wh + wo; a.wl = n.d_wl + wo;
-            a.bias = n.d_blob + (R[ISS_C_DUALB] - 1);
-            a.res = nullptr;
-            a.Kpad = a.Cin + a.Cin2;
-            if (!x3 || a.mode != 0 || !in || !a.in2 || !issk::pws2_dual_supported(a)) return kDualDeclined;
-            fl += 2.0 * a.Cin2 * (double)a.Cout * (double)a.M;
-            iss_prof_begin(c, 0, fl);
-            iss_prof_tag(c, ISS_PROF_PW);
-            iss_prof_row(c, r);
-            iss_prof_inst(c, "conv_x3_pws2_kernel<true,false,dual>");
-            issk::iss_pws2_launch(a, c->stream, false, true);
-            iss_prof_end(c);
-            return ISS_OK;
-        }
-        bool fp = false;                               // LDS-footprint kernel usable
-        if (x3 && a.mode == 0 && fp_shape_compiled(a.H_k, a.kw) && a.M < (1ll << 31)) {
-            const long long key = ((long long)r << 32);
-            auto it = n.fp_pix.find(key);
-            if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a)).first;
-            fp = it->second <= FPIX;
-        }
-        // weight-stationary kernel (conv_ws.h): the shared-first-layer convolution, 8..16 taps, one N tile of 64 channels
-        bool ws = false;
-        const bool no_ws = (c->diag & ISS_DIAG_NO_WS) != 0;
-        // the deferred first layer in front is zero-padded ('same'): only the FS form of the weight-stationary kernel can fuse it
-        const bool fs1 = pend >= 0 && (n.prog[(size_t)pend * ISS_PROG_COLS + ISS_C_HO] == n.prog[(size_t)pend * ISS_PROG_COLS + ISS_C_H]);
-        int ph1 = 1, pw1 = 1;                            // the deferred first layer's own fused (max) pool: the gather form only
-        if (pend >= 0) fused_pool_of(&n.prog[(size_t)pend * ISS_PROG_COLS], ph1, pw1);
-        const bool pool1 = ph1 * pw1 != 1;
-        if (!no_ws && fp && pend >= 0 && a.H_k * a.kw >= 8 && a.H_k * a.kw <= WS_MAXNT && ws_shape_compiled(a.H_k, a.kw) &&
-            a.Cin % F2_CH == 0 && a.H * a.W >= WS_PIX + 64 + (a.pt_ + 1) * a.W && ws_recip_exact(a.W, a.H * a.W + WS_PIX + a.W)) {
-            const long long key = ((long long)r << 32) | (1ll << 62);
-            auto it = n.fp_pix.find(key);
-            if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
-            ws = it->second <= WS_PIX && n.prog[(size_t)pend * ISS_PROG_COLS + ISS_C_PSOFF] < 0;     // (a post-activation affine of the
-        }                                                                                            //  first layer stays on conv_x3_fp_kernel)
-        // ring form (conv_ws.h RING): more than WS_MAXNT taps (7x7), first-layer-fused, one 512-row tile per group on a
-        // 1024-pixel footprint; row-major epilogue
-        bool ws_ring = false;
-        if (!no_ws && !(c->diag & ISS_DIAG_NO_RING) && pend >= 0 && !fs1 && x3 && a.mode == 0 && issk::iss_ws_ring_compiled(a.H_k, a.kw) &&
-            a.sh == 1 && a.sw == 1 && a.Cin % F2_CH == 0 && a.Cin >= 2 * F2_CH && a.M < (1ll << 31) &&
-            ws_recip_exact(a.W, a.H * a.W + WS_PIX2 + a.W) && n.prog[(size_t)pend * ISS_PROG_COLS + ISS_C_PSOFF] < 0) {
-            // rows per tile: the largest multiple of 4 (<= 512, >= 320) whose footprint fits the 1024 pixels -- a 512-row tile of a
-            // pooled 59 x 14 output under a 7-row filter spans 1036 pixels, 496 rows 1002 (ConvArgs::tmr; the rest of the tile idles)
-            const long long key = ((long long)r << 32) | (1ll << 57);
-            auto it = n.fp_pix.find(key);
-            if (it == n.fp_pix.end()) {
-                // ... and reaches into at most ONE following window (the fetch decomposes a footprint position into two windows)
-                const int cap = std::min<long long>(WS_PIX2, (long long)a.H * a.W - 64 - (long long)(a.pt_ + 1) * a.W);
-                int tmr = 0;
-                for (int cand = WS_TM; cand >= 320 && !tmr; cand -= 4)
-                    if (footprint_pixels(a, cand) <= cap) tmr = cand;
-                it = n.fp_pix.emplace(key, tmr).first;
-            }
-            a.tmr = it->second;
-            ws_ring = a.tmr > 0 && a.M % 4 == 0;
-            if (ws_ring) { ws = true; fp = true; } else a.tmr = 0;
-        }
-        const bool padded = a.pt_ != 0 || a.pl_ != 0 ||
-                            (R[ISS_C_HO] - 1) * a.sh - a.pt_ + a.H_k > a.H || (R[ISS_C_WO] - 1) * a.sw - a.pl_ + a.kw > a.W;
-        // exact-f32 mode (ISS_PREC_F32): the F32 form of the weight-stationary kernel for the first-layer-fused 5x3 layer
-        const bool no_f32ws = (c->diag & ISS_DIAG_NO_F32WS) != 0;
-        bool ws_f32 = false;
-        if (!x3 && !no_ws && !no_f32ws && pend >= 0 && !fs1 && a.mode == 0 && issk::iss_ws_f32_fused_compiled(a.H_k, a.kw) && !padded &&
-            a.sh == 1 && a.sw == 1 && issk::epi_is_pool_relu(a) && a.Cin % F2_CH == 0 && a.Cin >= 2 * F2_CH && a.M < (1ll << 31) &&
-            a.H * a.W >= WS_PIX + 64 + a.W && ws_recip_exact(a.W, a.H * a.W + WS_PIX + a.W) &&
-            n.prog[(size_t)pend * ISS_PROG_COLS + ISS_C_PSOFF] < 0) {
-            const long long key = ((long long)r << 32) | (1ll << 62);
-            auto it = n.fp_pix.find(key);
-            if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
-            ws_f32 = it->second <= WS_PIX;
-            if (ws_f32) { ws = true; fp = true; }
-        }
-        // FS form: row-major epilogue only.  A second conv WITHOUT a fused pool is not taken: its unpooled output through the row-major
-        // epilogue (4-byte stores) measured 3.1 -> 2.3 h/s on conv1_same_nopool against the per-window first layer + transposed kernel
-        // ... except the one transposed instantiation: unpadded 5x3 with bias + relu (cnn_ws_f.hip)
-        const bool fs_tr = a.pp == 1 && a.Cout % 4 == 0;
-        const bool fs_tr_ok = fs_tr && a.H_k == 5 && a.kw == 3 && !padded && issk::epi_is_simple_tr(a);
-        const bool ws_fs = fs1 && ws && issk::iss_ws_fs_compiled(a.H_k, a.kw) && (!fs_tr || fs_tr_ok) && a.sh == 1 && a.sw == 1 && a.W * a.Cin * 4 <= issk::WS_STAB &&
-                           a.Cin >= 2 * F2_CH && !(c->diag & ISS_DIAG_NO_FSAME);
-        if (fs1 && !ws_fs) ws = false;
-        // weight-stationary kernel with two column halves per workgroup (conv_ws.h, NH = 2): unpadded 3x3 stride-1 layers with
-        // a multiple of 128 output channels whose 512-row tiles fit a 1024-pixel footprint -- the 3x3 layers of the segmenter nets
-        bool ws_nh2 = false;
-        const bool no_ws3 = (c->diag & ISS_DIAG_NO_WS3) != 0;
-        const bool nh2_pad_pool = a.pp > 1 && issk::epi_is_pool_relu(a);                         // ... and row-major with the pooled relu epilogue
-        const bool nh2_pad_ok = (a.pp == 1 && a.Cout % 4 == 0 && issk::epi_is_simple_tr(a)) || nh2_pad_pool;   // the padded form is compiled transposed + simple
-        // (exact-f32 mode: the unpadded form with the simple transposed or the pooled relu epilogue only -- cnn_ws_h.hip)
-        const bool nh2_f32 = !x3 && !no_f32ws && !padded && ((a.pp == 1 && a.Cout % 4 == 0 && issk::epi_is_simple_tr(a)) || (a.pp > 1 && issk::epi_is_pool_relu(a)));
-        if (!no_ws && !no_ws3 && pend < 0 && (x3 || nh2_f32) && a.mode == 0 && (!padded || nh2_pad_ok) && a.sh == 1 && a.sw == 1 && !a.res && a.Cout % (2 * BN) == 0 &&
-            issk::iss_ws_nh2_compiled(a.H_k, a.kw) && a.Cin % F2_CH == 0 && a.M < (1ll << 31) &&
-            (long long)bc * a.img_stride * 4 < (1ll << 32)) {
-            const long long key = ((long long)r << 32) | (1ll << 60);
-            auto it = n.fp_pix.find(key);
-            if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
-            ws_nh2 = it->second <= WS_PIX2;
-        }
-        // plain weight-stationary launch: a padded 3x3 stride-1 layer too wide for the 360-pixel footprint kernel (see conv_ws.h)
-        bool ws_plain = false;
-        if (!no_ws && !fp && pend < 0 && x3 && a.mode == 0 && padded && a.sh == 1 && a.sw == 1 && a.pp == 1 && a.Cout % 4 == 0 &&
-            !a.res && issk::iss_ws_plain_compiled(a.H_k, a.kw) && a.Cin % F2_CH == 0 && a.M < (1ll << 31) &&
-            (long long)bc * a.img_stride * 4 < (1ll << 32)) {
-            const long long key = ((long long)r << 32) | (1ll << 61);
-            auto it = n.fp_pix.find(key);
-            if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
-            ws_plain = it->second <= WS_PIX;
-        }
-        // ... and the UNPADDED 3x3 stride-1 layers the two-column-half form does not take (64 / 96 output channels): they ran on
-        // conv_x3_fp_kernel (weights streamed per tap, 215-312 TF); simple transposed epilogue or pooled relu only (cnn_ws_c.hip)
-        bool ws_plain_u = false;
-        if (!no_ws && !(c->diag & ISS_DIAG_NO_WSU3) && !ws_nh2 && pend < 0 && x3 && a.mode == 0 && !padded && a.sh == 1 && a.sw == 1 && !a.res &&
-            issk::iss_ws_plain_compiled(a.H_k, a.kw) && a.Cin % F2_CH == 0 && a.Cin >= 2 * F2_CH && a.M < (1ll << 31) &&
-            (long long)bc * a.img_stride * 4 < (1ll << 32) &&
-            ((a.pp == 1 && a.Cout % 4 == 0 && issk::epi_is_simple_tr(a)) || (a.pp > 1 && issk::epi_is_pool_relu(a)))) {
-            const long long key = ((long long)r << 32) | (1ll << 56);
-            auto it = n.fp_pix.find(key);
-            if (it == n.fp_pix.end()) it = n.fp_pix.emplace(key, footprint_pixels(a, WS_TM)).first;
-            ws_plain_u = it->second <= WS_PIX;
-        }
-        bool fused = false;
-        if (pend >= 0) {
-            const int32_t* Rp = &n.prog[(size_t)pend * ISS_PROG_COLS];
-            const long long edge_rows = fs1 ? (long long)bc * (Rp[ISS_C_KH] - 1) : 0;                          // per-window edge rows behind R
-            fused = !pool1 && fp && (ws || (!fs1 && !padded && a.H_k * a.kw >= 12)) && d_winrow != nullptr &&
-                    ((long long)(rmax - rmin) + Rp[ISS_C_HO] + edge_rows) * Rp[ISS_C_WO] * Rp[ISS_C_COUT] * 4 < (1ll << 32);   // 32-bit BYTE offsets into R
-            if (ws_ring && !fused) { ws = false; fp = false; ws_ring = false; a.tmr = 0; }                                // (no footprint kernel of that shape)
-            if (ws_f32 && !fused) { ws = false; fp = false; ws_f32 = false; }                                              // (exact-f32 mode has no other one)
-        }
-        if (!fused && (long long)bc * a.img_stride >= (1ll << 32)) fp = false;        // 32-bit offsets into the input batch
-        // no footprint kernel fuses it and none would run this conv anyway: the generic gather kernel reads the shared first-layer
-        // rows itself and applies the window's affine map + activation before its operand split (conv_x3_kernel<3>) -- the per-window
-        // first-layer tensor (283-333 KB per slot) is neither written nor read for ANY second conv on overlapping windows
-        bool gfused = false;
-        if (pend >= 0 && !fused && x3 && a.mode == 0 && d_winrow != nullptr && !(c->diag & ISS_DIAG_NO_GFUSED) && !(fs1 && (c->diag & ISS_DIAG_NO_FSAME))) {
-            const int32_t* Rp = &n.prog[(size_t)pend * ISS_PROG_COLS];
-            gfused = (fs1 || (Rp[ISS_C_PT] == 0 && Rp[ISS_C_PL] == 0)) && Rp[ISS_C_PSOFF] < 0 && Rp[ISS_C_ACT] <= 1 && a.M < (1ll << 31) &&
-                     (!fs1 || n.wsumx_off[pend] >= 0);
-            if (gfused && fp) {
-                // conv_x3_fp_kernel would run this conv (unfused) at ~330 TFLOP/s where the gather kernel does ~230, but needs the
-                // per-window first-layer tensor, written at ~2.1 TB/s (measured: conv1_patch_x3_kernel): the gather kernel wins when
-                // flops * (1/230e12 - 1/330e12) < bytes / 2.1e12, i.e. below ~360 flops per byte of that tensor (narrow nets)
-                const double bytes1 = (double)bc * Rp[ISS_C_HO] * Rp[ISS_C_WO] * Rp[ISS_C_COUT] * 4.0;
-                gfused = fl < 360.0 * bytes1;
-            }
-            if (gfused) fp = false;
-        }
-        if (pend >= 0) {
-            if (!fused && !gfused) {                         // the deferred first layer runs on its own after all
-                const int rc = conv_row(pend, -1, -1, -1);
-                if (rc) return rc;
-            } else {
-                const int32_t* R1 = &n.prog[(size_t)pend * ISS_PROG_COLS];
-                const long long rrows = (long long)(rmax - rmin) + R1[ISS_C_HO];     // R: rows rmin .. rmax + H1 - 1
-                const long long rtot = rrows * R1[ISS_C_WO] * (R1[ISS_C_COUT] / 4);
-                const int f_ne = fs1 ? R1[ISS_C_KH] - 1 : 0;                         // zero-padded first layer: edge rows per window
-                const long long etot = (long long)bc * f_ne * R1[ISS_C_WO] * (R1[ISS_C_COUT] / 4);
-                // pooled planes (ph1 of them) + the transformed window list behind R (see pool_rows_kernel)
-                const int plane_rows = pool1 ? (int)(rrows / ph1) + 2 : 0;
-                const long long ptot = pool1 ? (long long)ph1 * plane_rows * (R1[ISS_C_WO] / pw1) * (R1[ISS_C_COUT] / 4) : 0;
-                { const int rc = iss_reserve(c, c->raw1, (size_t)(rtot + etot + ptot) * 16 + (pool1 ? (size_t)bc * 4 + 16 : 0)); if (rc) return rc; }
-                float* Rraw = (float*)c->raw1.p;
-                iss_prof_begin(c, 2, 0);
-                if (fs1) {
-                    // shared rows (all filter rows, the filter columns that see data) + the per-window edge rows behind them
-                    const int pt1 = R1[ISS_C_PT], pl1 = R1[ISS_C_PL], pb1 = R1[ISS_C_KH] - 1 - pt1;
-                    const float* S = n.d_wsum + n.wsumx_off[pend];
-                    const size_t lds1 = (size_t)R1[ISS_C_KH] * R1[ISS_C_KW] * R1[ISS_C_COUT] * 4;
-                    if (rtot >= (1ll << 31) || etot >= (1ll << 31)) return iss_fail(c, ISS_EINVAL, "internal: shared first layer over %lld + %lld items", rtot, etot);
-                    hipLaunchKernelGGL(first_layer_same_kernel, dim3((unsigned)std::min<long long>((rtot + 255) / 256, 4096)), dim3(256), lds1, c->stream,
-                                       (const float*)c->mspec.p, (int)c->T, rmin, rtot, R1[ISS_C_WO], R1[ISS_C_COUT], R1[ISS_C_KH], R1[ISS_C_KW],
-                                       pt1, pl1, (const float*)(n.d_blob + R1[ISS_C_WOFF]), n.kpad[pend], Rraw);
-                    if (etot > 0)
-                        hipLaunchKernelGGL(first_layer_edge_kernel, dim3((unsigned)std::min<long long>((etot + 255) / 256, 8192)), dim3(256), lds1, c->stream,
-                                           (const float*)c->mspec.p, d_winrow, d_stats, etot, R1[ISS_C_H], R1[ISS_C_WO], R1[ISS_C_COUT], R1[ISS_C_KH],
-                                           R1[ISS_C_KW], pt1, pb1, pl1, (const float*)(n.d_blob + R1[ISS_C_WOFF]), n.kpad[pend], S, Rraw + (size_t)rtot * 4);
-                    a.f_padt = pt1; a.f_padb = pb1; a.f_erow0 = (int)rrows;
-                } else {
-                const dim3 rgrid((unsigned)std::min<long long>((rtot + 255) / 256, 4096));
-                const size_t rlds = (size_t)R1[ISS_C_KH] * R1[ISS_C_KW] * R1[ISS_C_COUT] * 4;
-                const bool no_rows = (c->diag & ISS_DIAG_NO_FLROWS) != 0;             // diagnostic: the per-output kernel
-                // compiled for the two input widths of the reference's nets: 21 bands (smn / sm) -> 17 positions, 24 (gender) -> 20
-                const bool rows_ok = !no_rows && R1[ISS_C_KH] == 4 && R1[ISS_C_KW] == 5 && (R1[ISS_C_WO] == 17 || R1[ISS_C_WO] == 20) &&
-                                     rrows * (R1[ISS_C_COUT] / 4) < (1ll << 31);
-                const dim3 rowgrid((unsigned)std::min<long long>((rrows * (R1[ISS_C_COUT] / 4) + 255) / 256, 4096));
-                if (rows_ok && R1[ISS_C_WO] == 17)
-                    hipLaunchKernelGGL((first_layer_rows_kernel<4, 5, 17>), rowgrid, dim3(256), rlds, c->stream, (const float*)c->mspec.p, rmin, (int)rrows,
-                                       R1[ISS_C_COUT], (const float*)(n.d_blob + R1[ISS_C_WOFF]), n.kpad[pend], Rraw);
-                else if (rows_ok)
-                    hipLaunchKernelGGL((first_layer_rows_kernel<4, 5, 20>), rowgrid, dim3(256), rlds, c->stream, (const float*)c->mspec.p, rmin, (int)rrows,
-                                       R1[ISS_C_COUT], (const float*)(n.d_blob + R1[ISS_C_WOFF]), n.kpad[pend], Rraw);
-                else if (R1[ISS_C_KH] == 4 && R1[ISS_C_KW] == 5)
-                    hipLaunchKernelGGL((first_layer_raw_kernel<4, 5>), rgrid, dim3(256), rlds, c->stream, (const float*)c->mspec.p, rmin, rtot,
-                                       R1[ISS_C_WO], R1[ISS_C_COUT], 4, 5, (const float*)(n.d_blob + R1[ISS_C_WOFF]), n.kpad[pend], Rraw);
-                else
-                    hipLaunchKernelGGL((first_layer_raw_kernel<0, 0>), rgrid, dim3(256), rlds, c->stream, (const float*)c->mspec.p, rmin, rtot,
-                                       R1[ISS_C_WO], R1[ISS_C_COUT], R1[ISS_C_KH], R1[ISS_C_KW],
-                                       (const float*)(n.d_blob + R1[ISS_C_WOFF]), n.kpad[pend], Rraw);
-                }
-                a.in = Rraw; a.win_row = d_winrow; a.f_rmin = rmin;
-                if (pool1) {
-                    if (ptot >= (1ll << 40)) return iss_fail(c, ISS_EINVAL, "internal: pooled first layer over %lld items", ptot);
-                    float* P = Rraw + (size_t)(rtot + etot) * 4;
-                    int32_t* wr2 = reinterpret_cast<int32_t*>(P + (size_t)ptot * 4);
-                    hipLaunchKernelGGL(pool_rows_kernel, dim3((unsigned)std::min<long long>((ptot + 255) / 256, 8192)), dim3(256), 0, c->stream,
-                                       (const float*)Rraw, P, ptot, (int)rrows, R1[ISS_C_WO], R1[ISS_C_COUT], ph1, pw1, plane_rows);
-                    hipLaunchKernelGGL(winrow_pool_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, c->stream, d_winrow, wr2, bc, rmin, ph1, plane_rows);
-                    a.in = P; a.win_row = wr2; a.f_rmin = 0;
-                }
-                iss_prof_end(c);
-                a.stats = d_stats; a.finite = d_fin;
-                a.f_bias = n.d_blob + R1[ISS_C_BOFF];
-                a.f_wsum = fs1 ? n.d_wsum + n.wsumx_off[pend] : n.d_wsum + n.wsum_off[pend];
-                a.f_ps = R1[ISS_C_PSOFF] >= 0 ? n.d_blob + R1[ISS_C_PSOFF] : nullptr;
-                a.f_pt = R1[ISS_C_PTOFF] >= 0 ? n.d_blob + R1[ISS_C_PTOFF] : nullptr;
-                a.f_act = R1[ISS_C_ACT];
-                fl += 2.0 * R1[ISS_C_KH] * R1[ISS_C_KW] * (double)R1[ISS_C_COUT] * (double)bc * R1[ISS_C_HO] * R1[ISS_C_WO];
-            }
-        }
-        ws = ws && fused;
-        if (gfused) a.mode = fs1 ? 4 : 3;
-        // CHL output through the shared pooled epilogue (conv_common.h epilogue_impl / chl_store): every kernel family that ends in it --
-        // the weight-stationary forms, conv_x3_fp_kernel, the generic gather kernel -- can hand its pooled relu output to a
-        // conv_x3_wq3h_kernel the way conv_x3_wq_kernel does (the two launch sites with an epilogue of their own take it back below)
-        if (x3 && !patch && issk::epi_is_pool_relu(a) && a.Cout % 16 == 0 && want_hl_out(r, a.M / a.pp)) {
-            a.out_hl = 1; a.out_np = issk::chl_npad(a.M / a.pp); a.out_f16 = f16mode ? 1 : 0;
-            hl_out_row = r; hl_out_np = a.out_np; hl_out_f16 = f16mode;
-        }
-        auto no_chl_out = [&]() { a.out_hl = 0; a.out_np = 0; a.out_f16 = 0; if (hl_out_row == r) hl_out_row = -1; hl_out_f16 = false; hl_out_dense = false; };
-        iss_prof_begin(c, 0, fl);
-        iss_prof_tag(c, ws || ws_plain || ws_plain_u || ws_nh2 ? ISS_PROF_WS : fp ? ISS_PROF_FP : !x3 ? ISS_PROF_F32 : ISS_PROF_GATHER);
-        iss_prof_row(c, r);
-        // one-channel 3x3 'same' first layer of a non-PATCH network: direct f32 kernel (either arithmetic mode)
-        const bool no_direct = (c->diag & ISS_DIAG_NO_DIRECT1) != 0;
-        const bool direct1 = !no_direct && !patch && pend < 0 && a.Cin == 1 && a.H_k == 3 && a.kw == 3 && a.sh == 1 && a.sw == 1 && a.pt_ == 1 &&
-                             a.pl_ == 1 && R[ISS_C_HO] == a.H && R[ISS_C_WO] == a.W && a.pp == 1 && !a.res && !a.ps && a.act <= 1 && a.bias &&
-                             a.Cout % 4 == 0 && a.Cout <= 256 && a.M * (long long)(a.Cout / 4) < (1ll << 34);
-        if (direct1) {
-            iss_prof_tag(c, ISS_PROF_GATHER);
-            iss_prof_inst(c, "conv1_direct3x3_kernel<%s>", window ? "true" : "false");
-            const long long items = (long long)(a.M / ((long long)a.H * a.W)) * ((a.H + 7) / 8) * a.W * (a.Cout / 4);
-            if (items >= (1ll << 32)) return iss_fail(c, ISS_EINVAL, "internal: direct first layer over %lld work items", items);
-            const dim3 dgrid((unsigned)std::min<long long>((items + 255) / 256, 8192));
-            const size_t dlds = (size_t)9 * a.Cout * sizeof(float);
-            if (window) hipLaunchKernelGGL(conv1_direct3x3_kernel<true>, dgrid, dim3(256), dlds, c->stream, a);
-            else hipLaunchKernelGGL(conv1_direct3x3_kernel<false>, dgrid, dim3(256), dlds, c->stream, a);
-        } else
-        if (ws_nh2 && !x3) {
-            const unsigned ngroups = (unsigned)((a.M + WS_TM - 1) / WS_TM);
-            const unsigned ny = (unsigned)(a.Cout / (2 * BN));
-            const dim3 g2(std::min<unsigned>(ngroups, std::max(1u, 256u / ny)), ny);
-            const bool trn = a.pp == 1;
-            iss_prof_inst(c, "conv_x3_ws_kernel<3,3,false,%s,false,2,1,f32>", trn ? "true" : "false");
-            issk::iss_ws_launch_f32_nh2_3x3(a, g2, c->stream, trn);
-        } else
-        if (ws_nh2) {
-            const unsigned ngroups = (unsigned)((a.M + WS_TM - 1) / WS_TM);         // one 512-row tile per group
-            const unsigned ny = (unsigned)(a.Cout / (2 * BN));
-            const dim3 g2(std::min<unsigned>(ngroups, std::max(1u, 256u / ny)), ny);
-            {   // template arguments as iss_ws_launch_nh2_3x3* pick them: <KH,KW,PADDED,TR,FUSED,NH,EPI>
-                const bool trn = (padded && !nh2_pad_pool) || (a.pp == 1 && a.Cout % 4 == 0);
-                const int epi = padded ? 1 : (trn ? issk::epi_is_simple_tr(a) : issk::epi_is_pool_relu(a));
-                iss_prof_inst(c, "conv_x3_ws_kernel<%d,%d,%s,%s,false,2,%d>", a.H_k, a.kw, padded ? "true" : "false", trn ? "true" : "false", epi);
-            }
-            // one-wave-per-SIMD variant (conv_wq3.h): unpadded, bias + relu (kind 0) or relu + 2 x 1 max-pool (kind 1)
-            int wq3_kind = -1;
-            if (!(c->diag & ISS_DIAG_NO_WQ) && !padded && a.bias && a.act == 1 && !a.ps && !a.res && a.Cin >= 2 * F2_CH &&
-                ws_recip_exact(a.W, issk::WQ3_PIX + a.W)) {
-                if (a.pp == 1 && a.M * (long long)a.Cout * 4 < 0xFFF00000ll) wq3_kind = 0;
-                else if (a.pp == 2 && a.ph == 2 && a.poolkind == 0 && (a.M / 2) * (long long)a.Cout * 4 < 0xFFF00000ll) wq3_kind = 1;
-            }
-            if (wq3_kind >= 0) {
-                const long long key = ((long long)r << 32) | (1ll << 58);
-                auto it = n.fp_pix.find(key);
-                if (it == n.fp_pix.end()) {
-                    int tmr = 0;
-                    for (int cand = issk::WQ3_TM; cand >= issk::WQ3_TM - 64 && !tmr; cand -= 4)
-                        if (footprint_pixels(a, cand) <= issk::WQ3_PIX) tmr = cand;
-                    it = n.fp_pix.emplace(key, tmr).first;
-                }
-                a.tmr = it->second;
-                if (a.tmr <= 0) wq3_kind = -1;
-            }
-            if (wq3_kind >= 0) {
-                const unsigned qtiles = (unsigned)((a.M + a.tmr - 1) / a.tmr);
-                const dim3 qgrid(std::min<unsigned>((qtiles + 1) / 2, std::max(1u, 256u / ny)), ny);
-                no_chl_out();                                    // (these kernels have epilogues of their own: kind 0 decides below, kind 1 writes f32)
-                if (in_is_hl) {                                  // the producer wrote the CHL layout for this launch (want_hl_out)
-                    a.in_hl = 1; a.in_np = hl_np[R[ISS_C_IN]];
-                    if (hl_f16.count(R[ISS_C_IN])) { a.f16 = 1; a.wh = n.d_wh16 + R[ISS_C_WOFF]; a.wl = n.d_wl16 + R[ISS_C_WOFF]; }
-                    if (wq3_kind == 0 && want_hl_out(r, a.M)) { a.out_hl = 1; a.out_np = issk::chl_npad(a.M); hl_out_row = r; hl_out_np = a.out_np; }
-                    if (wq3_kind == 1 && want_dhl_out(r, a.Hq, a.Wq)) { a.out_hl = 1; a.out_np = issk::dhl_npad(bc); hl_out_row = r; hl_out_np = a.out_np; hl_out_dense = true; }
-                    if (a.out_hl && a.f16) hl_out_f16 = true;
-                    iss_prof_inst(c, "conv_x3_wq3h_kernel<%d,%s,%s>", wq3_kind, a.out_hl ? "true" : "false", a.f16 ? "true" : "false");     // <KIND,OUT_HL,F16>
-                    issk::iss_wq3h_launch(a, qgrid, c->stream, wq3_kind);
-                    in_hl_taken = true;
-                } else {
-                iss_prof_inst(c, "conv_x3_wq3_kernel<%d>", wq3_kind);
-                issk::iss_wq3_launch(a, qgrid, c->stream, wq3_kind);
-                }
-            } else
-            if (padded && nh2_pad_pool) issk::iss_ws_launch_nh2_3x3_padded_pool(a, g2, c->stream);
-            else if (padded) issk::iss_ws_launch_nh2_3x3_padded(a, g2, c->stream);
-            else issk::iss_ws_launch_nh2_3x3(a, g2, c->stream, a.pp == 1 && a.Cout % 4 == 0);
-        } else if (ws_plain_u) {
-            const unsigned ngroups = (unsigned)((a.M + (long long)WS_TM * WS_G - 1) / ((long long)WS_TM * WS_G));
-            const unsigned per_n = std::max(1u, 256u / grid.y);
-            const bool tru = a.pp == 1;
-            iss_prof_inst(c, "conv_x3_ws_kernel<3,3,false,%s,false,1,1,plain>", tru ? "true" : "false");
-            issk::iss_ws_launch_plain_3x3_unpadded(a, dim3(std::min<unsigned>(ngroups, per_n), grid.y), c->stream, tru);
-        } else if (ws_plain) {
-            const unsigned ngroups = (unsigned)((a.M + (long long)WS_TM * WS_G - 1) / ((long long)WS_TM * WS_G));
-            const unsigned per_n = std::max(1u, 256u / grid.y);                   // one 512-thread workgroup per CU in total
-            iss_prof_inst(c, "conv_x3_ws_kernel<3,3,true,true,false,1,%d>", (int)issk::epi_is_simple_tr(a));
-            issk::iss_ws_launch_plain_3x3(a, dim3(std::min<unsigned>(ngroups, per_n), grid.y), c->stream);
-        } else if (ws && ws_f32) {
-            const unsigned ngroups = (unsigned)((a.M + (long long)WS_TM * WS_G - 1) / ((long long)WS_TM * WS_G));
-            const dim3 wgrid(std::min<unsigned>(ngroups, 256u), grid.y);
-            iss_prof_inst(c, "conv_x3_ws_kernel<5,3,false,false,true,1,1,f32>");
-            issk::iss_ws_launch_f32_fused_5x3(a, wgrid, c->stream);
-        } else if (ws && ws_ring) {
-            const unsigned ngroups = (unsigned)((a.M + a.tmr - 1) / a.tmr);      // one tile of tmr rows per group
-            const dim3 wgrid(std::min<unsigned>(ngroups, 256u), grid.y);
-            iss_prof_inst(c, "conv_x3_ws_kernel<%d,%d,%s,false,true,1,%d,ring>", a.H_k, a.kw, padded ? "true" : "false", (int)issk::epi_is_pool_relu_any(a));
-            issk::iss_ws_launch_ring(a, wgrid, c->stream, padded);
-        } else if (ws && ws_fs) {
-            const unsigned ngroups = (unsigned)((a.M + (long long)WS_TM - 1) / (long long)WS_TM);      // FS: one tile per group (conv_ws.h G)
-            const dim3 wgrid(std::min<unsigned>(ngroups, 256u), grid.y);
-            iss_prof_inst(c, "conv_x3_ws_kernel<%d,%d,%s,%s,true,1,%d,fs>", a.H_k, a.kw, padded ? "true" : "false", fs_tr_ok ? "true" : "false",
-                          fs_tr_ok ? 1 : (int)issk::epi_is_pool_relu_any(a));
-            if (fs_tr_ok) issk::iss_ws_launch_fs_5x3_tr(a, wgrid, c->stream);
-            else if (a.H_k == 5) issk::iss_ws_launch_fs_5x3(a, wgrid, c->stream, padded);
-            else issk::iss_ws_launch_fs_3x3(a, wgrid, c->stream, padded);
-        } else if (ws) {
-            const unsigned ngroups = (unsigned)((a.M + (long long)WS_TM * WS_G - 1) / ((long long)WS_TM * WS_G));
-            const dim3 wgrid(std::min<unsigned>(ngroups, 256u), grid.y);         // persistent: one 512-thread workgroup per CU
-            const bool tr = a.pp == 1 && a.Cout % 4 == 0;
-            // <= 32 output channels: one 32-column block per workgroup (conv_ws.h NCB = 1) instead of half-empty 64-column ones
-            const bool ncb1 = !(c->diag & ISS_DIAG_NO_NCB1) && fused && !fs1 && !padded && !tr && a.Cout <= 32 && issk::epi_is_pool_relu(a) &&
-                              issk::iss_ws_ncb1_compiled(a.H_k, a.kw) && a.sh == 1 && a.sw == 1 && a.Cin >= 2 * F2_CH;
-            if (ncb1) {
-                iss_prof_inst(c, "conv_x3_ws_kernel<%d,%d,false,false,true,1,1,ncb1>", a.H_k, a.kw);
-                issk::iss_ws_launch_ncb1_5x3(a, wgrid, c->stream);
-            } else {
-            // one-wave-per-SIMD, two-footprint variant (conv_wq.h): the dominant launch of the segmenter nets
-            bool wq = false;
-            if (!(c->diag & ISS_DIAG_NO_WQ) && fused && !padded && !tr && issk::epi_is_pool_relu(a) && a.pp == 4 && a.ph == 2 &&
-                issk::iss_wq_compiled(a.H_k, a.kw) && a.sh == 1 && a.sw == 1 && a.Cin >= 2 * F2_CH && a.M % 4 == 0 &&
-                (a.M / 4) * (long long)a.Cout * 4 < 0xFFF00000ll && a.Cout <= 256) {
-                // rows per tile: the largest multiple of 4 (<= 512) whose footprint fits the kernel's 800 pixels
-                const long long key = ((long long)r << 32) | (1ll << 59);
-                auto it = n.fp_pix.find(key);
-                if (it == n.fp_pix.end()) {
-                    int tmr = 0;
-                    for (int cand = WS_TM; cand >= WS_TM - 32 && !tmr; cand -= 4)
-                        if (footprint_pixels(a, cand) <= issk::WQ_PIX) tmr = cand;
-                    it = n.fp_pix.emplace(key, tmr).first;
-                }
-                a.tmr = it->second;
-                wq = a.tmr > 0;
-            }
-            if (wq) {
-                const unsigned qtiles = (unsigned)((a.M + a.tmr - 1) / a.tmr);
-                const dim3 qgrid(std::min<unsigned>((qtiles + 1) / 2, 256u), grid.y);     // persistent: one 256-thread workgroup per CU
-                no_chl_out();                                    // (its own CHL epilogue; the halves follow the launch's operand type)
-                if (a.Cout % BN == 0 && want_hl_out(r, a.M / 4)) { a.out_hl = 1; a.out_np = issk::chl_npad(a.M / 4); hl_out_row = r; hl_out_np = a.out_np; }
-                if (row_f16) { a.f16 = 1; a.wh = n.d_wh16 + R[ISS_C_WOFF]; a.wl = n.d_wl16 + R[ISS_C_WOFF]; if (a.out_hl) hl_out_f16 = true; }
-                iss_prof_inst(c, "conv_x3_wq_kernel<%d,%d,%s,%s>", a.H_k, a.kw, a.out_hl ? "true" : "false", a.f16 ? "true" : "false");   // <KH,KW,OUT_HL,F16>
-                issk::iss_wq_launch_5x3(a, qgrid, c->stream);
-            } else {
-            {
-                const int epi = tr ? issk::epi_is_simple_tr(a) : issk::epi_is_pool_relu_any(a);
-                iss_prof_inst(c, "conv_x3_ws_kernel<%d,%d,%s,%s,true,1,%d>", a.H_k, a.kw, padded ? "true" : "false", tr ? "true" : "false", epi);
-            }
-#define ISS_WS_CASE(KH_, KW_) if (a.H_k == KH_ && a.kw == KW_) iss_ws_launch_##KH_##x##KW_(a, wgrid, c->stream, padded, tr, fused); else
-            ISS_WS_SHAPES(ISS_WS_CASE) { return iss_fail(c, ISS_EINVAL, "internal: no weight-stationary kernel for %dx%d", a.H_k, a.kw); }
-#undef ISS_WS_CASE
-            }
-            }
-        } else if (fp) {
-#define ISS_FP_CASE(KH_, KW_) if (a.H_k == KH_ && a.kw == KW_) iss_fp_launch_##KH_##x##KW_(a, pgrid, c->stream, padded, tr, fused, nh); else
-            // 128 output channels per workgroup where the layer has them: one LDS footprint serves two 64-column halves
-            const bool no_nh2 = (c->diag & ISS_DIAG_NO_NH2) != 0;
-            const int nh = (!fused && !no_nh2 && issk::iss_fp_has_nh2(a.H_k, a.kw) && a.Cout % (2 * BN) == 0) ? 2 : 1;
-            const dim3 pgrid(std::min<unsigned>(a.nblk, 512u), grid.y / nh);     // persistent: 2 workgroups per CU
-            const bool no_tr = (c->diag & ISS_DIAG_NO_TR) != 0;             // diagnostic: row-major epilogue everywhere
-            const bool tr = !no_tr && a.pp == 1 && a.Cout % 4 == 0;         // float4 epilogue on transposed accumulators
-            if (fused && a.H_k * a.kw >= 12) iss_prof_inst(c, "conv_x3_fp_kernel<%d,%d,false,%s,true,1>", a.H_k, a.kw, tr ? "true" : "false");
-            else iss_prof_inst(c, "conv_x3_fp_kernel<%d,%d,%s,%s,false,%d>", a.H_k, a.kw, padded ? "true" : "false", tr ? "true" : "false", nh);
-            ISS_FP_SHAPES(ISS_FP_CASE) { return iss_fail(c, ISS_EINVAL, "internal: no footprint kernel for %dx%d", a.H_k, a.kw); }
-#undef ISS_FP_CASE
-        } else if (x3 && patch && a.H_k * a.kw <= XBK && a.M < (1ll << 31)) {
-            const dim3 pgrid(std::min<unsigned>(a.nblk, 512u), grid.y);     // persistent, no barriers: 2 workgroups per CU
-            iss_prof_tag(c, ISS_PROF_PATCH1);
-            const bool ptr = a.pp == 1 && a.Cout % 4 == 0 && !a.res;
-            // fp16 mode: fp16 halves of the normalised window and of the weights here too (|z| <= sqrt(68 * 24), far inside fp16's range)
-            if (row_f16) { a.f16 = 1; a.wh = n.d_wh16 + R[ISS_C_WOFF]; a.wl = n.d_wl16 + R[ISS_C_WOFF]; }
-            iss_prof_inst(c, "conv1_patch_x3_kernel<%s,%s>", ptr ? "true" : "false", a.f16 ? "true" : "false");   // <TR,F16>
-            // blob offsets are multiples of 8 floats, so the float4 loads of bias / scale / shift are aligned
-            if (ptr && a.f16) hipLaunchKernelGGL((conv1_patch_x3_kernel<true, true>), pgrid, dim3(256), 0, c->stream, a);
-            else if (ptr) hipLaunchKernelGGL((conv1_patch_x3_kernel<true, false>), pgrid, dim3(256), 0, c->stream, a);
-            else if (a.f16) hipLaunchKernelGGL((conv1_patch_x3_kernel<false, true>), pgrid, dim3(256), 0, c->stream, a);
-            else hipLaunchKernelGGL((conv1_patch_x3_kernel<false, false>), pgrid, dim3(256), 0, c->stream, a);
-        } else if (x3) {
-            const bool tr = a.pp == 1 && a.Cout % 4 == 0;     // float4 epilogue on transposed accumulators
-            // wider N tiles for wide layers (A staged once per 128 / 256 output channels); 1-D XCD-aware grid
-            // NTN = 4 (128 x 128 tiles) is compiled but not selected: with the XCD-aware order the A tile is re-read from
-            // L2, not from HBM, and the wider tiles (fewer, fatter workgroups) measured 6 % SLOWER on ResNet-101
-            const int ntn = 2;
-            a.nblk_n = (unsigned)((a.Cout + 32 * ntn - 1) / (32 * ntn));
-            const dim3 gridw(a.nblk * a.nblk_n);
-            const bool no_pw = (c->diag & ISS_DIAG_NO_PW) != 0;
-            if (gfused) {
-                iss_prof_inst(c, "conv_x3_kernel<%d,%s,2>", a.mode, tr ? "true" : "false");
-                if (a.mode == 4 && tr) hipLaunchKernelGGL((conv_x3_kernel<4, true, 2>), gridw, dim3(256), 0, c->stream, a);
-                else if (a.mode == 4) hipLaunchKernelGGL((conv_x3_kernel<4, false, 2>), gridw, dim3(256), 0, c->stream, a);
-                else if (tr) hipLaunchKernelGGL((conv_x3_kernel<3, true, 2>), gridw, dim3(256), 0, c->stream, a);
-                else hipLaunchKernelGGL((conv_x3_kernel<3, false, 2>), gridw, dim3(256), 0, c->stream, a);
-                iss_prof_end(c);
-                return ISS_OK;
-            }
-            const bool pointwise = !no_pw && a.mode == 0 && tr && a.H_k == 1 && a.kw == 1 && a.sh == 1 && a.sw == 1 && a.pt_ == 0 &&
-                                   a.pl_ == 0 && R[ISS_C_HO] == a.H && R[ISS_C_WO] == a.W && a.Kpad == a.Cin;
-            if (pointwise) iss_prof_tag(c, ISS_PROF_PW);
-            // Streaming pointwise kernels (conv_pw.h) for K <= 2048.  The segmenter nets' first dense layer (K = 4992 / 8320,
-            // 192 columns, ~28 k rows per launch) keeps conv_x3_pw_kernel: it runs at 1.7 TB/s of activations on every tiling
-            // that was built for it (deeper ring -8 %; one workgroup per 64 rows x all 192 columns +6 %, with split-K +3..+11 %,
-            // with non-temporal activation loads +8 %: profiles/HISTORY.md, round 3)
-#ifdef ISS_PW_NO_ASM_RING                        // build-time escape when tools/check_ring_regs.py rejects this compiler's cnn_pw.o (Makefile)
-            const bool no_pws = true;
-#else
-            const bool no_pws = (c->diag & ISS_DIAG_NO_PWS) != 0;                // diagnostic: the round-2 pointwise kernel everywhere
-#endif
-            const bool no_pws2 = (c->diag & ISS_DIAG_NO_PWS2) != 0;              // diagnostic: 64-column tiles everywhere
-            const bool pws_ok = !no_pws && a.Kpad <= 2048 && !f16_dense_pw;        // (fp16 mode: a dense layer that would otherwise run in exact f32)
-            // strided 1x1 (the shortcut projections): the 128-column kernel on a strided pixel list
-            const bool pw_strided = pws_ok && !no_pws2 && a.mode == 0 && tr && a.H_k == 1 && a.kw == 1 && (a.sh > 1 || a.sw > 1) && a.pt_ == 0 &&
-                                    a.pl_ == 0 && a.Kpad == a.Cin && issk::pws2_strided_supported(a, R[ISS_C_HO], R[ISS_C_WO]);
-            const bool simple_pw = a.act <= 1 && !a.ps;
-            if (pw_strided) { iss_prof_tag(c, ISS_PROF_PW); iss_prof_inst(c, "conv_x3_pws2_kernel<true,true>"); issk::iss_pws2_launch(a, c->stream, true); }
-            else if (pointwise && pws_ok && !no_pws2 && issk::pws2_supported(a)) {
-                iss_prof_inst(c, "conv_x3_pws2_kernel<%s,false>", simple_pw ? "true" : "false");
-                issk::iss_pws2_launch(a, c->stream);
-            } else if (pointwise && pws_ok && issk::pws_supported(a)) {
-                iss_prof_inst(c, "conv_x3_pws_kernel<%s,%s>", a.res ? "true" : "false", simple_pw ? "true" : "false");
-                issk::iss_pws_launch(a, dim3(std::min<unsigned>(a.nblk * a.nblk_n, 512u)), c->stream);
-            } else if (pointwise) {
-                if (row_f16) {
-                    a.f16 = 1; a.wh = n.d_wh16 + R[ISS_C_WOFF]; a.wl = n.d_wl16 + R[ISS_C_WOFF];
-                    iss_prof_inst(c, "conv_x3_pw_kernel<true>");                                  // <F16>
-                    hipLaunchKernelGGL(conv_x3_pw_kernel<true>, dim3(std::min<unsigned>(a.nblk * a.nblk_n, 768u)), dim3(256), 0, c->stream, a);
-                } else {
-                iss_prof_inst(c, "conv_x3_pw_kernel<false>");
-                hipLaunchKernelGGL(conv_x3_pw_kernel<false>, dim3(std::min<unsigned>(a.nblk * a.nblk_n, 768u)), dim3(256), 0, c->stream, a);
-                }
-            } else {
-            iss_prof_inst(c, "conv_x3_kernel<%d,%s,2>", a.mode, (a.mode != 2 && tr) ? "true" : "false");
-            if (ntn == 4) hipLaunchKernelGGL((conv_x3_kernel<0, true, 4>), gridw, dim3(256), 0, c->stream, a);
-            else if (a.mode == 0 && tr) hipLaunchKernelGGL((conv_x3_kernel<0, true, 2>), gridw, dim3(256), 0, c->stream, a);
-            else if (a.mode == 0) hipLaunchKernelGGL((conv_x3_kernel<0, false, 2>), gridw, dim3(256), 0, c->stream, a);
-            else if (a.mode == 1 && tr) hipLaunchKernelGGL((conv_x3_kernel<1, true, 2>), gridw, dim3(256), 0, c->stream, a);
-            else if (a.mode == 1) hipLaunchKernelGGL((conv_x3_kernel<1, false, 2>), gridw, dim3(256), 0, c->stream, a);
-            else hipLaunchKernelGGL((conv_x3_kernel<2, false, 2>), gridw, dim3(256), 0, c->stream, a);
-            }
-        } else {
-            iss_prof_inst(c, "conv_igemm_kernel<%d>", a.mode);
-            if (a.mode == 0) hipLaunchKernelGGL(conv_igemm_kernel<0>, grid1, dim3(256), 0, c->stream, a);
-            else if (a.mode == 1) hipLaunchKernelGGL(conv_igemm_kernel<1>, grid1, dim3(256), 0, c->stream, a);
-            else hipLaunchKernelGGL(conv_igemm_kernel<2>, grid1, dim3(256), 0, c->stream, a);
-        }
-        iss_prof_end(c);
-        if (in_is_hl && !in_hl_taken) return iss_fail(c, ISS_EINVAL, "internal: row %d reads a CHL tensor on a kernel that expects f32", r);
-        return ISS_OK;
-    };
+    const PassIo io{d_winrow, d_stats, d_fin, d_input};
+    // ---- CHL hand-over between footprint kernels (conv_common.h, round 6): per activation buffer, whether the tensor in it is in
+    // the CHL layout.  A producer writes CHL only when the NEXT row is the tensor's only reader and runs on conv_x3_wq3h_kernel
+    // (want_hl_out / want_dhl_out, conv_select.h).  effective_precision: one network may run another mode (precision guard)
+    std::vector<ChlState> layout(std::max<size_t>(c->act.size(), (size_t)n.nbuf));
+    ConvEnv env = make_env(n, bc, rmin, rmax, share_first, effective_precision(c, n), c->diag, d_winrow != nullptr, d_input != nullptr,
+                           c->vbx_out.p != nullptr, layout.data());
     int pending = -1;                                            // deferred PATCH first layer (see can_defer)
     for (int r = 0; r < n.nrows; ++r) {
         const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
         const float* in = R[ISS_C_IN] == ISS_BUF_INPUT ? d_input : (const float*)c->act[R[ISS_C_IN]].p;
         float* out = (float*)c->act[R[ISS_C_OUT]].p;
         const int op = R[ISS_C_OP];
+        ChlState out_layout;                                     // of this row's output: f32 unless a conv launch says otherwise
         if (op == ISS_OP_CONV) {
-            if (pending < 0 && can_defer(r)) { pending = r; *result = out; continue; }
-            // identity-residual expansion followed by the next block's reduction: one chained launch (conv_pwc.h)
-            if (asm_ring_ok && pending < 0 && x3mode && chain_pair(r) &&
-                !(c->diag & (ISS_DIAG_NO_CHAIN | ISS_DIAG_NO_PW | ISS_DIAG_NO_PWS | ISS_DIAG_NO_PWS2))) {
-                const int rc2 = conv_row(r, -1, -1, r + 1);
-                if (rc2 == ISS_OK) {
-                    ISS_HIP(c, hipGetLastError());
-                    hl_np.erase(R[ISS_C_OUT]);
-                    ++r;
-                    hl_np.erase(n.prog[(size_t)r * ISS_PROG_COLS + ISS_C_OUT]);
-                    *result = (float*)c->act[n.prog[(size_t)r * ISS_PROG_COLS + ISS_C_OUT]].p;
-                    continue;
-                }
-                if (rc2 != kDualDeclined) return rc2;
-            }
-            // projection shortcut followed by its expansion (ISS_C_DUALW on the next row): one two-source launch when the split-bf16
-            // streaming kernels are in use (the diagnostic switches that move 1x1 layers elsewhere keep their meaning)
-            if (asm_ring_ok && pending < 0 && x3mode && r + 1 < n.nrows && n.prog[(size_t)(r + 1) * ISS_PROG_COLS + ISS_C_DUALW] > 0 &&
-                !(c->diag & (ISS_DIAG_NO_DUAL | ISS_DIAG_NO_PW | ISS_DIAG_NO_PWS | ISS_DIAG_NO_PWS2))) {
-                const int rc2 = conv_row(r + 1, -1, r, -1);
-                if (rc2 == ISS_OK) {
-                    ISS_HIP(c, hipGetLastError());
-                    hl_np.erase(R[ISS_C_OUT]);
-                    ++r;
-                    hl_np.erase(n.prog[(size_t)r * ISS_PROG_COLS + ISS_C_OUT]);
-                    *result = (float*)c->act[n.prog[(size_t)r * ISS_PROG_COLS + ISS_C_OUT]].p;
-                    continue;
-                }
-                if (rc2 != kDualDeclined) return rc2;
-            }
-            const int rc = conv_row(r, pending, -1, -1);
-            if (pending >= 0) hl_np.erase(n.prog[(size_t)pending * ISS_PROG_COLS + ISS_C_OUT]);
+            if (pending < 0 && can_defer(env, r)) { pending = r; *result = out; continue; }
+            const ConvChoice ch = select_conv(env, r, pending);
+            int rc = ISS_OK;
+            if (ch.first == FirstLayer::Alone) rc = run_conv(c, n, env, io, select_row(env, pending, -1, -1, -1), -1);   // (nothing fuses it after all)
+            if (!rc) rc = run_conv(c, n, env, io, ch, pending);
+            if (pending >= 0) layout[n.prog[(size_t)pending * ISS_PROG_COLS + ISS_C_OUT]] = ChlState{};
             pending = -1;
             if (rc) return rc;
+            if (ch.rows == 1 && env.layout_of(R[ISS_C_IN]).np && !ch.in_np)
+                return iss_fail(c, ISS_EINVAL, "internal: row %d reads a CHL tensor on a kernel that expects f32", r);
+            if (ch.rows == 2) {                                  // the chained pair / the two-source launch: rows r and r + 1 are done
+                layout[R[ISS_C_OUT]] = ChlState{};
+                R = &n.prog[(size_t)++r * ISS_PROG_COLS];
+                out = (float*)c->act[R[ISS_C_OUT]].p;
+            }
+            if (ch.out != OutLayout::F32) out_layout = ChlState{ch.out_np, ch.out_f16, ch.out == OutLayout::ChlDense};
         } else if (op == ISS_OP_POOL) {
             const long long total = (long long)bc * R[ISS_C_HO] * R[ISS_C_WO] * R[ISS_C_CIN];
             iss_prof_begin(c, 2, 0);
@@ -2321,7 +1736,7 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
             const bool chan = k == ISS_ELT_COPY || k == ISS_ELT_ZERO;
             const long long total = (long long)bc * hw * (chan ? R[ISS_C_KH] : R[ISS_C_CIN]);
             const float* res = R[ISS_C_RES] >= 0 ? (const float*)c->act[R[ISS_C_RES]].p : nullptr;
-            if (res && hl_np.count(R[ISS_C_RES])) return iss_fail(c, ISS_EINVAL, "internal: row %d reads a CHL tensor", r);
+            if (res && layout[R[ISS_C_RES]].np) return iss_fail(c, ISS_EINVAL, "internal: row %d reads a CHL tensor", r);
             int st[3] = {0, 0, 0};
             if (k == ISS_ELT_PERMUTE) {
                 const int sin[3] = {R[ISS_C_W] * R[ISS_C_CIN], R[ISS_C_CIN], 1};
@@ -2341,13 +1756,8 @@ int run_program(iss_ctx* c, IssNet& n, int bc, const int32_t* d_winrow, const fl
         }
         ISS_HIP(c, hipGetLastError());
         *result = out;
-        if (hl_out_row == r) {
-            hl_np[R[ISS_C_OUT]] = hl_out_np;
-            if (hl_out_f16) hl_f16[R[ISS_C_OUT]] = true; else hl_f16.erase(R[ISS_C_OUT]);
-            if (hl_out_dense) hl_dense[R[ISS_C_OUT]] = true; else hl_dense.erase(R[ISS_C_OUT]);
-        } else { hl_np.erase(R[ISS_C_OUT]); hl_f16.erase(R[ISS_C_OUT]); hl_dense.erase(R[ISS_C_OUT]); }
-        hl_out_f16 = false; hl_out_dense = false;
-        if (op != ISS_OP_CONV && R[ISS_C_IN] != ISS_BUF_INPUT && hl_np.count(R[ISS_C_IN]))
+        layout[R[ISS_C_OUT]] = out_layout;
+        if (op != ISS_OP_CONV && R[ISS_C_IN] != ISS_BUF_INPUT && layout[R[ISS_C_IN]].np)
             return iss_fail(c, ISS_EINVAL, "internal: row %d reads a CHL tensor", r);
     }
     return ISS_OK;

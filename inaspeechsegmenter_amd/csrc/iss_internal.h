@@ -1,6 +1,7 @@
 // Internal state of libiss_hip.so (not part of the ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstdarg>
@@ -49,7 +50,10 @@ struct IssNet {
     std::vector<int64_t> buf_elems;
     int in_h = 0, in_w = 0, in_c = 0, out_dim = 0;
     double flops_per_sample = 0;
-    std::unordered_map<long long, int> fp_pix;   // (row << 32 | kernel family bit) -> largest LDS footprint of a tile (or its rows)
+    // footprint cache (conv_select.h tile_span / tile_rows): (row, TM, 0, 0) -> largest pixel span of a TM-row tile of that row;
+    // (row, hi, lo, cap) -> the tallest tile in [lo, hi] spanning at most cap pixels.  Keyed on what the value depends on, so every
+    // kernel family that asks the same question shares the entry
+    std::map<std::array<int, 4>, int> fp_pix;
     // precision guard (iss_set_precision_guard / iss_cnn_precision_info)
     int prec_override = -1;               // -1: the context's mode; else ISS_PREC_* for this network only
     bool prec_by_caller = false;          // prec_override came from iss_cnn_set_net_precision (else from the guard: iss_set_precision re-arms)

@@ -264,7 +264,7 @@ SMALL_TAIL = [('conv', 4, 5, 64), ('bn_relu',), ('conv', 5, 3, 128), ('bn_relu',
 def test_small_demoted_layer_is_not_handed_the_chl_layout():
     """A pooled-relu producer in front of a 3 x 3, stride-1, 128 -> 128 bias + relu conv small enough to be demoted to exact f32 in
     fp16 mode (conv_igemm_kernel).  The producer may hand its output over in the CHL layout only to a conv_x3_wq3h_kernel launch
-    (wq3_plan), and conv_row and wq3_plan now decide the demotion with one helper, so a demoted consumer is never handed CHL
+    (want_hl_out), and the producer asks the consumer's own selection (select_conv), demotion included, so a demoted consumer is never handed CHL
     (it used to be possible in principle: "internal: row N reads a CHL tensor on a kernel that expects f32").  On this map the
     hand-over is not taken in either mode: a tile of the one-wave-per-SIMD kernel (192 - 256 output pixels) over 4 x 1 outputs
     reads a 4.5 x larger footprint than its 512-pixel capacity (and the weight-stationary kernel's 2 x) -- the same footprint

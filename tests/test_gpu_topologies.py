@@ -3,6 +3,8 @@ un-vendored nets -- padded / small / large filters, 32..128 channels incl. 48 / 
 or after the activation, big dense heads, pools in odd places -- must match the Keras-semantics oracle to 1e-4 on
 probabilities, on the overlapping-window path (shared first layer where it applies) AND on scattered windows, and
 through the asynchronous entry.  Plus the BASELINE config-size check: one hour of slots in several passes."""
+import os
+
 import numpy as np
 import pytest
 
@@ -146,3 +148,93 @@ def test_one_hour_of_slots_config_size(ctx):
         # The calibrated heads (|W| rms 0.27, tests/golden/make_standin_heads.py) amplify input differences ~2x more than
         # the seeded random ones this bound was first written for (1e-4 on probabilities); the input here is white noise
         assert err < 2e-4 and lerr < 1e-3
+
+
+_PRECS = (('bf16x3', _native.PREC_BF16X3), ('f16x3', _native.PREC_F16X3), ('f32', _native.PREC_F32))
+
+
+def _selection_cases(ctx):
+    """(case, outputs) of every case tests/golden/kernel_selection.json pins: small runs that between them reach every conv launch
+    site.  Consumed one at a time: the caller reads ctx.prof_instances() after each.  Leaves precision, diag and workspace limit
+    changed (the caller restores them)."""
+    import graph_nets as GN
+    import test_gpu_cnn as TC
+    from inaspeechsegmenter_amd import vbx as V
+    from oracle import vbx as ovbx
+
+    def run(case, fn, prec=_native.PREC_BF16X3, diag=0, limit=24 << 30):
+        ctx.set_precision(prec)
+        ctx.set_diag(diag)
+        ctx.set_workspace_limit(limit)
+        ctx.prof_reset()
+        out = fn()
+        return case, [np.asarray(o) for o in (out if isinstance(out, tuple) else (out,))]
+
+    T = 1500
+    for name in sorted(TP.SPECS):                                       # test_topology_parity's inputs
+        rng = np.random.default_rng(sum(map(ord, name)))
+        mspec = _mspec(rng, T)
+        mspec[700:703, 5] = -np.inf
+        ctx.set_mspec(mspec)
+        rows = S._window_rows(T)
+        for net, (layers, shp) in sorted(TP.nets(name).items()):
+            ctx.cnn_load(5, KM.compile_layers(layers, shp))
+            scat = np.sort(rng.integers(0, T - 68, 64)).astype(np.int32)
+            for pname, p in _PRECS:
+                yield run(f'topo/{name}/{net}/{pname}/overlapping', lambda: ctx.cnn_probs(5, rows), p)
+                yield run(f'topo/{name}/{net}/{pname}/scattered', lambda: ctx.cnn_probs(5, scat), p)
+            yield run(f'topo/{name}/{net}/bf16x3/overlapping_64MiB', lambda: ctx.cnn_probs(5, rows), limit=64 << 20)
+            if name == 'standin':
+                for bit in sorted(_native.DIAG_BITS):
+                    if bit != 'no_skip_dead':
+                        yield run(f'diag/{bit}/{net}', lambda: ctx.cnn_probs(5, rows), _native.PREC_F16X3, _native.DIAG_BITS[bit])
+    for name in sorted(TC.TOPOLOGIES):                                  # test_layer_semantics' inputs at 21 mel
+        rng = np.random.default_rng(sum(map(ord, name)) + 21)
+        ctx.cnn_load(5, KM.compile_layers(TC.TOPOLOGIES[name](rng, 21), (68, 21, 1)))
+        ctx.set_mspec(TC._mspec(rng, 400))
+        rows = rng.integers(0, 400 - 68, 301).astype(np.int32)
+        for pname, p in _PRECS:
+            yield run(f'layers/{name}/{pname}', lambda: ctx.cnn_probs(5, rows), p)
+    ex = V.VBxExtractor(ctx, ovbx.resnet101_random_params(0), batch_windows=8)      # test_gpu_vbx's seeded ResNet-101
+    fea = np.random.default_rng(9).normal(0, 1, (144 + 24 * 3, 64)).astype(np.float32)
+    for pname, p in _PRECS:                                             # (the suite's mode, the library's default, exact f32)
+        for dname in ('', 'no_dual', 'no_chain') if p != _native.PREC_F32 else ('',):
+            yield run(f'resnet101/{pname}/{dname or "all"}', lambda: ex.get_embeddings(fea, [0, 24, 48], 144), p, _native.diag_flags(dname))
+    for name in sorted(GN.NETS):                                        # host-fed (iss_cnn_forward): no patch first layer
+        for nmel, ncls in ((21, 3), (24, 2)):
+            layers, shp = GN.NETS[name](nmel, ncls, 5)
+            ctx.cnn_load(5, KM.compile_layers(layers, shp, patch_input=False))
+            x = np.random.default_rng(nmel).normal(0, 1, (5,) + tuple(shp)).astype(np.float32)
+            for pname, p in _PRECS:
+                yield run(f'graph/{name}/{nmel}/{pname}', lambda: ctx.cnn_forward(5, x), p)
+
+
+def _selection_run(ctx):
+    """{case: {instantiation: launches}} over _selection_cases, the context's settings restored."""
+    prev_limit = getattr(ctx, 'workspace_limit', None) or (24 << 30)
+    table = {}
+    ctx.prof_enable(True)
+    try:
+        for case, _ in _selection_cases(ctx):
+            table[case] = {i['kernel']: int(i['launches']) for i in ctx.prof_instances()}
+    finally:
+        ctx.prof_enable(False)
+        ctx.set_precision(_native.PREC_BF16X3)
+        ctx.set_diag(0)
+        ctx.set_workspace_limit(prev_limit)
+    return table
+
+
+def test_kernel_selection_is_pinned(ctx, golden):
+    """Which kernel instantiation runs each conv row, and how often, over every topology of the sweep (both nets, three arithmetic
+    modes, overlapping and scattered windows, several passes), each diagnostic switch on the stand-in, the layer-semantics nets,
+    the seeded ResNet-101 and the host-fed graph models: equal to tests/golden/kernel_selection.json, which was recorded before
+    kernel selection was split from the launch code.  A kernel change that renames or re-routes an instantiation on purpose
+    re-records the file; a refactor of the selection must not."""
+    import json
+    with open(os.path.join(golden, 'kernel_selection.json')) as f:
+        want = json.load(f)
+    got = _selection_run(ctx)
+    assert sorted(got) == sorted(want)
+    diff = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    assert not diff, diff
