@@ -374,7 +374,8 @@ class Context:
         self._keep_rs = src         # the async H2D copy reads it until the next sync
 
     def resample_signal(self, x, sr, fmt=None):
-        """A single source resampled on its own: the resident signal becomes its 16 kHz mono PCM16 -> its length."""
+        """A single source resampled on its own: the resident signal becomes its 16 kHz mono PCM16 -> its length.  (For arrays in
+        hand, as the tests have them; the product places a file through sources.RawSource.place: the same job row, the same call.)"""
         x = np.ascontiguousarray(x)
         job = self.resample_job(x, sr, 0, 0, fmt)
         self.resample(x.reshape(-1).view(np.uint8), [job], n_signal=job[-1])
@@ -392,7 +393,15 @@ class Context:
         self._ck(self._L.iss_resample_stats(self._h, C.byref(a), C.byref(b)), 'iss_resample_stats')
         return a.value, b.value
 
-    # ---- page-locked host arrays
+    def _status(self, name, n):
+        """This context's page-locked status array `name` of a decoder, grown on demand to hold n entries."""
+        st, n = self.__dict__.get(name), max(int(n), 1)
+        if st is None or st.size < n:
+            if st is not None:
+                self.pinned_free(st)
+            st = self.__dict__[name] = self.pinned_empty((int(n * 1.25) + 256,), np.int32)
+        return st
+
     # ---- FLAC decoder (iss_flac_*): compressed frames -> resident signal (PCM16), staging buffer, or resampled
     def flac_decode(self, src, frames, jobs, n_signal=-1):
         """iss_flac_decode: src = 1-D uint8 array of the compressed bytes of every job, frames = FLAC_FRAME rows, jobs = rows
@@ -401,11 +410,7 @@ class Context:
         src = np.ascontiguousarray(src, dtype=np.uint8)
         fr = np.ascontiguousarray(frames, dtype=FLAC_FRAME)
         jb = np.ascontiguousarray(np.array(jobs, dtype=FLAC_JOB).reshape(-1))
-        st = self.__dict__.get('_flac_status')
-        if st is None or st.size < max(len(fr), 1):
-            if st is not None:
-                self.pinned_free(st)
-            st = self._flac_status = self.pinned_empty((int(max(len(fr), 1) * 1.25) + 256,), np.int32)
+        st = self._status('_flac_status', len(fr))
         self._ck(self._L.iss_flac_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data), len(fr),
                                          C.c_void_p(jb.ctypes.data), jb.size, int(n_signal), _ptr(st, C.c_int32)),
                  'iss_flac_decode')
@@ -431,11 +436,7 @@ class Context:
         context's): valid after the next synchronising call (get_loge, adpcm_get_stage, synchronize)."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=ADPCM_JOB).reshape(-1))
-        st = self.__dict__.get('_adpcm_status')
-        if st is None or st.size < max(nblocks, 1):
-            if st is not None:
-                self.pinned_free(st)
-            st = self._adpcm_status = self.pinned_empty((int(max(nblocks, 1) * 1.25) + 256,), np.int32)
+        st = self._status('_adpcm_status', nblocks)
         self._ck(self._L.iss_adpcm_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data), jb.size,
                                           int(nblocks), int(n_signal), _ptr(st, C.c_int32)), 'iss_adpcm_decode')
         self._keep_adpcm = src         # the async H2D copy reads it until the next sync
@@ -453,6 +454,7 @@ class Context:
         self._ck(self._L.iss_adpcm_stats(self._h, C.byref(a), C.byref(b)), 'iss_adpcm_stats')
         return a.value, b.value
 
+    # ---- page-locked host arrays
     def pinned_empty(self, shape, dtype):
         """numpy array backed by hipHostMalloc memory (freed with the context, or by `pinned_free`)."""
         dt = np.dtype(dtype)

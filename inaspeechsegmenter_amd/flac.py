@@ -5,13 +5,16 @@ starting with `fLaC`, optionally behind an ID3v2 tag) reads exactly like its WAV
 rate and channels, 16 bits for 8/16-bit streams and 24 bits for 24-bit streams.  This module parses the metadata blocks
 (STREAMINFO used; PADDING, APPLICATION, SEEKTABLE, VORBIS_COMMENT, CUESHEET, PICTURE and reserved types skipped) and has the
 compiled host code index the frames (iss_flac_index); the samples are decoded by flac_decode_kernel on the device
-(`FlacSource`, Segmenter / pipeline) or by the host build of the same decoder (`read_host`, io.py).
+(`FlacSource`, one of the sources of sources.py) or by the host build of the same decoder (`FlacStream.stored`, io.py).
 """
 import struct
 
 import numpy as np
 
 from . import _native
+from . import resample as R
+from .io import need_16k_mono, source_of
+from .sources import CodedSource
 
 MAGIC = b'fLaC'
 # benchmark switch (tools/bench_flac.py), not a user option: True makes the ffmpeg-free read decode FLAC on the host
@@ -38,15 +41,6 @@ def is_flac(buf):
 
 def is_ogg_flac(buf):
     return buf[:4] == b'OggS' and b'\x7fFLAC' in buf[:128]
-
-
-def sniff(path):
-    """Is the file at `path` a FLAC stream (by its bytes, whatever its name)?"""
-    with open(path, 'rb') as f:
-        head = f.read(10)
-        p = _id3_end(head)
-        f.seek(p)
-        return f.read(4) == MAGIC
 
 
 class FlacStream:
@@ -113,18 +107,21 @@ class FlacStream:
         self.check(st)
         return x
 
+    stored = decode_host                                         # (the name sndfmt.Sound has for it: io._stored)
 
-class FlacSource:
-    """A FLAC file for the device decoder.  `size` is its 16 kHz length (resampled when `resample`), so it stands where a
-    decoded signal's `size` is read, like segmenter.RawSource.  kind: 'pcm' (mono 8/16-bit at 16 kHz: PCM16 straight into
-    the signal), 'float' (mono 24-bit at 16 kHz: the float path of a 24-bit WAV), 'resample' (downmixed and resampled)."""
-    __slots__ = ('s', 'kind', 'size', 'nbytes')
+    def source(self, resample=False):
+        return source(self, resample)
 
-    def __init__(self, stream, kind):
-        from . import resample
-        self.s, self.kind = stream, kind
-        self.size = resample.out_len(stream.n, stream.sr) if kind == 'resample' else stream.n
-        self.nbytes = stream.audio.nbytes
+
+class FlacSource(CodedSource):
+    """A FLAC file for the device decoder (sources.py states what it answers).  kind: 'pcm' (mono 8/16-bit at 16 kHz), 'float'
+    (mono 24-bit at 16 kHz: the float path of a 24-bit WAV, so it goes alone and its samples come back to the host) or
+    'resample'."""
+    __slots__ = ()
+    pass_order = 1
+    batchable = property(lambda self: self.kind != 'float')
+    payload = property(lambda self: self.s.audio)
+    units = property(lambda self: len(self.s.frames))
 
     def job(self, ctx, src_offset, frame_begin, dst_offset):
         """Its FLAC_JOB row: into the signal at dst_offset ('pcm'), resampled to dst_offset ('resample'), or staged ('float')."""
@@ -136,35 +133,43 @@ class FlacSource:
             return (src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_STAGE, fid, dst_offset, self.size)
         return (src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_STAGE, -1, 0, 0)
 
+    @staticmethod
+    def tables(group):
+        return np.concatenate([g.s.frames for g in group])
+
+    @staticmethod
+    def launch(ctx, staged, jobs, frames, n_signal=-1):
+        return ctx.flac_decode(staged, frames, jobs, n_signal)
+
+    def samples(self, ctx):
+        """'float', on its own: decoded to the staging buffer -> the stored int32 samples on the host (checked)."""
+        s = self.s
+        st = self.launch(ctx, s.audio, [self.job(ctx, 0, 0, 0)], s.frames, 0)
+        x = ctx.flac_get_stage(0, s.n, s.ch, s.bps)
+        s.check(st)
+        return x
+
 
 def source(stream, resample=False):
-    """The FlacSource of a parsed stream under the WAV-twin rules of the ffmpeg-free read: without `resample`, a rate other
-    than 16 kHz is the WAV path's AssertionError and several channels its ValueError; 16 kHz mono reads the same either way."""
-    from . import resample as R
+    """The FlacSource of a parsed stream under the WAV-twin rules of the ffmpeg-free read (io.need_16k_mono without
+    `resample`); 16 kHz mono reads the same either way.  (_HOST_DECODE: the samples decoded here, as the WAV twin reads.)"""
+    if _HOST_DECODE:
+        return source_of(stream.decode_host(), stream.sr, stream.name, resample)
     if stream.sr == R.SR_OUT and stream.ch == 1:
         return FlacSource(stream, 'float' if stream.bps > 16 else 'pcm')
     if not resample:
-        assert stream.sr == 16_000, \
-            f'Without ffmpeg, inaSpeechSegmenter can only take files sampled ' \
-            f'at 16000 Hz. The file {stream.name} is sampled at {stream.sr} Hz.'
-        raise ValueError(f'{stream.name}: {stream.ch} channels; without ffmpeg only mono files are supported')
+        need_16k_mono(stream.name, stream.sr, stream.ch)
     R.check_rate(stream.sr)
     return FlacSource(stream, 'resample')
 
 
 def decode_on(ctx, src):
     """One file on its own.  'pcm' / 'resample': the resident signal becomes its 16 kHz PCM16 -> the per-frame status, valid
-    after the context's next synchronising call (check it with src.s.check).  'float': -> the stored int32 samples (checked)."""
-    s = src.s
-    st = ctx.flac_decode(s.audio, s.frames, [src.job(ctx, 0, 0, 0)], n_signal=0 if src.kind == 'float' else src.size)
-    if src.kind == 'float':
-        x = ctx.flac_get_stage(0, s.n, s.ch, s.bps)
-        s.check(st)
-        return x
-    return st
+    after the context's next synchronising call (check it with src.check).  'float': -> the stored int32 samples (checked)."""
+    return src.place(ctx) if src.batchable else src.samples(ctx)
 
 
 def read_host(buf, name='<buffer>'):
     """ffmpeg-free host read: -> (stored samples, (n,) or (n, C), sr), the arrays io._parse_wav returns for the WAV twin."""
     stream = FlacStream(buf, name)
-    return stream.decode_host(), stream.sr
+    return stream.stored(), stream.sr

@@ -10,7 +10,8 @@ Decode stays on the host (north star); soundfile/libsndfile is not available in 
 image, so RIFF/WAVE is parsed here with libsndfile's conversion rules (PCM16 -> x/32768,
 unknown chunks skipped).  FLAC (flac.py) reads exactly like its WAV twin, decoded here by the host build of the
 device's frame decoder; so do G.711 and IMA ADPCM in WAV, RF64 / BW64, Wave64, AIFF / AIFF-C, AU and CAF (sndfmt.py: numpy
-tables, byte swaps and the host build of the device's IMA decoder).  `decode_pcm` is the entry the native pipeline uses: it keeps
+tables, byte swaps and the host build of the device's IMA decoder).  A file is read once (`_read_file`) and `_classify` says
+from its bytes which parser takes it: a new format is one line there.  `decode_pcm` is the entry the native pipeline uses: it keeps
 PCM16 as int16 so the device does the x/32768 scaling (2 B/sample over PCIe, not 4).
 """
 import os
@@ -18,6 +19,9 @@ import struct
 import subprocess
 
 import numpy as np
+
+from . import resample as R
+from .sources import RawSource
 
 
 def _parse_wav(buf, name='<buffer>'):
@@ -64,20 +68,27 @@ def _parse_wav(buf, name='<buffer>'):
     return a, sr
 
 
-def _read_nofmpeg(medianame):
-    """ffmpeg-free read of a WAV, FLAC or sndfmt.py file -> (samples as stored, sr) as _parse_wav returns them (for the WAV twin)."""
-    from . import flac
+def _read_file(medianame):
     with open(medianame, 'rb') as f:
-        buf = f.read()
+        return f.read()
+
+
+def _classify(buf, name):
+    """What the bytes of a file are to the ffmpeg-free read: a flac.FlacStream, a sndfmt.Sound (G.711 / IMA ADPCM WAV, RF64,
+    Wave64, AIFF, AU, CAF), or None for what _parse_wav reads or refuses.  One line per format; what comes back has `sr`,
+    `stored()` (the host decode) and `source(resample)` (what Segmenter reads).  (flac and sndfmt import this
+    module for need_16k_mono and _to_float, so they are imported here and not at the top.)"""
+    from . import flac, sndfmt
     if flac.is_flac(buf):
-        return flac.read_host(buf, medianame)
+        return flac.FlacStream(buf, name)
     if flac.is_ogg_flac(buf):
-        raise ValueError(f'{medianame}: Ogg-FLAC (FLAC in an Ogg container) is not supported without ffmpeg')
-    from . import sndfmt
-    snd = sndfmt.parse(buf, medianame)               # G.711 / IMA ADPCM WAV, RF64, Wave64, AIFF, AU, CAF: expanded to the twin's array
-    if snd is not None:
-        return snd.stored(), snd.sr
-    return _parse_wav(buf, medianame)
+        raise ValueError(f'{name}: Ogg-FLAC (FLAC in an Ogg container) is not supported without ffmpeg')
+    return sndfmt.parse(buf, name)
+
+
+def _stored(what, buf, name):
+    """what = _classify(buf, name) -> (samples as stored, sr) as _parse_wav returns them (for the WAV twin), decoded on the host."""
+    return _parse_wav(buf, name) if what is None else (what.stored(), what.sr)
 
 
 def _to_float(a, dtype):
@@ -119,17 +130,33 @@ def _check_no_ffmpeg(medianame, start_sec, stop_sec):
             f'or use ffmpeg. You gave medianame={medianame}.')
 
 
+def need_16k_mono(name, sr, channels):
+    """The refusal of the ffmpeg-free read without `resample` (io.py:53-55), the same for every format: rate first."""
+    assert sr == 16_000, \
+        f'Without ffmpeg, inaSpeechSegmenter can only take files sampled ' \
+        f'at 16000 Hz. The file {name} is sampled at {sr} Hz.'
+    if channels != 1:
+        raise ValueError(f'{name}: {channels} channels; without ffmpeg only mono files are supported')
+
+
+def source_of(x, sr, name, resample=False):
+    """What Segmenter reads for samples as stored on the host: the 16 kHz mono array (int16, or float32 for the float path);
+    anything else is refused without `resample` and handed to the device resampler as a RawSource with it."""
+    if sr == R.SR_OUT and x.ndim == 1:
+        return np.ascontiguousarray(x) if x.dtype == np.int16 else np.ascontiguousarray(_to_float(x, np.float32))
+    if not resample:
+        need_16k_mono(name, sr, 1 if x.ndim == 1 else x.shape[1])
+    R.check_rate(sr)
+    return RawSource(x, sr)
+
+
 def decode_pcm(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg'):
     """16 kHz mono samples for the device: int16 when the source is PCM16 (always, through
     ffmpeg), else float32 holding exactly what soundfile's float32 read would return."""
     if ffmpeg is None:
         _check_no_ffmpeg(medianame, start_sec, stop_sec)
-        a, sr = _read_nofmpeg(medianame)
-        assert sr == 16_000, \
-            f'Without ffmpeg, inaSpeechSegmenter can only take files sampled ' \
-            f'at 16000 Hz. The file {medianame} is sampled at {sr} Hz.'
-        if a.ndim != 1:
-            raise ValueError(f'{medianame}: {a.shape[1]} channels; without ffmpeg only mono files are supported')
+        a, sr = decode_source(medianame)
+        need_16k_mono(medianame, sr, 1 if a.ndim == 1 else a.shape[1])
     else:
         a = _run_ffmpeg(medianame, start_sec, stop_sec, ffmpeg)
     if a.dtype == np.int16:
@@ -138,9 +165,10 @@ def decode_pcm(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg'):
 
 
 def decode_source(medianame):
-    """ffmpeg-free read of any WAV or FLAC (Segmenter(ffmpeg=None, resample=True)): -> (samples as stored, (n,) or (n, C),
-    sr).  Nothing is converted: the device downmixes, resamples and quantises (inaspeechsegmenter_amd/resample.py)."""
-    return _read_nofmpeg(medianame)
+    """ffmpeg-free read of a WAV, FLAC or sndfmt.py file: -> (samples as stored, (n,) or (n, C), sr).  Nothing is converted:
+    the device downmixes, resamples and quantises (inaspeechsegmenter_amd/resample.py)."""
+    buf = _read_file(medianame)
+    return _stored(_classify(buf, medianame), buf, medianame)
 
 
 def media2sig16kmono(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg', dtype='float64'):

@@ -5,18 +5,17 @@ main thread runs the two Keras `predict` calls, the Viterbi smoothing and the ex
 (segmenter.py:297-335, medialist2feats :338-374).  On an MI355X a 5-minute file is ~14 ms of device work, so per-file
 launches, copies and Python bookkeeping become the limit.  Here files are processed in SUPER-BATCHES:
 
-  decode threads   N files  ->  int16 PCM (RIFF parse, or the ffmpeg pipe); with Segmenter(resample=True) WAVs at other
-                   rates / channel counts are handed on as stored (segmenter.RawSource); without ffmpeg FLAC files are
-                   handed on compressed, their frames indexed (flac.FlacSource); G.711, big-endian and IMA ADPCM files
-                   (sndfmt.py) are handed on as stored too (RawSource with its format, sndfmt.AdpcmSource)
+  decode threads   N files  ->  int16 PCM as a numpy array (RIFF parse, or the ffmpeg pipe), or -- without ffmpeg -- a source of
+                   sources.py, handed on as stored for the device to finish: a WAV at another rate / channel count with
+                   Segmenter(resample=True), G.711 and big-endian files (RawSource), FLAC frames (flac.FlacSource), IMA ADPCM
+                   blocks (sndfmt.AdpcmSource)
   packer           the PCM of a super-batch (default <= 32 files / ~40 min of audio) is laid end to end in ONE page-locked
                    buffer, every file starting on a multiple of 160 samples: frame t of file f is then frame
                    off_f / 160 + t of the concatenation, and the frames that straddle two files are simply never used
-                   (room is left for the resampled files, whose stored bytes go into a second page-locked buffer)
-  device worker    ONE H2D copy, ONE resample launch for all resampled files (one more H2D copy), ONE FLAC decode launch for
-                   all FLAC files (one more H2D copy of their compressed bytes; the resampled ones add one resample launch),
-                   likewise ONE ADPCM decode launch for all IMA ADPCM files (one more H2D copy, at most one resample launch),
-                   ONE sidekit launch, one log-energy read-back (with the FLAC frame status); per-file energy Viterbi (compiled);
+                   (room is left for the sources; the payloads of each class go end to end into a page-locked buffer of its own)
+  device worker    ONE H2D copy; per source class ONE more H2D copy of its payloads and ONE launch for all its files of the pass
+                   (resample; FLAC decode; IMA ADPCM decode -- the decoders add at most one resample launch each); ONE sidekit
+                   launch, one log-energy read-back (with the decoders' status); per-file energy Viterbi (compiled);
                    ONE iss_cnn_probs call for the VAD windows of all files, per-segment Viterbi; ONE call for the
                    gender windows, Viterbi; hand the segment lists to the exporter
   exporter         CSV / TextGrid writers
@@ -24,6 +23,9 @@ launches, copies and Python bookkeeping become the limit.  Here files are proces
 Four device workers with a context each (own stream, own workspace) take super-batches in turn, so while some are in their
 host phases (packing, Viterbi, bookkeeping) the others' kernels run.  Results are identical to per-file processing: every frame and
 every 20 ms slot is computed from the same samples by the same kernels (tests/test_gpu_segmenter.py).
+
+"Array or source" is the only distinction made here, and what a source is asked is what sources.py lists: a new format needs
+no line in this file.
 """
 import queue
 import sys
@@ -34,6 +36,8 @@ import warnings
 import numpy as np
 
 from . import _native
+from . import segmenter as S
+from . import sources
 
 FRAME_HOP = 160
 MIN_SAMPLES = 400 + FRAME_HOP * 67                  # 68 frames: shorter media take the single-file path (mspec padding)
@@ -49,14 +53,7 @@ class _Batch:
         return sum(-(-s.size // FRAME_HOP) * FRAME_HOP for s in self.sigs)
 
 
-def _held(sig):
-    """What a decoded source holds, in 16-bit sample units: its samples, or a stored source's bytes / 2 when larger; a FLAC
-    or IMA ADPCM source holds its compressed bytes."""
-    from . import flac, sndfmt
-    if isinstance(sig, (flac.FlacSource, sndfmt.AdpcmSource)):
-        return max(1, sig.nbytes // 2)
-    x = getattr(sig, 'x', None)
-    return sig.size if x is None else max(sig.size, x.nbytes // 2)
+_held = sources.held                                 # what a decoded signal holds while it waits, for the audio budget
 
 
 class _AudioBudget:
@@ -82,7 +79,6 @@ class _AudioBudget:
 def _decode_stage(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None, resample=False):
     """items: [(index, src)].  Puts (index, src, sig | None, errtext | None) on out_q in completion order, then None."""
     import random
-    from . import segmenter as S
     in_q = queue.Queue()
     for it in items:
         in_q.put(it)
@@ -133,10 +129,7 @@ class _Worker:
         else:
             self.owned = False
         self.ctx = ctx
-        self.pin = None
-        self.rpin = None                             # stored bytes of the resampled files of a pass
-        self.fpin = None                             # compressed bytes of the FLAC files of a pass
-        self.apin = None                             # blocks of the IMA ADPCM files of a pass
+        self.pins = {}                               # page-locked buffers by what they hold: 'signal', or a source class's staged bytes
         # wall seconds this worker spent per phase since the last reset (bench.py reports them: where a step's host time goes)
         self.stats = {k: 0.0 for k in ('pack', 'features', 'energy_host', 'cnn_device', 'smooth_host', 'batches', 'files')}
 
@@ -144,33 +137,14 @@ class _Worker:
         if self.owned:
             self.ctx.close()
 
-    def pinned(self, nsamples):
-        if self.pin is None or self.pin.size < nsamples:
-            if self.pin is not None:
-                self.ctx.pinned_free(self.pin)
-            self.pin = self.ctx.pinned_empty((int(nsamples * 1.25) + 4096,), np.int16)
-        return self.pin
-
-    def raw_pinned(self, nbytes):
-        if self.rpin is None or self.rpin.size < nbytes:
-            if self.rpin is not None:
-                self.ctx.pinned_free(self.rpin)
-            self.rpin = self.ctx.pinned_empty((int(nbytes * 1.25) + 4096,), np.uint8)
-        return self.rpin
-
-    def flac_pinned(self, nbytes):
-        if self.fpin is None or self.fpin.size < nbytes:
-            if self.fpin is not None:
-                self.ctx.pinned_free(self.fpin)
-            self.fpin = self.ctx.pinned_empty((int(nbytes * 1.25) + 4096,), np.uint8)
-        return self.fpin
-
-    def adpcm_pinned(self, nbytes):
-        if self.apin is None or self.apin.size < nbytes:
-            if self.apin is not None:
-                self.ctx.pinned_free(self.apin)
-            self.apin = self.ctx.pinned_empty((int(nbytes * 1.25) + 4096,), np.uint8)
-        return self.apin
+    def pinned(self, key, n, dtype):
+        """This worker's page-locked buffer `key`, grown on demand to hold n items."""
+        cur = self.pins.get(key)
+        if cur is None or cur.size < n:
+            if cur is not None:
+                self.ctx.pinned_free(cur)
+            cur = self.pins[key] = self.ctx.pinned_empty((int(n * 1.25) + 4096,), dtype)
+        return cur
 
     def sync_settings(self):
         """Arithmetic mode and workspace cap follow the Segmenter's own context (they may have changed since this
@@ -181,8 +155,6 @@ class _Worker:
     def run(self, batch):
         """-> [ [(label, start_slot, stop_slot)] per file of the batch ]; None for a FLAC / IMA ADPCM file whose frames / blocks
         the device found malformed (its message in batch.errs)"""
-        from . import segmenter as S
-        from . import flac, sndfmt
         seg, ctx = self.seg, self.ctx
         st = self.stats
         t_ = time.perf_counter()
@@ -190,73 +162,46 @@ class _Worker:
         for s in batch.sigs:
             offs.append(pos)
             pos += -(-s.size // FRAME_HOP) * FRAME_HOP
-        buf = self.pinned(pos)
-        raws, flacs, adpcms = [], [], []
+        buf = self.pinned('signal', pos, np.int16)
+        groups = {}                                  # source class -> [(file, source, offset in the signal)]
         for f, (s, o) in enumerate(zip(batch.sigs, offs)):
-            if isinstance(s, S.RawSource):           # written by the resample kernel
+            if isinstance(s, sources.Source):        # written by its class's kernel (and the resample kernel)
                 buf[o:o + s.size] = 0
-                raws.append((s, o))
-            elif isinstance(s, flac.FlacSource):     # written by the FLAC decode kernel (and the resample kernel)
-                buf[o:o + s.size] = 0
-                flacs.append((f, s, o))
-            elif isinstance(s, sndfmt.AdpcmSource):  # written by the ADPCM decode kernel (and the resample kernel)
-                buf[o:o + s.size] = 0
-                adpcms.append((f, s, o))
+                groups.setdefault(type(s), []).append((f, s, o))
             elif s.dtype == np.int16:
                 buf[o:o + s.size] = s
             else:                                    # float sources: what libsndfile's float32 read holds, re-quantised is NOT exact
                 raise TypeError('float media take the single-file path')
             buf[o + s.size:o + -(-s.size // FRAME_HOP) * FRAME_HOP] = 0
-        if raws:                                     # stored bytes end to end, each source on a 16-byte boundary
-            rb = self.raw_pinned(sum(-(-s.x.nbytes // 16) * 16 for s, _ in raws))
-            jobs, rpos = [], 0
-            for s, o in raws:
-                rb[rpos:rpos + s.x.nbytes] = s.x.reshape(-1).view(np.uint8)
-                jobs.append(ctx.resample_job(s.x, s.sr, rpos, o, s.fmt))
-                rpos += -(-s.x.nbytes // 16) * 16
-        if flacs:                                    # compressed frames end to end, each file on a 16-byte boundary
-            fb = self.flac_pinned(sum(-(-s.nbytes // 16) * 16 for _, s, _ in flacs))
-            fjobs, fpos, fbeg = [], 0, 0
-            for _, s, o in flacs:
-                fb[fpos:fpos + s.nbytes] = s.s.audio
-                fjobs.append(s.job(ctx, fpos, fbeg, o))
-                fpos += -(-s.nbytes // 16) * 16
-                fbeg += len(s.s.frames)
-            frames = np.concatenate([s.s.frames for _, s, _ in flacs])
-        if adpcms:                                   # stored blocks end to end, each file on a 16-byte boundary
-            ab = self.adpcm_pinned(sum(-(-s.nbytes // 16) * 16 for _, s, _ in adpcms))
-            ajobs, apos, abeg = [], 0, 0
-            for _, s, o in adpcms:
-                ab[apos:apos + s.nbytes] = s.s.data
-                ajobs.append(s.job(ctx, apos, abeg, o))
-                apos += -(-s.nbytes // 16) * 16
-                abeg += s.s.nblocks
+        launches = []
+        for cls in sorted(groups, key=lambda c: c.pass_order):
+            # the payloads of a class end to end, each file on a 16-byte boundary; job rows with running byte / unit offsets
+            grp = groups[cls]
+            pb = self.pinned(cls, sum(-(-s.payload.size // 16) * 16 for _, s, _ in grp), np.uint8)
+            jobs, bpos, ubeg = [], 0, 0
+            for _, s, o in grp:
+                p = s.payload
+                pb[bpos:bpos + p.size] = p
+                jobs.append(s.job(ctx, bpos, ubeg, o))
+                bpos += -(-p.size // 16) * 16
+                ubeg += s.units
+            launches.append((cls, grp, pb[:bpos], jobs, cls.tables([s for _, s, _ in grp])))
         st['pack'] += time.perf_counter() - t_; t_ = time.perf_counter()
         ctx.set_signal(buf[:pos])
-        if raws:
-            ctx.resample(rb[:rpos], jobs)            # one launch for every resampled file of the pass, into the signal above
-        if flacs:
-            fstat = ctx.flac_decode(fb[:fpos], frames, fjobs)   # one decode launch for every FLAC file of the pass
-        if adpcms:
-            astat = ctx.adpcm_decode(ab[:apos], ajobs, abeg)    # one decode launch for every ADPCM file of the pass
+        # ONE launch per class for all its files of the pass, into the signal above: resampled, FLAC, IMA ADPCM
+        status = [cls.launch(ctx, staged, jobs, tables) for cls, _, staged, jobs, tables in launches]
         ctx.sidekit()
         loge = ctx.get_loge()
-        if adpcms:                                   # the block status came back with the log-energy
-            abeg = 0
-            for f, s, _ in adpcms:
+        for (_, grp, _, _, _), stat in zip(launches, status):
+            if stat is None:
+                continue
+            ubeg = 0
+            for f, s, _ in grp:                      # the frame / block status came back with the log-energy
                 try:
-                    s.s.check(astat[abeg:abeg + s.s.nblocks])
+                    s.check(stat[ubeg:ubeg + s.units])
                 except ValueError as exc:
                     batch.errs[f] = 'error: %s %s' % (type(exc), exc)
-                abeg += s.s.nblocks
-        if flacs:                                    # the frame status came back with the log-energy
-            fbeg = 0
-            for f, s, _ in flacs:
-                try:
-                    s.s.check(fstat[fbeg:fbeg + len(s.s.frames)])
-                except ValueError as exc:
-                    batch.errs[f] = 'error: %s %s' % (type(exc), exc)
-                fbeg += len(s.s.frames)
+                ubeg += s.units
         st['features'] += time.perf_counter() - t_; t_ = time.perf_counter()
         g0 = [o // FRAME_HOP for o in offs]
         nfr = [(s.size - 400) // FRAME_HOP + 1 for s in batch.sigs]
@@ -266,11 +211,7 @@ class _Worker:
             if f in batch.errs:                      # a malformed FLAC / ADPCM file: no segments, no network rows
                 lsegs.append([])
                 continue
-            le = loge[g0[f]:g0[f] + nfr[f]]
-            lseg = []
-            for lab, start, stop in S._binidx2seglist(S._energy_activity(le, seg.energy_ratio)[::2]):
-                lseg.append(('noEnergy' if lab == 0 else 'energy', start, stop))
-            lsegs.append(lseg)
+            lsegs.append(S._energy_segments(loge[g0[f]:g0[f] + nfr[f]], seg.energy_ratio))
         st['energy_host'] += time.perf_counter() - t_
         wrs = [S._window_rows(nfr[f]) + np.int32(g0[f]) for f in range(len(lsegs))]
         # Segmenter.dense_batches (an extension, default False): every network on EVERY slot of every file -- the most work
@@ -295,7 +236,10 @@ class _Worker:
                         if dense:
                             sel.append(np.arange(wbase[f] + start, wbase[f] + stop))
             if not rows:
-                st['smooth_host'] += time.perf_counter() - t_
+                st['smooth_host'] += time.perf_counter() - t_; t_ = time.perf_counter()
+                if dense and len(allw):              # no `inlabel` segment in the whole pass: dense work does not depend on that
+                    net.probs(ctx, allw)
+                    st['cnn_device'] += time.perf_counter() - t_
                 continue
             allrows = np.concatenate(rows)
             st['smooth_host'] += time.perf_counter() - t_; t_ = time.perf_counter()
@@ -354,8 +298,6 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
     per-file 'ok <secs>' message reports, segmenter.py:322-327, when files are processed one by one).
     skip: set of indices not to process.  Device failures (NativeError) and exceptions raised by on_result (unwritable
     outputs) propagate to the caller: the first one is re-raised here once every stage has drained."""
-    from . import segmenter as S
-    from . import flac, sndfmt
     batch_files = batch_files or DEFAULT_BATCH_FILES
     batch_seconds = batch_seconds or DEFAULT_BATCH_SECONDS
     workers = workers or DEFAULT_WORKERS
@@ -389,13 +331,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                     except BaseException as exc:                   # noqa: B902
                         failure.append(exc)
                     continue
-                if isinstance(sig, (S.RawSource, sndfmt.AdpcmSource)):
-                    single = False
-                elif isinstance(sig, flac.FlacSource):
-                    single = sig.kind == 'float'             # 24-bit: the float path, as a 24-bit WAV takes
-                else:
-                    single = sig.dtype != np.int16
-                if single or sig.size < MIN_SAMPLES:
+                if not sources.batchable(sig) or sig.size < MIN_SAMPLES:
                     batch_q.put(('single', i, src, sig))
                     continue
                 cur.idx.append(i); cur.sigs.append(sig); cur.names.append(src)
@@ -486,10 +422,7 @@ def close_workers(seg):
 
 def _slots(seg, ctx, mspec, loge, difflen):
     """segment_slots of `seg` on another context (the networks are loaded there under the same ids)."""
-    from . import segmenter as S
-    lseg = []
-    for lab, start, stop in S._binidx2seglist(S._energy_activity(loge, seg.energy_ratio)[::2]):
-        lseg.append(('noEnergy' if lab == 0 else 'energy', start, stop))
+    lseg = S._energy_segments(loge, seg.energy_ratio)
     for net in ([seg.vad, seg.gender] if seg.detect_gender else [seg.vad]):
         lseg = net(mspec, lseg, difflen, ctx=ctx)
     return lseg

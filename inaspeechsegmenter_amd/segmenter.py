@@ -12,6 +12,9 @@ medialist2feats 338-374); the body is re-organised around the native pipeline:
 
 The 68-frame patches of `_get_patches` (segmenter.py:76-88) are never materialised: the
 host only builds the int32 list "first mel row of the window feeding slot i".
+
+What `_load_source` reads is a numpy array (16 kHz mono samples) or a source of sources.py (stored bytes the device resamples
+or decodes); `_place` is the one step that puts either on the device alone, shared by `_sig2feats` and `Segmenter.load_pcm`.
 """
 import os
 import time
@@ -25,9 +28,9 @@ import numpy as np
 from . import _native
 from . import tables
 from . import keras_model
-from . import flac
-from . import sndfmt
-from .io import decode_pcm, decode_source, _check_no_ffmpeg, _to_float
+from . import io as iss_io
+from .io import decode_pcm, _to_float
+from .sources import Source, RawSource               # noqa: F401  (RawSource is also imported from here, where it was)
 from .export_funcs import seg2csv, seg2textgrid
 
 _MODEL_DIRS = ('/root/.keras/inaSpeechSegmenter/', os.path.expanduser('~/.keras/inaSpeechSegmenter/'))
@@ -96,6 +99,12 @@ def _binidx2seglist(binidx):
     starts = np.concatenate(([0], cut))
     stops = np.concatenate((cut, [n]))
     return [(a[s].item() if hasattr(a[s], 'item') else a[s], int(s), int(e)) for s, e in zip(starts, stops)]
+
+
+def _energy_segments(loge, ratio):
+    """The energy detector's labelled segments in 20 ms slots (segmenter.py:261-267): [(label, start, stop)]."""
+    return [('noEnergy' if lab == 0 else 'energy', start, stop)
+            for lab, start, stop in _binidx2seglist(_energy_activity(loge, ratio)[::2])]
 
 
 def _window_rows(nframes, difflen=0):
@@ -304,45 +313,20 @@ def _ensure_resident(ctx, mspec):
     return m.shape[0]
 
 
-class RawSource:
-    """Samples at another rate or channel count, as stored, for the device resampler (Segmenter(ffmpeg=None, resample=True)).
-    `size` is its length once resampled to 16 kHz, so it stands where a decoded signal's `size` is read.  `fmt` is the
-    ISS_RS_* format of the stored bytes: the dtype's by default; explicit for signed bytes, G.711 and big-endian samples."""
-    __slots__ = ('x', 'sr', 'size', 'fmt')
-
-    def __init__(self, x, sr, fmt=None):
-        from . import resample
-        self.x, self.sr = np.ascontiguousarray(x), sr
-        self.fmt = _native.RS_FORMAT[self.x.dtype] if fmt is None else int(fmt)
-        self.size = resample.out_len(x.shape[0], sr)
-
-
 def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False):
-    """decode_pcm's 16 kHz mono samples; with `resample` (ffmpeg=None only) a WAV at another rate or with several channels
-    comes back as a RawSource instead of failing (16 kHz mono files are read exactly as decode_pcm reads them).  Without
-    ffmpeg a FLAC file comes back as a flac.FlacSource (compressed frames, decoded on the device like its WAV twin reads),
-    and a file of sndfmt.py as what sndfmt.source makes of it: stored bytes for the device (a RawSource with its format, a
-    sndfmt.AdpcmSource), or the twin's 16 kHz mono array."""
-    if ffmpeg is None:
-        _check_no_ffmpeg(medianame, start_sec, stop_sec)
-        what = sndfmt.device_decoded(medianame)                  # one look at the file's first bytes
-        if what == 'flac' and not flac._HOST_DECODE:
-            with open(medianame, 'rb') as f:
-                return flac.source(flac.FlacStream(f.read(), medianame), resample)
-        if what == 'snd':
-            with open(medianame, 'rb') as f:
-                snd = sndfmt.parse(f.read(), medianame)
-            if snd is not None:
-                return sndfmt.source(snd, resample)
-    if not resample:
+    """decode_pcm's 16 kHz mono samples (a numpy array), or -- without ffmpeg -- a source of sources.py for the device to
+    finish.  The file is read once and what io._classify makes of its bytes says what Segmenter reads: a FLAC stream
+    becomes a flac.FlacSource (compressed frames, decoded on the device like its WAV twin reads), a file of sndfmt.py what
+    sndfmt.source makes of it (a RawSource with its format, a sndfmt.AdpcmSource, or the twin's array), and a WAV at another
+    rate or with several channels a RawSource with `resample` and decode_pcm's refusal without it (io.source_of)."""
+    if ffmpeg is not None:
         return decode_pcm(medianame, start_sec, stop_sec, ffmpeg)
-    from . import resample as R
-    _check_no_ffmpeg(medianame, start_sec, stop_sec)
-    x, sr = decode_source(medianame)
-    if sr == R.SR_OUT and x.ndim == 1:
-        return np.ascontiguousarray(x) if x.dtype == np.int16 else np.ascontiguousarray(_to_float(x, np.float32))
-    R.check_rate(sr)
-    return RawSource(x, sr)
+    iss_io._check_no_ffmpeg(medianame, start_sec, stop_sec)
+    buf = iss_io._read_file(medianame)
+    what = iss_io._classify(buf, medianame)
+    if what is not None:
+        return what.source(resample)
+    return iss_io.source_of(*iss_io._parse_wav(buf, medianame), medianame, resample)
 
 
 def _media2feats(medianame, start_sec, stop_sec, ffmpeg, ctx=None, resample=False):
@@ -354,28 +338,29 @@ def _media2feats(medianame, start_sec, stop_sec, ffmpeg, ctx=None, resample=Fals
     return _sig2feats(ctx, sig, medianame)
 
 
+def _place(ctx, sig, resident=True):
+    """One file on the device, alone: `sig` becomes the resident signal -> (its samples where the host holds them, else None;
+    the status to hand to sig.check AFTER the context's next synchronising read-back, valid only then).  An array is uploaded
+    (resident=False: left where it is); a source places itself, but one that cannot be batched -- 24-bit FLAC, the float path
+    of its WAV twin -- comes back to the host as float32 and goes on as an array."""
+    if isinstance(sig, Source):
+        if sig.batchable:
+            return None, sig.place(ctx)
+        sig = _to_float(sig.samples(ctx), np.float32)
+    if resident:
+        ctx.set_signal(sig)
+    return sig, None
+
+
 def _sig2feats(ctx, sig, medianame='<signal>'):
-    """sig: 16 kHz mono samples (uploaded), a RawSource (resampled on the device into the resident signal), a FlacSource
-    (decoded on the device: into the signal, resampled, or -- 24-bit -- back to the host for the float path), or an
-    AdpcmSource (decoded on the device into the signal, or staged and resampled)."""
+    """sig: 16 kHz mono samples, or a source of sources.py (resampled / decoded on the device into the resident signal)."""
     if sig.size < 400:
         raise ValueError(f"media {medianame}: {sig.size} samples, less than one 25 ms analysis window")
-    status = None
-    if isinstance(sig, RawSource):
-        ctx.resample_signal(sig.x, sig.sr, sig.fmt)
-    elif isinstance(sig, sndfmt.AdpcmSource):
-        status = sndfmt.decode_on(ctx, sig)
-    elif isinstance(sig, flac.FlacSource):
-        if sig.kind == 'float':
-            ctx.set_signal(_to_float(flac.decode_on(ctx, sig), np.float32))
-        else:
-            status = flac.decode_on(ctx, sig)
-    else:
-        ctx.set_signal(sig)
+    host, status = _place(ctx, sig)
     nframes = ctx.sidekit()
     loge = ctx.get_loge()
-    if status is not None:                                      # read back with the log-energy
-        sig.s.check(status)
+    if host is None:                                            # read back with the log-energy
+        sig.check(status)
     difflen = 0
     if nframes < 68:                                            # segmenter.py:61-65
         difflen = 68 - nframes
@@ -443,9 +428,7 @@ class Segmenter:
             t1, p1, _ = self.vad.probs(ctx, rows, async_out=self._pinned_out(0, len(rows), len(self.vad.outlabels)))
             t2, p2, _ = self.gender.probs(ctx, rows, async_out=self._pinned_out(1, len(rows), len(self.gender.outlabels)))
             pending = (t1, p1, t2, p2)
-        lseg = []
-        for lab, start, stop in _binidx2seglist(_energy_activity(loge, self.energy_ratio)[::2]):
-            lseg.append(('noEnergy' if lab == 0 else 'energy', start, stop))
+        lseg = _energy_segments(loge, self.energy_ratio)
         if pending is not None:
             t1, p1, t2, p2 = pending
             self.ctx.wait(t1)
@@ -496,21 +479,11 @@ class Segmenter:
         ffmpeg a FLAC file is decoded on the device and its samples copied back (what decode_pcm gives for its WAV twin),
         and so is an IMA ADPCM file; G.711 and big-endian files at other rates or channel counts go to the resampler as stored."""
         sig = _load_source(medianame, None, None, self.ffmpeg, self.resample)
-        if isinstance(sig, flac.FlacSource):
-            if sig.kind == 'float':
-                return _to_float(flac.decode_on(self.ctx, sig), np.float32)
-            status = flac.decode_on(self.ctx, sig)
-            out = self.ctx.get_signal_pcm16(0, sig.size)
-            sig.s.check(status)
-            return out
-        if isinstance(sig, sndfmt.AdpcmSource):
-            status = sndfmt.decode_on(self.ctx, sig)
-            out = self.ctx.get_signal_pcm16(0, sig.size)
-            sig.s.check(status)
-            return out
-        if isinstance(sig, RawSource):
-            return self.ctx.get_signal_pcm16(0, self.ctx.resample_signal(sig.x, sig.sr, sig.fmt))
-        return sig
+        host, status = _place(self.ctx, sig, resident=False)
+        if host is None:
+            host = self.ctx.get_signal_pcm16(0, sig.size)
+            sig.check(status)
+        return host
 
     def __call__(self, medianame, start_sec=None, stop_sec=None):
         """segmenter.py:279-294."""

@@ -12,9 +12,9 @@ and channel count that holds
 
 This module parses the containers (the device never sees a header) into a `Sound`: the stored bytes plus what they mean.
 `Sound.stored()` expands them on the host into the array io._parse_wav returns for the twin (numpy tables, and the host
-build of the device's IMA decoder); `source()` hands them to the device as they are: G.711 bytes, signed bytes and big-endian
-samples to the resample kernel (ISS_RS_I8 / ISS_RS_ULAW / ISS_RS_ALAW / ISS_RS_SWAP), IMA blocks to adpcm_decode_kernel
-(`AdpcmSource`).  The frame count of an IMA file is its `fact` count when present and not larger than whole blocks *
+build of the device's IMA decoder); `source()` hands them to the device as they are, as one of the sources of sources.py: G.711
+bytes, signed bytes and big-endian samples to the resample kernel (a `RawSource` with ISS_RS_I8 / ISS_RS_ULAW / ISS_RS_ALAW /
+ISS_RS_SWAP), IMA blocks to adpcm_decode_kernel (`AdpcmSource`).  The frame count of an IMA file is its `fact` count when present and not larger than whole blocks *
 samples per block, else that product; a trailing partial block is ignored (a definition: libsndfile was not at hand to pin it).
 """
 import struct
@@ -22,6 +22,10 @@ import struct
 import numpy as np
 
 from . import _native
+from . import flac
+from . import resample as R
+from .io import _to_float, need_16k_mono
+from .sources import CodedSource, RawSource
 
 # benchmark switch (tools/bench_sndfmt.py), not a user option: True makes the ffmpeg-free read expand G.711 and IMA ADPCM on
 # the host (numpy table / iss_adpcm_decode_host in the decode threads) instead of handing the stored bytes to the device
@@ -103,6 +107,9 @@ class Sound:
             k = int(bad[0])
             why = _native.ADPCM_STATUS.get(int(status[k]), f'status {int(status[k])}')
             raise ValueError(f'{self.name}: block at byte {self.base + k * self.block_align}: {why}')
+
+    def source(self, resample=False):
+        return source(self, resample)
 
     def stored(self):
         """The array io._parse_wav returns for the WAV twin: (n,) or (n, ch), uint8 / int16 / int32 / float32 / float64."""
@@ -397,15 +404,13 @@ def _ours(head):
             if cid == b'data':
                 return False
             pos += 8 + size + (size & 1)
-    # a `fmt ` chunk past the first 4 KiB (a large bext / LIST / JUNK chunk in front): parse() decides on the whole file, and
-    # a plain PCM file among these is then read a second time by the WAV path (rare, and the result is the same)
+    # a `fmt ` chunk past the first 4 KiB (a large bext / LIST / JUNK chunk in front): parse() decides on the whole file
     return True
 
 
 def device_decoded(path):
     """One look at the first bytes of the file at `path` (whatever its name): 'flac' for a native FLAC stream, 'snd' for a
     file this module reads, None for anything else (a plain PCM / float WAV among them)."""
-    from . import flac
     with open(path, 'rb') as f:
         head = f.read(4096)
         p = flac._id3_end(head)
@@ -418,17 +423,12 @@ def device_decoded(path):
 
 
 # ------------------------------------------------------------------------------------------------ device sources
-class AdpcmSource:
-    """An IMA ADPCM file for the device decoder.  `size` is its 16 kHz length (resampled when kind is 'resample'), so it
-    stands where a decoded signal's `size` is read, like flac.FlacSource.  kind: 'pcm' (mono at 16 kHz: PCM16 straight into
-    the signal) or 'resample' (staged, downmixed and resampled in the same call)."""
-    __slots__ = ('s', 'kind', 'size', 'nbytes')
-
-    def __init__(self, sound, kind):
-        from . import resample
-        self.s, self.kind = sound, kind
-        self.size = resample.out_len(sound.n, sound.sr) if kind == 'resample' else sound.n
-        self.nbytes = sound.data.nbytes
+class AdpcmSource(CodedSource):
+    """An IMA ADPCM file for the device decoder (sources.py states what it answers).  kind: 'pcm' or 'resample'."""
+    __slots__ = ()
+    pass_order = 2
+    payload = property(lambda self: self.s.data)
+    units = property(lambda self: self.s.nblocks)
 
     def job(self, ctx, src_offset, block_begin, dst_offset):
         """Its ADPCM_JOB row: into the signal at dst_offset ('pcm') or staged and resampled to dst_offset ('resample')."""
@@ -438,26 +438,28 @@ class AdpcmSource:
         fid, _, _ = ctx.resample_filter(s.sr)
         return (src_offset, block_begin, s.nblocks, s.n, s.ch, s.block_align, _native.ADPCM_TO_STAGE, fid, dst_offset, self.size)
 
+    @staticmethod
+    def tables(group):
+        return sum(g.units for g in group)
+
+    @staticmethod
+    def launch(ctx, staged, jobs, nblocks, n_signal=-1):
+        return ctx.adpcm_decode(staged, jobs, nblocks, n_signal)
+
 
 def decode_on(ctx, src):
     """One IMA file on its own: the resident signal becomes its 16 kHz PCM16 -> the per-block status, valid after the
-    context's next synchronising call (check it with src.s.check)."""
-    return ctx.adpcm_decode(src.s.data, [src.job(ctx, 0, 0, 0)], src.s.nblocks, n_signal=src.size)
+    context's next synchronising call (check it with src.check)."""
+    return src.place(ctx)
 
 
 def source(snd, resample=False):
     """What Segmenter reads for a parsed file under the WAV-twin rules of the ffmpeg-free read: the twin's int16 / float32
-    array (16 kHz mono), an AdpcmSource, or a segmenter.RawSource holding the bytes as stored.  Without `resample`, a rate
-    other than 16 kHz is the WAV path's AssertionError and several channels its ValueError."""
-    from . import resample as R
-    from .io import _to_float
-    from .segmenter import RawSource
+    array (16 kHz mono), an AdpcmSource, or a sources.RawSource holding the bytes as stored.  Without `resample`, anything but
+    16 kHz mono is refused as the WAV path refuses it (io.need_16k_mono)."""
     mono16k = snd.sr == R.SR_OUT and snd.ch == 1
     if not mono16k and not resample:
-        assert snd.sr == 16_000, \
-            f'Without ffmpeg, inaSpeechSegmenter can only take files sampled ' \
-            f'at 16000 Hz. The file {snd.name} is sampled at {snd.sr} Hz.'
-        raise ValueError(f'{snd.name}: {snd.ch} channels; without ffmpeg only mono files are supported')
+        need_16k_mono(snd.name, snd.sr, snd.ch)
     host = _HOST_DECODE and snd.kind in ('ulaw', 'alaw', 'ima')
     if snd.kind == 'ima' and not host and snd.n > 0:
         if mono16k:

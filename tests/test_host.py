@@ -497,6 +497,21 @@ def test_super_batch_pipeline_equals_per_file_calls_with_fake_device(tmp_path):
     assert sum(calls) >= 2 * sum(nslots)                                                      # every slot, both nets (+ the single-file medium)
 
 
+def test_dense_pass_without_inlabel_segment_runs_every_slot(tmp_path, monkeypatch):
+    """Segmenter.dense_batches is "both networks on every slot of every file", whatever the networks decide -- also in a pass
+    none of whose files holds a segment for a network to refine.  The test above counts on that, and which files share a pass
+    depends there on the completion order of two decode threads.  Here the order is forced (one decode thread, the first medium
+    after the fifth): the two media without a 'speech' segment share the second pass, and the gender network must still run."""
+    from inaspeechsegmenter_amd import pipeline
+    decode = pipeline._decode_stage
+
+    def forced(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None, resample=False):
+        return decode(items[1:6] + items[:1] + items[6:], ffmpeg, nbtry, trydelay, out_q, 1, budget, resample)
+
+    monkeypatch.setattr(pipeline, '_decode_stage', forced)
+    test_super_batch_pipeline_equals_per_file_calls_with_fake_device(tmp_path)
+
+
 def test_batch_process_contract_with_fake_device(tmp_path):
     """segmenter.py:297-335 through the product's batch_process + pipeline on a fake device: return tuple, message codes
     (0 ok / 1 already exists / 2 error) in INPUT order, output directories created, skipifexist, both exporters, unknown format
@@ -909,3 +924,205 @@ def test_one_arithmetic_decision_per_network_across_device_contexts():
         gd.probs(wk, rows); gd.probs(own, rows)
         assert wk.told == [_native.PREC_BF16X3] and own.told == [] and (own.mode, wk.mode) == ('bf16x3', 'bf16x3')
     assert gd._mode_state['mode'] == _native.PREC_BF16X3
+
+
+class _RecordingDevice(_FakeDevice):
+    """_FakeDevice + the resampler / decoder half of the context API.  Nothing is decoded: every call is written down with a
+    SHA-256 of its byte arguments, its job rows, `n_signal` and its unit count; a decode call answers an all-zero status
+    (bad_last: its last entry 1, so the file that holds the last unit of the call is the malformed one)."""
+
+    def __init__(self, predicts, nmels, bad_last=False):
+        super().__init__(predicts, nmels)
+        self.calls, self.filters, self.bad_last = [], {}, bad_last
+
+    def _status(self, n):
+        st = np.zeros(int(n), np.int32)
+        st[-1:] = int(self.bad_last)
+        return st
+
+    @staticmethod
+    def _sha(a):
+        import hashlib
+        return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+    def _new_signal(self, n_signal):
+        if n_signal >= 0:
+            self.sig = np.zeros(n_signal, np.int16)
+
+    def pinned_empty(self, shape, dtype):
+        return np.zeros(shape, dtype)                              # (the 16-byte gaps between staged sources are hashed too)
+
+    def set_signal(self, sig):
+        self.calls.append(['set_signal', str(sig.dtype), int(sig.size), self._sha(sig)])
+        self.sig = np.array(sig, copy=True) if sig.dtype == np.int16 else np.asarray(sig, np.float32) * np.float32(32768.0)
+
+    def sidekit(self):
+        self.calls.append(['sidekit'])
+        return super().sidekit()
+
+    def get_loge(self):
+        self.calls.append(['get_loge'])
+        return super().get_loge()
+
+    def resample_filter(self, sr):
+        from inaspeechsegmenter_amd import resample
+        up, down, _ = resample.plan(sr)
+        self.calls.append(['resample_filter', int(sr)])
+        return self.filters.setdefault((up, down), len(self.filters)), up, down
+
+    resample_job, resample_signal = _native.Context.resample_job, _native.Context.resample_signal
+
+    def resample(self, src, jobs, n_signal=-1):
+        self.calls.append(['resample', self._sha(src), [[int(v) for v in j] for j in jobs], int(n_signal)])
+        self._new_signal(n_signal)
+
+    def flac_decode(self, src, frames, jobs, n_signal=-1):
+        self.calls.append(['flac_decode', self._sha(src), self._sha(frames), [[int(v) for v in j] for j in jobs], int(n_signal), len(frames)])
+        self._new_signal(n_signal)
+        return self._status(len(frames))
+
+    def adpcm_decode(self, src, jobs, nblocks, n_signal=-1):
+        self.calls.append(['adpcm_decode', self._sha(src), [[int(v) for v in j] for j in jobs], int(n_signal), int(nblocks)])
+        self._new_signal(n_signal)
+        return self._status(nblocks)
+
+    def get_signal_pcm16(self, offset, n):
+        self.calls.append(['get_signal_pcm16', int(offset), int(n)])
+        return self.sig[offset:offset + n].copy()
+
+    def flac_get_stage(self, job, frames_total, channels, bps):
+        self.calls.append(['flac_get_stage', int(job), int(frames_total), int(channels), int(bps)])
+        out = np.zeros((int(frames_total), int(channels)), np.int32 if bps > 16 else np.int16)
+        return out[:, 0] if channels == 1 else out
+
+
+def _pass_device_calls(tmp):
+    """The record tests/golden/pass_device_calls.json holds: a mixed set of files through pipeline.process_files (with and
+    without `resample`), Segmenter.load_pcm and _sig2feats on a _RecordingDevice."""
+    import flacgen
+    import sndgen
+    import wavgen
+    from inaspeechsegmenter_amd import pipeline
+    tmp = str(tmp)
+    sig = lambda n, ch, seed: wavgen.make_signal(n, ch, seed, peak=0.5)
+    pcm = lambda n, ch, seed, bps=16: np.round(sig(n, ch, seed) * 2 ** (bps - 1)).astype(np.int64)
+    p = lambda name: os.path.join(tmp, name)
+    files = [
+        wavgen.write_wav(p('pcm16.wav'), wavgen.encode(sig(32077, 1, 1), 'i16'), 16000, 'i16'),
+        wavgen.write_wav(p('stereo48k.wav'), wavgen.encode(sig(96005, 2, 2), 'i16'), 48000, 'i16'),
+        flacgen.write(p('f16.flac'), pcm(33001, 1, 3), 16000, 16),
+        flacgen.write(p('f24.flac'), pcm(20011, 1, 4, 24), 16000, 24),
+        sndgen.write(p('ima16k.wav'), 'wav', 'ima', False, sig(35003, 1, 5), 16000)[0],
+        wavgen.write_wav(p('float.wav'), wavgen.encode(sig(30001, 1, 6), 'f32'), 16000, 'f32'),
+        flacgen.write(p('f8k.flac'), pcm(16003, 1, 7), 8000, 16),
+        p('missing.wav'),
+        sndgen.write(p('ima8k_stereo.wav'), 'wav', 'ima', False, sig(17001, 2, 8), 8000)[0],
+        wavgen.write_wav(p('short.wav'), wavgen.encode(sig(9000, 1, 9), 'i16'), 16000, 'i16'),    # under 68 frames
+        sndgen.write(p('ulaw8k.au'), 'au', 'ulaw', True, sig(18007, 1, 10), 8000)[0],
+        sndgen.write(p('be16.aiff'), 'aiff', 'i16', True, sig(31013, 1, 11), 16000)[0],
+        p('cut.aiff'),
+    ]
+    with open(p('be16.aiff'), 'rb') as f, open(p('cut.aiff'), 'wb') as g:
+        g.write(f.read()[:30])                                     # a truncated AIFF: cut inside its COMM chunk
+    with open(p('ogg.flac'), 'wb') as g:
+        g.write(b'OggS' + bytes(24) + b'\x7fFLAC' + bytes(64))
+    refused = [('start_sec', (files[0], 1.0, None)), ('stop_sec', (files[2], None, 2.0)), ('http', ('http://host/a.wav', None, None)),
+               ('ogg.flac', (p('ogg.flac'), None, None))]
+    for name, made in (('wav', lambda q, x, sr: wavgen.write_wav(q, wavgen.encode(x, 'i16'), sr, 'i16')),
+                       ('flac', lambda q, x, sr: flacgen.write(q, np.round(x * 32768).astype(np.int64), sr, 16)),
+                       ('ima', lambda q, x, sr: sndgen.write(q, 'wav', 'ima', False, x, sr)[0]),
+                       ('au', lambda q, x, sr: sndgen.write(q, 'au', 'ulaw', True, x, sr)[0])):
+        refused += [('3 kHz ' + name, (made(p('r3k.' + name), sig(3001, 1, 12), 3000), None, None)),
+                    ('16 kHz stereo ' + name, (made(p('st16k.' + name), sig(4001, 2, 13), 16000), None, None))]
+    clean = lambda text: None if text is None else str(text).replace(tmp + os.sep, '')
+
+    def predict(nclass):
+        def run(batch):
+            x = np.asarray(batch)
+            out = np.full((len(x), nclass), 0.001, np.float32)
+            out[np.arange(len(x)), (np.nan_to_num(x[:, 30, 5, 0]) > 0).astype(int)] = 0.998
+            return out
+        return run
+
+    record = {}
+    for resample, bad_last in ((True, False), (False, False), (True, True)):
+        fake = _RecordingDevice({0: predict(3), 1: predict(2)}, {0: 21, 1: 24}, bad_last)
+        seg = object.__new__(S.Segmenter)
+        seg.energy_ratio, seg.detect_gender, seg.ctx, seg.ffmpeg, seg.resample = 0.03, True, fake, None, resample
+        seg.vad, seg.gender = object.__new__(S.SpeechMusicNoise), object.__new__(S.Gender)
+        seg.vad.ctx = seg.gender.ctx = fake
+        seg.vad.compiled = seg.gender.compiled = None
+        rec = record['resample=%s%s' % (resample, ', last unit bad' if bad_last else '')] = {'sources': {}, 'batches': [], 'pass errors': [], 'results': {}}
+        for path in files:                                         # what each file becomes, what it holds, or how it fails
+            name = os.path.basename(path)
+            try:
+                src = S._load_source(path, None, None, None, resample)
+            except BaseException as exc:                           # noqa: B902
+                rec['sources'][name] = {'error': [type(exc).__name__, clean(exc)]}
+                continue
+            rec['sources'][name] = {'type': type(src).__name__, 'dtype': str(getattr(src, 'dtype', None)), 'size': int(src.size),
+                                    'held': int(pipeline._held(src))}
+        for name, args in refused:                                 # the refusals of the ffmpeg-free read, by type and text
+            try:
+                rec['sources'][name] = {'type': type(S._load_source(*args, None, resample)).__name__}
+            except BaseException as exc:                           # noqa: B902
+                rec['sources'][name] = {'error': [type(exc).__name__, clean(exc)]}
+        run = pipeline._Worker.run
+
+        def recording_run(self, batch):
+            fake.calls.append(['pass', [os.path.basename(n) for n in batch.names]])
+            rec['batches'].append([os.path.basename(n) for n in batch.names])
+            out = run(self, batch)
+            rec['pass errors'] += [[int(k), clean(v)] for k, v in sorted(batch.errs.items())]
+            return out
+
+        def on_result(i, src, lseg, err, secs=0.0):
+            rec['results'][os.path.basename(src)] = 'segments' if lseg is not None else clean(err)
+
+        pipeline._Worker.run = recording_run
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore')
+                pipeline.process_files(seg, files, on_result, workers=1, decode_threads=1, batch_files=6)
+        finally:
+            pipeline._Worker.run = run
+        batched = {n for b in rec['batches'] for n in b}
+        for name, s in rec['sources'].items():                     # alone, or in a super-batch
+            if 'held' in s:
+                s['goes'] = 'batch' if name in batched else 'single'
+        rec['process_files'], fake.calls = fake.calls, []
+        if not resample or bad_last:
+            continue
+        for path in files:
+            name = os.path.basename(path)
+            if 'error' in rec['sources'][name]:
+                continue
+            out = seg.load_pcm(path)
+            fake.calls.append(['load_pcm', name, str(out.dtype), int(out.size)])
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore')
+                mspec, loge, difflen = S._sig2feats(fake, S._load_source(path, None, None, None, resample), path)
+            fake.calls.append(['_sig2feats', name, len(mspec), len(loge), int(difflen)])
+        rec['single files'] = fake.calls
+        seg.close()
+    return record
+
+
+def test_pass_device_calls_are_pinned(tmp_path):
+    """What a device pass is made of does not move when the host code around it is reorganised: the ordered device calls of
+    pipeline.process_files, Segmenter.load_pcm and _sig2feats over one file of every kind of decoded source (arrays, stored
+    samples for the resampler, FLAC frames, IMA ADPCM blocks; a float file, a 24-bit FLAC and a file under 68 frames that go
+    alone; a missing and a truncated file), with the bytes staged for each call, its job rows, signal sizes and unit counts;
+    every buffer given to set_signal; what each source holds for the audio budget; whether it goes alone or into a super-batch;
+    and every per-file error (with the last status entry of every decode call set: the second FLAC and the second IMA file of a
+    pass are then the malformed ones) -- equal to tests/golden/pass_device_calls.json, recorded before the sources got one interface.
+    One decode thread and one worker: completion order is input order.  batch_files is 6, not 4, so that one pass holds two FLAC
+    and two IMA ADPCM files: their job rows then carry running unit offsets."""
+    with open(os.path.join(GOLDEN, 'pass_device_calls.json')) as f:
+        want = json.load(f)
+    got = json.loads(json.dumps(_pass_device_calls(tmp_path)))
+    assert sorted(got) == sorted(want)
+    for key in want:
+        assert sorted(got[key]) == sorted(want[key]), key
+        diff = {k: (got[key][k], want[key][k]) for k in want[key] if got[key][k] != want[key][k]}
+        assert not diff, (key, diff)
