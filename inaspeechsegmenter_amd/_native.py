@@ -387,11 +387,19 @@ class Context:
         self._ck(self._L.iss_get_signal_pcm16(self._h, _ptr(out, C.c_int16), int(offset), int(n)), 'iss_get_signal_pcm16')
         return out
 
+    def _counters(self, fn):        # (launches, units) the stats entry point `fn` reports
+        a, b = C.c_int64(), C.c_int64()
+        self._ck(getattr(self._L, fn)(self._h, C.byref(a), C.byref(b)), fn)
+        return a.value, b.value
+
+    def _get_stage(self, fn, job, frames_total, channels, dtype):        # a decoder's read-back `fn`: (n,) or (n, channels)
+        out = np.empty((int(frames_total), int(channels)), dtype=dtype)
+        self._ck(getattr(self._L, fn)(self._h, int(job), C.c_void_p(out.ctypes.data), out.nbytes), fn)
+        return out[:, 0] if channels == 1 else out
+
     def resample_stats(self):
         """(resample launches, resample jobs) since the context was created."""
-        a, b = C.c_int64(), C.c_int64()
-        self._ck(self._L.iss_resample_stats(self._h, C.byref(a), C.byref(b)), 'iss_resample_stats')
-        return a.value, b.value
+        return self._counters('iss_resample_stats')
 
     def _status(self, name, n):
         """This context's page-locked status array `name` of a decoder, grown on demand to hold n entries."""
@@ -419,15 +427,11 @@ class Context:
 
     def flac_get_stage(self, job, frames_total, channels, bps):
         """Stored-format samples of staged job `job` of the last flac_decode: (n,) or (n, channels) int16 / int32."""
-        out = np.empty((int(frames_total), int(channels)), dtype=np.int32 if bps > 16 else np.int16)
-        self._ck(self._L.iss_flac_get_stage(self._h, int(job), C.c_void_p(out.ctypes.data), out.nbytes), 'iss_flac_get_stage')
-        return out[:, 0] if channels == 1 else out
+        return self._get_stage('iss_flac_get_stage', job, frames_total, channels, np.int32 if bps > 16 else np.int16)
 
     def flac_stats(self):
         """(FLAC decode launches, frames decoded) since the context was created."""
-        a, b = C.c_int64(), C.c_int64()
-        self._ck(self._L.iss_flac_stats(self._h, C.byref(a), C.byref(b)), 'iss_flac_stats')
-        return a.value, b.value
+        return self._counters('iss_flac_stats')
 
     # ---- IMA ADPCM decoder (iss_adpcm_*): stored blocks -> resident signal (PCM16), staging buffer, or resampled
     def adpcm_decode(self, src, jobs, nblocks, n_signal=-1):
@@ -444,15 +448,11 @@ class Context:
 
     def adpcm_get_stage(self, job, frames_total, channels):
         """PCM16 samples of staged job `job` of the last adpcm_decode: (n,) or (n, channels) int16."""
-        out = np.empty((int(frames_total), int(channels)), dtype=np.int16)
-        self._ck(self._L.iss_adpcm_get_stage(self._h, int(job), C.c_void_p(out.ctypes.data), out.nbytes), 'iss_adpcm_get_stage')
-        return out[:, 0] if channels == 1 else out
+        return self._get_stage('iss_adpcm_get_stage', job, frames_total, channels, np.int16)
 
     def adpcm_stats(self):
         """(ADPCM decode launches, blocks decoded) since the context was created."""
-        a, b = C.c_int64(), C.c_int64()
-        self._ck(self._L.iss_adpcm_stats(self._h, C.byref(a), C.byref(b)), 'iss_adpcm_stats')
-        return a.value, b.value
+        return self._counters('iss_adpcm_stats')
 
     # ---- page-locked host arrays
     def pinned_empty(self, shape, dtype):

@@ -9,7 +9,7 @@
 // a channel is serial, so lane c walks channel c (c, c + 64, ... for wide files) and writes its samples interleaved into
 // LDS; after a barrier the whole wave copies the block's samples to global memory, consecutive lanes to consecutive 16-bit
 // samples (a lane per block would store 16-bit samples a block apart: one cache line per store).  All offsets are 64-bit.
-#include "iss_internal.h"
+#include "decode_pass.h"
 #include <algorithm>
 #include <cstring>
 
@@ -125,18 +125,11 @@ extern "C" int iss_adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, 
                                 int64_t nblocks_total, int64_t n_signal, int32_t* status_out) {
     if (!c || njobs < 0 || (njobs > 0 && (!jobs || !status_out)) || src_bytes < 0 || (!src && src_bytes > 0) || nblocks_total < 0)
         return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: bad argument");
-    ISS_HIP(c, hipSetDevice(c->device));
-    int64_t nsig = n_signal;
-    if (n_signal < 0) {
-        if (c->sig_kind != 1 || c->sig_ptr != c->sig.p)
-            return iss_fail(c, ISS_ESTATE, "iss_adpcm_decode: n_signal < 0 needs a PCM16 signal uploaded by iss_signal_pcm16");
-        nsig = c->sig_n;
-    }
+    IssDecodePass pass;
+    int rc = pass.begin(c, "iss_adpcm_decode", n_signal, njobs);
+    if (rc) return rc;
     std::vector<AdJobDev> dev((size_t)njobs);
-    std::vector<iss_resample_job> rjobs;
-    std::vector<std::pair<int64_t, int64_t>> ranges;
-    std::vector<int64_t> stage_off((size_t)njobs, -1), stage_bytes((size_t)njobs, 0);
-    int64_t stage = 0, blocks = 0, lds = 0;
+    int64_t blocks = 0, lds = 0;
     for (int32_t j = 0; j < njobs; ++j) {
         const iss_adpcm_job& J = jobs[j];
         if (!geometry_ok(J.nblocks, J.channels, J.block_align, J.frames_total))
@@ -152,30 +145,11 @@ extern "C" int iss_adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, 
         AdJobDev& d = dev[(size_t)j];
         d.src_off = J.src_offset; d.block_base = blocks; d.nblocks = J.nblocks; d.frames_total = J.frames_total;
         d.ch = J.channels; d.block_align = J.block_align; d.spb = samples_per_block(J.block_align, J.channels);
-        if (J.output == ISS_ADPCM_TO_SIGNAL) {
-            if (J.channels != 1)
-                return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: only mono sources go to the signal", j);
-            if (J.dst_offset < 0 || J.dst_offset > nsig - J.frames_total)
-                return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: output [%lld, %lld) outside the %lld-sample signal", j,
-                                (long long)J.dst_offset, (long long)(J.dst_offset + J.frames_total), (long long)nsig);
-            ranges.push_back({J.dst_offset, J.dst_offset + J.frames_total});
-            d.to_sig = 1;
-            d.dst_byte = J.dst_offset * 2;
-        } else if (J.output == ISS_ADPCM_TO_STAGE) {
-            d.to_sig = 0;
-            d.dst_byte = stage;
-            stage_off[(size_t)j] = stage;
-            stage_bytes[(size_t)j] = J.frames_total * J.channels * 2;
-            if (J.filter >= 0) {
-                iss_resample_job r{};
-                r.src_offset = stage; r.frames_in = J.frames_total; r.channels = J.channels; r.format = ISS_RS_I16;
-                r.filter = J.filter; r.dst_offset = J.dst_offset; r.frames_out = J.frames_out;
-                rjobs.push_back(r);
-            }
-            stage += (stage_bytes[(size_t)j] + 15) / 16 * 16;
-        } else {
-            return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: bad output %d", j, J.output);
-        }
+        bool to_sig;
+        if ((rc = pass.place(j, {J.output, J.filter, J.dst_offset, J.frames_out}, J.frames_total, J.channels, 2, J.channels == 1,
+                             "mono", to_sig, d.dst_byte)))
+            return rc;
+        d.to_sig = to_sig ? 1 : 0;
         lds = std::max<int64_t>(lds, (int64_t)d.spb * d.ch * 2);
         blocks += J.nblocks;
     }
@@ -183,66 +157,27 @@ extern "C" int iss_adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, 
         return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: the jobs hold %lld blocks, not %lld", (long long)blocks,
                         (long long)nblocks_total);
     if (blocks > 0x7fffffffLL) return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: %lld blocks in one call", (long long)blocks);
-    IssRsPlan plan;
-    int rc = iss_resample_plan(c, rjobs.data(), (int32_t)rjobs.size(), stage, nsig, ranges, "iss_adpcm_decode", plan);
-    if (rc) return rc;
-    if (n_signal >= 0) {
-        rc = iss_reserve(c, c->sig, (size_t)nsig * 2 + 16);
-        if (rc) return rc;
-        if (nsig > 0) ISS_HIP(c, hipMemsetAsync(c->sig.p, 0, (size_t)nsig * 2, c->stream));
-        c->sig_ptr = c->sig.p; c->sig_kind = 1; c->sig_n = nsig;
-    }
-    c->have_feats = false; ++c->feat_epoch;
-    c->ad_stage_off = stage_off;
-    c->ad_stage_bytes = stage_bytes;
+    if ((rc = pass.commit(&c->adpcm))) return rc;
     if (blocks == 0) return ISS_OK;
-    if ((rc = iss_reserve(c, c->ad_src, (size_t)std::max<int64_t>(src_bytes, 16)))) return rc;
-    if ((rc = iss_reserve(c, c->ad_jobs, dev.size() * sizeof(AdJobDev)))) return rc;
-    if ((rc = iss_reserve(c, c->ad_status, (size_t)blocks * 4))) return rc;
-    if ((rc = iss_reserve(c, c->ad_stage, (size_t)std::max<int64_t>(stage, 16)))) return rc;
-    iss_prof_begin(c, ISS_PROF_OTHER, 0.0);
-    iss_prof_inst(c, "adpcm_h2d(%lld B)", (long long)src_bytes);
-    ISS_HIP(c, hipMemcpyAsync(c->ad_src.p, src, (size_t)src_bytes, hipMemcpyHostToDevice, c->stream));
-    iss_prof_end(c);
-    void* pinned = nullptr;
-    int slot = -1;
-    if ((rc = iss_stage_host(c, dev.data(), dev.size() * sizeof(AdJobDev), &pinned, &slot))) return rc;
-    ISS_HIP(c, hipMemcpyAsync(c->ad_jobs.p, pinned, dev.size() * sizeof(AdJobDev), hipMemcpyHostToDevice, c->stream));
-    iss_stage_mark(c, slot);
+    if ((rc = pass.upload(c->adpcm, src, src_bytes, (size_t)std::max<int64_t>(src_bytes, 16), dev.data(), dev.size() * sizeof(AdJobDev),
+                          blocks)))
+        return rc;
     if (lds + 1024 > 64 * 1024)                        // (the kernel's static LDS, 256 bytes, counts towards the 64 KiB default)
         ISS_HIP(c, hipFuncSetAttribute((const void*)adpcm_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     iss_prof_begin(c, ISS_PROF_FRONTEND, 0.0);
     iss_prof_inst(c, "adpcm_decode_kernel");
     hipLaunchKernelGGL(adpcm_decode_kernel, dim3((unsigned)blocks), dim3(AD_THREADS), (size_t)lds, c->stream,
-                       (const uint8_t*)c->ad_src.p, (const AdJobDev*)c->ad_jobs.p, (int)dev.size(), (int16_t*)c->sig.p,
-                       (uint8_t*)c->ad_stage.p, (int32_t*)c->ad_status.p);
+                       (const uint8_t*)c->adpcm.src.p, (const AdJobDev*)c->adpcm.rows.p, (int)dev.size(), (int16_t*)c->sig.p,
+                       (uint8_t*)c->adpcm.stage.p, (int32_t*)c->adpcm.status.p);
     ISS_HIP(c, hipGetLastError());
     iss_prof_end(c);
-    ISS_HIP(c, hipMemcpyAsync(status_out, c->ad_status.p, (size_t)blocks * 4, hipMemcpyDeviceToHost, c->stream));
-    c->ad_launches += 1;
-    c->ad_blocks_done += blocks;
-    if (!rjobs.empty()) return iss_resample_launch(c, (const uint8_t*)c->ad_stage.p, plan);
-    return ISS_OK;
+    return pass.finish(c->adpcm, status_out, blocks);
 }
 
 extern "C" int iss_adpcm_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {
-    if (!c || (!out && bytes > 0)) return iss_fail(c, ISS_EINVAL, "iss_adpcm_get_stage: bad argument");
-    if (job < 0 || job >= (int32_t)c->ad_stage_off.size() || c->ad_stage_off[(size_t)job] < 0)
-        return iss_fail(c, ISS_EINVAL, "iss_adpcm_get_stage: job %d of the last iss_adpcm_decode did not go to the staging buffer", job);
-    if (bytes != c->ad_stage_bytes[(size_t)job])
-        return iss_fail(c, ISS_EINVAL, "iss_adpcm_get_stage: job %d holds %lld bytes, not %lld", job,
-                        (long long)c->ad_stage_bytes[(size_t)job], (long long)bytes);
-    ISS_HIP(c, hipSetDevice(c->device));
-    if (bytes > 0)
-        ISS_HIP(c, hipMemcpyAsync(out, (const uint8_t*)c->ad_stage.p + c->ad_stage_off[(size_t)job], (size_t)bytes,
-                                  hipMemcpyDeviceToHost, c->stream));
-    ISS_HIP(c, hipStreamSynchronize(c->stream));
-    return ISS_OK;
+    return c ? iss_codec_get_stage(c, c->adpcm, job, out, bytes) : iss_fail(c, ISS_EINVAL, "iss_adpcm_get_stage: bad argument");
 }
 
 extern "C" int iss_adpcm_stats(iss_ctx* c, int64_t* launches, int64_t* blocks) {
-    if (!c) return ISS_EINVAL;
-    if (launches) *launches = c->ad_launches;
-    if (blocks) *blocks = c->ad_blocks_done;
-    return ISS_OK;
+    return iss_get_counters(c ? &c->adpcm.count : nullptr, launches, blocks);
 }

@@ -11,7 +11,7 @@
 // the output width, which is exact for left/side and side/right and lossless for mid, which always fits) and read back.
 // LPC / FIXED history and coefficients live in registers: the residual loop is a template on the order bucket (4, 8, 16, 32)
 // and on the sum width, so no register array is indexed at run time.
-#include "iss_internal.h"
+#include "decode_pass.h"
 #include <algorithm>
 #include <cstring>
 
@@ -508,19 +508,11 @@ extern "C" int iss_flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, c
     if (!c || njobs < 0 || (njobs > 0 && (!jobs || !frames || !status_out)) || src_bytes < 0 || (!src && src_bytes > 0) ||
         nframes < 0)
         return iss_fail(c, ISS_EINVAL, "iss_flac_decode: bad argument");
-    ISS_HIP(c, hipSetDevice(c->device));
-    int64_t nsig = n_signal;
-    if (n_signal < 0) {
-        if (c->sig_kind != 1 || c->sig_ptr != c->sig.p)
-            return iss_fail(c, ISS_ESTATE, "iss_flac_decode: n_signal < 0 needs a PCM16 signal uploaded by iss_signal_pcm16");
-        nsig = c->sig_n;
-    }
+    IssDecodePass pass;
+    int rc = pass.begin(c, "iss_flac_decode", n_signal, njobs);
+    if (rc) return rc;
     std::vector<FlacFrameDev> dev((size_t)nframes);
-    std::vector<iss_resample_job> rjobs;
-    std::vector<std::pair<int64_t, int64_t>> ranges;
-    std::vector<int64_t> stage_off((size_t)njobs, -1), stage_bytes((size_t)njobs, 0);
     std::vector<char> used((size_t)nframes, 0);
-    int64_t stage = 0;
     for (int32_t j = 0; j < njobs; ++j) {
         const iss_flac_job& J = jobs[j];
         if (J.channels < 1 || J.channels > 8 || (J.bps != 8 && J.bps != 16 && J.bps != 24))
@@ -542,31 +534,9 @@ extern "C" int iss_flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, c
         const int esz = wide ? 4 : 2;
         bool to_sig;
         int64_t base;
-        if (J.output == ISS_FLAC_TO_SIGNAL) {
-            if (J.channels != 1 || wide)
-                return iss_fail(c, ISS_EINVAL, "iss_flac_decode: job %d: only mono 8/16-bit sources go to the signal", j);
-            if (J.dst_offset < 0 || J.dst_offset > nsig - J.frames_total)
-                return iss_fail(c, ISS_EINVAL, "iss_flac_decode: job %d: output [%lld, %lld) outside the %lld-sample signal", j,
-                                (long long)J.dst_offset, (long long)(J.dst_offset + J.frames_total), (long long)nsig);
-            ranges.push_back({J.dst_offset, J.dst_offset + J.frames_total});
-            to_sig = true;
-            base = J.dst_offset * 2;
-        } else if (J.output == ISS_FLAC_TO_STAGE) {
-            to_sig = false;
-            base = stage;
-            stage_off[(size_t)j] = stage;
-            stage_bytes[(size_t)j] = J.frames_total * J.channels * esz;
-            stage += (stage_bytes[(size_t)j] + 15) / 16 * 16;
-            if (J.filter >= 0) {
-                iss_resample_job r{};
-                r.src_offset = base; r.frames_in = J.frames_total; r.channels = J.channels;
-                r.format = wide ? ISS_RS_I32 : ISS_RS_I16; r.filter = J.filter; r.dst_offset = J.dst_offset;
-                r.frames_out = J.frames_out;
-                rjobs.push_back(r);
-            }
-        } else {
-            return iss_fail(c, ISS_EINVAL, "iss_flac_decode: job %d: bad output %d", j, J.output);
-        }
+        if ((rc = pass.place(j, {J.output, J.filter, J.dst_offset, J.frames_out}, J.frames_total, J.channels, esz,
+                             J.channels == 1 && !wide, "mono 8/16-bit", to_sig, base)))
+            return rc;
         for (int64_t k = J.frame_begin; k < J.frame_begin + J.nframes; ++k) {
             const iss_flac_frame& f = frames[k];
             FlacFrameDev& d = dev[(size_t)k];
@@ -579,64 +549,25 @@ extern "C" int iss_flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, c
     }
     for (int64_t k = 0; k < nframes; ++k)
         if (!used[(size_t)k]) return iss_fail(c, ISS_EINVAL, "iss_flac_decode: frame row %lld belongs to no job", (long long)k);
-    IssRsPlan plan;
-    int rc = iss_resample_plan(c, rjobs.data(), (int32_t)rjobs.size(), stage, nsig, ranges, "iss_flac_decode", plan);
-    if (rc) return rc;
-    if (n_signal >= 0) {
-        rc = iss_reserve(c, c->sig, (size_t)nsig * 2 + 16);
-        if (rc) return rc;
-        if (nsig > 0) ISS_HIP(c, hipMemsetAsync(c->sig.p, 0, (size_t)nsig * 2, c->stream));
-        c->sig_ptr = c->sig.p; c->sig_kind = 1; c->sig_n = nsig;
-    }
-    c->have_feats = false; ++c->feat_epoch;
-    c->flac_stage_off = stage_off;
-    c->flac_stage_bytes = stage_bytes;
+    if ((rc = pass.commit(&c->flac))) return rc;
     if (nframes == 0) return ISS_OK;
-    if ((rc = iss_reserve(c, c->flac_src, (size_t)(src_bytes + 16) / 4 * 4 + 16))) return rc;
-    if ((rc = iss_reserve(c, c->flac_frames, dev.size() * sizeof(FlacFrameDev)))) return rc;
-    if ((rc = iss_reserve(c, c->flac_status, (size_t)nframes * 4))) return rc;
-    if ((rc = iss_reserve(c, c->flac_stage, (size_t)std::max<int64_t>(stage, 16)))) return rc;
-    iss_prof_begin(c, ISS_PROF_OTHER, 0.0);
-    iss_prof_inst(c, "flac_h2d(%lld B)", (long long)src_bytes);
-    if (src_bytes > 0) ISS_HIP(c, hipMemcpyAsync(c->flac_src.p, src, (size_t)src_bytes, hipMemcpyHostToDevice, c->stream));
-    iss_prof_end(c);
-    void* pinned = nullptr;
-    int slot = -1;
-    if ((rc = iss_stage_host(c, dev.data(), dev.size() * sizeof(FlacFrameDev), &pinned, &slot))) return rc;
-    ISS_HIP(c, hipMemcpyAsync(c->flac_frames.p, pinned, dev.size() * sizeof(FlacFrameDev), hipMemcpyHostToDevice, c->stream));
-    iss_stage_mark(c, slot);
+    if ((rc = pass.upload(c->flac, src, src_bytes, (size_t)(src_bytes + 16) / 4 * 4 + 16, dev.data(), dev.size() * sizeof(FlacFrameDev),
+                          nframes)))
+        return rc;
     iss_prof_begin(c, ISS_PROF_FRONTEND, 0.0);
     iss_prof_inst(c, "flac_decode_kernel");
     hipLaunchKernelGGL(flac_decode_kernel, dim3((unsigned)((nframes + FL_THREADS - 1) / FL_THREADS)), dim3(FL_THREADS), 0, c->stream,
-                       (const uint8_t*)c->flac_src.p, (const FlacFrameDev*)c->flac_frames.p, nframes, (int16_t*)c->sig.p,
-                       (uint8_t*)c->flac_stage.p, (int32_t*)c->flac_status.p);
+                       (const uint8_t*)c->flac.src.p, (const FlacFrameDev*)c->flac.rows.p, nframes, (int16_t*)c->sig.p,
+                       (uint8_t*)c->flac.stage.p, (int32_t*)c->flac.status.p);
     ISS_HIP(c, hipGetLastError());
     iss_prof_end(c);
-    ISS_HIP(c, hipMemcpyAsync(status_out, c->flac_status.p, (size_t)nframes * 4, hipMemcpyDeviceToHost, c->stream));
-    c->flac_launches += 1;
-    c->flac_frames_done += nframes;
-    if (!rjobs.empty()) return iss_resample_launch(c, (const uint8_t*)c->flac_stage.p, plan);
-    return ISS_OK;
+    return pass.finish(c->flac, status_out, nframes);
 }
 
 extern "C" int iss_flac_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {
-    if (!c || (!out && bytes > 0)) return iss_fail(c, ISS_EINVAL, "iss_flac_get_stage: bad argument");
-    if (job < 0 || job >= (int32_t)c->flac_stage_off.size() || c->flac_stage_off[(size_t)job] < 0)
-        return iss_fail(c, ISS_EINVAL, "iss_flac_get_stage: job %d of the last iss_flac_decode did not go to the staging buffer", job);
-    if (bytes != c->flac_stage_bytes[(size_t)job])
-        return iss_fail(c, ISS_EINVAL, "iss_flac_get_stage: job %d holds %lld bytes, not %lld", job,
-                        (long long)c->flac_stage_bytes[(size_t)job], (long long)bytes);
-    ISS_HIP(c, hipSetDevice(c->device));
-    if (bytes > 0)
-        ISS_HIP(c, hipMemcpyAsync(out, (const uint8_t*)c->flac_stage.p + c->flac_stage_off[(size_t)job], (size_t)bytes,
-                                  hipMemcpyDeviceToHost, c->stream));
-    ISS_HIP(c, hipStreamSynchronize(c->stream));
-    return ISS_OK;
+    return c ? iss_codec_get_stage(c, c->flac, job, out, bytes) : iss_fail(c, ISS_EINVAL, "iss_flac_get_stage: bad argument");
 }
 
 extern "C" int iss_flac_stats(iss_ctx* c, int64_t* launches, int64_t* frames) {
-    if (!c) return ISS_EINVAL;
-    if (launches) *launches = c->flac_launches;
-    if (frames) *frames = c->flac_frames_done;
-    return ISS_OK;
+    return iss_get_counters(c ? &c->flac.count : nullptr, launches, frames);
 }

@@ -78,8 +78,8 @@ extern "C" void iss_destroy(iss_ctx* c) {
     for (void* p : singles) if (p) (void)hipFree(p);
     DevBuf* bufs[] = {&c->sig, &c->mspec, &c->loge, &c->d_winrow, &c->d_stats, &c->d_finite, &c->d_out, &c->d_in, &c->raw1, &c->d_rowflag, &c->d_lfinite,
                       &c->vbx_sig, &c->vbx_dither, &c->vbx_fb, &c->vbx_out, &c->vbx_meta, &c->rs_src, &c->rs_jobs,
-                      &c->flac_src, &c->flac_frames, &c->flac_status, &c->flac_stage,
-                      &c->ad_src, &c->ad_jobs, &c->ad_status, &c->ad_stage};
+                      &c->flac.src, &c->flac.rows, &c->flac.status, &c->flac.stage,
+                      &c->adpcm.src, &c->adpcm.rows, &c->adpcm.status, &c->adpcm.stage};
     for (DevBuf* b : bufs) free_buf(*b);
     for (auto& b : c->act) free_buf(b);
     for (auto& f : c->rs_filters) if (f.d_taps) (void)hipFree(f.d_taps);
@@ -116,8 +116,8 @@ extern "C" int iss_scribble(iss_ctx* c, uint32_t word) {
     ISS_HIP(c, hipStreamSynchronize(c->stream));
     std::vector<DevBuf*> bufs = {&c->raw1, &c->d_stats, &c->d_finite, &c->d_lfinite, &c->d_out, &c->d_in, &c->d_winrow, &c->d_rowflag,
                                  &c->vbx_fb, &c->vbx_meta, &c->vbx_sig, &c->rs_src, &c->rs_jobs,
-                                 &c->flac_src, &c->flac_frames, &c->flac_status, &c->flac_stage,
-                                 &c->ad_src, &c->ad_jobs, &c->ad_status, &c->ad_stage};
+                                 &c->flac.src, &c->flac.rows, &c->flac.status, &c->flac.stage,
+                                 &c->adpcm.src, &c->adpcm.rows, &c->adpcm.status, &c->adpcm.stage};
     for (auto& b : c->act) bufs.push_back(&b);
     for (DevBuf* b : bufs) {
         if (!b->p) continue;
@@ -166,13 +166,18 @@ extern "C" int iss_sidekit_tables(iss_ctx* c, const double* window400, const flo
 }
 
 // ---------------------------------------------------------------- signal ingest
+void iss_set_signal(iss_ctx* c, const void* ptr, int kind, int64_t n) {
+    c->sig_ptr = ptr; c->sig_kind = kind; c->sig_n = n;
+    c->have_feats = false; ++c->feat_epoch;
+}
+
 static int put_signal(iss_ctx* c, const void* host, int64_t n, size_t esz, int kind) {
     if (!c || (!host && n > 0) || n < 0) return iss_fail(c, ISS_EINVAL, "iss_signal: bad argument");
     ISS_HIP(c, hipSetDevice(c->device));
     int rc = iss_reserve(c, c->sig, (size_t)n * esz + 16);
     if (rc) return rc;
     if (n > 0) ISS_HIP(c, hipMemcpyAsync(c->sig.p, host, (size_t)n * esz, hipMemcpyHostToDevice, c->stream));
-    c->sig_ptr = c->sig.p; c->sig_kind = kind; c->sig_n = n; c->have_feats = false; ++c->feat_epoch;
+    iss_set_signal(c, c->sig.p, kind, n);
     return ISS_OK;
 }
 extern "C" int iss_signal_pcm16(iss_ctx* c, const int16_t* pcm, int64_t n) { return put_signal(c, pcm, n, 2, 1); }
@@ -195,7 +200,7 @@ extern "C" int iss_signal_pcm16_device_stream(iss_ctx* c, const void* dev, int64
     if (!c->order_ev) ISS_HIP(c, hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming));
     ISS_HIP(c, hipEventRecord(c->order_ev, (hipStream_t)producer_stream));
     ISS_HIP(c, hipStreamWaitEvent(c->stream, c->order_ev, 0));
-    c->sig_ptr = dev; c->sig_kind = 1; c->sig_n = n; c->have_feats = false; ++c->feat_epoch;
+    iss_set_signal(c, dev, 1, n);
     return ISS_OK;
 }
 extern "C" int iss_signal_pcm16_device(iss_ctx* c, const void* dev, int64_t n) {

@@ -19,6 +19,15 @@ struct DevBuf {
 
 struct ConvOp;   // cnn.hip
 
+struct IssCounters { int64_t launches = 0, units = 0; };   // what the *_stats entry points report (iss_get_counters)
+// A coded decoder's device buffers and what its last call left (decode_pass.h).  A new format adds one member to iss_ctx
+struct IssCodec {
+    const char* name;                                  // "flac": iss_<name>_decode, <name>_h2d
+    DevBuf src, rows, status, stage;                   // payload, row table, per-unit status, staging buffer of the last call
+    std::vector<int64_t> stage_off, stage_bytes;       // per job of the last call (-1: not staged)
+    IssCounters count;                                 // launches, units (frames / blocks) decoded
+};
+
 // A network's device parameter arrays once another net shares them (iss_cnn_load_shared): freed with their last user.
 struct IssParamArrays {
     float* blob = nullptr;
@@ -86,23 +95,16 @@ struct iss_ctx {
     std::vector<RsFilter> rs_filters;
     std::map<std::pair<int32_t, int32_t>, int32_t> rs_filter_id;
     DevBuf rs_src, rs_jobs;
-    int64_t rs_launches = 0, rs_jobs_done = 0;
+    IssCounters rs_count;                 // launches, jobs
 
-    // FLAC decoder (flac.hip): compressed bytes, frame rows, per-frame status and the staging buffer of the last call
-    DevBuf flac_src, flac_frames, flac_status, flac_stage;
-    std::vector<int64_t> flac_stage_off, flac_stage_bytes;   // per job of the last call (-1: not staged)
-    int64_t flac_launches = 0, flac_frames_done = 0;
-
-    // IMA ADPCM decoder (adpcm.hip): stored blocks, job rows, per-block status and the staging buffer of the last call
-    DevBuf ad_src, ad_jobs, ad_status, ad_stage;
-    std::vector<int64_t> ad_stage_off, ad_stage_bytes;       // per job of the last call (-1: not staged)
-    int64_t ad_launches = 0, ad_blocks_done = 0;
+    // the coded decoders: FLAC (flac.hip: rows = frames) and IMA ADPCM (adpcm.hip: rows = jobs, status per block)
+    IssCodec flac{"flac"}, adpcm{"adpcm"};
 
     // resident features
     DevBuf mspec, loge;
     int32_t T = 0;
     bool have_feats = false;
-    uint64_t feat_epoch = 1;              // bumped wherever have_feats, sig_* or T is set: what was derived from the features is stale
+    uint64_t feat_epoch = 1;              // bumped wherever have_feats, sig_* (iss_set_signal) or T is set: what was derived from the features is stale
 
     // dead windows (cnn.hip, cnn_probs_impl): per resident log-mel row the lowest column holding a non-finite value (24: none),
     // read back once per feature set, and per network width w the prefix count of rows whose flag is < w
@@ -165,6 +167,7 @@ struct iss_ctx {
 
 int iss_fail(iss_ctx* c, int code, const char* fmt, ...);
 int iss_reserve(iss_ctx* c, DevBuf& b, size_t bytes);
+void iss_set_signal(iss_ctx* c, const void* ptr, int kind, int64_t n);   // the resident signal is now this; features are stale
 int iss_stage_host(iss_ctx* c, const void* src, size_t bytes, void** pinned_out, int* slot_out);   // copy into a pinned staging buffer
 void iss_stage_mark(iss_ctx* c, int slot);                                                       // record 'consumed' on the stream
 int iss_rowflag_host(iss_ctx* c, size_t rows);                                                   // page-locked h_rowflag of >= rows bytes

@@ -15,7 +15,7 @@
 //   3. thread t computes outputs i0 + t + 256*r: first input j0 = ceil((i*down - hl)/up), its tap i*down + hl - j0*up, then
 //      every `up`-th tap down to 0, summed in ascending j with separate multiply and add, then rint * 32768 and saturation
 // All index arithmetic is 64-bit: i*down passes 2^31 after ~5 minutes of 44.1 kHz output.
-#include "iss_internal.h"
+#include "decode_pass.h"
 #include <algorithm>
 #include <cstring>
 
@@ -259,14 +259,8 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, int32_t njobs, i
 int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& plan) {
     const std::vector<RsJobDev>& dj = plan.dj;
     if (dj.empty()) return ISS_OK;
-    int rc = iss_reserve(c, c->rs_jobs, dj.size() * sizeof(RsJobDev));
+    int rc = iss_upload_rows(c, c->rs_jobs, dj.data(), dj.size() * sizeof(RsJobDev));
     if (rc) return rc;
-    void* pinned = nullptr;
-    int slot = -1;
-    rc = iss_stage_host(c, dj.data(), dj.size() * sizeof(RsJobDev), &pinned, &slot);
-    if (rc) return rc;
-    ISS_HIP(c, hipMemcpyAsync(c->rs_jobs.p, pinned, dj.size() * sizeof(RsJobDev), hipMemcpyHostToDevice, c->stream));
-    iss_stage_mark(c, slot);
     bool ext = false;                                  // a format newer than the WAV five: the instantiation that reads them all
     for (const RsJobDev& d : dj) ext = ext || d.fmt > ISS_RS_F64;
     auto kernel = ext ? resample_kernel<true> : resample_kernel<false>;
@@ -280,8 +274,8 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
                        dev_src, (const RsJobDev*)c->rs_jobs.p, (int)dj.size(), (int16_t*)c->sig.p);
     ISS_HIP(c, hipGetLastError());
     iss_prof_end(c);
-    c->rs_launches += 1;
-    c->rs_jobs_done += (int64_t)dj.size();
+    c->rs_count.launches += 1;
+    c->rs_count.units += (int64_t)dj.size();
     return ISS_OK;
 }
 
@@ -289,36 +283,15 @@ extern "C" int iss_resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes
                                   int64_t n_signal) {
     if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0))
         return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: bad argument");
-    ISS_HIP(c, hipSetDevice(c->device));
-    int64_t nsig = n_signal;
-    if (n_signal < 0) {
-        if (c->sig_kind != 1 || c->sig_ptr != c->sig.p)
-            return iss_fail(c, ISS_ESTATE, "iss_resample_pcm16: n_signal < 0 needs a PCM16 signal uploaded by iss_signal_pcm16");
-        nsig = c->sig_n;
-    }
-    IssRsPlan plan;
-    int rc = iss_resample_plan(c, jobs, njobs, src_bytes, nsig, {}, "iss_resample_pcm16", plan);
-    if (rc) return rc;
-    if (n_signal >= 0) {                                   // a signal of its own, zero wherever no job writes
-        rc = iss_reserve(c, c->sig, (size_t)nsig * 2 + 16);
-        if (rc) return rc;
-        if (nsig > 0) ISS_HIP(c, hipMemsetAsync(c->sig.p, 0, (size_t)nsig * 2, c->stream));
-        c->sig_ptr = c->sig.p; c->sig_kind = 1; c->sig_n = nsig;
-    }
-    c->have_feats = false; ++c->feat_epoch;
+    IssDecodePass pass;
+    int rc = pass.begin(c, "iss_resample_pcm16", n_signal, 0);
+    pass.rjobs.assign(jobs, jobs + njobs); pass.stage = src_bytes;      // no placement: the caller's rows over the caller's bytes
+    if (rc || (rc = pass.commit(nullptr))) return rc;
     if (njobs == 0) return ISS_OK;
-    rc = iss_reserve(c, c->rs_src, (size_t)std::max<int64_t>(src_bytes, 16));
-    if (rc) return rc;
-    iss_prof_begin(c, ISS_PROF_OTHER, 0.0);
-    iss_prof_inst(c, "resample_h2d(%lld B)", (long long)src_bytes);
-    if (src_bytes > 0) ISS_HIP(c, hipMemcpyAsync(c->rs_src.p, src, (size_t)src_bytes, hipMemcpyHostToDevice, c->stream));
-    iss_prof_end(c);
-    return iss_resample_launch(c, (const uint8_t*)c->rs_src.p, plan);
+    if ((rc = iss_upload_payload(c, c->rs_src, "resample", src, src_bytes, (size_t)std::max<int64_t>(src_bytes, 16)))) return rc;
+    return iss_resample_launch(c, (const uint8_t*)c->rs_src.p, pass.plan);
 }
 
 extern "C" int iss_resample_stats(iss_ctx* c, int64_t* launches, int64_t* jobs) {
-    if (!c) return ISS_EINVAL;
-    if (launches) *launches = c->rs_launches;
-    if (jobs) *jobs = c->rs_jobs_done;
-    return ISS_OK;
+    return iss_get_counters(c ? &c->rs_count : nullptr, launches, jobs);
 }

@@ -136,18 +136,23 @@ def test_adpcm_kernel_largest_blocks(sctx):
 
 def _pack(ctx, sounds, kinds, pad_before=0):
     """Blocks of every file end to end (16-byte aligned, after pad_before zero bytes), jobs into a packed uploaded signal
-    (gaps of 160 samples filled with a marker) -> (src, jobs, nblocks, signal, dst offsets)."""
+    (gaps of 160 samples filled with a marker; kind 'stage': decoded to the staging buffer only, no room in the signal)
+    -> (src, jobs, nblocks, signal, dst offsets)."""
     src, jobs, offs = [np.zeros(pad_before, np.uint8)], [], []
     pos, bbeg, dpos = pad_before, 0, 0
     for s, kind in zip(sounds, kinds):
-        a = sndfmt.AdpcmSource(s, kind)
         offs.append(dpos)
-        jobs.append(a.job(ctx, pos, bbeg, dpos))
+        if kind == 'stage':                                             # staged only (no Source asks for it): nothing in the signal
+            jobs.append((pos, bbeg, s.nblocks, s.n, s.ch, s.block_align, _native.ADPCM_TO_STAGE, -1, 0, 0))
+        else:
+            a = sndfmt.AdpcmSource(s, kind)
+            jobs.append(a.job(ctx, pos, bbeg, dpos))
+            dpos += a.size
         pad = -s.data.size % 16
         src += [s.data, np.zeros(pad, np.uint8)]
         pos += s.data.size + pad
         bbeg += s.nblocks
-        dpos += a.size + 160
+        dpos += 160
     return np.concatenate(src), jobs, bbeg, np.full(dpos, 12345, dtype=np.int16), offs
 
 
@@ -157,9 +162,9 @@ def test_adpcm_ragged_batch_one_launch(sctx):
         sr, ch, align = [(16000, 1, 256), (8000, 1, 256), (8000, 2, 512), (44100, 2, 2048), (16000, 1, 1024), (11025, 3, 516)][k % 6]
         x = wavgen.make_signal(1500 + 977 * k, ch, 200 + k)
         s, twin = _sound(x, 'ima', False, sr, align, name=f'r{k}.wav')
-        kind = 'pcm' if (sr, ch) == (16000, 1) else 'resample'
+        kind = 'stage' if k % 12 == 11 else 'pcm' if (sr, ch) == (16000, 1) else 'resample'
         sounds.append(s); kinds.append(kind)
-        wants.append(twin if kind == 'pcm' else R.resample_ref(twin, sr))
+        wants.append(R.resample_ref(twin, sr) if kind == 'resample' else twin)
     src, jobs, nblocks, sig, offs = _pack(sctx, sounds, kinds)
     sctx.set_signal(sig)
     l0, b0 = sctx.adpcm_stats()
@@ -170,9 +175,12 @@ def test_adpcm_ragged_batch_one_launch(sctx):
     assert sctx.resample_stats()[0] == r0 + 1
     assert not st.any()
     covered = np.zeros(sig.size, bool)
-    for w, o in zip(wants, offs):
-        np.testing.assert_array_equal(got[o:o + w.size], w)
-        covered[o:o + w.size] = True
+    for j, (s, kind, w, o) in enumerate(zip(sounds, kinds, wants, offs)):
+        if kind == 'stage':
+            np.testing.assert_array_equal(sctx.adpcm_get_stage(j, s.n, s.ch), w)
+        else:
+            np.testing.assert_array_equal(got[o:o + w.size], w)
+            covered[o:o + w.size] = True
     assert np.all(got[~covered] == 12345)
 
 
