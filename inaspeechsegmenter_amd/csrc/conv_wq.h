@@ -32,6 +32,7 @@
 // rows >= tmr of a wave's last row block are computed and dropped.
 //
 // Compiled for the one combination the dominant launch uses: first-layer-fused, unpadded, relu + 2 x 2 max-pool epilogue.
+// The pieces shared with conv_ws.h, conv_wq3.h and conv_wq3h.h are in conv_wq_parts.h.
 #pragma once
 #include "conv_ws.h"
 
@@ -71,27 +72,16 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     const int li = lane & 31, lh = lane >> 5;
     const int M = (int)p.M;
     const int TMR = p.tmr;                           // rows per tile (<= 512, multiple of 4)
-    const int ntiles = (M + TMR - 1) / TMR;
-    const int ngroups = (ntiles + G - 1) / G;
+    const Tiles tl(M, TMR);
+    const int ntiles = tl.n, ngroups = tl.groups(G);
     int grp = (int)blockIdx.x;
     if (grp >= ngroups) return;
 
     // ---- geometry (parameters through the kernel-argument pointer, reciprocals from the host)
-    auto geo_args = [&]() {
-        KArg q = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(q));
-        GeoArgs ga;
-        ga.H = q->H; ga.W = q->W; ga.Hq = q->Hq; ga.Wq = q->Wq; ga.ph = q->ph; ga.pw = q->pw; ga.pp = q->pp;
-        ga.sh = q->sh; ga.sw = q->sw; ga.pt_ = q->pt_; ga.pl_ = q->pl_;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { ga.dv_mul[i] = q->dv_mul[i]; ga.dv_sh[i] = q->dv_sh[i]; }
-        return ga;
-    };
     struct TGeo { int p_lo, need, fy, fx, wb; };     // uniform per tile: first pixel, pixels needed, (y, x) of it, its window
-    auto clamp_tile = [&](int t) { return t < ntiles ? t : ntiles - 1; };
     auto geo_uniform = [&](const GeoArgs& ga, int tile) {
         TGeo u;
-        const int m0 = clamp_tile(tile) * TMR;
+        const int m0 = tl.clamp(tile) * TMR;
         int b, oy, ox;
         map_row32(ga, m0, b, oy, ox);
         u.p_lo = (b * ga.H + oy) * ga.W + ox;
@@ -105,7 +95,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     // LDS byte address of the lane's first tap in footprint `fb` for EVEN filter rows: pixel base + the 32-byte half that holds
     // this lane's k-half on that pixel's row (half = k-half ^ row parity); odd filter rows use this address ^ 32
     auto geo_lane = [&](const GeoArgs& ga, int tile, int rb, const TGeo& u, int fb) {
-        const int m0 = clamp_tile(tile) * TMR;
+        const int m0 = tl.clamp(tile) * TMR;
         const int m = m0 + (wv * 4 + rb) * 32 + li;
         int b, oy, ox;
         map_row32(ga, m < M ? m : m0, b, oy, ox);
@@ -113,30 +103,13 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
         const int hi = WQ_PIX - 1 - ((KH - 1) * ga.W + (KW - 1));       // keeps every tap of a row >= M (or >= tmr) inside the buffer
         return sF0 + (unsigned)(fb * WQ_FB) + (unsigned)((lp < 0 ? 0 : (lp > hi ? hi : lp)) * WQ_ROW) + (unsigned)(((lh ^ oy) & 1) << 5);
     };
-    struct Win { int wr0, wr1; float mean0, mean1, sd0, sd1; int live0, live1; };
     int nwin;
     { const int spp = p.Hq * p.Wq * p.pp; nwin = M / spp; }
-    auto windows_of = [&](int b) {                   // loads only: nothing here may USE the values (see conv_fp.h)
-        Win w;
-        const unsigned b0 = (unsigned)(b < nwin ? b : nwin - 1), b1 = (unsigned)(b + 1 < nwin ? b + 1 : nwin - 1);
-        w.wr0 = p.win_row[b0]; w.mean0 = p.stats[2u * b0]; w.sd0 = p.stats[2u * b0 + 1u]; w.live0 = p.finite[b0];
-        w.wr1 = p.win_row[b1]; w.mean1 = p.stats[2u * b1]; w.sd1 = p.stats[2u * b1 + 1u]; w.live1 = p.finite[b1];
-        return w;
-    };
-    auto settle = [&](const Win& w) {
-        Win s;
-        s.wr0 = __builtin_amdgcn_readfirstlane(w.wr0); s.wr1 = __builtin_amdgcn_readfirstlane(w.wr1);
-        s.mean0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w.mean0)));
-        s.mean1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w.mean1)));
-        s.sd0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w.sd0)));
-        s.sd1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w.sd1)));
-        s.live0 = __builtin_amdgcn_readfirstlane(w.live0); s.live1 = __builtin_amdgcn_readfirstlane(w.live1);
-        return s;
-    };
+    auto windows_of = [&](int b) { return issk::windows_of(p, nwin, b); };
 
     // ---- weights of one 16-channel chunk: NT tiles of 4 KB = 4 NT pieces of 1 KB; wave w moves pieces w, w + 4, ...:
     // piece i has (half, plane) = (i & 1, (i >> 1) & 1) = (w & 1, w >> 1) for every one of a wave's pieces, tap = i >> 2.
-    // Slot permutation on the source side as in conv_ws.h (conflict-free B reads).
+    // Slot permutation on the source side, and `bread` below: the weight-slot contract of conv_wq_parts.h.
     const int w_half = wv & 1, w_plane = (wv >> 1) & 1;
     unsigned boff_w;
     {
@@ -254,9 +227,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     struct BLo { bf16x8 l0, l1; };                   // lo plane: ONE set, read in the first slots of the step that uses it from slot 16
                                                      // on; the last tap's (read in front of the block's barrier) has a set of its own
     const unsigned wstep2 = (unsigned)(2 * p.W * WQ_ROW);       // two filter rows down
-    auto mfma = [&](const bf16x8& a, const bf16x8& b, const floatx16& c) {
-        return mfma_x3<F16>(a, b, c);
-    };
+    auto mfma = [&](const bf16x8& a, const bf16x8& b, const floatx16& c) { return mfma_ab<false, F16>(a, b, c); };
 
     // accumulators: acc<tile><row block><column block>, named (arrays passed by reference end up in scratch)
     floatx16 c000, c001, c010, c011, c020, c021, c030, c031, c100, c101, c110, c111, c120, c121, c130, c131;
@@ -271,13 +242,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     // ---- epilogue pieces: accumulator (rb, cb) of a tile, register group g (4 consecutive rows = one pool window):
     // max over the window, + bias, relu, one dword store.  ebase = byte offset of (pooled row of the wave's first row + lh,
     // column n0 + li) in `out`; tile_rows = rows of the tile that exist (the tmr / M bounds).
-    struct Epi { const float* bias; float* out; int cout; };
-    Epi ep;
-    {
-        KArg q = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(q));
-        ep.bias = q->bias; ep.out = q->out; ep.cout = q->Cout;
-    }
+    const Epi ep = epi_args();
     float ebias0 = 0.f, ebias1 = 0.f;                // bias of columns n0 + li and n0 + 32 + li (one launch = one layer)
     if (ep.bias) { ebias0 = ep.bias[n0 + li < ep.cout ? n0 + li : 0]; ebias1 = ep.bias[n0 + 32 + li < ep.cout ? n0 + 32 + li : 0]; }
     const bool ecol0 = n0 + li < ep.cout, ecol1 = n0 + 32 + li < ep.cout;
@@ -286,8 +251,6 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     const unsigned hl_np16 = OUT_HL ? p.out_np * 16u : 0u;      // bytes per CHL plane
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(ep.out, 0, OUT_HL ? (int)(p.out_np * (unsigned)ep.cout * 4u)
                                                                                               : (int)((unsigned)(M >> 2) * (unsigned)ep.cout * 4u), 0x00020000);
-    constexpr unsigned E_INVALID = 0xFFFF0000u;      // + the largest scalar offset below (< 16 KB) stays below 2^32: no wrap-around;
-                                                     // the host keeps the output below 0xFFF00000 bytes
     const int wrow = wv * 128 + 4 * lh;              // first row of the wave's pool windows of register group 0 inside the tile
     int rowb = ep.cout * 4;                          // bytes per pooled output row
     float e_x;
@@ -352,7 +315,6 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
             return (unsigned)(((unsigned)(((n0 >> 4) + (li >> 4)) * 4 + ((li >> 3) & 1) * 2) * p.out_np + (unsigned)(tile * (TMR >> 2) + wv * 32 + lh)) * 16u + (unsigned)((li & 7) * 2));
         return col ? (unsigned)(((tile * (TMR >> 2) + wv * 32 + lh) * ep.cout + n0 + cb * 32 + li) * 4) : E_INVALID;
     };
-    auto tile_rows_of = [&](int tile) { const int r = M - tile * TMR; return tile < ntiles ? (r < TMR ? r : TMR) : 0; };
 
     // ---- prologue: geometry of the first group; its first footprint converted serially into footprint 0
     TGeo ug[G + 2];                                  // the group's tiles + the next group's first two tiles
@@ -429,7 +391,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
             const unsigned wbase = sF0 + (unsigned)((1 - t) * WQ_FB) + wofs;      // the OTHER footprint
             unsigned vb0 = E_INVALID, vb1 = E_INVALID;
             int erows = 0;
-            if (EP) { vb0 = epi_base(etile, 0); vb1 = epi_base(etile, 1); erows = tile_rows_of(etile); if (OUT_HL) { e_lim = erows - wrow; e_inv = E_INVALID; asm volatile("" : "+v"(e_inv)); } }
+            if (EP) { vb0 = epi_base(etile, 0); vb1 = epi_base(etile, 1); erows = tl.rows_of(etile); if (OUT_HL) { e_lim = erows - wrow; e_inv = E_INVALID; asm volatile("" : "+v"(e_inv)); } }
 #pragma unroll
             for (int v = 0; v < NT; ++v) {
                 const int cs = (v + t) & 1, ns = cs ^ 1;
@@ -448,15 +410,12 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
 #pragma unroll
                 for (int s = 0; s < 24; ++s) {
                     const int term = s >> 3, rb = (s >> 1) & 3, cb = s & 1;
-                    floatx16& e = rb == 0 ? (cb ? d01 : d00) : rb == 1 ? (cb ? d11 : d10) : rb == 2 ? (cb ? d21 : d20) : (cb ? d31 : d30);
+                    floatx16& e = pick8<2>(rb, cb, d00, d01, d10, d11, d20, d21, d30, d31);
                     const bf16x8& av = term == 0 ? a[cs][rb].l : a[cs][rb].h;
                     const bf16x8& bv = term == 2 ? (last ? (cb ? blast.l1 : blast.l0) : (cb ? bl.l1 : bl.l0)) : (cb ? bh[cs].h1 : bh[cs].h0);
                     __builtin_amdgcn_sched_barrier(0);
                     if (ZC && v == 0 && term == 0) {
-                        floatx16 z;
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) z[i] = 0.f;
-                        e = mfma(av, bv, z);
+                        e = mfma(av, bv, zero16());
                     } else {
                         e = mfma(av, bv, e);
                     }
@@ -549,7 +508,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
                         const int unit = (v - 1) * 3 + s / 3;                  // 0..32
                         if (unit < 32) {
                             const int erb = unit >> 3, ecb = (unit >> 2) & 1, eg = unit & 3;
-                            const floatx16& oa = erb == 0 ? (ecb ? o01 : o00) : erb == 1 ? (ecb ? o11 : o10) : erb == 2 ? (ecb ? o21 : o20) : (ecb ? o31 : o30);
+                            const floatx16& oa = pick8<2>(erb, ecb, o00, o01, o10, o11, o20, o21, o30, o31);
                             if (s % 3 == 0) epi_a(oa, eg);
                             else if (s % 3 == 1) epi_b(oa, ecb, eg);
                             else epi_c(erb, ecb, eg, vb0, vb1, erows);
@@ -560,7 +519,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
                         const int unit = (v - 1) * 3 + s / 4;
                         if (unit < 32) {
                             const int erb = unit >> 3, ecb = (unit >> 2) & 1, eg = unit & 3;
-                            const floatx16& oa = erb == 0 ? (ecb ? o01 : o00) : erb == 1 ? (ecb ? o11 : o10) : erb == 2 ? (ecb ? o21 : o20) : (ecb ? o31 : o30);
+                            const floatx16& oa = pick8<2>(erb, ecb, o00, o01, o10, o11, o20, o21, o30, o31);
                             if (s % 4 == 0) epih_a(oa, eg);
                             else if (s % 4 == 1) epih_b(oa, ecb, eg);
                             else if (s % 4 == 2) epi_s();
@@ -617,11 +576,11 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     // ---- the last group's tile 1: the only serial epilogue of the workgroup
     {
         const unsigned vb0 = epi_base(prev_tile1, 0), vb1 = epi_base(prev_tile1, 1);
-        const int erows = tile_rows_of(prev_tile1);
+        const int erows = tl.rows_of(prev_tile1);
 #pragma unroll
         for (int unit = 0; unit < 32; ++unit) {
             const int erb = unit >> 3, ecb = (unit >> 2) & 1, eg = unit & 3;
-            const floatx16& oa = erb == 0 ? (ecb ? c101 : c100) : erb == 1 ? (ecb ? c111 : c110) : erb == 2 ? (ecb ? c121 : c120) : (ecb ? c131 : c130);
+            const floatx16& oa = pick8<2>(erb, ecb, ISS_WQ_SET1);
             if (OUT_HL) { e_lim = erows - wrow; e_inv = E_INVALID; asm volatile("" : "+v"(e_inv)); epih_a(oa, eg); epih_b(oa, ecb, eg); epi_s(); epih_c(erb, ecb, eg, vb0); }
             else { epi_a(oa, eg); epi_b(oa, ecb, eg); epi_c(erb, ecb, eg, vb0, vb1, erows); }
         }

@@ -7,7 +7,8 @@
 // (three split-operand terms x 2 row blocks x 4 column blocks) with twelve fragment reads (4 A, 8 B), one per slot.
 // LDS = [9 taps x 2 column halves x 4 KB of weights = 72 KB][two footprints of 512 pixels x 64 B = 64 KB]; footprint layout,
 // running tap addresses, the single barrier per block, the weight refresh behind the last tap and the epilogue of the OTHER
-// tile's accumulators behind the MFMAs of the next block are those of conv_wq.h (read its header first).  Differences:
+// tile's accumulators behind the MFMAs of the next block are those of conv_wq.h (read conv_wq_parts.h first -- the pieces the
+// kernels share, among them the f32 epilogue pieces this kernel and conv_wq3h.h use -- then conv_wq.h's header).  Differences:
 //   * plain NHWC f32 input (no fused first layer): a slice is fetched with one clamped address and split into bf16 hi / lo;
 //   * the row-parity key of the footprint swizzle is the parity of the FLATTENED input row (sample * H + y) -- the reader knows
 //     it from its output row, the writer from (first pixel's column + pixel offset) / W;
@@ -49,28 +50,17 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
     const int li = lane & 31, lh = lane >> 5;
     const int M = (int)p.M;
     const int TMR = p.tmr;                           // rows per tile (<= 256, multiple of 4)
-    const int ntiles = (M + TMR - 1) / TMR;
-    const int ngroups = (ntiles + G - 1) / G;
+    const Tiles tl(M, TMR);
+    const int ntiles = tl.n, ngroups = tl.groups(G);
     int grp = (int)blockIdx.x;
     if (grp >= ngroups) return;
     int totpix;                                      // samples * H * W
     { const int spp = p.Hq * p.Wq * p.pp; totpix = (int)(p.img_stride / p.Cin) * (M / spp); }
 
-    auto geo_args = [&]() {
-        KArg q = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(q));
-        GeoArgs ga;
-        ga.H = q->H; ga.W = q->W; ga.Hq = q->Hq; ga.Wq = q->Wq; ga.ph = q->ph; ga.pw = q->pw; ga.pp = q->pp;
-        ga.sh = q->sh; ga.sw = q->sw; ga.pt_ = q->pt_; ga.pl_ = q->pl_;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { ga.dv_mul[i] = q->dv_mul[i]; ga.dv_sh[i] = q->dv_sh[i]; }
-        return ga;
-    };
     struct TGeo { int p_lo, need, xlo, rpar; };      // uniform per tile: first pixel, pixels needed, its column, parity of its flattened row
-    auto clamp_tile = [&](int t) { return t < ntiles ? t : ntiles - 1; };
     auto geo_uniform = [&](const GeoArgs& ga, int tile) {
         TGeo u;
-        const int m0 = clamp_tile(tile) * TMR;
+        const int m0 = tl.clamp(tile) * TMR;
         int b, oy, ox;
         map_row32(ga, m0, b, oy, ox);
         u.p_lo = (b * ga.H + oy) * ga.W + ox;
@@ -83,7 +73,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
     };
     // LDS byte address of the lane's first tap in footprint `fb` for EVEN filter rows (32-byte half = k-half ^ row parity)
     auto geo_lane = [&](const GeoArgs& ga, int tile, int rb, const TGeo& u, int fb) {
-        const int m0 = clamp_tile(tile) * TMR;
+        const int m0 = tl.clamp(tile) * TMR;
         const int m = m0 + (wv * 2 + rb) * 32 + li;
         int b, oy, ox;
         map_row32(ga, m < M ? m : m0, b, oy, ox);
@@ -155,10 +145,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
 
     struct AFr { bf16x8 h, l; };
     const unsigned wstep2 = (unsigned)(2 * p.W * WQ_ROW);
-    auto mfma = [&](const bf16x8& a, const bf16x8& b, const floatx16& c) {
-        if (TR) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(b, a, c, 0, 0, 0);
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    };
+    auto mfma = [&](const bf16x8& a, const bf16x8& b, const floatx16& c) { return mfma_ab<TR, false>(a, b, c); };
 
     // accumulators: acc<tile><row block><column block>
     floatx16 c000, c001, c002, c003, c010, c011, c012, c013, c100, c101, c102, c103, c110, c111, c112, c113;
@@ -171,16 +158,9 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
     }
 
     // ---- epilogue pieces (buffer stores: an offset beyond the tensor is dropped by the hardware)
-    struct Epi { const float* bias; float* out; int cout; };
-    Epi ep;
-    {
-        KArg q = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(q));
-        ep.bias = q->bias; ep.out = q->out; ep.cout = q->Cout;
-    }
+    const Epi ep = epi_args();
     const unsigned out_bytes = TR ? (unsigned)M * (unsigned)ep.cout * 4u : (unsigned)(M >> 1) * (unsigned)ep.cout * 4u;
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(ep.out, 0, (int)out_bytes, 0x00020000);
-    constexpr unsigned E_INVALID = 0xFFFF0000u;      // (the host keeps the output below 0xFFF00000 bytes)
     int rowb = ep.cout * 4;                          // bytes per output row
     // KIND 1: bias of the lane's columns n0 + 32 cb + li
     float ebias[4] = {0.f, 0.f, 0.f, 0.f};
@@ -194,7 +174,6 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
     e_bb[0] = e_v; e_bb[1] = e_v;
     float e_p0 = 0.f, e_p1 = 0.f;
     // KIND 0, unit (rb, cb, g): channels n0 + 32 cb + 8 g + 4 lh + {0..3} of pixel row (wv * 2 + rb) * 32 + li
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     typedef const f32x4 __attribute__((address_space(3)))* LdsRF4;
     const unsigned bias_rd = sBias + (unsigned)(lh * 16);
     auto epi0_a = [&](int unit) {                    // the bias of unit `unit` (channels 32 cb + 8 g + 4 lh + {0..3}) into set unit & 1:
@@ -202,13 +181,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
         const f32x4 t = *(LdsRF4)(bias_rd + (unsigned)((32 * cb + 8 * g) * 4));
         e_bb[unit & 1] = make_float4(t[0], t[1], t[2], t[3]);
     };
-    auto epi0_b = [&](const floatx16& acc, int unit) {         // + bias, relu
-        const int g = unit & 3;
-        const float4 e_b = e_bb[unit & 1];
-        e_v = make_float4(fmaxf(acc[4 * g] + e_b.x, 0.f), fmaxf(acc[4 * g + 1] + e_b.y, 0.f),
-                          fmaxf(acc[4 * g + 2] + e_b.z, 0.f), fmaxf(acc[4 * g + 3] + e_b.w, 0.f));
-        asm volatile("" : "+v"(e_v.x), "+v"(e_v.y), "+v"(e_v.z), "+v"(e_v.w));
-    };
+    auto epi0_b = [&](const floatx16& acc, int unit) { wq3_epi0_relu(e_v, e_bb, acc, unit); };
     // vb: byte offset of (row tile * tmr + wv * 64 + li, channel n0 + 4 lh) in `out`
     auto epi0_c = [&](int rb, int cb, int g, unsigned vb, int tile_rows) {
         int wr = wrow;
@@ -221,27 +194,13 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
         if (!X_NOEPI) __builtin_amdgcn_raw_buffer_store_b128(d, orsrc, (int)off, rb * 32 * rowb + (32 * cb + 8 * g) * 4, 0);
     };
     // KIND 1, unit (rb, cb, g): rows 8 g + 4 lh + {0..3} of the row block = two 2 x 1 pool windows, column n0 + 32 cb + li
-    auto epi1_a = [&](const floatx16& acc, int cb, int g) {
-        e_p0 = fmaxf(fmaxf(acc[4 * g], acc[4 * g + 1]) + ebias[cb], 0.f);
-        e_p1 = fmaxf(fmaxf(acc[4 * g + 2], acc[4 * g + 3]) + ebias[cb], 0.f);
-        asm volatile("" : "+v"(e_p0), "+v"(e_p1));
-    };
+    auto epi1_a = [&](const floatx16& acc, int cb, int g) { wq3_epi1_pool(e_p0, e_p1, ebias, acc, cb, g); };
     // vb: byte offset of (pooled row (tile * tmr + wv * 64) / 2 + 2 lh, column n0 + li) in `out`
-    auto epi1_b = [&](int rb, int cb, int g, unsigned vb, int tile_rows) {
-        int wr = wrow;
-        asm volatile("" : "+v"(wr), "+s"(rowb));
-        const bool ok = wr < tile_rows - (rb * 32 + 8 * g);
-        const unsigned off = ok ? vb : E_INVALID;
-        if (!X_NOEPI) {
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e_p0), orsrc, (int)off, (rb * 16 + 4 * g) * rowb + cb * 128, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e_p1), orsrc, (int)off, (rb * 16 + 4 * g + 1) * rowb + cb * 128, 0);
-        }
-    };
+    auto epi1_b = [&](int rb, int cb, int g, unsigned vb, int tile_rows) { wq3_epi1_store<X_NOEPI>(e_p0, e_p1, orsrc, rowb, wrow, rb, cb, g, vb, tile_rows); };
     auto epi_base = [&](int tile) {
         if (TR) return (unsigned)(((tile * TMR + wv * 64 + li) * ep.cout + n0 + 4 * lh) * 4);
         return (unsigned)(((tile * (TMR >> 1) + wv * 32 + 2 * lh) * ep.cout + n0 + li) * 4);
     };
-    auto tile_rows_of = [&](int tile) { const int r = M - tile * TMR; return tile < ntiles ? (r < TMR ? r : TMR) : 0; };
 
     // ---- prologue
     TGeo ug[G + 2];
@@ -298,7 +257,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
             const unsigned wbase = sF0 + (unsigned)((1 - t) * WQ3_FB) + wofs;
             unsigned vb = E_INVALID;
             int erows = 0;
-            if (EP) { vb = epi_base(etile); erows = tile_rows_of(etile); }
+            if (EP) { vb = epi_base(etile); erows = tl.rows_of(etile); }
 #pragma unroll
             for (int v = 0; v < NT; ++v) {
                 const int cs = (v + t) & 1, ns = cs ^ 1;
@@ -314,15 +273,12 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
 #pragma unroll
                 for (int s = 0; s < 24; ++s) {
                     const int term = s >> 3, rb = (s >> 2) & 1, cb = s & 3;
-                    floatx16& e = rb == 0 ? (cb == 0 ? d00 : cb == 1 ? d01 : cb == 2 ? d02 : d03) : (cb == 0 ? d10 : cb == 1 ? d11 : cb == 2 ? d12 : d13);
+                    floatx16& e = pick8<4>(rb, cb, d00, d01, d02, d03, d10, d11, d12, d13);
                     const bf16x8& av = term == 0 ? a[cs][rb].l : a[cs][rb].h;
                     const bf16x8& bv = term == 2 ? (last ? blast[cb] : bl[cb]) : bh[cs][cb];
                     __builtin_amdgcn_sched_barrier(0);
                     if (ZC && v == 0 && term == 0) {
-                        floatx16 z;
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) z[i] = 0.f;
-                        e = mfma(av, bv, z);
+                        e = mfma(av, bv, zero16());
                     } else {
                         e = mfma(av, bv, e);
                     }
@@ -384,7 +340,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
                         if (TR && s < 12) {
                             const int unit = v * 4 + s / 3;
                             const int erb = unit >> 4, ecb = (unit >> 2) & 3, eg = unit & 3;
-                            const floatx16& oa = erb == 0 ? (ecb == 0 ? o00 : ecb == 1 ? o01 : ecb == 2 ? o02 : o03) : (ecb == 0 ? o10 : ecb == 1 ? o11 : ecb == 2 ? o12 : o13);
+                            const floatx16& oa = pick8<4>(erb, ecb, o00, o01, o02, o03, o10, o11, o12, o13);
                             if (s % 3 == 0) { if (unit == 0) epi0_a(0); if (unit + 1 < 32) epi0_a(unit + 1); }
                             else if (s % 3 == 1) epi0_b(oa, unit);
                             else epi0_c(erb, ecb, eg, vb, erows);
@@ -392,7 +348,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
                         if (!TR && s < 8) {
                             const int unit = v * 4 + s / 2;
                             const int erb = unit >> 4, ecb = (unit >> 2) & 3, eg = unit & 3;
-                            const floatx16& oa = erb == 0 ? (ecb == 0 ? o00 : ecb == 1 ? o01 : ecb == 2 ? o02 : o03) : (ecb == 0 ? o10 : ecb == 1 ? o11 : ecb == 2 ? o12 : o13);
+                            const floatx16& oa = pick8<4>(erb, ecb, o00, o01, o02, o03, o10, o11, o12, o13);
                             if (s % 2 == 0) epi1_a(oa, ecb, eg); else epi1_b(erb, ecb, eg, vb, erows);
                         }
                     }
@@ -443,7 +399,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
     // ---- the last group's tile 1: the only serial epilogue of the workgroup
     {
         const unsigned vb = epi_base(prev_tile1);
-        const int erows = tile_rows_of(prev_tile1);
+        const int erows = tl.rows_of(prev_tile1);
 #pragma unroll
         for (int unit = 0; unit < 32; ++unit) {
             const int erb = unit >> 4, ecb = (unit >> 2) & 3, eg = unit & 3;

@@ -1,5 +1,7 @@
 // conv_x3_wq3h_kernel: conv_x3_wq3_kernel (conv_wq3.h: one wave per SIMD, unpadded 3x3, 128 output channels per workgroup, two
 // 256-row tiles per group) on a CHL input (conv_common.h) -- round 6.
+// Read conv_wq_parts.h first (the pieces shared with conv_ws.h, conv_wq.h and conv_wq3.h: geometry read, tile bookkeeping, weight-slot
+// contract, the f32 epilogue pieces), then conv_wq.h and conv_wq3.h for the scheme; this header keeps what it adds to them.
 //
 // Timing-only builds of conv_x3_wq3_kernel (profiles/r06_wq3_experiments.txt) price its input path -- global loads into registers,
 // the bf16 hi / lo split (27 VALU per float4) and the LDS stores -- at 17-20 % of the launch, and its weight refresh (18 LDS-DMA
@@ -50,31 +52,20 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
     const int li = lane & 31, lh = lane >> 5;
     const int M = (int)p.M;
     const int TMR = p.tmr;                           // rows per tile (<= 256, multiple of 4)
-    const int ntiles = (M + TMR - 1) / TMR;
-    const int ngroups = (ntiles + G - 1) / G;
+    const Tiles tl(M, TMR);
+    const int ntiles = tl.n, ngroups = tl.groups(G);
     int grp = (int)blockIdx.x;
     if (grp >= ngroups) return;
 
-    auto geo_args = [&]() {
-        KArg q = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(q));
-        GeoArgs ga;
-        ga.H = q->H; ga.W = q->W; ga.Hq = q->Hq; ga.Wq = q->Wq; ga.ph = q->ph; ga.pw = q->pw; ga.pp = q->pp;
-        ga.sh = q->sh; ga.sw = q->sw; ga.pt_ = q->pt_; ga.pl_ = q->pl_;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { ga.dv_mul[i] = q->dv_mul[i]; ga.dv_sh[i] = q->dv_sh[i]; }
-        return ga;
-    };
-    auto clamp_tile = [&](int t) { return t < ntiles ? t : ntiles - 1; };
     // first input pixel of a tile (uniform)
     auto geo_plo = [&](const GeoArgs& ga, int tile) {
         int b, oy, ox;
-        map_row32(ga, clamp_tile(tile) * TMR, b, oy, ox);
+        map_row32(ga, tl.clamp(tile) * TMR, b, oy, ox);
         return (b * ga.H + oy) * ga.W + ox;
     };
     // LDS byte address of the lane's first tap (hi part) in footprint `fb`: plane 2 lh, pixel = the lane's row's first input pixel
     auto geo_lane = [&](const GeoArgs& ga, int tile, int rb, int p_lo, int fb) {
-        const int m0 = clamp_tile(tile) * TMR;
+        const int m0 = tl.clamp(tile) * TMR;
         const int m = m0 + (wv * 2 + rb) * 32 + li;
         int b, oy, ox;
         map_row32(ga, m < M ? m : m0, b, oy, ox);
@@ -119,10 +110,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
 
     struct AFr { bf16x8 h, l; };
     const unsigned wstep = (unsigned)(p.W * 16);     // one filter row down
-    auto mfma = [&](const bf16x8& a, const bf16x8& b, const floatx16& c) {
-        if (TR) return mfma_x3<F16>(b, a, c);
-        return mfma_x3<F16>(a, b, c);
-    };
+    auto mfma = [&](const bf16x8& a, const bf16x8& b, const floatx16& c) { return mfma_ab<TR, F16>(a, b, c); };
 
     // accumulators: acc<tile><row block><column block>
     floatx16 c000, c001, c002, c003, c010, c011, c012, c013, c100, c101, c102, c103, c110, c111, c112, c113;
@@ -135,18 +123,11 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
     }
 
     // ---- epilogue pieces (buffer stores: an offset beyond the tensor is dropped by the hardware)
-    struct Epi { const float* bias; float* out; int cout; };
-    Epi ep;
-    {
-        KArg q = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(q));
-        ep.bias = q->bias; ep.out = q->out; ep.cout = q->Cout;
-    }
+    const Epi ep = epi_args();
     const unsigned out_np16 = OUT_HL ? p.out_np * 16u : 0u;
     const unsigned out_bytes = OUT_HL && TR ? p.out_np * (unsigned)ep.cout * 4u
                                             : (TR ? (unsigned)M * (unsigned)ep.cout * 4u : (unsigned)(M >> 1) * (unsigned)ep.cout * 4u);
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(ep.out, 0, (int)out_bytes, 0x00020000);
-    constexpr unsigned E_INVALID = 0xFFFF0000u;      // (the host keeps the output below 0xFFF00000 bytes)
     int rowb = ep.cout * 4;                          // bytes per output row
     float ebias[4] = {0.f, 0.f, 0.f, 0.f};
     if (!TR) {
@@ -161,18 +142,12 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
     float e_p0 = 0.f, e_p1 = 0.f;
     typedef const f32x4 __attribute__((address_space(3)))* LdsRF4;
     const unsigned bias_rd = sBias + (unsigned)(lh * 16);
-    auto epi0_a = [&](int unit) {                    // the bias of unit `unit` (channels 32 cb + 8 g + 4 lh + {0..3}) into set unit & 1
-        const int cb = (unit >> 2) & 3, g = unit & 3;
+    auto epi0_a = [&](int unit) {                    // the bias of unit `unit` (channels 32 cb + 8 g + 4 lh + {0..3}) into set unit & 1:
+        const int cb = (unit >> 2) & 3, g = unit & 3;          // read one unit ahead of its use
         const f32x4 t = *(LdsRF4)(bias_rd + (unsigned)((32 * cb + 8 * g) * 4));
         e_bb[unit & 1] = make_float4(t[0], t[1], t[2], t[3]);
     };
-    auto epi0_b = [&](const floatx16& acc, int unit) {         // + bias, relu
-        const int g = unit & 3;
-        const float4 e_b = e_bb[unit & 1];
-        e_v = make_float4(fmaxf(acc[4 * g] + e_b.x, 0.f), fmaxf(acc[4 * g + 1] + e_b.y, 0.f),
-                          fmaxf(acc[4 * g + 2] + e_b.z, 0.f), fmaxf(acc[4 * g + 3] + e_b.w, 0.f));
-        asm volatile("" : "+v"(e_v.x), "+v"(e_v.y), "+v"(e_v.z), "+v"(e_v.w));
-    };
+    auto epi0_b = [&](const floatx16& acc, int unit) { wq3_epi0_relu(e_v, e_bb, acc, unit); };
     // OUT_HL: x = hi + lo per value, as the consumers split an f32 input (conv_common.h split4).  Written out: hipcc converts the
     // hi parts twice and SLP-packs the residuals into v_pk_add_f32 (an anti-lever beside MFMAs, MI355X_MICROARCH.md): 12 VALU per unit
     unsigned e_h01 = 0, e_h23 = 0, e_l01 = 0, e_l23 = 0;
@@ -223,21 +198,8 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
         }
     };
     // kind 1, unit (rb, cb, g): rows 8 g + 4 lh + {0..3} of the row block = two 2 x 1 pool windows, column n0 + 32 cb + li
-    auto epi1_a = [&](const floatx16& acc, int cb, int g) {
-        e_p0 = fmaxf(fmaxf(acc[4 * g], acc[4 * g + 1]) + ebias[cb], 0.f);
-        e_p1 = fmaxf(fmaxf(acc[4 * g + 2], acc[4 * g + 3]) + ebias[cb], 0.f);
-        asm volatile("" : "+v"(e_p0), "+v"(e_p1));
-    };
-    auto epi1_b = [&](int rb, int cb, int g, unsigned vb, int tile_rows) {
-        int wr = wrow;
-        asm volatile("" : "+v"(wr), "+s"(rowb));
-        const bool ok = wr < tile_rows - (rb * 32 + 8 * g);
-        const unsigned off = ok ? vb : E_INVALID;
-        if (!X_NOEPI) {
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e_p0), orsrc, (int)off, (rb * 16 + 4 * g) * rowb + cb * 128, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e_p1), orsrc, (int)off, (rb * 16 + 4 * g + 1) * rowb + cb * 128, 0);
-        }
-    };
+    auto epi1_a = [&](const floatx16& acc, int cb, int g) { wq3_epi1_pool(e_p0, e_p1, ebias, acc, cb, g); };
+    auto epi1_b = [&](int rb, int cb, int g, unsigned vb, int tile_rows) { wq3_epi1_store<X_NOEPI>(e_p0, e_p1, orsrc, rowb, wrow, rb, cb, g, vb, tile_rows); };
     // ---- kind 1, OUT_HL: the pooled output in the pixel-major split layout conv_dhl_kernel reads ("PHL"): pooled pixel P (NHWC order, so
     // that a window's pixels x channels ARE its flattened features) = Cout / 8 groups of [hi 8 x 16 bit | lo 8 x 16 bit] = the same
     // 4 bytes per element as f32.  Channel c of pixel P: byte P * Cout * 4 + (c >> 3) * 32 + (c & 7) * 2, lo part 16 bytes further.  The 32
@@ -267,7 +229,6 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
         if (TR) return (unsigned)(((tile * TMR + wv * 64 + li) * ep.cout + n0 + 4 * lh) * 4);
         return (unsigned)(((tile * (TMR >> 1) + wv * 32 + 2 * lh) * ep.cout + n0 + li) * 4);
     };
-    auto tile_rows_of = [&](int tile) { const int r = M - tile * TMR; return tile < ntiles ? (r < TMR ? r : TMR) : 0; };
 
     // ---- progress words: wave w has read tap v (0..6) of the second block of pass n for the last time -> word (v, w) = n
     auto publish = [&](int v, unsigned n) {          // v: compile-time
@@ -338,7 +299,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
             const unsigned sw_next = (pass & 1u) ? 0u : (unsigned)(2 * WQH_SLOT);    // taps 7, 8 of pass + 1
             unsigned vb = E_INVALID;
             int erows = 0;
-            if (EP) { vb = epi_base(etile); erows = tile_rows_of(etile); if (OUT_HL) { e_lim = erows - wrow; e_inv = E_INVALID; asm volatile("" : "+v"(e_inv)); }
+            if (EP) { vb = epi_base(etile); erows = tl.rows_of(etile); if (OUT_HL) { e_lim = erows - wrow; e_inv = E_INVALID; asm volatile("" : "+v"(e_inv)); }
                     }
 #pragma unroll
             for (int v = 0; v < NT; ++v) {
@@ -363,15 +324,12 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
 #pragma unroll
                 for (int s = 0; s < 24; ++s) {
                     const int term = s >> 3, rb = (s >> 2) & 1, cb = s & 3;
-                    floatx16& e = rb == 0 ? (cb == 0 ? d00 : cb == 1 ? d01 : cb == 2 ? d02 : d03) : (cb == 0 ? d10 : cb == 1 ? d11 : cb == 2 ? d12 : d13);
+                    floatx16& e = pick8<4>(rb, cb, d00, d01, d02, d03, d10, d11, d12, d13);
                     const bf16x8& av = term == 0 ? a[cs][rb].l : a[cs][rb].h;
                     const bf16x8& bv = term == 2 ? (last ? blast[cb] : bl[cb]) : bh[cs][cb];
                     __builtin_amdgcn_sched_barrier(0);
                     if (ZC && v == 0 && term == 0) {
-                        floatx16 z;
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) z[i] = 0.f;
-                        e = mfma(av, bv, z);
+                        e = mfma(av, bv, zero16());
                     } else {
                         e = mfma(av, bv, e);
                     }
@@ -415,7 +373,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
                         const int unit = v * 6 + s / 3;
                         if (unit < 32) {
                             const int erb = unit >> 4, ecb = (unit >> 2) & 3, eg = unit & 3;
-                            const floatx16& oa = erb == 0 ? (ecb == 0 ? o00 : ecb == 1 ? o01 : ecb == 2 ? o02 : o03) : (ecb == 0 ? o10 : ecb == 1 ? o11 : ecb == 2 ? o12 : o13);
+                            const floatx16& oa = pick8<4>(erb, ecb, o00, o01, o02, o03, o10, o11, o12, o13);
                             if (s % 3 == 0) { if (unit == 0) epi0_a(0); if (unit + 1 < 32) epi0_a(unit + 1); }
                             else if (s % 3 == 1) epi0_b(oa, unit);
                             else epi0_c(erb, ecb, eg, vb, erows);
@@ -425,7 +383,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
                         const int unit = v * 6 + s / 4;
                         if (unit < 32) {
                             const int erb = unit >> 4, ecb = (unit >> 2) & 3, eg = unit & 3;
-                            const floatx16& oa = erb == 0 ? (ecb == 0 ? o00 : ecb == 1 ? o01 : ecb == 2 ? o02 : o03) : (ecb == 0 ? o10 : ecb == 1 ? o11 : ecb == 2 ? o12 : o13);
+                            const floatx16& oa = pick8<4>(erb, ecb, o00, o01, o02, o03, o10, o11, o12, o13);
                             if (s % 4 == 0) { if (unit == 0) epi0_a(0); if (unit + 1 < 32) epi0_a(unit + 1); epi0_b(oa, unit); }
                             else if (s % 4 == 1) epi0_h();
                             else if (s % 4 == 2) epi0_l();
@@ -436,7 +394,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
                         const int unit = v * 6 + s / 4;
                         if (unit < 32) {
                             const int erb = unit >> 4, ecb = (unit >> 2) & 3, eg = unit & 3;
-                            const floatx16& oa = erb == 0 ? (ecb == 0 ? o00 : ecb == 1 ? o01 : ecb == 2 ? o02 : o03) : (ecb == 0 ? o10 : ecb == 1 ? o11 : ecb == 2 ? o12 : o13);
+                            const floatx16& oa = pick8<4>(erb, ecb, o00, o01, o02, o03, o10, o11, o12, o13);
                             if (s % 4 == 0) epi1_a(oa, ecb, eg);
                             else if (s % 4 == 1) epi1_split();
                             else if (s % 4 == 2) epi1_c(erb, ecb, eg, vb, erows);
@@ -445,7 +403,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
                     if (EP && !TR && !OUT_HL && v <= 3 && s < 16) {          // two pieces per unit, eight units per step
                         const int unit = v * 8 + s / 2;
                         const int erb = unit >> 4, ecb = (unit >> 2) & 3, eg = unit & 3;
-                        const floatx16& oa = erb == 0 ? (ecb == 0 ? o00 : ecb == 1 ? o01 : ecb == 2 ? o02 : o03) : (ecb == 0 ? o10 : ecb == 1 ? o11 : ecb == 2 ? o12 : o13);
+                        const floatx16& oa = pick8<4>(erb, ecb, o00, o01, o02, o03, o10, o11, o12, o13);
                         if (s % 2 == 0) epi1_a(oa, ecb, eg); else epi1_b(erb, ecb, eg, vb, erows);
                     }
                 }
@@ -487,12 +445,12 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
     // ---- the last group's tile 1: the only serial epilogue of the workgroup
     {
         const unsigned vb = epi_base(prev_tile1);
-        const int erows = tile_rows_of(prev_tile1);
+        const int erows = tl.rows_of(prev_tile1);
         e_lim = erows - wrow; e_inv = E_INVALID; asm volatile("" : "+v"(e_inv));
 #pragma unroll
         for (int unit = 0; unit < 32; ++unit) {
             const int erb = unit >> 4, ecb = (unit >> 2) & 3, eg = unit & 3;
-            const floatx16& oa = erb == 0 ? (ecb == 0 ? c100 : ecb == 1 ? c101 : ecb == 2 ? c102 : c103) : (ecb == 0 ? c110 : ecb == 1 ? c111 : ecb == 2 ? c112 : c113);
+            const floatx16& oa = pick8<4>(erb, ecb, ISS_WQH_SET1);
             if (TR) { epi0_a(unit); epi0_b(oa, unit); if (OUT_HL) { epi0_h(); epi0_l(); } epi0_c(erb, ecb, eg, vb, erows); }
             else if (OUT_HL) { epi1_a(oa, ecb, eg); epi1_split(); epi1_c(erb, ecb, eg, vb, erows); }
             else { epi1_a(oa, ecb, eg); epi1_b(erb, ecb, eg, vb, erows); }

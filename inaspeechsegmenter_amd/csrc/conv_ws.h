@@ -29,31 +29,18 @@
 // hit 16 different 16-byte bank groups (20 p mod 64 is a permutation of the multiples of 4).  Zero-padded taps read an
 // all-zero pixel kept behind the footprint (one v_cndmask on the address instead of zeroing eight fragment registers).
 // The 16-byte slots of a weight tile are permuted on the SOURCE side of the LDS-DMA (slot = 2 n + (h ^ ((n >> 3) & 1)) for
-// row n, k half h) so that the ds_read_b128 of the 16 lanes of a group are conflict-free.  Geometry and epilogue
+// row n, k half h) so that the ds_read_b128 of the 16 lanes of a group are conflict-free (the weight-slot contract of
+// conv_wq_parts.h, which holds what this kernel shares with conv_wq.h, conv_wq3.h and conv_wq3h.h).  Geometry and epilogue
 // parameters are read through an opaque copy of the kernel-argument pointer where they are needed instead of living in
 // SGPRs through the main loop (conv_x3_fp_kernel spills 136 SGPRs and 11 VGPRs of its 45-word argument block).
 #pragma once
-#include "conv_fp.h"
+#include "conv_wq_parts.h"
 
 namespace issk {
 
 constexpr int F2_ROW = 80;                        // bytes per footprint pixel: 16 ch hi (32 B) | 16 ch lo (32 B) | 16 B pad
 constexpr int F2_BST = 4096;                      // bytes of one weight stage: hi plane (64 rows x 16 k bf16 = 2 KB) | lo plane
 constexpr int F2_CH = 16;                         // channels per chunk (one k16 MFMA step)
-
-typedef const bf16x8 __attribute__((address_space(3)))* LdsR16;
-typedef bf16x4 __attribute__((address_space(3)))* LdsW8;
-typedef unsigned __attribute__((address_space(3)))* LdsW4;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef f32x4 __attribute__((address_space(3)))* LdsF4;
-
-// geometry parameters (row decomposition of a tile): loaded from the kernel-argument segment once per tile
-struct GeoArgs {
-    int H, W, Hq, Wq, ph, pw, pp, sh, sw, pt_, pl_;
-    unsigned dv_mul[4];
-    int dv_sh[4];
-};
-typedef const ConvArgs __attribute__((address_space(4)))* KArg;
 
 // epilogue parameters, loaded from the kernel-argument segment when a tile is complete
 struct EpiArgs {
@@ -158,16 +145,6 @@ __global__ __launch_bounds__(512, 2) void conv_x3_ws_kernel(const ConvArgs p) {
     if (grp >= ngroups) return;
 
     // ---- geometry (row decomposition parameters through the kernel-argument pointer)
-    auto geo_args = [&]() {
-        KArg q = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(q));
-        GeoArgs ga;
-        ga.H = q->H; ga.W = q->W; ga.Hq = q->Hq; ga.Wq = q->Wq; ga.ph = q->ph; ga.pw = q->pw; ga.pp = q->pp;
-        ga.sh = q->sh; ga.sw = q->sw; ga.pt_ = q->pt_; ga.pl_ = q->pl_;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { ga.dv_mul[i] = q->dv_mul[i]; ga.dv_sh[i] = q->dv_sh[i]; }
-        return ga;
-    };
     struct TGeo { int p_lo, need, fy, fx, wb; };     // uniform per tile: first pixel, pixels needed, FUSED: (y, x) of it and its window
     auto clamp_tile = [&](int t) { return t < ntiles ? t : ntiles - 1; };
     auto geo_uniform = [&](const GeoArgs& ga, int tile) {
@@ -204,28 +181,9 @@ __global__ __launch_bounds__(512, 2) void conv_x3_ws_kernel(const ConvArgs p) {
             vmask = vm;
         }
     };
-    // FUSED: per-window scalars of the (at most two) windows a footprint touches.  Loaded one block before they are used
-    // (`wpend`), then moved to SGPRs (`settle`): they are wave-uniform, and VGPRs are what this kernel is short of.
-    struct Win { int wr0, wr1; float mean0, mean1, sd0, sd1; int live0, live1; };
     int nwin;
     { const int spp = p.Hq * p.Wq * p.pp; nwin = M / spp; }
-    auto windows_of = [&](int b) {                   // loads only: nothing here may USE the values (see conv_fp.h)
-        Win w;
-        const unsigned b0 = (unsigned)(b < nwin ? b : nwin - 1), b1 = (unsigned)(b + 1 < nwin ? b + 1 : nwin - 1);
-        w.wr0 = p.win_row[b0]; w.mean0 = p.stats[2u * b0]; w.sd0 = p.stats[2u * b0 + 1u]; w.live0 = p.finite[b0];
-        w.wr1 = p.win_row[b1]; w.mean1 = p.stats[2u * b1]; w.sd1 = p.stats[2u * b1 + 1u]; w.live1 = p.finite[b1];
-        return w;
-    };
-    auto settle = [&](const Win& w) {
-        Win s;
-        s.wr0 = __builtin_amdgcn_readfirstlane(w.wr0); s.wr1 = __builtin_amdgcn_readfirstlane(w.wr1);
-        s.mean0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w.mean0)));
-        s.mean1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w.mean1)));
-        s.sd0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w.sd0)));
-        s.sd1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w.sd1)));
-        s.live0 = __builtin_amdgcn_readfirstlane(w.live0); s.live1 = __builtin_amdgcn_readfirstlane(w.live1);
-        return s;
-    };
+    auto windows_of = [&](int b) { return issk::windows_of(p, nwin, b); };
 
     // ---- weights of one 16-channel chunk: NT tiles of 4 KB = 4 NT pieces of 1 KB; wave w moves pieces w, w + 8, ...
     // piece i: tap i >> 2, plane (i >> 1) & 1 (hi / lo), half i & 1 (rows 0-31 / 32-63).  Lane l of a piece writes 16-byte
