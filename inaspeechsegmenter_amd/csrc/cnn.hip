@@ -1420,8 +1420,8 @@ int conv_args(iss_ctx* c, IssNet& n, const PassIo& io, int bc, const ConvChoice&
     a.out = (float*)c->act[R[ISS_C_OUT]].p;
     a.ktab = n.d_ktab + n.ktab_off[r];
     a.wh = n.d_wh + R[ISS_C_WOFF]; a.wl = n.d_wl + R[ISS_C_WOFF];
-    a.Kpad = n.kpad[r]; a.mode = ch.mode; a.tmr = ch.tmr;
-    if (ch.kernel == ConvKernel::Dhl) return ISS_OK;
+    a.Kpad = n.kpad[r]; a.mode = ch.inst.mode; a.tmr = ch.tmr;
+    if (ch.inst.kernel == ConvKernel::Dhl) return ISS_OK;
     if (R[ISS_C_INMODE] == 1) {
         if (!io.d_winrow) return iss_fail(c, ISS_ESTATE, "patch-mode network run without a window list");
         a.in = (const float*)c->mspec.p; a.win_row = io.d_winrow; a.stats = io.d_stats; a.finite = io.d_fin;
@@ -1435,13 +1435,13 @@ int conv_args(iss_ctx* c, IssNet& n, const PassIo& io, int bc, const ConvChoice&
     { static const int dbg = getenv("ISS_DBG") ? atoi(getenv("ISS_DBG")) : 0; a.dbg = dbg; }     // timing-only experiment bits (never in a release build)
 #endif
     a.nblk_n = (unsigned)((a.Cout + BN - 1) / BN);
-    if (ch.kernel == ConvKernel::Pwc) {
+    if (ch.inst.kernel == ConvKernel::Pwc) {
         const int32_t* Q = &n.prog[(size_t)ch.partner * ISS_PROG_COLS];
         a.wh2 = n.d_wh + Q[ISS_C_WOFF]; a.wl2 = n.d_wl + Q[ISS_C_WOFF];
         a.bias2 = Q[ISS_C_BOFF] >= 0 ? n.d_blob + Q[ISS_C_BOFF] : nullptr;
         a.out2 = (float*)c->act[Q[ISS_C_OUT]].p;
         a.act2 = Q[ISS_C_ACT]; a.Cout2 = Q[ISS_C_COUT];
-    } else if (ch.kernel == ConvKernel::Pws2Dual) {
+    } else if (ch.inst.kernel == ConvKernel::Pws2Dual) {
         const int32_t* P = &n.prog[(size_t)ch.partner * ISS_PROG_COLS];
         a.in2 = P[ISS_C_IN] == ISS_BUF_INPUT ? io.d_input : (const float*)c->act[P[ISS_C_IN]].p;
         a.Cin2 = P[ISS_C_CIN]; a.H2 = P[ISS_C_H]; a.W2 = P[ISS_C_W]; a.sh2 = P[ISS_C_SH]; a.sw2 = P[ISS_C_SW];
@@ -1450,8 +1450,8 @@ int conv_args(iss_ctx* c, IssNet& n, const PassIo& io, int bc, const ConvChoice&
         a.bias = n.d_blob + (R[ISS_C_DUALB] - 1); a.res = nullptr;
         a.Kpad = a.Cin + a.Cin2;
     }
-    if (ch.f16) { a.f16 = 1; a.wh = n.d_wh16 + R[ISS_C_WOFF]; a.wl = n.d_wl16 + R[ISS_C_WOFF]; }       // fp16 operand halves
-    if (ch.kernel == ConvKernel::Wq3h) { a.in_hl = 1; a.in_np = ch.in_np; }
+    if (ch.inst.f16) { a.f16 = 1; a.wh = n.d_wh16 + R[ISS_C_WOFF]; a.wl = n.d_wl16 + R[ISS_C_WOFF]; }       // fp16 operand halves
+    if (ch.inst.kernel == ConvKernel::Wq3h) { a.in_hl = 1; a.in_np = ch.in_np; }
     if (ch.out != OutLayout::F32) { a.out_hl = 1; a.out_np = ch.out_np; a.out_f16 = ch.generic_out && ch.out_f16 ? 1 : 0; }
     return ISS_OK;
 }
@@ -1528,129 +1528,138 @@ int launch_shared_first_layer(iss_ctx* c, IssNet& n, const PassIo& io, int pend,
     return ISS_OK;
 }
 
-// One launch, as selected: per kernel its grid and its launcher, with the template arguments inst_name spells.
+// The instantiations this unit holds itself, keyed like every launcher (conv_common.h ISS_LAUNCH_IF): the branch whose template
+// arguments equal `i` runs, and a launcher without one says so.
+bool launch_direct1(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t st, const ConvInst& i) {
+#define ISS_DIRECT1_TRY(WINDOW_) ISS_LAUNCH_IF(i.kernel == ConvKernel::Direct1 && i.window == WINDOW_, conv1_direct3x3_kernel<WINDOW_>, grid, 256, lds)
+    ISS_DIRECT1_TRY(true)
+    ISS_DIRECT1_TRY(false)
+#undef ISS_DIRECT1_TRY
+    return false;
+}
+bool launch_patch1(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i) {
+#define ISS_PATCH1_TRY(TR_, F16_) \
+    ISS_LAUNCH_IF(i.kernel == ConvKernel::Patch1 && i.tr == TR_ && i.f16 == F16_, (conv1_patch_x3_kernel<TR_, F16_>), grid, 256, 0)
+    ISS_PATCH1_TRY(true, true)
+    ISS_PATCH1_TRY(true, false)
+    ISS_PATCH1_TRY(false, true)
+    ISS_PATCH1_TRY(false, false)
+#undef ISS_PATCH1_TRY
+    return false;
+}
+// conv_x3_kernel is instantiated with NTN = 2 (64-column tiles) only: with the XCD-aware order the A tile is re-read from L2, not from
+// HBM, and NTN = 4 (128 x 128 tiles: fewer, fatter workgroups) measured 6 % SLOWER on ResNet-101.  The template still takes NTN = 4 / 8,
+// but nothing instantiates them: the device code holds the nine <MODE, TR, 2> kernels below and no other.
+constexpr int X3_NTN = 2;
+bool launch_x3(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i) {
+#define ISS_X3_TRY(MODE_, TR_)                                                                                                      \
+    ISS_LAUNCH_IF((i.kernel == ConvKernel::X3 || i.kernel == ConvKernel::Gather) && i.mode == MODE_ && i.tr == TR_, \
+                  (conv_x3_kernel<MODE_, TR_, X3_NTN>), grid, 256, 0)
+    ISS_X3_TRY(4, true)
+    ISS_X3_TRY(4, false)
+    ISS_X3_TRY(3, true)
+    ISS_X3_TRY(3, false)
+    ISS_X3_TRY(0, true)
+    ISS_X3_TRY(0, false)
+    ISS_X3_TRY(1, true)
+    ISS_X3_TRY(1, false)
+    ISS_X3_TRY(2, false)
+#undef ISS_X3_TRY
+    return false;
+}
+bool launch_pw(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i) {
+#define ISS_PW_TRY(F16_) ISS_LAUNCH_IF(i.kernel == ConvKernel::Pw && i.f16 == F16_, conv_x3_pw_kernel<F16_>, grid, 256, 0)
+    ISS_PW_TRY(true)
+    ISS_PW_TRY(false)
+#undef ISS_PW_TRY
+    return false;
+}
+bool launch_igemm(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i) {
+#define ISS_IGEMM_TRY(MODE_) ISS_LAUNCH_IF(i.kernel == ConvKernel::Igemm && i.mode == MODE_, conv_igemm_kernel<MODE_>, grid, 256, 0)
+    ISS_IGEMM_TRY(0)
+    ISS_IGEMM_TRY(1)
+    ISS_IGEMM_TRY(2)
+#undef ISS_IGEMM_TRY
+    return false;
+}
+
+// One launch, as selected: per kernel family its grid and its launcher, which gets the instantiation (ch.inst) and nothing else to pick
+// a template argument by.  A launcher that holds no such instantiation launches nothing and returns false: an error, not another kernel.
 int launch_conv(iss_ctx* c, IssNet& n, const ConvChoice& ch, ConvArgs& a, double fl) {
     const int r = ch.row;
     const int32_t* R = &n.prog[(size_t)r * ISS_PROG_COLS];
-    const bool padded = ch.padded, tr = ch.tr, fused = ch.fused;
-    const int nh = ch.nh;
+    const ConvInst& i = ch.inst;
+    hipStream_t st = c->stream;
     const dim3 grid(a.nblk, a.nblk_n);
     const unsigned ny = (unsigned)std::max(1, a.Cout / (2 * BN));                                             // NH = 2: column pairs
     const unsigned tiles = (unsigned)((a.M + WS_TM - 1) / WS_TM);                                             // 512-row tiles
     const unsigned groups = (unsigned)((a.M + (long long)WS_TM * WS_G - 1) / ((long long)WS_TM * WS_G));      // ... and groups of WS_G of them
     const unsigned qtiles = ch.tmr > 0 ? (unsigned)((a.M + ch.tmr - 1) / ch.tmr) : 0;                         // tiles of tmr rows
+    const dim3 nh2grid(std::min<unsigned>(tiles, std::max(1u, 256u / ny)), ny);                               // NH = 2: one 512-row tile per group
+    const dim3 wgrid(std::min<unsigned>(groups, 256u), grid.y);                                               // persistent: one 512-thread workgroup per CU
+    bool ok = false;
     iss_prof_begin(c, 0, fl);
-    iss_prof_tag(c, ch.tag), iss_prof_row(c, r), iss_prof_inst(c, "%s", inst_name(ch).c_str());
-    switch (ch.kernel) {
+    iss_prof_tag(c, ch.tag), iss_prof_row(c, r), iss_prof_inst(c, "%s", inst_name(i).c_str());
+    switch (i.kernel) {
     case ConvKernel::Dhl: {
         const int K = R[ISS_C_CIN];
-        uint16_t*& wp = n.dhl_wp[{r, ch.f16 ? 1 : 0}];
+        uint16_t*& wp = n.dhl_wp[{r, i.f16 ? 1 : 0}];
         if (!wp) {
             ISS_HIP(c, hipMalloc((void**)&wp, dhl_packed_elems(K, R[ISS_C_COUT]) * 2));
-            iss_dhl_pack((ch.f16 ? n.d_wh16 : n.d_wh) + R[ISS_C_WOFF], (ch.f16 ? n.d_wl16 : n.d_wl) + R[ISS_C_WOFF], wp, R[ISS_C_COUT], n.kpad[r], K, c->stream);
+            iss_dhl_pack((i.f16 ? n.d_wh16 : n.d_wh) + R[ISS_C_WOFF], (i.f16 ? n.d_wl16 : n.d_wl) + R[ISS_C_WOFF], wp, R[ISS_C_COUT], n.kpad[r], K, st);
         }
         DhlArgs d;
         d.a = reinterpret_cast<const uint16_t*>(a.in); d.wp = wp; d.bias = a.bias; d.out = a.out;
         d.np = ch.in_np; d.M = (int)a.M; d.K = K; d.Cout = R[ISS_C_COUT]; d.act = R[ISS_C_ACT];       // (a dense row: one GEMM row per window)
-        iss_dhl_launch(d, c->stream, ch.f16);
+        ok = iss_dhl_launch(d, st, i);
         break;
     }
-    case ConvKernel::Pwc: iss_pwc_launch(a, c->stream); break;
-    case ConvKernel::Pws2Dual: iss_pws2_launch(a, c->stream, false, true); break;
+    case ConvKernel::Pwc: ok = iss_pwc_launch(a, st, i); break;
+    case ConvKernel::Pws2Dual: case ConvKernel::Pws2Strided: case ConvKernel::Pws2: ok = iss_pws2_launch(a, st, i); break;
     case ConvKernel::Direct1: {
         const long long items = (long long)(a.M / ((long long)a.H * a.W)) * ((a.H + 7) / 8) * a.W * (a.Cout / 4);
         if (items >= (1ll << 32)) return iss_fail(c, ISS_EINVAL, "internal: direct first layer over %lld work items", items);
-        const dim3 dgrid((unsigned)std::min<long long>((items + 255) / 256, 8192));
-        const size_t dlds = (size_t)9 * a.Cout * sizeof(float);
-        if (ch.window) hipLaunchKernelGGL(conv1_direct3x3_kernel<true>, dgrid, dim3(256), dlds, c->stream, a);
-        else hipLaunchKernelGGL(conv1_direct3x3_kernel<false>, dgrid, dim3(256), dlds, c->stream, a);
+        ok = launch_direct1(a, dim3((unsigned)std::min<long long>((items + 255) / 256, 8192)), (size_t)9 * a.Cout * sizeof(float), st, i);
         break;
     }
-    case ConvKernel::WsNh2F32: iss_ws_launch_f32_nh2_3x3(a, dim3(std::min<unsigned>(tiles, std::max(1u, 256u / ny)), ny), c->stream, tr); break;
-    case ConvKernel::WsNh2: {                            // one 512-row tile per group
-        const dim3 g2(std::min<unsigned>(tiles, std::max(1u, 256u / ny)), ny);
-        if (padded && !tr) iss_ws_launch_nh2_3x3_padded_pool(a, g2, c->stream);
-        else if (padded) iss_ws_launch_nh2_3x3_padded(a, g2, c->stream);
-        else iss_ws_launch_nh2_3x3(a, g2, c->stream, tr);
+    case ConvKernel::WsNh2F32: ok = iss_ws_launch_f32_nh2_3x3(a, nh2grid, st, i); break;
+    case ConvKernel::WsNh2: ok = iss_ws_launch_nh2_3x3(a, nh2grid, st, i); break;
+    case ConvKernel::Wq3: ok = iss_wq3_launch(a, dim3(std::min<unsigned>((qtiles + 1) / 2, std::max(1u, 256u / ny)), ny), st, i); break;
+    case ConvKernel::Wq3h: ok = iss_wq3h_launch(a, dim3(std::min<unsigned>((qtiles + 1) / 2, std::max(1u, 256u / ny)), ny), st, i); break;
+    case ConvKernel::WsPlainU: case ConvKernel::WsPlain: {
+        const dim3 pgrid(std::min<unsigned>(groups, std::max(1u, 256u / grid.y)), grid.y);                    // one 512-thread workgroup per CU in total
+        ok = iss_ws_launch_plain_3x3(a, pgrid, st, i);
         break;
     }
-    case ConvKernel::Wq3: case ConvKernel::Wq3h: {
-        const dim3 qgrid(std::min<unsigned>((qtiles + 1) / 2, std::max(1u, 256u / ny)), ny);
-        if (ch.kernel == ConvKernel::Wq3h) iss_wq3h_launch(a, qgrid, c->stream, ch.kind);
-        else iss_wq3_launch(a, qgrid, c->stream, ch.kind);
-        break;
-    }
-    case ConvKernel::WsPlainU: iss_ws_launch_plain_3x3_unpadded(a, dim3(std::min<unsigned>(groups, std::max(1u, 256u / grid.y)), grid.y), c->stream, tr); break;
-    case ConvKernel::WsPlain: iss_ws_launch_plain_3x3(a, dim3(std::min<unsigned>(groups, std::max(1u, 256u / grid.y)), grid.y), c->stream); break;   // one 512-thread workgroup per CU in total
-    case ConvKernel::WsF32Fused: iss_ws_launch_f32_fused_5x3(a, dim3(std::min<unsigned>(groups, 256u), grid.y), c->stream); break;
-    case ConvKernel::WsRing: iss_ws_launch_ring(a, dim3(std::min<unsigned>(qtiles, 256u), grid.y), c->stream, padded); break;   // one tile of tmr rows per group
-    case ConvKernel::WsFs: {                             // FS: one tile per group (conv_ws.h G)
-        const dim3 wgrid(std::min<unsigned>(tiles, 256u), grid.y);
-        if (tr) iss_ws_launch_fs_5x3_tr(a, wgrid, c->stream);
-        else if (a.H_k == 5) iss_ws_launch_fs_5x3(a, wgrid, c->stream, padded);
-        else iss_ws_launch_fs_3x3(a, wgrid, c->stream, padded);
-        break;
-    }
-    case ConvKernel::WsNcb1: iss_ws_launch_ncb1_5x3(a, dim3(std::min<unsigned>(groups, 256u), grid.y), c->stream); break;
-    case ConvKernel::Wq: iss_wq_launch_5x3(a, dim3(std::min<unsigned>((qtiles + 1) / 2, 256u), grid.y), c->stream); break;   // persistent: one 256-thread workgroup per CU
-    case ConvKernel::Ws: {
-        const dim3 wgrid(std::min<unsigned>(groups, 256u), grid.y);         // persistent: one 512-thread workgroup per CU
-#define ISS_WS_CASE(KH_, KW_) if (a.H_k == KH_ && a.kw == KW_) iss_ws_launch_##KH_##x##KW_(a, wgrid, c->stream, padded, tr, fused); else
-        ISS_WS_SHAPES(ISS_WS_CASE) { return iss_fail(c, ISS_EINVAL, "internal: no weight-stationary kernel for %dx%d", a.H_k, a.kw); }
+    case ConvKernel::WsF32Fused: ok = iss_ws_launch_f32_fused_5x3(a, wgrid, st, i); break;
+    case ConvKernel::WsRing: ok = iss_ws_launch_ring(a, dim3(std::min<unsigned>(qtiles, 256u), grid.y), st, i); break;   // one tile of tmr rows per group
+    case ConvKernel::WsFs: ok = iss_ws_launch_fs(a, dim3(std::min<unsigned>(tiles, 256u), grid.y), st, i); break;        // FS: one tile per group (conv_ws.h G)
+    case ConvKernel::WsNcb1: ok = iss_ws_launch_ncb1_5x3(a, wgrid, st, i); break;
+    case ConvKernel::Wq: ok = iss_wq_launch_5x3(a, dim3(std::min<unsigned>((qtiles + 1) / 2, 256u), grid.y), st, i); break;   // persistent: one 256-thread workgroup per CU
+    case ConvKernel::Ws:
+#define ISS_WS_CASE(KH_, KW_) if (i.kh == KH_ && i.kw == KW_) ok = iss_ws_launch_##KH_##x##KW_(a, wgrid, st, i);
+        ISS_WS_SHAPES(ISS_WS_CASE)
 #undef ISS_WS_CASE
         break;
-    }
     case ConvKernel::Fp: {
-        const dim3 pgrid(std::min<unsigned>(a.nblk, 512u), grid.y / nh);     // persistent: 2 workgroups per CU
-#define ISS_FP_CASE(KH_, KW_) if (a.H_k == KH_ && a.kw == KW_) iss_fp_launch_##KH_##x##KW_(a, pgrid, c->stream, padded, tr, fused, nh); else
-        ISS_FP_SHAPES(ISS_FP_CASE) { return iss_fail(c, ISS_EINVAL, "internal: no footprint kernel for %dx%d", a.H_k, a.kw); }
+        const dim3 pgrid(std::min<unsigned>(a.nblk, 512u), grid.y / i.nh);     // persistent: 2 workgroups per CU
+#define ISS_FP_CASE(KH_, KW_) if (i.kh == KH_ && i.kw == KW_) ok = iss_fp_launch_##KH_##x##KW_(a, pgrid, st, i);
+        ISS_FP_SHAPES(ISS_FP_CASE)
 #undef ISS_FP_CASE
         break;
     }
-    case ConvKernel::Patch1: {
-        const dim3 pgrid(std::min<unsigned>(a.nblk, 512u), grid.y);     // persistent, no barriers: 2 workgroups per CU
-        // blob offsets are multiples of 8 floats, so the float4 loads of bias / scale / shift are aligned
-        if (tr && ch.f16) hipLaunchKernelGGL((conv1_patch_x3_kernel<true, true>), pgrid, dim3(256), 0, c->stream, a);
-        else if (tr) hipLaunchKernelGGL((conv1_patch_x3_kernel<true, false>), pgrid, dim3(256), 0, c->stream, a);
-        else if (ch.f16) hipLaunchKernelGGL((conv1_patch_x3_kernel<false, true>), pgrid, dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL((conv1_patch_x3_kernel<false, false>), pgrid, dim3(256), 0, c->stream, a);
+    // persistent, no barriers: 2 workgroups per CU (blob offsets are multiples of 8 floats, so the float4 loads of bias / scale / shift are aligned)
+    case ConvKernel::Patch1: ok = launch_patch1(a, dim3(std::min<unsigned>(a.nblk, 512u), grid.y), st, i); break;
+    case ConvKernel::Gather: case ConvKernel::X3:        // A staged once per 32 X3_NTN output channels; 1-D XCD-aware grid
+        a.nblk_n = (unsigned)((a.Cout + 32 * X3_NTN - 1) / (32 * X3_NTN));
+        ok = launch_x3(a, dim3(a.nblk * a.nblk_n), st, i);
         break;
-    }
-    case ConvKernel::Gather: case ConvKernel::X3: {
-        // wider N tiles for wide layers (A staged once per 128 / 256 output channels); 1-D XCD-aware grid
-        // NTN = 4 (128 x 128 tiles) is compiled but not selected: with the XCD-aware order the A tile is re-read from
-        // L2, not from HBM, and the wider tiles (fewer, fatter workgroups) measured 6 % SLOWER on ResNet-101
-        constexpr int ntn = 2;
-        a.nblk_n = (unsigned)((a.Cout + 32 * ntn - 1) / (32 * ntn));
-        const dim3 gridw(a.nblk * a.nblk_n);
-        if (a.mode == 4 && tr) hipLaunchKernelGGL((conv_x3_kernel<4, true, 2>), gridw, dim3(256), 0, c->stream, a);
-        else if (a.mode == 4) hipLaunchKernelGGL((conv_x3_kernel<4, false, 2>), gridw, dim3(256), 0, c->stream, a);
-        else if (a.mode == 3 && tr) hipLaunchKernelGGL((conv_x3_kernel<3, true, 2>), gridw, dim3(256), 0, c->stream, a);
-        else if (a.mode == 3) hipLaunchKernelGGL((conv_x3_kernel<3, false, 2>), gridw, dim3(256), 0, c->stream, a);
-        else if (a.mode == 0 && tr) hipLaunchKernelGGL((conv_x3_kernel<0, true, 2>), gridw, dim3(256), 0, c->stream, a);
-        else if (a.mode == 0) hipLaunchKernelGGL((conv_x3_kernel<0, false, 2>), gridw, dim3(256), 0, c->stream, a);
-        else if (a.mode == 1 && tr) hipLaunchKernelGGL((conv_x3_kernel<1, true, 2>), gridw, dim3(256), 0, c->stream, a);
-        else if (a.mode == 1) hipLaunchKernelGGL((conv_x3_kernel<1, false, 2>), gridw, dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL((conv_x3_kernel<2, false, 2>), gridw, dim3(256), 0, c->stream, a);
-        break;
-    }
-    case ConvKernel::Pws2Strided: case ConvKernel::Pws2: case ConvKernel::Pws: case ConvKernel::Pw: {
-        if (ch.kernel == ConvKernel::Pws2Strided) iss_pws2_launch(a, c->stream, true);
-        else if (ch.kernel == ConvKernel::Pws2) iss_pws2_launch(a, c->stream);
-        else if (ch.kernel == ConvKernel::Pws) iss_pws_launch(a, dim3(std::min<unsigned>(a.nblk * a.nblk_n, 512u)), c->stream);
-        else if (ch.f16) hipLaunchKernelGGL(conv_x3_pw_kernel<true>, dim3(std::min<unsigned>(a.nblk * a.nblk_n, 768u)), dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL(conv_x3_pw_kernel<false>, dim3(std::min<unsigned>(a.nblk * a.nblk_n, 768u)), dim3(256), 0, c->stream, a);
-        break;
-    }
-    case ConvKernel::Igemm: {                            // generic kernels: 1-D, XCD-aware (gemm_tile_of_block)
-        const dim3 grid1(a.nblk * a.nblk_n);
-        if (a.mode == 0) hipLaunchKernelGGL(conv_igemm_kernel<0>, grid1, dim3(256), 0, c->stream, a);
-        else if (a.mode == 1) hipLaunchKernelGGL(conv_igemm_kernel<1>, grid1, dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL(conv_igemm_kernel<2>, grid1, dim3(256), 0, c->stream, a);
-        break;
-    }
+    case ConvKernel::Pws: ok = iss_pws_launch(a, dim3(std::min<unsigned>(a.nblk * a.nblk_n, 512u)), st, i); break;
+    case ConvKernel::Pw: ok = launch_pw(a, dim3(std::min<unsigned>(a.nblk * a.nblk_n, 768u)), st, i); break;
+    case ConvKernel::Igemm: ok = launch_igemm(a, dim3(a.nblk * a.nblk_n), st, i); break;      // generic kernels: 1-D, XCD-aware (gemm_tile_of_block)
     case ConvKernel::Declined: return iss_fail(c, ISS_EINVAL, "internal: row %d has no kernel", r);
     }
+    if (!ok) return iss_fail(c, ISS_EINVAL, "internal: %s is not compiled", inst_name(i).c_str());
     iss_prof_end(c);
     return ISS_OK;
 }
@@ -1662,9 +1671,9 @@ int run_conv(iss_ctx* c, IssNet& n, const ConvEnv& env, const PassIo& io, const 
     int rc = conv_args(c, n, io, env.bc, ch, a);
     if (rc) return rc;
     double fl = conv_flops(R, (double)a.M);
-    if (ch.kernel == ConvKernel::Dhl) fl = 2.0 * R[ISS_C_CIN] * (double)R[ISS_C_COUT] * (double)env.bc;
-    if (ch.kernel == ConvKernel::Pwc) fl += 2.0 * a.Cout * (double)a.Cout2 * (double)a.M;
-    if (ch.kernel == ConvKernel::Pws2Dual) fl += 2.0 * a.Cin2 * (double)a.Cout * (double)a.M;
+    if (ch.inst.kernel == ConvKernel::Dhl) fl = 2.0 * R[ISS_C_CIN] * (double)R[ISS_C_COUT] * (double)env.bc;
+    if (ch.inst.kernel == ConvKernel::Pwc) fl += 2.0 * a.Cout * (double)a.Cout2 * (double)a.M;
+    if (ch.inst.kernel == ConvKernel::Pws2Dual) fl += 2.0 * a.Cin2 * (double)a.Cout * (double)a.M;
     if (ch.first == FirstLayer::Fused || ch.first == FirstLayer::Gather)
         if ((rc = launch_shared_first_layer(c, n, io, pend, env.bc, env.rmin, env.rmax, a, &fl))) return rc;
     return launch_conv(c, n, ch, a, fl);

@@ -25,9 +25,12 @@ void iss_dhl_pack(const uint16_t* wh, const uint16_t* wl, uint16_t* out, int Cou
     const long long total = (long long)dhl_packed_elems(K, Cout);
     hipLaunchKernelGGL(dhl_pack_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, st, wh, wl, out, Cout, Kpad, K);
 }
-void iss_dhl_launch(const DhlArgs& a, hipStream_t st, bool f16) {
+bool iss_dhl_launch(const DhlArgs& a, hipStream_t st, const ConvInst& i) {
     const dim3 grid((unsigned)((a.M + DHL_BM - 1) / DHL_BM), (unsigned)dhl_col_tiles(a.Cout));
-    if (f16) hipLaunchKernelGGL((conv_dhl_kernel<true>), grid, dim3(ISS_DHL_NW * 64), 0, st, a);
-    else hipLaunchKernelGGL((conv_dhl_kernel<false>), grid, dim3(ISS_DHL_NW * 64), 0, st, a);
+#define ISS_DHL_TRY(F16_) ISS_LAUNCH_IF(i.kernel == ConvKernel::Dhl && i.f16 == F16_, (conv_dhl_kernel<F16_>), grid, ISS_DHL_NW * 64, 0)
+    ISS_DHL_TRY(true)
+    ISS_DHL_TRY(false)
+#undef ISS_DHL_TRY
+    return false;
 }
 }  // namespace issk

@@ -2,20 +2,27 @@
 #include "conv_pw.h"
 
 namespace issk {
-void iss_pws_launch(const ConvArgs& a, dim3 grid, hipStream_t st) {
-    const bool simple = a.act <= 1 && !a.ps;
-    if (a.res && simple) hipLaunchKernelGGL((conv_x3_pws_kernel<true, true>), grid, dim3(256), 0, st, a);
-    else if (simple) hipLaunchKernelGGL((conv_x3_pws_kernel<false, true>), grid, dim3(256), 0, st, a);
-    else if (a.res) hipLaunchKernelGGL((conv_x3_pws_kernel<true, false>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_x3_pws_kernel<false, false>), grid, dim3(256), 0, st, a);
+bool iss_pws_launch(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i) {
+#define ISS_PWS_TRY(RES_, SIMPLE_) \
+    ISS_LAUNCH_IF(i.kernel == ConvKernel::Pws && i.has_res == RES_ && i.simple_pw == SIMPLE_, (conv_x3_pws_kernel<RES_, SIMPLE_>), grid, 256, 0)
+    ISS_PWS_TRY(true, true)
+    ISS_PWS_TRY(false, true)
+    ISS_PWS_TRY(true, false)
+    ISS_PWS_TRY(false, false)
+#undef ISS_PWS_TRY
+    return false;
 }
-void iss_pws2_launch(const ConvArgs& a0, hipStream_t st, bool strided, bool dual) {
+bool iss_pws2_launch(const ConvArgs& a0, hipStream_t st, const ConvInst& i) {
     ConvArgs a = a0;
     a.nblk_n = (unsigned)(a.Cout / 128);
     const dim3 grid(std::min<unsigned>(a.nblk * a.nblk_n, 512u));
-    if (dual) hipLaunchKernelGGL((conv_x3_pws2_kernel<true, false, true>), grid, dim3(256), 0, st, a);
-    else if (strided) hipLaunchKernelGGL((conv_x3_pws2_kernel<true, true>), grid, dim3(256), 0, st, a);
-    else if (a.act <= 1 && !a.ps) hipLaunchKernelGGL((conv_x3_pws2_kernel<true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_x3_pws2_kernel<false>), grid, dim3(256), 0, st, a);
+#define ISS_PWS2_TRY(K_, SIMPLE_, STRIDED_, DUAL_) \
+    ISS_LAUNCH_IF(i.kernel == K_ && i.simple_pw == SIMPLE_, (conv_x3_pws2_kernel<SIMPLE_, STRIDED_, DUAL_>), grid, 256, 0)
+    ISS_PWS2_TRY(ConvKernel::Pws2Dual, true, false, true)
+    ISS_PWS2_TRY(ConvKernel::Pws2Strided, true, true, false)
+    ISS_PWS2_TRY(ConvKernel::Pws2, true, false, false)
+    ISS_PWS2_TRY(ConvKernel::Pws2, false, false, false)
+#undef ISS_PWS2_TRY
+    return false;
 }
 }  // namespace issk

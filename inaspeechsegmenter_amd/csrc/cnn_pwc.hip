@@ -2,15 +2,15 @@
 #include "conv_pwc.h"
 
 namespace issk {
-void iss_pwc_launch(const ConvArgs& a, hipStream_t st) {
-    const dim3 grid(std::min<unsigned>(a.nblk, 256u));       // one workgroup per CU (155 KB of LDS)
-    // C1 = 32: 68 / 73 KB of LDS and <= 252 registers -- TWO workgroups fit a CU, and the second one's waves run their epilogue / split /
-    // staging phases under the first one's MFMAs (profiles/r06_pwc_experiments.txt: those phases, not memory, bind the kernel)
-    const dim3 grid2(std::min<unsigned>(a.nblk, 512u));
-    if (a.Cin == 32 && a.Cout2 == 32) hipLaunchKernelGGL((conv_x3_pwc_kernel<1, 1>), grid2, dim3(256), 0, st, a);
-    else if (a.Cin == 32) hipLaunchKernelGGL((conv_x3_pwc_kernel<1, 2>), grid2, dim3(256), 0, st, a);
-    else if (a.Cin == 64 && a.Cout2 == 64) hipLaunchKernelGGL((conv_x3_pwc_kernel<2, 2>), grid, dim3(256), 0, st, a);
-    else if (a.Cin == 64) hipLaunchKernelGGL((conv_x3_pwc_kernel<2, 4>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_x3_pwc_kernel<4, 4>), grid, dim3(256), 0, st, a);
+bool iss_pwc_launch(const ConvArgs& a, hipStream_t st, const ConvInst& i) {
+    // one workgroup per CU (155 KB of LDS).  K1T = 1: 68 / 73 KB of LDS and <= 252 registers -- TWO workgroups fit a CU, and the second
+    // one's waves run their epilogue / split / staging phases under the first one's MFMAs (profiles/r06_pwc_experiments.txt: those
+    // phases, not memory, bind the kernel)
+#define ISS_PWC_TRY(K1T_, NC3_)                                                                                     \
+    ISS_LAUNCH_IF(i.kernel == ConvKernel::Pwc && i.c1 == K1T_ && i.c3 == NC3_, (conv_x3_pwc_kernel<K1T_, NC3_>), \
+                  dim3(std::min<unsigned>(a.nblk, K1T_ == 1 ? 512u : 256u)), 256, 0)
+    ISS_PWC_PAIRS(ISS_PWC_TRY)
+#undef ISS_PWC_TRY
+    return false;
 }
 }  // namespace issk

@@ -3,10 +3,10 @@
 #include "conv_wq.h"
 
 namespace issk {
-void iss_wq_launch_5x3_f16(const ConvArgs& a, dim3 grid, hipStream_t st);
-void iss_wq_launch_5x3(const ConvArgs& a, dim3 grid, hipStream_t st) {
-    if (a.f16) return iss_wq_launch_5x3_f16(a, grid, st);
-    if (a.out_hl) hipLaunchKernelGGL((conv_x3_wq_kernel<5, 3, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_x3_wq_kernel<5, 3, false>), grid, dim3(256), 0, st, a);
+bool iss_wq_launch_5x3_f16(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i);
+bool iss_wq_launch_5x3(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i) {
+    ISS_WQ_TRY(5, 3, true, false)
+    ISS_WQ_TRY(5, 3, false, false)
+    return iss_wq_launch_5x3_f16(a, grid, st, i);
 }
 }  // namespace issk

@@ -3,8 +3,11 @@
 #include "conv_wq3.h"
 
 namespace issk {
-void iss_wq3_launch(const ConvArgs& a, dim3 grid, hipStream_t st, int kind) {
-    if (kind == 0) hipLaunchKernelGGL((conv_x3_wq3_kernel<0>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_x3_wq3_kernel<1>), grid, dim3(256), 0, st, a);
+bool iss_wq3_launch(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i) {
+#define ISS_WQ3_TRY(KIND_) ISS_LAUNCH_IF(i.kernel == ConvKernel::Wq3 && i.kind == KIND_, (conv_x3_wq3_kernel<KIND_>), grid, 256, 0)
+    ISS_WQ3_TRY(0)
+    ISS_WQ3_TRY(1)
+#undef ISS_WQ3_TRY
+    return false;
 }
 }  // namespace issk

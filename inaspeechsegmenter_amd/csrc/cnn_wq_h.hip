@@ -2,8 +2,9 @@
 #include "conv_wq.h"
 
 namespace issk {
-void iss_wq_launch_5x3_f16(const ConvArgs& a, dim3 grid, hipStream_t st) {
-    if (a.out_hl) hipLaunchKernelGGL((conv_x3_wq_kernel<5, 3, true, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_x3_wq_kernel<5, 3, false, true>), grid, dim3(256), 0, st, a);
+bool iss_wq_launch_5x3_f16(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i) {
+    ISS_WQ_TRY(5, 3, true, true)
+    ISS_WQ_TRY(5, 3, false, true)
+    return false;
 }
 }  // namespace issk

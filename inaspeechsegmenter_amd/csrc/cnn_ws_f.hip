@@ -2,8 +2,9 @@
 #include "conv_ws.h"
 
 namespace issk {
-void iss_ws_launch_fs_5x3(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded) { launch_ws_fused_rowmajor<5, 3, true>(a, grid, st, padded); }
-void iss_ws_launch_fs_5x3_tr(const ConvArgs& a, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL((conv_x3_ws_kernel<5, 3, false, true, true, 1, 1, true>), grid, dim3(512), 0, st, a);
+ISS_WS_LAUNCHER(iss_ws_launch_fs_5x3) {
+    if (launch_ws_fused_rowmajor<5, 3, true>(a, grid, st, i)) return true;
+    ISS_WS_TRY(ConvKernel::WsFs, 5, 3, false, true, true, 1, 1, true)       // no fused pool: transposed simple epilogue (bias + relu)
+    return false;
 }
 }  // namespace issk

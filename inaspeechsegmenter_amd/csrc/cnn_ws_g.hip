@@ -2,5 +2,5 @@
 #include "conv_ws.h"
 
 namespace issk {
-void iss_ws_launch_fs_3x3(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded) { launch_ws_fused_rowmajor<3, 3, true>(a, grid, st, padded); }
+ISS_WS_LAUNCHER(iss_ws_launch_fs_3x3) { return launch_ws_fused_rowmajor<3, 3, true>(a, grid, st, i); }
 }  // namespace issk

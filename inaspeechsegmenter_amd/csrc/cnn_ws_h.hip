@@ -3,11 +3,13 @@
 #include "conv_ws.h"
 
 namespace issk {
-void iss_ws_launch_f32_fused_5x3(const ConvArgs& a, dim3 grid, hipStream_t st) {      // relu + 2x2 max-pool (epi_is_pool_relu)
-    hipLaunchKernelGGL((conv_x3_ws_kernel<5, 3, false, false, true, 1, 1, false, true>), grid, dim3(512), 0, st, a);
+ISS_WS_LAUNCHER(iss_ws_launch_f32_fused_5x3) {         // relu + 2x2 max-pool
+    ISS_WS_TRY(ConvKernel::WsF32Fused, 5, 3, false, false, true, 1, 1, false, true)
+    return false;
 }
-void iss_ws_launch_f32_nh2_3x3(const ConvArgs& a, dim3 grid, hipStream_t st, bool tr) {  // tr: bias + relu, transposed; else pooled relu
-    if (tr) hipLaunchKernelGGL((conv_x3_ws_kernel<3, 3, false, true, false, 2, 1, false, true>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((conv_x3_ws_kernel<3, 3, false, false, false, 2, 1, false, true>), grid, dim3(512), 0, st, a);
+ISS_WS_LAUNCHER(iss_ws_launch_f32_nh2_3x3) {           // bias + relu, transposed; or pooled relu
+    ISS_WS_TRY(ConvKernel::WsNh2F32, 3, 3, false, true, false, 2, 1, false, true)
+    ISS_WS_TRY(ConvKernel::WsNh2F32, 3, 3, false, false, false, 2, 1, false, true)
+    return false;
 }
 }  // namespace issk

@@ -2,5 +2,5 @@
 #include "conv_ws.h"
 
 namespace issk {
-void iss_ws_launch_ring_5x5(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded) { launch_ws_fused_rowmajor<5, 5, false>(a, grid, st, padded); }
+ISS_WS_LAUNCHER(iss_ws_launch_ring_5x5) { return launch_ws_fused_rowmajor<5, 5, false>(a, grid, st, i); }
 }  // namespace issk

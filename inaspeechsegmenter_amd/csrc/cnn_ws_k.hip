@@ -3,7 +3,8 @@
 #include "conv_ws.h"
 
 namespace issk {
-void iss_ws_launch_ncb1_5x3(const ConvArgs& a, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL((conv_x3_ws_kernel<5, 3, false, false, true, 1, 1, false, false, 1>), grid, dim3(512), 0, st, a);
+ISS_WS_LAUNCHER(iss_ws_launch_ncb1_5x3) {
+    ISS_WS_TRY(ConvKernel::WsNcb1, 5, 3, false, false, true, 1, 1, false, false, 1)
+    return false;
 }
 }  // namespace issk

@@ -94,6 +94,26 @@ struct ConvArgs {
                              // the launch's own operand type is
 };
 
+// Which instantiation a launch is: the kernel family (one value per launch site; Wq3h is Wq3 on a CHL input) and the template
+// arguments.  Selection (conv_select.h) fills it, inst_name spells it for the profiler, and every launcher compares it against the
+// instantiations its unit holds -- nothing decides a template argument a second time.  The arguments without a field of their own
+// (FS, RING, F32, NCB of conv_x3_ws_kernel; STRIDED, DUAL of conv_x3_pws2_kernel) are what `kernel` says.
+enum class ConvKernel { Declined, Dhl, Pwc, Pws2Dual, Direct1, WsNh2F32, Wq3, Wq3h, WsNh2, WsPlainU, WsPlain, WsF32Fused, WsRing, WsFs, WsNcb1, Wq, Ws, Fp,
+                        Patch1, Gather, Pws2Strided, Pws2, Pws, Pw, X3, Igemm };
+struct ConvInst {
+    ConvKernel kernel = ConvKernel::Declined;
+    int kh = 0, kw = 0, mode = 0, epi = 0, nh = 1, kind = -1, c1 = 0, c3 = 0;
+    bool padded = false, tr = false, fused = false, f16 = false, window = false, has_res = false, simple_pw = false;
+    bool out_hl = false;     // OUT_HL of the one-wave-per-SIMD kernels: their own CHL epilogue
+};
+// One branch of a launcher, which takes (const ConvArgs& a, ..., hipStream_t st, const ConvInst& i) and returns whether it launched:
+// KERNEL (an instantiation, in parentheses) runs when WHEN finds in `i` every template argument it fixes.  The per-family forms
+// built on it (ISS_WS_TRY, ISS_FP_TRY, ...) write each argument once, for the test and for the template.
+#define ISS_LAUNCH_IF(WHEN, KERNEL, GRID, THREADS, LDS) \
+    if (WHEN) { hipLaunchKernelGGL(KERNEL, GRID, dim3(THREADS), LDS, st, a); return true; }
+// body of a *_compiled(kh, kw) predicate over a family's shape list
+#define ISS_SHAPE_IS(KH_, KW_) if (kh == KH_ && kw == KW_) return true;
+
 // ------------------------------------------------------------------------------------------
 // CHL: the activation layout a footprint kernel's producer writes for a footprint kernel that consumes it (round 6).
 // An f32 NHWC tensor costs its consumer a global load into registers, ~7 VALU per element for the bf16 hi / lo operand split and two

@@ -192,6 +192,6 @@ __host__ __device__ inline int dhl_col_tiles(int Cout) { return (Cout + DHL_BN -
 inline unsigned dhl_npad(long long windows) { return (unsigned)((windows + DHL_BM - 1) / DHL_BM * DHL_BM); }
 inline size_t dhl_packed_elems(int K, int Cout = DHL_BN) { return (size_t)dhl_col_tiles(Cout) * (K / 8) * 2 * DHL_BN * 8; }   // [column tile][K / 32][4][2][192][8]
 void iss_dhl_pack(const uint16_t* wh, const uint16_t* wl, uint16_t* out, int Cout, int Kpad, int K, hipStream_t st);
-void iss_dhl_launch(const DhlArgs& a, hipStream_t st, bool f16);
+bool iss_dhl_launch(const DhlArgs& a, hipStream_t st, const ConvInst& i);
 
 }  // namespace issk

@@ -420,30 +420,29 @@ __global__ __launch_bounds__(256, 2) void conv_x3_fp_kernel(const ConvArgs p) {
     wait_vmcnt<0>();                                 // the unused prefetches of the last chunk
 }
 
+// Launches conv_x3_fp_kernel<KH, KW, PADDED, TR, FUSED, NH> if `i` names exactly that instantiation
+#define ISS_FP_TRY(KH_, KW_, P_, TR_, FU_, NH_)                                                                                   \
+    ISS_LAUNCH_IF(i.kernel == ConvKernel::Fp && i.kh == KH_ && i.kw == KW_ && i.padded == P_ && i.tr == TR_ && i.fused == FU_ && \
+                  i.nh == NH_, (conv_x3_fp_kernel<KH_, KW_, P_, TR_, FU_, NH_>), grid, 256, 0)
 // one filter shape, all (PADDED, TR) variants; fused = shared first layer (ConvArgs::f_*), unpadded shapes with >= 12
 // taps only (one footprint slice per tap)
 template <int KH, int KW>
-void launch_fp_shape(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded, bool tr, bool fused, int nh) {
+bool launch_fp_shape(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i) {
     if constexpr (KH * KW >= 12) {
-        if (fused) {
-            if (tr) hipLaunchKernelGGL((conv_x3_fp_kernel<KH, KW, false, true, true>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((conv_x3_fp_kernel<KH, KW, false, false, true>), grid, dim3(256), 0, st, a);
-            return;
-        }
+        ISS_FP_TRY(KH, KW, false, true, true, 1)
+        ISS_FP_TRY(KH, KW, false, false, true, 1)
     }
     if constexpr (KH == 3 && KW == 3) {              // two 64-column halves per workgroup (see iss_fp_has_nh2)
-        if (nh == 2) {
-            if (padded && tr) hipLaunchKernelGGL((conv_x3_fp_kernel<KH, KW, true, true, false, 2>), grid, dim3(256), 0, st, a);
-            else if (padded) hipLaunchKernelGGL((conv_x3_fp_kernel<KH, KW, true, false, false, 2>), grid, dim3(256), 0, st, a);
-            else if (tr) hipLaunchKernelGGL((conv_x3_fp_kernel<KH, KW, false, true, false, 2>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((conv_x3_fp_kernel<KH, KW, false, false, false, 2>), grid, dim3(256), 0, st, a);
-            return;
-        }
+        ISS_FP_TRY(KH, KW, true, true, false, 2)
+        ISS_FP_TRY(KH, KW, true, false, false, 2)
+        ISS_FP_TRY(KH, KW, false, true, false, 2)
+        ISS_FP_TRY(KH, KW, false, false, false, 2)
     }
-    if (padded && tr) hipLaunchKernelGGL((conv_x3_fp_kernel<KH, KW, true, true>), grid, dim3(256), 0, st, a);
-    else if (padded) hipLaunchKernelGGL((conv_x3_fp_kernel<KH, KW, true, false>), grid, dim3(256), 0, st, a);
-    else if (tr) hipLaunchKernelGGL((conv_x3_fp_kernel<KH, KW, false, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_x3_fp_kernel<KH, KW, false, false>), grid, dim3(256), 0, st, a);
+    ISS_FP_TRY(KH, KW, true, true, false, 1)
+    ISS_FP_TRY(KH, KW, true, false, false, 1)
+    ISS_FP_TRY(KH, KW, false, true, false, 1)
+    ISS_FP_TRY(KH, KW, false, false, false, 1)
+    return false;
 }
 inline bool iss_fp_has_nh2(int kh, int kw) { return kh == 3 && kw == 3; }
 
@@ -452,10 +451,8 @@ inline bool iss_fp_has_nh2(int kh, int kw) { return kh == 3 && kw == 3; }
 // Filter shapes the footprint kernel is instantiated for (the tap loop is unrolled at compile time); other shapes
 // run on conv_x3_kernel.  One extern launcher per shape, defined in the cnn_fp_*.hip units.
 #define ISS_FP_SHAPES(X) X(3, 3) X(5, 3) X(3, 5) X(5, 5) X(2, 2) X(4, 4) X(1, 3) X(3, 1)
-#define ISS_FP_DECL(KH_, KW_) void iss_fp_launch_##KH_##x##KW_(const issk::ConvArgs& a, dim3 grid, hipStream_t st, bool padded, bool tr, bool fused, int nh);
+#define ISS_FP_DECL(KH_, KW_) bool iss_fp_launch_##KH_##x##KW_(const issk::ConvArgs& a, dim3 grid, hipStream_t st, const issk::ConvInst& i);
 ISS_FP_SHAPES(ISS_FP_DECL)
 #undef ISS_FP_DECL
-#define ISS_FP_DEFINE(KH_, KW_)                                                                               \
-    void iss_fp_launch_##KH_##x##KW_(const issk::ConvArgs& a, dim3 grid, hipStream_t st, bool padded, bool tr, bool fused, int nh) { \
-        issk::launch_fp_shape<KH_, KW_>(a, grid, st, padded, tr, fused, nh);                                          \
-    }
+#define ISS_FP_DEFINE(KH_, KW_) \
+    bool iss_fp_launch_##KH_##x##KW_(const issk::ConvArgs& a, dim3 grid, hipStream_t st, const issk::ConvInst& i) { return issk::launch_fp_shape<KH_, KW_>(a, grid, st, i); }

@@ -551,7 +551,7 @@ inline bool pws2_strided_supported(const ConvArgs& a, int Ho, int Wo) {
     return pws2_supported(a) && a.M < (1ll << 31) && a.act <= 1 && !a.ps &&
            ((long long)(BM / ((long long)Ho * Wo) + 2) * a.img_stride * 4 < (1ll << 31));
 }
-void iss_pws_launch(const ConvArgs& a, dim3 grid, hipStream_t st);               // cnn_pw.hip
+bool iss_pws_launch(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i);       // cnn_pw.hip
 // two-source form (ConvArgs::in2): a = the row that carries the residual, with res cleared, bias / wh / wl / Kpad of the
 // concatenated matrix; every byte offset of a tile relative to its first pixel stays below 2^31 in both sources
 inline bool pws2_dual_supported(const ConvArgs& a) {
@@ -560,6 +560,6 @@ inline bool pws2_dual_supported(const ConvArgs& a) {
            (long long)BM * a.Cin * 4 < (1ll << 31) && (long long)a.Cout * a.Kpad * 2 < (1ll << 31) && (long long)BM * a.Cout * 4 < (1ll << 31) &&
            ((long long)(BM / ((long long)a.Hq * a.Wq) + 2) * a.H2 * a.W2 * a.Cin2 * 4 < (1ll << 31));
 }
-void iss_pws2_launch(const ConvArgs& a, hipStream_t st, bool strided = false, bool dual = false);   // 128 x 128 tiles: sets its own column tiling and grid
+bool iss_pws2_launch(const ConvArgs& a, hipStream_t st, const ConvInst& i);   // 128 x 128 tiles (plain, strided or two-source): sets its own column tiling and grid
 
 }  // namespace issk

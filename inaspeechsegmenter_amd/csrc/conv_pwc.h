@@ -342,15 +342,20 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pwc_kernel(const ConvArgs p) {
 
 // host: rows j (expansion, in place, relu, residual) and j + 1 (reduction to 128 channels) of an op program as one launch.
 // a: ConvArgs of row j with wh2 / wl2 / bias2 / out2 / act2 of row j + 1.
-// (C1, C3) pairs the kernel is instantiated for: ResNet-101's stages 1-3 and the transitions between them (cnn_pwc.hip)
-inline bool pwc_compiled(int c1, int c3) {
-    return (c1 == 32 && (c3 == 32 || c3 == 64)) || (c1 == 64 && (c3 == 64 || c3 == 128)) || (c1 == 128 && c3 == 128);
+// <K1T, NC3> pairs the kernel is instantiated for, in units of 32 channels: ResNet-101's stages 1-3 and the transitions between them
+// (cnn_pwc.hip dispatches over the same list)
+#define ISS_PWC_PAIRS(X) X(1, 1) X(1, 2) X(2, 2) X(2, 4) X(4, 4)
+inline bool pwc_compiled(int c1, int c3) {           // input channels of the first GEMM, outputs of the second
+#define ISS_PWC_IS(K1T_, NC3_) if (c1 == 32 * K1T_ && c3 == 32 * NC3_) return true;
+    ISS_PWC_PAIRS(ISS_PWC_IS)
+#undef ISS_PWC_IS
+    return false;
 }
 inline bool pwc_supported(const ConvArgs& a) {
     return a.bias && a.bias2 && a.res && a.res == a.out && !a.ps && a.act == 1 && a.act2 <= 1 && a.pp == 1 && a.Kpad == a.Cin &&
            pwc_compiled(a.Cin, a.Cout2) && a.Cout % 32 == 0 && a.Cout >= 128 && a.Cout <= 2048 &&
            a.M * (long long)a.Cout < (1ll << 40);
 }
-void iss_pwc_launch(const ConvArgs& a, hipStream_t st);
+bool iss_pwc_launch(const ConvArgs& a, hipStream_t st, const ConvInst& i);
 
 }  // namespace issk

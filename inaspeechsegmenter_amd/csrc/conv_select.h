@@ -1,5 +1,7 @@
-// Which kernel runs a conv row of the op program, decided on the host without touching the device (cnn.hip launches by the
-// answer: launch_conv / inst_name).  Every condition a kernel family is taken under is written here once.
+// Which kernel runs a conv row of the op program, decided on the host without touching the device.  Every condition a kernel family
+// is taken under is written here once, and the answer names the instantiation once (ConvChoice::inst, a ConvInst of conv_common.h):
+// inst_name spells it for the profiler, launch_conv (cnn.hip) hands it to the family's launcher, and a launcher runs the instantiation
+// whose template arguments equal it or reports that it holds none -- it has nothing else to choose by.
 #pragma once
 #include <array>
 #include <numeric>
@@ -23,18 +25,8 @@ inline bool ws_recip_exact(int W, long long limit) {
     const long long m = (65536 + W - 1) / W;
     return limit * (m * W - 65536) < 65536 && limit * m < (1ll << 31);
 }
-inline bool ws_shape_compiled(int kh, int kw) {
-#define ISS_WS_HAS(KH_, KW_) if (kh == KH_ && kw == KW_) return true;
-    ISS_WS_SHAPES(ISS_WS_HAS)
-#undef ISS_WS_HAS
-    return false;
-}
-inline bool fp_shape_compiled(int kh, int kw) {
-#define ISS_FP_HAS(KH_, KW_) if (kh == KH_ && kw == KW_) return true;
-    ISS_FP_SHAPES(ISS_FP_HAS)
-#undef ISS_FP_HAS
-    return false;
-}
+inline bool ws_shape_compiled(int kh, int kw) { ISS_WS_SHAPES(ISS_SHAPE_IS) return false; }
+inline bool fp_shape_compiled(int kh, int kw) { ISS_FP_SHAPES(ISS_SHAPE_IS) return false; }
 #ifdef ISS_PW_NO_ASM_RING                            // build-time escape (Makefile): none of the asm-load kernels of conv_pw.h / conv_pwc.h
 constexpr bool asm_ring_ok = false;
 #else
@@ -112,20 +104,15 @@ inline int tile_rows(IssNet& n, int r, const ConvArgs& a, int hi, int lo, int ca
     return n.fp_pix.emplace(std::array<int, 4>{r, hi, lo, cap}, tmr).first->second;
 }
 
-// One value per launch site.  (Wq3h is Wq3 on a CHL input.)
-enum class ConvKernel { Declined, Dhl, Pwc, Pws2Dual, Direct1, WsNh2F32, Wq3, Wq3h, WsNh2, WsPlainU, WsPlain, WsF32Fused, WsRing, WsFs, WsNcb1, Wq, Ws, Fp,
-                        Patch1, Gather, Pws2Strided, Pws2, Pws, Pw, X3, Igemm };
 enum class FirstLayer { None, Fused, Gather, Alone };   // a deferred first layer: staged by a footprint kernel, read by the gather kernel, or run by itself first
 enum class OutLayout { F32, Chl, ChlDense };
 struct ChlState { unsigned np = 0; bool f16 = false, dense = false; };   // np != 0: the buffer holds a CHL tensor of np pixels per plane (fp16 halves; of a dense layer)
 
 struct ConvChoice {
-    ConvKernel kernel = ConvKernel::Declined;
+    ConvInst inst;                           // the instantiation: kernel family and template arguments (what inst_name spells and the launcher matches)
     int row = -1, partner = -1, rows = 1;    // the row launched; the chained row behind it / the projection row in front of it; program rows consumed
     int tag = ISS_PROF_GATHER;               // kernel class the profiler counts the launch under
-    // template arguments (what inst_name spells and launch_conv passes on)
-    int kh = 0, kw = 0, mode = 0, epi = 0, nh = 1, kind = -1, c1 = 0, c3 = 0, tmr = 0;
-    bool padded = false, tr = false, fused = false, f16 = false, window = false, has_res = false, simple_pw = false;
+    int tmr = 0;                             // rows per tile where the kernel takes them from the host (ConvArgs::tmr)
     FirstLayer first = FirstLayer::None;
     OutLayout out = OutLayout::F32;
     bool out_f16 = false;                    // CHL output in fp16 (not bf16) halves
@@ -268,7 +255,7 @@ inline bool want_hl_out(const ConvEnv& env, int r, long long npix) {
     if (npix != (long long)env.bc * Q[ISS_C_H] * Q[ISS_C_W] || !chl_fits(npix, R[ISS_C_COUT])) return false;
     ConvEnv f32in = env;
     f32in.layout = nullptr;
-    return select_conv(f32in, r + 1, -1).kernel == ConvKernel::Wq3 && sole_reader_is_next(env, r);
+    return select_conv(f32in, r + 1, -1).inst.kernel == ConvKernel::Wq3 && sole_reader_is_next(env, r);
 }
 // row r is a pooled conv launch (conv_x3_wq3h_kernel<1, ..>) whose output, flattened, is read by the dense layer of row r + 1 and by
 // nobody else: it may write the CHL tensor conv_dhl_kernel fetches by LDS-DMA (window = "pixel", feature = "channel").  The selector
@@ -303,6 +290,7 @@ inline ConvChoice select_row(const ConvEnv& env, int r, int pend, int dual, int 
     // epi_is_* helpers it calls may test a ConvArgs pointer for null (and res == out), never read through it or its value
     static const float has = 0.f;
     ConvChoice ch;
+    ConvInst& inst = ch.inst;                                     // every field a launch's template fixes ends up here, whichever way it was decided
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     const bool padded = fill_geometry(a, R, bc);
@@ -315,14 +303,14 @@ inline ConvChoice select_row(const ConvEnv& env, int r, int pend, int dual, int 
     const bool small_row = small_row_of(env, r, pend, &f16_dense_pw);
     const bool x3 = env.x3mode() && !small_row, f16mode = env.f16mode();
     const ChlState in_l = env.layout_of(R[ISS_C_IN]);            // (only conv_x3_wq3h_kernel and conv_dhl_kernel read the CHL layout)
-    ch.row = r; ch.kh = a.H_k; ch.kw = a.kw; ch.padded = padded; ch.window = window;
+    ch.row = r; inst.kh = a.H_k; inst.kw = a.kw; inst.padded = padded; inst.window = window;
     if (in_l.np && in_l.dense) {
         // the first dense layer on the flattened-feature CHL tensor conv4 wrote for it (want_dhl_out): both operands by LDS-DMA
-        ch.kernel = ConvKernel::Dhl; ch.f16 = in_l.f16; ch.in_np = in_l.np; ch.tag = ISS_PROF_PW;
+        inst.kernel = ConvKernel::Dhl; inst.f16 = in_l.f16; ch.in_np = in_l.np; ch.tag = ISS_PROF_PW;
         return ch;
     }
     a.mode = patch ? 2 : window ? 1 : ((a.Cin % (x3 ? XBK : 4) == 0) ? 0 : 1);
-    ch.mode = a.mode;
+    inst.mode = a.mode;
     const double fl = conv_flops(R, (double)a.M);
     if (chain >= 0) {
         // row r (in-place 1x1 expansion + identity residual + relu) and row `chain` = r + 1 (the next Bottleneck's 1x1 reduction
@@ -332,7 +320,7 @@ inline ConvChoice select_row(const ConvEnv& env, int r, int pend, int dual, int 
         a.out = R[ISS_C_RES] == R[ISS_C_OUT] ? const_cast<float*>(a.res) : nullptr;
         a.act2 = Q[ISS_C_ACT]; a.Cout2 = Q[ISS_C_COUT];
         if (!x3 || a.mode != 0 || !present(R) || !pwc_supported(a)) return ch;
-        ch.kernel = ConvKernel::Pwc; ch.partner = chain; ch.rows = 2; ch.c1 = a.Cin / 32; ch.c3 = a.Cout2 / 32; ch.tag = ISS_PROF_PW;
+        inst.kernel = ConvKernel::Pwc; ch.partner = chain; ch.rows = 2; inst.c1 = a.Cin / 32; inst.c3 = a.Cout2 / 32; ch.tag = ISS_PROF_PW;
         return ch;
     }
     if (dual >= 0) {
@@ -343,7 +331,7 @@ inline ConvChoice select_row(const ConvEnv& env, int r, int pend, int dual, int 
         a.bias = &has; a.res = nullptr;
         a.Kpad = a.Cin + a.Cin2;
         if (!x3 || a.mode != 0 || !present(R) || !present(P) || !pws2_dual_supported(a)) return ch;
-        ch.kernel = ConvKernel::Pws2Dual; ch.partner = dual; ch.rows = 2; ch.tag = ISS_PROF_PW;
+        inst.kernel = ConvKernel::Pws2Dual; inst.simple_pw = true; ch.partner = dual; ch.rows = 2; ch.tag = ISS_PROF_PW;
         return ch;
     }
     const int taps = a.H_k * a.kw;
@@ -433,18 +421,18 @@ inline ConvChoice select_row(const ConvEnv& env, int r, int pend, int dual, int 
     }
     if (Rp) ch.first = fused ? FirstLayer::Fused : gfused ? FirstLayer::Gather : FirstLayer::Alone;
     ws = ws && fused;
-    if (gfused) ch.mode = a.mode = fs1 ? 4 : 3;
-    ch.fused = fused; ch.tmr = tmr;
+    if (gfused) inst.mode = a.mode = fs1 ? 4 : 3;
+    inst.fused = fused; ch.tmr = tmr;
     ch.tag = ws || ws_plain || ws_plain_u || ws_nh2 ? ISS_PROF_WS : fp ? ISS_PROF_FP : !x3 ? ISS_PROF_F32 : ISS_PROF_GATHER;
-    ch.tr = a.pp == 1 && a.Cout % 4 == 0;            // float4 epilogue on transposed accumulators (the families below that differ say so)
+    inst.tr = a.pp == 1 && a.Cout % 4 == 0;            // float4 epilogue on transposed accumulators (the families below that differ say so)
     // one-channel 3x3 'same' first layer of a non-PATCH network: direct f32 kernel (either arithmetic mode)
     const bool direct1 = !(diag & ISS_DIAG_NO_DIRECT1) && !patch && pend < 0 && a.Cin == 1 && a.H_k == 3 && a.kw == 3 && unit_stride && a.pt_ == 1 &&
                          a.pl_ == 1 && R[ISS_C_HO] == a.H && R[ISS_C_WO] == a.W && a.pp == 1 && !a.res && !a.ps && a.act <= 1 && a.bias &&
                          a.Cout % 4 == 0 && a.Cout <= 256 && a.M * (long long)(a.Cout / 4) < (1ll << 34);
     if (direct1) {
-        ch.kernel = ConvKernel::Direct1; ch.tag = ISS_PROF_GATHER;
+        inst.kernel = ConvKernel::Direct1; ch.tag = ISS_PROF_GATHER;
     } else if (ws_nh2 && !x3) {
-        ch.kernel = ConvKernel::WsNh2F32; ch.tr = a.pp == 1;
+        inst.kernel = ConvKernel::WsNh2F32; inst.tr = a.pp == 1; inst.nh = 2; inst.epi = 1;
     } else if (ws_nh2) {
         // one-wave-per-SIMD variant (conv_wq3.h): unpadded, bias + relu (kind 0) or relu + 2 x 1 max-pool (kind 1)
         int kind = -1;
@@ -455,48 +443,48 @@ inline ConvChoice select_row(const ConvEnv& env, int r, int pend, int dual, int 
         }
         if (kind >= 0 && (ch.tmr = tile_rows(n, r, a, WQ3_TM, WQ3_TM - 64, WQ3_PIX)) <= 0) kind = -1;
         if (kind >= 0) {
-            ch.kernel = in_l.np ? ConvKernel::Wq3h : ConvKernel::Wq3;       // the producer wrote the CHL layout for this launch (want_hl_out)
-            ch.kind = kind; ch.in_np = in_l.np; ch.f16 = in_l.np && in_l.f16;
-        } else {                                         // template arguments as iss_ws_launch_nh2_3x3* pick them: <KH,KW,PADDED,TR,FUSED,NH,EPI>
-            ch.kernel = ConvKernel::WsNh2;
-            ch.tr = (padded && !nh2_pad_pool) || (a.pp == 1 && a.Cout % 4 == 0);
-            ch.epi = padded ? 1 : (ch.tr ? epi_is_simple_tr(a) : epi_is_pool_relu(a));
+            inst.kernel = in_l.np ? ConvKernel::Wq3h : ConvKernel::Wq3;       // the producer wrote the CHL layout for this launch (want_hl_out)
+            inst.kind = kind; ch.in_np = in_l.np; inst.f16 = in_l.np && in_l.f16;
+        } else {
+            inst.kernel = ConvKernel::WsNh2; inst.nh = 2;
+            inst.tr = (padded && !nh2_pad_pool) || (a.pp == 1 && a.Cout % 4 == 0);
+            inst.epi = padded ? 1 : (inst.tr ? epi_is_simple_tr(a) : epi_is_pool_relu(a));
         }
     } else if (ws_plain_u) {
-        ch.kernel = ConvKernel::WsPlainU; ch.tr = a.pp == 1;
+        inst.kernel = ConvKernel::WsPlainU; inst.tr = a.pp == 1; inst.epi = 1;
     } else if (ws_plain) {
-        ch.kernel = ConvKernel::WsPlain; ch.epi = epi_is_simple_tr(a);
+        inst.kernel = ConvKernel::WsPlain; inst.epi = epi_is_simple_tr(a);
     } else if (ws && ws_f32) {
-        ch.kernel = ConvKernel::WsF32Fused;
+        inst.kernel = ConvKernel::WsF32Fused; inst.epi = 1;
     } else if (ws && ws_ring) {
-        ch.kernel = ConvKernel::WsRing; ch.epi = epi_is_pool_relu_any(a);
+        inst.kernel = ConvKernel::WsRing; inst.tr = false; inst.epi = epi_is_pool_relu_any(a);
     } else if (ws && ws_fs) {
-        ch.kernel = ConvKernel::WsFs; ch.tr = fs_tr_ok; ch.epi = fs_tr_ok ? 1 : (int)epi_is_pool_relu_any(a);
+        inst.kernel = ConvKernel::WsFs; inst.tr = fs_tr_ok; inst.epi = fs_tr_ok ? 1 : (int)epi_is_pool_relu_any(a);
     } else if (ws) {
-        const bool rowmajor_pool = fused && !padded && !ch.tr && epi_is_pool_relu(a) && unit_stride && a.Cin >= 2 * F2_CH;
+        const bool rowmajor_pool = fused && !padded && !inst.tr && epi_is_pool_relu(a) && unit_stride && a.Cin >= 2 * F2_CH;
         // <= 32 output channels: one 32-column block per workgroup (conv_ws.h NCB = 1) instead of half-empty 64-column ones
         if (!(diag & ISS_DIAG_NO_NCB1) && rowmajor_pool && !fs1 && a.Cout <= 32 && iss_ws_ncb1_compiled(a.H_k, a.kw)) {
-            ch.kernel = ConvKernel::WsNcb1;
+            inst.kernel = ConvKernel::WsNcb1; inst.epi = 1;
         } else if (!(diag & ISS_DIAG_NO_WQ) && rowmajor_pool && a.pp == 4 && a.ph == 2 && iss_wq_compiled(a.H_k, a.kw) && a.M % 4 == 0 &&
                    (a.M / 4) * (long long)a.Cout * 4 < 0xFFF00000ll && a.Cout <= 256 && (ch.tmr = tile_rows(n, r, a, WS_TM, WS_TM - 32, WQ_PIX)) > 0) {
             // one-wave-per-SIMD, two-footprint variant (conv_wq.h): the dominant launch of the segmenter nets
             // (tmr, rows per tile: the largest multiple of 4 (<= 512) whose footprint fits the kernel's 800 pixels)
-            ch.kernel = ConvKernel::Wq; ch.f16 = f16mode;
+            inst.kernel = ConvKernel::Wq; inst.f16 = f16mode;
         } else {
-            ch.kernel = ConvKernel::Ws; ch.epi = ch.tr ? epi_is_simple_tr(a) : epi_is_pool_relu_any(a);
+            inst.kernel = ConvKernel::Ws; inst.epi = inst.tr ? epi_is_simple_tr(a) : epi_is_pool_relu_any(a);
         }
     } else if (fp) {
-        ch.kernel = ConvKernel::Fp;
+        inst.kernel = ConvKernel::Fp;
         // 128 output channels per workgroup where the layer has them: one LDS footprint serves two 64-column halves
-        ch.nh = (!fused && !(diag & ISS_DIAG_NO_NH2) && iss_fp_has_nh2(a.H_k, a.kw) && a.Cout % (2 * BN) == 0) ? 2 : 1;
-        ch.tr = !(diag & ISS_DIAG_NO_TR) && ch.tr;       // diagnostic: row-major epilogue everywhere
+        inst.nh = (!fused && !(diag & ISS_DIAG_NO_NH2) && iss_fp_has_nh2(a.H_k, a.kw) && a.Cout % (2 * BN) == 0) ? 2 : 1;
+        inst.tr = !(diag & ISS_DIAG_NO_TR) && inst.tr;       // diagnostic: row-major epilogue everywhere
     } else if (x3 && patch && taps <= XBK && a.M < (1ll << 31)) {
         // fp16 mode: fp16 halves of the normalised window and of the weights here too (|z| <= sqrt(68 * 24), far inside fp16's range)
-        ch.kernel = ConvKernel::Patch1; ch.tag = ISS_PROF_PATCH1; ch.tr = ch.tr && !a.res; ch.f16 = f16mode;
+        inst.kernel = ConvKernel::Patch1; ch.tag = ISS_PROF_PATCH1; inst.tr = inst.tr && !a.res; inst.f16 = f16mode;
     } else if (x3 && gfused) {
-        ch.kernel = ConvKernel::Gather;
+        inst.kernel = ConvKernel::Gather;
     } else if (x3) {
-        const bool pointwise = !(diag & ISS_DIAG_NO_PW) && a.mode == 0 && ch.tr && taps == 1 && unit_stride && a.pt_ == 0 &&
+        const bool pointwise = !(diag & ISS_DIAG_NO_PW) && a.mode == 0 && inst.tr && taps == 1 && unit_stride && a.pt_ == 0 &&
                                a.pl_ == 0 && R[ISS_C_HO] == a.H && R[ISS_C_WO] == a.W && a.Kpad == a.Cin;
         if (pointwise) ch.tag = ISS_PROF_PW;
         // Streaming pointwise kernels (conv_pw.h) for K <= 2048.  The segmenter nets' first dense layer (K = 4992 / 8320,
@@ -507,27 +495,29 @@ inline ConvChoice select_row(const ConvEnv& env, int r, int pend, int dual, int 
         const bool no_pws2 = (diag & ISS_DIAG_NO_PWS2) != 0;                // diagnostic: 64-column tiles everywhere
         const bool pws_ok = !no_pws && a.Kpad <= 2048 && !f16_dense_pw;      // (fp16 mode: a dense layer that would otherwise run in exact f32)
         // strided 1x1 (the shortcut projections): the 128-column kernel on a strided pixel list
-        const bool pw_strided = pws_ok && !no_pws2 && a.mode == 0 && ch.tr && taps == 1 && (a.sh > 1 || a.sw > 1) && a.pt_ == 0 &&
+        const bool pw_strided = pws_ok && !no_pws2 && a.mode == 0 && inst.tr && taps == 1 && (a.sh > 1 || a.sw > 1) && a.pt_ == 0 &&
                                 a.pl_ == 0 && a.Kpad == a.Cin && pws2_strided_supported(a, R[ISS_C_HO], R[ISS_C_WO]);
-        ch.simple_pw = a.act <= 1 && !a.ps; ch.has_res = a.res != nullptr;
-        if (pw_strided) { ch.kernel = ConvKernel::Pws2Strided; ch.tag = ISS_PROF_PW; }
-        else if (pointwise && pws_ok && !no_pws2 && pws2_supported(a)) ch.kernel = ConvKernel::Pws2;
-        else if (pointwise && pws_ok && pws_supported(a)) ch.kernel = ConvKernel::Pws;
-        else if (pointwise) { ch.kernel = ConvKernel::Pw; ch.f16 = f16mode; }
-        else { ch.kernel = ConvKernel::X3; ch.tr = ch.tr && a.mode != 2; }
+        inst.simple_pw = a.act <= 1 && !a.ps; inst.has_res = a.res != nullptr;
+        if (pw_strided) { inst.kernel = ConvKernel::Pws2Strided; ch.tag = ISS_PROF_PW; }
+        else if (pointwise && pws_ok && !no_pws2 && pws2_supported(a)) inst.kernel = ConvKernel::Pws2;
+        else if (pointwise && pws_ok && pws_supported(a)) inst.kernel = ConvKernel::Pws;
+        else if (pointwise) { inst.kernel = ConvKernel::Pw; inst.f16 = f16mode; }
+        else { inst.kernel = ConvKernel::X3; inst.tr = inst.tr && a.mode != 2; }
     } else {
-        ch.kernel = ConvKernel::Igemm;
+        inst.kernel = ConvKernel::Igemm;
     }
     // The output layout, once per family.  CHL through the shared pooled epilogue (conv_common.h epilogue_impl / chl_store): every kernel
     // family that ends in it -- the weight-stationary forms, conv_x3_fp_kernel, the generic gather kernel -- can hand its pooled relu
     // output to a conv_x3_wq3h_kernel the way conv_x3_wq_kernel does; the one-wave-per-SIMD kernels have epilogues of their own
-    if (ch.kernel == ConvKernel::Wq) {                   // (its own CHL epilogue; the halves follow the launch's operand type)
-        if (a.Cout % BN == 0 && want_hl_out(env, r, a.M / 4)) { ch.out = OutLayout::Chl; ch.out_np = chl_npad(a.M / 4); ch.out_f16 = ch.f16; }
-    } else if (ch.kernel == ConvKernel::Wq3h) {          // (kind 0 hands on CHL, kind 1 the dense layer's tensor; on an f32 input both write f32)
-        if (ch.kind == 0 && want_hl_out(env, r, a.M)) { ch.out = OutLayout::Chl; ch.out_np = chl_npad(a.M); }
-        if (ch.kind == 1 && want_dhl_out(env, r, a.Hq, a.Wq)) { ch.out = OutLayout::ChlDense; ch.out_np = dhl_npad(bc); }
-        ch.out_f16 = ch.out != OutLayout::F32 && ch.f16;
-    } else if (ch.kernel != ConvKernel::Wq3 && x3 && !patch && epi_is_pool_relu(a) && a.Cout % 16 == 0 && want_hl_out(env, r, a.M / a.pp)) {
+    if (inst.kernel == ConvKernel::Wq) {                   // (its own CHL epilogue; the halves follow the launch's operand type)
+        if (a.Cout % BN == 0 && want_hl_out(env, r, a.M / 4)) { ch.out = OutLayout::Chl; ch.out_np = chl_npad(a.M / 4); ch.out_f16 = inst.f16; }
+        inst.out_hl = ch.out != OutLayout::F32;
+    } else if (inst.kernel == ConvKernel::Wq3h) {          // (kind 0 hands on CHL, kind 1 the dense layer's tensor; on an f32 input both write f32)
+        if (inst.kind == 0 && want_hl_out(env, r, a.M)) { ch.out = OutLayout::Chl; ch.out_np = chl_npad(a.M); }
+        if (inst.kind == 1 && want_dhl_out(env, r, a.Hq, a.Wq)) { ch.out = OutLayout::ChlDense; ch.out_np = dhl_npad(bc); }
+        inst.out_hl = ch.out != OutLayout::F32;
+        ch.out_f16 = inst.out_hl && inst.f16;
+    } else if (inst.kernel != ConvKernel::Wq3 && x3 && !patch && epi_is_pool_relu(a) && a.Cout % 16 == 0 && want_hl_out(env, r, a.M / a.pp)) {
         ch.out = OutLayout::Chl; ch.out_np = chl_npad(a.M / a.pp); ch.out_f16 = f16mode; ch.generic_out = true;
     }
     return ch;
@@ -540,43 +530,43 @@ inline ConvChoice select_conv(const ConvEnv& env, int r, int pend) {
     // identity-residual expansion followed by the next block's reduction: one chained launch (conv_pwc.h)
     if (pair && !(env.diag & ISS_DIAG_NO_CHAIN) && chain_pair(env, r)) {
         const ConvChoice ch = select_row(env, r, -1, -1, r + 1);
-        if (ch.kernel != ConvKernel::Declined) return ch;
+        if (ch.inst.kernel != ConvKernel::Declined) return ch;
     }
     // projection shortcut followed by its expansion (ISS_C_DUALW on the next row): one two-source launch when the split-bf16
     // streaming kernels are in use (the diagnostic switches that move 1x1 layers elsewhere keep their meaning)
     if (pair && !(env.diag & ISS_DIAG_NO_DUAL) && r + 1 < env.n.nrows && env.row(r + 1)[ISS_C_DUALW] > 0) {
         const ConvChoice ch = select_row(env, r + 1, -1, r, -1);
-        if (ch.kernel != ConvKernel::Declined) return ch;
+        if (ch.inst.kernel != ConvKernel::Declined) return ch;
     }
     return select_row(env, r, pend, -1, -1);
 }
 
-// The instantiation the profiler reports (bench.py's roofline.dominant and the GPU tests read these): spelled from the fields
-// launch_conv passes to the launcher, so a name cannot disagree with the template that ran.
-inline std::string inst_name(const ConvChoice& c) {
+// The instantiation the profiler reports (bench.py's roofline.dominant and the GPU tests read these): spelled from the ConvInst the
+// launcher is keyed on.  The forms of conv_x3_ws_kernel print <KH,KW,PADDED,TR,FUSED,NH,EPI> and a word for the arguments behind them.
+inline std::string inst_name(const ConvInst& c) {
     auto B = [](bool b) { return b ? "true" : "false"; };
     char s[160];
+    auto ws = [&](const char* form) {
+        snprintf(s, sizeof s, "conv_x3_ws_kernel<%d,%d,%s,%s,%s,%d,%d%s>", c.kh, c.kw, B(c.padded), B(c.tr), B(c.fused), c.nh, c.epi, form);
+    };
     switch (c.kernel) {
     case ConvKernel::Dhl: snprintf(s, sizeof s, "conv_dhl_kernel<%s,%d>", B(c.f16), ISS_DHL_NW); break;                           // <F16,NW>
     case ConvKernel::Pwc: snprintf(s, sizeof s, "conv_x3_pwc_kernel<%d,%d>", c.c1, c.c3); break;
-    case ConvKernel::Pws2Dual: snprintf(s, sizeof s, "conv_x3_pws2_kernel<true,false,dual>"); break;
+    case ConvKernel::Pws2Dual: snprintf(s, sizeof s, "conv_x3_pws2_kernel<%s,false,dual>", B(c.simple_pw)); break;
     case ConvKernel::Direct1: snprintf(s, sizeof s, "conv1_direct3x3_kernel<%s>", B(c.window)); break;
-    case ConvKernel::WsNh2F32: snprintf(s, sizeof s, "conv_x3_ws_kernel<3,3,false,%s,false,2,1,f32>", B(c.tr)); break;
     case ConvKernel::Wq3: snprintf(s, sizeof s, "conv_x3_wq3_kernel<%d>", c.kind); break;
-    case ConvKernel::Wq3h: snprintf(s, sizeof s, "conv_x3_wq3h_kernel<%d,%s,%s>", c.kind, B(c.out != OutLayout::F32), B(c.f16)); break;   // <KIND,OUT_HL,F16>
-    case ConvKernel::WsNh2: snprintf(s, sizeof s, "conv_x3_ws_kernel<%d,%d,%s,%s,false,2,%d>", c.kh, c.kw, B(c.padded), B(c.tr), c.epi); break;
-    case ConvKernel::WsPlainU: snprintf(s, sizeof s, "conv_x3_ws_kernel<3,3,false,%s,false,1,1,plain>", B(c.tr)); break;
-    case ConvKernel::WsPlain: snprintf(s, sizeof s, "conv_x3_ws_kernel<3,3,true,true,false,1,%d>", c.epi); break;
-    case ConvKernel::WsF32Fused: snprintf(s, sizeof s, "conv_x3_ws_kernel<5,3,false,false,true,1,1,f32>"); break;
-    case ConvKernel::WsRing: snprintf(s, sizeof s, "conv_x3_ws_kernel<%d,%d,%s,false,true,1,%d,ring>", c.kh, c.kw, B(c.padded), c.epi); break;
-    case ConvKernel::WsFs: snprintf(s, sizeof s, "conv_x3_ws_kernel<%d,%d,%s,%s,true,1,%d,fs>", c.kh, c.kw, B(c.padded), B(c.tr), c.epi); break;
-    case ConvKernel::WsNcb1: snprintf(s, sizeof s, "conv_x3_ws_kernel<%d,%d,false,false,true,1,1,ncb1>", c.kh, c.kw); break;
-    case ConvKernel::Wq: snprintf(s, sizeof s, "conv_x3_wq_kernel<%d,%d,%s,%s>", c.kh, c.kw, B(c.out != OutLayout::F32), B(c.f16)); break;   // <KH,KW,OUT_HL,F16>
-    case ConvKernel::Ws: snprintf(s, sizeof s, "conv_x3_ws_kernel<%d,%d,%s,%s,true,1,%d>", c.kh, c.kw, B(c.padded), B(c.tr), c.epi); break;
+    case ConvKernel::Wq3h: snprintf(s, sizeof s, "conv_x3_wq3h_kernel<%d,%s,%s>", c.kind, B(c.out_hl), B(c.f16)); break;           // <KIND,OUT_HL,F16>
+    case ConvKernel::WsNh2: case ConvKernel::WsPlain: case ConvKernel::Ws: ws(""); break;
+    case ConvKernel::WsNh2F32: case ConvKernel::WsF32Fused: ws(",f32"); break;
+    case ConvKernel::WsPlainU: ws(",plain"); break;
+    case ConvKernel::WsRing: ws(",ring"); break;
+    case ConvKernel::WsFs: ws(",fs"); break;
+    case ConvKernel::WsNcb1: ws(",ncb1"); break;
+    case ConvKernel::Wq: snprintf(s, sizeof s, "conv_x3_wq_kernel<%d,%d,%s,%s>", c.kh, c.kw, B(c.out_hl), B(c.f16)); break;        // <KH,KW,OUT_HL,F16>
     case ConvKernel::Fp: snprintf(s, sizeof s, "conv_x3_fp_kernel<%d,%d,%s,%s,%s,%d>", c.kh, c.kw, B(c.padded), B(c.tr), B(c.fused), c.nh); break;
     case ConvKernel::Patch1: snprintf(s, sizeof s, "conv1_patch_x3_kernel<%s,%s>", B(c.tr), B(c.f16)); break;                       // <TR,F16>
     case ConvKernel::Gather: case ConvKernel::X3: snprintf(s, sizeof s, "conv_x3_kernel<%d,%s,2>", c.mode, B(c.tr)); break;
-    case ConvKernel::Pws2Strided: snprintf(s, sizeof s, "conv_x3_pws2_kernel<true,true>"); break;
+    case ConvKernel::Pws2Strided: snprintf(s, sizeof s, "conv_x3_pws2_kernel<%s,true>", B(c.simple_pw)); break;
     case ConvKernel::Pws2: snprintf(s, sizeof s, "conv_x3_pws2_kernel<%s,false>", B(c.simple_pw)); break;
     case ConvKernel::Pws: snprintf(s, sizeof s, "conv_x3_pws_kernel<%s,%s>", B(c.has_res), B(c.simple_pw)); break;
     case ConvKernel::Pw: snprintf(s, sizeof s, "conv_x3_pw_kernel<%s>", B(c.f16)); break;                                          // <F16>

@@ -592,6 +592,8 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
 // host: does the weight-stationary quad kernel take this launch?  (fused first layer, unpadded, relu + 2 x 2 max-pool, 64 output
 // channels per workgroup, 5x3; tiles of ConvArgs::tmr rows within 800 pixels)
 inline bool iss_wq_compiled(int kh, int kw) { return kh == 5 && kw == 3; }
-void iss_wq_launch_5x3(const ConvArgs& a, dim3 grid, hipStream_t st);       // a.out_hl: the CHL-output instantiation
+#define ISS_WQ_TRY(KH_, KW_, HL_, F16_) \
+    ISS_LAUNCH_IF(i.kernel == ConvKernel::Wq && i.kh == KH_ && i.kw == KW_ && i.out_hl == HL_ && i.f16 == F16_, (conv_x3_wq_kernel<KH_, KW_, HL_, F16_>), grid, 256, 0)
+bool iss_wq_launch_5x3(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i);
 
 }  // namespace issk

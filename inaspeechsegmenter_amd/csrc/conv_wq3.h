@@ -412,6 +412,6 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3_kernel(const ConvArgs p) {
 #undef ISS_WQ3_SET1
 }
 
-void iss_wq3_launch(const ConvArgs& a, dim3 grid, hipStream_t st, int kind);
+bool iss_wq3_launch(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i);
 
 }  // namespace issk

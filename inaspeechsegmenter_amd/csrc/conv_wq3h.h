@@ -461,8 +461,10 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq3h_kernel(const ConvArgs p) 
 #undef ISS_WQH_SET1
 }
 
-// kind 0 = bias + relu (f32 NHWC or, a.out_hl, CHL output), kind 1 = relu + 2 x 1 max-pool (f32 output or, a.out_hl, the CHL input of a
+// kind 0 = bias + relu (f32 NHWC or, OUT_HL, CHL output), kind 1 = relu + 2 x 1 max-pool (f32 output or, OUT_HL, the CHL input of a
 // dense layer: conv_dhl.h); a.in_hl is implied
-void iss_wq3h_launch(const ConvArgs& a, dim3 grid, hipStream_t st, int kind);
+#define ISS_WQ3H_TRY(KIND_, HL_, F16_) \
+    ISS_LAUNCH_IF(i.kernel == ConvKernel::Wq3h && i.kind == KIND_ && i.out_hl == HL_ && i.f16 == F16_, (conv_x3_wq3h_kernel<KIND_, HL_, F16_>), grid, 256, 0)
+bool iss_wq3h_launch(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i);
 
 }  // namespace issk

@@ -629,75 +629,97 @@ __global__ __launch_bounds__(512, 2) void conv_x3_ws_kernel(const ConvArgs p) {
     }
 }
 
+// Launches conv_x3_ws_kernel<KH, KW, PADDED, TR, FUSED, NH, EPI, ...> if `i` names exactly that instantiation of family K_ (the
+// arguments behind EPI -- FS, F32, NCB -- are the family's)
+#define ISS_WS_TRY(K_, KH_, KW_, P_, TR_, FU_, NH_, EPI_, ...)                                                                      \
+    ISS_LAUNCH_IF(i.kernel == K_ && i.kh == KH_ && i.kw == KW_ && i.padded == P_ && i.tr == TR_ && i.fused == FU_ && i.nh == NH_ && \
+                  i.epi == EPI_, (conv_x3_ws_kernel<KH_, KW_, P_, TR_, FU_, NH_, EPI_, ##__VA_ARGS__>), grid, 512, 0)
+
+// one filter shape of 8..16 taps behind the shared first layer, all (PADDED, TR, EPI) variants: the dominant launch of the segmenter
+// nets -- every instantiation costs minutes of compile time; the other footprint layers stay on conv_x3_fp_kernel
 template <int KH, int KW>
-void launch_ws_shape(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded, bool tr, bool fused) {
+bool launch_ws_shape(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i) {
     if constexpr (KH * KW >= 8 && KH * KW <= WS_MAXNT) {
-#define ISS_WS_LAUNCH(...) hipLaunchKernelGGL((conv_x3_ws_kernel<KH, KW, __VA_ARGS__>), grid, dim3(512), 0, st, a)
-        // instantiated for the shared-first-layer convolution (the dominant launch of the segmenter nets) -- every
-        // instantiation costs minutes of compile time; the other footprint layers stay on conv_x3_fp_kernel
-        if (!fused) return;
-        const bool fast = tr ? epi_is_simple_tr(a) : epi_is_pool_relu_any(a);
-        if (padded) {
-            if (tr) { if (fast) ISS_WS_LAUNCH(true, true, true, 1, 1); else ISS_WS_LAUNCH(true, true, true); }
-            else { if (fast) ISS_WS_LAUNCH(true, false, true, 1, 1); else ISS_WS_LAUNCH(true, false, true); }
-        } else {
-            if (tr) { if (fast) ISS_WS_LAUNCH(false, true, true, 1, 1); else ISS_WS_LAUNCH(false, true, true); }
-            else { if (fast) ISS_WS_LAUNCH(false, false, true, 1, 1); else ISS_WS_LAUNCH(false, false, true); }
-        }
-#undef ISS_WS_LAUNCH
+        ISS_WS_TRY(ConvKernel::Ws, KH, KW, true, true, true, 1, 1)
+        ISS_WS_TRY(ConvKernel::Ws, KH, KW, true, true, true, 1, 0)
+        ISS_WS_TRY(ConvKernel::Ws, KH, KW, true, false, true, 1, 1)
+        ISS_WS_TRY(ConvKernel::Ws, KH, KW, true, false, true, 1, 0)
+        ISS_WS_TRY(ConvKernel::Ws, KH, KW, false, true, true, 1, 1)
+        ISS_WS_TRY(ConvKernel::Ws, KH, KW, false, true, true, 1, 0)
+        ISS_WS_TRY(ConvKernel::Ws, KH, KW, false, false, true, 1, 1)
+        ISS_WS_TRY(ConvKernel::Ws, KH, KW, false, false, true, 1, 0)
     }
+    return false;
+}
+// the first-layer-fused row-major forms of one shape: RING (more than WS_MAXNT taps) or, with FS_, behind a zero-padded first layer
+template <int KH, int KW, bool FS_>
+bool launch_ws_fused_rowmajor(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i) {
+    constexpr ConvKernel K = FS_ ? ConvKernel::WsFs : ConvKernel::WsRing;
+    ISS_WS_TRY(K, KH, KW, true, false, true, 1, 1, FS_)
+    ISS_WS_TRY(K, KH, KW, true, false, true, 1, 0, FS_)
+    ISS_WS_TRY(K, KH, KW, false, false, true, 1, 1, FS_)
+    ISS_WS_TRY(K, KH, KW, false, false, true, 1, 0, FS_)
+    return false;
 }
 
-// Ring form (more than WS_MAXNT taps): first-layer-fused, row-major epilogue only (cnn_ws_e.hip)
-inline bool iss_ws_ring_compiled(int kh, int kw) { return (kh == 7 && kw == 7) || (kh == 5 && kw == 5) || (kh == 4 && kw == 5); }
-void iss_ws_launch_ring_7x7(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded);
-void iss_ws_launch_ring_5x5(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded);      // cnn_ws_i.hip
-void iss_ws_launch_ring_4x5(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded);      // cnn_ws_j.hip
-inline void iss_ws_launch_ring(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded) {
-    if (a.H_k == 7) iss_ws_launch_ring_7x7(a, grid, st, padded);
-    else if (a.H_k == 5) iss_ws_launch_ring_5x5(a, grid, st, padded);
-    else iss_ws_launch_ring_4x5(a, grid, st, padded);
+// Per form: the shapes it is compiled for (one list: the declarations, the *_compiled predicate and the dispatch come from it) and
+// its launchers, each defined in the unit named.
+#define ISS_WS_LAUNCHER(NAME_) bool NAME_(const ConvArgs& a, dim3 grid, hipStream_t st, const ConvInst& i)
+// Ring form (more than WS_MAXNT taps): first-layer-fused, row-major epilogue only (cnn_ws_e.hip, cnn_ws_i.hip, cnn_ws_j.hip)
+#define ISS_WS_RING_SHAPES(X) X(7, 7) X(5, 5) X(4, 5)
+// FS form (zero-padded first layer in front): first-layer-fused; row-major epilogue, and unpadded 5x3 without a fused pool with the
+// transposed simple one (bias + relu) (cnn_ws_f.hip, cnn_ws_g.hip)
+#define ISS_WS_FS_SHAPES(X) X(5, 3) X(3, 3)
+#define ISS_WS_RING_DECL(KH_, KW_) ISS_WS_LAUNCHER(iss_ws_launch_ring_##KH_##x##KW_);
+#define ISS_WS_FS_DECL(KH_, KW_) ISS_WS_LAUNCHER(iss_ws_launch_fs_##KH_##x##KW_);
+ISS_WS_RING_SHAPES(ISS_WS_RING_DECL)
+ISS_WS_FS_SHAPES(ISS_WS_FS_DECL)
+#undef ISS_WS_RING_DECL
+#undef ISS_WS_FS_DECL
+inline bool iss_ws_ring_compiled(int kh, int kw) { ISS_WS_RING_SHAPES(ISS_SHAPE_IS) return false; }
+inline bool iss_ws_fs_compiled(int kh, int kw) { ISS_WS_FS_SHAPES(ISS_SHAPE_IS) return false; }
+inline ISS_WS_LAUNCHER(iss_ws_launch_ring) {
+#define ISS_WS_RING_CASE(KH_, KW_) if (i.kh == KH_ && i.kw == KW_) return iss_ws_launch_ring_##KH_##x##KW_(a, grid, st, i);
+    ISS_WS_RING_SHAPES(ISS_WS_RING_CASE)
+#undef ISS_WS_RING_CASE
+    return false;
 }
-// FS form (zero-padded first layer in front): first-layer-fused, row-major epilogue only (cnn_ws_f.hip, cnn_ws_g.hip)
-inline bool iss_ws_fs_compiled(int kh, int kw) { return (kh == 5 && kw == 3) || (kh == 3 && kw == 3); }
-void iss_ws_launch_fs_5x3(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded);
-void iss_ws_launch_fs_3x3(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded);
-void iss_ws_launch_fs_5x3_tr(const ConvArgs& a, dim3 grid, hipStream_t st);   // unpadded, no fused pool: transposed simple epilogue (bias + relu)
-template <int KH, int KW, bool FS_>
-void launch_ws_fused_rowmajor(const ConvArgs& a, dim3 grid, hipStream_t st, bool padded) {
-    const bool fast = epi_is_pool_relu_any(a);
-#define ISS_WS_LAUNCH2(P_, E_) hipLaunchKernelGGL((conv_x3_ws_kernel<KH, KW, P_, false, true, 1, E_, FS_>), grid, dim3(512), 0, st, a)
-    if (padded) { if (fast) ISS_WS_LAUNCH2(true, 1); else ISS_WS_LAUNCH2(true, 0); }
-    else { if (fast) ISS_WS_LAUNCH2(false, 1); else ISS_WS_LAUNCH2(false, 0); }
-#undef ISS_WS_LAUNCH2
+inline ISS_WS_LAUNCHER(iss_ws_launch_fs) {
+#define ISS_WS_FS_CASE(KH_, KW_) if (i.kh == KH_ && i.kw == KW_) return iss_ws_launch_fs_##KH_##x##KW_(a, grid, st, i);
+    ISS_WS_FS_SHAPES(ISS_WS_FS_CASE)
+#undef ISS_WS_FS_CASE
+    return false;
 }
 
 // NCB = 1 form (cnn_ws_k.hip): first-layer-fused unpadded 5x3 with <= 32 output channels, pooled relu epilogue
 inline bool iss_ws_ncb1_compiled(int kh, int kw) { return kh == 5 && kw == 3; }
-void iss_ws_launch_ncb1_5x3(const ConvArgs& a, dim3 grid, hipStream_t st);
-// exact-f32 form (cnn_ws_h.hip): the fused 5x3 layer (pooled relu epilogue) and the unpadded 3x3 NH = 2 layers (simple epilogues)
+ISS_WS_LAUNCHER(iss_ws_launch_ncb1_5x3);
+// exact-f32 form (cnn_ws_h.hip): the fused 5x3 layer (pooled relu epilogue) and the unpadded 3x3 NH = 2 layers (bias + relu
+// transposed, or pooled relu)
 inline bool iss_ws_f32_fused_compiled(int kh, int kw) { return kh == 5 && kw == 3; }
-void iss_ws_launch_f32_fused_5x3(const ConvArgs& a, dim3 grid, hipStream_t st);
-void iss_ws_launch_f32_nh2_3x3(const ConvArgs& a, dim3 grid, hipStream_t st, bool tr);
+ISS_WS_LAUNCHER(iss_ws_launch_f32_fused_5x3);
+ISS_WS_LAUNCHER(iss_ws_launch_f32_nh2_3x3);
 
 // Plain (not first-layer-fused) use of the kernel: zero-padded 3x3 stride-1 layers whose 128-row tile does not fit
 // conv_x3_fp_kernel's 360-pixel footprint because the image is WIDE (ResNet-101's 32 -> 32 convolutions at 64 x 144: 580
 // pixels per 128 rows, 802 per 512 rows <= WS_PIX) -- they ran on the gather kernel at 6 x their bandwidth bound.
 inline bool iss_ws_plain_compiled(int kh, int kw) { return kh == 3 && kw == 3; }
-void iss_ws_launch_plain_3x3(const ConvArgs& a, dim3 grid, hipStream_t st);     // padded, transposed epilogue (cnn_ws_c.hip)
-void iss_ws_launch_plain_3x3_unpadded(const ConvArgs& a, dim3 grid, hipStream_t st, bool tr);   // tr: bias + relu transposed; else pooled relu
-// NH = 2 (see the kernel): unpadded 3x3 layers with a multiple of 128 output channels (cnn_ws_d.hip); tr: transposed epilogue
+// ... and the unpadded ones of 64 / 96 output channels, bias + relu transposed or pooled relu (cnn_ws_c.hip)
+ISS_WS_LAUNCHER(iss_ws_launch_plain_3x3);
+// NH = 2 (see the kernel): 3x3 layers with a multiple of 128 output channels (cnn_ws_d.hip) -- unpadded with either epilogue; zero-padded
+// transposed + simple (bias, optional relu) or row-major with relu + fused max-pool
 inline bool iss_ws_nh2_compiled(int kh, int kw) { return kh == 3 && kw == 3; }
-void iss_ws_launch_nh2_3x3(const ConvArgs& a, dim3 grid, hipStream_t st, bool tr);
-void iss_ws_launch_nh2_3x3_padded(const ConvArgs& a, dim3 grid, hipStream_t st);    // transposed + simple epilogue (epi_is_simple_tr)
-void iss_ws_launch_nh2_3x3_padded_pool(const ConvArgs& a, dim3 grid, hipStream_t st);   // row-major, relu + fused max-pool (epi_is_pool_relu)
+ISS_WS_LAUNCHER(iss_ws_launch_nh2_3x3);
 
 }  // namespace issk
 
-// Filter shapes the weight-stationary kernel is instantiated for (cnn_ws.hip)
+// Filter shapes the first-layer-fused weight-stationary kernel of 8..16 taps is instantiated for (cnn_ws_a.hip, cnn_ws_b.hip: one
+// unit each, they are the longest compiles)
 #define ISS_WS_SHAPES_A(X) X(5, 3)
 #define ISS_WS_SHAPES_B(X) X(3, 3)
 #define ISS_WS_SHAPES(X) ISS_WS_SHAPES_A(X) ISS_WS_SHAPES_B(X)
-#define ISS_WS_DECL(KH_, KW_) void iss_ws_launch_##KH_##x##KW_(const issk::ConvArgs& a, dim3 grid, hipStream_t st, bool padded, bool tr, bool fused);
+#define ISS_WS_DECL(KH_, KW_) bool iss_ws_launch_##KH_##x##KW_(const issk::ConvArgs& a, dim3 grid, hipStream_t st, const issk::ConvInst& i);
 ISS_WS_SHAPES(ISS_WS_DECL)
 #undef ISS_WS_DECL
+#define ISS_WS_DEFINE(KH_, KW_) \
+    bool iss_ws_launch_##KH_##x##KW_(const issk::ConvArgs& a, dim3 grid, hipStream_t st, const issk::ConvInst& i) { return issk::launch_ws_shape<KH_, KW_>(a, grid, st, i); }
