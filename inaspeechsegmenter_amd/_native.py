@@ -39,6 +39,8 @@ FLAC_FRAME = np.dtype([('offset', '<i8'), ('length', '<i8'), ('first_sample', '<
 FLAC_JOB = np.dtype([('src_offset', '<i8'), ('frame_begin', '<i8'), ('nframes', '<i8'), ('frames_total', '<i8'), ('channels', '<i4'),
                      ('bps', '<i4'), ('output', '<i4'), ('filter', '<i4'), ('dst_offset', '<i8'), ('frames_out', '<i8')])
 FLAC_TO_SIGNAL, FLAC_TO_STAGE = 0, 1
+# iss_window (include/iss.h): the row beside a job row of the *_windows entry points
+WINDOW = np.dtype([('s_begin', '<i8'), ('s_end', '<i8'), ('frames_total', '<i8'), ('out_begin', '<i8'), ('out_count', '<i8')])
 # ISS_FLAC_* frame status codes -> reason
 FLAC_STATUS = {1: 'reserved subframe type', 2: 'subframe header padding bit set', 3: 'wasted bits exceed the sample size',
                4: 'reserved residual coding method', 5: 'residual partition order does not fit the block',
@@ -48,6 +50,14 @@ FLAC_STATUS = {1: 'reserved subframe type', 2: 'subframe header padding bit set'
 
 class NativeError(RuntimeError):
     pass
+
+
+def _window_rows(windows, njobs):
+    """WINDOW rows for a *_windows entry point: one beside every job."""
+    wn = np.ascontiguousarray(np.array(windows, dtype=WINDOW).reshape(-1))
+    if wn.size != njobs:
+        raise ValueError(f'{wn.size} windows for {njobs} jobs')
+    return wn
 
 
 _lib = None
@@ -88,6 +98,9 @@ def lib():
         'iss_signal_pcm16_device_stream': (C.c_int, [vp, vp, i64, vp]),
         'iss_resample_filter': (C.c_int, [vp, i32, i32, pd, i64, pi32]),
         'iss_resample_pcm16': (C.c_int, [vp, vp, i64, vp, i32, i64]),
+        'iss_resample_pcm16_windows': (C.c_int, [vp, vp, i64, vp, vp, i32, i64]),
+        'iss_flac_decode_windows': (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i32, i64, pi32]),
+        'iss_adpcm_decode_windows': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32]),
         'iss_get_signal_pcm16': (C.c_int, [vp, pi16, i64, i64]),
         'iss_resample_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_flac_index': (C.c_int, [vp, i64, i64, vp, vp, i64, pi64, pi64, C.c_char_p, i32]),
@@ -364,13 +377,21 @@ class Context:
         return (src_offset, n, 1 if x.ndim == 1 else x.shape[1], RS_FORMAT[x.dtype] if fmt is None else int(fmt), fid, 0,
                 dst_offset, -(-n * up // down))
 
-    def resample(self, src, jobs, n_signal=-1):
+    def resample(self, src, jobs, n_signal=-1, windows=None):
         """iss_resample_pcm16: src = 1-D uint8 array of the stored samples of every job, jobs = rows of RS_JOB; one H2D copy,
-        one launch.  n_signal >= 0: a new resident signal of that many samples; < 0: into the signal of the last set_signal."""
+        one launch.  n_signal >= 0: a new resident signal of that many samples; < 0: into the signal of the last set_signal.
+        windows: rows of WINDOW, one beside every job (iss_resample_pcm16_windows): src holds frames [s_begin, s_end) of each
+        file, and the outputs [out_begin, out_begin + out_count) are written."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=RS_JOB))
-        self._ck(self._L.iss_resample_pcm16(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
-                                            jb.size, int(n_signal)), 'iss_resample_pcm16')
+        if windows is None:
+            self._ck(self._L.iss_resample_pcm16(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
+                                                jb.size, int(n_signal)), 'iss_resample_pcm16')
+        else:
+            wn = _window_rows(windows, jb.size)
+            self._ck(self._L.iss_resample_pcm16_windows(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
+                                                        C.c_void_p(wn.ctypes.data), jb.size, int(n_signal)),
+                     'iss_resample_pcm16_windows')
         self._keep_rs = src         # the async H2D copy reads it until the next sync
 
     def resample_signal(self, x, sr, fmt=None):
@@ -411,17 +432,25 @@ class Context:
         return st
 
     # ---- FLAC decoder (iss_flac_*): compressed frames -> resident signal (PCM16), staging buffer, or resampled
-    def flac_decode(self, src, frames, jobs, n_signal=-1):
+    def flac_decode(self, src, frames, jobs, n_signal=-1, windows=None):
         """iss_flac_decode: src = 1-D uint8 array of the compressed bytes of every job, frames = FLAC_FRAME rows, jobs = rows
         of FLAC_JOB; one H2D copy, one decode launch (+ one resample launch).  -> the per-frame status array (page-locked,
-        this context's): valid after the next synchronising call (get_loge, flac_get_stage, synchronize)."""
+        this context's): valid after the next synchronising call (get_loge, flac_get_stage, synchronize).
+        windows: rows of WINDOW, one beside every job (iss_flac_decode_windows): each job's rows are a run of its file's frames
+        that covers [s_begin, s_end), and only those samples are produced."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         fr = np.ascontiguousarray(frames, dtype=FLAC_FRAME)
         jb = np.ascontiguousarray(np.array(jobs, dtype=FLAC_JOB).reshape(-1))
         st = self._status('_flac_status', len(fr))
-        self._ck(self._L.iss_flac_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data), len(fr),
-                                         C.c_void_p(jb.ctypes.data), jb.size, int(n_signal), _ptr(st, C.c_int32)),
-                 'iss_flac_decode')
+        if windows is None:
+            self._ck(self._L.iss_flac_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data), len(fr),
+                                             C.c_void_p(jb.ctypes.data), jb.size, int(n_signal), _ptr(st, C.c_int32)),
+                     'iss_flac_decode')
+        else:
+            wn = _window_rows(windows, jb.size)
+            self._ck(self._L.iss_flac_decode_windows(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data),
+                                                     len(fr), C.c_void_p(jb.ctypes.data), C.c_void_p(wn.ctypes.data), jb.size,
+                                                     int(n_signal), _ptr(st, C.c_int32)), 'iss_flac_decode_windows')
         self._keep_flac = (src, fr)    # the async H2D copy reads them until the next sync
         return st[:len(fr)]
 
@@ -434,15 +463,23 @@ class Context:
         return self._counters('iss_flac_stats')
 
     # ---- IMA ADPCM decoder (iss_adpcm_*): stored blocks -> resident signal (PCM16), staging buffer, or resampled
-    def adpcm_decode(self, src, jobs, nblocks, n_signal=-1):
+    def adpcm_decode(self, src, jobs, nblocks, n_signal=-1, windows=None):
         """iss_adpcm_decode: src = 1-D uint8 array of the blocks of every job, jobs = rows of ADPCM_JOB, nblocks = their
         sum; one H2D copy, one decode launch (+ one resample launch).  -> the per-block status array (page-locked, this
-        context's): valid after the next synchronising call (get_loge, adpcm_get_stage, synchronize)."""
+        context's): valid after the next synchronising call (get_loge, adpcm_get_stage, synchronize).
+        windows: rows of WINDOW, one beside every job (iss_adpcm_decode_windows): each job holds exactly the blocks that its
+        samples [s_begin, s_end) lie in, and only those samples are produced."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=ADPCM_JOB).reshape(-1))
         st = self._status('_adpcm_status', nblocks)
-        self._ck(self._L.iss_adpcm_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data), jb.size,
-                                          int(nblocks), int(n_signal), _ptr(st, C.c_int32)), 'iss_adpcm_decode')
+        if windows is None:
+            self._ck(self._L.iss_adpcm_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data), jb.size,
+                                              int(nblocks), int(n_signal), _ptr(st, C.c_int32)), 'iss_adpcm_decode')
+        else:
+            wn = _window_rows(windows, jb.size)
+            self._ck(self._L.iss_adpcm_decode_windows(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
+                                                      C.c_void_p(wn.ctypes.data), jb.size, int(nblocks), int(n_signal),
+                                                      _ptr(st, C.c_int32)), 'iss_adpcm_decode_windows')
         self._keep_adpcm = src         # the async H2D copy reads it until the next sync
         return st[:int(nblocks)]
 

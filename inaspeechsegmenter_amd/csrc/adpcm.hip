@@ -9,6 +9,10 @@
 // a channel is serial, so lane c walks channel c (c, c + 64, ... for wide files) and writes its samples interleaved into
 // LDS; after a barrier the whole wave copies the block's samples to global memory, consecutive lanes to consecutive 16-bit
 // samples (a lane per block would store 16-bit samples a block apart: one cache line per store).  All offsets are 64-bit.
+//
+// Windows (include/iss.h, iss_window): WIN = true is a second instantiation for calls that carry a window beside every job.
+// The job's blocks are the file's blocks from block0 on; a block is walked into LDS as always (the walk starts at its header),
+// and the coalesced store keeps the samples inside [s_begin, s_end), at their position counted from s_begin.
 #include "decode_pass.h"
 #include <algorithm>
 #include <cstring>
@@ -68,6 +72,9 @@ struct AdJobDev {
     int32_t ch, block_align, spb, to_sig;
 };
 
+struct AdWinDev { int64_t block0, s_begin, s_end; };      // beside AdJobDev k of a windowed call (dst_byte: where sample s_begin goes)
+
+template <bool WIN>
 __global__ __launch_bounds__(AD_THREADS) void adpcm_decode_kernel(const uint8_t* __restrict__ src, const AdJobDev* __restrict__ jobs,
                                                                   int njobs, int16_t* __restrict__ sig, uint8_t* __restrict__ stage,
                                                                   int32_t* __restrict__ status) {
@@ -81,7 +88,9 @@ __global__ __launch_bounds__(AD_THREADS) void adpcm_decode_kernel(const uint8_t*
     const AdJobDev J = jobs[lo];
     const int64_t kb = b - J.block_base;
     if (kb >= J.nblocks) return;                                         // (never: the grid is the sum of the jobs' blocks)
-    const int64_t first = kb * J.spb;
+    AdWinDev W{};
+    if constexpr (WIN) W = reinterpret_cast<const AdWinDev*>(jobs + njobs)[lo];     // the window table follows the job table
+    const int64_t first = (W.block0 + kb) * J.spb;                       // the block's first sample, in the file's numbering
     const int n = (int)min((int64_t)J.spb, J.frames_total - first);      // a `fact` count may cut the last block
     const uint8_t* blk = src + J.src_off + kb * (int64_t)J.block_align;
     int st = ISS_ADPCM_OK;
@@ -89,9 +98,15 @@ __global__ __launch_bounds__(AD_THREADS) void adpcm_decode_kernel(const uint8_t*
     st = __syncthreads_or(st) ? ISS_ADPCM_STEP_INDEX : ISS_ADPCM_OK;   // (the barrier tells zero from non-zero only: the one code there is;
                                                                         //  a second status code needs the value itself reduced)
     if (threadIdx.x == 0) status[b] = st;
-    int16_t* dst = reinterpret_cast<int16_t*>((J.to_sig ? reinterpret_cast<uint8_t*>(sig) : stage) + J.dst_byte) + first * J.ch;
+    int16_t* dst = reinterpret_cast<int16_t*>((J.to_sig ? reinterpret_cast<uint8_t*>(sig) : stage) + J.dst_byte) +
+                   (first - W.s_begin) * J.ch;
     const int total = n * J.ch;
-    for (int i = threadIdx.x; i < total; i += AD_THREADS) dst[i] = ad_smem[i];
+    if constexpr (WIN) {
+        const int i_lo = (int)max(W.s_begin - first, (int64_t)0) * J.ch, i_hi = (int)min(W.s_end - first, (int64_t)n) * J.ch;
+        for (int i = i_lo + threadIdx.x; i < i_hi; i += AD_THREADS) dst[i] = ad_smem[i];
+    } else {
+        for (int i = threadIdx.x; i < total; i += AD_THREADS) dst[i] = ad_smem[i];
+    }
 }
 
 int samples_per_block(int32_t block_align, int32_t ch) { return (block_align / ch - 4) * 2 + 1; }
@@ -121,20 +136,39 @@ extern "C" int iss_adpcm_decode_host(const uint8_t* buf, int64_t len, int64_t nb
     return ISS_OK;
 }
 
-extern "C" int iss_adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, int32_t njobs,
-                                int64_t nblocks_total, int64_t n_signal, int32_t* status_out) {
+extern "C" int iss_adpcm_decode_windows(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs,
+                                        const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
+                                        int32_t* status_out) {
     if (!c || njobs < 0 || (njobs > 0 && (!jobs || !status_out)) || src_bytes < 0 || (!src && src_bytes > 0) || nblocks_total < 0)
         return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: bad argument");
     IssDecodePass pass;
     int rc = pass.begin(c, "iss_adpcm_decode", n_signal, njobs);
     if (rc) return rc;
-    std::vector<AdJobDev> dev((size_t)njobs);
+    // one table: the job rows, then (windowed) their AdWinDev
+    std::vector<uint8_t> table((size_t)njobs * (sizeof(AdJobDev) + (windows ? sizeof(AdWinDev) : 0)));
+    AdJobDev* dev = reinterpret_cast<AdJobDev*>(table.data());
+    AdWinDev* dwin = reinterpret_cast<AdWinDev*>(dev + njobs);
     int64_t blocks = 0, lds = 0;
     for (int32_t j = 0; j < njobs; ++j) {
         const iss_adpcm_job& J = jobs[j];
-        if (!geometry_ok(J.nblocks, J.channels, J.block_align, J.frames_total))
-            return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: %lld blocks of %d bytes, %d channels, %lld samples", j,
-                            (long long)J.nblocks, J.block_align, J.channels, (long long)J.frames_total);
+        // windowed: the geometry of the file up to the window's last block, and exactly the blocks the window touches
+        int64_t block0 = 0;
+        bool geo;
+        if (windows) {
+            const iss_window& w = windows[j];
+            geo = geometry_ok(1, J.channels, J.block_align, 1) && w.s_begin >= 0 && w.s_begin < w.s_end && w.s_end <= J.frames_total;
+            if (geo) {
+                const int64_t spb = samples_per_block(J.block_align, J.channels);
+                block0 = w.s_begin / spb;
+                geo = J.nblocks == (w.s_end - 1) / spb - block0 + 1 && J.frames_total <= ((int64_t)1 << 40) / J.block_align * spb;
+            }
+        } else {
+            geo = geometry_ok(J.nblocks, J.channels, J.block_align, J.frames_total);
+        }
+        if (!geo)
+            return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: %lld blocks of %d bytes, %d channels, %lld samples%s", j,
+                            (long long)J.nblocks, J.block_align, J.channels, (long long)J.frames_total,
+                            windows ? " (windowed: not the blocks of the window)" : "");
         if (J.block_begin != blocks)
             return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: job %d: status rows start at %lld, expected %lld", j,
                             (long long)J.block_begin, (long long)blocks);
@@ -147,8 +181,9 @@ extern "C" int iss_adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, 
         d.ch = J.channels; d.block_align = J.block_align; d.spb = samples_per_block(J.block_align, J.channels);
         bool to_sig;
         if ((rc = pass.place(j, {J.output, J.filter, J.dst_offset, J.frames_out}, J.frames_total, J.channels, 2, J.channels == 1,
-                             "mono", to_sig, d.dst_byte)))
+                             "mono", to_sig, d.dst_byte, windows ? windows + j : nullptr)))
             return rc;
+        if (windows) dwin[j] = AdWinDev{block0, windows[j].s_begin, windows[j].s_end};
         d.to_sig = to_sig ? 1 : 0;
         lds = std::max<int64_t>(lds, (int64_t)d.spb * d.ch * 2);
         blocks += J.nblocks;
@@ -159,19 +194,24 @@ extern "C" int iss_adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, 
     if (blocks > 0x7fffffffLL) return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: %lld blocks in one call", (long long)blocks);
     if ((rc = pass.commit(&c->adpcm))) return rc;
     if (blocks == 0) return ISS_OK;
-    if ((rc = pass.upload(c->adpcm, src, src_bytes, (size_t)std::max<int64_t>(src_bytes, 16), dev.data(), dev.size() * sizeof(AdJobDev),
-                          blocks)))
+    if ((rc = pass.upload(c->adpcm, src, src_bytes, (size_t)std::max<int64_t>(src_bytes, 16), table.data(), table.size(), blocks)))
         return rc;
+    auto kernel = windows ? adpcm_decode_kernel<true> : adpcm_decode_kernel<false>;
     if (lds + 1024 > 64 * 1024)                        // (the kernel's static LDS, 256 bytes, counts towards the 64 KiB default)
-        ISS_HIP(c, hipFuncSetAttribute((const void*)adpcm_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ISS_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     iss_prof_begin(c, ISS_PROF_FRONTEND, 0.0);
     iss_prof_inst(c, "adpcm_decode_kernel");
-    hipLaunchKernelGGL(adpcm_decode_kernel, dim3((unsigned)blocks), dim3(AD_THREADS), (size_t)lds, c->stream,
-                       (const uint8_t*)c->adpcm.src.p, (const AdJobDev*)c->adpcm.rows.p, (int)dev.size(), (int16_t*)c->sig.p,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(AD_THREADS), (size_t)lds, c->stream,
+                       (const uint8_t*)c->adpcm.src.p, (const AdJobDev*)c->adpcm.rows.p, (int)njobs, (int16_t*)c->sig.p,
                        (uint8_t*)c->adpcm.stage.p, (int32_t*)c->adpcm.status.p);
     ISS_HIP(c, hipGetLastError());
     iss_prof_end(c);
     return pass.finish(c->adpcm, status_out, blocks);
+}
+
+extern "C" int iss_adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, int32_t njobs,
+                                int64_t nblocks_total, int64_t n_signal, int32_t* status_out) {
+    return iss_adpcm_decode_windows(c, src, src_bytes, jobs, nullptr, njobs, nblocks_total, n_signal, status_out);
 }
 
 extern "C" int iss_adpcm_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {

@@ -16,7 +16,16 @@ int IssDecodePass::begin(iss_ctx* ctx, const char* name, int64_t n_sig, int32_t 
 }
 
 int IssDecodePass::place(int32_t j, const IssJobDst& d, int64_t frames_total, int32_t channels, int esz, bool signal_ok,
-                         const char* only, bool& to_sig, int64_t& dst_byte) {
+                         const char* only, bool& to_sig, int64_t& dst_byte, const iss_window* w) {
+    iss_window full{0, frames_total, frames_total, 0, d.frames_out};
+    if (w) {
+        windowed = true;
+        if (w->frames_total != frames_total || w->s_begin < 0 || w->s_begin >= w->s_end || w->s_end > frames_total)
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: window [%lld, %lld) of %lld samples, the job has %lld", who, j,
+                            (long long)w->s_begin, (long long)w->s_end, (long long)w->frames_total, (long long)frames_total);
+        full = *w;
+        frames_total = w->s_end - w->s_begin;              // what is placed from here on
+    }
     if (d.output == ISS_FLAC_TO_SIGNAL) {
         if (!signal_ok) return iss_fail(c, ISS_EINVAL, "%s: job %d: only %s sources go to the signal", who, j, only);
         if (d.dst_offset < 0 || d.dst_offset > nsig - frames_total)
@@ -36,6 +45,7 @@ int IssDecodePass::place(int32_t j, const IssJobDst& d, int64_t frames_total, in
             r.format = esz == 4 ? ISS_RS_I32 : ISS_RS_I16; r.filter = d.filter; r.dst_offset = d.dst_offset;
             r.frames_out = d.frames_out;
             rjobs.push_back(r);
+            rwins.push_back(full);
         }
     } else {
         return iss_fail(c, ISS_EINVAL, "%s: job %d: bad output %d", who, j, d.output);
@@ -44,7 +54,8 @@ int IssDecodePass::place(int32_t j, const IssJobDst& d, int64_t frames_total, in
 }
 
 int IssDecodePass::commit(IssCodec* dec) {
-    int rc = iss_resample_plan(c, rjobs.data(), (int32_t)rjobs.size(), stage, nsig, ranges, who, plan);
+    int rc = iss_resample_plan(c, rjobs.data(), windowed ? rwins.data() : nullptr, (int32_t)rjobs.size(), stage, nsig, ranges,
+                               who, plan);
     if (rc) return rc;
     if (n_signal >= 0) {                                   // a signal of its own, zero wherever no job writes
         if ((rc = iss_reserve(c, c->sig, (size_t)nsig * 2 + 16))) return rc;

@@ -15,6 +15,8 @@ struct IssDecodePass {
     int64_t n_signal = -1, nsig = 0;       // as given, and the length of the signal the jobs write into
     std::vector<std::pair<int64_t, int64_t>> ranges;          // signal ranges of the TO_SIGNAL jobs
     std::vector<iss_resample_job> rjobs;                      // one per TO_STAGE job with a filter: reads the staging buffer
+    std::vector<iss_window> rwins;                            // beside rjobs (a whole-file window for a job without one) ...
+    bool windowed = false;                                    // ... and handed to the planner only when the call has windows
     std::vector<int64_t> stage_off, stage_bytes;              // per job (-1: not staged)
     int64_t stage = 0;                                        // bytes those rows read from: the staging buffer so far
     IssRsPlan plan;
@@ -24,8 +26,10 @@ struct IssDecodePass {
     // Job j: frames_total x channels samples of esz (2 or 4) bytes.  TO_SIGNAL, where signal_ok (`only` names who may, for the
     // error text): range checked and recorded.  TO_STAGE: the next 16-byte aligned staging offset, and with a filter the
     // resample row reading it.  -> to_sig, and dst_byte into the signal / the staging buffer
+    // `w` (NULL: the whole file): the job produces samples [s_begin, s_end) only, and that many are placed; dst_byte is where
+    // sample s_begin goes.  Checked here: the window lies inside the file and states the job's frames_total.
     int place(int32_t j, const IssJobDst& d, int64_t frames_total, int32_t channels, int esz, bool signal_ok, const char* only,
-              bool& to_sig, int64_t& dst_byte);
+              bool& to_sig, int64_t& dst_byte, const iss_window* w = nullptr);
     // Plans rjobs against the recorded ranges, then changes the context: a zeroed signal of its own for n_signal >= 0, features
     // stale, and the stage tables of `dec` (NULL: the raw resampler, whose rjobs are the caller's rows and `stage` its source bytes)
     int commit(IssCodec* dec);

@@ -11,6 +11,11 @@
 // the output width, which is exact for left/side and side/right and lossless for mid, which always fits) and read back.
 // LPC / FIXED history and coefficients live in registers: the residual loop is a template on the order bucket (4, 8, 16, 32)
 // and on the sum width, so no register array is indexed at run time.
+//
+// Windows (include/iss.h, iss_window): the decode is a template on the sink.  Sink<false> is the sink there always was;
+// Sink<true> keeps only the samples lo <= i < hi of its frame, so a frame that straddles a window's edge is decoded whole
+// (its predictor chain starts at the frame; header, padding and CRC-16 checks all run) and stored in part.  A skipped
+// sample is neither stored nor read back: the second subframe of a stereo pair reads only what the first stored at the same i.
 #include "decode_pass.h"
 #include <algorithm>
 #include <cstring>
@@ -101,10 +106,12 @@ struct Bits {
 
 // Where one subframe's samples go.  kind 0: stored as they are; 1..3: the second subframe of left/side, side/right and
 // mid/side, combined with the first (already stored) into both channels.
+template <bool WIN>
 struct Sink {
     uint8_t* p;
     int stride, chan, sh, kind;
     bool wide;
+    int lo, hi;            // WIN: the frame's samples inside the window
 
     __host__ __device__ inline int32_t ld(int64_t e) const {
         return wide ? reinterpret_cast<const int32_t*>(p)[e] : (int32_t)reinterpret_cast<const int16_t*>(p)[e];
@@ -114,6 +121,8 @@ struct Sink {
         else      reinterpret_cast<int16_t*>(p)[e] = (int16_t)(uint16_t)v;
     }
     __host__ __device__ inline void put(int64_t i, int32_t v) const {
+        if constexpr (WIN)
+            if (i < lo || i >= hi) return;
         const int64_t e = i * stride;
         switch (kind) {
             case 0: st(e + chan, (uint32_t)v << sh); break;
@@ -130,8 +139,8 @@ struct Sink {
 
 // Residual partitions + prediction of a FIXED or LPC subframe, history and coefficients in registers.  N: order bucket (>=
 // order); WIDE: 64-bit sums.  The warm-up samples have been read into h (h[0] most recent) and emitted.
-template <int N, bool WIDE>
-__host__ __device__ __forceinline__ int residual_predict(Bits& br, int64_t limit, const Sink& out, int bs, int order, const int32_t (&q)[N],
+template <int N, bool WIDE, class S>
+__host__ __device__ __forceinline__ int residual_predict(Bits& br, int64_t limit, const S& out, int bs, int order, const int32_t (&q)[N],
                                                 int32_t (&h)[N], int shift, int wasted) {
     const uint32_t method = br.get(2);
     if (method > 1) return FL_RESIDUAL_METHOD;
@@ -176,8 +185,8 @@ __host__ __device__ __forceinline__ int residual_predict(Bits& br, int64_t limit
 }
 
 // warm-up, coefficients, then the residual loop of bucket N
-template <int N>
-__host__ __device__ __forceinline__ int predicted(Bits& br, int64_t limit, const Sink& out, int bs, int sbps, int wasted, int order,
+template <int N, class S>
+__host__ __device__ __forceinline__ int predicted(Bits& br, int64_t limit, const S& out, int bs, int sbps, int wasted, int order,
                                          int fixed) {
     int32_t q[N], h[N];
 #pragma unroll
@@ -220,13 +229,15 @@ __host__ __device__ __forceinline__ int predicted(Bits& br, int64_t limit, const
 
 // One frame: subframes after its `hdr`-byte header, samples [0, bs) of every channel into dst (element 0 = channel 0 of
 // the frame's first sample), then padding and CRC-16.  Returns a FlacStatus.
+// WIN: only samples [lo, hi) of the frame are stored (dst is still where sample 0 would go)
+template <bool WIN>
 __host__ __device__ __forceinline__ int flac_decode_frame(const uint8_t* base, int64_t blen, int64_t off, int64_t len, int hdr, int bs, int mode,
-                                          int bps, uint8_t* dst, bool wide, const uint16_t* crc_tab) {
+                                          int bps, uint8_t* dst, bool wide, const uint16_t* crc_tab, int lo = 0, int hi = 0) {
     const int nch = mode < 8 ? mode + 1 : 2;
     const int64_t end_bit = (off + len - 2) * 8;
     Bits br;
     br.init(base, blen, off + hdr, off + len);
-    Sink out{dst, nch, 0, (wide ? 32 : 16) - bps, 0, wide};
+    Sink<WIN> out{dst, nch, 0, (wide ? 32 : 16) - bps, 0, wide, lo, hi};
     for (int ch = 0; ch < nch; ++ch) {
         const bool side = (mode == 8 && ch == 1) || (mode == 9 && ch == 0) || (mode == 10 && ch == 1);
         int sbps = bps + (side ? 1 : 0);
@@ -288,6 +299,10 @@ struct FlacFrameDev {
     int32_t pad2;
 };
 
+struct FlacWinDev { int32_t lo, hi; };      // beside FlacFrameDev k of a windowed call: the frame's samples inside its job's window
+
+// WIN = false is the kernel every call without windows launches; WIN = true reads the window table that follows the rows
+template <bool WIN>
 __global__ __launch_bounds__(FL_THREADS) void flac_decode_kernel(const uint8_t* __restrict__ src, const FlacFrameDev* __restrict__ fr,
                                                                  int64_t nfr, int16_t* sig, uint8_t* stage, int32_t* __restrict__ status) {
     __shared__ uint16_t tab[256];
@@ -297,7 +312,12 @@ __global__ __launch_bounds__(FL_THREADS) void flac_decode_kernel(const uint8_t* 
     if (i >= nfr) return;
     const FlacFrameDev F = fr[i];
     uint8_t* dst = (F.to_sig ? reinterpret_cast<uint8_t*>(sig) : stage) + F.dst_byte;
-    status[i] = flac_decode_frame(src, 0, F.src_off, F.len, F.hdr, F.bs, F.mode, F.bps, dst, F.wide != 0, tab);
+    if constexpr (WIN) {
+        const FlacWinDev W = reinterpret_cast<const FlacWinDev*>(fr + nfr)[i];
+        status[i] = flac_decode_frame<true>(src, 0, F.src_off, F.len, F.hdr, F.bs, F.mode, F.bps, dst, F.wide != 0, tab, W.lo, W.hi);
+    } else {
+        status[i] = flac_decode_frame<false>(src, 0, F.src_off, F.len, F.hdr, F.bs, F.mode, F.bps, dst, F.wide != 0, tab);
+    }
 }
 
 const uint16_t* host_crc16_table() {
@@ -473,8 +493,12 @@ extern "C" int iss_flac_index(const uint8_t* buf, int64_t len, int64_t first_fra
     return ISS_OK;
 }
 
-static bool frame_rows_ok(const iss_flac_frame* fr, int64_t nfr, int64_t bytes, int32_t channels, int32_t bps, int64_t total) {
-    int64_t t = 0;
+// The rows tile [0, total) in order; with a window `w` they are a contiguous run of the file's frames (the file's numbering)
+// that lies inside [0, total) and covers [w->s_begin, w->s_end).
+static bool frame_rows_ok(const iss_flac_frame* fr, int64_t nfr, int64_t bytes, int32_t channels, int32_t bps, int64_t total,
+                          const iss_window* w = nullptr) {
+    int64_t t = w ? fr[0].first_sample : 0;
+    if (w && (t < 0 || t > w->s_begin)) return false;
     for (int64_t k = 0; k < nfr; ++k) {
         const iss_flac_frame& f = fr[k];
         const int nch = f.channel_mode < 8 ? f.channel_mode + 1 : 2;
@@ -484,7 +508,7 @@ static bool frame_rows_ok(const iss_flac_frame* fr, int64_t nfr, int64_t bytes, 
             return false;
         t += f.block_size;
     }
-    return t == total;
+    return w ? t >= w->s_end && t <= total : t == total;
 }
 
 extern "C" int iss_flac_decode_host(const uint8_t* buf, int64_t len, const iss_flac_frame* frames, int64_t nframes, int32_t channels,
@@ -497,21 +521,25 @@ extern "C" int iss_flac_decode_host(const uint8_t* buf, int64_t len, const iss_f
     for (int64_t k = 0; k < nframes; ++k) {
         const iss_flac_frame& f = frames[k];
         uint8_t* dst = (uint8_t*)out + f.first_sample * channels * (wide ? 4 : 2);
-        status_out[k] = flac_decode_frame(buf, len, f.offset, f.length, f.header_bytes, f.block_size, f.channel_mode, f.bps, dst,
+        status_out[k] = flac_decode_frame<false>(buf, len, f.offset, f.length, f.header_bytes, f.block_size, f.channel_mode, f.bps, dst,
                                           wide, tab);
     }
     return ISS_OK;
 }
 
-extern "C" int iss_flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
-                               const iss_flac_job* jobs, int32_t njobs, int64_t n_signal, int32_t* status_out) {
+extern "C" int iss_flac_decode_windows(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
+                                       const iss_flac_job* jobs, const iss_window* windows, int32_t njobs, int64_t n_signal,
+                                       int32_t* status_out) {
     if (!c || njobs < 0 || (njobs > 0 && (!jobs || !frames || !status_out)) || src_bytes < 0 || (!src && src_bytes > 0) ||
         nframes < 0)
         return iss_fail(c, ISS_EINVAL, "iss_flac_decode: bad argument");
     IssDecodePass pass;
     int rc = pass.begin(c, "iss_flac_decode", n_signal, njobs);
     if (rc) return rc;
-    std::vector<FlacFrameDev> dev((size_t)nframes);
+    // one table: the frame rows, then (windowed) their FlacWinDev
+    std::vector<uint8_t> table((size_t)nframes * (sizeof(FlacFrameDev) + (windows ? sizeof(FlacWinDev) : 0)));
+    FlacFrameDev* dev = reinterpret_cast<FlacFrameDev*>(table.data());
+    FlacWinDev* dwin = reinterpret_cast<FlacWinDev*>(dev + nframes);
     std::vector<char> used((size_t)nframes, 0);
     for (int32_t j = 0; j < njobs; ++j) {
         const iss_flac_job& J = jobs[j];
@@ -523,9 +551,11 @@ extern "C" int iss_flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, c
         if (J.frames_total < 1 || J.frames_total > ((int64_t)1 << 40) / (4 * J.channels))
             return iss_fail(c, ISS_EINVAL, "iss_flac_decode: job %d: %lld samples", j, (long long)J.frames_total);
         if (J.src_offset < 0 || J.src_offset > src_bytes ||
-            !frame_rows_ok(frames + J.frame_begin, J.nframes, src_bytes - J.src_offset, J.channels, J.bps, J.frames_total))
+            !frame_rows_ok(frames + J.frame_begin, J.nframes, src_bytes - J.src_offset, J.channels, J.bps, J.frames_total,
+                           windows ? windows + j : nullptr))
             return iss_fail(c, ISS_EINVAL, "iss_flac_decode: job %d: frame rows outside the source bytes, not consecutive from "
-                            "sample 0 to frames_total, or not of the job's channels / bits", j);
+                            "sample 0 to frames_total%s, or not of the job's channels / bits", j,
+                            windows ? " (windowed: not a run of the file's frames that covers the window)" : "");
         for (int64_t k = J.frame_begin; k < J.frame_begin + J.nframes; ++k) {
             if (used[(size_t)k]) return iss_fail(c, ISS_EINVAL, "iss_flac_decode: frame row %lld belongs to two jobs", (long long)k);
             used[(size_t)k] = 1;
@@ -535,13 +565,19 @@ extern "C" int iss_flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, c
         bool to_sig;
         int64_t base;
         if ((rc = pass.place(j, {J.output, J.filter, J.dst_offset, J.frames_out}, J.frames_total, J.channels, esz,
-                             J.channels == 1 && !wide, "mono 8/16-bit", to_sig, base)))
+                             J.channels == 1 && !wide, "mono 8/16-bit", to_sig, base, windows ? windows + j : nullptr)))
             return rc;
+        const int64_t s_begin = windows ? windows[j].s_begin : 0;      // `base` is where this sample goes
         for (int64_t k = J.frame_begin; k < J.frame_begin + J.nframes; ++k) {
             const iss_flac_frame& f = frames[k];
             FlacFrameDev& d = dev[(size_t)k];
             d.src_off = J.src_offset + f.offset;
-            d.dst_byte = base + f.first_sample * J.channels * esz;
+            d.dst_byte = base + (f.first_sample - s_begin) * J.channels * esz;
+            if (windows) {
+                const int64_t lo = s_begin - f.first_sample, hi = windows[j].s_end - f.first_sample;
+                dwin[k].lo = (int32_t)std::max<int64_t>(lo, 0);
+                dwin[k].hi = (int32_t)std::min<int64_t>(std::max<int64_t>(hi, 0), f.block_size);
+            }
             d.len = (int32_t)f.length; d.hdr = f.header_bytes; d.bs = f.block_size;
             d.mode = (int16_t)f.channel_mode; d.bps = (int16_t)f.bps;
             d.wide = wide ? 1 : 0; d.to_sig = to_sig ? 1 : 0; d.pad0 = d.pad1 = 0; d.pad2 = 0;
@@ -551,17 +587,21 @@ extern "C" int iss_flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, c
         if (!used[(size_t)k]) return iss_fail(c, ISS_EINVAL, "iss_flac_decode: frame row %lld belongs to no job", (long long)k);
     if ((rc = pass.commit(&c->flac))) return rc;
     if (nframes == 0) return ISS_OK;
-    if ((rc = pass.upload(c->flac, src, src_bytes, (size_t)(src_bytes + 16) / 4 * 4 + 16, dev.data(), dev.size() * sizeof(FlacFrameDev),
-                          nframes)))
+    if ((rc = pass.upload(c->flac, src, src_bytes, (size_t)(src_bytes + 16) / 4 * 4 + 16, table.data(), table.size(), nframes)))
         return rc;
     iss_prof_begin(c, ISS_PROF_FRONTEND, 0.0);
     iss_prof_inst(c, "flac_decode_kernel");
-    hipLaunchKernelGGL(flac_decode_kernel, dim3((unsigned)((nframes + FL_THREADS - 1) / FL_THREADS)), dim3(FL_THREADS), 0, c->stream,
+    hipLaunchKernelGGL(windows ? flac_decode_kernel<true> : flac_decode_kernel<false>, dim3((unsigned)((nframes + FL_THREADS - 1) / FL_THREADS)), dim3(FL_THREADS), 0, c->stream,
                        (const uint8_t*)c->flac.src.p, (const FlacFrameDev*)c->flac.rows.p, nframes, (int16_t*)c->sig.p,
                        (uint8_t*)c->flac.stage.p, (int32_t*)c->flac.status.p);
     ISS_HIP(c, hipGetLastError());
     iss_prof_end(c);
     return pass.finish(c->flac, status_out, nframes);
+}
+
+extern "C" int iss_flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
+                               const iss_flac_job* jobs, int32_t njobs, int64_t n_signal, int32_t* status_out) {
+    return iss_flac_decode_windows(c, src, src_bytes, frames, nframes, jobs, nullptr, njobs, n_signal, status_out);
 }
 
 extern "C" int iss_flac_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {

@@ -203,12 +203,15 @@ struct RsJobDev {
     const double* taps;
     int32_t ch, fmt, up, down, hl, tile, lds_tab, pad;
 };
+struct RsWinDev { int64_t in_begin, frames_total, out_begin, out_end; };   // beside RsJobDev k of a windowed call (n_in: staged frames)
 struct IssRsPlan {
     std::vector<RsJobDev> dj;
+    std::vector<RsWinDev> dw;             // empty: no windows, the launch every call made before there were any
     int64_t tiles = 0, lds = 0;
 };
 // `ranges`: destination ranges of other writers of the same call, checked for overlap with the jobs' (error texts start with `who`)
-int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, int32_t njobs, int64_t src_bytes, int64_t nsig,
+// `wins`: NULL, or a window beside every job (include/iss.h)
+int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes, int64_t nsig,
                       std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan);
 int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& plan);
 

@@ -15,6 +15,10 @@
 //   3. thread t computes outputs i0 + t + 256*r: first input j0 = ceil((i*down - hl)/up), its tap i*down + hl - j0*up, then
 //      every `up`-th tap down to 0, summed in ascending j with separate multiply and add, then rint * 32768 and saturation
 // All index arithmetic is 64-bit: i*down passes 2^31 after ~5 minutes of 44.1 kHz output.
+//
+// Windows (include/iss.h, iss_window): WIN = true is a second pair of instantiations for calls that carry a window beside every
+// job.  The tiles are laid over the outputs [out_begin, out_end) of the window, the staged bytes hold the file's frames from
+// in_begin on, and frames outside [0, frames_total) are 0: steps 2 and 3 are otherwise the code above, on the file's own indices.
 #include "decode_pass.h"
 #include <algorithm>
 #include <cstring>
@@ -79,15 +83,22 @@ struct LdSwapF64 {
 };
 
 // frames s0 .. s0+len-1 of one source, downmixed to float64 (channels summed in order, divided by their count)
-template <typename L>
+// (WIN: the source's bytes start at frame W.in_begin of a file of W.frames_total frames, n_in of them staged)
+template <typename L, bool WIN>
 __device__ __forceinline__ void stage_span(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
-                                           double* __restrict__ span) {
+                                           double* __restrict__ span, const RsWinDev& W) {
     using T = typename L::type;
     const T* p = reinterpret_cast<const T*>(src);
     for (int k = threadIdx.x; k < len; k += RS_THREADS) {
-        const int64_t j = s0 + k;
+        int64_t j = s0 + k;
         double v = 0.0;
-        if (j >= 0 && j < n_in) {
+        bool in = j >= 0 && j < n_in;
+        if constexpr (WIN) {
+            in = j >= 0 && j < W.frames_total;
+            j -= W.in_begin;
+            in = in && j >= 0 && j < n_in;                 // (the planner saw to it that a window reaches no unstaged frame)
+        }
+        if (in) {
             const T* q = p + j * ch;
             v = L::get(q);
             for (int c = 1; c < ch; ++c) v = __dadd_rn(v, L::get(q + c));
@@ -117,7 +128,7 @@ __device__ __forceinline__ void compute_tile(const RsJobDev& J, const double* __
 
 // EXT = false: the five little-endian WAV formats only, the instantiation every call without a newer format launches (its
 // switch, and so its code, is what it was before the newer formats existed); EXT = true adds them behind the default case.
-template <bool EXT>
+template <bool EXT, bool WIN>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __restrict__ src, const RsJobDev* __restrict__ jobs,
                                                               int njobs, int16_t* __restrict__ dst) {
     extern __shared__ __attribute__((aligned(16))) double rs_smem[];
@@ -128,8 +139,10 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __r
         if (jobs[mid].tile_base <= b) lo = mid; else hi = mid - 1;
     }
     const RsJobDev J = jobs[lo];
-    const int64_t i0 = (b - J.tile_base) * J.tile;
-    const int64_t i_end = min(i0 + (int64_t)J.tile, J.n_out);
+    RsWinDev W{};
+    if constexpr (WIN) W = reinterpret_cast<const RsWinDev*>(jobs + njobs)[lo];      // the window table follows the job table
+    const int64_t i0 = (WIN ? W.out_begin : 0) + (b - J.tile_base) * J.tile;
+    const int64_t i_end = min(i0 + (int64_t)J.tile, WIN ? W.out_end : J.n_out);
     const int64_t s0 = floor_div(i0 * J.down - J.hl, J.up);
     const int64_t s1 = floor_div((i_end - 1) * J.down + J.hl, J.up);
     const int len = (int)(s1 - s0 + 1);
@@ -139,23 +152,23 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __r
         for (int k = threadIdx.x; k < ntaps; k += RS_THREADS) rs_smem[k] = J.taps[k];
     const uint8_t* s = src + J.src_off;
     switch (J.fmt) {
-        case ISS_RS_U8:  stage_span<LdPlain<uint8_t>>(s, J.n_in, J.ch, s0, len, span); break;
-        case ISS_RS_I16: stage_span<LdPlain<int16_t>>(s, J.n_in, J.ch, s0, len, span); break;
-        case ISS_RS_I32: stage_span<LdPlain<int32_t>>(s, J.n_in, J.ch, s0, len, span); break;
-        case ISS_RS_F32: stage_span<LdPlain<float>>(s, J.n_in, J.ch, s0, len, span); break;
+        case ISS_RS_U8:  stage_span<LdPlain<uint8_t>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
+        case ISS_RS_I16: stage_span<LdPlain<int16_t>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
+        case ISS_RS_I32: stage_span<LdPlain<int32_t>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
+        case ISS_RS_F32: stage_span<LdPlain<float>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
         default:
             if constexpr (!EXT) {
-                stage_span<LdPlain<double>>(s, J.n_in, J.ch, s0, len, span);
+                stage_span<LdPlain<double>, WIN>(s, J.n_in, J.ch, s0, len, span, W);
             } else {
                 switch (J.fmt) {
-                    case ISS_RS_F64:  stage_span<LdPlain<double>>(s, J.n_in, J.ch, s0, len, span); break;
-                    case ISS_RS_I8:   stage_span<LdPlain<int8_t>>(s, J.n_in, J.ch, s0, len, span); break;
-                    case ISS_RS_ULAW: stage_span<LdUlaw>(s, J.n_in, J.ch, s0, len, span); break;
-                    case ISS_RS_ALAW: stage_span<LdAlaw>(s, J.n_in, J.ch, s0, len, span); break;
-                    case ISS_RS_I16 | ISS_RS_SWAP: stage_span<LdSwapI16>(s, J.n_in, J.ch, s0, len, span); break;
-                    case ISS_RS_I32 | ISS_RS_SWAP: stage_span<LdSwapI32>(s, J.n_in, J.ch, s0, len, span); break;
-                    case ISS_RS_F32 | ISS_RS_SWAP: stage_span<LdSwapF32>(s, J.n_in, J.ch, s0, len, span); break;
-                    default:          stage_span<LdSwapF64>(s, J.n_in, J.ch, s0, len, span); break;      // ISS_RS_F64 | ISS_RS_SWAP
+                    case ISS_RS_F64:  stage_span<LdPlain<double>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
+                    case ISS_RS_I8:   stage_span<LdPlain<int8_t>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
+                    case ISS_RS_ULAW: stage_span<LdUlaw, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
+                    case ISS_RS_ALAW: stage_span<LdAlaw, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
+                    case ISS_RS_I16 | ISS_RS_SWAP: stage_span<LdSwapI16, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
+                    case ISS_RS_I32 | ISS_RS_SWAP: stage_span<LdSwapI32, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
+                    case ISS_RS_F32 | ISS_RS_SWAP: stage_span<LdSwapF32, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
+                    default:          stage_span<LdSwapF64, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;      // ISS_RS_F64 | ISS_RS_SWAP
                 }
             }
             break;
@@ -200,11 +213,14 @@ extern "C" int iss_resample_filter(iss_ctx* c, int32_t up, int32_t down, const d
     return ISS_OK;
 }
 
-int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, int32_t njobs, int64_t src_bytes, int64_t nsig,
-                      std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan) {
+static int64_t floor_div_host(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }      // b > 0
+
+int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes,
+                      int64_t nsig, std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan) {
     // validate every job, build the device descriptors and the tile prefix sum
     std::vector<RsJobDev>& dj = plan.dj;
     dj.assign((size_t)njobs, RsJobDev{});
+    plan.dw.assign(wins ? (size_t)njobs : 0, RsWinDev{});
     int64_t tiles = 0, lds = 0;
     for (int32_t k = 0; k < njobs; ++k) {
         const iss_resample_job& J = jobs[k];
@@ -224,7 +240,31 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, int32_t njobs, i
             return iss_fail(c, ISS_EINVAL, "%s: job %d: source bytes [%lld, %lld) outside the %lld-byte buffer or "
                             "not aligned to %lld", who, k, (long long)J.src_offset, (long long)(J.src_offset + nbytes),
                             (long long)src_bytes, (long long)esz);
-        const int64_t nout = (J.frames_in * f.up + f.down - 1) / f.down;
+        int64_t nout = (J.frames_in * f.up + f.down - 1) / f.down, out_begin = 0;
+        if (wins) {
+            // the window's outputs lie inside the file's, and their reach [j_lo, j_hi] inside the staged frames
+            const iss_window& w = wins[k];
+            if (w.frames_total < 1 || w.frames_total > (int64_t(1) << 40) / (esz * J.channels) || w.s_begin < 0 ||
+                w.s_begin >= w.s_end || w.s_end > w.frames_total || w.s_end - w.s_begin != J.frames_in)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: window frames [%lld, %lld) of %lld, %lld staged", who, k,
+                                (long long)w.s_begin, (long long)w.s_end, (long long)w.frames_total, (long long)J.frames_in);
+            const int64_t file_out = (w.frames_total * f.up + f.down - 1) / f.down;
+            if (w.out_begin < 0 || w.out_count < 1 || w.out_begin > file_out - w.out_count)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: window outputs [%lld, +%lld) outside the file's %lld", who, k,
+                                (long long)w.out_begin, (long long)w.out_count, (long long)file_out);
+            const int64_t j_lo = std::max<int64_t>(0, -floor_div_host(f.hl - w.out_begin * f.down, f.up));    // ceil: the first tap
+            const int64_t j_hi = std::min(w.frames_total - 1, floor_div_host((w.out_begin + w.out_count - 1) * f.down + f.hl, f.up));
+            if (j_lo < w.s_begin || j_hi >= w.s_end)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: window outputs [%lld, +%lld) reach frames [%lld, %lld], staged are "
+                                "[%lld, %lld)", who, k, (long long)w.out_begin, (long long)w.out_count, (long long)j_lo,
+                                (long long)j_hi, (long long)w.s_begin, (long long)w.s_end);
+            nout = w.out_count;
+            out_begin = w.out_begin;
+            plan.dw[(size_t)k] = RsWinDev{w.s_begin, w.frames_total, w.out_begin, w.out_begin + w.out_count};
+        }
+        if (J.frames_out != nout && wins)
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: frames_out %lld, the window's out_count is %lld", who, k,
+                            (long long)J.frames_out, (long long)nout);
         if (J.frames_out != nout)
             return iss_fail(c, ISS_EINVAL, "%s: job %d: frames_out %lld, ceil(%lld * %d / %d) = %lld", who, k,
                             (long long)J.frames_out, (long long)J.frames_in, f.up, f.down, (long long)nout);
@@ -239,7 +279,7 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, int32_t njobs, i
         const bool lds_tab = span_b + tab_b <= RS_LDS_MAX;
         lds = std::max(lds, span_b + (lds_tab ? tab_b : 0));
         RsJobDev& d = dj[(size_t)k];
-        d.src_off = J.src_offset; d.n_in = J.frames_in; d.dst_off = J.dst_offset; d.n_out = nout; d.tile_base = tiles;
+        d.src_off = J.src_offset; d.n_in = J.frames_in; d.dst_off = J.dst_offset - out_begin; d.n_out = nout; d.tile_base = tiles;
         d.taps = f.d_taps; d.ch = J.channels; d.fmt = J.format; d.up = f.up; d.down = f.down; d.hl = f.hl;
         d.tile = (int32_t)tile; d.lds_tab = lds_tab ? 1 : 0; d.pad = 0;
         tiles += (nout + tile - 1) / tile;
@@ -259,11 +299,21 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, int32_t njobs, i
 int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& plan) {
     const std::vector<RsJobDev>& dj = plan.dj;
     if (dj.empty()) return ISS_OK;
-    int rc = iss_upload_rows(c, c->rs_jobs, dj.data(), dj.size() * sizeof(RsJobDev));
+    const bool win = !plan.dw.empty();
+    int rc;
+    if (win) {                                         // one table: the jobs, then their windows
+        std::vector<uint8_t> rows(dj.size() * (sizeof(RsJobDev) + sizeof(RsWinDev)));
+        memcpy(rows.data(), dj.data(), dj.size() * sizeof(RsJobDev));
+        memcpy(rows.data() + dj.size() * sizeof(RsJobDev), plan.dw.data(), dj.size() * sizeof(RsWinDev));
+        rc = iss_upload_rows(c, c->rs_jobs, rows.data(), rows.size());
+    } else {
+        rc = iss_upload_rows(c, c->rs_jobs, dj.data(), dj.size() * sizeof(RsJobDev));
+    }
     if (rc) return rc;
     bool ext = false;                                  // a format newer than the WAV five: the instantiation that reads them all
     for (const RsJobDev& d : dj) ext = ext || d.fmt > ISS_RS_F64;
-    auto kernel = ext ? resample_kernel<true> : resample_kernel<false>;
+    auto kernel = win ? (ext ? resample_kernel<true, true> : resample_kernel<false, true>)
+                      : (ext ? resample_kernel<true, false> : resample_kernel<false, false>);
     if (plan.lds > 64 * 1024)
         ISS_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
     double flops = 0;
@@ -279,17 +329,24 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     return ISS_OK;
 }
 
-extern "C" int iss_resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
-                                  int64_t n_signal) {
+extern "C" int iss_resample_pcm16_windows(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
+                                          const iss_window* windows, int32_t njobs, int64_t n_signal) {
+    const char* who = windows ? "iss_resample_pcm16_windows" : "iss_resample_pcm16";
     if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0))
-        return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16: bad argument");
+        return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
     IssDecodePass pass;
-    int rc = pass.begin(c, "iss_resample_pcm16", n_signal, 0);
+    int rc = pass.begin(c, who, n_signal, 0);
     pass.rjobs.assign(jobs, jobs + njobs); pass.stage = src_bytes;      // no placement: the caller's rows over the caller's bytes
+    if (windows) { pass.rwins.assign(windows, windows + njobs); pass.windowed = true; }
     if (rc || (rc = pass.commit(nullptr))) return rc;
     if (njobs == 0) return ISS_OK;
     if ((rc = iss_upload_payload(c, c->rs_src, "resample", src, src_bytes, (size_t)std::max<int64_t>(src_bytes, 16)))) return rc;
     return iss_resample_launch(c, (const uint8_t*)c->rs_src.p, pass.plan);
+}
+
+extern "C" int iss_resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
+                                  int64_t n_signal) {
+    return iss_resample_pcm16_windows(c, src, src_bytes, jobs, nullptr, njobs, n_signal);
 }
 
 extern "C" int iss_resample_stats(iss_ctx* c, int64_t* launches, int64_t* jobs) {

@@ -93,13 +93,13 @@ class FlacStream:
         self.sr, self.ch, self.bps = sr, ch, bps
         self.n = int(frames['first_sample'][-1] + frames['block_size'][-1])
 
-    def check(self, status):
-        """Raise ValueError for the first frame whose decode status (ISS_FLAC_*) is not 0."""
+    def check(self, status, first=0):
+        """Raise ValueError for the first frame whose decode status (ISS_FLAC_*) is not 0; status[0] is frame `first`'s."""
         bad = np.flatnonzero(np.asarray(status))
         if bad.size:
             k = int(bad[0])
             why = _native.FLAC_STATUS.get(int(status[k]), f'status {int(status[k])}')
-            raise ValueError(f'{self.name}: frame at byte {self.base + int(self.frames["offset"][k])}: {why}')
+            raise ValueError(f'{self.name}: frame at byte {self.base + int(self.frames["offset"][first + k])}: {why}')
 
     def decode_host(self):
         """The stored samples ((n,) or (n, ch) int16 / int32 << 8) by the host build of the decoder."""
@@ -148,6 +148,64 @@ class FlacSource(CodedSource):
         x = ctx.flac_get_stage(0, s.n, s.ch, s.bps)
         s.check(st)
         return x
+
+
+class FlacExcerpt(CodedSource):
+    """Outputs [a, b) of a FLAC file for the windowed decode: the frames that cover the stored-rate samples the excerpt needs
+    ('pcm': [a, b) themselves; 'resample': resample.input_span of them) and their bytes only.  The rows keep the file's sample
+    numbering; a malformed frame is named by its byte offset in the file.  Frames outside the run are not decoded, so not checked."""
+    __slots__ = ('k0', 'rows', 'win', '_payload')
+    pass_order = 1
+    payload = property(lambda self: self._payload)
+    units = property(lambda self: len(self.rows))
+
+    def __init__(self, stream, kind, a, b):
+        self.s, self.kind, self.size = stream, kind, b - a
+        if kind == 'pcm':
+            s0, s1 = a, b
+        else:
+            j_lo, j_hi = R.input_span(stream.sr, stream.n, a, b - a)
+            s0, s1 = j_lo, j_hi + 1
+        fr = stream.frames
+        k0 = int(np.searchsorted(fr['first_sample'] + fr['block_size'], s0, side='right'))
+        k1 = int(np.searchsorted(fr['first_sample'], s1, side='left')) - 1
+        rows = fr[k0:k1 + 1].copy()
+        byte0 = int(rows['offset'][0])
+        rows['offset'] -= byte0
+        self.k0, self.rows, self.win = k0, rows, (s0, s1, stream.n, a, b - a)
+        self._payload = stream.audio[byte0:byte0 + int(rows['offset'][-1] + rows['length'][-1])]
+        self.nbytes = self._payload.nbytes
+
+    def job(self, ctx, src_offset, frame_begin, dst_offset):
+        s = self.s
+        if self.kind == 'pcm':
+            row = (src_offset, frame_begin, len(self.rows), s.n, s.ch, s.bps, _native.FLAC_TO_SIGNAL, -1, dst_offset, 0)
+        else:
+            fid, _, _ = ctx.resample_filter(s.sr)
+            row = (src_offset, frame_begin, len(self.rows), s.n, s.ch, s.bps, _native.FLAC_TO_STAGE, fid, dst_offset, self.size)
+        return row, self.win
+
+    @staticmethod
+    def tables(group):
+        return np.concatenate([g.rows for g in group])
+
+    @staticmethod
+    def launch(ctx, staged, jobs, frames, n_signal=-1):
+        return ctx.flac_decode(staged, frames, [j for j, _ in jobs], n_signal, windows=[w for _, w in jobs])
+
+    def check(self, status):
+        self.s.check(status, self.k0)
+
+    def host(self):
+        """The same samples by the host build of the decoder, on the same frames (and resample.resample_ref)."""
+        s, (s0, s1, total, a, count) = self.s, self.win
+        rows = self.rows.copy()
+        first = int(rows['first_sample'][0])
+        rows['first_sample'] -= first                            # the run alone tiles [0, its samples)
+        x, st = _native.flac_decode_host(self._payload, rows, s.ch, s.bps, int(rows['first_sample'][-1] + rows['block_size'][-1]))
+        self.check(st)
+        x = x[s0 - first:s1 - first]
+        return np.ascontiguousarray(x) if self.kind == 'pcm' else R.resample_ref(x, s.sr, a, count, s0, total)
 
 
 def source(stream, resample=False):

@@ -13,6 +13,8 @@ device's frame decoder; so do G.711 and IMA ADPCM in WAV, RF64 / BW64, Wave64, A
 tables, byte swaps and the host build of the device's IMA decoder).  A file is read once (`_read_file`) and `_classify` says
 from its bytes which parser takes it: a new format is one line there.  `decode_pcm` is the entry the native pipeline uses: it keeps
 PCM16 as int16 so the device does the x/32768 scaling (2 B/sample over PCIe, not 4).
+`excerpts` reads time ranges of one file without ffmpeg (an extension: start/stop through decode_pcm keep raising): per range the
+samples of the 16 kHz mono twin or a windowed source holding only the bytes it needs; `decode_excerpts` finishes them on the host.
 """
 import os
 import struct
@@ -71,6 +73,14 @@ def _parse_wav(buf, name='<buffer>'):
 def _read_file(medianame):
     with open(medianame, 'rb') as f:
         return f.read()
+
+
+def _read_range(path, offset, size):
+    """`size` bytes of the file at `path` from byte `offset` (fewer at its end).  Every read of the excerpt path (`excerpts`)
+    goes through here, so what an excerpt costs in disk reads can be counted."""
+    with open(path, 'rb') as f:
+        f.seek(offset)
+        return f.read(size)
 
 
 def _classify(buf, name):
@@ -175,3 +185,117 @@ def media2sig16kmono(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg', 
     """Reference-compatible signature and result (float array of `dtype`)."""
     a = decode_pcm(medianame, start_sec, stop_sec, ffmpeg)
     return _to_float(a, np.dtype(dtype)) if a.dtype == np.int16 else a.astype(dtype)
+
+
+# ---------------------------------------------------------------------------------------------- excerpts (time ranges of a file)
+def _check_range(name, start_sec, stop_sec):
+    """What can be refused of a range before the file is opened."""
+    import math
+    if isinstance(start_sec, bool) or not isinstance(start_sec, (int, float, np.integer, np.floating)) or \
+            not math.isfinite(start_sec) or start_sec < 0:
+        raise ValueError(f'{name}: start_sec={start_sec!r} must be a finite number of seconds, 0 or more')
+    if stop_sec is not None:
+        if isinstance(stop_sec, bool) or not isinstance(stop_sec, (int, float, np.integer, np.floating)) or math.isnan(stop_sec):
+            raise ValueError(f'{name}: stop_sec={stop_sec!r} must be a number of seconds or None')
+        if stop_sec <= start_sec:
+            raise ValueError(f'{name}: stop_sec={stop_sec!r} is not after start_sec={start_sec!r}')
+
+
+def excerpt_bounds(name, n16, start_sec, stop_sec):
+    """-> (a, b): the samples of the file's 16 kHz mono twin (n16 of them) that the range (start_sec, stop_sec) means:
+    a = floor(start_sec * 16000 + 0.5), b = n16 for stop_sec None, else min(n16, floor(stop_sec * 16000 + 0.5)).
+    This rounding is a definition: ffmpeg's own for -ss / -to was not at hand to pin it.  ValueError (naming the file) for a
+    start at or past the end, and for fewer than 400 samples."""
+    import math
+    _check_range(name, start_sec, stop_sec)
+    a = math.floor(start_sec * R.SR_OUT + 0.5)
+    b = n16 if stop_sec is None or math.isinf(stop_sec) else min(n16, math.floor(stop_sec * R.SR_OUT + 0.5))
+    if a >= n16:
+        raise ValueError(f'{name}: start_sec={start_sec!r} is at or past the end of the file, which lasts '
+                         f'{n16 / R.SR_OUT:.3f} s ({n16} samples at 16 kHz)')
+    if b - a < 400:
+        raise ValueError(f"media {name}: {b - a} samples, less than one 25 ms analysis window")
+    return a, b
+
+
+def _sound_excerpts(h, ranges, resample):
+    """The excerpts of a sndfmt.Sound or SoundHeader `h`: arrays where the whole-file read hands on an array (16 kHz mono:
+    the bytes of [a, b) alone, expanded as sndfmt.source expands the file), windowed sources for the device otherwise."""
+    from . import sndfmt
+    from .sources import RawExcerpt
+    mono16k = h.sr == R.SR_OUT and h.ch == 1
+    if not mono16k:
+        if not resample:
+            need_16k_mono(h.name, h.sr, h.ch)
+        R.check_rate(h.sr)
+    n16 = h.n if mono16k else R.out_len(h.n, h.sr)
+    out = []
+    for start, stop in ranges:
+        a, b = excerpt_bounds(h.name, n16, start, stop)
+        if h.kind == 'ima':
+            out.append(sndfmt.AdpcmExcerpt(h, 'pcm' if mono16k else 'resample', a, b))
+        elif mono16k:
+            x = sndfmt.sub_sound(h, a, b)[0].stored()
+            out.append(np.ascontiguousarray(x) if x.dtype == np.int16 else np.ascontiguousarray(_to_float(x, np.float32)))
+        else:
+            j_lo, j_hi = R.input_span(h.sr, h.n, a, b - a)
+            sub, _ = sndfmt.sub_sound(h, j_lo, j_hi + 1)
+            out.append(RawExcerpt(sub, *sub.raw(), a, b, j_lo, h.n))
+    return out
+
+
+def excerpts(medianame, ranges, resample=False):
+    """The time ranges [(start_sec, stop_sec | None)] of one file, read without ffmpeg: per range the samples [a, b) of the
+    file's 16 kHz mono twin (excerpt_bounds) as a numpy array, or a windowed source of sources.py that the device -- or its
+    `host()` -- turns into exactly those samples, holding only the bytes it needs.  None stands for "as the whole-file read
+    does, sliced" (the float path of 24-bit FLAC; a WAV whose chunk sizes need the whole file): the caller decodes the file once.
+    A plain RIFF/WAVE file is read by byte ranges (its chunk headers, then per range the frames or IMA blocks needed); every
+    other container, and FLAC -- whose frame index needs the scan --, is read whole once, and the ranges are cut from its bytes.
+    Ranges are validated before any sample is read where the header allows it; without `resample` a file that is not 16 kHz
+    mono is refused as the whole-file read refuses it (need_16k_mono: the rate first)."""
+    from . import flac, sndfmt
+    ranges = [tuple(r) for r in ranges]
+    for start, stop in ranges:
+        _check_range(medianame, start, stop)
+    _check_no_ffmpeg(medianame, None, None)
+    h = sndfmt.read_header(medianame)
+    if h is None:
+        buf = _read_range(medianame, 0, os.path.getsize(medianame))
+        h = _classify(buf, medianame)
+        if h is None:                                             # a WAV only the whole-file read can judge (or refuse)
+            return [None] * len(ranges)
+    if not isinstance(h, flac.FlacStream):
+        return _sound_excerpts(h, ranges, resample)
+    mono16k = h.sr == R.SR_OUT and h.ch == 1
+    if not mono16k:
+        if not resample:
+            need_16k_mono(h.name, h.sr, h.ch)
+        R.check_rate(h.sr)
+    n16 = h.n if mono16k else R.out_len(h.n, h.sr)
+    out = []
+    for start, stop in ranges:
+        a, b = excerpt_bounds(h.name, n16, start, stop)
+        out.append(None if mono16k and h.bps > 16 else flac.FlacExcerpt(h, 'pcm' if mono16k else 'resample', a, b))
+    return out
+
+
+def decode_excerpts(medianame, ranges, resample=False):
+    """Host-only twin of Segmenter.load_pcm_excerpts: [the samples [a, b) of the file's 16 kHz mono twin, per range], by the
+    host builds of the decoders (compiled FLAC / IMA, numpy G.711) on the frames, blocks and bytes of each excerpt alone, and
+    a windowed resample.resample_ref for sources at another rate or channel count."""
+    from .sources import Source
+    ranges = [tuple(r) for r in ranges]
+    sigs = excerpts(medianame, ranges, resample)
+    whole = None
+    out = []
+    for (start, stop), s in zip(ranges, sigs):
+        if s is None:
+            if whole is None:
+                x, sr = decode_source(medianame)
+                whole = source_of(x, sr, medianame, resample)
+                if isinstance(whole, Source):
+                    whole = R.resample_ref(x, sr)
+            a, b = excerpt_bounds(medianame, whole.size, start, stop)
+            s = whole[a:b]
+        out.append(s.host() if isinstance(s, Source) else s)
+    return out

@@ -68,24 +68,42 @@ def downmix(x):
     return m.mean(axis=1) if m.ndim == 2 else m
 
 
-def resample_float(m, sr):
-    """Step 2 on float64 mono samples, in the device's summation order (ascending input index)."""
+def input_span(sr, frames_total, out_begin, out_count):
+    """-> (j_lo, j_hi): the first and last input frame that carry a tap of outputs [out_begin, out_begin + out_count) of a
+    file of `frames_total` frames: j_lo = max(0, ceil((out_begin*down - hl)/up)), j_hi = min(frames_total - 1,
+    floor(((out_begin + out_count - 1)*down + hl)/up)).  (floor at the low end, where a tile's staging starts, names one
+    frame more whenever the division is not exact: that frame's tap would be 2*hl + something, outside the table.)"""
+    up, down, h = plan(sr)
+    hl = (h.size - 1) // 2
+    return (max(0, -((hl - int(out_begin) * down) // up)),
+            min(int(frames_total) - 1, ((int(out_begin) + int(out_count) - 1) * down + hl) // up))
+
+
+def resample_float(m, sr, out_begin=0, out_count=None, in_begin=0, frames_total=None):
+    """Step 2 on float64 mono samples, in the device's summation order (ascending input index).
+    A window: outputs [out_begin, out_begin + out_count) of the file (default: all of them), from `m` = the file's frames
+    [in_begin, in_begin + m.size) of `frames_total` (default: `m` ends the file).  A frame outside `m` counts as zero, as a
+    frame outside the file does: the result is the whole-file result's slice when `m` holds input_span() of the window."""
     up, down, h = plan(sr)
     m = np.asarray(m, dtype=np.float64)
-    n = m.size
+    n = int(in_begin) + m.size if frames_total is None else int(frames_total)
     nout = -(-n * up // down)
+    if out_count is None:
+        out_count = nout - int(out_begin)
+    if out_begin < 0 or out_count < 0 or out_begin + out_count > nout:
+        raise ValueError(f'outputs [{out_begin}, {out_begin + out_count}) outside the {nout} of {n} input frames')
     hl = (h.size - 1) // 2
     kmax = 2 * hl // up + 1                          # taps of the longest phase
-    i = np.arange(nout, dtype=np.int64)
+    i = np.arange(int(out_begin), int(out_begin) + int(out_count), dtype=np.int64)
     j0 = -((hl - i * down) // up)                    # ceil((i*down - hl) / up): first input under the filter
     t0 = i * down + hl - j0 * up                     # its tap, in (2*hl - up, 2*hl]; the next input's is `up` lower
-    pad = kmax + 1
-    mp = np.concatenate((np.zeros(pad), m, np.zeros(kmax + pad)))
+    mp = np.concatenate((np.zeros(1), m[:max(0, n - int(in_begin))]))     # mp[0] = 0 stands for the frames outside `m` / the file
     hp = np.concatenate((np.zeros(1), h))            # hp[0] = 0 stands for the taps below 0
-    acc = np.zeros(nout)
+    acc = np.zeros(i.size)
     for k in range(kmax):
         t = t0 - k * up
-        acc += hp[np.maximum(t, -1) + 1] * mp[j0 + k + pad]
+        j = j0 + k - int(in_begin)
+        acc += hp[np.maximum(t, -1) + 1] * mp[np.where((j >= 0) & (j < mp.size - 1), j + 1, 0)]
     return acc
 
 
@@ -93,6 +111,8 @@ def quantise(y):
     return np.clip(np.rint(y * 32768.0), -32768, 32767).astype(np.int16)
 
 
-def resample_ref(x, sr):
-    """The three steps above on stored samples x ((n,) or (n, C), any io dtype) -> 16 kHz mono int16."""
-    return quantise(resample_float(downmix(x), sr))
+def resample_ref(x, sr, out_begin=0, out_count=None, in_begin=0, frames_total=None):
+    """The three steps above on stored samples x ((n,) or (n, C), any io dtype) -> 16 kHz mono int16.  out_begin / out_count:
+    only those outputs (the defaults give them all); in_begin / frames_total: x holds the file's frames from in_begin on
+    (resample_float states the window)."""
+    return quantise(resample_float(downmix(x), sr, out_begin, out_count, in_begin, frames_total))

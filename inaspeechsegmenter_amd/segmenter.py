@@ -485,6 +485,110 @@ class Segmenter:
             sig.check(status)
         return host
 
+    # ---- time ranges of one file without ffmpeg (an extension: the reference cuts them with ffmpeg's -ss / -to)
+    def _excerpt_sigs(self, medianame, ranges):
+        """io.excerpts for this Segmenter -> (ranges as a list, per range an array or a windowed source).  What io.excerpts
+        leaves to the whole-file read (None) is decoded once, as load_pcm does, and sliced."""
+        if self.ffmpeg is not None:
+            raise ValueError(f'excerpts are read without ffmpeg (Segmenter(ffmpeg=None)); with ffmpeg={self.ffmpeg!r} pass '
+                             f'start_sec / stop_sec to Segmenter.__call__, one range per call')
+        ranges = [tuple(r) for r in ranges]
+        sigs = iss_io.excerpts(medianame, ranges, self.resample)
+        whole = None
+        for k, ((start, stop), s) in enumerate(zip(ranges, sigs)):
+            if s is None:
+                if whole is None:
+                    whole = self.load_pcm(medianame)
+                a, b = iss_io.excerpt_bounds(medianame, whole.size, start, stop)
+                sigs[k] = whole[a:b]
+        return ranges, sigs
+
+    @staticmethod
+    def _excerpt_passes(todo, sigs, batch_files, batch_seconds):
+        """The indices `todo` cut into device passes under the limits of batch_process (files, seconds of audio per pass)."""
+        from . import pipeline
+        nmax = batch_files or pipeline.DEFAULT_BATCH_FILES
+        smax = (batch_seconds or pipeline.DEFAULT_BATCH_SECONDS) * 16000
+        cur, held = [], 0
+        for k in todo:
+            cur.append(k)
+            held += -(-sigs[k].size // pipeline.FRAME_HOP) * pipeline.FRAME_HOP
+            if len(cur) >= nmax or held >= smax:
+                yield cur
+                cur, held = [], 0
+        if cur:
+            yield cur
+
+    def load_pcm_excerpts(self, medianame, ranges, batch_files=None, batch_seconds=None):
+        """load_pcm for time ranges [(start_sec, stop_sec | None)] of one file: [the samples [a, b) of what load_pcm(medianame)
+        returns, per range], a = floor(start_sec * 16000 + 0.5), b = its length for stop_sec None, else min(length, floor(stop_sec
+        * 16000 + 0.5)) -- a definition (io.excerpt_bounds): ffmpeg's rounding of -ss / -to was not at hand to pin it.  Only the
+        bytes, IMA blocks and FLAC frames the ranges need are staged, and all ranges that fit a pass (batch_files /
+        batch_seconds as for batch_process) take ONE launch per kernel.  Frames and blocks that are not decoded are not checked."""
+        ranges, sigs = self._excerpt_sigs(medianame, ranges)
+        out = [None if isinstance(s, Source) else s for s in sigs]
+        todo = [k for k, s in enumerate(sigs) if isinstance(s, Source)]
+        ctx = self.ctx
+        for idx in self._excerpt_passes(todo, sigs, batch_files, batch_seconds):
+            cls = type(sigs[idx[0]])                             # (one file: one class)
+            staged = np.zeros(sum(-(-sigs[k].payload.size // 16) * 16 for k in idx), dtype=np.uint8)
+            jobs, offs, bpos, ubeg, pos = [], [], 0, 0, 0
+            for k in idx:
+                s, p = sigs[k], sigs[k].payload
+                staged[bpos:bpos + p.size] = p
+                jobs.append(s.job(ctx, bpos, ubeg, pos))
+                offs.append(pos)
+                bpos += -(-p.size // 16) * 16
+                ubeg += s.units
+                pos += s.size
+            status = cls.launch(ctx, staged, jobs, cls.tables([sigs[k] for k in idx]), pos)
+            for k, o in zip(idx, offs):
+                out[k] = ctx.get_signal_pcm16(o, sigs[k].size)
+            ubeg = 0
+            for k in idx:
+                if status is not None:
+                    sigs[k].check(status[ubeg:ubeg + sigs[k].units])
+                ubeg += sigs[k].units
+        return out
+
+    def segment_excerpts(self, medianame, ranges, batch_files=None, batch_seconds=None):
+        """Segment time ranges [(start_sec, stop_sec | None)] of one file without ffmpeg -> [[(label, start, stop), ...] per range],
+        in the order of `ranges` (they may overlap or repeat).  Range k gives exactly what
+        segment_signal(load_pcm(medianame)[a:b], start_sec=start_sec) gives, a and b as load_pcm_excerpts states them (a
+        definition: ffmpeg's rounding of -ss / -to was not at hand to pin it); times are offset by start_sec as given.
+        The ranges are cut on the device: only the bytes, IMA blocks and FLAC frames they need are staged, and all ranges of a
+        pass (at most batch_files ranges / batch_seconds of audio, the defaults of batch_process) share one launch per decode
+        kernel, one resample launch and one feature pass.  Ranges shorter than 68 frames, and float media, go alone as
+        segment_signal would take them (padding and warning included).  ValueError, naming the file: a bad range, one that
+        starts at or past the end (the message states the duration), one of fewer than 400 samples, a malformed FLAC frame or IMA
+        block among those decoded (by its byte offset in the file; what is not decoded is not checked).  With ffmpeg set, use
+        __call__(medianame, start_sec, stop_sec)."""
+        from . import pipeline
+        ranges, sigs = self._excerpt_sigs(medianame, ranges)
+        out = [None] * len(sigs)
+        todo = []
+        for k, s in enumerate(sigs):
+            if not pipeline.sources.batchable(s) or s.size < pipeline.MIN_SAMPLES:
+                mspec, loge, difflen = _sig2feats(self.ctx, s, medianame)
+                out[k] = self.segment_feats(mspec, loge, difflen, ranges[k][0])
+            else:
+                todo.append(k)
+        if todo:
+            cache = self.__dict__.setdefault('_pipeline_workers', [])
+            if not cache:
+                cache.append(pipeline._Worker(self, self.ctx))
+            w = cache[0]
+        for idx in self._excerpt_passes(todo, sigs, batch_files, batch_seconds):
+            batch = pipeline._Batch()
+            batch.idx, batch.sigs, batch.names = list(idx), [sigs[k] for k in idx], [medianame] * len(idx)
+            lsegs = w.run(batch)
+            for f, (k, lseg) in enumerate(zip(idx, lsegs)):
+                if lseg is None:                                 # 'error: <class ValueError> <message>' (pipeline._Worker.run)
+                    raise ValueError(batch.errs[f][len('error: %s ' % (ValueError,)):])
+                start = ranges[k][0]
+                out[k] = [(lab, start + a * .02, start + b * .02) for lab, a, b in lseg]
+        return out
+
     def __call__(self, medianame, start_sec=None, stop_sec=None):
         """segmenter.py:279-294."""
         mspec, loge, difflen = _media2feats(medianame, start_sec, stop_sec, self.ffmpeg, self.ctx, self.resample)

@@ -97,6 +97,10 @@ class Sound:
     def nblocks(self):
         return len(self.data) // self.block_align if self.kind == 'ima' else 0
 
+    def fetch(self, byte0, byte1):
+        """Bytes [byte0, byte1) of `data` (what a SoundHeader reads from the file)."""
+        return self.data[byte0:byte1]
+
     def _shape(self, a):
         return a.reshape(-1, self.ch) if self.ch > 1 else a.reshape(-1)
 
@@ -150,6 +154,31 @@ class Sound:
             x = self.data if w == 1 else self.data.view({'i16': '<i2', 'i32': '<i4', 'f32': '<f4', 'f64': '<f8'}[k])
             return self._shape(x), _RS_CODE[k]
         return self._shape(self.data.view('<u%d' % w)), _RS_CODE[k] | _native.RS_SWAP
+
+
+class SoundHeader:
+    """What a Sound says of a file before any sample is read: the same fields but `data`, and `fetch` reads the bytes from
+    the file at `path` (io._read_range).  read_header makes one from the chunk headers of a RIFF/WAVE file."""
+    __slots__ = ('name', 'path', 'sr', 'ch', 'n', 'kind', 'big', 'base', 'block_align', 'spb')
+
+    def fetch(self, byte0, byte1):
+        from .io import _read_range
+        buf = _read_range(self.path, self.base + byte0, byte1 - byte0)
+        if len(buf) != byte1 - byte0:
+            raise ValueError(f'{self.name}: the file ends inside bytes [{self.base + byte0}, {self.base + byte1})')
+        return np.frombuffer(buf, dtype=np.uint8)
+
+
+def sub_sound(h, f0, f1):
+    """-> (the Sound of frames [f0, f1) of `h` -- of the whole IMA blocks they lie in --, the file's frame number of its first
+    frame).  `h` is a Sound or a SoundHeader; only those bytes are fetched, and `base` stays an offset in the file."""
+    if h.kind == 'ima':
+        k0, k1 = f0 // h.spb, (f1 - 1) // h.spb
+        data = h.fetch(k0 * h.block_align, (k1 + 1) * h.block_align)
+        return Sound(h.name, h.sr, h.ch, 'ima', False, data, h.base + k0 * h.block_align,
+                     frames=min(h.n, (k1 + 1) * h.spb) - k0 * h.spb, block_align=h.block_align, spb=h.spb), k0 * h.spb
+    fb = _WIDTH[h.kind] * h.ch
+    return Sound(h.name, h.sr, h.ch, h.kind, h.big, h.fetch(f0 * fb, f1 * fb), h.base + f0 * fb), f0
 
 
 # ------------------------------------------------------------------------------------------------ containers
@@ -359,6 +388,60 @@ def _parse_caf(buf, name):
     raise ValueError(f'{name}: missing desc or data chunk')
 
 
+def read_header(path, name=None):
+    """The SoundHeader of a plain RIFF/WAVE file (PCM, float, G.711 or IMA ADPCM), from its chunk headers alone: 12 bytes, then
+    8 per chunk and the bodies of `fmt ` and `fact`; a `data` chunk behind a large unknown chunk costs one more 8-byte read.
+    None for every other container and for whatever needs the whole file to be judged (RF64 sizes, a piped WAV without a length, a
+    file cut short): io.excerpts then reads the file as the whole-file read does."""
+    import os
+    from .io import _read_range
+    name = path if name is None else name
+    size_file = os.path.getsize(path)
+    head = _read_range(path, 0, 12)
+    if head[:4] != b'RIFF' or head[8:12] != b'WAVE':
+        return None
+    pos, fmt, fact = 12, None, None
+    while pos + 8 <= size_file:
+        head = _read_range(path, pos, 8)
+        if len(head) < 8:
+            return None
+        cid, size = head[:4], struct.unpack('<I', head[4:])[0]
+        body = pos + 8
+        if cid == b'fmt ':
+            chunk = _read_range(path, body, min(size, 64))
+            if len(chunk) < 16:
+                return None
+            fmt = _parse_fmt(chunk, 0, size, name)
+        elif cid == b'fact' and size >= 4:
+            fact = struct.unpack('<I', _read_range(path, body, 4))[0]
+        elif cid == b'data':
+            if fmt is None or size == 0xFFFFFFFF or fact == 0xFFFFFFFF or body + size > size_file:
+                return None
+            tag, ch, sr, align, bits, spb = fmt
+            h = SoundHeader()
+            try:
+                kind = _wav_kind(name, tag, bits)
+            except ValueError:
+                return None                                       # (the whole-file read words the refusal)
+            h.name, h.path, h.sr, h.ch, h.kind, h.big, h.base = name, path, int(sr), int(ch), kind, False, body
+            h.block_align = h.spb = 0
+            if ch < 1 or sr < 1:
+                return None
+            if h.kind == 'ima':
+                # (the rules of _wav_sound and Sound.__init__, on the header's numbers)
+                want = (align // ch - 4) * 2 + 1
+                if align % (4 * ch) != 0 or align <= 4 * ch or (spb is not None and spb != want) or ch > MAX_ADPCM_CHANNELS or \
+                        align > MAX_ADPCM_ALIGN:
+                    return None
+                n = size // align * want
+                h.n, h.block_align, h.spb = (int(fact) if fact is not None and fact <= n else n), int(align), want
+            else:
+                h.n = size // (_WIDTH[h.kind] * ch)
+            return h
+        pos = body + size + (size & 1)
+    return None
+
+
 def _container(head):
     """The parser of these leading bytes, with the container's name; None when they start none of them."""
     if head[:4] in (b'RIFF', b'RF64', b'BW64') and head[8:12] == b'WAVE':
@@ -445,6 +528,46 @@ class AdpcmSource(CodedSource):
     @staticmethod
     def launch(ctx, staged, jobs, nblocks, n_signal=-1):
         return ctx.adpcm_decode(staged, jobs, nblocks, n_signal)
+
+
+class AdpcmExcerpt(CodedSource):
+    """Outputs [a, b) of an IMA ADPCM file for the windowed decode: `s` = the sub_sound of the blocks that hold the
+    stored-rate samples the excerpt needs ('pcm': [a, b); 'resample': resample.input_span of them), `first` the file's sample
+    number of its first sample.  A bad block is named by its byte offset in the file (s.base is one)."""
+    __slots__ = ('first', 'win')
+    pass_order = 2
+    payload = property(lambda self: self.s.data)
+    units = property(lambda self: self.s.nblocks)
+
+    def __init__(self, h, kind, a, b):
+        self.kind, self.size = kind, b - a
+        s0, s1 = (a, b) if kind == 'pcm' else (lambda lo, hi: (lo, hi + 1))(*R.input_span(h.sr, h.n, a, b - a))
+        self.s, self.first = sub_sound(h, s0, s1)
+        self.win = (s0, s1, h.n, a, b - a)
+        self.nbytes = self.s.data.nbytes
+
+    def job(self, ctx, src_offset, block_begin, dst_offset):
+        s, total = self.s, self.win[2]
+        if self.kind == 'pcm':
+            row = (src_offset, block_begin, s.nblocks, total, s.ch, s.block_align, _native.ADPCM_TO_SIGNAL, -1, dst_offset, 0)
+        else:
+            fid, _, _ = ctx.resample_filter(s.sr)
+            row = (src_offset, block_begin, s.nblocks, total, s.ch, s.block_align, _native.ADPCM_TO_STAGE, fid, dst_offset, self.size)
+        return row, self.win
+
+    @staticmethod
+    def tables(group):
+        return sum(g.units for g in group)
+
+    @staticmethod
+    def launch(ctx, staged, jobs, nblocks, n_signal=-1):
+        return ctx.adpcm_decode(staged, [j for j, _ in jobs], nblocks, n_signal, windows=[w for _, w in jobs])
+
+    def host(self):
+        """The same samples by the host build of the decoder, on the same blocks (and resample.resample_ref)."""
+        s0, s1, total, a, count = self.win
+        x = self.s.stored()[s0 - self.first:s1 - self.first]
+        return np.ascontiguousarray(x) if self.kind == 'pcm' else R.resample_ref(x, self.s.sr, a, count, s0, total)
 
 
 def decode_on(ctx, src):

@@ -14,6 +14,9 @@ bytes as stored, which a kernel turns into 16 kHz mono PCM16 inside the resident
                             array (valid after the context's next synchronising call) or None
     place(ctx)              that launch for this file alone: the resident signal becomes its `size` samples
 
+An excerpt of a file (io.excerpts) is a source too: its `size` is the excerpt's, its `payload` only the bytes the excerpt needs,
+and its job row comes with the window row (iss_window) that its class's launch hands to the windowed entry point.
+
 `pass_order` places a class's launch among the device calls of a pass.  pipeline._Worker.run and segmenter._place are written
 against this and nothing else: a new format is one class, and one line in io._classify.
 """
@@ -65,6 +68,41 @@ class RawSource(Source):
     @staticmethod
     def launch(ctx, staged, jobs, tables, n_signal=-1):
         ctx.resample(staged, jobs, n_signal)
+
+
+class RawExcerpt(Source):
+    """Outputs [a, b) of a file at another rate or channel count, for the windowed resample kernel: `x` = the stored frames
+    j_lo .. j_hi that carry a tap of those outputs (resample.input_span) and nothing else of the file, `sub` the parsed slice
+    they came from (its host decode is what `host()` resamples), `win` the iss_window row."""
+    __slots__ = ('sub', 'x', 'sr', 'fmt', 'size', 'win')
+    pass_order = 0
+
+    def __init__(self, sub, x, fmt, a, b, j_lo, frames_total):
+        self.sub, self.x, self.sr, self.fmt = sub, np.ascontiguousarray(x), sub.sr, int(fmt)
+        self.size = b - a
+        self.win = (j_lo, j_lo + self.x.shape[0], frames_total, a, b - a)
+
+    @property
+    def held(self):
+        return max(self.size, self.x.nbytes // 2)
+
+    @property
+    def payload(self):
+        return self.x.reshape(-1).view(np.uint8)
+
+    def job(self, ctx, src_offset, unit_begin, dst_offset):
+        fid, _, _ = ctx.resample_filter(self.sr)
+        x = self.x
+        return (src_offset, x.shape[0], 1 if x.ndim == 1 else x.shape[1], self.fmt, fid, 0, dst_offset, self.size), self.win
+
+    @staticmethod
+    def launch(ctx, staged, jobs, tables, n_signal=-1):
+        ctx.resample(staged, [j for j, _ in jobs], n_signal, windows=[w for _, w in jobs])
+
+    def host(self):
+        """The same samples by resample.resample_ref on the host decode of the slice."""
+        j_lo, _, total, a, count = self.win
+        return resample.resample_ref(self.sub.stored(), self.sr, a, count, j_lo, total)
 
 
 class CodedSource(Source):

@@ -251,6 +251,43 @@ int iss_adpcm_get_stage(iss_ctx* ctx, int32_t job, void* out, int64_t bytes);
 /* ADPCM decode launches and blocks since the context was created.                                                    */
 int iss_adpcm_stats(iss_ctx* ctx, int64_t* launches, int64_t* blocks);
 
+/* Windows: a time range of a file through the three kernels above, touching only what the range needs.  A window row stands
+ * beside a job row (windows[k] belongs to jobs[k]); windows == NULL is the unwindowed call, to the bit and to the launch.
+ *   resample rows   `src` holds frames [s_begin, s_end) of a file of frames_total frames (the job's frames_in = s_end -
+ *                   s_begin); outputs i in [out_begin, out_begin + out_count) are computed exactly as the whole-file call
+ *                   computes them (same tap walk, ascending-j sum, separate multiply and add, same rounding) and written to
+ *                   dst_offset + i - out_begin (the job's frames_out = out_count).  Frames outside [0, frames_total) are
+ *                   zero: the edge of the staged slice is not the edge of the file.  Tiles are laid over the window.  The reach
+ *                   j_lo = max(0, ceil((out_begin*down - hl)/up)) .. j_hi = min(frames_total - 1, floor(((out_begin +
+ *                   out_count - 1)*down + hl)/up)) -- the frames that carry a tap -- must lie inside [s_begin, s_end): else
+ *                   ISS_EINVAL, nothing launched.  A tile's staging that starts one frame lower reads that frame as zero.
+ *   decoder rows    the job's frames_total stays the FILE's samples per channel (the window's frames_total must equal it) and
+ *                   the samples [s_begin, s_end) are produced: TO_SIGNAL at dst_offset + s - s_begin; TO_STAGE at the staging
+ *                   position of s - s_begin (s_end - s_begin samples staged), and with a filter resampled from there as a
+ *                   resample row with the same window (the job's frames_out = out_count).  out_begin / out_count are read
+ *                   only with a filter.
+ *     FLAC          the job's frame rows are a contiguous run of the file's frames, first_sample in the file's numbering,
+ *                   covering [s_begin, s_end); frame offsets are relative to src_offset as always (the caller stages only the
+ *                   run's bytes).  Every row is decoded whole (its predictor chain starts at the frame) and fully checked,
+ *                   CRC-16 included; only samples inside the window are stored.  Frames that are not among the rows are not
+ *                   decoded and so not checked.
+ *     IMA ADPCM     the job's blocks are exactly the file's blocks s_begin / samples_per_block .. (s_end - 1) /
+ *                   samples_per_block, src_offset pointing at the first of them; status rows as always, one per staged block.
+ * Everything else (signal rule, status, staging, counters, errors) is as for the unwindowed entry point.                   */
+typedef struct {
+    int64_t s_begin, s_end;        /* stored-rate frames of the file, 0 <= s_begin < s_end <= frames_total                  */
+    int64_t frames_total;          /* the file's frames (samples per channel)                                                */
+    int64_t out_begin, out_count;  /* 16 kHz outputs: out_begin >= 0, out_count >= 1, inside ceil(frames_total * up / down)  */
+} iss_window;
+int iss_resample_pcm16_windows(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
+                               const iss_window* windows, int32_t njobs, int64_t n_signal);
+int iss_flac_decode_windows(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
+                            const iss_flac_job* jobs, const iss_window* windows, int32_t njobs, int64_t n_signal,
+                            int32_t* status_out);
+int iss_adpcm_decode_windows(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs,
+                             const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
+                             int32_t* status_out);
+
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */
 int iss_host_alloc(iss_ctx* ctx, size_t bytes, void** out);
