@@ -41,6 +41,8 @@ FLAC_JOB = np.dtype([('src_offset', '<i8'), ('frame_begin', '<i8'), ('nframes', 
 FLAC_TO_SIGNAL, FLAC_TO_STAGE = 0, 1
 # iss_window (include/iss.h): the row beside a job row of the *_windows entry points
 WINDOW = np.dtype([('s_begin', '<i8'), ('s_end', '<i8'), ('frames_total', '<i8'), ('out_begin', '<i8'), ('out_count', '<i8')])
+# iss_split (include/iss.h): the row beside a job row of the *_split entry points
+SPLIT = np.dtype([('dst_stride', '<i8'), ('sel_begin', '<i4'), ('sel_count', '<i4')])
 # ISS_FLAC_* frame status codes -> reason
 FLAC_STATUS = {1: 'reserved subframe type', 2: 'subframe header padding bit set', 3: 'wasted bits exceed the sample size',
                4: 'reserved residual coding method', 5: 'residual partition order does not fit the block',
@@ -58,6 +60,23 @@ def _window_rows(windows, njobs):
     if wn.size != njobs:
         raise ValueError(f'{wn.size} windows for {njobs} jobs')
     return wn
+
+
+def _split_rows(splits, njobs):
+    """(SPLIT rows, int32 channel table) for a *_split entry point from one `(dst_stride, [channels])` or None (downmix) per
+    job; a pair of arrays (SPLIT rows, channel table) is handed on as given."""
+    if isinstance(splits, tuple) and len(splits) == 2 and isinstance(splits[0], np.ndarray):
+        rows, sel = np.ascontiguousarray(splits[0], dtype=SPLIT).reshape(-1), np.ascontiguousarray(splits[1], dtype=np.int32)
+    else:
+        rows, sel = np.zeros(len(splits), dtype=SPLIT), []
+        for k, sp in enumerate(splits):
+            if sp is not None:
+                rows[k] = (int(sp[0]), len(sel), len(sp[1]))
+                sel.extend(int(ch) for ch in sp[1])
+        sel = np.array(sel, dtype=np.int32)
+    if rows.size != njobs:
+        raise ValueError(f'{rows.size} splits for {njobs} jobs')
+    return rows, sel
 
 
 _lib = None
@@ -101,6 +120,10 @@ def lib():
         'iss_resample_pcm16_windows': (C.c_int, [vp, vp, i64, vp, vp, i32, i64]),
         'iss_flac_decode_windows': (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i32, i64, pi32]),
         'iss_adpcm_decode_windows': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32]),
+        'iss_resample_pcm16_split': (C.c_int, [vp, vp, i64, vp, i32, i64, vp, vp, i64]),
+        'iss_flac_decode_split': (C.c_int, [vp, vp, i64, vp, i64, vp, i32, i64, pi32, vp, vp, i64]),
+        'iss_adpcm_decode_split': (C.c_int, [vp, vp, i64, vp, i32, i64, i64, pi32, vp, vp, i64]),
+        'iss_resample_split_geometry': (C.c_int, [vp, i32, i32, pi32, pi32]),
         'iss_get_signal_pcm16': (C.c_int, [vp, pi16, i64, i64]),
         'iss_resample_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_flac_index': (C.c_int, [vp, i64, i64, vp, vp, i64, pi64, pi64, C.c_char_p, i32]),
@@ -377,14 +400,23 @@ class Context:
         return (src_offset, n, 1 if x.ndim == 1 else x.shape[1], RS_FORMAT[x.dtype] if fmt is None else int(fmt), fid, 0,
                 dst_offset, -(-n * up // down))
 
-    def resample(self, src, jobs, n_signal=-1, windows=None):
+    def resample(self, src, jobs, n_signal=-1, windows=None, splits=None):
         """iss_resample_pcm16: src = 1-D uint8 array of the stored samples of every job, jobs = rows of RS_JOB; one H2D copy,
         one launch.  n_signal >= 0: a new resident signal of that many samples; < 0: into the signal of the last set_signal.
         windows: rows of WINDOW, one beside every job (iss_resample_pcm16_windows): src holds frames [s_begin, s_end) of each
-        file, and the outputs [out_begin, out_begin + out_count) are written."""
+        file, and the outputs [out_begin, out_begin + out_count) are written.
+        splits: `(dst_stride, [channels])` or None per job (iss_resample_pcm16_split): the selected channels of a job are written
+        apart, channel k of the selection at dst_offset + k * dst_stride; None downmixes as ever.  Not with windows."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=RS_JOB))
-        if windows is None:
+        if splits is not None:
+            if windows is not None:
+                raise ValueError('windows and splits are not combined')
+            sp, sel = _split_rows(splits, jb.size)
+            self._ck(self._L.iss_resample_pcm16_split(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
+                                                      jb.size, int(n_signal), C.c_void_p(sp.ctypes.data),
+                                                      C.c_void_p(sel.ctypes.data), sel.size), 'iss_resample_pcm16_split')
+        elif windows is None:
             self._ck(self._L.iss_resample_pcm16(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
                                                 jb.size, int(n_signal)), 'iss_resample_pcm16')
         else:
@@ -401,6 +433,14 @@ class Context:
         job = self.resample_job(x, sr, 0, 0, fmt)
         self.resample(x.reshape(-1).view(np.uint8), [job], n_signal=job[-1])
         return job[-1]
+
+    def resample_split_geometry(self, sr, nsel):
+        """(outputs per tile, channels per group) the planner gives a selection of `nsel` channels at source rate `sr`."""
+        fid, _, _ = self.resample_filter(sr)
+        tile, group = C.c_int32(), C.c_int32()
+        self._ck(self._L.iss_resample_split_geometry(self._h, fid, int(nsel), C.byref(tile), C.byref(group)),
+                 'iss_resample_split_geometry')
+        return tile.value, group.value
 
     def get_signal_pcm16(self, offset, n):
         """Samples [offset, offset + n) of the resident PCM16 signal (e.g. what `resample` wrote)."""
@@ -432,17 +472,26 @@ class Context:
         return st
 
     # ---- FLAC decoder (iss_flac_*): compressed frames -> resident signal (PCM16), staging buffer, or resampled
-    def flac_decode(self, src, frames, jobs, n_signal=-1, windows=None):
+    def flac_decode(self, src, frames, jobs, n_signal=-1, windows=None, splits=None):
         """iss_flac_decode: src = 1-D uint8 array of the compressed bytes of every job, frames = FLAC_FRAME rows, jobs = rows
         of FLAC_JOB; one H2D copy, one decode launch (+ one resample launch).  -> the per-frame status array (page-locked,
         this context's): valid after the next synchronising call (get_loge, flac_get_stage, synchronize).
         windows: rows of WINDOW, one beside every job (iss_flac_decode_windows): each job's rows are a run of its file's frames
-        that covers [s_begin, s_end), and only those samples are produced."""
+        that covers [s_begin, s_end), and only those samples are produced.
+        splits: as for `resample` (iss_flac_decode_split), for TO_STAGE jobs with a filter; None for every other job."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         fr = np.ascontiguousarray(frames, dtype=FLAC_FRAME)
         jb = np.ascontiguousarray(np.array(jobs, dtype=FLAC_JOB).reshape(-1))
         st = self._status('_flac_status', len(fr))
-        if windows is None:
+        if splits is not None:
+            if windows is not None:
+                raise ValueError('windows and splits are not combined')
+            sp, sel = _split_rows(splits, jb.size)
+            self._ck(self._L.iss_flac_decode_split(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data),
+                                                   len(fr), C.c_void_p(jb.ctypes.data), jb.size, int(n_signal), _ptr(st, C.c_int32),
+                                                   C.c_void_p(sp.ctypes.data), C.c_void_p(sel.ctypes.data), sel.size),
+                     'iss_flac_decode_split')
+        elif windows is None:
             self._ck(self._L.iss_flac_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data), len(fr),
                                              C.c_void_p(jb.ctypes.data), jb.size, int(n_signal), _ptr(st, C.c_int32)),
                      'iss_flac_decode')
@@ -463,16 +512,25 @@ class Context:
         return self._counters('iss_flac_stats')
 
     # ---- IMA ADPCM decoder (iss_adpcm_*): stored blocks -> resident signal (PCM16), staging buffer, or resampled
-    def adpcm_decode(self, src, jobs, nblocks, n_signal=-1, windows=None):
+    def adpcm_decode(self, src, jobs, nblocks, n_signal=-1, windows=None, splits=None):
         """iss_adpcm_decode: src = 1-D uint8 array of the blocks of every job, jobs = rows of ADPCM_JOB, nblocks = their
         sum; one H2D copy, one decode launch (+ one resample launch).  -> the per-block status array (page-locked, this
         context's): valid after the next synchronising call (get_loge, adpcm_get_stage, synchronize).
         windows: rows of WINDOW, one beside every job (iss_adpcm_decode_windows): each job holds exactly the blocks that its
-        samples [s_begin, s_end) lie in, and only those samples are produced."""
+        samples [s_begin, s_end) lie in, and only those samples are produced.
+        splits: as for `resample` (iss_adpcm_decode_split), for TO_STAGE jobs with a filter; None for every other job."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=ADPCM_JOB).reshape(-1))
         st = self._status('_adpcm_status', nblocks)
-        if windows is None:
+        if splits is not None:
+            if windows is not None:
+                raise ValueError('windows and splits are not combined')
+            sp, sel = _split_rows(splits, jb.size)
+            self._ck(self._L.iss_adpcm_decode_split(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
+                                                    jb.size, int(nblocks), int(n_signal), _ptr(st, C.c_int32),
+                                                    C.c_void_p(sp.ctypes.data), C.c_void_p(sel.ctypes.data), sel.size),
+                     'iss_adpcm_decode_split')
+        elif windows is None:
             self._ck(self._L.iss_adpcm_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data), jb.size,
                                               int(nblocks), int(n_signal), _ptr(st, C.c_int32)), 'iss_adpcm_decode')
         else:

@@ -136,14 +136,16 @@ extern "C" int iss_adpcm_decode_host(const uint8_t* buf, int64_t len, int64_t nb
     return ISS_OK;
 }
 
-extern "C" int iss_adpcm_decode_windows(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs,
-                                        const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
-                                        int32_t* status_out) {
+// the three entry points: windows beside the jobs, splits (with their selection table) beside the jobs, or neither
+static int adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, const iss_window* windows,
+                        int32_t njobs, int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_split* splits,
+                        const int32_t* channel_sel, int64_t nsel) {
     if (!c || njobs < 0 || (njobs > 0 && (!jobs || !status_out)) || src_bytes < 0 || (!src && src_bytes > 0) || nblocks_total < 0)
         return iss_fail(c, ISS_EINVAL, "iss_adpcm_decode: bad argument");
     IssDecodePass pass;
     int rc = pass.begin(c, "iss_adpcm_decode", n_signal, njobs);
     if (rc) return rc;
+    pass.jsplits = splits; pass.sel = channel_sel; pass.nsel = nsel;
     // one table: the job rows, then (windowed) their AdWinDev
     std::vector<uint8_t> table((size_t)njobs * (sizeof(AdJobDev) + (windows ? sizeof(AdWinDev) : 0)));
     AdJobDev* dev = reinterpret_cast<AdJobDev*>(table.data());
@@ -209,9 +211,21 @@ extern "C" int iss_adpcm_decode_windows(iss_ctx* c, const void* src, int64_t src
     return pass.finish(c->adpcm, status_out, blocks);
 }
 
+extern "C" int iss_adpcm_decode_windows(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs,
+                                        const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
+                                        int32_t* status_out) {
+    return adpcm_decode(c, src, src_bytes, jobs, windows, njobs, nblocks_total, n_signal, status_out, nullptr, nullptr, 0);
+}
+
 extern "C" int iss_adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, int32_t njobs,
                                 int64_t nblocks_total, int64_t n_signal, int32_t* status_out) {
-    return iss_adpcm_decode_windows(c, src, src_bytes, jobs, nullptr, njobs, nblocks_total, n_signal, status_out);
+    return adpcm_decode(c, src, src_bytes, jobs, nullptr, njobs, nblocks_total, n_signal, status_out, nullptr, nullptr, 0);
+}
+
+extern "C" int iss_adpcm_decode_split(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, int32_t njobs,
+                                      int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_split* splits,
+                                      const int32_t* channel_sel, int64_t nsel) {
+    return adpcm_decode(c, src, src_bytes, jobs, nullptr, njobs, nblocks_total, n_signal, status_out, splits, channel_sel, nsel);
 }
 
 extern "C" int iss_adpcm_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {

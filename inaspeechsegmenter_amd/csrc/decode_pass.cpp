@@ -26,6 +26,11 @@ int IssDecodePass::place(int32_t j, const IssJobDst& d, int64_t frames_total, in
         full = *w;
         frames_total = w->s_end - w->s_begin;              // what is placed from here on
     }
+    const iss_split none{0, 0, 0};
+    const iss_split& sp = jsplits ? jsplits[j] : none;
+    if (jsplits) split = true;
+    if (sp.sel_count != 0 && !(d.output == ISS_FLAC_TO_STAGE && d.filter >= 0))
+        return iss_fail(c, ISS_EINVAL, "%s: job %d: a channel selection needs a TO_STAGE job with a filter", who, j);
     if (d.output == ISS_FLAC_TO_SIGNAL) {
         if (!signal_ok) return iss_fail(c, ISS_EINVAL, "%s: job %d: only %s sources go to the signal", who, j, only);
         if (d.dst_offset < 0 || d.dst_offset > nsig - frames_total)
@@ -46,6 +51,7 @@ int IssDecodePass::place(int32_t j, const IssJobDst& d, int64_t frames_total, in
             r.frames_out = d.frames_out;
             rjobs.push_back(r);
             rwins.push_back(full);
+            rsplits.push_back(sp);
         }
     } else {
         return iss_fail(c, ISS_EINVAL, "%s: job %d: bad output %d", who, j, d.output);
@@ -55,7 +61,7 @@ int IssDecodePass::place(int32_t j, const IssJobDst& d, int64_t frames_total, in
 
 int IssDecodePass::commit(IssCodec* dec) {
     int rc = iss_resample_plan(c, rjobs.data(), windowed ? rwins.data() : nullptr, (int32_t)rjobs.size(), stage, nsig, ranges,
-                               who, plan);
+                               who, plan, split ? rsplits.data() : nullptr, sel, nsel);
     if (rc) return rc;
     if (n_signal >= 0) {                                   // a signal of its own, zero wherever no job writes
         if ((rc = iss_reserve(c, c->sig, (size_t)nsig * 2 + 16))) return rc;

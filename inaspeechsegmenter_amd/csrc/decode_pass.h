@@ -17,6 +17,11 @@ struct IssDecodePass {
     std::vector<iss_resample_job> rjobs;                      // one per TO_STAGE job with a filter: reads the staging buffer
     std::vector<iss_window> rwins;                            // beside rjobs (a whole-file window for a job without one) ...
     bool windowed = false;                                    // ... and handed to the planner only when the call has windows
+    const iss_split* jsplits = nullptr;                       // a split entry point's rows, one per JOB (NULL: the plain call) ...
+    std::vector<iss_split> rsplits;                           // ... handed on beside rjobs (no selection for a job without one) ...
+    bool split = false;                                       // ... and to the planner only when the call has splits,
+    const int32_t* sel = nullptr;                             // with the caller's channel selection table
+    int64_t nsel = 0;
     std::vector<int64_t> stage_off, stage_bytes;              // per job (-1: not staged)
     int64_t stage = 0;                                        // bytes those rows read from: the staging buffer so far
     IssRsPlan plan;
@@ -28,6 +33,7 @@ struct IssDecodePass {
     // resample row reading it.  -> to_sig, and dst_byte into the signal / the staging buffer
     // `w` (NULL: the whole file): the job produces samples [s_begin, s_end) only, and that many are placed; dst_byte is where
     // sample s_begin goes.  Checked here: the window lies inside the file and states the job's frames_total.
+    // A job's split (jsplits) goes to its resample row; a selection on a job without one (TO_SIGNAL, or no filter) is refused.
     int place(int32_t j, const IssJobDst& d, int64_t frames_total, int32_t channels, int esz, bool signal_ok, const char* only,
               bool& to_sig, int64_t& dst_byte, const iss_window* w = nullptr);
     // Plans rjobs against the recorded ranges, then changes the context: a zeroed signal of its own for n_signal >= 0, features

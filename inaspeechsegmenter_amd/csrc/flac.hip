@@ -527,15 +527,17 @@ extern "C" int iss_flac_decode_host(const uint8_t* buf, int64_t len, const iss_f
     return ISS_OK;
 }
 
-extern "C" int iss_flac_decode_windows(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
-                                       const iss_flac_job* jobs, const iss_window* windows, int32_t njobs, int64_t n_signal,
-                                       int32_t* status_out) {
+// the three entry points: windows beside the jobs, splits (with their selection table) beside the jobs, or neither
+static int flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
+                       const iss_flac_job* jobs, const iss_window* windows, int32_t njobs, int64_t n_signal, int32_t* status_out,
+                       const iss_split* splits, const int32_t* channel_sel, int64_t nsel) {
     if (!c || njobs < 0 || (njobs > 0 && (!jobs || !frames || !status_out)) || src_bytes < 0 || (!src && src_bytes > 0) ||
         nframes < 0)
         return iss_fail(c, ISS_EINVAL, "iss_flac_decode: bad argument");
     IssDecodePass pass;
     int rc = pass.begin(c, "iss_flac_decode", n_signal, njobs);
     if (rc) return rc;
+    pass.jsplits = splits; pass.sel = channel_sel; pass.nsel = nsel;
     // one table: the frame rows, then (windowed) their FlacWinDev
     std::vector<uint8_t> table((size_t)nframes * (sizeof(FlacFrameDev) + (windows ? sizeof(FlacWinDev) : 0)));
     FlacFrameDev* dev = reinterpret_cast<FlacFrameDev*>(table.data());
@@ -599,9 +601,21 @@ extern "C" int iss_flac_decode_windows(iss_ctx* c, const void* src, int64_t src_
     return pass.finish(c->flac, status_out, nframes);
 }
 
+extern "C" int iss_flac_decode_windows(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
+                                       const iss_flac_job* jobs, const iss_window* windows, int32_t njobs, int64_t n_signal,
+                                       int32_t* status_out) {
+    return flac_decode(c, src, src_bytes, frames, nframes, jobs, windows, njobs, n_signal, status_out, nullptr, nullptr, 0);
+}
+
 extern "C" int iss_flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
                                const iss_flac_job* jobs, int32_t njobs, int64_t n_signal, int32_t* status_out) {
-    return iss_flac_decode_windows(c, src, src_bytes, frames, nframes, jobs, nullptr, njobs, n_signal, status_out);
+    return flac_decode(c, src, src_bytes, frames, nframes, jobs, nullptr, njobs, n_signal, status_out, nullptr, nullptr, 0);
+}
+
+extern "C" int iss_flac_decode_split(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
+                                     const iss_flac_job* jobs, int32_t njobs, int64_t n_signal, int32_t* status_out,
+                                     const iss_split* splits, const int32_t* channel_sel, int64_t nsel) {
+    return flac_decode(c, src, src_bytes, frames, nframes, jobs, nullptr, njobs, n_signal, status_out, splits, channel_sel, nsel);
 }
 
 extern "C" int iss_flac_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {

@@ -204,15 +204,21 @@ struct RsJobDev {
     int32_t ch, fmt, up, down, hl, tile, lds_tab, pad;
 };
 struct RsWinDev { int64_t in_begin, frames_total, out_begin, out_end; };   // beside RsJobDev k of a windowed call (n_in: staged frames)
+// beside RsJobDev k of a split call: sel_count selected channels (rows [sel_begin, +sel_count) of the selection table; 0: downmix),
+// `group` of them per workgroup at `stride` float64 apart in LDS, each over `ntiles` tiles; ident: the selection is 0, 1, 2, ...
+struct RsSplitDev { int64_t dst_stride, ntiles; int32_t sel_begin, sel_count, group, stride, ident, pad; };
 struct IssRsPlan {
     std::vector<RsJobDev> dj;
     std::vector<RsWinDev> dw;             // empty: no windows, the launch every call made before there were any
+    std::vector<RsSplitDev> ds;           // empty: no splits, likewise
+    std::vector<int32_t> sel;             // the channel selections the rows of ds point into
     int64_t tiles = 0, lds = 0;
 };
 // `ranges`: destination ranges of other writers of the same call, checked for overlap with the jobs' (error texts start with `who`)
-// `wins`: NULL, or a window beside every job (include/iss.h)
+// `wins`: NULL, or a window beside every job (include/iss.h);  `splits`: NULL, or a split beside every job, into sel[0, nsel)
 int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes, int64_t nsig,
-                      std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan);
+                      std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan,
+                      const iss_split* splits = nullptr, const int32_t* sel = nullptr, int64_t nsel = 0);
 int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& plan);
 
 // implemented in the .hip files

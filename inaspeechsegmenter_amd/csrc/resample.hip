@@ -19,6 +19,13 @@
 // Windows (include/iss.h, iss_window): WIN = true is a second pair of instantiations for calls that carry a window beside every
 // job.  The tiles are laid over the outputs [out_begin, out_end) of the window, the staged bytes hold the file's frames from
 // in_begin on, and frames outside [0, frames_total) are 0: steps 2 and 3 are otherwise the code above, on the file's own indices.
+//
+// Splits (include/iss.h, iss_split): SPLIT = true is a third pair of instantiations for calls that carry a split row beside every
+// job.  A job with a selection of channels writes each selected channel apart instead of averaging them: its grid is ragged over
+// (channel group, tile), a group being the selected channels whose spans fit RS_SPAN_MAX side by side.  The workgroup stages
+// span[k][.] for the channels of its group in one pass over the interleaved frames ((frame, channel) flattened over the threads:
+// contiguous reads when the selection is the channels in order) and runs step 3 once per channel, on m[j] = the channel's own
+// sample.  A job without a selection (sel_count 0) is the downmix above, in the same launch.
 #include "decode_pass.h"
 #include <algorithm>
 #include <cstring>
@@ -108,6 +115,36 @@ __device__ __forceinline__ void stage_span(const uint8_t* __restrict__ src, int6
     }
 }
 
+// frames s0 .. s0+len-1 of `gc` selected channels, each on its own: span[k * stride + .] = channel sel[k] (sel == NULL: channel
+// c0 + k).  Thread e takes (frame e / gc, channel e % gc): neighbouring lanes read neighbouring samples of a frame
+template <typename L>
+__device__ __forceinline__ void stage_channels(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
+                                               double* __restrict__ span, int stride, int c0, int gc,
+                                               const int32_t* __restrict__ sel) {
+    using T = typename L::type;
+    const T* p = reinterpret_cast<const T*>(src);
+    const int total = len * gc;
+    for (int e = threadIdx.x; e < total; e += RS_THREADS) {
+        const int k = e / gc, kk = e - k * gc;
+        const int64_t j = s0 + k;
+        double v = 0.0;
+        if (j >= 0 && j < n_in) v = L::get(p + j * ch + (sel ? sel[kk] : c0 + kk));
+        span[(int64_t)kk * stride + k] = v;
+    }
+}
+
+// what a workgroup of a SPLIT launch stages: the downmix (gc == 0), or channels [c0, c0 + gc) of its job's selection
+struct RsGroup { int64_t dst_stride; int stride, c0, gc; const int32_t* sel; };
+
+template <typename L, bool WIN, bool SPLIT>
+__device__ __forceinline__ void stage(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
+                                      double* __restrict__ span, const RsWinDev& W, const RsGroup& G) {
+    if constexpr (SPLIT) {
+        if (G.gc > 0) { stage_channels<L>(src, n_in, ch, s0, len, span, G.stride, G.c0, G.gc, G.sel); return; }
+    }
+    stage_span<L, WIN>(src, n_in, ch, s0, len, span, W);
+}
+
 __device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) {      // b > 0
     return a >= 0 ? a / b : -((-a + b - 1) / b);
 }
@@ -128,7 +165,10 @@ __device__ __forceinline__ void compute_tile(const RsJobDev& J, const double* __
 
 // EXT = false: the five little-endian WAV formats only, the instantiation every call without a newer format launches (its
 // switch, and so its code, is what it was before the newer formats existed); EXT = true adds them behind the default case.
-template <bool EXT, bool WIN>
+// SPLIT = false is the kernel every call without splits launches; SPLIT = true reads the split table and the channel selections
+// that follow the rows.
+#define RS_STAGE(L) stage<L, WIN, SPLIT>(s, J.n_in, J.ch, s0, len, span, W, G)
+template <bool EXT, bool WIN, bool SPLIT>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __restrict__ src, const RsJobDev* __restrict__ jobs,
                                                               int njobs, int16_t* __restrict__ dst) {
     extern __shared__ __attribute__((aligned(16))) double rs_smem[];
@@ -141,7 +181,22 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __r
     const RsJobDev J = jobs[lo];
     RsWinDev W{};
     if constexpr (WIN) W = reinterpret_cast<const RsWinDev*>(jobs + njobs)[lo];      // the window table follows the job table
-    const int64_t i0 = (WIN ? W.out_begin : 0) + (b - J.tile_base) * J.tile;
+    int64_t t = b - J.tile_base;                                            // SPLIT: (channel group, tile), else the tile
+    RsGroup G{};
+    if constexpr (SPLIT) {
+        static_assert(!WIN, "windows and splits are not combined");
+        const RsSplitDev* splits = reinterpret_cast<const RsSplitDev*>(jobs + njobs);     // the split table follows the job table,
+        const int32_t* sels = reinterpret_cast<const int32_t*>(splits + njobs);          // the channel selections follow that
+        const RsSplitDev S = splits[lo];
+        if (S.sel_count > 0) {
+            const int g = (int)(t / S.ntiles);
+            t -= g * S.ntiles;
+            G.dst_stride = S.dst_stride; G.stride = S.stride; G.c0 = g * S.group; G.gc = min(S.group, S.sel_count - G.c0);
+            G.sel = S.ident ? nullptr : sels + S.sel_begin + G.c0;
+            dst += (int64_t)G.c0 * S.dst_stride;
+        }
+    }
+    const int64_t i0 = (WIN ? W.out_begin : 0) + t * J.tile;
     const int64_t i_end = min(i0 + (int64_t)J.tile, WIN ? W.out_end : J.n_out);
     const int64_t s0 = floor_div(i0 * J.down - J.hl, J.up);
     const int64_t s1 = floor_div((i_end - 1) * J.down + J.hl, J.up);
@@ -152,37 +207,60 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __r
         for (int k = threadIdx.x; k < ntaps; k += RS_THREADS) rs_smem[k] = J.taps[k];
     const uint8_t* s = src + J.src_off;
     switch (J.fmt) {
-        case ISS_RS_U8:  stage_span<LdPlain<uint8_t>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
-        case ISS_RS_I16: stage_span<LdPlain<int16_t>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
-        case ISS_RS_I32: stage_span<LdPlain<int32_t>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
-        case ISS_RS_F32: stage_span<LdPlain<float>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
+        case ISS_RS_U8:  RS_STAGE(LdPlain<uint8_t>); break;
+        case ISS_RS_I16: RS_STAGE(LdPlain<int16_t>); break;
+        case ISS_RS_I32: RS_STAGE(LdPlain<int32_t>); break;
+        case ISS_RS_F32: RS_STAGE(LdPlain<float>); break;
         default:
             if constexpr (!EXT) {
-                stage_span<LdPlain<double>, WIN>(s, J.n_in, J.ch, s0, len, span, W);
+                RS_STAGE(LdPlain<double>);
             } else {
                 switch (J.fmt) {
-                    case ISS_RS_F64:  stage_span<LdPlain<double>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
-                    case ISS_RS_I8:   stage_span<LdPlain<int8_t>, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
-                    case ISS_RS_ULAW: stage_span<LdUlaw, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
-                    case ISS_RS_ALAW: stage_span<LdAlaw, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
-                    case ISS_RS_I16 | ISS_RS_SWAP: stage_span<LdSwapI16, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
-                    case ISS_RS_I32 | ISS_RS_SWAP: stage_span<LdSwapI32, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
-                    case ISS_RS_F32 | ISS_RS_SWAP: stage_span<LdSwapF32, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;
-                    default:          stage_span<LdSwapF64, WIN>(s, J.n_in, J.ch, s0, len, span, W); break;      // ISS_RS_F64 | ISS_RS_SWAP
+                    case ISS_RS_F64:  RS_STAGE(LdPlain<double>); break;
+                    case ISS_RS_I8:   RS_STAGE(LdPlain<int8_t>); break;
+                    case ISS_RS_ULAW: RS_STAGE(LdUlaw); break;
+                    case ISS_RS_ALAW: RS_STAGE(LdAlaw); break;
+                    case ISS_RS_I16 | ISS_RS_SWAP: RS_STAGE(LdSwapI16); break;
+                    case ISS_RS_I32 | ISS_RS_SWAP: RS_STAGE(LdSwapI32); break;
+                    case ISS_RS_F32 | ISS_RS_SWAP: RS_STAGE(LdSwapF32); break;
+                    default:          RS_STAGE(LdSwapF64); break;      // ISS_RS_F64 | ISS_RS_SWAP
                 }
             }
             break;
     }
     __syncthreads();
+    if constexpr (SPLIT) {
+        if (G.gc > 0) {                                                     // one pass of step 3 per channel of the group
+            for (int k = 0; k < G.gc; ++k, span += G.stride, dst += G.dst_stride) {
+                if (J.lds_tab) compute_tile(J, rs_smem, span, s0, i0, i_end, dst);
+                else           compute_tile(J, J.taps, span, s0, i0, i_end, dst);
+            }
+            return;
+        }
+    }
     if (J.lds_tab) compute_tile(J, rs_smem, span, s0, i0, i_end, dst);
     else           compute_tile(J, J.taps, span, s0, i0, i_end, dst);
 }
+#undef RS_STAGE
 
 const int kFmtBytes[11] = {1, 2, 4, 4, 8, 0, 0, 0, 1, 1, 1};      // bytes per stored sample of ISS_RS_* (0: not a format)
 
 // longest input span of a tile of `tile` outputs: floor(((tile-1)*down + 2*hl) / up) + 2 frames
 int64_t span_frames(const iss_ctx::RsFilter& f, int64_t tile) {
     return ((tile - 1) * f.down + 2 * (int64_t)f.hl) / f.up + 2;
+}
+
+// (tile, group, stride) of a job of `nsel` channels written apart: the largest tile at which the spans of two channels (of
+// one, for a single channel) fit RS_SPAN_MAX side by side, then as many channels per group as fit at that tile.  `stride`,
+// float64 between the spans of a group: the span rounded up to 16, plus 16 / group -- the 16 lanes of one LDS store group
+// hold 16 / group frames of each channel, which then fall on different banks
+void split_geometry(const iss_ctx::RsFilter& f, int64_t nsel, int64_t& tile, int64_t& group, int64_t& stride) {
+    const int64_t keep = std::min<int64_t>(nsel, 2);
+    tile = RS_THREADS * 4;
+    while (tile > RS_THREADS && keep * span_frames(f, tile) * 8 > RS_SPAN_MAX) tile /= 2;
+    const int64_t span = span_frames(f, tile);
+    group = std::max<int64_t>(1, std::min(nsel, RS_SPAN_MAX / (span * 8)));
+    stride = group == 1 ? span : (span + 15) / 16 * 16 + std::max<int64_t>(1, 16 / group);
 }
 
 }  // namespace
@@ -216,11 +294,17 @@ extern "C" int iss_resample_filter(iss_ctx* c, int32_t up, int32_t down, const d
 static int64_t floor_div_host(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }      // b > 0
 
 int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes,
-                      int64_t nsig, std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan) {
+                      int64_t nsig, std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan,
+                      const iss_split* splits, const int32_t* sel, int64_t nsel) {
     // validate every job, build the device descriptors and the tile prefix sum
     std::vector<RsJobDev>& dj = plan.dj;
     dj.assign((size_t)njobs, RsJobDev{});
     plan.dw.assign(wins ? (size_t)njobs : 0, RsWinDev{});
+    plan.ds.assign(splits ? (size_t)njobs : 0, RsSplitDev{});
+    plan.sel.clear();
+    if (splits && (wins || nsel < 0 || nsel > 0x7fffffffLL || (nsel > 0 && !sel)))
+        return iss_fail(c, ISS_EINVAL, "%s: splits with windows, or a bad channel selection table", who);
+    if (splits) plan.sel.assign(sel, sel + nsel);
     int64_t tiles = 0, lds = 0;
     for (int32_t k = 0; k < njobs; ++k) {
         const iss_resample_job& J = jobs[k];
@@ -272,9 +356,39 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
             return iss_fail(c, ISS_EINVAL, "%s: job %d: output [%lld, %lld) outside the %lld-sample signal", who, k,
                             (long long)J.dst_offset, (long long)(J.dst_offset + nout), (long long)nsig);
         ranges.push_back({J.dst_offset, J.dst_offset + nout});
-        int64_t tile = RS_THREADS * 4;
-        while (tile > RS_THREADS && span_frames(f, tile) * 8 > RS_SPAN_MAX) tile /= 2;
-        const int64_t span_b = span_frames(f, tile) * 8;
+        int64_t tile = RS_THREADS * 4, span_b, groups = 1;
+        if (splits && splits[k].sel_count != 0) {
+            // a selection: its rows, its channels, and one destination range per selected channel
+            const iss_split& sp = splits[k];
+            if (sp.sel_count < 0 || sp.sel_begin < 0 || sp.sel_begin > nsel - sp.sel_count)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: selection rows [%d, +%d) outside the %lld of channel_sel", who, k,
+                                sp.sel_begin, sp.sel_count, (long long)nsel);
+            bool ident = true;
+            for (int32_t q = 0; q < sp.sel_count; ++q) {
+                const int32_t ch = sel[sp.sel_begin + q];
+                if (ch < 0 || ch >= J.channels)
+                    return iss_fail(c, ISS_EINVAL, "%s: job %d: selected channel %d of %d", who, k, ch, J.channels);
+                ident = ident && ch == q;
+            }
+            if (sp.dst_stride < nout || sp.dst_stride > (int64_t(1) << 40))
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: dst_stride %lld below the %lld outputs of a channel", who, k,
+                                (long long)sp.dst_stride, (long long)nout);
+            const int64_t last = J.dst_offset + (sp.sel_count - 1) * sp.dst_stride;
+            if (last > nsig - nout)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: output [%lld, %lld) of selected channel %d outside the %lld-sample "
+                                "signal", who, k, (long long)last, (long long)(last + nout), sp.sel_count - 1, (long long)nsig);
+            for (int32_t q = 1; q < sp.sel_count; ++q)
+                ranges.push_back({J.dst_offset + q * sp.dst_stride, J.dst_offset + q * sp.dst_stride + nout});
+            int64_t group, stride;
+            split_geometry(f, sp.sel_count, tile, group, stride);
+            span_b = group * stride * 8;
+            groups = (sp.sel_count + group - 1) / group;
+            plan.ds[(size_t)k] = RsSplitDev{sp.dst_stride, (nout + tile - 1) / tile, sp.sel_begin, sp.sel_count, (int32_t)group,
+                                            (int32_t)stride, ident ? 1 : 0, 0};
+        } else {
+            while (tile > RS_THREADS && span_frames(f, tile) * 8 > RS_SPAN_MAX) tile /= 2;
+            span_b = span_frames(f, tile) * 8;
+        }
         const int64_t tab_b = ((f.ntaps + 1) & ~int64_t(1)) * 8;
         const bool lds_tab = span_b + tab_b <= RS_LDS_MAX;
         lds = std::max(lds, span_b + (lds_tab ? tab_b : 0));
@@ -282,7 +396,7 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
         d.src_off = J.src_offset; d.n_in = J.frames_in; d.dst_off = J.dst_offset - out_begin; d.n_out = nout; d.tile_base = tiles;
         d.taps = f.d_taps; d.ch = J.channels; d.fmt = J.format; d.up = f.up; d.down = f.down; d.hl = f.hl;
         d.tile = (int32_t)tile; d.lds_tab = lds_tab ? 1 : 0; d.pad = 0;
-        tiles += (nout + tile - 1) / tile;
+        tiles += groups * ((nout + tile - 1) / tile);
     }
     std::sort(ranges.begin(), ranges.end());
     for (size_t k = 1; k < ranges.size(); ++k)
@@ -299,9 +413,16 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
 int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& plan) {
     const std::vector<RsJobDev>& dj = plan.dj;
     if (dj.empty()) return ISS_OK;
-    const bool win = !plan.dw.empty();
+    const bool win = !plan.dw.empty(), split = !plan.ds.empty();
     int rc;
-    if (win) {                                         // one table: the jobs, then their windows
+    if (split) {                                       // one table: the jobs, their splits, the channel selections
+        const size_t nj = dj.size() * sizeof(RsJobDev), ns = dj.size() * sizeof(RsSplitDev);
+        std::vector<uint8_t> rows(nj + ns + std::max<size_t>(plan.sel.size(), 1) * sizeof(int32_t));
+        memcpy(rows.data(), dj.data(), nj);
+        memcpy(rows.data() + nj, plan.ds.data(), ns);
+        if (!plan.sel.empty()) memcpy(rows.data() + nj + ns, plan.sel.data(), plan.sel.size() * sizeof(int32_t));
+        rc = iss_upload_rows(c, c->rs_jobs, rows.data(), rows.size());
+    } else if (win) {                                         // one table: the jobs, then their windows
         std::vector<uint8_t> rows(dj.size() * (sizeof(RsJobDev) + sizeof(RsWinDev)));
         memcpy(rows.data(), dj.data(), dj.size() * sizeof(RsJobDev));
         memcpy(rows.data() + dj.size() * sizeof(RsJobDev), plan.dw.data(), dj.size() * sizeof(RsWinDev));
@@ -312,12 +433,14 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     if (rc) return rc;
     bool ext = false;                                  // a format newer than the WAV five: the instantiation that reads them all
     for (const RsJobDev& d : dj) ext = ext || d.fmt > ISS_RS_F64;
-    auto kernel = win ? (ext ? resample_kernel<true, true> : resample_kernel<false, true>)
-                      : (ext ? resample_kernel<true, false> : resample_kernel<false, false>);
+    auto kernel = split ? (ext ? resample_kernel<true, false, true> : resample_kernel<false, false, true>)
+                  : win ? (ext ? resample_kernel<true, true, false> : resample_kernel<false, true, false>)
+                        : (ext ? resample_kernel<true, false, false> : resample_kernel<false, false, false>);
     if (plan.lds > 64 * 1024)
         ISS_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
     double flops = 0;
-    for (const RsJobDev& d : dj) flops += 2.0 * (double)d.n_out * (2.0 * d.hl + 1) / d.up;
+    for (size_t k = 0; k < dj.size(); ++k)
+        flops += 2.0 * (double)dj[k].n_out * (2.0 * dj[k].hl + 1) / dj[k].up * (split ? std::max(plan.ds[k].sel_count, 1) : 1);
     iss_prof_begin(c, ISS_PROF_FRONTEND, flops);
     iss_prof_inst(c, "resample_kernel");
     hipLaunchKernelGGL(kernel, dim3((unsigned)plan.tiles), dim3(RS_THREADS), (size_t)plan.lds, c->stream,
@@ -342,6 +465,32 @@ extern "C" int iss_resample_pcm16_windows(iss_ctx* c, const void* src, int64_t s
     if (njobs == 0) return ISS_OK;
     if ((rc = iss_upload_payload(c, c->rs_src, "resample", src, src_bytes, (size_t)std::max<int64_t>(src_bytes, 16)))) return rc;
     return iss_resample_launch(c, (const uint8_t*)c->rs_src.p, pass.plan);
+}
+
+extern "C" int iss_resample_pcm16_split(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
+                                        int64_t n_signal, const iss_split* splits, const int32_t* channel_sel, int64_t nsel) {
+    if (!splits) return iss_resample_pcm16_windows(c, src, src_bytes, jobs, nullptr, njobs, n_signal);
+    const char* who = "iss_resample_pcm16_split";
+    if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0))
+        return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
+    IssDecodePass pass;
+    int rc = pass.begin(c, who, n_signal, 0);
+    pass.rjobs.assign(jobs, jobs + njobs); pass.stage = src_bytes;
+    pass.rsplits.assign(splits, splits + njobs); pass.split = true; pass.sel = channel_sel; pass.nsel = nsel;
+    if (rc || (rc = pass.commit(nullptr))) return rc;
+    if (njobs == 0) return ISS_OK;
+    if ((rc = iss_upload_payload(c, c->rs_src, "resample", src, src_bytes, (size_t)std::max<int64_t>(src_bytes, 16)))) return rc;
+    return iss_resample_launch(c, (const uint8_t*)c->rs_src.p, pass.plan);
+}
+
+// (tile, channels per group) the planner gives a job of `nsel` selected channels through filter `filter`
+extern "C" int iss_resample_split_geometry(iss_ctx* c, int32_t filter, int32_t nsel, int32_t* tile_out, int32_t* group_out) {
+    if (!c || !tile_out || !group_out || nsel < 1 || filter < 0 || filter >= (int32_t)c->rs_filters.size())
+        return iss_fail(c, ISS_EINVAL, "iss_resample_split_geometry: bad argument");
+    int64_t tile, group, stride;
+    split_geometry(c->rs_filters[(size_t)filter], nsel, tile, group, stride);
+    *tile_out = (int32_t)tile; *group_out = (int32_t)group;
+    return ISS_OK;
 }
 
 extern "C" int iss_resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,

@@ -14,7 +14,7 @@ import numpy as np
 from . import _native
 from . import resample as R
 from .io import need_16k_mono, source_of
-from .sources import CodedSource
+from .sources import CodedSource, RawSource, rows_splits
 
 MAGIC = b'fLaC'
 # benchmark switch (tools/bench_flac.py), not a user option: True makes the ffmpeg-free read decode FLAC on the host
@@ -112,6 +112,12 @@ class FlacStream:
     def source(self, resample=False):
         return source(self, resample)
 
+    def split_source(self, sel):
+        """What Segmenter reads for the channels `sel` of a multi-channel stream, each on its own (io.split_source)."""
+        if _HOST_DECODE:
+            return RawSource(self.decode_host(), self.sr, sel=sel)
+        return FlacSource(self, 'resample', sel)
+
 
 class FlacSource(CodedSource):
     """A FLAC file for the device decoder (sources.py states what it answers).  kind: 'pcm' (mono 8/16-bit at 16 kHz), 'float'
@@ -130,7 +136,8 @@ class FlacSource(CodedSource):
             return (src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_SIGNAL, -1, dst_offset, 0)
         if self.kind == 'resample':
             fid, _, _ = ctx.resample_filter(s.sr)
-            return (src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_STAGE, fid, dst_offset, self.size)
+            return self.with_split((src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_STAGE, fid,
+                                    dst_offset, self.size))
         return (src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_STAGE, -1, 0, 0)
 
     @staticmethod
@@ -139,7 +146,8 @@ class FlacSource(CodedSource):
 
     @staticmethod
     def launch(ctx, staged, jobs, frames, n_signal=-1):
-        return ctx.flac_decode(staged, frames, jobs, n_signal)
+        rows, kw = rows_splits(jobs)
+        return ctx.flac_decode(staged, frames, rows, n_signal, **kw)
 
     def samples(self, ctx):
         """'float', on its own: decoded to the staging buffer -> the stored int32 samples on the host (checked)."""

@@ -13,6 +13,8 @@ device's frame decoder; so do G.711 and IMA ADPCM in WAV, RF64 / BW64, Wave64, A
 tables, byte swaps and the host build of the device's IMA decoder).  A file is read once (`_read_file`) and `_classify` says
 from its bytes which parser takes it: a new format is one line there.  `decode_pcm` is the entry the native pipeline uses: it keeps
 PCM16 as int16 so the device does the x/32768 scaling (2 B/sample over PCIe, not 4).
+`split_source` reads the channels of a file each on its own (an extension: the reference needs one ffmpeg -map_channel run per
+channel): a source with a channel selection for the device; `decode_channels` is its host-only twin.
 `excerpts` reads time ranges of one file without ffmpeg (an extension: start/stop through decode_pcm keep raising): per range the
 samples of the 16 kHz mono twin or a windowed source holding only the bytes it needs; `decode_excerpts` finishes them on the host.
 """
@@ -140,11 +142,16 @@ def _check_no_ffmpeg(medianame, start_sec, stop_sec):
             f'or use ffmpeg. You gave medianame={medianame}.')
 
 
-def need_16k_mono(name, sr, channels):
-    """The refusal of the ffmpeg-free read without `resample` (io.py:53-55), the same for every format: rate first."""
+def need_16k(name, sr):
+    """The rate half of need_16k_mono, for reads that take the channels apart."""
     assert sr == 16_000, \
         f'Without ffmpeg, inaSpeechSegmenter can only take files sampled ' \
         f'at 16000 Hz. The file {name} is sampled at {sr} Hz.'
+
+
+def need_16k_mono(name, sr, channels):
+    """The refusal of the ffmpeg-free read without `resample` (io.py:53-55), the same for every format: rate first."""
+    need_16k(name, sr)
     if channels != 1:
         raise ValueError(f'{name}: {channels} channels; without ffmpeg only mono files are supported')
 
@@ -185,6 +192,75 @@ def media2sig16kmono(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg', 
     """Reference-compatible signature and result (float array of `dtype`)."""
     a = decode_pcm(medianame, start_sec, stop_sec, ffmpeg)
     return _to_float(a, np.dtype(dtype)) if a.dtype == np.int16 else a.astype(dtype)
+
+
+# ---------------------------------------------------------------------------------------------- channels of a file, each on its own
+def channel_selection(name, channels, nch):
+    """The selection `channels` of a file of `nch` channels as a list: None = all, ascending; else 0-based indices in the order
+    given (repeats allowed).  ValueError, naming the file: an empty selection, an index outside the file's channels."""
+    if channels is None:
+        return list(range(nch))
+    if isinstance(channels, (str, bytes)):
+        raise ValueError(f'{name}: channels={channels!r} must be None or a sequence of channel indices')
+    sel = [int(ch) for ch in channels]
+    if not sel:
+        raise ValueError(f'{name}: empty channel selection')
+    for ch in sel:
+        if not 0 <= ch < nch:
+            raise ValueError(f'{name}: channel {ch} is outside the file\'s {nch} channel{"s" if nch > 1 else ""} (0 .. {nch - 1})')
+    return sel
+
+
+def channel_name(dst, k):
+    """The output of channel k of a file whose unsplit output is `dst`: a.csv -> a.ch<k>.csv."""
+    stem, ext = os.path.splitext(dst)
+    return f'{stem}.ch{k}{ext}'
+
+
+def _check_local(medianame):
+    if medianame.startswith('http://') or medianame.startswith('https://'):
+        raise ValueError(f'{medianame}: the channels of media on http servers cannot be read; download the file beforehand')
+
+
+def split_source(medianame, channels=None, resample=False):
+    """-> (sel, sig): the selection as a list, and what Segmenter reads for it.  A file of two or more channels gives a source
+    of sources.py carrying the selection (RawSource, flac.FlacSource, sndfmt.AdpcmSource: one signal per selected channel, the
+    16 kHz twin of that channel alone); a one-channel file gives what the whole-file read gives (sel is then all zeros).
+    Without `resample` a rate other than 16 kHz is refused as the whole-file read refuses it; the channel count is not."""
+    _check_local(medianame)
+    buf = _read_file(medianame)
+    what = _classify(buf, medianame)
+    if what is None:
+        x, sr = _parse_wav(buf, medianame)
+        nch = 1 if x.ndim == 1 else x.shape[1]
+    else:
+        nch, sr = what.ch, what.sr
+    sel = channel_selection(medianame, channels, nch)
+    if nch == 1:
+        return sel, what.source(resample) if what is not None else source_of(x, sr, medianame, resample)
+    if not resample:
+        need_16k(medianame, sr)
+    R.check_rate(sr)
+    return sel, RawSource(x, sr, sel=sel) if what is None else what.split_source(sel)
+
+
+def decode_channels(medianame, channels=None, resample=True):
+    """Host-only twin of Segmenter.load_pcm_channels: [resample.resample_ref(stored[:, c], sr) for c in channels] for a file of
+    two or more channels (stored, sr = decode_source(medianame)), [decode_pcm(medianame, ffmpeg=None)] per selected entry for a
+    one-channel file.  channels: None (all, ascending) or 0-based indices in the order given.  resample=False refuses a rate
+    other than 16 kHz as Segmenter(resample=False) does."""
+    _check_local(medianame)
+    x, sr = decode_source(medianame)
+    nch = 1 if x.ndim == 1 else x.shape[1]
+    sel = channel_selection(medianame, channels, nch)
+    if nch == 1:
+        if sr != R.SR_OUT and resample:
+            return [R.resample_ref(x, sr)] * len(sel)
+        return [decode_pcm(medianame, ffmpeg=None)] * len(sel)
+    if not resample:
+        need_16k(medianame, sr)
+    R.check_rate(sr)
+    return [R.resample_ref(x[:, ch], sr) for ch in sel]
 
 
 # ---------------------------------------------------------------------------------------------- excerpts (time ranges of a file)

@@ -39,7 +39,7 @@ from . import _native
 from . import segmenter as S
 from . import sources
 
-FRAME_HOP = 160
+FRAME_HOP = sources.FRAME_HOP
 MIN_SAMPLES = 400 + FRAME_HOP * 67                  # 68 frames: shorter media take the single-file path (mspec padding)
 
 
@@ -49,8 +49,16 @@ class _Batch:
     def __init__(self):
         self.idx, self.sigs, self.names, self.errs = [], [], [], {}
 
-    def samples(self):                               # 16 kHz samples (a RawSource's size is its resampled length)
-        return sum(-(-s.size // FRAME_HOP) * FRAME_HOP for s in self.sigs)
+    def samples(self):                               # 16 kHz samples (a RawSource's size is its resampled length), of every part
+        return sum(_parts(s) * (-(-s.size // FRAME_HOP) * FRAME_HOP) for s in self.sigs)
+
+    def parts(self):                                 # signals of the pass: a file split by channel counts one per channel
+        return sum(_parts(s) for s in self.sigs)
+
+
+def _parts(sig):
+    """Signals a decoded file writes: an array one, a source what it says (one per selected channel)."""
+    return sig.parts if isinstance(sig, sources.Source) else 1
 
 
 _held = sources.held                                 # what a decoded signal holds while it waits, for the audio budget
@@ -76,7 +84,7 @@ class _AudioBudget:
             self.cv.notify_all()
 
 
-def _decode_stage(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None, resample=False):
+def _decode_stage(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None, resample=False, channels=None):
     """items: [(index, src)].  Puts (index, src, sig | None, errtext | None) on out_q in completion order, then None."""
     import random
     in_q = queue.Queue()
@@ -92,7 +100,7 @@ def _decode_stage(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None, 
             sig, err, itry = None, None, 0
             while sig is None and itry < nbtry:
                 try:
-                    sig = S._load_source(src, None, None, ffmpeg, resample)
+                    sig = S._load_source(src, None, None, ffmpeg, resample, channels)
                 except:                                            # noqa: E722  (reference semantics, segmenter.py:364-370)
                     itry += 1
                     err = 'error: ' + str(sys.exc_info()[0])
@@ -153,20 +161,25 @@ class _Worker:
             self.ctx.mirror_settings(self.seg.ctx)
 
     def run(self, batch):
-        """-> [ [(label, start_slot, stop_slot)] per file of the batch ]; None for a FLAC / IMA ADPCM file whose frames / blocks
-        the device found malformed (its message in batch.errs)"""
+        """-> [ [(label, start_slot, stop_slot)] per part of the batch ] -- per file, but one per selected channel, in order, for
+        a file split by channel --; None for (every part of) a FLAC / IMA ADPCM file whose frames / blocks the device found
+        malformed (its message in batch.errs, by file)"""
         seg, ctx = self.seg, self.ctx
         st = self.stats
         t_ = time.perf_counter()
-        offs, pos = [], 0
-        for s in batch.sigs:
+        offs, pos = [], 0                            # per file: where its first part starts
+        owner, poffs, psize = [], [], []             # per part: its file, its offset, its samples
+        for f, s in enumerate(batch.sigs):
             offs.append(pos)
-            pos += -(-s.size // FRAME_HOP) * FRAME_HOP
+            stride = -(-s.size // FRAME_HOP) * FRAME_HOP
+            for _ in range(_parts(s)):
+                owner.append(f); poffs.append(pos); psize.append(s.size)
+                pos += stride
         buf = self.pinned('signal', pos, np.int16)
         groups = {}                                  # source class -> [(file, source, offset in the signal)]
         for f, (s, o) in enumerate(zip(batch.sigs, offs)):
             if isinstance(s, sources.Source):        # written by its class's kernel (and the resample kernel)
-                buf[o:o + s.size] = 0
+                buf[o:o + s.parts * s.stride] = 0
                 groups.setdefault(type(s), []).append((f, s, o))
             elif s.dtype == np.int16:
                 buf[o:o + s.size] = s
@@ -203,12 +216,12 @@ class _Worker:
                     batch.errs[f] = 'error: %s %s' % (type(exc), exc)
                 ubeg += s.units
         st['features'] += time.perf_counter() - t_; t_ = time.perf_counter()
-        g0 = [o // FRAME_HOP for o in offs]
-        nfr = [(s.size - 400) // FRAME_HOP + 1 for s in batch.sigs]
-        # energy segmentation per file (segmenter.py:261-267)
+        g0 = [o // FRAME_HOP for o in poffs]
+        nfr = [(n - 400) // FRAME_HOP + 1 for n in psize]
+        # energy segmentation per part (segmenter.py:261-267)
         lsegs = []
-        for f in range(len(batch.sigs)):
-            if f in batch.errs:                      # a malformed FLAC / ADPCM file: no segments, no network rows
+        for f in range(len(owner)):
+            if owner[f] in batch.errs:               # a malformed FLAC / ADPCM file: no segments, no network rows, for any part
                 lsegs.append([])
                 continue
             lsegs.append(S._energy_segments(loge[g0[f]:g0[f] + nfr[f]], seg.energy_ratio))
@@ -280,7 +293,7 @@ class _Worker:
             st['smooth_host'] += time.perf_counter() - t_
         st['batches'] += 1
         st['files'] += len(batch.sigs)
-        return [None if f in batch.errs else l for f, l in enumerate(lsegs)]
+        return [None if owner[f] in batch.errs else l for f, l in enumerate(lsegs)]
 
 
 DEFAULT_BATCH_FILES = 32          # files per device pass at most ...
@@ -291,20 +304,22 @@ DEFAULT_WORKERS = 4               # passes with more contexts in flight overlap 
 
 
 def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch_files=None, batch_seconds=None,
-                  workers=None, decode_threads=4):
+                  workers=None, decode_threads=4, channels=None):
     """Segment `linput` with the networks of `seg`; on_result(index, src, lseg | None, errtext | None, secs) is called from
     the worker threads (serialised by a lock) as results become available, lseg = [(label, start_sec, stop_sec)], secs =
     this file's share of the processing time of its device pass (the pass's wall time / its files: what the reference's
     per-file 'ok <secs>' message reports, segmenter.py:322-327, when files are processed one by one).
     skip: set of indices not to process.  Device failures (NativeError) and exceptions raised by on_result (unwritable
-    outputs) propagate to the caller: the first one is re-raised here once every stage has drained."""
+    outputs) propagate to the caller: the first one is re-raised here once every stage has drained.
+    channels='split': every channel of every file on its own; lseg is then a LIST of segment lists, one per channel of the file."""
     batch_files = batch_files or DEFAULT_BATCH_FILES
     batch_seconds = batch_seconds or DEFAULT_BATCH_SECONDS
     workers = workers or DEFAULT_WORKERS
     items = [(i, src) for i, src in enumerate(linput) if not (skip and i in skip)]
     dec_q = queue.Queue(maxsize=4 * batch_files)
     budget = _AudioBudget(2 * batch_seconds * 16000)        # decoded audio waiting for the packer: <= 2 super-batches
-    _decode_stage(items, seg.ffmpeg, nbtry, trydelay, dec_q, decode_threads, budget, getattr(seg, 'resample', False))
+    _decode_stage(items, seg.ffmpeg, nbtry, trydelay, dec_q, decode_threads, budget, getattr(seg, 'resample', False),
+                  **({} if channels is None else {'channels': channels}))
     batch_q = queue.Queue(maxsize=max(2, workers))
     lock = threading.Lock()
     failure = []
@@ -338,7 +353,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                 # the first passes of a call are short (5, 10, 20 ... minutes of audio) so that the device starts as soon as
                 # a few files are decoded instead of after a whole 40-minute pass per worker
                 lim_s = min(batch_seconds, RAMP_SECONDS * (1 << min(nbatch, 20)))
-                if len(cur.idx) >= batch_files or cur.samples() >= lim_s * 16000:
+                if cur.parts() >= batch_files or cur.samples() >= lim_s * 16000:
                     batch_q.put(('batch', cur))
                     cur = _Batch()
                     nbatch += 1
@@ -373,11 +388,15 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                 if job[0] == 'single':
                     _, i, src, sig = job
                     try:
-                        with warnings.catch_warnings():
-                            warnings.simplefilter('ignore')
-                            mspec, loge, difflen = S._sig2feats(w.ctx, sig, src)
-                        lseg = [(lab, a * .02, b * .02) for lab, a, b in _slots(seg, w.ctx, mspec, loge, difflen)]
-                        res = (lseg, None)
+                        # (a file split by channel: its channels come back to the host and go one by one)
+                        alone = S._parts_pcm(w.ctx, sig) if _parts(sig) > 1 or getattr(sig, 'sel', None) is not None else [sig]
+                        lseg = []
+                        for one in alone:
+                            with warnings.catch_warnings():
+                                warnings.simplefilter('ignore')
+                                mspec, loge, difflen = S._sig2feats(w.ctx, one, src)
+                            lseg.append([(lab, a * .02, b * .02) for lab, a, b in _slots(seg, w.ctx, mspec, loge, difflen)])
+                        res = (lseg if channels is not None else lseg[0], None)
                     except ValueError as exc:                      # too short to analyse: a per-file error
                         res = (None, 'error: %s %s' % (type(exc), exc))
                     with lock:
@@ -385,13 +404,17 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                     continue
                 b = job[1]
                 lsegs = w.run(b)
-                share = (time.time() - t0) / max(len(b.idx), 1)
+                share = (time.time() - t0) / max(len(lsegs), 1)
                 with lock:
-                    for f, (i, src, lseg) in enumerate(zip(b.idx, b.names, lsegs)):
-                        if lseg is None:
+                    q = 0
+                    for f, (i, src, sig) in enumerate(zip(b.idx, b.names, b.sigs)):
+                        mine = lsegs[q:q + _parts(sig)]
+                        q += len(mine)
+                        if f in b.errs:
                             on_result(i, src, None, b.errs[f], share)
-                        else:
-                            on_result(i, src, [(lab, a * .02, c * .02) for lab, a, c in lseg], None, share)
+                            continue
+                        mine = [[(lab, a * .02, c * .02) for lab, a, c in lseg] for lseg in mine]
+                        on_result(i, src, mine if channels is not None else mine[0], None, share)
             except BaseException as exc:                           # noqa: B902  propagate to the caller's thread
                 failure.append(exc)
 

@@ -313,12 +313,15 @@ def _ensure_resident(ctx, mspec):
     return m.shape[0]
 
 
-def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False):
+def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False, channels=None):
     """decode_pcm's 16 kHz mono samples (a numpy array), or -- without ffmpeg -- a source of sources.py for the device to
     finish.  The file is read once and what io._classify makes of its bytes says what Segmenter reads: a FLAC stream
     becomes a flac.FlacSource (compressed frames, decoded on the device like its WAV twin reads), a file of sndfmt.py what
     sndfmt.source makes of it (a RawSource with its format, a sndfmt.AdpcmSource, or the twin's array), and a WAV at another
-    rate or with several channels a RawSource with `resample` and decode_pcm's refusal without it (io.source_of)."""
+    rate or with several channels a RawSource with `resample` and decode_pcm's refusal without it (io.source_of).
+    channels='split' (ffmpeg=None): every channel on its own -- io.split_source's source with all channels selected."""
+    if channels is not None:
+        return iss_io.split_source(medianame, None, resample)[1]
     if ffmpeg is not None:
         return decode_pcm(medianame, start_sec, stop_sec, ffmpeg)
     iss_io._check_no_ffmpeg(medianame, start_sec, stop_sec)
@@ -350,6 +353,15 @@ def _place(ctx, sig, resident=True):
     if resident:
         ctx.set_signal(sig)
     return sig, None
+
+
+def _parts_pcm(ctx, sig):
+    """The signals of a source placed alone (one per selected channel, one otherwise), copied back to the host and checked."""
+    status = sig.place(ctx)
+    out = [ctx.get_signal_pcm16(k * sig.stride, sig.size) for k in range(sig.parts)]
+    if status is not None:
+        sig.check(status)
+    return out
 
 
 def _sig2feats(ctx, sig, medianame='<signal>'):
@@ -485,6 +497,63 @@ class Segmenter:
             sig.check(status)
         return host
 
+    # ---- the channels of one file, each on its own, without ffmpeg (an extension: the reference needs one ffmpeg run per channel)
+    def _channel_sig(self, medianame, channels):
+        if self.ffmpeg is not None:
+            raise ValueError(f'channels are split without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={self.ffmpeg!r} downmixes '
+                             f'every file with -ac 1')
+        return iss_io.split_source(medianame, channels, self.resample)
+
+    def _mono_pcm(self, sig):
+        host, status = _place(self.ctx, sig, resident=False)
+        if host is None:
+            host = self.ctx.get_signal_pcm16(0, sig.size)
+            sig.check(status)
+        return host
+
+    def load_pcm_channels(self, medianame, channels=None):
+        """One int16 array per selected channel of `medianame`: for a file of two or more channels exactly
+        resample.resample_ref(stored[:, c], sr), stored and sr from io.decode_source -- channel c alone, scaled, resampled to
+        16 kHz and quantised like load_pcm's downmix (at 16 kHz the stored PCM16 values themselves) --, all of them by ONE decode
+        launch and ONE resample launch.  A one-channel file gives [load_pcm(medianame)] (the float path included).
+        channels: None (all, ascending) or a sequence of 0-based indices, in the order given; repeats are allowed.
+        ValueError, naming the file: an index outside the file's channels, an empty selection, an http source; naming the
+        argument with ffmpeg set.  Without resample=True a rate other than 16 kHz is refused as load_pcm refuses it."""
+        sel, sig = self._channel_sig(medianame, channels)
+        if getattr(sig, 'sel', None) is None:                    # a one-channel file
+            return [self._mono_pcm(sig)] * len(sel)
+        return _parts_pcm(self.ctx, sig)
+
+    def segment_channels(self, medianame, channels=None, batch_files=None, batch_seconds=None):
+        """Segment every selected channel of one file on its own -> [[(label, start, stop), ...] per selected channel], in the
+        order of `channels` (as load_pcm_channels takes them).  List k is exactly what
+        segment_signal(load_pcm_channels(medianame, [channels[k]])[0]) gives.  All channels of the file that fit a pass (at most
+        batch_files channels / batch_seconds of audio, the defaults of batch_process) go through one decode launch, one
+        resample launch and one feature pass.  Channels shorter than 68 frames go alone as segment_signal takes them (padding
+        and warning included).  Errors as load_pcm_channels; a malformed FLAC frame or IMA block fails the call (ValueError
+        naming its byte offset)."""
+        from . import pipeline
+        sel, sig = self._channel_sig(medianame, channels)
+        if getattr(sig, 'sel', None) is None:
+            return [self.segment_signal(self._mono_pcm(sig))] * len(sel)
+        if sig.size < pipeline.MIN_SAMPLES:
+            return [self.segment_signal(x) for x in _parts_pcm(self.ctx, sig)]
+        cache = self.__dict__.setdefault('_pipeline_workers', [])
+        if not cache:
+            cache.append(pipeline._Worker(self, self.ctx))
+        nmax = batch_files or pipeline.DEFAULT_BATCH_FILES
+        smax = (batch_seconds or pipeline.DEFAULT_BATCH_SECONDS) * 16000
+        per = max(1, min(nmax, -(-smax // sig.stride)))          # channels per pass
+        out = []
+        for k in range(0, len(sel), per):
+            batch = pipeline._Batch()
+            batch.idx, batch.sigs, batch.names = [0], [sig.reselect(sel[k:k + per])], [medianame]
+            lsegs = cache[0].run(batch)
+            if 0 in batch.errs:                                  # 'error: <class ValueError> <message>' (pipeline._Worker.run)
+                raise ValueError(batch.errs[0][len('error: %s ' % (ValueError,)):])
+            out += [[(lab, a * .02, b * .02) for lab, a, b in lseg] for lseg in lsegs]
+        return out
+
     # ---- time ranges of one file without ffmpeg (an extension: the reference cuts them with ffmpeg's -ss / -to)
     def _excerpt_sigs(self, medianame, ranges):
         """io.excerpts for this Segmenter -> (ranges as a list, per range an array or a windowed source).  What io.excerpts
@@ -597,14 +666,26 @@ class Segmenter:
         return self.segment_feats(mspec, loge, difflen, start_sec)
 
     def batch_process(self, linput, loutput, verbose=False, skipifexist=False, nbtry=1, trydelay=2., output_format='csv',
-                      batch_files=None, workers=None, batch_seconds=None):
+                      batch_files=None, workers=None, batch_seconds=None, channels=None):
         """segmenter.py:297-335: same arguments, same (t_batch_dur, nb_processed, avg, lmsg) with
         lmsg entries (dst, code, text), code 0 ok / 1 already exists / 2 error, in input order.
         The files run through pipeline.process_files: decode threads, super-batches of at most `batch_files` files /
         `batch_seconds` of audio per device pass (defaults 32 / 40 min), `workers` (default 4) device contexts in turn (the reference overlaps the feature extraction of file i+1 with the
         networks of file i, :377-387).  Undecodable or too-short media are per-file errors (code 2) as in the
-        reference; device failures and unwritable outputs raise."""
+        reference; device failures and unwritable outputs raise.
+        channels (an extension, ffmpeg=None only): None is the above; 'split' segments every channel of every file on its own
+        (segment_channels) and writes one output per channel, <dst stem>.ch<k><ext> (a.csv -> a.ch0.csv, a.ch1.csv; a mono file
+        writes .ch0 only).  A file's outputs are written in descending channel order, so .ch0 existing means the file is complete:
+        skipifexist tests that name.  lmsg then holds one entry per written output, files in input order and channels ascending;
+        a file that fails to decode gives one code-2 entry carrying the unsplit dst.  Each channel counts as a file against
+        batch_files, its samples against batch_seconds."""
         from . import pipeline
+        if channels not in (None, 'split'):
+            raise ValueError(f"channels={channels!r}: None or 'split'")
+        if channels is not None and self.ffmpeg is not None:
+            raise ValueError(f"channels='split' reads files without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={self.ffmpeg!r} "
+                             f"downmixes every file with -ac 1")
+        first = (lambda dst: dst) if channels is None else (lambda dst: iss_io.channel_name(dst, 0))
         if verbose:
             print('batch_processing %d files' % len(linput))
         if output_format == 'csv':
@@ -618,8 +699,8 @@ class Segmenter:
         linput, loutput = list(linput), list(loutput)
         msgs, skip, done = {}, set(), [0]
         for i, dst in enumerate(loutput):
-            if skipifexist and os.path.exists(dst):
-                msgs[i] = (dst, 1, 'already exists')
+            if skipifexist and os.path.exists(first(dst)):
+                msgs[i] = (first(dst), 1, 'already exists')
                 skip.add(i)
             else:
                 dname = os.path.dirname(dst)
@@ -630,6 +711,12 @@ class Segmenter:
             dst = loutput[i]
             if lseg is None:
                 msgs[i] = (dst, 2, err)
+            elif channels is not None:                         # one segment list per channel: the last channel's output first
+                b = time.time()
+                for k in reversed(range(len(lseg))):
+                    fexport(lseg[k], iss_io.channel_name(dst, k))
+                text = 'ok ' + str(secs + (time.time() - b) / len(lseg))
+                msgs[i] = [(iss_io.channel_name(dst, k), 0, text) for k in range(len(lseg))]
             else:
                 b = time.time()
                 fexport(lseg, dst)
@@ -641,8 +728,8 @@ class Segmenter:
                 print('%d/%d' % (done[0] + len(skip), len(linput)), [msgs[i]])
 
         pipeline.process_files(self, linput, on_result, skip=skip, nbtry=nbtry, trydelay=trydelay,
-                               batch_files=batch_files, workers=workers, batch_seconds=batch_seconds)
-        lmsg = [msgs[i] for i in range(len(linput))]
+                               batch_files=batch_files, workers=workers, batch_seconds=batch_seconds, channels=channels)
+        lmsg = [m for i in range(len(linput)) for m in (msgs[i] if isinstance(msgs[i], list) else [msgs[i]])]
         t_batch_dur = time.time() - t_batch_start
         nb_processed = len([e for e in lmsg if e[1] == 0])
         avg = t_batch_dur / nb_processed if nb_processed > 0 else -1

@@ -25,7 +25,7 @@ from . import _native
 from . import flac
 from . import resample as R
 from .io import _to_float, need_16k_mono
-from .sources import CodedSource, RawSource
+from .sources import CodedSource, RawSource, rows_splits
 
 # benchmark switch (tools/bench_sndfmt.py), not a user option: True makes the ffmpeg-free read expand G.711 and IMA ADPCM on
 # the host (numpy table / iss_adpcm_decode_host in the decode threads) instead of handing the stored bytes to the device
@@ -114,6 +114,16 @@ class Sound:
 
     def source(self, resample=False):
         return source(self, resample)
+
+    def split_source(self, sel):
+        """What Segmenter reads for the channels `sel` of a multi-channel file, each on its own (io.split_source)."""
+        host = _HOST_DECODE and self.kind in ('ulaw', 'alaw', 'ima')
+        if self.kind == 'ima' and not host and self.n > 0:
+            return AdpcmSource(self, 'resample', sel)
+        if host or self.kind == 'ima':
+            return RawSource(self.stored(), self.sr, sel=sel)
+        x, fmt = self.raw()
+        return RawSource(x, self.sr, fmt, sel)
 
     def stored(self):
         """The array io._parse_wav returns for the WAV twin: (n,) or (n, ch), uint8 / int16 / int32 / float32 / float64."""
@@ -519,7 +529,8 @@ class AdpcmSource(CodedSource):
         if self.kind == 'pcm':
             return (src_offset, block_begin, s.nblocks, s.n, s.ch, s.block_align, _native.ADPCM_TO_SIGNAL, -1, dst_offset, 0)
         fid, _, _ = ctx.resample_filter(s.sr)
-        return (src_offset, block_begin, s.nblocks, s.n, s.ch, s.block_align, _native.ADPCM_TO_STAGE, fid, dst_offset, self.size)
+        return self.with_split((src_offset, block_begin, s.nblocks, s.n, s.ch, s.block_align, _native.ADPCM_TO_STAGE, fid,
+                                dst_offset, self.size))
 
     @staticmethod
     def tables(group):
@@ -527,7 +538,8 @@ class AdpcmSource(CodedSource):
 
     @staticmethod
     def launch(ctx, staged, jobs, nblocks, n_signal=-1):
-        return ctx.adpcm_decode(staged, jobs, nblocks, n_signal)
+        rows, kw = rows_splits(jobs)
+        return ctx.adpcm_decode(staged, rows, nblocks, n_signal, **kw)
 
 
 class AdpcmExcerpt(CodedSource):

@@ -288,6 +288,48 @@ int iss_adpcm_decode_windows(iss_ctx* ctx, const void* src, int64_t src_bytes, c
                              const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
                              int32_t* status_out);
 
+/* Splits: the channels of a file written apart instead of averaged, through the same three entry points' kernels.  A split row
+ * stands beside a job row (splits[k] belongs to jobs[k]); splits == NULL is the plain call, to the bit and to the launch.
+ * channel_sel[0, nsel) is one table of 0-based channel indices for the whole call; a job's selection is its rows
+ * sel[q] = channel_sel[sel_begin + q], q in [0, sel_count).
+ *   resample rows   sel_count > 0: the job writes sel_count mono outputs of frames_out samples each, output q at dst_offset +
+ *                   q * dst_stride.  Output q is channel c = sel[q] of the source alone: m[j] is the stored sample of channel c
+ *                   scaled as above, with no sum and no division by the channel count; tap walk, ascending-j sum with separate
+ *                   multiply and add, rounding and saturation are those of the plain call (inaspeechsegmenter_amd/resample.py's
+ *                   resample_ref on the channel's column, to the bit; with up = down = 1 the stored PCM16 value itself).
+ *                   Entries of a selection lie in [0, channels); they may repeat and come in any order.  dst_stride >=
+ *                   frames_out.  Samples between the end of an output and the next stride are not written.
+ *                   sel_count == 0: the job downmixes all its channels exactly as the plain call does, in the same launch;
+ *                   dst_stride and sel_begin are not read.
+ *   decoder rows    only a TO_STAGE job with a filter may carry sel_count > 0: the decode kernel stages the interleaved samples
+ *                   as always, and the split row is handed to the resample row that reads them.  Any other job must have
+ *                   sel_count == 0.
+ * The grid of the resample launch is ragged over (job, channel group, tile): a group holds as many selected channels as fit
+ * 64 KiB of float64 spans side by side at the job's tile (two channels are kept in one group before the tile grows); a
+ * workgroup stages its group once and computes its channels one after the other.  iss_resample_split_geometry reports the
+ * (tile, channels per group) of a selection of nsel channels through a registered filter.
+ * ISS_EINVAL (checked before anything is launched or the context changes, the text names the job): sel_count < 0, selection
+ * rows outside [0, nsel), a selected channel outside [0, channels), dst_stride < frames_out, one of the sel_count destination
+ * ranges outside the signal, any two destination ranges of the call overlapping (those of other jobs and of TO_SIGNAL jobs
+ * included), a decoder job with a selection that is not TO_STAGE with a filter.
+ * Windows and splits are not combined: the split entry points take no iss_window, and the *_windows entry points no split.
+ * iss_resample_stats counts a split job as ONE job whatever its sel_count; launches, status, staging, the signal rule and all
+ * other errors are as for the plain entry point.                                                                              */
+typedef struct {
+    int64_t dst_stride;   /* samples between the outputs of consecutive selected channels, >= frames_out */
+    int32_t sel_begin;    /* the job's rows of channel_sel: [sel_begin, sel_begin + sel_count)            */
+    int32_t sel_count;    /* 0: downmix all channels, exactly as the plain call does                      */
+} iss_split;
+int iss_resample_pcm16_split(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
+                             int64_t n_signal, const iss_split* splits, const int32_t* channel_sel, int64_t nsel);
+int iss_flac_decode_split(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
+                          const iss_flac_job* jobs, int32_t njobs, int64_t n_signal, int32_t* status_out,
+                          const iss_split* splits, const int32_t* channel_sel, int64_t nsel);
+int iss_adpcm_decode_split(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, int32_t njobs,
+                           int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_split* splits,
+                           const int32_t* channel_sel, int64_t nsel);
+int iss_resample_split_geometry(iss_ctx* ctx, int32_t filter, int32_t nsel, int32_t* tile_out, int32_t* group_out);
+
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */
 int iss_host_alloc(iss_ctx* ctx, size_t bytes, void** out);

@@ -42,6 +42,9 @@ def build_parser():
     ap.add_argument('--resample', action='store_true',
                     help='with -b None: downmix and resample files of other rates / channel counts (8 kHz G.711 telephony, 44.1 kHz AIFF ...) to '
                          '16 kHz mono on the GPU')
+    ap.add_argument('--channels', choices=['mix', 'split'], default='mix',
+                    help="with -b None: 'split' segments every channel of a file on its own (two-channel call recordings, multi-track "
+                         "broadcast files) and writes <basename>.ch<k>.<format> per channel; 'mix' downmixes as ever")
     return ap
 
 
@@ -50,6 +53,10 @@ def main(argv=None):
     ffmpeg = None if args.ffmpeg_binary.lower() in ('none', '') else args.ffmpeg_binary
     if args.resample and ffmpeg is not None:
         build_parser().error('--resample needs -b None (ffmpeg already resamples)')
+    if args.channels == 'split' and ffmpeg is not None:
+        build_parser().error('--channels split needs -b None (ffmpeg downmixes every file)')
+    if args.channels == 'split' and int(os.environ.get('WORLD_SIZE', '1')) != 1:
+        build_parser().error('--channels split runs on one GPU')
     if ffmpeg is None:
         print('Disabling ffmpeg. ' + ('WAV files at other rates or with several channels are resampled on the GPU.' if args.resample
                                       else 'Make sure your audio files are already sampled at 16kHz.'))
@@ -69,7 +76,8 @@ def main(argv=None):
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         if world == 1:
-            seg.batch_process(inputs, outputs, verbose=True, output_format=args.export_format)
+            seg.batch_process(inputs, outputs, verbose=True, output_format=args.export_format,
+                              **({'channels': 'split'} if args.channels == 'split' else {}))
             return 0
         import torch
         import torch.distributed as dist
