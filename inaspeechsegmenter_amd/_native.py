@@ -409,22 +409,24 @@ class Context:
         apart, channel k of the selection at dst_offset + k * dst_stride; None downmixes as ever.  Not with windows."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=RS_JOB))
+        self._decode_call('iss_resample_pcm16', (C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data)),
+                          (jb.size, int(n_signal)), windows, splits)
+        self._keep_rs = src         # the async H2D copy reads it until the next sync
+
+    def _decode_call(self, base, lead, trail, windows, splits):
+        """One of the three entry points of `base`: base(ctx, *lead, *trail), or base_windows with the WINDOW rows between
+        `lead` (which ends with the job rows) and `trail` (which begins with their count), or base_split with the SPLIT rows,
+        the channel table and its length behind `trail`."""
+        name, args = base, lead + trail
         if splits is not None:
             if windows is not None:
                 raise ValueError('windows and splits are not combined')
-            sp, sel = _split_rows(splits, jb.size)
-            self._ck(self._L.iss_resample_pcm16_split(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
-                                                      jb.size, int(n_signal), C.c_void_p(sp.ctypes.data),
-                                                      C.c_void_p(sel.ctypes.data), sel.size), 'iss_resample_pcm16_split')
-        elif windows is None:
-            self._ck(self._L.iss_resample_pcm16(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
-                                                jb.size, int(n_signal)), 'iss_resample_pcm16')
-        else:
-            wn = _window_rows(windows, jb.size)
-            self._ck(self._L.iss_resample_pcm16_windows(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
-                                                        C.c_void_p(wn.ctypes.data), jb.size, int(n_signal)),
-                     'iss_resample_pcm16_windows')
-        self._keep_rs = src         # the async H2D copy reads it until the next sync
+            sp, sel = _split_rows(splits, trail[0])
+            name, args = base + '_split', args + (C.c_void_p(sp.ctypes.data), C.c_void_p(sel.ctypes.data), sel.size)
+        elif windows is not None:
+            wn = _window_rows(windows, trail[0])
+            name, args = base + '_windows', lead + (C.c_void_p(wn.ctypes.data),) + trail
+        self._ck(getattr(self._L, name)(self._h, *args), name)
 
     def resample_signal(self, x, sr, fmt=None):
         """A single source resampled on its own: the resident signal becomes its 16 kHz mono PCM16 -> its length.  (For arrays in
@@ -483,23 +485,9 @@ class Context:
         fr = np.ascontiguousarray(frames, dtype=FLAC_FRAME)
         jb = np.ascontiguousarray(np.array(jobs, dtype=FLAC_JOB).reshape(-1))
         st = self._status('_flac_status', len(fr))
-        if splits is not None:
-            if windows is not None:
-                raise ValueError('windows and splits are not combined')
-            sp, sel = _split_rows(splits, jb.size)
-            self._ck(self._L.iss_flac_decode_split(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data),
-                                                   len(fr), C.c_void_p(jb.ctypes.data), jb.size, int(n_signal), _ptr(st, C.c_int32),
-                                                   C.c_void_p(sp.ctypes.data), C.c_void_p(sel.ctypes.data), sel.size),
-                     'iss_flac_decode_split')
-        elif windows is None:
-            self._ck(self._L.iss_flac_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data), len(fr),
-                                             C.c_void_p(jb.ctypes.data), jb.size, int(n_signal), _ptr(st, C.c_int32)),
-                     'iss_flac_decode')
-        else:
-            wn = _window_rows(windows, jb.size)
-            self._ck(self._L.iss_flac_decode_windows(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data),
-                                                     len(fr), C.c_void_p(jb.ctypes.data), C.c_void_p(wn.ctypes.data), jb.size,
-                                                     int(n_signal), _ptr(st, C.c_int32)), 'iss_flac_decode_windows')
+        self._decode_call('iss_flac_decode', (C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data), len(fr),
+                                              C.c_void_p(jb.ctypes.data)), (jb.size, int(n_signal), _ptr(st, C.c_int32)),
+                          windows, splits)
         self._keep_flac = (src, fr)    # the async H2D copy reads them until the next sync
         return st[:len(fr)]
 
@@ -522,22 +510,8 @@ class Context:
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=ADPCM_JOB).reshape(-1))
         st = self._status('_adpcm_status', nblocks)
-        if splits is not None:
-            if windows is not None:
-                raise ValueError('windows and splits are not combined')
-            sp, sel = _split_rows(splits, jb.size)
-            self._ck(self._L.iss_adpcm_decode_split(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
-                                                    jb.size, int(nblocks), int(n_signal), _ptr(st, C.c_int32),
-                                                    C.c_void_p(sp.ctypes.data), C.c_void_p(sel.ctypes.data), sel.size),
-                     'iss_adpcm_decode_split')
-        elif windows is None:
-            self._ck(self._L.iss_adpcm_decode(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data), jb.size,
-                                              int(nblocks), int(n_signal), _ptr(st, C.c_int32)), 'iss_adpcm_decode')
-        else:
-            wn = _window_rows(windows, jb.size)
-            self._ck(self._L.iss_adpcm_decode_windows(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data),
-                                                      C.c_void_p(wn.ctypes.data), jb.size, int(nblocks), int(n_signal),
-                                                      _ptr(st, C.c_int32)), 'iss_adpcm_decode_windows')
+        self._decode_call('iss_adpcm_decode', (C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data)),
+                          (jb.size, int(nblocks), int(n_signal), _ptr(st, C.c_int32)), windows, splits)
         self._keep_adpcm = src         # the async H2D copy reads it until the next sync
         return st[:int(nblocks)]
 

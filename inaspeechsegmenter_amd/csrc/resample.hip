@@ -452,35 +452,32 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     return ISS_OK;
 }
 
-extern "C" int iss_resample_pcm16_windows(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
-                                          const iss_window* windows, int32_t njobs, int64_t n_signal) {
-    const char* who = windows ? "iss_resample_pcm16_windows" : "iss_resample_pcm16";
+// the one body of the three entry points: `windows`, `splits` or neither beside the jobs (a null pointer is "neither")
+static int resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
+                          int64_t n_signal, const iss_window* windows, const iss_split* splits, const int32_t* channel_sel,
+                          int64_t nsel) {
+    const char* who = splits ? "iss_resample_pcm16_split" : windows ? "iss_resample_pcm16_windows" : "iss_resample_pcm16";
     if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0))
         return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
     IssDecodePass pass;
     int rc = pass.begin(c, who, n_signal, 0);
     pass.rjobs.assign(jobs, jobs + njobs); pass.stage = src_bytes;      // no placement: the caller's rows over the caller's bytes
     if (windows) { pass.rwins.assign(windows, windows + njobs); pass.windowed = true; }
+    if (splits) { pass.rsplits.assign(splits, splits + njobs); pass.split = true; pass.sel = channel_sel; pass.nsel = nsel; }
     if (rc || (rc = pass.commit(nullptr))) return rc;
     if (njobs == 0) return ISS_OK;
     if ((rc = iss_upload_payload(c, c->rs_src, "resample", src, src_bytes, (size_t)std::max<int64_t>(src_bytes, 16)))) return rc;
     return iss_resample_launch(c, (const uint8_t*)c->rs_src.p, pass.plan);
 }
 
+extern "C" int iss_resample_pcm16_windows(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
+                                          const iss_window* windows, int32_t njobs, int64_t n_signal) {
+    return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, windows, nullptr, nullptr, 0);
+}
+
 extern "C" int iss_resample_pcm16_split(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
                                         int64_t n_signal, const iss_split* splits, const int32_t* channel_sel, int64_t nsel) {
-    if (!splits) return iss_resample_pcm16_windows(c, src, src_bytes, jobs, nullptr, njobs, n_signal);
-    const char* who = "iss_resample_pcm16_split";
-    if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0))
-        return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
-    IssDecodePass pass;
-    int rc = pass.begin(c, who, n_signal, 0);
-    pass.rjobs.assign(jobs, jobs + njobs); pass.stage = src_bytes;
-    pass.rsplits.assign(splits, splits + njobs); pass.split = true; pass.sel = channel_sel; pass.nsel = nsel;
-    if (rc || (rc = pass.commit(nullptr))) return rc;
-    if (njobs == 0) return ISS_OK;
-    if ((rc = iss_upload_payload(c, c->rs_src, "resample", src, src_bytes, (size_t)std::max<int64_t>(src_bytes, 16)))) return rc;
-    return iss_resample_launch(c, (const uint8_t*)c->rs_src.p, pass.plan);
+    return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, nullptr, splits, channel_sel, nsel);
 }
 
 // (tile, channels per group) the planner gives a job of `nsel` selected channels through filter `filter`
@@ -495,7 +492,7 @@ extern "C" int iss_resample_split_geometry(iss_ctx* c, int32_t filter, int32_t n
 
 extern "C" int iss_resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
                                   int64_t n_signal) {
-    return iss_resample_pcm16_windows(c, src, src_bytes, jobs, nullptr, njobs, n_signal);
+    return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, nullptr, nullptr, nullptr, 0);
 }
 
 extern "C" int iss_resample_stats(iss_ctx* c, int64_t* launches, int64_t* jobs) {

@@ -14,7 +14,7 @@ import numpy as np
 from . import _native
 from . import resample as R
 from .io import need_16k_mono, source_of
-from .sources import CodedSource, RawSource, rows_splits
+from .sources import CodedSource, RawSource
 
 MAGIC = b'fLaC'
 # benchmark switch (tools/bench_flac.py), not a user option: True makes the ffmpeg-free read decode FLAC on the host
@@ -127,45 +127,43 @@ class FlacSource(CodedSource):
     pass_order = 1
     batchable = property(lambda self: self.kind != 'float')
     payload = property(lambda self: self.s.audio)
-    units = property(lambda self: len(self.s.frames))
+    frames = property(lambda self: self.s.frames)
+    units = property(lambda self: len(self.frames))
 
-    def job(self, ctx, src_offset, frame_begin, dst_offset):
+    def row(self, ctx, src_offset, frame_begin, dst_offset):
         """Its FLAC_JOB row: into the signal at dst_offset ('pcm'), resampled to dst_offset ('resample'), or staged ('float')."""
         s = self.s
+        to, fid, dst, nout = _native.FLAC_TO_STAGE, -1, 0, 0
         if self.kind == 'pcm':
-            return (src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_SIGNAL, -1, dst_offset, 0)
-        if self.kind == 'resample':
-            fid, _, _ = ctx.resample_filter(s.sr)
-            return self.with_split((src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_STAGE, fid,
-                                    dst_offset, self.size))
-        return (src_offset, frame_begin, len(s.frames), s.n, s.ch, s.bps, _native.FLAC_TO_STAGE, -1, 0, 0)
+            to, dst = _native.FLAC_TO_SIGNAL, dst_offset
+        elif self.kind == 'resample':
+            fid, dst, nout = ctx.resample_filter(s.sr)[0], dst_offset, self.size
+        return (src_offset, frame_begin, self.units, s.n, s.ch, s.bps, to, fid, dst, nout)
 
     @staticmethod
     def tables(group):
-        return np.concatenate([g.s.frames for g in group])
+        return np.concatenate([g.frames for g in group])
 
     @staticmethod
-    def launch(ctx, staged, jobs, frames, n_signal=-1):
-        rows, kw = rows_splits(jobs)
+    def launch(ctx, staged, rows, frames, n_signal=-1, **kw):
         return ctx.flac_decode(staged, frames, rows, n_signal, **kw)
 
     def samples(self, ctx):
         """'float', on its own: decoded to the staging buffer -> the stored int32 samples on the host (checked)."""
         s = self.s
-        st = self.launch(ctx, s.audio, [self.job(ctx, 0, 0, 0)], s.frames, 0)
+        st = self.launch(ctx, s.audio, [self.row(ctx, 0, 0, 0)], s.frames, 0)
         x = ctx.flac_get_stage(0, s.n, s.ch, s.bps)
         s.check(st)
         return x
 
 
-class FlacExcerpt(CodedSource):
+class FlacExcerpt(FlacSource):
     """Outputs [a, b) of a FLAC file for the windowed decode: the frames that cover the stored-rate samples the excerpt needs
-    ('pcm': [a, b) themselves; 'resample': resample.input_span of them) and their bytes only.  The rows keep the file's sample
+    ('pcm': [a, b) themselves; 'resample': resample.input_span of them) and their bytes only.  Its `frames` keep the file's sample
     numbering; a malformed frame is named by its byte offset in the file.  Frames outside the run are not decoded, so not checked."""
     __slots__ = ('k0', 'rows', 'win', '_payload')
-    pass_order = 1
     payload = property(lambda self: self._payload)
-    units = property(lambda self: len(self.rows))
+    frames = property(lambda self: self.rows)
 
     def __init__(self, stream, kind, a, b):
         self.s, self.kind, self.size = stream, kind, b - a
@@ -183,23 +181,6 @@ class FlacExcerpt(CodedSource):
         self.k0, self.rows, self.win = k0, rows, (s0, s1, stream.n, a, b - a)
         self._payload = stream.audio[byte0:byte0 + int(rows['offset'][-1] + rows['length'][-1])]
         self.nbytes = self._payload.nbytes
-
-    def job(self, ctx, src_offset, frame_begin, dst_offset):
-        s = self.s
-        if self.kind == 'pcm':
-            row = (src_offset, frame_begin, len(self.rows), s.n, s.ch, s.bps, _native.FLAC_TO_SIGNAL, -1, dst_offset, 0)
-        else:
-            fid, _, _ = ctx.resample_filter(s.sr)
-            row = (src_offset, frame_begin, len(self.rows), s.n, s.ch, s.bps, _native.FLAC_TO_STAGE, fid, dst_offset, self.size)
-        return row, self.win
-
-    @staticmethod
-    def tables(group):
-        return np.concatenate([g.rows for g in group])
-
-    @staticmethod
-    def launch(ctx, staged, jobs, frames, n_signal=-1):
-        return ctx.flac_decode(staged, frames, [j for j, _ in jobs], n_signal, windows=[w for _, w in jobs])
 
     def check(self, status):
         self.s.check(status, self.k0)

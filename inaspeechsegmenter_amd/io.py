@@ -294,17 +294,23 @@ def excerpt_bounds(name, n16, start_sec, stop_sec):
     return a, b
 
 
-def _sound_excerpts(h, ranges, resample):
-    """The excerpts of a sndfmt.Sound or SoundHeader `h`: arrays where the whole-file read hands on an array (16 kHz mono:
-    the bytes of [a, b) alone, expanded as sndfmt.source expands the file), windowed sources for the device otherwise."""
-    from . import sndfmt
-    from .sources import RawExcerpt
+def _twin_length(h, resample):
+    """-> (is the parsed file `h` 16 kHz mono?, the length of its 16 kHz mono twin).  A file that is not is refused as the
+    whole-file read refuses it: without `resample` altogether (need_16k_mono), with it for a rate the resampler does not take."""
     mono16k = h.sr == R.SR_OUT and h.ch == 1
     if not mono16k:
         if not resample:
             need_16k_mono(h.name, h.sr, h.ch)
         R.check_rate(h.sr)
-    n16 = h.n if mono16k else R.out_len(h.n, h.sr)
+    return mono16k, h.n if mono16k else R.out_len(h.n, h.sr)
+
+
+def _sound_excerpts(h, ranges, resample):
+    """The excerpts of a sndfmt.Sound or SoundHeader `h`: arrays where the whole-file read hands on an array (16 kHz mono:
+    the bytes of [a, b) alone, expanded as sndfmt.source expands the file), windowed sources for the device otherwise."""
+    from . import sndfmt
+    from .sources import RawExcerpt
+    mono16k, n16 = _twin_length(h, resample)
     out = []
     for start, stop in ranges:
         a, b = excerpt_bounds(h.name, n16, start, stop)
@@ -342,12 +348,7 @@ def excerpts(medianame, ranges, resample=False):
             return [None] * len(ranges)
     if not isinstance(h, flac.FlacStream):
         return _sound_excerpts(h, ranges, resample)
-    mono16k = h.sr == R.SR_OUT and h.ch == 1
-    if not mono16k:
-        if not resample:
-            need_16k_mono(h.name, h.sr, h.ch)
-        R.check_rate(h.sr)
-    n16 = h.n if mono16k else R.out_len(h.n, h.sr)
+    mono16k, n16 = _twin_length(h, resample)
     out = []
     for start, stop in ranges:
         a, b = excerpt_bounds(h.name, n16, start, stop)

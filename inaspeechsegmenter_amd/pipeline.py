@@ -55,6 +55,9 @@ class _Batch:
     def parts(self):                                 # signals of the pass: a file split by channel counts one per channel
         return sum(_parts(s) for s in self.sigs)
 
+    def full(self, batch_files, limit_samples):      # the one rule that closes a pass
+        return self.parts() >= batch_files or self.samples() >= limit_samples
+
 
 def _parts(sig):
     """Signals a decoded file writes: an array one, a source what it says (one per selected channel)."""
@@ -163,7 +166,7 @@ class _Worker:
     def run(self, batch):
         """-> [ [(label, start_slot, stop_slot)] per part of the batch ] -- per file, but one per selected channel, in order, for
         a file split by channel --; None for (every part of) a FLAC / IMA ADPCM file whose frames / blocks the device found
-        malformed (its message in batch.errs, by file)"""
+        malformed (the ValueError in batch.errs, by file)"""
         seg, ctx = self.seg, self.ctx
         st = self.stats
         t_ = time.perf_counter()
@@ -176,45 +179,28 @@ class _Worker:
                 owner.append(f); poffs.append(pos); psize.append(s.size)
                 pos += stride
         buf = self.pinned('signal', pos, np.int16)
-        groups = {}                                  # source class -> [(file, source, offset in the signal)]
+        placed, files = {}, {}                       # source class -> [(source, offset in the signal)]; -> [its file]
         for f, (s, o) in enumerate(zip(batch.sigs, offs)):
             if isinstance(s, sources.Source):        # written by its class's kernel (and the resample kernel)
                 buf[o:o + s.parts * s.stride] = 0
-                groups.setdefault(type(s), []).append((f, s, o))
+                placed.setdefault(type(s), []).append((s, o))
+                files.setdefault(type(s), []).append(f)
             elif s.dtype == np.int16:
                 buf[o:o + s.size] = s
             else:                                    # float sources: what libsndfile's float32 read holds, re-quantised is NOT exact
                 raise TypeError('float media take the single-file path')
             buf[o + s.size:o + -(-s.size // FRAME_HOP) * FRAME_HOP] = 0
-        launches = []
-        for cls in sorted(groups, key=lambda c: c.pass_order):
-            # the payloads of a class end to end, each file on a 16-byte boundary; job rows with running byte / unit offsets
-            grp = groups[cls]
-            pb = self.pinned(cls, sum(-(-s.payload.size // 16) * 16 for _, s, _ in grp), np.uint8)
-            jobs, bpos, ubeg = [], 0, 0
-            for _, s, o in grp:
-                p = s.payload
-                pb[bpos:bpos + p.size] = p
-                jobs.append(s.job(ctx, bpos, ubeg, o))
-                bpos += -(-p.size // 16) * 16
-                ubeg += s.units
-            launches.append((cls, grp, pb[:bpos], jobs, cls.tables([s for _, s, _ in grp])))
+        # the payloads of each class staged in a page-locked buffer of its own
+        groups = [sources.Group(ctx, cls, placed[cls], lambda n, cls=cls: self.pinned(cls, n, np.uint8))
+                  for cls in sorted(placed, key=lambda c: c.pass_order)]
         st['pack'] += time.perf_counter() - t_; t_ = time.perf_counter()
         ctx.set_signal(buf[:pos])
-        # ONE launch per class for all its files of the pass, into the signal above: resampled, FLAC, IMA ADPCM
-        status = [cls.launch(ctx, staged, jobs, tables) for cls, _, staged, jobs, tables in launches]
+        for g in groups:                             # ONE launch per class for all its files of the pass, into the signal above
+            g.launch()
         ctx.sidekit()
         loge = ctx.get_loge()
-        for (_, grp, _, _, _), stat in zip(launches, status):
-            if stat is None:
-                continue
-            ubeg = 0
-            for f, s, _ in grp:                      # the frame / block status came back with the log-energy
-                try:
-                    s.check(stat[ubeg:ubeg + s.units])
-                except ValueError as exc:
-                    batch.errs[f] = 'error: %s %s' % (type(exc), exc)
-                ubeg += s.units
+        for g in groups:                             # the frame / block status came back with the log-energy
+            g.check(lambda k, exc, g=g: batch.errs.__setitem__(files[g.cls][k], exc))
         st['features'] += time.perf_counter() - t_; t_ = time.perf_counter()
         g0 = [o // FRAME_HOP for o in poffs]
         nfr = [(n - 400) // FRAME_HOP + 1 for n in psize]
@@ -312,8 +298,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
     skip: set of indices not to process.  Device failures (NativeError) and exceptions raised by on_result (unwritable
     outputs) propagate to the caller: the first one is re-raised here once every stage has drained.
     channels='split': every channel of every file on its own; lseg is then a LIST of segment lists, one per channel of the file."""
-    batch_files = batch_files or DEFAULT_BATCH_FILES
-    batch_seconds = batch_seconds or DEFAULT_BATCH_SECONDS
+    batch_files, batch_seconds = _limits(batch_files, batch_seconds)
     workers = workers or DEFAULT_WORKERS
     items = [(i, src) for i, src in enumerate(linput) if not (skip and i in skip)]
     dec_q = queue.Queue(maxsize=4 * batch_files)
@@ -353,7 +338,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                 # the first passes of a call are short (5, 10, 20 ... minutes of audio) so that the device starts as soon as
                 # a few files are decoded instead of after a whole 40-minute pass per worker
                 lim_s = min(batch_seconds, RAMP_SECONDS * (1 << min(nbatch, 20)))
-                if cur.parts() >= batch_files or cur.samples() >= lim_s * 16000:
+                if cur.full(batch_files, lim_s * 16000):
                     batch_q.put(('batch', cur))
                     cur = _Batch()
                     nbatch += 1
@@ -388,14 +373,9 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                 if job[0] == 'single':
                     _, i, src, sig = job
                     try:
-                        # (a file split by channel: its channels come back to the host and go one by one)
-                        alone = S._parts_pcm(w.ctx, sig) if _parts(sig) > 1 or getattr(sig, 'sel', None) is not None else [sig]
-                        lseg = []
-                        for one in alone:
-                            with warnings.catch_warnings():
-                                warnings.simplefilter('ignore')
-                                mspec, loge, difflen = S._sig2feats(w.ctx, one, src)
-                            lseg.append([(lab, a * .02, b * .02) for lab, a, b in _slots(seg, w.ctx, mspec, loge, difflen)])
+                        with warnings.catch_warnings():
+                            warnings.simplefilter('ignore')
+                            lseg = one_by_one(seg, w.ctx, sig, src)
                         res = (lseg if channels is not None else lseg[0], None)
                     except ValueError as exc:                      # too short to analyse: a per-file error
                         res = (None, 'error: %s %s' % (type(exc), exc))
@@ -411,19 +391,14 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                         mine = lsegs[q:q + _parts(sig)]
                         q += len(mine)
                         if f in b.errs:
-                            on_result(i, src, None, b.errs[f], share)
+                            on_result(i, src, None, 'error: %s %s' % (type(b.errs[f]), b.errs[f]), share)
                             continue
                         mine = [[(lab, a * .02, c * .02) for lab, a, c in lseg] for lseg in mine]
                         on_result(i, src, mine if channels is not None else mine[0], None, share)
             except BaseException as exc:                           # noqa: B902  propagate to the caller's thread
                 failure.append(exc)
 
-    # device workers are kept with the Segmenter between calls (context creation, network upload and the first
-    # workspace allocation cost more than a 5-minute file)
-    cache = seg.__dict__.setdefault('_pipeline_workers', [])
-    while len(cache) < max(1, workers):
-        cache.append(_Worker(seg, seg.ctx if not cache else None))
-    ws = cache[:max(1, workers)]
+    ws = _workers(seg, workers)
     for w in ws:
         w.sync_settings()
     threads = [threading.Thread(target=work, args=(w,), daemon=True) for w in ws]
@@ -438,9 +413,59 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
         raise failure[0]
 
 
+def _limits(batch_files, batch_seconds):
+    """(files, seconds of audio) a device pass holds at most: the defaults where none is given."""
+    return batch_files or DEFAULT_BATCH_FILES, batch_seconds or DEFAULT_BATCH_SECONDS
+
+
+def _workers(seg, n):
+    """The first n device workers of `seg` (at least one; the first drives seg's own context).  They are kept with the
+    Segmenter between calls: context creation, network upload and the first workspace allocation cost more than a 5-minute file."""
+    cache = seg.__dict__.setdefault('_pipeline_workers', [])
+    while len(cache) < max(1, n):
+        cache.append(_Worker(seg, seg.ctx if not cache else None))
+    return cache[:max(1, n)]
+
+
 def close_workers(seg):
     for w in seg.__dict__.pop('_pipeline_workers', []):
         w.close()
+
+
+def cut_passes(sigs, batch_files=None, batch_seconds=None):
+    """`sigs` in order, cut into device passes under the limits of process_files -> [[index into sigs]]."""
+    batch_files, batch_seconds = _limits(batch_files, batch_seconds)
+    passes, cur = [], _Batch()
+    for k, s in enumerate(sigs):
+        cur.idx.append(k); cur.sigs.append(s)
+        if cur.full(batch_files, batch_seconds * 16000):
+            passes.append(cur.idx)
+            cur = _Batch()
+    return passes + [cur.idx] if cur.idx else passes
+
+
+def run_passes(seg, names, sigs, passes):
+    """The `passes` (cut_passes) of `sigs`, one after the other on seg's own context -> [(label, start_slot, stop_slot)]
+    lists, one per part of every signal of every pass, in that order.  The first malformed file of a pass raises its ValueError."""
+    out = []
+    for idx in passes:
+        batch = _Batch()
+        batch.idx, batch.sigs, batch.names = list(idx), [sigs[k] for k in idx], [names[k] for k in idx]
+        out += _workers(seg, 1)[0].run(batch)
+        if batch.errs:
+            raise ValueError(str(batch.errs[min(batch.errs)]))
+    return out
+
+
+def one_by_one(seg, ctx, sig, name='<signal>'):
+    """A signal that shares no pass (float, or under 68 frames), on `ctx` -> [[(label, start_sec, stop_sec)] per part]: the
+    channels of a file split by channel come back to the host and go one after the other, as any signal alone does."""
+    alone = S._parts_pcm(ctx, sig) if getattr(sig, 'sel', None) is not None else [sig]
+    out = []
+    for one in alone:
+        mspec, loge, difflen = S._sig2feats(ctx, one, name)
+        out.append([(lab, a * .02, b * .02) for lab, a, b in _slots(seg, ctx, mspec, loge, difflen)])
+    return out
 
 
 def _slots(seg, ctx, mspec, loge, difflen):

@@ -485,17 +485,20 @@ class Segmenter:
         mspec, loge, difflen = _sig2feats(self.ctx, np.ascontiguousarray(sig))
         return self.segment_feats(mspec, loge, difflen, start_sec)
 
-    def load_pcm(self, medianame):
-        """The 16 kHz mono samples the front end reads for `medianame` (decode_pcm's int16 or float32 array); with
-        resample=True a WAV at another rate or channel count is resampled on the device and its PCM16 copied back.  Without
-        ffmpeg a FLAC file is decoded on the device and its samples copied back (what decode_pcm gives for its WAV twin),
-        and so is an IMA ADPCM file; G.711 and big-endian files at other rates or channel counts go to the resampler as stored."""
-        sig = _load_source(medianame, None, None, self.ffmpeg, self.resample)
+    def _mono_pcm(self, sig):
+        """The 16 kHz mono samples of what `_load_source` read, on the host: a source placed alone and copied back, checked."""
         host, status = _place(self.ctx, sig, resident=False)
         if host is None:
             host = self.ctx.get_signal_pcm16(0, sig.size)
             sig.check(status)
         return host
+
+    def load_pcm(self, medianame):
+        """The 16 kHz mono samples the front end reads for `medianame` (decode_pcm's int16 or float32 array); with
+        resample=True a WAV at another rate or channel count is resampled on the device and its PCM16 copied back.  Without
+        ffmpeg a FLAC file is decoded on the device and its samples copied back (what decode_pcm gives for its WAV twin),
+        and so is an IMA ADPCM file; G.711 and big-endian files at other rates or channel counts go to the resampler as stored."""
+        return self._mono_pcm(_load_source(medianame, None, None, self.ffmpeg, self.resample))
 
     # ---- the channels of one file, each on its own, without ffmpeg (an extension: the reference needs one ffmpeg run per channel)
     def _channel_sig(self, medianame, channels):
@@ -503,13 +506,6 @@ class Segmenter:
             raise ValueError(f'channels are split without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={self.ffmpeg!r} downmixes '
                              f'every file with -ac 1')
         return iss_io.split_source(medianame, channels, self.resample)
-
-    def _mono_pcm(self, sig):
-        host, status = _place(self.ctx, sig, resident=False)
-        if host is None:
-            host = self.ctx.get_signal_pcm16(0, sig.size)
-            sig.check(status)
-        return host
 
     def load_pcm_channels(self, medianame, channels=None):
         """One int16 array per selected channel of `medianame`: for a file of two or more channels exactly
@@ -537,22 +533,13 @@ class Segmenter:
         if getattr(sig, 'sel', None) is None:
             return [self.segment_signal(self._mono_pcm(sig))] * len(sel)
         if sig.size < pipeline.MIN_SAMPLES:
-            return [self.segment_signal(x) for x in _parts_pcm(self.ctx, sig)]
-        cache = self.__dict__.setdefault('_pipeline_workers', [])
-        if not cache:
-            cache.append(pipeline._Worker(self, self.ctx))
-        nmax = batch_files or pipeline.DEFAULT_BATCH_FILES
-        smax = (batch_seconds or pipeline.DEFAULT_BATCH_SECONDS) * 16000
-        per = max(1, min(nmax, -(-smax // sig.stride)))          # channels per pass
-        out = []
-        for k in range(0, len(sel), per):
-            batch = pipeline._Batch()
-            batch.idx, batch.sigs, batch.names = [0], [sig.reselect(sel[k:k + per])], [medianame]
-            lsegs = cache[0].run(batch)
-            if 0 in batch.errs:                                  # 'error: <class ValueError> <message>' (pipeline._Worker.run)
-                raise ValueError(batch.errs[0][len('error: %s ' % (ValueError,)):])
-            out += [[(lab, a * .02, b * .02) for lab, a, b in lseg] for lseg in lsegs]
-        return out
+            return pipeline.one_by_one(self, self.ctx, sig)
+        # the channels cut into passes as files of their length would be (min(batch_files, ceil(limit / stride)) each), and
+        # each pass one source again: the file with that pass's channels selected
+        passes = pipeline.cut_passes([sig.reselect([ch]) for ch in sel], batch_files, batch_seconds)
+        sigs = [sig.reselect([sel[k] for k in idx]) for idx in passes]
+        lsegs = pipeline.run_passes(self, [medianame] * len(sigs), sigs, [[k] for k in range(len(sigs))])
+        return [[(lab, a * .02, b * .02) for lab, a, b in lseg] for lseg in lsegs]
 
     # ---- time ranges of one file without ffmpeg (an extension: the reference cuts them with ffmpeg's -ss / -to)
     def _excerpt_sigs(self, medianame, ranges):
@@ -572,52 +559,26 @@ class Segmenter:
                 sigs[k] = whole[a:b]
         return ranges, sigs
 
-    @staticmethod
-    def _excerpt_passes(todo, sigs, batch_files, batch_seconds):
-        """The indices `todo` cut into device passes under the limits of batch_process (files, seconds of audio per pass)."""
-        from . import pipeline
-        nmax = batch_files or pipeline.DEFAULT_BATCH_FILES
-        smax = (batch_seconds or pipeline.DEFAULT_BATCH_SECONDS) * 16000
-        cur, held = [], 0
-        for k in todo:
-            cur.append(k)
-            held += -(-sigs[k].size // pipeline.FRAME_HOP) * pipeline.FRAME_HOP
-            if len(cur) >= nmax or held >= smax:
-                yield cur
-                cur, held = [], 0
-        if cur:
-            yield cur
-
     def load_pcm_excerpts(self, medianame, ranges, batch_files=None, batch_seconds=None):
         """load_pcm for time ranges [(start_sec, stop_sec | None)] of one file: [the samples [a, b) of what load_pcm(medianame)
         returns, per range], a = floor(start_sec * 16000 + 0.5), b = its length for stop_sec None, else min(length, floor(stop_sec
         * 16000 + 0.5)) -- a definition (io.excerpt_bounds): ffmpeg's rounding of -ss / -to was not at hand to pin it.  Only the
         bytes, IMA blocks and FLAC frames the ranges need are staged, and all ranges that fit a pass (batch_files /
         batch_seconds as for batch_process) take ONE launch per kernel.  Frames and blocks that are not decoded are not checked."""
+        from . import pipeline
+        from .sources import Group
         ranges, sigs = self._excerpt_sigs(medianame, ranges)
         out = [None if isinstance(s, Source) else s for s in sigs]
         todo = [k for k, s in enumerate(sigs) if isinstance(s, Source)]
-        ctx = self.ctx
-        for idx in self._excerpt_passes(todo, sigs, batch_files, batch_seconds):
-            cls = type(sigs[idx[0]])                             # (one file: one class)
-            staged = np.zeros(sum(-(-sigs[k].payload.size // 16) * 16 for k in idx), dtype=np.uint8)
-            jobs, offs, bpos, ubeg, pos = [], [], 0, 0, 0
-            for k in idx:
-                s, p = sigs[k], sigs[k].payload
-                staged[bpos:bpos + p.size] = p
-                jobs.append(s.job(ctx, bpos, ubeg, pos))
-                offs.append(pos)
-                bpos += -(-p.size // 16) * 16
-                ubeg += s.units
-                pos += s.size
-            status = cls.launch(ctx, staged, jobs, cls.tables([sigs[k] for k in idx]), pos)
-            for k, o in zip(idx, offs):
-                out[k] = ctx.get_signal_pcm16(o, sigs[k].size)
-            ubeg = 0
-            for k in idx:
-                if status is not None:
-                    sigs[k].check(status[ubeg:ubeg + sigs[k].units])
-                ubeg += sigs[k].units
+        for idx in pipeline.cut_passes([sigs[k] for k in todo], batch_files, batch_seconds):
+            placed, pos = [], 0                                  # end to end: the launch creates a signal of just these samples
+            for i in idx:
+                placed.append((sigs[todo[i]], pos))
+                pos += placed[-1][0].size
+            group = Group(self.ctx, type(placed[0][0]), placed).launch(pos)      # (one file: one class)
+            for i, (s, o) in zip(idx, placed):
+                out[todo[i]] = self.ctx.get_signal_pcm16(o, s.size)
+            group.check()
         return out
 
     def segment_excerpts(self, medianame, ranges, batch_files=None, batch_seconds=None):
@@ -642,20 +603,11 @@ class Segmenter:
                 out[k] = self.segment_feats(mspec, loge, difflen, ranges[k][0])
             else:
                 todo.append(k)
-        if todo:
-            cache = self.__dict__.setdefault('_pipeline_workers', [])
-            if not cache:
-                cache.append(pipeline._Worker(self, self.ctx))
-            w = cache[0]
-        for idx in self._excerpt_passes(todo, sigs, batch_files, batch_seconds):
-            batch = pipeline._Batch()
-            batch.idx, batch.sigs, batch.names = list(idx), [sigs[k] for k in idx], [medianame] * len(idx)
-            lsegs = w.run(batch)
-            for f, (k, lseg) in enumerate(zip(idx, lsegs)):
-                if lseg is None:                                 # 'error: <class ValueError> <message>' (pipeline._Worker.run)
-                    raise ValueError(batch.errs[f][len('error: %s ' % (ValueError,)):])
-                start = ranges[k][0]
-                out[k] = [(lab, start + a * .02, start + b * .02) for lab, a, b in lseg]
+        rest = [sigs[k] for k in todo]
+        lsegs = pipeline.run_passes(self, [medianame] * len(rest), rest, pipeline.cut_passes(rest, batch_files, batch_seconds))
+        for k, lseg in zip(todo, lsegs):
+            start = ranges[k][0]
+            out[k] = [(lab, start + a * .02, start + b * .02) for lab, a, b in lseg]
         return out
 
     def __call__(self, medianame, start_sec=None, stop_sec=None):

@@ -25,7 +25,7 @@ from . import _native
 from . import flac
 from . import resample as R
 from .io import _to_float, need_16k_mono
-from .sources import CodedSource, RawSource, rows_splits
+from .sources import CodedSource, RawSource
 
 # benchmark switch (tools/bench_sndfmt.py), not a user option: True makes the ffmpeg-free read expand G.711 and IMA ADPCM on
 # the host (numpy table / iss_adpcm_decode_host in the decode threads) instead of handing the stored bytes to the device
@@ -523,33 +523,29 @@ class AdpcmSource(CodedSource):
     payload = property(lambda self: self.s.data)
     units = property(lambda self: self.s.nblocks)
 
-    def job(self, ctx, src_offset, block_begin, dst_offset):
-        """Its ADPCM_JOB row: into the signal at dst_offset ('pcm') or staged and resampled to dst_offset ('resample')."""
-        s = self.s
-        if self.kind == 'pcm':
-            return (src_offset, block_begin, s.nblocks, s.n, s.ch, s.block_align, _native.ADPCM_TO_SIGNAL, -1, dst_offset, 0)
-        fid, _, _ = ctx.resample_filter(s.sr)
-        return self.with_split((src_offset, block_begin, s.nblocks, s.n, s.ch, s.block_align, _native.ADPCM_TO_STAGE, fid,
-                                dst_offset, self.size))
+    def row(self, ctx, src_offset, block_begin, dst_offset):
+        """Its ADPCM_JOB row: into the signal at dst_offset ('pcm') or staged and resampled to dst_offset ('resample'); the
+        sample count is the whole file's, also where `s` holds the blocks of an excerpt."""
+        s, total = self.s, self.s.n if self.win is None else self.win[2]
+        to, fid, nout = _native.ADPCM_TO_SIGNAL, -1, 0
+        if self.kind != 'pcm':
+            to, fid, nout = _native.ADPCM_TO_STAGE, ctx.resample_filter(s.sr)[0], self.size
+        return (src_offset, block_begin, s.nblocks, total, s.ch, s.block_align, to, fid, dst_offset, nout)
 
     @staticmethod
     def tables(group):
         return sum(g.units for g in group)
 
     @staticmethod
-    def launch(ctx, staged, jobs, nblocks, n_signal=-1):
-        rows, kw = rows_splits(jobs)
+    def launch(ctx, staged, rows, nblocks, n_signal=-1, **kw):
         return ctx.adpcm_decode(staged, rows, nblocks, n_signal, **kw)
 
 
-class AdpcmExcerpt(CodedSource):
+class AdpcmExcerpt(AdpcmSource):
     """Outputs [a, b) of an IMA ADPCM file for the windowed decode: `s` = the sub_sound of the blocks that hold the
     stored-rate samples the excerpt needs ('pcm': [a, b); 'resample': resample.input_span of them), `first` the file's sample
     number of its first sample.  A bad block is named by its byte offset in the file (s.base is one)."""
     __slots__ = ('first', 'win')
-    pass_order = 2
-    payload = property(lambda self: self.s.data)
-    units = property(lambda self: self.s.nblocks)
 
     def __init__(self, h, kind, a, b):
         self.kind, self.size = kind, b - a
@@ -557,23 +553,6 @@ class AdpcmExcerpt(CodedSource):
         self.s, self.first = sub_sound(h, s0, s1)
         self.win = (s0, s1, h.n, a, b - a)
         self.nbytes = self.s.data.nbytes
-
-    def job(self, ctx, src_offset, block_begin, dst_offset):
-        s, total = self.s, self.win[2]
-        if self.kind == 'pcm':
-            row = (src_offset, block_begin, s.nblocks, total, s.ch, s.block_align, _native.ADPCM_TO_SIGNAL, -1, dst_offset, 0)
-        else:
-            fid, _, _ = ctx.resample_filter(s.sr)
-            row = (src_offset, block_begin, s.nblocks, total, s.ch, s.block_align, _native.ADPCM_TO_STAGE, fid, dst_offset, self.size)
-        return row, self.win
-
-    @staticmethod
-    def tables(group):
-        return sum(g.units for g in group)
-
-    @staticmethod
-    def launch(ctx, staged, jobs, nblocks, n_signal=-1):
-        return ctx.adpcm_decode(staged, [j for j, _ in jobs], nblocks, n_signal, windows=[w for _, w in jobs])
 
     def host(self):
         """The same samples by the host build of the decoder, on the same blocks (and resample.resample_ref)."""

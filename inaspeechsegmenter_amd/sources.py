@@ -1,4 +1,5 @@
-"""Decoded sources the device finishes: what every kind of them answers, and the one written for the resample kernel.
+"""Decoded sources the device finishes: what every kind of them answers, the one launch a group of them shares, and the
+kind written for the resample kernel.
 
 The ffmpeg-free read hands on a plain numpy array (16 kHz mono samples: int16, or float32 for the float path) or a `Source`:
 bytes as stored, which a kernel turns into 16 kHz mono PCM16 inside the resident signal.  A source answers
@@ -6,26 +7,31 @@ bytes as stored, which a kernel turns into 16 kHz mono PCM16 inside the resident
     size, held, batchable   its length at 16 kHz (it stands where a signal's `size` is read); what it holds while it waits for
                             the packer, in 16-bit sample units; may it share a device pass with other files?
     payload, units          the bytes to stage (a 1-D uint8 view); status entries the device writes for it (frames, blocks)
-    job(ctx, src_offset, unit_begin, dst_offset)   its job row: payload at byte `src_offset` of the staged bytes, status from
-                            entry `unit_begin`, samples to `dst_offset` of the signal
+    row(ctx, src_offset, unit_begin, dst_offset)   its job row, written once per format: payload at byte `src_offset` of the
+                            staged bytes, status from entry `unit_begin`, samples to `dst_offset` of the signal
+    job(...)                that row as a `Job`, with what the source carries beside it: its window row or its split row
     check(status)           ValueError for a malformed file, from its slice of the status array
-    tables(group), launch(ctx, staged, jobs, tables, n_signal)   (of the class) ONE launch for a group of sources of this
-                            class: what it needs besides bytes and rows (built while packing), and the launch -> the status
-                            array (valid after the context's next synchronising call) or None
-    place(ctx)              that launch for this file alone: the resident signal becomes its `size` samples
+    tables(group), launch(ctx, staged, rows, tables, n_signal, **kw)   (of the class) what ONE launch for a group of sources of
+                            this class needs besides bytes and rows, and the launch -> the status array (valid after the
+                            context's next synchronising call) or None; kw: `windows=` or `splits=`, only where some job has one
     parts                   how many consecutive signals it writes (default 1): `parts` signals of `size` samples each, signal k at
                             dst_offset + k * `stride`, stride = `size` rounded up to FRAME_HOP
 
 A source made with a channel selection `sel` (RawSource, flac.FlacSource, sndfmt.AdpcmSource) writes one signal per selected
-channel instead of their average: `parts` = len(sel), and its job row comes as a SplitJob with the split row (iss_split) that its
-class's launch hands to the split entry point -- downmixed and split files of a pass in the same launch.
+channel instead of their average: `parts` = len(sel), and its job carries the split row (iss_split) for the split entry point
+-- downmixed and split files of a pass in the same launch.
 
-An excerpt of a file (io.excerpts) is a source too: its `size` is the excerpt's, its `payload` only the bytes the excerpt needs,
-and its job row comes with the window row (iss_window) that its class's launch hands to the windowed entry point.
+An excerpt of a file (io.excerpts) is a source too, of a class of its own below its format's: its `size` is the excerpt's, its
+`payload` only the bytes the excerpt needs, and its job carries the window row (iss_window) for the windowed entry point.  A
+windowed launch needs a window beside every job, so whole files and excerpts never share one: launches go by class.
 
-`pass_order` places a class's launch among the device calls of a pass.  pipeline._Worker.run and segmenter._place are written
-against this and nothing else: a new format is one class, and one line in io._classify.
+`Group` is the only place that stages payloads, numbers job rows, launches and hands the status back; `pass_order` places a
+class's launch among the device calls of a pass.  pipeline._Worker.run, Segmenter.load_pcm_excerpts and Source.place (one file
+alone: segmenter._place) are written against this and nothing else: a new format is one class, and one line in io._classify.
 """
+import copy
+from typing import NamedTuple
+
 import numpy as np
 
 from . import _native
@@ -35,20 +41,11 @@ from . import resample
 FRAME_HOP = 160
 
 
-class SplitJob(tuple):
-    """(job row, (dst_stride, [channels])): what `job` returns for a source with a channel selection."""
-    __slots__ = ()
-    row = property(lambda self: self[0])
-    split = property(lambda self: self[1])
-
-
-def rows_splits(jobs):
-    """-> (the job rows of a launch, its keyword arguments): nothing for plain jobs -- the call every launch made before there
-    were splits --, else `splits`: the split of every SplitJob among them, None beside a plain job."""
-    if not any(isinstance(j, SplitJob) for j in jobs):
-        return jobs, {}
-    return ([j.row if isinstance(j, SplitJob) else j for j in jobs],
-            {'splits': [j.split if isinstance(j, SplitJob) else None for j in jobs]})
+class Job(NamedTuple):
+    """What `Source.job` returns: the job row, and the window row or the split `(dst_stride, [channels])` that goes beside it."""
+    row: tuple
+    window: tuple = None
+    split: tuple = None
 
 
 class Source:
@@ -56,6 +53,7 @@ class Source:
     batchable = True
     units = 0
     sel = None                                       # the channel selection, where the class takes one and one was given
+    win = None                                       # the window row, of an excerpt
 
     @property
     def parts(self):
@@ -66,14 +64,12 @@ class Source:
     def stride(self):
         return -(-self.size // FRAME_HOP) * FRAME_HOP
 
-    def with_split(self, row):
-        """The job `row` as it stands, or with this source's split row beside it."""
+    def job(self, ctx, src_offset, unit_begin, dst_offset):
         sel = getattr(self, 'sel', None)
-        return row if sel is None else SplitJob((row, (self.stride, sel)))
+        return Job(self.row(ctx, src_offset, unit_begin, dst_offset), self.win, None if sel is None else (self.stride, sel))
 
     def reselect(self, sel):
         """This source with another selection of its channels (the file is not read again)."""
-        import copy
         other = copy.copy(self)
         other.sel = [int(ch) for ch in sel]
         return other
@@ -86,8 +82,59 @@ class Source:
         return None
 
     def place(self, ctx):
-        return self.launch(ctx, self.payload, [self.job(ctx, 0, 0, 0)], self.tables([self]),
-                           (self.parts - 1) * self.stride + self.size)
+        """The launch for this file alone (its payload handed on where it lies): the resident signal becomes its samples ->
+        the status, or None."""
+        return Group(ctx, type(self), [(self, 0)], in_place=True).launch((self.parts - 1) * self.stride + self.size).status
+
+
+class Group:
+    """ONE launch for sources of one class, `placed` = [(source, dst_offset)], in the two steps a pass takes it.  Made while
+    the pass is packed: the payloads staged end to end, each on a 16-byte boundary -- in `into(nbytes)`, a page-locked buffer
+    of the caller's, else a zeroed array; in_place: one source, not copied --, the jobs with running byte and unit offsets, the
+    class's tables.  `launch`ed once
+    the signal is there (n_signal >= 0: the launch creates it); `check` after the context's next synchronising read-back."""
+    __slots__ = ('ctx', 'cls', 'placed', 'staged', 'jobs', 'tables', 'status')
+
+    def __init__(self, ctx, cls, placed, into=None, in_place=False):
+        self.ctx, self.cls, self.placed, self.jobs, self.status = ctx, cls, placed, [], None
+        if in_place:                                 # one source alone: nothing to lay out, its payload as it stands
+            (only, _), = placed
+            self.staged = only.payload
+        else:
+            nbytes = sum(-(-s.payload.size // 16) * 16 for s, _ in placed)
+            self.staged = np.zeros(nbytes, dtype=np.uint8) if into is None else into(nbytes)[:nbytes]
+        bpos = ubeg = 0
+        for s, dst in placed:
+            p = s.payload
+            if not in_place:
+                self.staged[bpos:bpos + p.size] = p
+            self.jobs.append(s.job(ctx, bpos, ubeg, dst))
+            bpos += -(-p.size // 16) * 16
+            ubeg += s.units
+        self.tables = cls.tables([s for s, _ in placed])
+
+    def launch(self, n_signal=-1):
+        kw = {}                                      # (a plain launch: the call every launch made before there were any)
+        if any(j.window is not None for j in self.jobs):
+            kw['windows'] = [j.window for j in self.jobs]
+        if any(j.split is not None for j in self.jobs):
+            kw['splits'] = [j.split for j in self.jobs]
+        self.status = self.cls.launch(self.ctx, self.staged, [j.row for j in self.jobs], self.tables, n_signal, **kw)
+        return self
+
+    def check(self, on_error=None):
+        """Every source checks its slice of the status.  A ValueError goes to on_error(index in `placed`, exception) and the
+        others are still checked; without on_error the first is raised."""
+        ubeg = 0
+        for k, (s, _) in enumerate(self.placed):
+            if self.status is not None:
+                try:
+                    s.check(self.status[ubeg:ubeg + s.units])
+                except ValueError as exc:
+                    if on_error is None:
+                        raise
+                    on_error(k, exc)
+            ubeg += s.units
 
 
 class RawSource(Source):
@@ -111,43 +158,27 @@ class RawSource(Source):
     def payload(self):
         return self.x.reshape(-1).view(np.uint8)
 
-    def job(self, ctx, src_offset, unit_begin, dst_offset):
-        return self.with_split(ctx.resample_job(self.x, self.sr, src_offset, dst_offset, self.fmt))
+    def row(self, ctx, src_offset, unit_begin, dst_offset):
+        """Its RS_JOB row: `size` is ceil(frames * up / down) for a whole file, the window's count for an excerpt."""
+        fid, _, _ = ctx.resample_filter(self.sr)
+        x = self.x
+        return (src_offset, x.shape[0], 1 if x.ndim == 1 else x.shape[1], self.fmt, fid, 0, dst_offset, self.size)
 
     @staticmethod
-    def launch(ctx, staged, jobs, tables, n_signal=-1):
-        rows, kw = rows_splits(jobs)
+    def launch(ctx, staged, rows, tables, n_signal=-1, **kw):
         ctx.resample(staged, rows, n_signal, **kw)
 
 
-class RawExcerpt(Source):
+class RawExcerpt(RawSource):
     """Outputs [a, b) of a file at another rate or channel count, for the windowed resample kernel: `x` = the stored frames
     j_lo .. j_hi that carry a tap of those outputs (resample.input_span) and nothing else of the file, `sub` the parsed slice
     they came from (its host decode is what `host()` resamples), `win` the iss_window row."""
-    __slots__ = ('sub', 'x', 'sr', 'fmt', 'size', 'win')
-    pass_order = 0
+    __slots__ = ('sub', 'win')
 
     def __init__(self, sub, x, fmt, a, b, j_lo, frames_total):
-        self.sub, self.x, self.sr, self.fmt = sub, np.ascontiguousarray(x), sub.sr, int(fmt)
+        self.sub, self.x, self.sr, self.fmt, self.sel = sub, np.ascontiguousarray(x), sub.sr, int(fmt), None
         self.size = b - a
         self.win = (j_lo, j_lo + self.x.shape[0], frames_total, a, b - a)
-
-    @property
-    def held(self):
-        return max(self.size, self.x.nbytes // 2)
-
-    @property
-    def payload(self):
-        return self.x.reshape(-1).view(np.uint8)
-
-    def job(self, ctx, src_offset, unit_begin, dst_offset):
-        fid, _, _ = ctx.resample_filter(self.sr)
-        x = self.x
-        return (src_offset, x.shape[0], 1 if x.ndim == 1 else x.shape[1], self.fmt, fid, 0, dst_offset, self.size), self.win
-
-    @staticmethod
-    def launch(ctx, staged, jobs, tables, n_signal=-1):
-        ctx.resample(staged, [j for j, _ in jobs], n_signal, windows=[w for _, w in jobs])
 
     def host(self):
         """The same samples by resample.resample_ref on the host decode of the slice."""

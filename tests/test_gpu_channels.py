@@ -139,7 +139,7 @@ def test_planner_refusals(seg, tmp_path):
     path = sndgen.write(tmp_path / 'm.wav', 'wav', 'ima', False, wavgen.make_signal(3000, 1, 28), 16000, block_align=256)[0]
     s = sndfmt.AdpcmSource(sndfmt.parse(open(path, 'rb').read(), path), 'pcm')
     with pytest.raises(_native.NativeError, match=r'job 0: a channel selection needs a TO_STAGE job with a filter'):
-        ctx.adpcm_decode(s.payload, [s.job(ctx, 0, 0, 0)], s.units, n_signal=s.size, splits=[(_hop(s.size), [0])])
+        ctx.adpcm_decode(s.payload, [s.job(ctx, 0, 0, 0).row], s.units, n_signal=s.size, splits=[(_hop(s.size), [0])])
     assert (ctx.resample_stats(), ctx.adpcm_stats()) == before                  # nothing launched
 
 

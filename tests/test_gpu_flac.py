@@ -93,7 +93,7 @@ def _pack(fctx, streams, kinds, pad_before=0):
     for s, kind in zip(streams, kinds):
         fs = flac.FlacSource(s, kind)
         offs.append(dpos)
-        jobs.append(fs.job(fctx, pos, fbeg, dpos))
+        jobs.append(fs.job(fctx, pos, fbeg, dpos).row)
         frames.append(s.frames)
         src.append(s.audio)
         pad = -s.audio.size % 16

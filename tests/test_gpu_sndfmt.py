@@ -146,7 +146,7 @@ def _pack(ctx, sounds, kinds, pad_before=0):
             jobs.append((pos, bbeg, s.nblocks, s.n, s.ch, s.block_align, _native.ADPCM_TO_STAGE, -1, 0, 0))
         else:
             a = sndfmt.AdpcmSource(s, kind)
-            jobs.append(a.job(ctx, pos, bbeg, dpos))
+            jobs.append(a.job(ctx, pos, bbeg, dpos).row)
             dpos += a.size
         pad = -s.data.size % 16
         src += [s.data, np.zeros(pad, np.uint8)]

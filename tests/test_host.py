@@ -972,18 +972,26 @@ class _RecordingDevice(_FakeDevice):
 
     resample_job, resample_signal = _native.Context.resample_job, _native.Context.resample_signal
 
-    def resample(self, src, jobs, n_signal=-1):
-        self.calls.append(['resample', self._sha(src), [[int(v) for v in j] for j in jobs], int(n_signal)])
+    def _call(self, call, n_signal, windows, splits):
+        """Write a launch down: `windows` / `splits` only where given (the calls made before there were any stay as recorded)."""
+        if windows is not None:
+            call.append(['windows', [[int(v) for v in w] for w in windows]])
+        if splits is not None:
+            call.append(['splits', [None if sp is None else [int(sp[0]), [int(ch) for ch in sp[1]]] for sp in splits]])
+        self.calls.append(call)
         self._new_signal(n_signal)
 
-    def flac_decode(self, src, frames, jobs, n_signal=-1):
-        self.calls.append(['flac_decode', self._sha(src), self._sha(frames), [[int(v) for v in j] for j in jobs], int(n_signal), len(frames)])
-        self._new_signal(n_signal)
+    def resample(self, src, jobs, n_signal=-1, windows=None, splits=None):
+        self._call(['resample', self._sha(src), [[int(v) for v in j] for j in jobs], int(n_signal)], n_signal, windows, splits)
+
+    def flac_decode(self, src, frames, jobs, n_signal=-1, windows=None, splits=None):
+        self._call(['flac_decode', self._sha(src), self._sha(frames), [[int(v) for v in j] for j in jobs], int(n_signal), len(frames)],
+                   n_signal, windows, splits)
         return self._status(len(frames))
 
-    def adpcm_decode(self, src, jobs, nblocks, n_signal=-1):
-        self.calls.append(['adpcm_decode', self._sha(src), [[int(v) for v in j] for j in jobs], int(n_signal), int(nblocks)])
-        self._new_signal(n_signal)
+    def adpcm_decode(self, src, jobs, nblocks, n_signal=-1, windows=None, splits=None):
+        self._call(['adpcm_decode', self._sha(src), [[int(v) for v in j] for j in jobs], int(n_signal), int(nblocks)],
+                   n_signal, windows, splits)
         return self._status(nblocks)
 
     def get_signal_pcm16(self, offset, n):
@@ -994,6 +1002,26 @@ class _RecordingDevice(_FakeDevice):
         self.calls.append(['flac_get_stage', int(job), int(frames_total), int(channels), int(bps)])
         out = np.zeros((int(frames_total), int(channels)), np.int32 if bps > 16 else np.int16)
         return out[:, 0] if channels == 1 else out
+
+
+def _recording_segmenter(resample, bad_last):
+    """-> (a Segmenter(ffmpeg=None, resample=resample) around a _RecordingDevice, that device); the networks answer from one
+    value of each window."""
+    def predict(nclass):
+        def run(batch):
+            x = np.asarray(batch)
+            out = np.full((len(x), nclass), 0.001, np.float32)
+            out[np.arange(len(x)), (np.nan_to_num(x[:, 30, 5, 0]) > 0).astype(int)] = 0.998
+            return out
+        return run
+
+    fake = _RecordingDevice({0: predict(3), 1: predict(2)}, {0: 21, 1: 24}, bad_last)
+    seg = object.__new__(S.Segmenter)
+    seg.energy_ratio, seg.detect_gender, seg.ctx, seg.ffmpeg, seg.resample = 0.03, True, fake, None, resample
+    seg.vad, seg.gender = object.__new__(S.SpeechMusicNoise), object.__new__(S.Gender)
+    seg.vad.ctx = seg.gender.ctx = fake
+    seg.vad.compiled = seg.gender.compiled = None
+    return seg, fake
 
 
 def _pass_device_calls(tmp):
@@ -1036,22 +1064,9 @@ def _pass_device_calls(tmp):
                     ('16 kHz stereo ' + name, (made(p('st16k.' + name), sig(4001, 2, 13), 16000), None, None))]
     clean = lambda text: None if text is None else str(text).replace(tmp + os.sep, '')
 
-    def predict(nclass):
-        def run(batch):
-            x = np.asarray(batch)
-            out = np.full((len(x), nclass), 0.001, np.float32)
-            out[np.arange(len(x)), (np.nan_to_num(x[:, 30, 5, 0]) > 0).astype(int)] = 0.998
-            return out
-        return run
-
     record = {}
     for resample, bad_last in ((True, False), (False, False), (True, True)):
-        fake = _RecordingDevice({0: predict(3), 1: predict(2)}, {0: 21, 1: 24}, bad_last)
-        seg = object.__new__(S.Segmenter)
-        seg.energy_ratio, seg.detect_gender, seg.ctx, seg.ffmpeg, seg.resample = 0.03, True, fake, None, resample
-        seg.vad, seg.gender = object.__new__(S.SpeechMusicNoise), object.__new__(S.Gender)
-        seg.vad.ctx = seg.gender.ctx = fake
-        seg.vad.compiled = seg.gender.compiled = None
+        seg, fake = _recording_segmenter(resample, bad_last)
         rec = record['resample=%s%s' % (resample, ', last unit bad' if bad_last else '')] = {'sources': {}, 'batches': [], 'pass errors': [], 'results': {}}
         for path in files:                                         # what each file becomes, what it holds, or how it fails
             name = os.path.basename(path)
@@ -1073,7 +1088,7 @@ def _pass_device_calls(tmp):
             fake.calls.append(['pass', [os.path.basename(n) for n in batch.names]])
             rec['batches'].append([os.path.basename(n) for n in batch.names])
             out = run(self, batch)
-            rec['pass errors'] += [[int(k), clean(v)] for k, v in sorted(batch.errs.items())]
+            rec['pass errors'] += [[int(k), clean('error: %s %s' % (type(v), v))] for k, v in sorted(batch.errs.items())]
             return out
 
         def on_result(i, src, lseg, err, secs=0.0):
@@ -1118,11 +1133,103 @@ def test_pass_device_calls_are_pinned(tmp_path):
     pass are then the malformed ones) -- equal to tests/golden/pass_device_calls.json, recorded before the sources got one interface.
     One decode thread and one worker: completion order is input order.  batch_files is 6, not 4, so that one pass holds two FLAC
     and two IMA ADPCM files: their job rows then carry running unit offsets."""
-    with open(os.path.join(GOLDEN, 'pass_device_calls.json')) as f:
+    _assert_record(_pass_device_calls(tmp_path), 'pass_device_calls.json')
+
+
+def _assert_record(record, golden):
+    with open(os.path.join(GOLDEN, golden)) as f:
         want = json.load(f)
-    got = json.loads(json.dumps(_pass_device_calls(tmp_path)))
+    got = json.loads(json.dumps(record))
     assert sorted(got) == sorted(want)
     for key in want:
         assert sorted(got[key]) == sorted(want[key]), key
         diff = {k: (got[key][k], want[key][k]) for k in want[key] if got[key][k] != want[key][k]}
         assert not diff, (key, diff)
+
+
+def _pass_device_calls_modes(tmp):
+    """The record tests/golden/pass_device_calls_modes.json holds: the channels of a file (load_pcm_channels, segment_channels,
+    process_files(channels='split')) and time ranges of a file (load_pcm_excerpts, segment_excerpts) on a _RecordingDevice.
+    Per call: every device call (a 'pass' entry where a pipeline pass starts), the error it raised, the lengths of its result."""
+    import flacgen
+    import sndgen
+    import wavgen
+    from inaspeechsegmenter_amd import pipeline
+    tmp = str(tmp)
+    sig = lambda n, ch, seed: wavgen.make_signal(n, ch, seed, peak=0.5)
+    pcm = lambda n, ch, seed, bps=16: np.round(sig(n, ch, seed) * 2 ** (bps - 1)).astype(np.int64)
+    p = lambda name: os.path.join(tmp, name)
+    by_channel = [
+        wavgen.write_wav(p('three48k.wav'), wavgen.encode(sig(60007, 3, 21), 'i16'), 48000, 'i16'),
+        sndgen.write(p('ima8k_stereo.wav'), 'wav', 'ima', False, sig(17001, 2, 22), 8000)[0],
+        flacgen.write(p('stereo44k.flac'), pcm(50003, 2, 23), 44100, 16),
+        wavgen.write_wav(p('mono16k.wav'), wavgen.encode(sig(32077, 1, 24), 'i16'), 16000, 'i16'),
+        wavgen.write_wav(p('short_stereo48k.wav'), wavgen.encode(sig(24001, 2, 25), 'i16'), 48000, 'i16'),   # under 68 frames
+    ]
+    by_range = [
+        wavgen.write_wav(p('stereo48k.wav'), wavgen.encode(sig(96005, 2, 26), 'i16'), 48000, 'i16'),
+        flacgen.write(p('f16.flac'), pcm(33001, 1, 27), 16000, 16),
+        sndgen.write(p('ima8k.wav'), 'wav', 'ima', False, sig(17001, 1, 28), 8000)[0],
+        flacgen.write(p('f24.flac'), pcm(33011, 1, 29, 24), 16000, 24),          # io.excerpts leaves it to the whole-file read
+        wavgen.write_wav(p('pcm16.wav'), wavgen.encode(sig(32077, 1, 30), 'i16'), 16000, 'i16'),             # arrays
+    ]
+    ranges = [(0.25, 1.45), (0.8, 1.1), (1.2, None)]              # the second: 4800 samples, under 68 frames
+    clean = lambda text: None if text is None else str(text).replace(tmp + os.sep, '')
+    lengths = lambda out: [lengths(o) if isinstance(o, list) else len(o) for o in out]
+
+    record = {}
+    for bad_last in (False, True):
+        seg, fake = _recording_segmenter(True, bad_last)
+        rec = record['resample=True%s' % (', last unit bad' if bad_last else '')] = {}
+        run = pipeline._Worker.run
+
+        def recording_run(self, batch):
+            fake.calls.append(['pass', [os.path.basename(n) for n in batch.names]])
+            return run(self, batch)
+
+        def recorded(key, fn, *args, **kw):
+            entry = rec[key] = {'error': None, 'result': None}
+            try:
+                with warnings.catch_warnings():
+                    warnings.simplefilter('ignore')
+                    entry['result'] = lengths(fn(*args, **kw))
+            except BaseException as exc:                           # noqa: B902
+                entry['error'] = [type(exc).__name__, clean(exc)]
+            entry['calls'], fake.calls = fake.calls, []
+
+        pipeline._Worker.run = recording_run
+        try:
+            for path in by_channel:
+                name = os.path.basename(path)
+                recorded('load_pcm_channels ' + name, seg.load_pcm_channels, path)
+                recorded('segment_channels ' + name, seg.segment_channels, path, batch_files=2)
+            for path in by_range:
+                name = os.path.basename(path)
+                recorded('load_pcm_excerpts ' + name, seg.load_pcm_excerpts, path, ranges, batch_files=2)
+                recorded('segment_excerpts ' + name, seg.segment_excerpts, path, ranges, batch_files=2)
+            results = {}
+
+            def on_result(i, src, lseg, err, secs=0.0):
+                results[os.path.basename(src)] = lengths(lseg) if lseg is not None else clean(err)
+
+            def split_files():
+                pipeline.process_files(seg, by_channel, on_result, workers=1, decode_threads=1, batch_files=4, channels='split')
+                return []
+
+            recorded("process_files channels='split'", split_files)
+            rec["process_files channels='split'"]['result'] = results
+        finally:
+            pipeline._Worker.run = run
+        seg.close()
+    return record
+
+
+def test_pass_device_calls_of_channels_and_excerpts_are_pinned(tmp_path):
+    """test_pass_device_calls_are_pinned for the routes that read the channels of a file and time ranges of a file: the ordered
+    device calls -- split rows and window rows beside the job rows, signal sizes, offsets of every read-back -- of
+    load_pcm_channels, segment_channels (batch_files=2: the three channels of a file take two passes), load_pcm_excerpts and
+    segment_excerpts (three ranges, one under 68 frames; a 24-bit FLAC that is decoded whole and sliced), and of process_files
+    with channels='split', over PCM, IMA ADPCM and FLAC files, a mono file and one under 68 frames; with the errors each call
+    raises when the last status entry of every decode call is set -- equal to tests/golden/pass_device_calls_modes.json,
+    recorded before these routes shared one pass routine with process_files."""
+    _assert_record(_pass_device_calls_modes(tmp_path), 'pass_device_calls_modes.json')
