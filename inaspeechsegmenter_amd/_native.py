@@ -123,6 +123,9 @@ def lib():
         'iss_resample_pcm16_split': (C.c_int, [vp, vp, i64, vp, i32, i64, vp, vp, i64]),
         'iss_flac_decode_split': (C.c_int, [vp, vp, i64, vp, i64, vp, i32, i64, pi32, vp, vp, i64]),
         'iss_adpcm_decode_split': (C.c_int, [vp, vp, i64, vp, i32, i64, i64, pi32, vp, vp, i64]),
+        'iss_resample_pcm16_windows_split': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, vp, vp, i64]),
+        'iss_flac_decode_windows_split': (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i32, i64, pi32, vp, vp, i64]),
+        'iss_adpcm_decode_windows_split': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64]),
         'iss_resample_split_geometry': (C.c_int, [vp, i32, i32, pi32, pi32]),
         'iss_get_signal_pcm16': (C.c_int, [vp, pi16, i64, i64]),
         'iss_resample_stats': (C.c_int, [vp, pi64, pi64]),
@@ -406,7 +409,8 @@ class Context:
         windows: rows of WINDOW, one beside every job (iss_resample_pcm16_windows): src holds frames [s_begin, s_end) of each
         file, and the outputs [out_begin, out_begin + out_count) are written.
         splits: `(dst_stride, [channels])` or None per job (iss_resample_pcm16_split): the selected channels of a job are written
-        apart, channel k of the selection at dst_offset + k * dst_stride; None downmixes as ever.  Not with windows."""
+        apart, channel k of the selection at dst_offset + k * dst_stride; None downmixes as ever.  With windows
+        (iss_resample_pcm16_windows_split): the window's outputs of each selected channel, dst_stride >= out_count."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=RS_JOB))
         self._decode_call('iss_resample_pcm16', (C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data)),
@@ -414,18 +418,16 @@ class Context:
         self._keep_rs = src         # the async H2D copy reads it until the next sync
 
     def _decode_call(self, base, lead, trail, windows, splits):
-        """One of the three entry points of `base`: base(ctx, *lead, *trail), or base_windows with the WINDOW rows between
+        """One of the four entry points of `base`: base(ctx, *lead, *trail), or base_windows with the WINDOW rows between
         `lead` (which ends with the job rows) and `trail` (which begins with their count), or base_split with the SPLIT rows,
-        the channel table and its length behind `trail`."""
+        the channel table and its length behind `trail`, or base_windows_split with both."""
         name, args = base, lead + trail
-        if splits is not None:
-            if windows is not None:
-                raise ValueError('windows and splits are not combined')
-            sp, sel = _split_rows(splits, trail[0])
-            name, args = base + '_split', args + (C.c_void_p(sp.ctypes.data), C.c_void_p(sel.ctypes.data), sel.size)
-        elif windows is not None:
+        if windows is not None:
             wn = _window_rows(windows, trail[0])
             name, args = base + '_windows', lead + (C.c_void_p(wn.ctypes.data),) + trail
+        if splits is not None:
+            sp, sel = _split_rows(splits, trail[0])
+            name, args = name + '_split', args + (C.c_void_p(sp.ctypes.data), C.c_void_p(sel.ctypes.data), sel.size)
         self._ck(getattr(self._L, name)(self._h, *args), name)
 
     def resample_signal(self, x, sr, fmt=None):

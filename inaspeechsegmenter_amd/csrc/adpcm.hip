@@ -136,7 +136,7 @@ extern "C" int iss_adpcm_decode_host(const uint8_t* buf, int64_t len, int64_t nb
     return ISS_OK;
 }
 
-// the three entry points: windows beside the jobs, splits (with their selection table) beside the jobs, or neither
+// the four entry points: windows beside the jobs, splits (with their selection table) beside the jobs, both, or neither
 static int adpcm_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, const iss_window* windows,
                         int32_t njobs, int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_split* splits,
                         const int32_t* channel_sel, int64_t nsel) {
@@ -226,6 +226,13 @@ extern "C" int iss_adpcm_decode_split(iss_ctx* c, const void* src, int64_t src_b
                                       int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_split* splits,
                                       const int32_t* channel_sel, int64_t nsel) {
     return adpcm_decode(c, src, src_bytes, jobs, nullptr, njobs, nblocks_total, n_signal, status_out, splits, channel_sel, nsel);
+}
+
+extern "C" int iss_adpcm_decode_windows_split(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs,
+                                              const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
+                                              int32_t* status_out, const iss_split* splits, const int32_t* channel_sel,
+                                              int64_t nsel) {
+    return adpcm_decode(c, src, src_bytes, jobs, windows, njobs, nblocks_total, n_signal, status_out, splits, channel_sel, nsel);
 }
 
 extern "C" int iss_adpcm_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {

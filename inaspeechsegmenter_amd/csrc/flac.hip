@@ -527,7 +527,7 @@ extern "C" int iss_flac_decode_host(const uint8_t* buf, int64_t len, const iss_f
     return ISS_OK;
 }
 
-// the three entry points: windows beside the jobs, splits (with their selection table) beside the jobs, or neither
+// the four entry points: windows beside the jobs, splits (with their selection table) beside the jobs, both, or neither
 static int flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
                        const iss_flac_job* jobs, const iss_window* windows, int32_t njobs, int64_t n_signal, int32_t* status_out,
                        const iss_split* splits, const int32_t* channel_sel, int64_t nsel) {
@@ -616,6 +616,13 @@ extern "C" int iss_flac_decode_split(iss_ctx* c, const void* src, int64_t src_by
                                      const iss_flac_job* jobs, int32_t njobs, int64_t n_signal, int32_t* status_out,
                                      const iss_split* splits, const int32_t* channel_sel, int64_t nsel) {
     return flac_decode(c, src, src_bytes, frames, nframes, jobs, nullptr, njobs, n_signal, status_out, splits, channel_sel, nsel);
+}
+
+extern "C" int iss_flac_decode_windows_split(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames,
+                                             int64_t nframes, const iss_flac_job* jobs, const iss_window* windows, int32_t njobs,
+                                             int64_t n_signal, int32_t* status_out, const iss_split* splits,
+                                             const int32_t* channel_sel, int64_t nsel) {
+    return flac_decode(c, src, src_bytes, frames, nframes, jobs, windows, njobs, n_signal, status_out, splits, channel_sel, nsel);
 }
 
 extern "C" int iss_flac_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {

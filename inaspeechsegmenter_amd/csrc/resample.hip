@@ -26,6 +26,11 @@
 // span[k][.] for the channels of its group in one pass over the interleaved frames ((frame, channel) flattened over the threads:
 // contiguous reads when the selection is the channels in order) and runs step 3 once per channel, on m[j] = the channel's own
 // sample.  A job without a selection (sel_count 0) is the downmix above, in the same launch.
+//
+// Windows with splits (include/iss.h, "Windows and splits together"): WIN = SPLIT = true is the fourth pair, for calls that carry
+// both rows beside every job.  The workgroup takes (channel group, tile) from its block index as a split does, lays the tile
+// over [out_begin, out_end) as a window does, and stages its group's channels by the window's rule: the file's own frame
+// indices, read at in_begin less, 0 outside [0, frames_total).  Table: job rows, window rows, split rows, channel selections.
 #include "decode_pass.h"
 #include <algorithm>
 #include <cstring>
@@ -117,18 +122,25 @@ __device__ __forceinline__ void stage_span(const uint8_t* __restrict__ src, int6
 
 // frames s0 .. s0+len-1 of `gc` selected channels, each on its own: span[k * stride + .] = channel sel[k] (sel == NULL: channel
 // c0 + k).  Thread e takes (frame e / gc, channel e % gc): neighbouring lanes read neighbouring samples of a frame
-template <typename L>
+// (WIN: stage_span's rule -- s0 + k is the file's own frame, 0 outside [0, W.frames_total), read at W.in_begin less)
+template <typename L, bool WIN>
 __device__ __forceinline__ void stage_channels(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
                                                double* __restrict__ span, int stride, int c0, int gc,
-                                               const int32_t* __restrict__ sel) {
+                                               const int32_t* __restrict__ sel, const RsWinDev& W) {
     using T = typename L::type;
     const T* p = reinterpret_cast<const T*>(src);
     const int total = len * gc;
     for (int e = threadIdx.x; e < total; e += RS_THREADS) {
         const int k = e / gc, kk = e - k * gc;
-        const int64_t j = s0 + k;
+        int64_t j = s0 + k;
         double v = 0.0;
-        if (j >= 0 && j < n_in) v = L::get(p + j * ch + (sel ? sel[kk] : c0 + kk));
+        bool in = j >= 0 && j < n_in;
+        if constexpr (WIN) {
+            in = j >= 0 && j < W.frames_total;
+            j -= W.in_begin;
+            in = in && j >= 0 && j < n_in;                 // (the planner saw to it that a window reaches no unstaged frame)
+        }
+        if (in) v = L::get(p + j * ch + (sel ? sel[kk] : c0 + kk));
         span[(int64_t)kk * stride + k] = v;
     }
 }
@@ -140,7 +152,7 @@ template <typename L, bool WIN, bool SPLIT>
 __device__ __forceinline__ void stage(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
                                       double* __restrict__ span, const RsWinDev& W, const RsGroup& G) {
     if constexpr (SPLIT) {
-        if (G.gc > 0) { stage_channels<L>(src, n_in, ch, s0, len, span, G.stride, G.c0, G.gc, G.sel); return; }
+        if (G.gc > 0) { stage_channels<L, WIN>(src, n_in, ch, s0, len, span, G.stride, G.c0, G.gc, G.sel, W); return; }
     }
     stage_span<L, WIN>(src, n_in, ch, s0, len, span, W);
 }
@@ -184,8 +196,9 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __r
     int64_t t = b - J.tile_base;                                            // SPLIT: (channel group, tile), else the tile
     RsGroup G{};
     if constexpr (SPLIT) {
-        static_assert(!WIN, "windows and splits are not combined");
-        const RsSplitDev* splits = reinterpret_cast<const RsSplitDev*>(jobs + njobs);     // the split table follows the job table,
+        const void* after = jobs + njobs;                                            // the split table follows the job table
+        if constexpr (WIN) after = reinterpret_cast<const RsWinDev*>(after) + njobs;      // (WIN: ... follows the window table),
+        const RsSplitDev* splits = reinterpret_cast<const RsSplitDev*>(after);
         const int32_t* sels = reinterpret_cast<const int32_t*>(splits + njobs);          // the channel selections follow that
         const RsSplitDev S = splits[lo];
         if (S.sel_count > 0) {
@@ -302,8 +315,8 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
     plan.dw.assign(wins ? (size_t)njobs : 0, RsWinDev{});
     plan.ds.assign(splits ? (size_t)njobs : 0, RsSplitDev{});
     plan.sel.clear();
-    if (splits && (wins || nsel < 0 || nsel > 0x7fffffffLL || (nsel > 0 && !sel)))
-        return iss_fail(c, ISS_EINVAL, "%s: splits with windows, or a bad channel selection table", who);
+    if (splits && (nsel < 0 || nsel > 0x7fffffffLL || (nsel > 0 && !sel)))
+        return iss_fail(c, ISS_EINVAL, "%s: a bad channel selection table", who);
     if (splits) plan.sel.assign(sel, sel + nsel);
     int64_t tiles = 0, lds = 0;
     for (int32_t k = 0; k < njobs; ++k) {
@@ -415,12 +428,13 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     if (dj.empty()) return ISS_OK;
     const bool win = !plan.dw.empty(), split = !plan.ds.empty();
     int rc;
-    if (split) {                                       // one table: the jobs, their splits, the channel selections
-        const size_t nj = dj.size() * sizeof(RsJobDev), ns = dj.size() * sizeof(RsSplitDev);
-        std::vector<uint8_t> rows(nj + ns + std::max<size_t>(plan.sel.size(), 1) * sizeof(int32_t));
+    if (split) {                                       // one table: the jobs, (their windows,) their splits, the channel selections
+        const size_t nj = dj.size() * sizeof(RsJobDev), nw = win ? dj.size() * sizeof(RsWinDev) : 0, ns = dj.size() * sizeof(RsSplitDev);
+        std::vector<uint8_t> rows(nj + nw + ns + std::max<size_t>(plan.sel.size(), 1) * sizeof(int32_t));
         memcpy(rows.data(), dj.data(), nj);
-        memcpy(rows.data() + nj, plan.ds.data(), ns);
-        if (!plan.sel.empty()) memcpy(rows.data() + nj + ns, plan.sel.data(), plan.sel.size() * sizeof(int32_t));
+        if (win) memcpy(rows.data() + nj, plan.dw.data(), nw);
+        memcpy(rows.data() + nj + nw, plan.ds.data(), ns);
+        if (!plan.sel.empty()) memcpy(rows.data() + nj + nw + ns, plan.sel.data(), plan.sel.size() * sizeof(int32_t));
         rc = iss_upload_rows(c, c->rs_jobs, rows.data(), rows.size());
     } else if (win) {                                         // one table: the jobs, then their windows
         std::vector<uint8_t> rows(dj.size() * (sizeof(RsJobDev) + sizeof(RsWinDev)));
@@ -433,7 +447,8 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     if (rc) return rc;
     bool ext = false;                                  // a format newer than the WAV five: the instantiation that reads them all
     for (const RsJobDev& d : dj) ext = ext || d.fmt > ISS_RS_F64;
-    auto kernel = split ? (ext ? resample_kernel<true, false, true> : resample_kernel<false, false, true>)
+    auto kernel = split && win ? (ext ? resample_kernel<true, true, true> : resample_kernel<false, true, true>)
+                  : split ? (ext ? resample_kernel<true, false, true> : resample_kernel<false, false, true>)
                   : win ? (ext ? resample_kernel<true, true, false> : resample_kernel<false, true, false>)
                         : (ext ? resample_kernel<true, false, false> : resample_kernel<false, false, false>);
     if (plan.lds > 64 * 1024)
@@ -452,11 +467,12 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     return ISS_OK;
 }
 
-// the one body of the three entry points: `windows`, `splits` or neither beside the jobs (a null pointer is "neither")
+// the one body of the four entry points: `windows`, `splits`, both or neither beside the jobs (a null pointer is "neither")
 static int resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
                           int64_t n_signal, const iss_window* windows, const iss_split* splits, const int32_t* channel_sel,
                           int64_t nsel) {
-    const char* who = splits ? "iss_resample_pcm16_split" : windows ? "iss_resample_pcm16_windows" : "iss_resample_pcm16";
+    const char* who = splits && windows ? "iss_resample_pcm16_windows_split" : splits ? "iss_resample_pcm16_split"
+                      : windows ? "iss_resample_pcm16_windows" : "iss_resample_pcm16";
     if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0))
         return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
     IssDecodePass pass;
@@ -478,6 +494,12 @@ extern "C" int iss_resample_pcm16_windows(iss_ctx* c, const void* src, int64_t s
 extern "C" int iss_resample_pcm16_split(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
                                         int64_t n_signal, const iss_split* splits, const int32_t* channel_sel, int64_t nsel) {
     return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, nullptr, splits, channel_sel, nsel);
+}
+
+extern "C" int iss_resample_pcm16_windows_split(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
+                                                const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_split* splits,
+                                                const int32_t* channel_sel, int64_t nsel) {
+    return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, windows, splits, channel_sel, nsel);
 }
 
 // (tile, channels per group) the planner gives a job of `nsel` selected channels through filter `filter`

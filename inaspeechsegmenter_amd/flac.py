@@ -14,7 +14,7 @@ import numpy as np
 from . import _native
 from . import resample as R
 from .io import need_16k_mono, source_of
-from .sources import CodedSource, RawSource
+from .sources import CodedSource, RawSource, host_window
 
 MAGIC = b'fLaC'
 # benchmark switch (tools/bench_flac.py), not a user option: True makes the ffmpeg-free read decode FLAC on the host
@@ -160,13 +160,15 @@ class FlacSource(CodedSource):
 class FlacExcerpt(FlacSource):
     """Outputs [a, b) of a FLAC file for the windowed decode: the frames that cover the stored-rate samples the excerpt needs
     ('pcm': [a, b) themselves; 'resample': resample.input_span of them) and their bytes only.  Its `frames` keep the file's sample
-    numbering; a malformed frame is named by its byte offset in the file.  Frames outside the run are not decoded, so not checked."""
+    numbering; a malformed frame is named by its byte offset in the file.  Frames outside the run are not decoded, so not checked.
+    `sel` ('resample' only): the channels to write apart (None: their average)."""
     __slots__ = ('k0', 'rows', 'win', '_payload')
     payload = property(lambda self: self._payload)
     frames = property(lambda self: self.rows)
 
-    def __init__(self, stream, kind, a, b):
+    def __init__(self, stream, kind, a, b, sel=None):
         self.s, self.kind, self.size = stream, kind, b - a
+        self.sel = None if sel is None else [int(ch) for ch in sel]
         if kind == 'pcm':
             s0, s1 = a, b
         else:
@@ -194,7 +196,7 @@ class FlacExcerpt(FlacSource):
         x, st = _native.flac_decode_host(self._payload, rows, s.ch, s.bps, int(rows['first_sample'][-1] + rows['block_size'][-1]))
         self.check(st)
         x = x[s0 - first:s1 - first]
-        return np.ascontiguousarray(x) if self.kind == 'pcm' else R.resample_ref(x, s.sr, a, count, s0, total)
+        return np.ascontiguousarray(x) if self.kind == 'pcm' else host_window(x, s.sr, self.win, self.sel)
 
 
 def source(stream, resample=False):

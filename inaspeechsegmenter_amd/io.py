@@ -17,6 +17,8 @@ PCM16 as int16 so the device does the x/32768 scaling (2 B/sample over PCIe, not
 channel): a source with a channel selection for the device; `decode_channels` is its host-only twin.
 `excerpts` reads time ranges of one file without ffmpeg (an extension: start/stop through decode_pcm keep raising): per range the
 samples of the 16 kHz mono twin or a windowed source holding only the bytes it needs; `decode_excerpts` finishes them on the host.
+`channel_excerpts` is both at once: time ranges of single channels, windowed sources with a channel selection;
+`decode_channel_excerpts` is its host-only twin.
 """
 import os
 import struct
@@ -376,3 +378,60 @@ def decode_excerpts(medianame, ranges, resample=False):
             s = whole[a:b]
         out.append(s.host() if isinstance(s, Source) else s)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- excerpts of single channels
+def channel_excerpts(medianame, ranges, channels=None, resample=False):
+    """-> (sel, [source | None per range]): the time ranges of `excerpts`, of the channels `split_source` selects.  For a file
+    of two or more channels every range is a windowed source carrying the selection (sources.RawExcerpt, flac.FlacExcerpt,
+    sndfmt.AdpcmExcerpt: one signal per selected channel, the samples [a, b) of that channel's 16 kHz twin, a and b from
+    excerpt_bounds on the twin's length), holding only the bytes, frames or blocks the range needs.  A one-channel file gives
+    what `excerpts` gives (sel is then all zeros).  Ranges are validated as `excerpts` validates them, the selection by
+    channel_selection; without `resample` a rate other than 16 kHz is refused, the channel count is not.  A plain RIFF/WAVE
+    file is read by byte ranges; every other container, and FLAC, is read whole once."""
+    from . import flac, sndfmt
+    from .sources import RawExcerpt
+    ranges = [tuple(r) for r in ranges]
+    for start, stop in ranges:
+        _check_range(medianame, start, stop)
+    _check_local(medianame)
+    h = sndfmt.read_header(medianame)
+    if h is None:
+        buf = _read_range(medianame, 0, os.path.getsize(medianame))
+        h = _classify(buf, medianame)
+        if h is None:                                             # a WAV only the whole-file read can judge (or refuse)
+            x, sr = _parse_wav(buf, medianame)
+            kind = {'uint8': 'u8', 'int16': 'i16', 'int32': 'i32', 'float32': 'f32', 'float64': 'f64'}[x.dtype.name]
+            x = np.ascontiguousarray(x)                           # (24-bit: widened, as the whole-file read stages it)
+            h = sndfmt.Sound(medianame, sr, 1 if x.ndim == 1 else x.shape[1], kind, False, x.reshape(-1).view(np.uint8), 0)
+    sel = channel_selection(medianame, channels, h.ch)
+    if h.ch == 1:
+        return sel, excerpts(medianame, ranges, resample)
+    if not resample:
+        need_16k(medianame, h.sr)
+    R.check_rate(h.sr)
+    n16 = R.out_len(h.n, h.sr)
+    out = []
+    for start, stop in ranges:
+        a, b = excerpt_bounds(medianame, n16, start, stop)
+        if isinstance(h, flac.FlacStream):
+            out.append(flac.FlacExcerpt(h, 'resample', a, b, sel))
+        elif h.kind == 'ima':
+            out.append(sndfmt.AdpcmExcerpt(h, 'resample', a, b, sel))
+        else:
+            j_lo, j_hi = R.input_span(h.sr, h.n, a, b - a)
+            sub, _ = sndfmt.sub_sound(h, j_lo, j_hi + 1)
+            out.append(RawExcerpt(sub, *sub.raw(), a, b, j_lo, h.n, sel))
+    return sel, out
+
+
+def decode_channel_excerpts(medianame, ranges, channels=None, resample=True):
+    """Host-only twin of Segmenter.load_pcm_channel_excerpts: out[r][k] = the samples [a, b) of decode_channels(medianame,
+    [sel[k]])[0] for range r, by the host builds of the decoders on the frames, blocks and bytes of each excerpt alone and a
+    windowed resample.resample_ref per selected channel; [decode_excerpts(...)[r]] * len(sel) for a one-channel file."""
+    from .sources import Source
+    ranges = [tuple(r) for r in ranges]
+    sel, sigs = channel_excerpts(medianame, ranges, channels, resample)
+    if not all(isinstance(s, Source) and s.sel is not None for s in sigs):          # a one-channel file
+        return [[one] * len(sel) for one in decode_excerpts(medianame, ranges, resample)]
+    return [s.host() for s in sigs]

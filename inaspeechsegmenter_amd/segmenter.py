@@ -610,6 +610,97 @@ class Segmenter:
             out[k] = [(lab, start + a * .02, start + b * .02) for lab, a, b in lseg]
         return out
 
+    # ---- time ranges of single channels without ffmpeg: the two extensions above in one launch per kernel
+    def _channel_excerpt_sigs(self, medianame, ranges, channels):
+        """io.channel_excerpts for this Segmenter -> (ranges as a list, the selection, per range a windowed source carrying it;
+        None instead of the sources for a one-channel file, which the excerpt calls read)."""
+        if self.ffmpeg is not None:
+            raise ValueError(f'excerpts of channels are read without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={self.ffmpeg!r} '
+                             f'downmixes every file with -ac 1')
+        ranges = [tuple(r) for r in ranges]
+        sel, sigs = iss_io.channel_excerpts(medianame, ranges, channels, self.resample)
+        if not all(isinstance(s, Source) and s.sel is not None for s in sigs):
+            sigs = None
+        return ranges, sel, sigs
+
+    @staticmethod
+    def _pair_passes(sigs, todo, sel, batch_files, batch_seconds):
+        """The (range, channel) pairs of the ranges `todo`, range by range, cut into passes as signals of their length would be
+        -> per pass [(range, [k of sel])]: each range of a pass is one source again, with that pass's channels selected."""
+        from . import pipeline
+        pairs = [(r, k) for r in todo for k in range(len(sel))]
+        out = []
+        for idx in pipeline.cut_passes([sigs[r].reselect([sel[k]]) for r, k in pairs], batch_files, batch_seconds):
+            per = []
+            for r, k in (pairs[i] for i in idx):
+                if per and per[-1][0] == r:
+                    per[-1][1].append(k)
+                else:
+                    per.append((r, [k]))
+            out.append(per)
+        return out
+
+    def load_pcm_channel_excerpts(self, medianame, ranges, channels=None, batch_files=None, batch_seconds=None):
+        """load_pcm_channels for time ranges [(start_sec, stop_sec | None)] of one file -> out[r][k] = the int16 samples [a, b)
+        of load_pcm_channels(medianame, [sel[k]])[0], (a, b) = io.excerpt_bounds(medianame, n16, *ranges[r]) on the length n16
+        of a channel's 16 kHz twin, sel = channels as load_pcm_channels takes them (None: all, ascending; repeats and any order
+        allowed).  Only the bytes, IMA blocks and FLAC frames the ranges need are staged, and all (range, channel) pairs that
+        fit a pass (batch_files / batch_seconds as for batch_process) take ONE launch per decode kernel and ONE resample launch.
+        A one-channel file gives [load_pcm_excerpts(...)[r]] * len(sel) per range (the float path included).  Range errors as
+        segment_excerpts, channel errors as load_pcm_channels; with ffmpeg set, ValueError naming the argument.  Frames and
+        blocks that are not decoded are not checked."""
+        from .sources import Group
+        ranges, sel, sigs = self._channel_excerpt_sigs(medianame, ranges, channels)
+        if sigs is None:
+            return [[one] * len(sel) for one in self.load_pcm_excerpts(medianame, ranges, batch_files, batch_seconds)]
+        out = [[None] * len(sel) for _ in ranges]
+        for per in self._pair_passes(sigs, range(len(ranges)), sel, batch_files, batch_seconds):
+            placed, pos = [], 0                                  # end to end: the launch creates a signal of just these samples
+            for r, ks in per:
+                placed.append((sigs[r].reselect([sel[k] for k in ks]), pos))
+                pos += len(ks) * placed[-1][0].stride
+            group = Group(self.ctx, type(placed[0][0]), placed).launch(pos)      # (one file: one class)
+            for (r, ks), (s, o) in zip(per, placed):
+                for q, k in enumerate(ks):
+                    out[r][k] = self.ctx.get_signal_pcm16(o + q * s.stride, s.size)
+            group.check()
+        return out
+
+    def segment_channel_excerpts(self, medianame, ranges, channels=None, batch_files=None, batch_seconds=None):
+        """Segment time ranges of single channels of one file without ffmpeg -> out[r][k] = exactly what
+        segment_signal(load_pcm_channel_excerpts(...)[r][k], start_sec=ranges[r][0]) gives, for every range r and every selected
+        channel k (arguments as load_pcm_channel_excerpts; times are offset by start_sec as given).  Ranges and channels are cut
+        and split on the device: all (range, channel) pairs of a pass (at most batch_files pairs / batch_seconds of audio, the
+        defaults of batch_process) share one launch per decode kernel, one resample launch and one feature pass.  Ranges
+        shorter than 68 frames go alone as segment_signal would take them (padding and warning included).  A one-channel file
+        gives [segment_excerpts(...)[r]] * len(sel) per range.  Errors as load_pcm_channel_excerpts; a malformed FLAC frame or IMA
+        block among those decoded fails the call (ValueError naming its byte offset in the file)."""
+        from . import pipeline
+        ranges, sel, sigs = self._channel_excerpt_sigs(medianame, ranges, channels)
+        if sigs is None:
+            return [[one] * len(sel) for one in self.segment_excerpts(medianame, ranges, batch_files, batch_seconds)]
+        out = [[None] * len(sel) for _ in ranges]
+        todo = []
+        for r, s in enumerate(sigs):
+            if s.size < pipeline.MIN_SAMPLES:
+                for k, one in enumerate(_parts_pcm(self.ctx, s)):
+                    mspec, loge, difflen = _sig2feats(self.ctx, one, medianame)
+                    out[r][k] = self.segment_feats(mspec, loge, difflen, ranges[r][0])
+            else:
+                todo.append(r)
+        per_pass = self._pair_passes(sigs, todo, sel, batch_files, batch_seconds)
+        srcs, passes = [], []
+        for per in per_pass:
+            passes.append(list(range(len(srcs), len(srcs) + len(per))))
+            srcs += [sigs[r].reselect([sel[k] for k in ks]) for r, ks in per]
+        lsegs = iter(pipeline.run_passes(self, [medianame] * len(srcs), srcs, passes))
+        for per in per_pass:
+            for r, ks in per:
+                start = ranges[r][0]
+                for k in ks:
+                    out[r][k] = [(lab, start + a * .02, start + b * .02) for lab, a, b in next(lsegs)]
+        return out
+
     def __call__(self, medianame, start_sec=None, stop_sec=None):
         """segmenter.py:279-294."""
         mspec, loge, difflen = _media2feats(medianame, start_sec, stop_sec, self.ffmpeg, self.ctx, self.resample)

@@ -25,7 +25,7 @@ from . import _native
 from . import flac
 from . import resample as R
 from .io import _to_float, need_16k_mono
-from .sources import CodedSource, RawSource
+from .sources import CodedSource, RawSource, host_window
 
 # benchmark switch (tools/bench_sndfmt.py), not a user option: True makes the ffmpeg-free read expand G.711 and IMA ADPCM on
 # the host (numpy table / iss_adpcm_decode_host in the decode threads) instead of handing the stored bytes to the device
@@ -544,11 +544,13 @@ class AdpcmSource(CodedSource):
 class AdpcmExcerpt(AdpcmSource):
     """Outputs [a, b) of an IMA ADPCM file for the windowed decode: `s` = the sub_sound of the blocks that hold the
     stored-rate samples the excerpt needs ('pcm': [a, b); 'resample': resample.input_span of them), `first` the file's sample
-    number of its first sample.  A bad block is named by its byte offset in the file (s.base is one)."""
+    number of its first sample.  A bad block is named by its byte offset in the file (s.base is one).  `sel` ('resample' only):
+    the channels to write apart (None: their average)."""
     __slots__ = ('first', 'win')
 
-    def __init__(self, h, kind, a, b):
+    def __init__(self, h, kind, a, b, sel=None):
         self.kind, self.size = kind, b - a
+        self.sel = None if sel is None else [int(ch) for ch in sel]
         s0, s1 = (a, b) if kind == 'pcm' else (lambda lo, hi: (lo, hi + 1))(*R.input_span(h.sr, h.n, a, b - a))
         self.s, self.first = sub_sound(h, s0, s1)
         self.win = (s0, s1, h.n, a, b - a)
@@ -558,7 +560,7 @@ class AdpcmExcerpt(AdpcmSource):
         """The same samples by the host build of the decoder, on the same blocks (and resample.resample_ref)."""
         s0, s1, total, a, count = self.win
         x = self.s.stored()[s0 - self.first:s1 - self.first]
-        return np.ascontiguousarray(x) if self.kind == 'pcm' else R.resample_ref(x, self.s.sr, a, count, s0, total)
+        return np.ascontiguousarray(x) if self.kind == 'pcm' else host_window(x, self.s.sr, self.win, self.sel)
 
 
 def decode_on(ctx, src):

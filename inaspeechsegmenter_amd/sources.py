@@ -13,7 +13,7 @@ bytes as stored, which a kernel turns into 16 kHz mono PCM16 inside the resident
     check(status)           ValueError for a malformed file, from its slice of the status array
     tables(group), launch(ctx, staged, rows, tables, n_signal, **kw)   (of the class) what ONE launch for a group of sources of
                             this class needs besides bytes and rows, and the launch -> the status array (valid after the
-                            context's next synchronising call) or None; kw: `windows=` or `splits=`, only where some job has one
+                            context's next synchronising call) or None; kw: `windows=`, `splits=` or both, only where some job has one
     parts                   how many consecutive signals it writes (default 1): `parts` signals of `size` samples each, signal k at
                             dst_offset + k * `stride`, stride = `size` rounded up to FRAME_HOP
 
@@ -24,6 +24,12 @@ channel instead of their average: `parts` = len(sel), and its job carries the sp
 An excerpt of a file (io.excerpts) is a source too, of a class of its own below its format's: its `size` is the excerpt's, its
 `payload` only the bytes the excerpt needs, and its job carries the window row (iss_window) for the windowed entry point.  A
 windowed launch needs a window beside every job, so whole files and excerpts never share one: launches go by class.
+
+An excerpt made with a channel selection (io.channel_excerpts: RawExcerpt, flac.FlacExcerpt, sndfmt.AdpcmExcerpt) is both: its
+job carries the window row AND the split row, for the *_windows_split entry point, which writes the window's outputs of each
+selected channel apart -- `parts`, `stride`, `held` and `reselect` as on a whole file with a selection, `size` the excerpt's.
+Excerpts with and without a selection share a launch (the downmixed ones with no split beside them), and `host()` of one with
+a selection gives one array per selected channel.
 
 `Group` is the only place that stages payloads, numbers job rows, launches and hands the status back; `pass_order` places a
 class's launch among the device calls of a pass.  pipeline._Worker.run, Segmenter.load_pcm_excerpts and Source.place (one file
@@ -175,15 +181,24 @@ class RawExcerpt(RawSource):
     they came from (its host decode is what `host()` resamples), `win` the iss_window row."""
     __slots__ = ('sub', 'win')
 
-    def __init__(self, sub, x, fmt, a, b, j_lo, frames_total):
-        self.sub, self.x, self.sr, self.fmt, self.sel = sub, np.ascontiguousarray(x), sub.sr, int(fmt), None
+    def __init__(self, sub, x, fmt, a, b, j_lo, frames_total, sel=None):
+        self.sub, self.x, self.sr, self.fmt = sub, np.ascontiguousarray(x), sub.sr, int(fmt)
+        self.sel = None if sel is None else [int(ch) for ch in sel]
         self.size = b - a
         self.win = (j_lo, j_lo + self.x.shape[0], frames_total, a, b - a)
 
     def host(self):
-        """The same samples by resample.resample_ref on the host decode of the slice."""
-        j_lo, _, total, a, count = self.win
-        return resample.resample_ref(self.sub.stored(), self.sr, a, count, j_lo, total)
+        """The same samples by resample.resample_ref on the host decode of the slice (one array per selected channel)."""
+        return host_window(self.sub.stored(), self.sr, self.win, self.sel)
+
+
+def host_window(x, sr, win, sel=None):
+    """What an excerpt's `host()` gives for x = the stored frames [s_begin, s_end) of its window row `win`: their downmix's
+    outputs, or with a selection one array per selected channel, each resample.resample_ref on that channel's column."""
+    s0, _, total, a, count = win
+    if sel is None:
+        return resample.resample_ref(x, sr, a, count, s0, total)
+    return [resample.resample_ref(x[:, ch], sr, a, count, s0, total) for ch in sel]
 
 
 class CodedSource(Source):

@@ -312,7 +312,6 @@ int iss_adpcm_decode_windows(iss_ctx* ctx, const void* src, int64_t src_bytes, c
  * rows outside [0, nsel), a selected channel outside [0, channels), dst_stride < frames_out, one of the sel_count destination
  * ranges outside the signal, any two destination ranges of the call overlapping (those of other jobs and of TO_SIGNAL jobs
  * included), a decoder job with a selection that is not TO_STAGE with a filter.
- * Windows and splits are not combined: the split entry points take no iss_window, and the *_windows entry points no split.
  * iss_resample_stats counts a split job as ONE job whatever its sel_count; launches, status, staging, the signal rule and all
  * other errors are as for the plain entry point.                                                                              */
 typedef struct {
@@ -329,6 +328,33 @@ int iss_adpcm_decode_split(iss_ctx* ctx, const void* src, int64_t src_bytes, con
                            int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_split* splits,
                            const int32_t* channel_sel, int64_t nsel);
 int iss_resample_split_geometry(iss_ctx* ctx, int32_t filter, int32_t nsel, int32_t* tile_out, int32_t* group_out);
+
+/* Windows and splits together: a time range of single channels.  The *_windows_split entry points take a window row AND a split
+ * row beside every job row (windows[k] and splits[k] belong to jobs[k]) and the channel_sel table of the call; each of the two
+ * contracts above holds as written, with frames_out = out_count.
+ *   resample rows   sel_count > 0: `src` holds frames [s_begin, s_end) of the file, all channels interleaved; output q is the
+ *                   outputs i in [out_begin, out_begin + out_count) of channel sel[q] alone, computed exactly as the split
+ *                   call computes them on the whole file (resample_ref(x[s_begin:s_end, c], rate, out_begin, out_count,
+ *                   s_begin, frames_total), to the bit), written to dst_offset + q * dst_stride + i - out_begin.  dst_stride >=
+ *                   out_count.  Frames outside [0, frames_total) are zero, the reach must lie inside [s_begin, s_end), and
+ *                   samples between the end of an output and the next stride are not written.
+ *                   sel_count == 0: the windowed downmix of iss_resample_pcm16_windows, in the same launch.
+ *   decoder rows    only a TO_STAGE job with a filter may carry sel_count > 0: the decode kernel stages the interleaved samples
+ *                   [s_begin, s_end) of the window as a windowed call does, and the resample row reads them with the same
+ *                   window and the split row.  FLAC frame rows and IMA ADPCM blocks are those of the windowed call.
+ * The grid of the resample launch is ragged over (job, channel group, tile) with the tiles laid over the window; groups and
+ * tile are those iss_resample_split_geometry reports.  Device table: job rows, window rows, split rows, channel selections.
+ * ISS_EINVAL: everything either contract refuses, with the same text.  iss_resample_stats counts a windowed split job as ONE
+ * job.  A call with windows only or splits only takes the entry point it always took.                                         */
+int iss_resample_pcm16_windows_split(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
+                                     const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_split* splits,
+                                     const int32_t* channel_sel, int64_t nsel);
+int iss_flac_decode_windows_split(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
+                                  const iss_flac_job* jobs, const iss_window* windows, int32_t njobs, int64_t n_signal,
+                                  int32_t* status_out, const iss_split* splits, const int32_t* channel_sel, int64_t nsel);
+int iss_adpcm_decode_windows_split(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs,
+                                   const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
+                                   int32_t* status_out, const iss_split* splits, const int32_t* channel_sel, int64_t nsel);
 
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */

@@ -10,6 +10,12 @@ Both must give the same segments.  Also recorded: the bytes the excerpt route as
 file's size, and, from one profiled call of each route, the bytes staged (the *_h2d brackets) and the decode / resample kernel
 times of the library's profiler.
 Writes one JSON (default profiles/excerpts.json) and prints it.
+
+--channels is the channel leg: the same ranges of both channels of a two-channel recording, as 48 kHz PCM16 WAV, 16 kHz left/side
+FLAC and 8 kHz IMA ADPCM (the second channel is the first one, delayed).  Timed the same way:
+  excerpts    seg.segment_channel_excerpts(file, ranges): the ranges cut and the channels split on the device
+  whole       the route there was before: seg.load_pcm_channels(file) once, host slices, seg.segment_signal per slice
+Default output: profiles/channel_excerpts.json; each leg's spread ((max - min) / min of its runs) is recorded beside its times.
 """
 import argparse
 import json
@@ -33,6 +39,7 @@ def main(argv=None):
     ap.add_argument('--excerpts', type=int, default=24)
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--channels', action='store_true', help='the channel leg: two-channel files, segment_channel_excerpts')
     args = ap.parse_args(argv)
 
     import bench
@@ -55,6 +62,18 @@ def main(argv=None):
     nrep = int(args.hours * 3600 * 8000 / (spb * (30 * 8000 // spb)))
     files['ima_8k_mono'] = sndgen.write_riff(os.path.join(tmp, 'r_ima.wav'), sndgen.wav_fmt('ima', 8000, 1, 256), bytes(blocks) * nrep,
                                              fact=spb * (30 * 8000 // spb) * nrep)
+    if args.channels:
+        files = {}
+        pcm2 = np.stack([pcm, np.roll(pcm, 16000 * 7)], axis=1)         # the second channel: the first, seven seconds later
+        files['wav_48k_stereo'] = wavgen.write_wav(os.path.join(tmp, 'c.wav'), np.tile(np.repeat(pcm2, 3, axis=0), (minutes, 1)), 48000, 'i16')
+        files['flac_16k_left_side'] = flacgen.write(os.path.join(tmp, 'c.flac'), np.tile(pcm2, (minutes, 1)).astype(np.int64), 16000, 16,
+                                                    channel_mode='left_side', subframe={'type': 'fixed', 'order': 2})
+        spb = sndgen.ima_samples_per_block(512, 2)
+        per = spb * (30 * 8000 // spb)
+        blocks = sndgen.ima_encode(pcm2[::2][:per], 512)
+        nrep = int(args.hours * 3600 * 8000 / per)
+        files['ima_8k_stereo'] = sndgen.write_riff(os.path.join(tmp, 'c_ima.wav'), sndgen.wav_fmt('ima', 8000, 2, 512), bytes(blocks) * nrep,
+                                                   fact=per * nrep)
     gen_s = time.time() - t0
     step = args.hours * 3600.0 / args.excerpts
     ranges = [(round(k * step + 7.3, 3), round(k * step + 67.3, 3)) for k in range(args.excerpts)]
@@ -68,6 +87,17 @@ def main(argv=None):
     def whole(path):
         twin = seg.load_pcm(path)
         return [seg.segment_signal(twin[slice(*iss_io.excerpt_bounds(path, twin.size, a, b))], start_sec=a) for a, b in ranges]
+
+    if args.channels:
+        def excerpts(path):                                             # noqa: F811
+            return seg.segment_channel_excerpts(path, ranges)
+
+        def whole(path):                                                # noqa: F811
+            out = [[] for _ in ranges]
+            for twin in seg.load_pcm_channels(path):
+                for r, (a, b) in enumerate(ranges):
+                    out[r].append(seg.segment_signal(twin[slice(*iss_io.excerpt_bounds(path, twin.size, a, b))], start_sec=a))
+            return out
 
     def profiled(fn, path):
         ctx.prof_enable(True)
@@ -92,7 +122,7 @@ def main(argv=None):
         asked.append(size)
         return real(path, offset, size)
 
-    result = {'hours': args.hours, 'excerpts': args.excerpts, 'excerpt_seconds': 60.0, 'reps': args.reps,
+    result = {'leg': 'channels' if args.channels else 'mono', 'hours': args.hours, 'excerpts': args.excerpts, 'excerpt_seconds': 60.0, 'reps': args.reps,
               'generate_s': round(gen_s, 2), 'files': {}}
     ok = True
     for name, path in files.items():
@@ -112,14 +142,15 @@ def main(argv=None):
         finally:
             iss_io._read_range = real
         te, tw = min(legs['excerpts']), min(legs['whole'])
-        audio_h = args.excerpts * 60.0 / 3600.0
+        audio_h = args.excerpts * 60.0 / 3600.0 * (2 if args.channels else 1)
         result['files'][name] = {
             'file_bytes': os.path.getsize(path), 'bytes_read_excerpts': int(sum(asked)), 'segments_identical': same,
             'excerpts_s_runs': legs['excerpts'], 'whole_s_runs': legs['whole'],
+            'excerpts_spread': max(legs['excerpts']) / te - 1.0, 'whole_spread': max(legs['whole']) / tw - 1.0,
             'excerpts_audio_h_per_s': audio_h / te, 'whole_audio_h_per_s': audio_h / tw, 'speedup': tw / te,
             'excerpts_profile': profiled(excerpts, path), 'whole_profile': profiled(whole, path),
         }
-    path = args.out or os.path.join(ROOT, 'profiles', 'excerpts.json')
+    path = args.out or os.path.join(ROOT, 'profiles', 'channel_excerpts.json' if args.channels else 'excerpts.json')
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, 'w') as f:
         json.dump(result, f, indent=1)
