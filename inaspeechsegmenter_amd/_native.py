@@ -168,6 +168,8 @@ def lib():
         'iss_vbx_set_dither': (C.c_int, [vp, pd, i64]),
         'iss_vbx_features_pcm16': (C.c_int, [vp, pi16, i64, pf, pi32]),
         'iss_vbx_features_batch_pcm16': (C.c_int, [vp, pi16, pi64, i32, pi32, pf]),
+        'iss_vbx_features_resident': (C.c_int, [vp, pi64, pi64, i32, pi32, pf]),
+        'iss_vbx_resident_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_vbx_embed': (C.c_int, [vp, C.c_int, pi32, i32, pf]),
         'iss_prof_enable': (C.c_int, [vp, C.c_int]),
         'iss_prof_get': (C.c_int, [vp, C.c_int, pd, pi64, pd]),
@@ -785,6 +787,25 @@ class Context:
                                                       _ptr(foff, C.c_int32), _ptr(out, C.c_float) if to_host else None),
                  'iss_vbx_features_batch_pcm16')
         return foff, out
+
+    def vbx_features_resident(self, begins, counts, to_host=False):
+        """The batch front end on parts of the resident PCM16 signal (iss_vbx_features_resident): part p = its samples
+        [begins[p], begins[p] + counts[p]); nothing is uploaded but the two tables.  -> (frame_off, fea) as
+        vbx_features_batch_pcm16 returns them, fea None unless to_host."""
+        b = np.ascontiguousarray(begins, dtype=np.int64).reshape(-1)
+        n = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+        if b.size != n.size:
+            raise ValueError(f'vbx_features_resident: {b.size} begins, {n.size} counts')
+        foff = np.zeros(b.size + 1, dtype=np.int32)
+        T = int(sum((int(k) + 320 - 400) // 160 + 1 for k in n if k >= 200))
+        out = np.empty((T, 64), dtype=np.float32) if to_host else None
+        self._ck(self._L.iss_vbx_features_resident(self._h, _ptr(b, C.c_int64), _ptr(n, C.c_int64), b.size, _ptr(foff, C.c_int32),
+                                                   _ptr(out, C.c_float) if to_host else None), 'iss_vbx_features_resident')
+        return foff, (out[:foff[-1]] if to_host else None)
+
+    def vbx_resident_stats(self):
+        """(vbx_features_resident calls that launched -- one fbank launch each --, parts they took) since the context was created."""
+        return self._counters('iss_vbx_resident_stats')
 
     def vbx_embed(self, net_id, starts):
         st = np.ascontiguousarray(starts, dtype=np.int32)

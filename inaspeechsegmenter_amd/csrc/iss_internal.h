@@ -133,9 +133,10 @@ struct iss_ctx {
     double* d_vbx_melw = nullptr;
     int32_t* d_vbx_mellim = nullptr;
     DevBuf vbx_sig, vbx_dither, vbx_fb, vbx_out;
-    DevBuf vbx_meta;                       // batch front end: per-file sample offsets (int64) then frame offsets (int32)
+    DevBuf vbx_meta;                       // batch front end: per-file sample offsets (int64; resident parts: begins, then lengths) then frame offsets (int32)
     int32_t vbx_T = 0;
     int64_t vbx_dither_n = 0;              // length of the dither stream cached in vbx_dither (0 = none)
+    IssCounters vbx_res_count;             // iss_vbx_features_resident: calls (one fbank launch each), parts
 
     // pinned staging buffers of the asynchronous entry points (window lists): reused once their copy has completed
     struct Staging { void* p = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool busy = false; };

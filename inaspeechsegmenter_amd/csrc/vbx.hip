@@ -17,8 +17,11 @@
 // and their batch forms (iss_vbx_features_batch_pcm16): one fbank grid over the frames of many files, one cumsum
 // wavefront per file, one ragged CMN launch -- three launches per batch, each file's frames bit-identical to its own run.
 // The batch kernels are separate copies: the single-file kernels' code stays exactly as it is.
+// iss_vbx_features_resident runs the batch kernels on parts of the resident PCM16 signal (what a decode pass left there): the
+// fbank kernel's second instantiation takes a length per part, the cumsum and CMN kernels are the same.
 #include "iss_internal.h"
 #include "fft256.h"
+#include <algorithm>
 
 namespace {
 
@@ -162,7 +165,12 @@ __device__ __forceinline__ int file_of(const int32_t* __restrict__ foff, int nfi
 // vbx_fbank_kernel over all frames of many files (T = their total).  Each file is framed, reflect-padded and dithered on its
 // own -- the sample and dither index is the file's LOCAL one, every file restarts the stream -- so every file's rows are
 // bit-identical to a vbx_fbank_kernel<int16_t> run on that file alone.  Only `fetch` differs from that kernel.
+// kLen = false: files back to back, file f = pcm[soff[f] .. soff[f + 1]) (slen unused).  kLen = true (iss_vbx_features_resident):
+// part f = pcm[soff[f] .. soff[f] + slen[f]), parts in any order with gaps between them; soff then holds nfiles entries.
+// seg_at folds every index into [0, n), so nothing outside a part is read.
+template <bool kLen>
 __global__ __launch_bounds__(256) void vbx_fbank_batch_kernel(const int16_t* __restrict__ pcm, const int64_t* __restrict__ soff,
+                                                              const int64_t* __restrict__ slen,
                                                               const int32_t* __restrict__ foff, int nfiles,
                                                               const double* __restrict__ u, int T, const double* __restrict__ window,
                                                         const double* __restrict__ tw, const double* __restrict__ melw,
@@ -200,7 +208,7 @@ __global__ __launch_bounds__(256) void vbx_fbank_batch_kernel(const int16_t* __r
         tt = __builtin_amdgcn_readfirstlane(tt < T ? tt : T - 1);
         const int f = file_of(foff, nfiles, tt);
         const int16_t* sig = pcm + soff[f];
-        const int64_t n = soff[f + 1] - soff[f];
+        const int64_t n = kLen ? slen[f] : soff[f + 1] - soff[f];
         const int64_t s0 = (int64_t)(tt - foff[f]) * 160;
 #pragma unroll
         for (int r = 0; r < 7; ++r) {
@@ -554,8 +562,8 @@ extern "C" int iss_vbx_features_batch_pcm16(iss_ctx* c, const int16_t* pcm, cons
     int blocks = (T + 3) / 4;
     if (blocks > 2048) blocks = 2048;
     iss_prof_begin(c, 1, 0.0);
-    hipLaunchKernelGGL(vbx_fbank_batch_kernel, dim3(blocks), dim3(256), 0, c->stream, (const int16_t*)c->vbx_sig.p, d_soff, d_foff,
-                       nfiles, (const double*)c->vbx_dither.p, T, c->d_vbx_window, c->d_tw, c->d_vbx_melw, c->d_vbx_mellim, fb);
+    hipLaunchKernelGGL(vbx_fbank_batch_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, (const int16_t*)c->vbx_sig.p, d_soff,
+                       (const int64_t*)nullptr, d_foff, nfiles, (const double*)c->vbx_dither.p, T, c->d_vbx_window, c->d_tw, c->d_vbx_melw, c->d_vbx_mellim, fb);
     iss_prof_end(c);
     iss_prof_begin(c, 2, 0.0);
     hipLaunchKernelGGL(vbx_cumsum_batch_kernel, dim3(nfiles), dim3(64), 0, c->stream, fb, d_foff, f);
@@ -568,5 +576,85 @@ extern "C" int iss_vbx_features_batch_pcm16(iss_ctx* c, const int16_t* pcm, cons
     iss_prof_collect(c);
     c->vbx_T = T;
     for (size_t i = 0; i < foff.size(); ++i) frame_off_out[i] = foff[i];
+    return ISS_OK;
+}
+
+// The batch front end on parts of the RESIDENT PCM16 signal (include/iss.h): nothing is uploaded but the part table.
+extern "C" int iss_vbx_features_resident(iss_ctx* c, const int64_t* sample_begin, const int64_t* sample_count, int32_t nparts,
+                                         int32_t* frame_off_out, float* out) {
+    if (!c || !sample_begin || !sample_count || nparts <= 0 || !frame_off_out)
+        return iss_fail(c, ISS_EINVAL, "iss_vbx_features_resident: bad argument");
+    if (!c->vbx_tables) return iss_fail(c, ISS_ESTATE, "iss_vbx_features_resident: call iss_vbx_tables first");
+    if (c->sig_kind != 1) return iss_fail(c, ISS_ESTATE, "iss_vbx_features_resident: no resident PCM16 signal");
+    const int64_t max_total = (1LL << 31) - 8192;            // as iss_vbx_features_batch_pcm16
+    std::vector<int32_t> foff((size_t)nparts + 1);
+    std::vector<int32_t> order((size_t)nparts);
+    int64_t total = 0, longest = 0;
+    for (int p = 0; p < nparts; ++p) {
+        const int64_t b = sample_begin[p], n = sample_count[p];
+        if (n < 200)
+            return iss_fail(c, ISS_EINVAL, "iss_vbx_features_resident: part %d has %lld samples (need >= 200)", p, (long long)n);
+        if (b < 0 || b > c->sig_n || n > c->sig_n - b)
+            return iss_fail(c, ISS_EINVAL, "iss_vbx_features_resident: part %d [%lld, +%lld) is outside the signal of %lld samples", p,
+                            (long long)b, (long long)n, (long long)c->sig_n);
+        const int64_t T64 = (n + 320 - 400) / 160 + 1;
+        if (T64 > (1 << 26)) return iss_fail(c, ISS_EINVAL, "iss_vbx_features_resident: part %d: unsupported length", p);
+        total += T64;
+        if (total > max_total)
+            return iss_fail(c, ISS_EINVAL, "iss_vbx_features_resident: more than %lld frames in one call (part %d)",
+                            (long long)max_total, p);
+        longest = n > longest ? n : longest;
+        foff[p + 1] = (int32_t)total;
+        order[p] = p;
+    }
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return sample_begin[a] < sample_begin[b]; });
+    for (int i = 0; i + 1 < nparts; ++i)
+        if (sample_begin[order[i]] + sample_count[order[i]] > sample_begin[order[i + 1]])
+            return iss_fail(c, ISS_EINVAL, "iss_vbx_features_resident: parts %d and %d overlap", order[i], order[i + 1]);
+    if (c->vbx_dither_n < longest)
+        return iss_fail(c, ISS_ESTATE, "iss_vbx_features_resident: cached dither stream holds %lld values, the longest part needs %lld "
+                        "(iss_vbx_set_dither)", (long long)c->vbx_dither_n, (long long)longest);
+    ISS_HIP(c, hipSetDevice(c->device));
+    const int T = (int)total;
+    const size_t tab = (size_t)nparts * sizeof(int64_t);
+    int rc;
+    if ((rc = iss_reserve(c, c->vbx_meta, 2 * tab + foff.size() * sizeof(int32_t)))) return rc;
+    if ((rc = iss_reserve(c, c->vbx_fb, ((size_t)2 * T + nparts) * 64 * 8))) return rc;     // fbank rows, then the prefix rows
+    if ((rc = iss_reserve(c, c->vbx_out, (size_t)T * 64 * 4))) return rc;
+    int64_t* d_soff = (int64_t*)c->vbx_meta.p;
+    int64_t* d_slen = d_soff + nparts;
+    int32_t* d_foff = (int32_t*)(d_slen + nparts);
+    // (pageable sources: each copy has left the host array when the call returns, and the stream orders it after earlier kernels)
+    ISS_HIP(c, hipMemcpyAsync(d_soff, sample_begin, tab, hipMemcpyHostToDevice, c->stream));
+    ISS_HIP(c, hipMemcpyAsync(d_slen, sample_count, tab, hipMemcpyHostToDevice, c->stream));
+    ISS_HIP(c, hipMemcpyAsync(d_foff, foff.data(), foff.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    double* fb = (double*)c->vbx_fb.p;
+    double* f = fb + (size_t)T * 64;
+    int blocks = (T + 3) / 4;
+    if (blocks > 2048) blocks = 2048;
+    iss_prof_begin(c, 1, 0.0);
+    hipLaunchKernelGGL(vbx_fbank_batch_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, (const int16_t*)c->sig_ptr, d_soff, d_slen,
+                       d_foff, nparts, (const double*)c->vbx_dither.p, T, c->d_vbx_window, c->d_tw, c->d_vbx_melw, c->d_vbx_mellim, fb);
+    iss_prof_end(c);
+    iss_prof_begin(c, 2, 0.0);
+    hipLaunchKernelGGL(vbx_cumsum_batch_kernel, dim3(nparts), dim3(64), 0, c->stream, fb, d_foff, f);
+    hipLaunchKernelGGL(vbx_cmn_batch_kernel, dim3((unsigned)(((long long)T * 64 + 255) / 256)), dim3(256), 0, c->stream, fb, f, d_foff,
+                       nparts, T, 150, 300, (float*)c->vbx_out.p);
+    iss_prof_end(c);
+    ISS_HIP(c, hipGetLastError());
+    if (out) ISS_HIP(c, hipMemcpyAsync(out, c->vbx_out.p, (size_t)T * 64 * 4, hipMemcpyDeviceToHost, c->stream));
+    ISS_HIP(c, hipStreamSynchronize(c->stream));
+    iss_prof_collect(c);
+    c->vbx_T = T;
+    c->vbx_res_count.launches += 1;
+    c->vbx_res_count.units += nparts;
+    for (size_t i = 0; i < foff.size(); ++i) frame_off_out[i] = foff[i];
+    return ISS_OK;
+}
+
+extern "C" int iss_vbx_resident_stats(iss_ctx* c, int64_t* launches, int64_t* parts) {
+    if (!c || !launches || !parts) return iss_fail(c, ISS_EINVAL, "iss_vbx_resident_stats: NULL argument");
+    *launches = c->vbx_res_count.launches;
+    *parts = c->vbx_res_count.units;
     return ISS_OK;
 }

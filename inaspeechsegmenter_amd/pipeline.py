@@ -44,10 +44,13 @@ MIN_SAMPLES = 400 + FRAME_HOP * 67                  # 68 frames: shorter media t
 
 
 class _Batch:
-    __slots__ = ('idx', 'sigs', 'names', 'errs')
+    __slots__ = ('idx', 'sigs', 'names', 'errs', 'poffs', 'psize')
 
     def __init__(self):
         self.idx, self.sigs, self.names, self.errs = [], [], [], {}
+        # set by _Worker.run, per part of the pass: where it starts in the resident signal and how many samples it has -- the signal
+        # stays resident after the pass, so a caller can read the parts there (vfs.py: iss_vbx_features_resident)
+        self.poffs, self.psize = None, None
 
     def samples(self):                               # 16 kHz samples (a RawSource's size is its resampled length), of every part
         return sum(_parts(s) * (-(-s.size // FRAME_HOP) * FRAME_HOP) for s in self.sigs)
@@ -178,6 +181,7 @@ class _Worker:
             for _ in range(_parts(s)):
                 owner.append(f); poffs.append(pos); psize.append(s.size)
                 pos += stride
+        batch.poffs, batch.psize = list(poffs), list(psize)
         buf = self.pinned('signal', pos, np.int16)
         placed, files = {}, {}                       # source class -> [(source, offset in the signal)]; -> [its file]
         for f, (s, o) in enumerate(zip(batch.sigs, offs)):

@@ -25,7 +25,7 @@ import numpy as np
 from . import _native, keras_model
 from .io import decode_pcm, media2sig16kmono, _to_float
 from . import sndfmt
-from .segmenter import Segmenter, locate_model
+from .segmenter import Segmenter, locate_model, _parts_pcm
 from .vbx import FeatureExtractor, VBxExtractor, SR, frame_count, pcm16_of, plan_windows
 
 _MLP_NET = 3          # engine net id of the gender MLP (0/1: VAD / gender CNNs, 4..: ResNet programs)
@@ -226,6 +226,127 @@ class VoiceFemininityScoring:
         g = [(seg[0], seg[1], p) for (_, seg, _), p in zip(x_vectors, pred)]
         return get_femininity_score(g), speech_dur, len(g)
 
+    def score_signal(self, sig, basename='<signal>'):
+        """__call__ behind the decode, for an already decoded 16 kHz mono signal (int16 or float32 array) -> (score,
+        speech_duration, nb_vectors): exactly what __call__ returns for the PCM16 (or float) WAV holding those samples read
+        without ffmpeg.  The definition score_channels / score_excerpts / score_channel_excerpts refer to."""
+        a = np.ascontiguousarray(sig)
+        if a.dtype not in (np.int16, np.float32):
+            raise TypeError(f'signal dtype {a.dtype}: need int16 or float32')
+        signal = _to_float(a, np.float64) if a.dtype == np.int16 else a.astype(np.float64)
+        speech = speech_intervals(self.vad.segment_signal(a))
+        speech_dur = speech_duration(speech)
+        if not speech_dur:
+            return None, speech_dur, 0
+        feats = self.features(signal)
+        return self._score(self.xvector_model(basename, feats, len(signal) / SR), speech, speech_dur)
+
+    # ---- channels and time ranges of one file, scored where the decode pass left them (an extension; ffmpeg=None only)
+    def _alone(self, fpath, sig, basename):
+        """A part that shares no pass (float media, under 68 frames), through score_signal as batch_process sends float media."""
+        if sig.size < 400:
+            raise ValueError(f"media {fpath}: {sig.size} samples, less than one 25 ms analysis window")
+        return self.score_signal(self.vad._mono_pcm(sig), basename)
+
+    def _score_passes(self, fpath, basename, sigs, passes):
+        """The `passes` (pipeline.cut_passes) of the batchable signals `sigs`, one after the other on this scorer's context ->
+        one (score, speech_duration, nb_vectors) per part of every signal of every pass, in that order.  Per pass: the
+        worker's `run` stages, decodes and resamples every part into the resident signal and runs the VAD over all of them;
+        the 64-band front end reads the parts with speech right there (iss_vbx_features_resident: no PCM comes back, none is
+        uploaded again); then _score_batch's steps: windows with the mid-speech filter, one embed_batch, __call__'s tail per
+        part.  The first malformed FLAC frame / IMA block of a pass raises its ValueError (the file and its byte offset)."""
+        from . import pipeline
+        worker = pipeline._workers(self.vad, 1)[0]                # drives self.ctx: the VAD, the tables and the ResNet share it
+        out = []
+        for idx in passes:
+            batch = pipeline._Batch()
+            batch.idx, batch.sigs, batch.names = list(idx), [sigs[k] for k in idx], [fpath] * len(idx)
+            lsegs = worker.run(batch)
+            if batch.errs:
+                raise ValueError(str(batch.errs[min(batch.errs)]))
+            speeches = [speech_intervals([(lab, a * .02, b * .02) for lab, a, b in lseg]) for lseg in lsegs]
+            durs = [speech_duration(s) for s in speeches]
+            res = [(None, d, 0) for d in durs]
+            live = [p for p, d in enumerate(durs) if d]           # a part without speech never reaches the front end
+            if live:
+                counts = [batch.psize[p] for p in live]
+                self.features._ensure_dither(max(counts))
+                self.ctx.vbx_features_resident([batch.poffs[p] for p in live], counts)
+                self.ctx._vbx_resident = None                     # the single-file arena is gone
+                plan = plan_windows([frame_count(n) for n in counts], [n / SR for n in counts], [basename] * len(live),
+                                    keep=lambda f, t: is_mid_speech(t[0], t[1], speeches[live[f]]))
+                for p, x in zip(live, self.xvector_model.embed_batch(plan)):
+                    res[p] = self._score(x, speeches[p], durs[p])
+            out += res
+        return out
+
+    def score_channels(self, fpath, channels=None, batch_files=None, batch_seconds=None):
+        """Score every selected channel of one file on its own -> [(score, speech_duration, nb_vectors) per selected channel],
+        in the order of `channels`.  Entry k is exactly score_signal(self.vad.load_pcm_channels(fpath, [sel[k]])[0]), sel =
+        `channels` as Segmenter.load_pcm_channels takes them (None: all, ascending; any order, repeats allowed).  Arguments,
+        passes and errors as Segmenter.segment_channels (ValueError with ffmpeg set; a one-channel file gives its one result
+        len(sel) times; a malformed FLAC frame or IMA block fails the call, naming its byte offset).  The channels of a
+        pass are split on the device and scored from the resident signal (_score_passes); a file whose channels are under
+        68 frames goes channel by channel through score_signal."""
+        from . import pipeline
+        basename = os.path.splitext(os.path.basename(fpath))[0]
+        sel, sig = self.vad._channel_sig(fpath, channels)
+        if getattr(sig, 'sel', None) is None:                     # a one-channel file
+            return [self._alone(fpath, sig, basename)] * len(sel)
+        if sig.size < pipeline.MIN_SAMPLES:
+            return [self._alone(fpath, one, basename) for one in _parts_pcm(self.ctx, sig)]
+        passes = pipeline.cut_passes([sig.reselect([ch]) for ch in sel], batch_files, batch_seconds)
+        sigs = [sig.reselect([sel[k] for k in idx]) for idx in passes]
+        return self._score_passes(fpath, basename, sigs, [[k] for k in range(len(sigs))])
+
+    def score_excerpts(self, fpath, ranges, batch_files=None, batch_seconds=None):
+        """Score time ranges [(start_sec, stop_sec | None)] of one file -> [(score, speech_duration, nb_vectors) per range], in
+        the order of `ranges` (they may overlap or repeat).  Entry r is exactly
+        score_signal(self.vad.load_pcm_excerpts(fpath, [ranges[r]])[0]): window times count from the start of the range.
+        Arguments, passes and errors as Segmenter.segment_excerpts; ranges under 68 frames and float media go alone through
+        score_signal, the others are cut on the device and scored from the resident signal (_score_passes)."""
+        from . import pipeline
+        basename = os.path.splitext(os.path.basename(fpath))[0]
+        ranges, sigs = self.vad._excerpt_sigs(fpath, ranges)
+        out, todo = [None] * len(sigs), []
+        for k, s in enumerate(sigs):
+            if not pipeline.sources.batchable(s) or s.size < pipeline.MIN_SAMPLES:
+                out[k] = self._alone(fpath, s, basename)
+            else:
+                todo.append(k)
+        rest = [sigs[k] for k in todo]
+        for k, r in zip(todo, self._score_passes(fpath, basename, rest, pipeline.cut_passes(rest, batch_files, batch_seconds))):
+            out[k] = r
+        return out
+
+    def score_channel_excerpts(self, fpath, ranges, channels=None, batch_files=None, batch_seconds=None):
+        """Score time ranges of single channels of one file -> out[r][k] = exactly
+        score_signal(self.vad.load_pcm_channel_excerpts(fpath, [ranges[r]], [sel[k]])[0][0]) for every range r and selected
+        channel k.  Arguments, passes and errors as Segmenter.segment_channel_excerpts (a one-channel file gives
+        [score_excerpts(...)[r]] * len(sel) per range); window times count from the start of the range."""
+        from . import pipeline
+        basename = os.path.splitext(os.path.basename(fpath))[0]
+        ranges, sel, sigs = self.vad._channel_excerpt_sigs(fpath, ranges, channels)
+        if sigs is None:
+            return [[one] * len(sel) for one in self.score_excerpts(fpath, ranges, batch_files, batch_seconds)]
+        out, todo = [[None] * len(sel) for _ in ranges], []
+        for r, s in enumerate(sigs):
+            if s.size < pipeline.MIN_SAMPLES:
+                out[r] = [self._alone(fpath, one, basename) for one in _parts_pcm(self.ctx, s)]
+            else:
+                todo.append(r)
+        per_pass = self.vad._pair_passes(sigs, todo, sel, batch_files, batch_seconds)
+        srcs, passes = [], []
+        for per in per_pass:                                      # each range of a pass one source, that pass's channels selected
+            passes.append(list(range(len(srcs), len(srcs) + len(per))))
+            srcs += [sigs[r].reselect([sel[k] for k in ks]) for r, ks in per]
+        res = iter(self._score_passes(fpath, basename, srcs, passes))
+        for per in per_pass:
+            for r, ks in per:
+                for k in ks:
+                    out[r][k] = next(res)
+        return out
+
     def _decoded_on_device(self, fpath):
         """Is the file decoded on the device when read without ffmpeg (FLAC, or a file of sndfmt.py)?  Then it is decoded
         once (Segmenter.load_pcm), like a resampled WAV."""
@@ -271,7 +392,7 @@ class VoiceFemininityScoring:
         xv = self.xvector_model.embed_batch(plan)
         return {b[0]: self._score(x, b[4], b[5]) for b, x in zip(batch, xv)}
 
-    def batch_process(self, linput, output_csv=None, batch_seconds=3600, nbtry=1, trydelay=2., verbose=False):
+    def batch_process(self, linput, output_csv=None, batch_seconds=3600, nbtry=1, trydelay=2., verbose=False, channels=None):
         """__call__ on many files -> [(score, speech_duration, nb_vectors) or an error message] in `linput` order, the same
         results as __call__ on each file.  Every file is decoded once (to PCM16): the VAD and the x-vector front end read the
         same array.  Files with speech are gathered into batches of at most `batch_seconds` of audio (a longer file makes a
@@ -279,7 +400,15 @@ class VoiceFemininityScoring:
         windows, one per distinct last-window width on the parameters already on the device.  A file that cannot be decoded
         (`nbtry` attempts, `trydelay` s apart) or is too short for the VAD gets an error message and the batch goes on;
         device failures raise.  output_csv: also write a TSV `path score speech_duration nb_vectors` (header line first;
-        a failed file's row carries its message)."""
+        a failed file's row carries its message).
+        channels (an extension, ffmpeg=None only): None is the above; 'split' scores every channel of every file on its own
+        (score_channels, file by file: passes are not shared across files; batch_seconds is its pass limit): results[i] is then
+        a list with one (score, speech_duration, nb_vectors) per channel, or the file's error message, and the TSV reads
+        `path channel score speech_duration nb_vectors`, one row per channel (a failed file: one row, its channel column empty)."""
+        if channels not in (None, 'split'):
+            raise ValueError(f"channels={channels!r}: None or 'split'")
+        if channels is not None:
+            return self._batch_channels(list(linput), output_csv, batch_seconds, nbtry, trydelay, verbose)
         linput = list(linput)
         results = [None] * len(linput)
         batch, held = [], 0.0
@@ -326,4 +455,35 @@ class VoiceFemininityScoring:
                 fh.write('path\tscore\tspeech_duration\tnb_vectors\n')
                 for fpath, r in zip(linput, results):
                     fh.write('\t'.join([fpath] + ([str(v) for v in r] if isinstance(r, tuple) else [r])) + '\n')
+        return results
+
+    def _batch_channels(self, linput, output_csv, batch_seconds, nbtry, trydelay, verbose):
+        """batch_process(channels='split')."""
+        if self.ffmpeg is not None:
+            raise ValueError(f"channels='split' reads files without ffmpeg (VoiceFemininityScoring(ffmpeg=None)); "
+                             f"ffmpeg={self.ffmpeg!r} downmixes every file with -ac 1")
+        results = []
+        for fpath in linput:
+            for itry in range(nbtry):
+                try:
+                    results.append(self.score_channels(fpath, batch_seconds=batch_seconds))
+                    break
+                except _native.NativeError:
+                    raise
+                except Exception as exc:
+                    if itry + 1 == nbtry:
+                        results.append(f'{type(exc).__name__}: {exc}')
+                    else:
+                        time.sleep(trydelay)
+            if verbose:
+                print('%d/%d' % (len(results), len(linput)), fpath, results[-1])
+        if output_csv is not None:
+            with open(output_csv, 'w') as fh:
+                fh.write('path\tchannel\tscore\tspeech_duration\tnb_vectors\n')
+                for fpath, r in zip(linput, results):
+                    if isinstance(r, str):                    # a failed file: one row, no channel
+                        fh.write('\t'.join([fpath, '', r]) + '\n')
+                        continue
+                    for k, one in enumerate(r):
+                        fh.write('\t'.join([fpath, str(k)] + [str(v) for v in one]) + '\n')
         return results

@@ -590,6 +590,23 @@ int iss_vbx_features_pcm16(iss_ctx* ctx, const int16_t* pcm, int64_t n,
  * 2^31 - 8192 frames in all.  Replaces a per-file loop over get_features (vbx_segmenter.py:72-89).                      */
 int iss_vbx_features_batch_pcm16(iss_ctx* ctx, const int16_t* pcm, const int64_t* sample_off, int32_t nfiles,
                                  int32_t* frame_off_out, float* fea_out /* (sum T_f)*64, or NULL: stay resident */);
+/* The same batch front end on parts of the RESIDENT PCM16 signal (iss_signal_pcm16*, or what a decode / resample pass wrote
+ * there): part p = samples [sample_begin[p], sample_begin[p] + sample_count[p]) of the signal.  Nothing is uploaded but the part
+ * table.  The parts need not touch and may come in any order: a pass leaves a gap up to the next multiple of 160 behind every
+ * part, so each part carries its own length; none is derived from the next offset.  Per part: its own framing, reflect padding,
+ * cumsum and CMN; the cached dither stream restarts at u[0].  Leaves the resident (sum T_p, 64) f32 arena iss_vbx_embed reads,
+ * parts in the order given; frame_off_out[p] = first arena row of part p (nparts + 1 entries).  Three launches per call.
+ * Contract:
+ *   - the frames of part p are bit-identical to iss_vbx_features_pcm16 on those samples alone;
+ *   - no sample outside a part is read: not the gap behind it, not a neighbouring part, not what lies past the signal's end;
+ *   - ISS_EINVAL, nothing launched and nothing resident changed: a part under 200 samples or over the per-file limit, a part
+ *     outside the signal, two parts that overlap, more than 2^31 - 8192 frames in all;
+ *   - ISS_ESTATE, likewise: no tables (iss_vbx_tables), a cached dither stream shorter than the longest part, a resident
+ *     signal that is not PCM16 (iss_signal_f32) or none.
+ * iss_vbx_resident_stats: calls that launched (one fbank launch each) and parts they took, since the context was created.  */
+int iss_vbx_features_resident(iss_ctx* ctx, const int64_t* sample_begin, const int64_t* sample_count, int32_t nparts,
+                              int32_t* frame_off_out, float* fea_out /* (sum T_p)*64, or NULL: stay resident */);
+int iss_vbx_resident_stats(iss_ctx* ctx, int64_t* launches, int64_t* parts);
 /* x-vectors of n windows [starts[i], starts[i] + frames) of the RESIDENT features (frames = the loaded network's input
  * width; its first conv must be a window-mode conv, ISS_C_INMODE 2): replaces the window loop of
  * vbx_segmenter.py:222-231 + get_embedding (:262-266) without copying windows through the host.                        */

@@ -2,7 +2,8 @@
 """Command line front end of the MI355X-native voice femininity scoring (VoiceFemininityScoring.batch_process).
 
 Scores every input file and writes one TSV: path, score, speech duration, number of x-vectors (a file that could not be
-read gets its error message instead).  Argument handling as scripts/ina_speech_segmenter_amd.py: -i takes paths or glob
+read gets its error message instead); with --channels split (-b None) one row per channel, the channel in a column of its
+own.  Argument handling as scripts/ina_speech_segmenter_amd.py: -i takes paths or glob
 patterns, -b None reads 16 kHz mono WAV or FLAC directly (with --resample: WAV / FLAC at any rate / channel count, resampled on
 the GPU),
 --models synthetic runs seeded stand-in weights.
@@ -30,6 +31,9 @@ def build_parser():
     ap.add_argument('--resample', action='store_true',
                     help='with -b None: downmix and resample files of other rates / channel counts (8 kHz G.711 telephony, 44.1 kHz AIFF ...) to '
                          '16 kHz mono on the GPU')
+    ap.add_argument('--channels', choices=['mix', 'split'], default='mix',
+                    help="'split' (with -b None): score every channel of every file on its own, split on the GPU; the TSV then has a "
+                         "channel column and one row per channel")
     return ap
 
 
@@ -45,6 +49,8 @@ def main(argv=None):
     ffmpeg = None if args.ffmpeg_binary.lower() in ('none', '') else args.ffmpeg_binary
     if args.resample and ffmpeg is not None:
         build_parser().error('--resample needs -b None (ffmpeg already resamples)')
+    if args.channels == 'split' and ffmpeg is not None:
+        build_parser().error('--channels split needs -b None (ffmpeg downmixes every file)')
     if ffmpeg is None:
         print('Disabling ffmpeg. ' + ('WAV files at other rates or with several channels are resampled on the GPU.' if args.resample
                                       else 'Make sure your audio files are already sampled at 16kHz.'))
@@ -56,8 +62,9 @@ def main(argv=None):
     vfs = VoiceFemininityScoring(gd_model_criteria=args.criteria, ffmpeg=ffmpeg, models=args.models, resample=args.resample)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        res = vfs.batch_process(inputs, output_csv=args.output, batch_seconds=args.batch_seconds, verbose=True)
-    print('%d files, %d scored, %d failed -> %s' % (len(res), sum(isinstance(r, tuple) for r in res),
+        res = vfs.batch_process(inputs, output_csv=args.output, batch_seconds=args.batch_seconds, verbose=True,
+                                **({'channels': 'split'} if args.channels == 'split' else {}))
+    print('%d files, %d scored, %d failed -> %s' % (len(res), sum(not isinstance(r, str) for r in res),
                                                   sum(isinstance(r, str) for r in res), args.output))
     return 0
 
