@@ -30,7 +30,7 @@ RS_I8, RS_ULAW, RS_ALAW, RS_SWAP = 8, 9, 10, 0x100
 ADPCM_JOB = np.dtype([('src_offset', '<i8'), ('block_begin', '<i8'), ('nblocks', '<i8'), ('frames_total', '<i8'), ('channels', '<i4'),
                       ('block_align', '<i4'), ('output', '<i4'), ('filter', '<i4'), ('dst_offset', '<i8'), ('frames_out', '<i8')])
 ADPCM_TO_SIGNAL, ADPCM_TO_STAGE = 0, 1
-ADPCM_STATUS = {1: 'step index above 88'}
+ADPCM_STATUS = {1: 'step index above 88', 2: 'predictor index above 6'}
 # iss_flac_info / iss_flac_frame / iss_flac_job (include/iss.h)
 FLAC_INFO = np.dtype([('sample_rate', '<i4'), ('channels', '<i4'), ('bps', '<i4'), ('min_block', '<i4'), ('max_block', '<i4'),
                       ('reserved', '<i4'), ('total_samples', '<i8')])
@@ -120,12 +120,15 @@ def lib():
         'iss_resample_pcm16_windows': (C.c_int, [vp, vp, i64, vp, vp, i32, i64]),
         'iss_flac_decode_windows': (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i32, i64, pi32]),
         'iss_adpcm_decode_windows': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32]),
+        'iss_msadpcm_decode_windows': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32]),
         'iss_resample_pcm16_split': (C.c_int, [vp, vp, i64, vp, i32, i64, vp, vp, i64]),
         'iss_flac_decode_split': (C.c_int, [vp, vp, i64, vp, i64, vp, i32, i64, pi32, vp, vp, i64]),
         'iss_adpcm_decode_split': (C.c_int, [vp, vp, i64, vp, i32, i64, i64, pi32, vp, vp, i64]),
+        'iss_msadpcm_decode_split': (C.c_int, [vp, vp, i64, vp, i32, i64, i64, pi32, vp, vp, i64]),
         'iss_resample_pcm16_windows_split': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, vp, vp, i64]),
         'iss_flac_decode_windows_split': (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i32, i64, pi32, vp, vp, i64]),
         'iss_adpcm_decode_windows_split': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64]),
+        'iss_msadpcm_decode_windows_split': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64]),
         'iss_resample_split_geometry': (C.c_int, [vp, i32, i32, pi32, pi32]),
         'iss_get_signal_pcm16': (C.c_int, [vp, pi16, i64, i64]),
         'iss_resample_stats': (C.c_int, [vp, pi64, pi64]),
@@ -139,6 +142,10 @@ def lib():
         'iss_adpcm_decode': (C.c_int, [vp, vp, i64, vp, i32, i64, i64, pi32]),
         'iss_adpcm_get_stage': (C.c_int, [vp, i32, vp, i64]),
         'iss_adpcm_stats': (C.c_int, [vp, pi64, pi64]),
+        'iss_msadpcm_decode_host': (C.c_int, [vp, i64, i64, i32, i32, i64, pi16, pi32]),
+        'iss_msadpcm_decode': (C.c_int, [vp, vp, i64, vp, i32, i64, i64, pi32]),
+        'iss_msadpcm_get_stage': (C.c_int, [vp, i32, vp, i64]),
+        'iss_msadpcm_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_host_alloc': (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
         'iss_host_free': (C.c_int, [vp, vp]),
         'iss_cnn_probs_async': (C.c_int, [vp, C.c_int, pi32, i32, pf, pu8, pi64]),
@@ -304,16 +311,21 @@ def flac_decode_host(buf, frames, channels, bps, frames_total):
     return (out[:, 0] if channels == 1 else out), st
 
 
-def adpcm_decode_host(buf, nblocks, channels, block_align, frames_total):
+def adpcm_decode_host(buf, nblocks, channels, block_align, frames_total, fn='iss_adpcm_decode_host'):
     """iss_adpcm_decode_host -> (PCM16 samples (n,) or (n, channels), per-block ISS_ADPCM_* status)."""
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
     out = np.empty((int(frames_total), int(channels)), dtype=np.int16)
     st = np.zeros(int(nblocks), dtype=np.int32)
-    rc = lib().iss_adpcm_decode_host(C.c_void_p(buf.ctypes.data), buf.size, int(nblocks), int(channels), int(block_align),
-                                     int(frames_total), _ptr(out, C.c_int16), _ptr(st, C.c_int32))
+    rc = getattr(lib(), fn)(C.c_void_p(buf.ctypes.data), buf.size, int(nblocks), int(channels), int(block_align),
+                            int(frames_total), _ptr(out, C.c_int16), _ptr(st, C.c_int32))
     if rc != 0:
-        raise NativeError(f'iss_adpcm_decode_host failed ({rc}): bad block geometry')
+        raise NativeError(f'{fn} failed ({rc}): bad block geometry')
     return (out[:, 0] if channels == 1 else out), st
+
+
+def msadpcm_decode_host(buf, nblocks, channels, block_align, frames_total):
+    """iss_msadpcm_decode_host: as adpcm_decode_host, Microsoft ADPCM blocks."""
+    return adpcm_decode_host(buf, nblocks, channels, block_align, frames_total, 'iss_msadpcm_decode_host')
 
 
 class Context:
@@ -511,12 +523,17 @@ class Context:
         windows: rows of WINDOW, one beside every job (iss_adpcm_decode_windows): each job holds exactly the blocks that its
         samples [s_begin, s_end) lie in, and only those samples are produced.
         splits: as for `resample` (iss_adpcm_decode_split), for TO_STAGE jobs with a filter; None for every other job."""
+        return self._block_decode('adpcm', src, jobs, nblocks, n_signal, windows, splits)
+
+    def _block_decode(self, coder, src, jobs, nblocks, n_signal, windows, splits):
+        """iss_<coder>_decode.  Status array and kept source bytes are the coder's own: a pass launches both coders before it
+        reads either's status."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=ADPCM_JOB).reshape(-1))
-        st = self._status('_adpcm_status', nblocks)
-        self._decode_call('iss_adpcm_decode', (C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data)),
+        st = self._status(f'_{coder}_status', nblocks)
+        self._decode_call(f'iss_{coder}_decode', (C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data)),
                           (jb.size, int(nblocks), int(n_signal), _ptr(st, C.c_int32)), windows, splits)
-        self._keep_adpcm = src         # the async H2D copy reads it until the next sync
+        setattr(self, f'_keep_{coder}', src)         # the async H2D copy reads it until the next sync
         return st[:int(nblocks)]
 
     def adpcm_get_stage(self, job, frames_total, channels):
@@ -526,6 +543,19 @@ class Context:
     def adpcm_stats(self):
         """(ADPCM decode launches, blocks decoded) since the context was created."""
         return self._counters('iss_adpcm_stats')
+
+    # ---- Microsoft ADPCM decoder (iss_msadpcm_*): the IMA decoder's rows and contracts, state of its own
+    def msadpcm_decode(self, src, jobs, nblocks, n_signal=-1, windows=None, splits=None):
+        """iss_msadpcm_decode: as adpcm_decode, for Microsoft ADPCM blocks (status ISS_ADPCM_PREDICTOR for a bad block)."""
+        return self._block_decode('msadpcm', src, jobs, nblocks, n_signal, windows, splits)
+
+    def msadpcm_get_stage(self, job, frames_total, channels):
+        """PCM16 samples of staged job `job` of the last msadpcm_decode: (n,) or (n, channels) int16."""
+        return self._get_stage('iss_msadpcm_get_stage', job, frames_total, channels, np.int16)
+
+    def msadpcm_stats(self):
+        """(Microsoft ADPCM decode launches, blocks decoded) since the context was created."""
+        return self._counters('iss_msadpcm_stats')
 
     # ---- page-locked host arrays
     def pinned_empty(self, shape, dtype):

@@ -79,7 +79,8 @@ extern "C" void iss_destroy(iss_ctx* c) {
     DevBuf* bufs[] = {&c->sig, &c->mspec, &c->loge, &c->d_winrow, &c->d_stats, &c->d_finite, &c->d_out, &c->d_in, &c->raw1, &c->d_rowflag, &c->d_lfinite,
                       &c->vbx_sig, &c->vbx_dither, &c->vbx_fb, &c->vbx_out, &c->vbx_meta, &c->rs_src, &c->rs_jobs,
                       &c->flac.src, &c->flac.rows, &c->flac.status, &c->flac.stage,
-                      &c->adpcm.src, &c->adpcm.rows, &c->adpcm.status, &c->adpcm.stage};
+                      &c->adpcm.src, &c->adpcm.rows, &c->adpcm.status, &c->adpcm.stage,
+                      &c->msadpcm.src, &c->msadpcm.rows, &c->msadpcm.status, &c->msadpcm.stage};
     for (DevBuf* b : bufs) free_buf(*b);
     for (auto& b : c->act) free_buf(b);
     for (auto& f : c->rs_filters) if (f.d_taps) (void)hipFree(f.d_taps);
@@ -117,7 +118,8 @@ extern "C" int iss_scribble(iss_ctx* c, uint32_t word) {
     std::vector<DevBuf*> bufs = {&c->raw1, &c->d_stats, &c->d_finite, &c->d_lfinite, &c->d_out, &c->d_in, &c->d_winrow, &c->d_rowflag,
                                  &c->vbx_fb, &c->vbx_meta, &c->vbx_sig, &c->rs_src, &c->rs_jobs,
                                  &c->flac.src, &c->flac.rows, &c->flac.status, &c->flac.stage,
-                                 &c->adpcm.src, &c->adpcm.rows, &c->adpcm.status, &c->adpcm.stage};
+                                 &c->adpcm.src, &c->adpcm.rows, &c->adpcm.status, &c->adpcm.stage,
+                                 &c->msadpcm.src, &c->msadpcm.rows, &c->msadpcm.status, &c->msadpcm.stage};
     for (auto& b : c->act) bufs.push_back(&b);
     for (DevBuf* b : bufs) {
         if (!b->p) continue;

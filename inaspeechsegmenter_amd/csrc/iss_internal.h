@@ -97,8 +97,9 @@ struct iss_ctx {
     DevBuf rs_src, rs_jobs;
     IssCounters rs_count;                 // launches, jobs
 
-    // the coded decoders: FLAC (flac.hip: rows = frames) and IMA ADPCM (adpcm.hip: rows = jobs, status per block)
-    IssCodec flac{"flac"}, adpcm{"adpcm"};
+    // the coded decoders: FLAC (flac.hip: rows = frames), IMA ADPCM and Microsoft ADPCM (adpcm.hip: rows = jobs, status per block).
+    // The two ADPCM coders share a kernel template and nothing of their state: a pass with files of both makes two calls
+    IssCodec flac{"flac"}, adpcm{"adpcm"}, msadpcm{"msadpcm"};
 
     // resident features
     DevBuf mspec, loge;

@@ -9,8 +9,8 @@ Mirrors io.py:32-79 `media2sig16kmono(medianame, start_sec, stop_sec, ffmpeg, dt
 Decode stays on the host (north star); soundfile/libsndfile is not available in the target
 image, so RIFF/WAVE is parsed here with libsndfile's conversion rules (PCM16 -> x/32768,
 unknown chunks skipped).  FLAC (flac.py) reads exactly like its WAV twin, decoded here by the host build of the
-device's frame decoder; so do G.711 and IMA ADPCM in WAV, RF64 / BW64, Wave64, AIFF / AIFF-C, AU and CAF (sndfmt.py: numpy
-tables, byte swaps and the host build of the device's IMA decoder).  A file is read once (`_read_file`) and `_classify` says
+device's frame decoder; so do G.711, IMA ADPCM and Microsoft ADPCM in WAV, RF64 / BW64, Wave64, AIFF / AIFF-C, AU and CAF (sndfmt.py: numpy
+tables, byte swaps and the host builds of the device's two ADPCM decoders).  A file is read once (`_read_file`) and `_classify` says
 from its bytes which parser takes it: a new format is one line there.  `decode_pcm` is the entry the native pipeline uses: it keeps
 PCM16 as int16 so the device does the x/32768 scaling (2 B/sample over PCIe, not 4).
 `split_source` reads the channels of a file each on its own (an extension: the reference needs one ffmpeg -map_channel run per
@@ -88,7 +88,7 @@ def _read_range(path, offset, size):
 
 
 def _classify(buf, name):
-    """What the bytes of a file are to the ffmpeg-free read: a flac.FlacStream, a sndfmt.Sound (G.711 / IMA ADPCM WAV, RF64,
+    """What the bytes of a file are to the ffmpeg-free read: a flac.FlacStream, a sndfmt.Sound (G.711 / IMA / Microsoft ADPCM WAV, RF64,
     Wave64, AIFF, AU, CAF), or None for what _parse_wav reads or refuses.  One line per format; what comes back has `sr`,
     `stored()` (the host decode) and `source(resample)` (what Segmenter reads).  (flac and sndfmt import this
     module for need_16k_mono and _to_float, so they are imported here and not at the top.)"""
@@ -316,8 +316,9 @@ def _sound_excerpts(h, ranges, resample):
     out = []
     for start, stop in ranges:
         a, b = excerpt_bounds(h.name, n16, start, stop)
-        if h.kind == 'ima':
-            out.append(sndfmt.AdpcmExcerpt(h, 'pcm' if mono16k else 'resample', a, b))
+        blocks = sndfmt.block_excerpt(h, 'pcm' if mono16k else 'resample', a, b)
+        if blocks is not None:
+            out.append(blocks)
         elif mono16k:
             x = sndfmt.sub_sound(h, a, b)[0].stored()
             out.append(np.ascontiguousarray(x) if x.dtype == np.int16 else np.ascontiguousarray(_to_float(x, np.float32)))
@@ -416,8 +417,10 @@ def channel_excerpts(medianame, ranges, channels=None, resample=False):
         a, b = excerpt_bounds(medianame, n16, start, stop)
         if isinstance(h, flac.FlacStream):
             out.append(flac.FlacExcerpt(h, 'resample', a, b, sel))
-        elif h.kind == 'ima':
-            out.append(sndfmt.AdpcmExcerpt(h, 'resample', a, b, sel))
+            continue
+        blocks = sndfmt.block_excerpt(h, 'resample', a, b, sel)
+        if blocks is not None:
+            out.append(blocks)
         else:
             j_lo, j_hi = R.input_span(h.sr, h.n, a, b - a)
             sub, _ = sndfmt.sub_sound(h, j_lo, j_hi + 1)

@@ -8,7 +8,7 @@ launches, copies and Python bookkeeping become the limit.  Here files are proces
   decode threads   N files  ->  int16 PCM as a numpy array (RIFF parse, or the ffmpeg pipe), or -- without ffmpeg -- a source of
                    sources.py, handed on as stored for the device to finish: a WAV at another rate / channel count with
                    Segmenter(resample=True), G.711 and big-endian files (RawSource), FLAC frames (flac.FlacSource), IMA ADPCM
-                   blocks (sndfmt.AdpcmSource)
+                   and Microsoft ADPCM blocks (sndfmt.AdpcmSource, sndfmt.MsAdpcmSource)
   packer           the PCM of a super-batch (default <= 32 files / ~40 min of audio) is laid end to end in ONE page-locked
                    buffer, every file starting on a multiple of 160 samples: frame t of file f is then frame
                    off_f / 160 + t of the concatenation, and the frames that straddle two files are simply never used

@@ -394,7 +394,7 @@ class Segmenter:
         device: HIP device ordinal.  models: None -> Keras files from ~/.keras/inaSpeechSegmenter
         (remote_utils.py search path); 'synthetic' -> seeded stand-in weights; or a dict
         {model_fname: (layers, in_shape)}.
-        resample (extension, ffmpeg=None only): files (WAV, FLAC, G.711 / IMA ADPCM, AIFF, AU, CAF, Wave64) at other integer rates (4 000 - 384 000 Hz) or with several
+        resample (extension, ffmpeg=None only): files (WAV, FLAC, G.711 / IMA ADPCM / Microsoft ADPCM, AIFF, AU, CAF, Wave64) at other integer rates (4 000 - 384 000 Hz) or with several
         channels are downmixed, resampled to 16 kHz and quantised to PCM16 on the device (resample.py states the
         arithmetic) instead of failing; 16 kHz mono files are read as without it."""
         if resample and ffmpeg is not None:
@@ -497,7 +497,7 @@ class Segmenter:
         """The 16 kHz mono samples the front end reads for `medianame` (decode_pcm's int16 or float32 array); with
         resample=True a WAV at another rate or channel count is resampled on the device and its PCM16 copied back.  Without
         ffmpeg a FLAC file is decoded on the device and its samples copied back (what decode_pcm gives for its WAV twin),
-        and so is an IMA ADPCM file; G.711 and big-endian files at other rates or channel counts go to the resampler as stored."""
+        and so is an IMA or Microsoft ADPCM file; G.711 and big-endian files at other rates or channel counts go to the resampler as stored."""
         return self._mono_pcm(_load_source(medianame, None, None, self.ffmpeg, self.resample))
 
     # ---- the channels of one file, each on its own, without ffmpeg (an extension: the reference needs one ffmpeg run per channel)

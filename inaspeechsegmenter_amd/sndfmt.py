@@ -1,10 +1,11 @@
-"""Telephony and studio containers without ffmpeg: G.711, IMA ADPCM, AIFF / AIFF-C, AU, CAF, Wave64, RF64 / BW64.
+"""Telephony and studio containers without ffmpeg: G.711, IMA and Microsoft ADPCM, AIFF / AIFF-C, AU, CAF, Wave64, RF64 / BW64.
 
 The reference's ffmpeg-free read is `soundfile.read` (io.py:36-55), and libsndfile opens all of these.  Here a file is
 recognised by its leading bytes and then reads exactly like its WAV twin: the little-endian RIFF/WAVE file of the same rate
 and channel count that holds
 
-    G.711 mu-law / A-law, IMA ADPCM (WAV tag 0x11)   PCM16, the decoded value (include/iss.h states the three decoders)
+    G.711 mu-law / A-law, IMA ADPCM (WAV tag 0x11),  PCM16, the decoded value (include/iss.h states the four decoders)
+    Microsoft ADPCM (WAV tag 2)
     signed 8-bit (AIFF, AU, CAF)                     8-bit WAV (unsigned), x + 128
     unsigned 8-bit (AIFF-C `raw `)                   8-bit WAV, as stored
     16 / 24 / 32-bit integer, either byte order      PCM of the same width, same values
@@ -16,8 +17,13 @@ build of the device's IMA decoder); `source()` hands them to the device as they 
 bytes, signed bytes and big-endian samples to the resample kernel (a `RawSource` with ISS_RS_I8 / ISS_RS_ULAW / ISS_RS_ALAW /
 ISS_RS_SWAP), IMA blocks to adpcm_decode_kernel (`AdpcmSource`).  The frame count of an IMA file is its `fact` count when present and not larger than whole blocks *
 samples per block, else that product; a trailing partial block is ignored (a definition: libsndfile was not at hand to pin it).
+Microsoft ADPCM (kind 'ms') is the second block-coded kind and follows IMA through every branch: `_BLOCK` below is the table of what
+tells the two apart (samples-per-block rule, host decoder, source classes), and the same frame-count rule holds.  Only files whose
+`fmt ` chunk carries the 32-byte extension with the seven standard coefficient pairs are read (what libsndfile decodes: it
+uses its own table); its decode rules, floor rounding among them, are definitions stated in include/iss.h.
 """
 import struct
+from typing import NamedTuple
 
 import numpy as np
 
@@ -27,14 +33,16 @@ from . import resample as R
 from .io import _to_float, need_16k_mono
 from .sources import CodedSource, RawSource, host_window
 
-# benchmark switch (tools/bench_sndfmt.py), not a user option: True makes the ffmpeg-free read expand G.711 and IMA ADPCM on
-# the host (numpy table / iss_adpcm_decode_host in the decode threads) instead of handing the stored bytes to the device
+# benchmark switch (tools/bench_sndfmt.py), not a user option: True makes the ffmpeg-free read expand G.711 and ADPCM on
+# the host (numpy table / iss_adpcm_decode_host, iss_msadpcm_decode_host in the decode threads) instead of handing the stored bytes to the device
 _HOST_DECODE = False
 
 _WIDTH = {'u8': 1, 'i8': 1, 'ulaw': 1, 'alaw': 1, 'i16': 2, 'i24': 3, 'i32': 4, 'f32': 4, 'f64': 8}
 _RS_CODE = {'u8': 0, 'i16': 1, 'i32': 2, 'f32': 3, 'f64': 4, 'i8': _native.RS_I8, 'ulaw': _native.RS_ULAW, 'alaw': _native.RS_ALAW}
 _W64_TAIL = bytes.fromhex('f3acd3118cd100c04f8edb8a')            # GUID tail of the Wave64 chunk ids 'wave', 'fmt ', 'data', 'fact'
 _W64_RIFF = b'riff' + bytes.fromhex('2e91cf11a5d628db04c10000')
+_MS_TAG = 'WAVE format tag 2 (MS ADPCM)'                        # every refusal of such a file says this
+_MS_COEFS = (256, 0, 512, -256, 0, 0, 192, 64, 240, 0, 460, -208, 392, -232)
 _WAV_TAGS = {2: 'MS ADPCM', 0x10: 'OKI ADPCM', 0x14: 'G.723 ADPCM', 0x31: 'GSM 06.10', 0x40: 'G.721 ADPCM', 0x45: 'G.726 ADPCM',
              0x50: 'MPEG', 0x55: 'MPEG Layer III', 0x64: 'G.726 ADPCM'}
 _AU_ENC = {1: 'ulaw', 2: 'i8', 3: 'i16', 4: 'i24', 5: 'i32', 6: 'f32', 7: 'f64', 27: 'alaw'}
@@ -65,8 +73,8 @@ for _t in (ULAW_TABLE, ALAW_TABLE):
 
 class Sound:
     """A parsed file: `data` = the stored sample bytes (uint8, exactly the frames that count), `kind` one of u8 i8 i16 i24
-    i32 f32 f64 ulaw alaw ima, `big` = stored big-endian, `base` = byte offset of `data` in the file.  ima: `block_align`
-    bytes per block, `spb` samples per block, `data` = whole blocks."""
+    i32 f32 f64 ulaw alaw ima ms, `big` = stored big-endian, `base` = byte offset of `data` in the file.  ima, ms (the
+    block-coded kinds of _BLOCK): `block_align` bytes per block, `spb` samples per block, `data` = whole blocks."""
     __slots__ = ('name', 'sr', 'ch', 'n', 'kind', 'big', 'data', 'base', 'block_align', 'spb')
 
     def __init__(self, name, sr, ch, kind, big, data, base, frames=None, block_align=0, spb=0):
@@ -76,9 +84,9 @@ class Sound:
             raise ValueError(f'{name}: sample rate {sr} Hz')
         self.name, self.sr, self.ch, self.kind, self.big, self.base = name, int(sr), int(ch), kind, bool(big), int(base)
         self.block_align, self.spb = int(block_align), int(spb)
-        if kind == 'ima':
+        if kind in _BLOCK:
             if ch > MAX_ADPCM_CHANNELS or block_align > MAX_ADPCM_ALIGN:
-                raise ValueError(f'{name}: IMA ADPCM with {ch} channels in {block_align}-byte blocks is not supported '
+                raise ValueError(f'{name}: {_BLOCK[kind].label} with {ch} channels in {block_align}-byte blocks is not supported '
                                  f'(at most {MAX_ADPCM_CHANNELS} channels, {MAX_ADPCM_ALIGN}-byte blocks)')
             nblocks = len(data) // block_align
             n = nblocks * spb
@@ -95,7 +103,7 @@ class Sound:
 
     @property
     def nblocks(self):
-        return len(self.data) // self.block_align if self.kind == 'ima' else 0
+        return len(self.data) // self.block_align if self.kind in _BLOCK else 0
 
     def fetch(self, byte0, byte1):
         """Bytes [byte0, byte1) of `data` (what a SoundHeader reads from the file)."""
@@ -105,7 +113,7 @@ class Sound:
         return a.reshape(-1, self.ch) if self.ch > 1 else a.reshape(-1)
 
     def check(self, status):
-        """Raise ValueError for the first IMA block whose decode status (ISS_ADPCM_*) is not 0."""
+        """Raise ValueError for the first ADPCM block whose decode status (ISS_ADPCM_*) is not 0."""
         bad = np.flatnonzero(np.asarray(status))
         if bad.size:
             k = int(bad[0])
@@ -117,10 +125,10 @@ class Sound:
 
     def split_source(self, sel):
         """What Segmenter reads for the channels `sel` of a multi-channel file, each on its own (io.split_source)."""
-        host = _HOST_DECODE and self.kind in ('ulaw', 'alaw', 'ima')
-        if self.kind == 'ima' and not host and self.n > 0:
-            return AdpcmSource(self, 'resample', sel)
-        if host or self.kind == 'ima':
+        host = _HOST_DECODE and self.kind in _HOST_KINDS
+        if self.kind in _BLOCK and not host and self.n > 0:
+            return _BLOCK[self.kind].source(self, 'resample', sel)
+        if host or self.kind in _BLOCK:
             return RawSource(self.stored(), self.sr, sel=sel)
         x, fmt = self.raw()
         return RawSource(x, self.sr, fmt, sel)
@@ -136,10 +144,10 @@ class Sound:
             a = ULAW_TABLE[d]
         elif k == 'alaw':
             a = ALAW_TABLE[d]
-        elif k == 'ima':
+        elif k in _BLOCK:
             if self.n == 0:
                 return self._shape(np.empty(0, dtype=np.int16))
-            a, st = _native.adpcm_decode_host(d, self.nblocks, self.ch, self.block_align, self.n)
+            a, st = _BLOCK[k].host(d, self.nblocks, self.ch, self.block_align, self.n)
             self.check(st)
             return a
         elif k == 'i24':
@@ -157,8 +165,8 @@ class Sound:
         k = self.kind
         if k == 'i24':
             return self.stored(), _native.RS_FORMAT[np.dtype('<i4')]
-        if k == 'ima':
-            raise ValueError(f'{self.name}: IMA ADPCM blocks are decoded by their own kernel')
+        if k in _BLOCK:
+            raise ValueError(f'{self.name}: {_BLOCK[k].label} blocks are decoded by their own kernel')
         w = _WIDTH[k]
         if w == 1 or not self.big:
             x = self.data if w == 1 else self.data.view({'i16': '<i2', 'i32': '<i4', 'f32': '<f4', 'f64': '<f8'}[k])
@@ -180,12 +188,12 @@ class SoundHeader:
 
 
 def sub_sound(h, f0, f1):
-    """-> (the Sound of frames [f0, f1) of `h` -- of the whole IMA blocks they lie in --, the file's frame number of its first
+    """-> (the Sound of frames [f0, f1) of `h` -- of the whole ADPCM blocks they lie in --, the file's frame number of its first
     frame).  `h` is a Sound or a SoundHeader; only those bytes are fetched, and `base` stays an offset in the file."""
-    if h.kind == 'ima':
+    if h.kind in _BLOCK:
         k0, k1 = f0 // h.spb, (f1 - 1) // h.spb
         data = h.fetch(k0 * h.block_align, (k1 + 1) * h.block_align)
-        return Sound(h.name, h.sr, h.ch, 'ima', False, data, h.base + k0 * h.block_align,
+        return Sound(h.name, h.sr, h.ch, h.kind, False, data, h.base + k0 * h.block_align,
                      frames=min(h.n, (k1 + 1) * h.spb) - k0 * h.spb, block_align=h.block_align, spb=h.spb), k0 * h.spb
     fb = _WIDTH[h.kind] * h.ch
     return Sound(h.name, h.sr, h.ch, h.kind, h.big, h.fetch(f0 * fb, f1 * fb), h.base + f0 * fb), f0
@@ -210,32 +218,68 @@ def _wav_kind(name, tag, bits):
         if bits != 4:
             raise ValueError(f'{name}: {bits}-bit IMA ADPCM is not supported (4 bits are)')
         return 'ima'
+    if tag == 2:
+        return 'ms'                                               # (_block_geometry judges its `fmt ` extension)
     what = _WAV_TAGS.get(tag)
     raise ValueError(f'{name}: unsupported WAVE format tag {tag}' + (f' ({what})' if what else ''))
 
 
 def _parse_fmt(buf, body, size, name):
-    """A `fmt ` chunk body -> (tag, ch, sr, block_align, bits, samples per block | None)."""
+    """A `fmt ` chunk body -> (tag, ch, sr, block_align, bits, samples per block | None).  Format tag 2: samples per block =
+    (wSamplesPerBlock, cbSize, wNumCoef, the coefficients), or a str saying what its extension lacks."""
     tag, ch, sr, _, align, bits = struct.unpack_from('<HHIIHH', buf, body)
     spb = None
     if size >= 20 and tag == 0x11:
         spb = struct.unpack_from('<H', buf, body + 18)[0]
+    if tag == 2:
+        if size < 50 or len(buf) < body + 50:
+            spb = f'a {size}-byte fmt chunk without the 32-byte extension (wSamplesPerBlock, wNumCoef, 7 coefficient pairs)'
+        else:
+            ext = struct.unpack_from('<HHH14h', buf, body + 16)
+            spb = (ext[1], ext[0], ext[2], ext[3:])
     if tag == 0xFFFE and size >= 26:                              # WAVE_FORMAT_EXTENSIBLE
         tag = struct.unpack_from('<H', buf, body + 24)[0]
+        if tag == 2:
+            spb = 'wrapped in WAVE_FORMAT_EXTENSIBLE, which has no room for the coefficient table'
     return tag, ch, sr, align, bits, spb
+
+
+def _block_geometry(kind, ch, align, bits, spb):
+    """-> (samples per block, None) of a block-coded `fmt `, or (None, why it is refused): the rules of adpcm.hip's
+    geometry_ok and, for Microsoft ADPCM, of the extension -- one place for the whole-file read and read_header."""
+    if kind == 'ima':
+        if ch < 1 or align % (4 * ch) != 0 or align <= 4 * ch:
+            return None, f'IMA ADPCM block size {align} is not a multiple of 4 * {ch} channels above one header'
+        want = _BLOCK[kind].spb(align, ch)
+        if spb is not None and spb != want:
+            return None, f'IMA ADPCM {spb} samples per block, {align}-byte blocks of {ch} channels hold {want}'
+        return want, None
+    if isinstance(spb, str):
+        return None, f'{_MS_TAG}: {spb}'
+    stated, cb, ncoef, coefs = spb
+    if cb < 32:
+        return None, f'{_MS_TAG}: cbSize {cb}, the extension takes 32 bytes'
+    if bits != 4:
+        return None, f'{_MS_TAG}: {bits} bits per sample (4 are)'
+    if ch < 1 or align <= 7 * ch or (align - 7 * ch) * 2 % ch != 0:
+        return None, f'{_MS_TAG}: block size {align} does not hold a 7-byte header and whole samples of {ch} channels'
+    want = _BLOCK[kind].spb(align, ch)
+    if stated != want:
+        return None, f'{_MS_TAG}: {stated} samples per block, {align}-byte blocks of {ch} channels hold {want}'
+    if ncoef != 7 or tuple(coefs) != _MS_COEFS:
+        return None, f'{_MS_TAG}: {ncoef} coefficient pairs {list(coefs[:2 * min(ncoef, 7)])}, only the 7 standard pairs are decoded'
+    return want, None
 
 
 def _wav_sound(buf, name, fmt, fact, body, end):
     tag, ch, sr, align, bits, spb = fmt
     kind = _wav_kind(name, tag, bits)
     data = np.frombuffer(buf, dtype=np.uint8, count=end - body, offset=body)
-    if kind != 'ima':
+    if kind not in _BLOCK:
         return Sound(name, sr, ch, kind, False, data, body)       # (`fact` is advisory for sample-per-byte formats, as for PCM)
-    if ch < 1 or align % (4 * ch) != 0 or align <= 4 * ch:
-        raise ValueError(f'{name}: IMA ADPCM block size {align} is not a multiple of 4 * {ch} channels above one header')
-    want = (align // ch - 4) * 2 + 1
-    if spb is not None and spb != want:
-        raise ValueError(f'{name}: IMA ADPCM {spb} samples per block, {align}-byte blocks of {ch} channels hold {want}')
+    want, why = _block_geometry(kind, ch, align, bits, spb)
+    if why:
+        raise ValueError(f'{name}: {why}')
     return Sound(name, sr, ch, kind, False, data, body, frames=fact, block_align=align, spb=want)
 
 
@@ -251,7 +295,7 @@ def _parse_riff(buf, name):
             ds64 = struct.unpack_from('<QQQ', buf, body)
         elif cid == b'fmt ':
             fmt = _parse_fmt(buf, body, size, name)
-            if not rf64 and fmt[0] not in (6, 7, 0x11):
+            if not rf64 and fmt[0] not in (6, 7, 0x11, 2):
                 return None
         elif cid == b'fact' and size >= 4:
             fact = struct.unpack_from('<I', buf, body)[0]
@@ -399,7 +443,7 @@ def _parse_caf(buf, name):
 
 
 def read_header(path, name=None):
-    """The SoundHeader of a plain RIFF/WAVE file (PCM, float, G.711 or IMA ADPCM), from its chunk headers alone: 12 bytes, then
+    """The SoundHeader of a plain RIFF/WAVE file (PCM, float, G.711, IMA or Microsoft ADPCM), from its chunk headers alone: 12 bytes, then
     8 per chunk and the bodies of `fmt ` and `fact`; a `data` chunk behind a large unknown chunk costs one more 8-byte read.
     None for every other container and for whatever needs the whole file to be judged (RF64 sizes, a piped WAV without a length, a
     file cut short): io.excerpts then reads the file as the whole-file read does."""
@@ -437,11 +481,10 @@ def read_header(path, name=None):
             h.block_align = h.spb = 0
             if ch < 1 or sr < 1:
                 return None
-            if h.kind == 'ima':
+            if h.kind in _BLOCK:
                 # (the rules of _wav_sound and Sound.__init__, on the header's numbers)
-                want = (align // ch - 4) * 2 + 1
-                if align % (4 * ch) != 0 or align <= 4 * ch or (spb is not None and spb != want) or ch > MAX_ADPCM_CHANNELS or \
-                        align > MAX_ADPCM_ALIGN:
+                want, why = _block_geometry(h.kind, ch, align, bits, spb)
+                if why or ch > MAX_ADPCM_CHANNELS or align > MAX_ADPCM_ALIGN:
                     return None
                 n = size // align * want
                 h.n, h.block_align, h.spb = (int(fact) if fact is not None and fact <= n else n), int(align), want
@@ -493,7 +536,7 @@ def _ours(head):
                 tag = struct.unpack_from('<H', head, pos + 8)[0]
                 if tag == 0xFFFE and size >= 26 and pos + 34 <= len(head):
                     tag = struct.unpack_from('<H', head, pos + 32)[0]
-                return tag in (6, 7, 0x11)
+                return tag in (6, 7, 0x11, 2)
             if cid == b'data':
                 return False
             pos += 8 + size + (size & 1)
@@ -542,7 +585,7 @@ class AdpcmSource(CodedSource):
 
 
 class AdpcmExcerpt(AdpcmSource):
-    """Outputs [a, b) of an IMA ADPCM file for the windowed decode: `s` = the sub_sound of the blocks that hold the
+    """Outputs [a, b) of an IMA (or, as MsAdpcmExcerpt, Microsoft) ADPCM file for the windowed decode: `s` = the sub_sound of the blocks that hold the
     stored-rate samples the excerpt needs ('pcm': [a, b); 'resample': resample.input_span of them), `first` the file's sample
     number of its first sample.  A bad block is named by its byte offset in the file (s.base is one).  `sel` ('resample' only):
     the channels to write apart (None: their average)."""
@@ -563,25 +606,62 @@ class AdpcmExcerpt(AdpcmSource):
         return np.ascontiguousarray(x) if self.kind == 'pcm' else host_window(x, self.s.sr, self.win, self.sel)
 
 
+class MsAdpcmSource(AdpcmSource):
+    """A Microsoft ADPCM file for the device decoder: AdpcmSource's rows, its own launch (iss_msadpcm_decode) after IMA's."""
+    __slots__ = ()
+    pass_order = 3
+
+    @staticmethod
+    def launch(ctx, staged, rows, nblocks, n_signal=-1, **kw):
+        return ctx.msadpcm_decode(staged, rows, nblocks, n_signal, **kw)
+
+
+class MsAdpcmExcerpt(AdpcmExcerpt, MsAdpcmSource):
+    """Outputs [a, b) of a Microsoft ADPCM file: AdpcmExcerpt's window on MsAdpcmSource's launch."""
+    __slots__ = ()
+
+
+class _BlockKind(NamedTuple):
+    """What tells the block-coded kinds apart; every `kind in _BLOCK` branch of this module reads its columns."""
+    label: str
+    spb: object            # (block_align, channels) -> samples per block
+    host: object           # the host build of the decoder (_native)
+    source: type
+    excerpt: type
+
+
+_BLOCK = {'ima': _BlockKind('IMA ADPCM', lambda align, ch: (align // ch - 4) * 2 + 1, _native.adpcm_decode_host,
+                            AdpcmSource, AdpcmExcerpt),
+          'ms': _BlockKind('MS ADPCM', lambda align, ch: (align - 7 * ch) * 2 // ch + 2, _native.msadpcm_decode_host,
+                           MsAdpcmSource, MsAdpcmExcerpt)}
+_HOST_KINDS = ('ulaw', 'alaw') + tuple(_BLOCK)                   # what _HOST_DECODE expands on the host
+
+
+def block_excerpt(h, kind, a, b, sel=None):
+    """The windowed source of outputs [a, b) of a block-coded file `h` (io.excerpts, io.channel_excerpts), or None for any
+    other kind."""
+    return _BLOCK[h.kind].excerpt(h, kind, a, b, sel) if h.kind in _BLOCK else None
+
+
 def decode_on(ctx, src):
-    """One IMA file on its own: the resident signal becomes its 16 kHz PCM16 -> the per-block status, valid after the
+    """One ADPCM file on its own: the resident signal becomes its 16 kHz PCM16 -> the per-block status, valid after the
     context's next synchronising call (check it with src.check)."""
     return src.place(ctx)
 
 
 def source(snd, resample=False):
     """What Segmenter reads for a parsed file under the WAV-twin rules of the ffmpeg-free read: the twin's int16 / float32
-    array (16 kHz mono), an AdpcmSource, or a sources.RawSource holding the bytes as stored.  Without `resample`, anything but
+    array (16 kHz mono), an AdpcmSource / MsAdpcmSource, or a sources.RawSource holding the bytes as stored.  Without `resample`, anything but
     16 kHz mono is refused as the WAV path refuses it (io.need_16k_mono)."""
     mono16k = snd.sr == R.SR_OUT and snd.ch == 1
     if not mono16k and not resample:
         need_16k_mono(snd.name, snd.sr, snd.ch)
-    host = _HOST_DECODE and snd.kind in ('ulaw', 'alaw', 'ima')
-    if snd.kind == 'ima' and not host and snd.n > 0:
+    host = _HOST_DECODE and snd.kind in _HOST_KINDS
+    if snd.kind in _BLOCK and not host and snd.n > 0:
         if mono16k:
-            return AdpcmSource(snd, 'pcm')
+            return _BLOCK[snd.kind].source(snd, 'pcm')
         R.check_rate(snd.sr)
-        return AdpcmSource(snd, 'resample')
+        return _BLOCK[snd.kind].source(snd, 'resample')
     if mono16k:
         if snd.kind == 'i16' and snd.big and snd.n > 0:           # swapped on the device, through the identity filter
             x, fmt = snd.raw()
@@ -589,7 +669,7 @@ def source(snd, resample=False):
         x = snd.stored()                                          # G.711: the 256-entry table; the float path's conversions
         return np.ascontiguousarray(x) if x.dtype == np.int16 else np.ascontiguousarray(_to_float(x, np.float32))
     R.check_rate(snd.sr)
-    if host or snd.kind == 'ima':
+    if host or snd.kind in _BLOCK:
         return RawSource(snd.stored(), snd.sr)
     x, fmt = snd.raw()
     return RawSource(x, snd.sr, fmt)

@@ -17,7 +17,7 @@ bytes as stored, which a kernel turns into 16 kHz mono PCM16 inside the resident
     parts                   how many consecutive signals it writes (default 1): `parts` signals of `size` samples each, signal k at
                             dst_offset + k * `stride`, stride = `size` rounded up to FRAME_HOP
 
-A source made with a channel selection `sel` (RawSource, flac.FlacSource, sndfmt.AdpcmSource) writes one signal per selected
+A source made with a channel selection `sel` (RawSource, flac.FlacSource, sndfmt.AdpcmSource and its Microsoft twin) writes one signal per selected
 channel instead of their average: `parts` = len(sel), and its job carries the split row (iss_split) for the split entry point
 -- downmixed and split files of a pass in the same launch.
 

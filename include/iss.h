@@ -225,7 +225,8 @@ typedef struct {
     int64_t nblocks;       /* whole blocks, >= 1                                                                          */
     int64_t frames_total;  /* samples per channel, in ((nblocks - 1) * samples_per_block, nblocks * samples_per_block]     */
     int32_t channels;      /* 1 .. 64                                                                                     */
-    int32_t block_align;   /* bytes per block: a multiple of 4 * channels, > 4 * channels, at most 32768                  */
+    int32_t block_align;   /* bytes per block: a multiple of 4 * channels, > 4 * channels, at most 32768 (iss_msadpcm_*:
+                              the Microsoft geometry stated with those entry points)                                      */
     int32_t output;        /* ISS_ADPCM_TO_SIGNAL / ISS_ADPCM_TO_STAGE                                                    */
     int32_t filter;        /* TO_STAGE: iss_resample_filter id, or -1 (decode only)                                      */
     int64_t dst_offset;    /* TO_SIGNAL, or TO_STAGE with a filter: first output sample in the resident signal           */
@@ -250,6 +251,42 @@ int iss_adpcm_decode(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss
 int iss_adpcm_get_stage(iss_ctx* ctx, int32_t job, void* out, int64_t bytes);
 /* ADPCM decode launches and blocks since the context was created.                                                    */
 int iss_adpcm_stats(iss_ctx* ctx, int64_t* launches, int64_t* blocks);
+
+/* Microsoft ADPCM in WAV (format tag 2) without ffmpeg.  A block of `block_align` bytes, `ch` channels:
+ *   header  bPredictor[ch] (uint8 each), iDelta[ch] (int16 LE each), iSamp1[ch] (int16 LE each), iSamp2[ch] (int16 LE each)
+ *           = 7 * ch bytes
+ *   body    4-bit codes, HIGH nibble first, cycling through the channels: code k (k = 0, 1, ...) belongs to sample 2 + k / ch of
+ *           channel k % ch and sits in byte 7 * ch + (k >> 1), the high nibble when k is even
+ *   samples_per_block = (block_align - 7 * ch) * 2 / ch + 2
+ *   output  sample 0 = iSamp2, sample 1 = iSamp1, then per code n (0 .. 15), s = n >= 8 ? n - 16 : n:
+ *             pred  = (samp1 * C1[bPredictor] + samp2 * C2[bPredictor]) >> 8     (arithmetic shift: floor, NOT C division)
+ *             v     = clamp16(pred + s * delta);  samp2 = samp1;  samp1 = v;  emit v
+ *             delta = min(2^21, max(16, (ADAPT[n] * delta) >> 8))
+ *   C1 = {256, 512, 0, 192, 240, 460, 392}   C2 = {0, -256, 0, 64, 0, -208, -232}
+ *   ADAPT = {230, 230, 230, 230, 307, 409, 512, 614, 768, 614, 512, 409, 307, 230, 230, 230}
+ * Channels are interleaved in the output: the file reads like the PCM16 WAV holding these samples.  Definitions:
+ *   - the `>> 8` is floor, libsndfile's rule (the reference reads through it); the Microsoft text truncates towards zero, which
+ *     differs on negative sums.  No libsndfile was at hand to pin the rule: it round-trips a noisy sine through a nearest-code
+ *     encoder at 36 - 38 dB, which shows that the formulas hang together and nothing more.
+ *   - the header's iDelta is read as a signed int16; a value below 16 (a negative one too) is raised to 16 before the first code.
+ *   - delta can triple per code and the format gives it no ceiling; it is capped at 2^21, so that 768 * delta, 8 * delta and the
+ *     prediction sum stay inside 32 bits and the host build has no signed overflow.  A code moves the output by up to 8 * delta, so a
+ *     delta above 2^13 already spans the whole 16-bit range; an encoder that codes the nearest value never grows it further,
+ *     and no encoder's stream reaches the cap (only crafted blocks do).  Host and device builds are one function.
+ *   - bPredictor >= 7 is a malformed block: status ISS_ADPCM_PREDICTOR, the block decoded with predictor 0 (garbage in that
+ *     block only), as a step index above 88 is treated in an IMA block.
+ * Limits as for IMA: 1 .. 64 channels, block_align <= 32768; block_align > 7 * ch with (block_align - 7 * ch) * 2 a multiple of
+ * ch.  A block need not be a multiple of 4 bytes (3 channels x 70 bytes) and header fields sit at odd offsets: the decoder
+ * reads bytes.  The entry points take the rows of the IMA ones (iss_adpcm_job, iss_window, iss_split) and follow their
+ * contracts word for word with this geometry; they keep device state of their own (source, rows, status, staging), so an
+ * iss_msadpcm_decode after an iss_adpcm_decode overwrites nothing the first call's status or iss_adpcm_get_stage still reads. */
+#define ISS_ADPCM_PREDICTOR   2   /* a Microsoft ADPCM channel header's bPredictor is above 6 (decoded with predictor 0)          */
+int iss_msadpcm_decode_host(const uint8_t* buf, int64_t len, int64_t nblocks, int32_t channels, int32_t block_align,
+                            int64_t frames_total, int16_t* out, int32_t* status_out);
+int iss_msadpcm_decode(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, int32_t njobs,
+                       int64_t nblocks_total, int64_t n_signal, int32_t* status_out);
+int iss_msadpcm_get_stage(iss_ctx* ctx, int32_t job, void* out, int64_t bytes);
+int iss_msadpcm_stats(iss_ctx* ctx, int64_t* launches, int64_t* blocks);
 
 /* Windows: a time range of a file through the three kernels above, touching only what the range needs.  A window row stands
  * beside a job row (windows[k] belongs to jobs[k]); windows == NULL is the unwindowed call, to the bit and to the launch.
@@ -287,6 +324,9 @@ int iss_flac_decode_windows(iss_ctx* ctx, const void* src, int64_t src_bytes, co
 int iss_adpcm_decode_windows(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs,
                              const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
                              int32_t* status_out);
+int iss_msadpcm_decode_windows(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs,
+                               const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
+                               int32_t* status_out);          /* as iss_adpcm_decode_windows, Microsoft ADPCM blocks */
 
 /* Splits: the channels of a file written apart instead of averaged, through the same three entry points' kernels.  A split row
  * stands beside a job row (splits[k] belongs to jobs[k]); splits == NULL is the plain call, to the bit and to the launch.
@@ -327,6 +367,9 @@ int iss_flac_decode_split(iss_ctx* ctx, const void* src, int64_t src_bytes, cons
 int iss_adpcm_decode_split(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, int32_t njobs,
                            int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_split* splits,
                            const int32_t* channel_sel, int64_t nsel);
+int iss_msadpcm_decode_split(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, int32_t njobs,
+                             int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_split* splits,
+                             const int32_t* channel_sel, int64_t nsel);
 int iss_resample_split_geometry(iss_ctx* ctx, int32_t filter, int32_t nsel, int32_t* tile_out, int32_t* group_out);
 
 /* Windows and splits together: a time range of single channels.  The *_windows_split entry points take a window row AND a split
@@ -355,6 +398,9 @@ int iss_flac_decode_windows_split(iss_ctx* ctx, const void* src, int64_t src_byt
 int iss_adpcm_decode_windows_split(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs,
                                    const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
                                    int32_t* status_out, const iss_split* splits, const int32_t* channel_sel, int64_t nsel);
+int iss_msadpcm_decode_windows_split(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs,
+                                     const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
+                                     int32_t* status_out, const iss_split* splits, const int32_t* channel_sel, int64_t nsel);
 
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */

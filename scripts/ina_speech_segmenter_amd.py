@@ -34,8 +34,8 @@ def build_parser():
     ap.add_argument('-s', '--batch_size', type=int, default=32, help='accepted for compatibility (the engine sizes its own passes)')
     ap.add_argument('-d', '--vad_engine', choices=['sm', 'smn'], default='smn')
     ap.add_argument('-g', '--detect_gender', type=_truthy, default=True, metavar='{true,false}')
-    ap.add_argument('-b', '--ffmpeg_binary', default='ffmpeg', help="ffmpeg binary; 'None' reads 16 kHz mono WAV, FLAC, G.711 / IMA ADPCM WAV, AIFF, AU, CAF, Wave64 and RF64 directly "
-                                                                      "(FLAC and IMA ADPCM decoded on the GPU)")
+    ap.add_argument('-b', '--ffmpeg_binary', default='ffmpeg', help="ffmpeg binary; 'None' reads 16 kHz mono WAV, FLAC, G.711 / IMA ADPCM / Microsoft ADPCM WAV, AIFF, AU, CAF, Wave64 and RF64 directly "
+                                                                      "(FLAC, IMA and Microsoft ADPCM decoded on the GPU)")
     ap.add_argument('-e', '--export_format', choices=['csv', 'textgrid'], default='csv')
     ap.add_argument('-r', '--energy_ratio', type=float, default=0.03)
     ap.add_argument('--models', default=None, help="'synthetic' = seeded stand-in weights")
@@ -58,7 +58,8 @@ def main(argv=None):
     if args.channels == 'split' and int(os.environ.get('WORLD_SIZE', '1')) != 1:
         build_parser().error('--channels split runs on one GPU')
     if ffmpeg is None:
-        print('Disabling ffmpeg. ' + ('WAV files at other rates or with several channels are resampled on the GPU.' if args.resample
+        print('Disabling ffmpeg. WAV (PCM, float, G.711, IMA and Microsoft ADPCM), FLAC, AIFF, AU, CAF, Wave64 and RF64 files are read directly. '
+              + ('Files at other rates or with several channels are resampled on the GPU.' if args.resample
                                       else 'Make sure your audio files are already sampled at 16kHz.'))
     inputs = []
     for pat in args.input:

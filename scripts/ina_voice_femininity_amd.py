@@ -24,8 +24,8 @@ def build_parser():
     ap.add_argument('-i', '--input', nargs='+', required=True, help='media paths or glob patterns')
     ap.add_argument('-o', '--output', required=True, help='TSV file receiving path, score, speech_duration, nb_vectors')
     ap.add_argument('-c', '--criteria', choices=['bgc', 'vfp'], default='bgc', help='gender detection model criteria')
-    ap.add_argument('-b', '--ffmpeg_binary', default='ffmpeg', help="ffmpeg binary; 'None' reads 16 kHz mono WAV, FLAC, G.711 / IMA ADPCM WAV, AIFF, AU, CAF, Wave64 and RF64 directly "
-                                                                      "(FLAC and IMA ADPCM decoded on the GPU)")
+    ap.add_argument('-b', '--ffmpeg_binary', default='ffmpeg', help="ffmpeg binary; 'None' reads 16 kHz mono WAV, FLAC, G.711 / IMA ADPCM / Microsoft ADPCM WAV, AIFF, AU, CAF, Wave64 and RF64 directly "
+                                                                      "(FLAC, IMA and Microsoft ADPCM decoded on the GPU)")
     ap.add_argument('--batch_seconds', type=float, default=3600, help='audio held on the device per batch (seconds)')
     ap.add_argument('--models', default=None, help="'synthetic' = seeded stand-in weights")
     ap.add_argument('--resample', action='store_true',
@@ -52,7 +52,8 @@ def main(argv=None):
     if args.channels == 'split' and ffmpeg is not None:
         build_parser().error('--channels split needs -b None (ffmpeg downmixes every file)')
     if ffmpeg is None:
-        print('Disabling ffmpeg. ' + ('WAV files at other rates or with several channels are resampled on the GPU.' if args.resample
+        print('Disabling ffmpeg. WAV (PCM, float, G.711, IMA and Microsoft ADPCM), FLAC, AIFF, AU, CAF, Wave64 and RF64 files are read directly. '
+              + ('Files at other rates or with several channels are resampled on the GPU.' if args.resample
                                       else 'Make sure your audio files are already sampled at 16kHz.'))
     inputs = expand_inputs(args.input)
     assert len(inputs) > 0, 'No media selected for analysis! Bad values provided to -i (%s)' % args.input
