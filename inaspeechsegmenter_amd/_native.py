@@ -43,6 +43,10 @@ FLAC_TO_SIGNAL, FLAC_TO_STAGE = 0, 1
 WINDOW = np.dtype([('s_begin', '<i8'), ('s_end', '<i8'), ('frames_total', '<i8'), ('out_begin', '<i8'), ('out_count', '<i8')])
 # iss_split (include/iss.h): the row beside a job row of the *_split entry points
 SPLIT = np.dtype([('dst_stride', '<i8'), ('sel_begin', '<i4'), ('sel_count', '<i4')])
+# iss_mixset / iss_mix / iss_mix_term (include/iss.h): the row beside a job row of the *_mix entry points, and the call's two tables
+MIXSET = np.dtype([('dst_stride', '<i8'), ('mix_begin', '<i4'), ('mix_count', '<i4')])
+MIX = np.dtype([('term_begin', '<i4'), ('term_count', '<i4'), ('divisor', '<f8')])
+MIX_TERM = np.dtype([('channel', '<i4'), ('reserved', '<i4'), ('weight', '<f8')])
 # ISS_FLAC_* frame status codes -> reason
 FLAC_STATUS = {1: 'reserved subframe type', 2: 'subframe header padding bit set', 3: 'wasted bits exceed the sample size',
                4: 'reserved residual coding method', 5: 'residual partition order does not fit the block',
@@ -77,6 +81,26 @@ def _split_rows(splits, njobs):
     if rows.size != njobs:
         raise ValueError(f'{rows.size} splits for {njobs} jobs')
     return rows, sel
+
+
+def _mix_rows(mixes, njobs):
+    """(MIXSET rows, MIX rows, MIX_TERM rows) for a *_mix entry point from one `(dst_stride, [mix, ...])` or None (downmix) per
+    job, a mix being a resample.Mix or a channel index (that channel alone); a triple of arrays is handed on as given."""
+    if isinstance(mixes, tuple) and len(mixes) == 3 and isinstance(mixes[0], np.ndarray):
+        sets, rows, terms = (np.ascontiguousarray(a, dtype=dt).reshape(-1) for a, dt in zip(mixes, (MIXSET, MIX, MIX_TERM)))
+    else:
+        sets, rows, terms = np.zeros(len(mixes), dtype=MIXSET), [], []
+        for k, ms in enumerate(mixes):
+            if ms is not None:
+                sets[k] = (int(ms[0]), len(rows), len(ms[1]))
+                for m in ms[1]:
+                    t, d = (((m, 1.0),), 1.0) if isinstance(m, (int, np.integer)) else (m.terms, m.divisor)
+                    rows.append((len(terms), len(t), float(d)))
+                    terms.extend((int(ch), 0, float(w)) for ch, w in t)
+        rows, terms = np.array(rows, dtype=MIX).reshape(-1), np.array(terms, dtype=MIX_TERM).reshape(-1)
+    if sets.size != njobs:
+        raise ValueError(f'{sets.size} mix sets for {njobs} jobs')
+    return sets, rows, terms
 
 
 _lib = None
@@ -130,6 +154,10 @@ def lib():
         'iss_adpcm_decode_windows_split': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64]),
         'iss_msadpcm_decode_windows_split': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64]),
         'iss_resample_split_geometry': (C.c_int, [vp, i32, i32, pi32, pi32]),
+        'iss_resample_pcm16_mix': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, vp, vp, i64, vp, i64]),
+        'iss_flac_decode_mix': (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i32, i64, pi32, vp, vp, i64, vp, i64]),
+        'iss_adpcm_decode_mix': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64, vp, i64]),
+        'iss_msadpcm_decode_mix': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64, vp, i64]),
         'iss_get_signal_pcm16': (C.c_int, [vp, pi16, i64, i64]),
         'iss_resample_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_flac_index': (C.c_int, [vp, i64, i64, vp, vp, i64, pi64, pi64, C.c_char_p, i32]),
@@ -417,25 +445,38 @@ class Context:
         return (src_offset, n, 1 if x.ndim == 1 else x.shape[1], RS_FORMAT[x.dtype] if fmt is None else int(fmt), fid, 0,
                 dst_offset, -(-n * up // down))
 
-    def resample(self, src, jobs, n_signal=-1, windows=None, splits=None):
+    def resample(self, src, jobs, n_signal=-1, windows=None, splits=None, mixes=None):
         """iss_resample_pcm16: src = 1-D uint8 array of the stored samples of every job, jobs = rows of RS_JOB; one H2D copy,
         one launch.  n_signal >= 0: a new resident signal of that many samples; < 0: into the signal of the last set_signal.
         windows: rows of WINDOW, one beside every job (iss_resample_pcm16_windows): src holds frames [s_begin, s_end) of each
         file, and the outputs [out_begin, out_begin + out_count) are written.
         splits: `(dst_stride, [channels])` or None per job (iss_resample_pcm16_split): the selected channels of a job are written
         apart, channel k of the selection at dst_offset + k * dst_stride; None downmixes as ever.  With windows
-        (iss_resample_pcm16_windows_split): the window's outputs of each selected channel, dst_stride >= out_count."""
+        (iss_resample_pcm16_windows_split): the window's outputs of each selected channel, dst_stride >= out_count.
+        mixes (not with splits): `(dst_stride, [mix, ...])` or None per job (iss_resample_pcm16_mix, with or without windows): mix
+        k of a job -- a resample.Mix, or a channel index for that channel alone -- is written at dst_offset + k * dst_stride;
+        None downmixes as ever."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=RS_JOB))
         self._decode_call('iss_resample_pcm16', (C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data)),
-                          (jb.size, int(n_signal)), windows, splits)
+                          (jb.size, int(n_signal)), windows, splits, mixes)
         self._keep_rs = src         # the async H2D copy reads it until the next sync
 
-    def _decode_call(self, base, lead, trail, windows, splits):
-        """One of the four entry points of `base`: base(ctx, *lead, *trail), or base_windows with the WINDOW rows between
+    def _decode_call(self, base, lead, trail, windows, splits, mixes=None):
+        """One of the five entry points of `base`: base(ctx, *lead, *trail), or base_windows with the WINDOW rows between
         `lead` (which ends with the job rows) and `trail` (which begins with their count), or base_split with the SPLIT rows,
-        the channel table and its length behind `trail`, or base_windows_split with both."""
+        the channel table and its length behind `trail`, or base_windows_split with both; or base_mix with the WINDOW rows or
+        NULL between `lead` and `trail` and the three mix tables behind `trail`."""
         name, args = base, lead + trail
+        if mixes is not None:
+            if splits is not None:
+                raise ValueError('a call carries splits or mixes, not both')
+            wn = None if windows is None else _window_rows(windows, trail[0])
+            sets, rows, terms = _mix_rows(mixes, trail[0])
+            args = lead + (None if wn is None else C.c_void_p(wn.ctypes.data),) + trail + (
+                C.c_void_p(sets.ctypes.data), C.c_void_p(rows.ctypes.data), rows.size, C.c_void_p(terms.ctypes.data), terms.size)
+            self._ck(getattr(self._L, base + '_mix')(self._h, *args), base + '_mix')
+            return
         if windows is not None:
             wn = _window_rows(windows, trail[0])
             name, args = base + '_windows', lead + (C.c_void_p(wn.ctypes.data),) + trail
@@ -490,20 +531,21 @@ class Context:
         return st
 
     # ---- FLAC decoder (iss_flac_*): compressed frames -> resident signal (PCM16), staging buffer, or resampled
-    def flac_decode(self, src, frames, jobs, n_signal=-1, windows=None, splits=None):
+    def flac_decode(self, src, frames, jobs, n_signal=-1, windows=None, splits=None, mixes=None):
         """iss_flac_decode: src = 1-D uint8 array of the compressed bytes of every job, frames = FLAC_FRAME rows, jobs = rows
         of FLAC_JOB; one H2D copy, one decode launch (+ one resample launch).  -> the per-frame status array (page-locked,
         this context's): valid after the next synchronising call (get_loge, flac_get_stage, synchronize).
         windows: rows of WINDOW, one beside every job (iss_flac_decode_windows): each job's rows are a run of its file's frames
         that covers [s_begin, s_end), and only those samples are produced.
-        splits: as for `resample` (iss_flac_decode_split), for TO_STAGE jobs with a filter; None for every other job."""
+        splits: as for `resample` (iss_flac_decode_split), for TO_STAGE jobs with a filter; None for every other job.
+        mixes: as for `resample` (iss_flac_decode_mix), for the same jobs."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         fr = np.ascontiguousarray(frames, dtype=FLAC_FRAME)
         jb = np.ascontiguousarray(np.array(jobs, dtype=FLAC_JOB).reshape(-1))
         st = self._status('_flac_status', len(fr))
         self._decode_call('iss_flac_decode', (C.c_void_p(src.ctypes.data), src.size, C.c_void_p(fr.ctypes.data), len(fr),
                                               C.c_void_p(jb.ctypes.data)), (jb.size, int(n_signal), _ptr(st, C.c_int32)),
-                          windows, splits)
+                          windows, splits, mixes)
         self._keep_flac = (src, fr)    # the async H2D copy reads them until the next sync
         return st[:len(fr)]
 
@@ -516,23 +558,24 @@ class Context:
         return self._counters('iss_flac_stats')
 
     # ---- IMA ADPCM decoder (iss_adpcm_*): stored blocks -> resident signal (PCM16), staging buffer, or resampled
-    def adpcm_decode(self, src, jobs, nblocks, n_signal=-1, windows=None, splits=None):
+    def adpcm_decode(self, src, jobs, nblocks, n_signal=-1, windows=None, splits=None, mixes=None):
         """iss_adpcm_decode: src = 1-D uint8 array of the blocks of every job, jobs = rows of ADPCM_JOB, nblocks = their
         sum; one H2D copy, one decode launch (+ one resample launch).  -> the per-block status array (page-locked, this
         context's): valid after the next synchronising call (get_loge, adpcm_get_stage, synchronize).
         windows: rows of WINDOW, one beside every job (iss_adpcm_decode_windows): each job holds exactly the blocks that its
         samples [s_begin, s_end) lie in, and only those samples are produced.
-        splits: as for `resample` (iss_adpcm_decode_split), for TO_STAGE jobs with a filter; None for every other job."""
-        return self._block_decode('adpcm', src, jobs, nblocks, n_signal, windows, splits)
+        splits: as for `resample` (iss_adpcm_decode_split), for TO_STAGE jobs with a filter; None for every other job.
+        mixes: as for `resample` (iss_adpcm_decode_mix), for the same jobs."""
+        return self._block_decode('adpcm', src, jobs, nblocks, n_signal, windows, splits, mixes)
 
-    def _block_decode(self, coder, src, jobs, nblocks, n_signal, windows, splits):
+    def _block_decode(self, coder, src, jobs, nblocks, n_signal, windows, splits, mixes=None):
         """iss_<coder>_decode.  Status array and kept source bytes are the coder's own: a pass launches both coders before it
         reads either's status."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=ADPCM_JOB).reshape(-1))
         st = self._status(f'_{coder}_status', nblocks)
         self._decode_call(f'iss_{coder}_decode', (C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data)),
-                          (jb.size, int(nblocks), int(n_signal), _ptr(st, C.c_int32)), windows, splits)
+                          (jb.size, int(nblocks), int(n_signal), _ptr(st, C.c_int32)), windows, splits, mixes)
         setattr(self, f'_keep_{coder}', src)         # the async H2D copy reads it until the next sync
         return st[:int(nblocks)]
 
@@ -545,9 +588,9 @@ class Context:
         return self._counters('iss_adpcm_stats')
 
     # ---- Microsoft ADPCM decoder (iss_msadpcm_*): the IMA decoder's rows and contracts, state of its own
-    def msadpcm_decode(self, src, jobs, nblocks, n_signal=-1, windows=None, splits=None):
+    def msadpcm_decode(self, src, jobs, nblocks, n_signal=-1, windows=None, splits=None, mixes=None):
         """iss_msadpcm_decode: as adpcm_decode, for Microsoft ADPCM blocks (status ISS_ADPCM_PREDICTOR for a bad block)."""
-        return self._block_decode('msadpcm', src, jobs, nblocks, n_signal, windows, splits)
+        return self._block_decode('msadpcm', src, jobs, nblocks, n_signal, windows, splits, mixes)
 
     def msadpcm_get_stage(self, job, frames_total, channels):
         """PCM16 samples of staged job `job` of the last msadpcm_decode: (n,) or (n, channels) int16."""

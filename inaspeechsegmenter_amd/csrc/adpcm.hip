@@ -202,20 +202,21 @@ extern "C" int iss_msadpcm_decode_host(const uint8_t* buf, int64_t len, int64_t 
     return decode_host(CODER_MS, buf, len, nblocks, channels, block_align, frames_total, out, status_out);
 }
 
-// the four entry points of a coder: windows beside the jobs, splits (with their selection table) beside the jobs, both, or
-// neither.  Each coder has its own IssCodec: a pass that holds files of both makes two calls, and the second must not take the
+// the five entry points of a coder: windows beside the jobs, splits (with their selection table) beside the jobs, both, or
+// neither; or the mix tables `mix` (with or without windows).  Each coder has its own IssCodec: a pass that holds files of both makes two calls, and the second must not take the
 // status and staging buffers the first has not been read from yet.
 static int adpcm_decode(iss_ctx* c, int coder, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, const iss_window* windows,
                         int32_t njobs, int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_split* splits,
-                        const int32_t* channel_sel, int64_t nsel) {
+                        const int32_t* channel_sel, int64_t nsel, const IssMixTables* mix = nullptr) {
     const char* who = coder == CODER_IMA ? "iss_adpcm_decode" : "iss_msadpcm_decode";
-    if (!c || njobs < 0 || (njobs > 0 && (!jobs || !status_out)) || src_bytes < 0 || (!src && src_bytes > 0) || nblocks_total < 0)
+    if (!c || njobs < 0 || (njobs > 0 && (!jobs || !status_out)) || src_bytes < 0 || (!src && src_bytes > 0) || nblocks_total < 0 ||
+        (mix && njobs > 0 && !mix->sets))
         return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
     IssCodec& dec = coder == CODER_IMA ? c->adpcm : c->msadpcm;
     IssDecodePass pass;
     int rc = pass.begin(c, who, n_signal, njobs);
     if (rc) return rc;
-    pass.jsplits = splits; pass.sel = channel_sel; pass.nsel = nsel;
+    pass.jsplits = splits; pass.sel = channel_sel; pass.nsel = nsel; pass.jmix = mix;
     // one table: the job rows, then (windowed) their AdWinDev
     std::vector<uint8_t> table((size_t)njobs * (sizeof(AdJobDev) + (windows ? sizeof(AdWinDev) : 0)));
     AdJobDev* dev = reinterpret_cast<AdJobDev*>(table.data());
@@ -306,6 +307,14 @@ extern "C" int iss_adpcm_decode_windows_split(iss_ctx* c, const void* src, int64
     return adpcm_decode(c, CODER_IMA, src, src_bytes, jobs, windows, njobs, nblocks_total, n_signal, status_out, splits, channel_sel, nsel);
 }
 
+extern "C" int iss_adpcm_decode_mix(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, const iss_window* windows,
+                                    int32_t njobs, int64_t nblocks_total, int64_t n_signal, int32_t* status_out,
+                                    const iss_mixset* mixsets, const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms,
+                                    int64_t nterms) {
+    const IssMixTables mix{mixsets, mixes, nmixes, terms, nterms};
+    return adpcm_decode(c, CODER_IMA, src, src_bytes, jobs, windows, njobs, nblocks_total, n_signal, status_out, nullptr, nullptr, 0, &mix);
+}
+
 extern "C" int iss_adpcm_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {
     return c ? iss_codec_get_stage(c, c->adpcm, job, out, bytes) : iss_fail(c, ISS_EINVAL, "iss_adpcm_get_stage: bad argument");
 }
@@ -314,7 +323,7 @@ extern "C" int iss_adpcm_stats(iss_ctx* c, int64_t* launches, int64_t* blocks) {
     return iss_get_counters(c ? &c->adpcm.count : nullptr, launches, blocks);
 }
 
-// the same seven for Microsoft ADPCM: its own codec state, the same rows
+// the same eight for Microsoft ADPCM: its own codec state, the same rows
 extern "C" int iss_msadpcm_decode_windows(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs,
                                         const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
                                         int32_t* status_out) {
@@ -337,6 +346,14 @@ extern "C" int iss_msadpcm_decode_windows_split(iss_ctx* c, const void* src, int
                                               int32_t* status_out, const iss_split* splits, const int32_t* channel_sel,
                                               int64_t nsel) {
     return adpcm_decode(c, CODER_MS, src, src_bytes, jobs, windows, njobs, nblocks_total, n_signal, status_out, splits, channel_sel, nsel);
+}
+
+extern "C" int iss_msadpcm_decode_mix(iss_ctx* c, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, const iss_window* windows,
+                                      int32_t njobs, int64_t nblocks_total, int64_t n_signal, int32_t* status_out,
+                                      const iss_mixset* mixsets, const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms,
+                                      int64_t nterms) {
+    const IssMixTables mix{mixsets, mixes, nmixes, terms, nterms};
+    return adpcm_decode(c, CODER_MS, src, src_bytes, jobs, windows, njobs, nblocks_total, n_signal, status_out, nullptr, nullptr, 0, &mix);
 }
 
 extern "C" int iss_msadpcm_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {

@@ -31,6 +31,10 @@ int IssDecodePass::place(int32_t j, const IssJobDst& d, int64_t frames_total, in
     if (jsplits) split = true;
     if (sp.sel_count != 0 && !(d.output == ISS_FLAC_TO_STAGE && d.filter >= 0))
         return iss_fail(c, ISS_EINVAL, "%s: job %d: a channel selection needs a TO_STAGE job with a filter", who, j);
+    const iss_mixset nomix{0, 0, 0};
+    const iss_mixset& ms = jmix ? jmix->sets[j] : nomix;
+    if (ms.mix_count != 0 && !(d.output == ISS_FLAC_TO_STAGE && d.filter >= 0))
+        return iss_fail(c, ISS_EINVAL, "%s: job %d: mixes need a TO_STAGE job with a filter", who, j);
     if (d.output == ISS_FLAC_TO_SIGNAL) {
         if (!signal_ok) return iss_fail(c, ISS_EINVAL, "%s: job %d: only %s sources go to the signal", who, j, only);
         if (d.dst_offset < 0 || d.dst_offset > nsig - frames_total)
@@ -52,6 +56,7 @@ int IssDecodePass::place(int32_t j, const IssJobDst& d, int64_t frames_total, in
             rjobs.push_back(r);
             rwins.push_back(full);
             rsplits.push_back(sp);
+            rmixsets.push_back(ms);
         }
     } else {
         return iss_fail(c, ISS_EINVAL, "%s: job %d: bad output %d", who, j, d.output);
@@ -60,8 +65,10 @@ int IssDecodePass::place(int32_t j, const IssJobDst& d, int64_t frames_total, in
 }
 
 int IssDecodePass::commit(IssCodec* dec) {
+    IssMixTables rmix{};                                   // the caller's mix and term rows, the sets beside rjobs
+    if (jmix) { rmix = *jmix; rmix.sets = rmixsets.data(); }
     int rc = iss_resample_plan(c, rjobs.data(), windowed ? rwins.data() : nullptr, (int32_t)rjobs.size(), stage, nsig, ranges,
-                               who, plan, split ? rsplits.data() : nullptr, sel, nsel);
+                               who, plan, split ? rsplits.data() : nullptr, sel, nsel, jmix ? &rmix : nullptr);
     if (rc) return rc;
     if (n_signal >= 0) {                                   // a signal of its own, zero wherever no job writes
         if ((rc = iss_reserve(c, c->sig, (size_t)nsig * 2 + 16))) return rc;

@@ -22,6 +22,8 @@ struct IssDecodePass {
     bool split = false;                                       // ... and to the planner only when the call has splits,
     const int32_t* sel = nullptr;                             // with the caller's channel selection table
     int64_t nsel = 0;
+    const IssMixTables* jmix = nullptr;                       // a mix entry point's tables, `sets` one per JOB (NULL: not one) ...
+    std::vector<iss_mixset> rmixsets;                         // ... the sets handed on beside rjobs (no mixes for a job without any)
     std::vector<int64_t> stage_off, stage_bytes;              // per job (-1: not staged)
     int64_t stage = 0;                                        // bytes those rows read from: the staging buffer so far
     IssRsPlan plan;
@@ -34,6 +36,7 @@ struct IssDecodePass {
     // `w` (NULL: the whole file): the job produces samples [s_begin, s_end) only, and that many are placed; dst_byte is where
     // sample s_begin goes.  Checked here: the window lies inside the file and states the job's frames_total.
     // A job's split (jsplits) goes to its resample row; a selection on a job without one (TO_SIGNAL, or no filter) is refused.
+    // Likewise a job's mix set (jmix).
     int place(int32_t j, const IssJobDst& d, int64_t frames_total, int32_t channels, int esz, bool signal_ok, const char* only,
               bool& to_sig, int64_t& dst_byte, const iss_window* w = nullptr);
     // Plans rjobs against the recorded ranges, then changes the context: a zeroed signal of its own for n_signal >= 0, features

@@ -527,17 +527,18 @@ extern "C" int iss_flac_decode_host(const uint8_t* buf, int64_t len, const iss_f
     return ISS_OK;
 }
 
-// the four entry points: windows beside the jobs, splits (with their selection table) beside the jobs, both, or neither
+// the five entry points: windows beside the jobs, splits (with their selection table) beside the jobs, both, or neither; or
+// the mix tables `mix` (with or without windows)
 static int flac_decode(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
                        const iss_flac_job* jobs, const iss_window* windows, int32_t njobs, int64_t n_signal, int32_t* status_out,
-                       const iss_split* splits, const int32_t* channel_sel, int64_t nsel) {
+                       const iss_split* splits, const int32_t* channel_sel, int64_t nsel, const IssMixTables* mix = nullptr) {
     if (!c || njobs < 0 || (njobs > 0 && (!jobs || !frames || !status_out)) || src_bytes < 0 || (!src && src_bytes > 0) ||
-        nframes < 0)
+        nframes < 0 || (mix && njobs > 0 && !mix->sets))
         return iss_fail(c, ISS_EINVAL, "iss_flac_decode: bad argument");
     IssDecodePass pass;
     int rc = pass.begin(c, "iss_flac_decode", n_signal, njobs);
     if (rc) return rc;
-    pass.jsplits = splits; pass.sel = channel_sel; pass.nsel = nsel;
+    pass.jsplits = splits; pass.sel = channel_sel; pass.nsel = nsel; pass.jmix = mix;
     // one table: the frame rows, then (windowed) their FlacWinDev
     std::vector<uint8_t> table((size_t)nframes * (sizeof(FlacFrameDev) + (windows ? sizeof(FlacWinDev) : 0)));
     FlacFrameDev* dev = reinterpret_cast<FlacFrameDev*>(table.data());
@@ -623,6 +624,14 @@ extern "C" int iss_flac_decode_windows_split(iss_ctx* c, const void* src, int64_
                                              int64_t n_signal, int32_t* status_out, const iss_split* splits,
                                              const int32_t* channel_sel, int64_t nsel) {
     return flac_decode(c, src, src_bytes, frames, nframes, jobs, windows, njobs, n_signal, status_out, splits, channel_sel, nsel);
+}
+
+extern "C" int iss_flac_decode_mix(iss_ctx* c, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
+                                   const iss_flac_job* jobs, const iss_window* windows, int32_t njobs, int64_t n_signal,
+                                   int32_t* status_out, const iss_mixset* mixsets, const iss_mix* mixes, int64_t nmixes,
+                                   const iss_mix_term* terms, int64_t nterms) {
+    const IssMixTables mix{mixsets, mixes, nmixes, terms, nterms};
+    return flac_decode(c, src, src_bytes, frames, nframes, jobs, windows, njobs, n_signal, status_out, nullptr, nullptr, 0, &mix);
 }
 
 extern "C" int iss_flac_get_stage(iss_ctx* c, int32_t job, void* out, int64_t bytes) {

@@ -209,18 +209,32 @@ struct RsWinDev { int64_t in_begin, frames_total, out_begin, out_end; };   // be
 // beside RsJobDev k of a split call: sel_count selected channels (rows [sel_begin, +sel_count) of the selection table; 0: downmix),
 // `group` of them per workgroup at `stride` float64 apart in LDS, each over `ntiles` tiles; ident: the selection is 0, 1, 2, ...
 struct RsSplitDev { int64_t dst_stride, ntiles; int32_t sel_begin, sel_count, group, stride, ident, pad; };
+// beside RsJobDev k of a mix call: mix_count mixes (0: downmix), `group` of them per workgroup at `stride` float64 apart in LDS,
+// each over `ntiles` tiles; the job's mixes are rows [mix_begin, +mix_count) of the 16-byte rows that follow the mix-set table:
+// first the call's RsMixRow, then its RsTermDev, a mix's term_begin counted from the first of those rows
+struct RsMixDev { int64_t dst_stride, ntiles; int32_t mix_begin, mix_count, group, stride; };
+struct RsMixRow { int32_t term_begin, term_count; double divisor; };
+struct RsTermDev { int32_t channel, pad; double weight; };
+static_assert(sizeof(RsMixRow) == 16 && sizeof(RsTermDev) == 16, "one array of 16-byte rows");
+// the three tables of a *_mix entry point (include/iss.h); `sets` one per job
+struct IssMixTables { const iss_mixset* sets; const iss_mix* mixes; int64_t nmixes; const iss_mix_term* terms; int64_t nterms; };
 struct IssRsPlan {
     std::vector<RsJobDev> dj;
     std::vector<RsWinDev> dw;             // empty: no windows, the launch every call made before there were any
     std::vector<RsSplitDev> ds;           // empty: no splits, likewise
     std::vector<int32_t> sel;             // the channel selections the rows of ds point into
+    std::vector<RsMixDev> dm;             // empty: no mixes, likewise
+    std::vector<RsMixRow> mixes;          // the mix rows the rows of dm point into ...
+    std::vector<RsTermDev> terms;         // ... and the term rows those point into
     int64_t tiles = 0, lds = 0;
 };
 // `ranges`: destination ranges of other writers of the same call, checked for overlap with the jobs' (error texts start with `who`)
-// `wins`: NULL, or a window beside every job (include/iss.h);  `splits`: NULL, or a split beside every job, into sel[0, nsel)
+// `wins`: NULL, or a window beside every job (include/iss.h);  `splits`: NULL, or a split beside every job, into sel[0, nsel);
+// `mix`: NULL, or the tables of a mix call with a mix set beside every job (never together with `splits`)
 int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes, int64_t nsig,
                       std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan,
-                      const iss_split* splits = nullptr, const int32_t* sel = nullptr, int64_t nsel = 0);
+                      const iss_split* splits = nullptr, const int32_t* sel = nullptr, int64_t nsel = 0,
+                      const IssMixTables* mix = nullptr);
 int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& plan);
 
 // implemented in the .hip files

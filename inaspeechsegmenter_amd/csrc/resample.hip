@@ -31,8 +31,16 @@
 // both rows beside every job.  The workgroup takes (channel group, tile) from its block index as a split does, lays the tile
 // over [out_begin, out_end) as a window does, and stages its group's channels by the window's rule: the file's own frame
 // indices, read at in_begin less, 0 outside [0, frames_total).  Table: job rows, window rows, split rows, channel selections.
+//
+// Mixes (include/iss.h, iss_mixset): MIX = true is two more pairs, plain and windowed, for calls that carry a mix-set row beside
+// every job.  A staged row is a linear combination of channels instead of one channel: the workgroup takes (mix group, tile)
+// from its block index as a split takes (channel group, tile), stages span[q][.] = (w_0 x[., c_0] + w_1 x[., c_1] + ...) / d for
+// the mixes q of its group ((frame, mix) flattened over the threads, the terms in order, every product, sum and the one
+// division rounded on its own) and runs step 3 once per mix.  Geometry is split_geometry's for mix_count rows; a job without
+// mixes (mix_count 0) is the downmix above, in the same launch.  Table: job rows, (window rows,) mix-set rows, mix rows, terms.
 #include "decode_pass.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 namespace {
@@ -145,14 +153,49 @@ __device__ __forceinline__ void stage_channels(const uint8_t* __restrict__ src, 
     }
 }
 
-// what a workgroup of a SPLIT launch stages: the downmix (gc == 0), or channels [c0, c0 + gc) of its job's selection
-struct RsGroup { int64_t dst_stride; int stride, c0, gc; const int32_t* sel; };
+// frames s0 .. s0+len-1 of `gm` mixes: span[q * stride + .] = mix q of `mixes`, its terms rows of `rows` (include/iss.h states
+// the arithmetic).  Thread e takes (frame e / gm, mix e % gm); WIN: stage_span's rule.  A frame outside the file is 0, not 0 / d
+template <typename L, bool WIN>
+__device__ __forceinline__ void stage_mixes(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
+                                            double* __restrict__ span, int stride, int gm, const RsMixRow* __restrict__ mixes,
+                                            const RsTermDev* __restrict__ rows, const RsWinDev& W) {
+    using T = typename L::type;
+    const T* p = reinterpret_cast<const T*>(src);
+    const int total = len * gm;
+    for (int e = threadIdx.x; e < total; e += RS_THREADS) {
+        const int k = e / gm, q = e - k * gm;
+        int64_t j = s0 + k;
+        double v = 0.0;
+        bool in = j >= 0 && j < n_in;
+        if constexpr (WIN) {
+            in = j >= 0 && j < W.frames_total;
+            j -= W.in_begin;
+            in = in && j >= 0 && j < n_in;                 // (the planner saw to it that a window reaches no unstaged frame)
+        }
+        if (in) {
+            const T* f = p + j * ch;
+            const RsMixRow M = mixes[q];
+            const RsTermDev* t = rows + M.term_begin;
+            v = __dmul_rn(t[0].weight, L::get(f + t[0].channel));
+            for (int n = 1; n < M.term_count; ++n) v = __dadd_rn(v, __dmul_rn(t[n].weight, L::get(f + t[n].channel)));
+            v = __ddiv_rn(v, M.divisor);
+        }
+        span[(int64_t)q * stride + k] = v;
+    }
+}
 
-template <typename L, bool WIN, bool SPLIT>
+// what a workgroup of a SPLIT launch stages: the downmix (gc == 0), or channels [c0, c0 + gc) of its job's selection;
+// of a MIX launch: the downmix, or the gc mixes from `mix` on (rows of the 16-byte table `rows`, which holds their terms too)
+struct RsGroup { int64_t dst_stride; int stride, c0, gc; const int32_t* sel; const RsMixRow* mix; const RsTermDev* rows; };
+
+template <typename L, bool WIN, bool SPLIT, bool MIX>
 __device__ __forceinline__ void stage(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
                                       double* __restrict__ span, const RsWinDev& W, const RsGroup& G) {
     if constexpr (SPLIT) {
         if (G.gc > 0) { stage_channels<L, WIN>(src, n_in, ch, s0, len, span, G.stride, G.c0, G.gc, G.sel, W); return; }
+    }
+    if constexpr (MIX) {
+        if (G.gc > 0) { stage_mixes<L, WIN>(src, n_in, ch, s0, len, span, G.stride, G.gc, G.mix, G.rows, W); return; }
     }
     stage_span<L, WIN>(src, n_in, ch, s0, len, span, W);
 }
@@ -178,11 +221,12 @@ __device__ __forceinline__ void compute_tile(const RsJobDev& J, const double* __
 // EXT = false: the five little-endian WAV formats only, the instantiation every call without a newer format launches (its
 // switch, and so its code, is what it was before the newer formats existed); EXT = true adds them behind the default case.
 // SPLIT = false is the kernel every call without splits launches; SPLIT = true reads the split table and the channel selections
-// that follow the rows.
-#define RS_STAGE(L) stage<L, WIN, SPLIT>(s, J.n_in, J.ch, s0, len, span, W, G)
-template <bool EXT, bool WIN, bool SPLIT>
+// that follow the rows.  MIX = true (never with SPLIT) reads the mix-set table and the mix and term rows that follow it.
+#define RS_STAGE(L) stage<L, WIN, SPLIT, MIX>(s, J.n_in, J.ch, s0, len, span, W, G)
+template <bool EXT, bool WIN, bool SPLIT, bool MIX = false>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __restrict__ src, const RsJobDev* __restrict__ jobs,
                                                               int njobs, int16_t* __restrict__ dst) {
+    static_assert(!(SPLIT && MIX), "a call carries split rows or mix-set rows");
     extern __shared__ __attribute__((aligned(16))) double rs_smem[];
     const int64_t b = blockIdx.x;
     int lo = 0, hi = njobs - 1;                                             // last job whose tile_base <= b
@@ -206,6 +250,20 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __r
             t -= g * S.ntiles;
             G.dst_stride = S.dst_stride; G.stride = S.stride; G.c0 = g * S.group; G.gc = min(S.group, S.sel_count - G.c0);
             G.sel = S.ident ? nullptr : sels + S.sel_begin + G.c0;
+            dst += (int64_t)G.c0 * S.dst_stride;
+        }
+    }
+    if constexpr (MIX) {
+        const void* after = jobs + njobs;                                            // the mix-set table follows the job table
+        if constexpr (WIN) after = reinterpret_cast<const RsWinDev*>(after) + njobs;      // (WIN: ... follows the window table),
+        const RsMixDev* sets = reinterpret_cast<const RsMixDev*>(after);
+        const RsMixRow* rows = reinterpret_cast<const RsMixRow*>(sets + njobs);          // the mix rows and the term rows follow that
+        const RsMixDev S = sets[lo];
+        if (S.mix_count > 0) {
+            const int g = (int)(t / S.ntiles);
+            t -= g * S.ntiles;
+            G.dst_stride = S.dst_stride; G.stride = S.stride; G.c0 = g * S.group; G.gc = min(S.group, S.mix_count - G.c0);
+            G.mix = rows + S.mix_begin + G.c0; G.rows = reinterpret_cast<const RsTermDev*>(rows);
             dst += (int64_t)G.c0 * S.dst_stride;
         }
     }
@@ -242,8 +300,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __r
             break;
     }
     __syncthreads();
-    if constexpr (SPLIT) {
-        if (G.gc > 0) {                                                     // one pass of step 3 per channel of the group
+    if constexpr (SPLIT || MIX) {
+        if (G.gc > 0) {                                                     // one pass of step 3 per channel (mix) of the group
             for (int k = 0; k < G.gc; ++k, span += G.stride, dst += G.dst_stride) {
                 if (J.lds_tab) compute_tile(J, rs_smem, span, s0, i0, i_end, dst);
                 else           compute_tile(J, J.taps, span, s0, i0, i_end, dst);
@@ -308,13 +366,27 @@ static int64_t floor_div_host(int64_t a, int64_t b) { return a >= 0 ? a / b : -(
 
 int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes,
                       int64_t nsig, std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan,
-                      const iss_split* splits, const int32_t* sel, int64_t nsel) {
+                      const iss_split* splits, const int32_t* sel, int64_t nsel, const IssMixTables* mix) {
     // validate every job, build the device descriptors and the tile prefix sum
     std::vector<RsJobDev>& dj = plan.dj;
     dj.assign((size_t)njobs, RsJobDev{});
     plan.dw.assign(wins ? (size_t)njobs : 0, RsWinDev{});
     plan.ds.assign(splits ? (size_t)njobs : 0, RsSplitDev{});
     plan.sel.clear();
+    plan.dm.assign(mix ? (size_t)njobs : 0, RsMixDev{});
+    plan.mixes.clear();
+    plan.terms.clear();
+    if (mix && (splits || (njobs > 0 && !mix->sets) || mix->nmixes < 0 || mix->nmixes > 0x3fffffffLL || (mix->nmixes > 0 && !mix->mixes) ||
+                mix->nterms < 0 || mix->nterms > 0x3fffffffLL || (mix->nterms > 0 && !mix->terms)))
+        return iss_fail(c, ISS_EINVAL, "%s: bad mix tables", who);
+    if (mix) {                                             // the device's rows: the mixes, then the terms they count from there
+        plan.mixes.resize((size_t)mix->nmixes);
+        plan.terms.resize((size_t)mix->nterms);
+        for (int64_t q = 0; q < mix->nmixes; ++q)
+            plan.mixes[(size_t)q] = RsMixRow{(int32_t)((int64_t)mix->mixes[q].term_begin + mix->nmixes), mix->mixes[q].term_count,
+                                             mix->mixes[q].divisor};      // (a row of no job is never read, nor checked)
+        for (int64_t q = 0; q < mix->nterms; ++q) plan.terms[(size_t)q] = RsTermDev{mix->terms[q].channel, 0, mix->terms[q].weight};
+    }
     if (splits && (nsel < 0 || nsel > 0x7fffffffLL || (nsel > 0 && !sel)))
         return iss_fail(c, ISS_EINVAL, "%s: a bad channel selection table", who);
     if (splits) plan.sel.assign(sel, sel + nsel);
@@ -398,6 +470,43 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
             groups = (sp.sel_count + group - 1) / group;
             plan.ds[(size_t)k] = RsSplitDev{sp.dst_stride, (nout + tile - 1) / tile, sp.sel_begin, sp.sel_count, (int32_t)group,
                                             (int32_t)stride, ident ? 1 : 0, 0};
+        } else if (mix && mix->sets[k].mix_count != 0) {
+            // mixes: their rows, every term of every one of them, and one destination range per mix
+            const iss_mixset& ms = mix->sets[k];
+            if (ms.mix_count < 0 || ms.mix_begin < 0 || ms.mix_begin > mix->nmixes - ms.mix_count)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: mix rows [%d, +%d) outside the %lld of the call", who, k, ms.mix_begin,
+                                ms.mix_count, (long long)mix->nmixes);
+            for (int32_t q = 0; q < ms.mix_count; ++q) {
+                const iss_mix& m = mix->mixes[ms.mix_begin + q];
+                if (m.term_count < 1 || m.term_begin < 0 || m.term_begin > mix->nterms - m.term_count)
+                    return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: term rows [%d, +%d) outside the %lld of the call, or no "
+                                    "term", who, k, q, m.term_begin, m.term_count, (long long)mix->nterms);
+                if (!std::isfinite(m.divisor) || m.divisor == 0.0)
+                    return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: divisor %g", who, k, q, m.divisor);
+                for (int32_t n = 0; n < m.term_count; ++n) {
+                    const iss_mix_term& t = mix->terms[m.term_begin + n];
+                    if (t.channel < 0 || t.channel >= J.channels)
+                        return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: term %d: channel %d of %d", who, k, q, n, t.channel,
+                                        J.channels);
+                    if (!std::isfinite(t.weight))
+                        return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: term %d: weight %g", who, k, q, n, t.weight);
+                }
+            }
+            if (ms.dst_stride < nout || ms.dst_stride > (int64_t(1) << 40))
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: dst_stride %lld below the %lld outputs of a mix", who, k,
+                                (long long)ms.dst_stride, (long long)nout);
+            if ((nsig - nout - J.dst_offset) / ms.dst_stride < ms.mix_count - 1)      // (no product that could pass 2^63)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: output of mix %d, %d strides of %lld behind %lld, outside the "
+                                "%lld-sample signal", who, k, ms.mix_count - 1, ms.mix_count - 1, (long long)ms.dst_stride,
+                                (long long)J.dst_offset, (long long)nsig);
+            for (int32_t q = 1; q < ms.mix_count; ++q)
+                ranges.push_back({J.dst_offset + q * ms.dst_stride, J.dst_offset + q * ms.dst_stride + nout});
+            int64_t group, stride;
+            split_geometry(f, ms.mix_count, tile, group, stride);
+            span_b = group * stride * 8;
+            groups = (ms.mix_count + group - 1) / group;
+            plan.dm[(size_t)k] = RsMixDev{ms.dst_stride, (nout + tile - 1) / tile, ms.mix_begin, ms.mix_count, (int32_t)group,
+                                          (int32_t)stride};
         } else {
             while (tile > RS_THREADS && span_frames(f, tile) * 8 > RS_SPAN_MAX) tile /= 2;
             span_b = span_frames(f, tile) * 8;
@@ -426,9 +535,19 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
 int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& plan) {
     const std::vector<RsJobDev>& dj = plan.dj;
     if (dj.empty()) return ISS_OK;
-    const bool win = !plan.dw.empty(), split = !plan.ds.empty();
+    const bool win = !plan.dw.empty(), split = !plan.ds.empty(), mix = !plan.dm.empty();
     int rc;
-    if (split) {                                       // one table: the jobs, (their windows,) their splits, the channel selections
+    if (mix) {                                         // one table: the jobs, (their windows,) their mix sets, the mix rows, the terms
+        const size_t nj = dj.size() * sizeof(RsJobDev), nw = win ? dj.size() * sizeof(RsWinDev) : 0, nm = dj.size() * sizeof(RsMixDev);
+        const size_t nr = plan.mixes.size() * sizeof(RsMixRow), nt = plan.terms.size() * sizeof(RsTermDev);
+        std::vector<uint8_t> rows(nj + nw + nm + std::max<size_t>(nr + nt, 16));
+        memcpy(rows.data(), dj.data(), nj);
+        if (win) memcpy(rows.data() + nj, plan.dw.data(), nw);
+        memcpy(rows.data() + nj + nw, plan.dm.data(), nm);
+        if (nr) memcpy(rows.data() + nj + nw + nm, plan.mixes.data(), nr);
+        if (nt) memcpy(rows.data() + nj + nw + nm + nr, plan.terms.data(), nt);
+        rc = iss_upload_rows(c, c->rs_jobs, rows.data(), rows.size());
+    } else if (split) {                                       // one table: the jobs, (their windows,) their splits, the channel selections
         const size_t nj = dj.size() * sizeof(RsJobDev), nw = win ? dj.size() * sizeof(RsWinDev) : 0, ns = dj.size() * sizeof(RsSplitDev);
         std::vector<uint8_t> rows(nj + nw + ns + std::max<size_t>(plan.sel.size(), 1) * sizeof(int32_t));
         memcpy(rows.data(), dj.data(), nj);
@@ -447,7 +566,9 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     if (rc) return rc;
     bool ext = false;                                  // a format newer than the WAV five: the instantiation that reads them all
     for (const RsJobDev& d : dj) ext = ext || d.fmt > ISS_RS_F64;
-    auto kernel = split && win ? (ext ? resample_kernel<true, true, true> : resample_kernel<false, true, true>)
+    auto kernel = mix ? (win ? (ext ? resample_kernel<true, true, false, true> : resample_kernel<false, true, false, true>)
+                             : (ext ? resample_kernel<true, false, false, true> : resample_kernel<false, false, false, true>))
+                  : split && win ? (ext ? resample_kernel<true, true, true> : resample_kernel<false, true, true>)
                   : split ? (ext ? resample_kernel<true, false, true> : resample_kernel<false, false, true>)
                   : win ? (ext ? resample_kernel<true, true, false> : resample_kernel<false, true, false>)
                         : (ext ? resample_kernel<true, false, false> : resample_kernel<false, false, false>);
@@ -455,7 +576,7 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
         ISS_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
     double flops = 0;
     for (size_t k = 0; k < dj.size(); ++k)
-        flops += 2.0 * (double)dj[k].n_out * (2.0 * dj[k].hl + 1) / dj[k].up * (split ? std::max(plan.ds[k].sel_count, 1) : 1);
+        flops += 2.0 * (double)dj[k].n_out * (2.0 * dj[k].hl + 1) / dj[k].up * (split ? std::max(plan.ds[k].sel_count, 1) : mix ? std::max(plan.dm[k].mix_count, 1) : 1);
     iss_prof_begin(c, ISS_PROF_FRONTEND, flops);
     iss_prof_inst(c, "resample_kernel");
     hipLaunchKernelGGL(kernel, dim3((unsigned)plan.tiles), dim3(RS_THREADS), (size_t)plan.lds, c->stream,
@@ -467,16 +588,18 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     return ISS_OK;
 }
 
-// the one body of the four entry points: `windows`, `splits`, both or neither beside the jobs (a null pointer is "neither")
+// the one body of the five entry points: `windows`, `splits`, both or neither beside the jobs (a null pointer is "neither"), or
+// the tables `mix` of iss_resample_pcm16_mix (with or without windows)
 static int resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
                           int64_t n_signal, const iss_window* windows, const iss_split* splits, const int32_t* channel_sel,
-                          int64_t nsel) {
-    const char* who = splits && windows ? "iss_resample_pcm16_windows_split" : splits ? "iss_resample_pcm16_split"
+                          int64_t nsel, const IssMixTables* mix = nullptr) {
+    const char* who = mix ? "iss_resample_pcm16_mix" : splits && windows ? "iss_resample_pcm16_windows_split" : splits ? "iss_resample_pcm16_split"
                       : windows ? "iss_resample_pcm16_windows" : "iss_resample_pcm16";
-    if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0))
+    if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0) || (mix && njobs > 0 && !mix->sets))
         return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
     IssDecodePass pass;
     int rc = pass.begin(c, who, n_signal, 0);
+    if (mix) { pass.jmix = mix; pass.rmixsets.assign(mix->sets, mix->sets + njobs); }
     pass.rjobs.assign(jobs, jobs + njobs); pass.stage = src_bytes;      // no placement: the caller's rows over the caller's bytes
     if (windows) { pass.rwins.assign(windows, windows + njobs); pass.windowed = true; }
     if (splits) { pass.rsplits.assign(splits, splits + njobs); pass.split = true; pass.sel = channel_sel; pass.nsel = nsel; }
@@ -502,7 +625,14 @@ extern "C" int iss_resample_pcm16_windows_split(iss_ctx* c, const void* src, int
     return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, windows, splits, channel_sel, nsel);
 }
 
-// (tile, channels per group) the planner gives a job of `nsel` selected channels through filter `filter`
+extern "C" int iss_resample_pcm16_mix(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
+                                      const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_mixset* mixsets,
+                                      const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms, int64_t nterms) {
+    const IssMixTables mix{mixsets, mixes, nmixes, terms, nterms};
+    return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, windows, nullptr, nullptr, 0, &mix);
+}
+
+// (tile, channels per group) the planner gives a job of `nsel` selected channels (or mixes) through filter `filter`
 extern "C" int iss_resample_split_geometry(iss_ctx* c, int32_t filter, int32_t nsel, int32_t* tile_out, int32_t* group_out) {
     if (!c || !tile_out || !group_out || nsel < 1 || filter < 0 || filter >= (int32_t)c->rs_filters.size())
         return iss_fail(c, ISS_EINVAL, "iss_resample_split_geometry: bad argument");

@@ -14,7 +14,7 @@ import numpy as np
 from . import _native
 from . import resample as R
 from .io import need_16k_mono, source_of
-from .sources import CodedSource, RawSource, host_window
+from .sources import CodedSource, RawSource, host_window, selection
 
 MAGIC = b'fLaC'
 # benchmark switch (tools/bench_flac.py), not a user option: True makes the ffmpeg-free read decode FLAC on the host
@@ -168,7 +168,7 @@ class FlacExcerpt(FlacSource):
 
     def __init__(self, stream, kind, a, b, sel=None):
         self.s, self.kind, self.size = stream, kind, b - a
-        self.sel = None if sel is None else [int(ch) for ch in sel]
+        self.sel = selection(sel)
         if kind == 'pcm':
             s0, s1 = a, b
         else:

@@ -19,6 +19,9 @@ channel): a source with a channel selection for the device; `decode_channels` is
 samples of the 16 kHz mono twin or a windowed source holding only the bytes it needs; `decode_excerpts` finishes them on the host.
 `channel_excerpts` is both at once: time ranges of single channels, windowed sources with a channel selection;
 `decode_channel_excerpts` is its host-only twin.
+`mix_source` and `mix_excerpts` read weighted sums of a file's channels (resample.py states a mix) where the two above read single
+channels: the same sources, an entry of whose selection is a resample.Mix; `decode_mixes` and `decode_mix_excerpts` are the
+host-only twins.
 """
 import os
 import struct
@@ -265,6 +268,49 @@ def decode_channels(medianame, channels=None, resample=True):
     return [R.resample_ref(x[:, ch], sr) for ch in sel]
 
 
+# ---------------------------------------------------------------------------------------------- mixes: weighted sums of channels
+def mix_name(dst, k):
+    """The output of mix k of a file whose unmixed output is `dst`: a.csv -> a.mix<k>.csv."""
+    stem, ext = os.path.splitext(dst)
+    return f'{stem}.mix{k}{ext}'
+
+
+def mix_source(medianame, mixes, resample=False):
+    """-> (mixes, sig): the mix specification as a list of resample.Mix (resample.normalise_mixes against the file's channel
+    count: ValueError naming the file, the mix and the reason), and what Segmenter reads for it: a source of sources.py whose
+    selection is that list (RawSource, flac.FlacSource, sndfmt.AdpcmSource and its Microsoft twin), one signal per mix,
+    resample.mix_ref(stored, sr, mix) of the file's host decode.  A one-channel file is no exception (its mixes name channel 0),
+    and the output is PCM16 also where the whole-file read takes the float path.  Without `resample` a rate other than 16 kHz
+    is refused as the whole-file read refuses it."""
+    _check_local(medianame)
+    R.normalise_mixes(mixes, None, medianame)                    # (what can be refused before the file is read)
+    buf = _read_file(medianame)
+    what = _classify(buf, medianame)
+    if what is None:
+        x, sr = _parse_wav(buf, medianame)
+        nch = 1 if x.ndim == 1 else x.shape[1]
+    else:
+        nch, sr = what.ch, what.sr
+    mixes = R.normalise_mixes(mixes, nch, medianame)
+    if not resample:
+        need_16k(medianame, sr)
+    R.check_rate(sr)
+    return mixes, RawSource(x, sr, sel=mixes) if what is None else what.split_source(mixes)
+
+
+def decode_mixes(medianame, mixes, resample=True):
+    """Host-only twin of Segmenter.load_pcm_mixes: [resample.mix_ref(stored, sr, mix) for mix in mixes], stored and sr from
+    decode_source(medianame).  resample=False refuses a rate other than 16 kHz as Segmenter(resample=False) does."""
+    _check_local(medianame)
+    R.normalise_mixes(mixes, None, medianame)
+    x, sr = decode_source(medianame)
+    mixes = R.normalise_mixes(mixes, 1 if x.ndim == 1 else x.shape[1], medianame)
+    if not resample:
+        need_16k(medianame, sr)
+    R.check_rate(sr)
+    return [R.mix_ref(x, sr, m) for m in mixes]
+
+
 # ---------------------------------------------------------------------------------------------- excerpts (time ranges of a file)
 def _check_range(name, start_sec, stop_sec):
     """What can be refused of a range before the file is opened."""
@@ -390,6 +436,12 @@ def channel_excerpts(medianame, ranges, channels=None, resample=False):
     what `excerpts` gives (sel is then all zeros).  Ranges are validated as `excerpts` validates them, the selection by
     channel_selection; without `resample` a rate other than 16 kHz is refused, the channel count is not.  A plain RIFF/WAVE
     file is read by byte ranges; every other container, and FLAC, is read whole once."""
+    return _selected_excerpts(medianame, ranges, lambda nch: channel_selection(medianame, channels, nch), resample, True)
+
+
+def _selected_excerpts(medianame, ranges, select, resample, mono_plain):
+    """channel_excerpts and mix_excerpts: `select(channel count)` -> the selection (channel indices, or mixes); mono_plain: a
+    one-channel file gives what `excerpts` gives."""
     from . import flac, sndfmt
     from .sources import RawExcerpt
     ranges = [tuple(r) for r in ranges]
@@ -405,8 +457,8 @@ def channel_excerpts(medianame, ranges, channels=None, resample=False):
             kind = {'uint8': 'u8', 'int16': 'i16', 'int32': 'i32', 'float32': 'f32', 'float64': 'f64'}[x.dtype.name]
             x = np.ascontiguousarray(x)                           # (24-bit: widened, as the whole-file read stages it)
             h = sndfmt.Sound(medianame, sr, 1 if x.ndim == 1 else x.shape[1], kind, False, x.reshape(-1).view(np.uint8), 0)
-    sel = channel_selection(medianame, channels, h.ch)
-    if h.ch == 1:
+    sel = select(h.ch)
+    if h.ch == 1 and mono_plain:
         return sel, excerpts(medianame, ranges, resample)
     if not resample:
         need_16k(medianame, h.sr)
@@ -438,3 +490,20 @@ def decode_channel_excerpts(medianame, ranges, channels=None, resample=True):
     if not all(isinstance(s, Source) and s.sel is not None for s in sigs):          # a one-channel file
         return [[one] * len(sel) for one in decode_excerpts(medianame, ranges, resample)]
     return [s.host() for s in sigs]
+
+
+# ---------------------------------------------------------------------------------------------- excerpts of mixes
+def mix_excerpts(medianame, ranges, mixes, resample=False):
+    """-> (mixes, [source per range]): the time ranges of `excerpts`, of the mixes `mix_source` normalises: every range a
+    windowed source whose selection is the list of resample.Mix (sources.RawExcerpt, flac.FlacExcerpt, sndfmt.AdpcmExcerpt: one
+    signal per mix, the samples [a, b) of that mix's 16 kHz twin), holding only the bytes, frames or blocks the range needs.
+    Ranges, rate and reads as for channel_excerpts; a one-channel file is no exception."""
+    R.normalise_mixes(mixes, None, medianame)
+    return _selected_excerpts(medianame, ranges, lambda nch: R.normalise_mixes(mixes, nch, medianame), resample, False)
+
+
+def decode_mix_excerpts(medianame, ranges, mixes, resample=True):
+    """Host-only twin of Segmenter.load_pcm_mix_excerpts: out[r][k] = the samples [a, b) of decode_mixes(medianame, [mixes[k]])[0]
+    for range r, by the host builds of the decoders on the frames, blocks and bytes of each excerpt alone and a windowed
+    resample.mix_ref per mix."""
+    return [s.host() for s in mix_excerpts(medianame, ranges, mixes, resample)[1]]

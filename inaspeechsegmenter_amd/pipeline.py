@@ -301,7 +301,8 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
     per-file 'ok <secs>' message reports, segmenter.py:322-327, when files are processed one by one).
     skip: set of indices not to process.  Device failures (NativeError) and exceptions raised by on_result (unwritable
     outputs) propagate to the caller: the first one is re-raised here once every stage has drained.
-    channels='split': every channel of every file on its own; lseg is then a LIST of segment lists, one per channel of the file."""
+    channels='split': every channel of every file on its own; lseg is then a LIST of segment lists, one per channel of the file.
+    channels = a list of resample.Mix: those mixes of every file, likewise (segmenter._load_source reads either)."""
     batch_files, batch_seconds = _limits(batch_files, batch_seconds)
     workers = workers or DEFAULT_WORKERS
     items = [(i, src) for i, src in enumerate(linput) if not (skip and i in skip)]

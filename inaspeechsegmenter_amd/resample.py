@@ -10,11 +10,27 @@ reads, in three steps that follow what `ffmpeg -ac 1 -ar 16000 -acodec pcm_s16le
                  for i < ceil(n*up/down), summed in ascending j
   3. quantise    pcm = clip(rint(y * 32768), -32768, 32767).astype(int16)   (round half to even, then saturate)
 
+Mixes (an extension: weighted sums of a file's channels, `Segmenter.load_pcm_mixes` and what follows it).  A MIX is K >= 1 terms
+(c_k, w_k) and a divisor d: c_k a 0-based channel index (channels may repeat and come in any order), w_k a finite float64, d
+finite and not zero.  It replaces step 1: for stored frame j, x[j, c] the stored sample scaled by io._to_float,
+
+    m[j] = ( (w_0 * x[j, c_0]) + w_1 * x[j, c_1] + ... + w_{K-1} * x[j, c_{K-1}] ) / d
+
+in float64, every product and every sum rounded on its own (no FMA), the terms taken in ascending k, the division always
+performed, once, at the end (d = 1 is exact).  Steps 2 and 3 apply unchanged, at 16 kHz too (through the identity filter): a
+mix whose sum leaves [-1, 1) saturates, as ffmpeg's pcm_s16le does, and the output is PCM16 whatever the stored format.
+Two identities follow: K = 1, w = 1, d = 1 is the channel alone (1.0 * x and x / 1.0 are exact), and all C channels in order
+with every w = 1 and d = C is the device's plain downmix, which sums the channels in order and divides by C.  numpy's
+`mean(axis=1)` is NOT that sum for float64 rows of 8 or more channels (it adds pairwise); for samples of the integer formats
+every partial sum is exact and the order cannot matter.  `mixdown` therefore states the loop and never calls `mean`.
+`Mix` is the general form; `normalise_mixes` states the spellings a mix specification accepts, `parse_mixes` the command line's.
+
 `plan(sr)` is the host part the device needs (one table per rate, cached).  `resample_ref` is the float64 statement of the
 three steps that the tests and tools/bench_resample.py compare the device with; the product never calls it.
 """
 import functools
 import math
+from typing import NamedTuple
 
 import numpy as np
 
@@ -116,3 +132,119 @@ def resample_ref(x, sr, out_begin=0, out_count=None, in_begin=0, frames_total=No
     only those outputs (the defaults give them all); in_begin / frames_total: x holds the file's frames from in_begin on
     (resample_float states the window)."""
     return quantise(resample_float(downmix(x), sr, out_begin, out_count, in_begin, frames_total))
+
+
+# ---------------------------------------------------------------------------------------------- mixes: weighted sums of channels
+class Mix(NamedTuple):
+    """One mix: `terms` = ((channel, weight), ...) in the order they are summed, and the `divisor` of the sum."""
+    terms: tuple
+    divisor: float = 1.0
+
+
+def _one_mix(k, m, channels, name):
+    """Mix k of a specification -> a Mix with int channels and float weights, or ValueError naming it."""
+    def bad(why):
+        return ValueError(f'{name}: mix {k} ({m!r}): {why}')
+
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+    def is_num(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+    if is_int(m):                                                       # a channel alone
+        terms, divisor = [(m, 1.0)], 1.0
+    elif isinstance(m, Mix):
+        terms, divisor = m.terms, m.divisor
+    elif isinstance(m, (str, bytes)):
+        raise bad('a mix is a channel index, a sequence of them, (channel, weight) pairs, a mapping or a resample.Mix')
+    elif hasattr(m, 'items'):                                           # channel -> weight: the weighted sum
+        terms, divisor = list(m.items()), 1.0
+    else:
+        try:
+            entries = list(m)
+        except TypeError:
+            raise bad('a mix is a channel index, a sequence of them, (channel, weight) pairs, a mapping or a resample.Mix') from None
+        if entries and all(is_int(e) for e in entries):                 # channel indices: their mean, summed in the order given
+            terms, divisor = [(e, 1.0) for e in entries], float(len(entries))
+        else:                                                           # (channel, weight) pairs: the weighted sum
+            terms, divisor = entries, 1.0
+    out = []
+    try:
+        terms = [tuple(t) for t in terms]
+    except TypeError:
+        raise bad('its terms are (channel, weight) pairs') from None
+    if not terms:
+        raise bad('empty mix')
+    for t in terms:
+        if len(t) != 2 or not is_int(t[0]) or not is_num(t[1]):
+            raise bad(f'term {t!r} is not a (channel, weight) pair')
+        ch, w = int(t[0]), float(t[1])
+        if ch < 0 or (channels is not None and ch >= channels):
+            of = '' if channels is None else f" the file's {channels} channel{'s' if channels > 1 else ''} (0 .. {channels - 1})"
+            raise bad(f'channel {ch} is outside{of}' if of else f'channel {ch} is negative')
+        if not math.isfinite(w):
+            raise bad(f'weight {w!r} of channel {ch} is not finite')
+        out.append((ch, w))
+    if not is_num(divisor) or not math.isfinite(divisor) or divisor == 0:
+        raise bad(f'divisor {divisor!r} must be finite and not zero')
+    return Mix(tuple(out), float(divisor))
+
+
+def normalise_mixes(spec, channels=None, name='mixes'):
+    """A mix specification -- a sequence of mixes -- as a list of `Mix`.  A mix is spelt
+        an int c                                    that channel alone
+        a sequence of ints                          their mean, summed in the order given (divisor = their count)
+        a mapping channel -> weight, or a sequence of (channel, weight) pairs     the weighted sum (divisor 1)
+        Mix(terms, divisor)                         the general form
+    ValueError naming `name`, the mix and the reason: an empty specification or mix, a channel that is negative or (with
+    `channels`, the file's channel count) outside the file, a weight that is not finite, a divisor that is zero or not finite."""
+    if spec is None or isinstance(spec, (str, bytes, Mix)) or hasattr(spec, 'items'):
+        raise ValueError(f'{name}: a mix specification is a sequence of mixes, not {spec!r}')
+    try:
+        spec = list(spec)
+    except TypeError:
+        raise ValueError(f'{name}: a mix specification is a sequence of mixes, not {spec!r}') from None
+    if not spec:
+        raise ValueError(f'{name}: empty mix specification')
+    return [_one_mix(k, m, channels, name) for k, m in enumerate(spec)]
+
+
+def parse_mixes(text):
+    """The command line's spelling of a mix specification -> a list of `Mix`: mixes separated by commas, terms joined by `+`.
+    A mix whose terms are all bare channel numbers ("0+1") is their mean; a mix with any `weight*channel` term
+    ("0.7*4+0.7*5+2") is a weighted sum, in which a bare channel has weight 1 and nothing is divided."""
+    spec = []
+    for k, part in enumerate(str(text).split(',')):
+        terms, weighted = [], False
+        for t in part.split('+'):
+            w, star, ch = t.partition('*')
+            if not star:
+                w, ch = '1', w
+            weighted = weighted or bool(star)
+            try:
+                terms.append((int(ch.strip()), float(w.strip())))
+            except ValueError:
+                raise ValueError(f'--mixes: mix {k} ({part.strip()!r}): term {t.strip()!r} is not CHANNEL or WEIGHT*CHANNEL') from None
+        spec.append(Mix(tuple(terms), 1.0 if weighted else float(len(terms))))
+    return normalise_mixes(spec, None, '--mixes')
+
+
+def mixdown(x, mix):
+    """Stored samples (n,) or (n, C) -> float64 mono by the definition above: the explicit loop over the terms, vectorised over
+    frames only (numpy rounds each elementwise product, sum and quotient on its own)."""
+    from .io import _to_float
+    m = _to_float(np.asarray(x), np.float64)
+    if m.ndim == 1:
+        m = m[:, None]
+    (mix,) = normalise_mixes([mix], m.shape[1])
+    (c0, w0), rest = mix.terms[0], mix.terms[1:]
+    acc = w0 * m[:, c0]
+    for ch, w in rest:
+        acc = acc + w * m[:, ch]
+    return acc / mix.divisor
+
+
+def mix_ref(x, sr, mix, out_begin=0, out_count=None, in_begin=0, frames_total=None):
+    """resample_ref with `mixdown(x, mix)` in place of the downmix -> 16 kHz mono int16 (windows as resample_ref states them)."""
+    return quantise(resample_float(mixdown(x, mix), sr, out_begin, out_count, in_begin, frames_total))

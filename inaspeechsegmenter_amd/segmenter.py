@@ -29,6 +29,7 @@ from . import _native
 from . import tables
 from . import keras_model
 from . import io as iss_io
+from . import resample as resample_mod
 from .io import decode_pcm, _to_float
 from .sources import Source, RawSource               # noqa: F401  (RawSource is also imported from here, where it was)
 from .export_funcs import seg2csv, seg2textgrid
@@ -319,8 +320,11 @@ def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False, channel
     becomes a flac.FlacSource (compressed frames, decoded on the device like its WAV twin reads), a file of sndfmt.py what
     sndfmt.source makes of it (a RawSource with its format, a sndfmt.AdpcmSource, or the twin's array), and a WAV at another
     rate or with several channels a RawSource with `resample` and decode_pcm's refusal without it (io.source_of).
-    channels='split' (ffmpeg=None): every channel on its own -- io.split_source's source with all channels selected."""
+    channels='split' (ffmpeg=None): every channel on its own -- io.split_source's source with all channels selected;
+    channels = a list of resample.Mix: those mixes, each on its own -- io.mix_source's source."""
     if channels is not None:
+        if channels != 'split':
+            return iss_io.mix_source(medianame, channels, resample)[1]
         return iss_io.split_source(medianame, None, resample)[1]
     if ffmpeg is not None:
         return decode_pcm(medianame, start_sec, stop_sec, ffmpeg)
@@ -532,6 +536,11 @@ class Segmenter:
         sel, sig = self._channel_sig(medianame, channels)
         if getattr(sig, 'sel', None) is None:
             return [self.segment_signal(self._mono_pcm(sig))] * len(sel)
+        return self._segment_parts(medianame, sel, sig, batch_files, batch_seconds)
+
+    def _segment_parts(self, medianame, sel, sig, batch_files, batch_seconds):
+        """segment_channels and segment_mixes: the signals `sel` (channels, or mixes) of the source `sig`, in passes."""
+        from . import pipeline
         if sig.size < pipeline.MIN_SAMPLES:
             return pipeline.one_by_one(self, self.ctx, sig)
         # the channels cut into passes as files of their length would be (min(batch_files, ceil(limit / stride)) each), and
@@ -649,10 +658,14 @@ class Segmenter:
         A one-channel file gives [load_pcm_excerpts(...)[r]] * len(sel) per range (the float path included).  Range errors as
         segment_excerpts, channel errors as load_pcm_channels; with ffmpeg set, ValueError naming the argument.  Frames and
         blocks that are not decoded are not checked."""
-        from .sources import Group
         ranges, sel, sigs = self._channel_excerpt_sigs(medianame, ranges, channels)
         if sigs is None:
             return [[one] * len(sel) for one in self.load_pcm_excerpts(medianame, ranges, batch_files, batch_seconds)]
+        return self._load_pairs(ranges, sel, sigs, batch_files, batch_seconds)
+
+    def _load_pairs(self, ranges, sel, sigs, batch_files, batch_seconds):
+        """load_pcm_channel_excerpts and load_pcm_mix_excerpts: the signals `sel` (channels, or mixes) of every range's source."""
+        from .sources import Group
         out = [[None] * len(sel) for _ in ranges]
         for per in self._pair_passes(sigs, range(len(ranges)), sel, batch_files, batch_seconds):
             placed, pos = [], 0                                  # end to end: the launch creates a signal of just these samples
@@ -675,10 +688,14 @@ class Segmenter:
         shorter than 68 frames go alone as segment_signal would take them (padding and warning included).  A one-channel file
         gives [segment_excerpts(...)[r]] * len(sel) per range.  Errors as load_pcm_channel_excerpts; a malformed FLAC frame or IMA
         block among those decoded fails the call (ValueError naming its byte offset in the file)."""
-        from . import pipeline
         ranges, sel, sigs = self._channel_excerpt_sigs(medianame, ranges, channels)
         if sigs is None:
             return [[one] * len(sel) for one in self.segment_excerpts(medianame, ranges, batch_files, batch_seconds)]
+        return self._segment_pairs(medianame, ranges, sel, sigs, batch_files, batch_seconds)
+
+    def _segment_pairs(self, medianame, ranges, sel, sigs, batch_files, batch_seconds):
+        """segment_channel_excerpts and segment_mix_excerpts: the signals `sel` (channels, or mixes) of every range's source."""
+        from . import pipeline
         out = [[None] * len(sel) for _ in ranges]
         todo = []
         for r, s in enumerate(sigs):
@@ -701,6 +718,49 @@ class Segmenter:
                     out[r][k] = [(lab, start + a * .02, start + b * .02) for lab, a, b in next(lsegs)]
         return out
 
+    # ---- weighted sums of a file's channels without ffmpeg (an extension; resample.py states a mix): mixed on the device
+    def _no_ffmpeg_mixes(self):
+        if self.ffmpeg is not None:
+            raise ValueError(f'mixes are read without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={self.ffmpeg!r} downmixes every '
+                             f'file with -ac 1')
+
+    def load_pcm_mixes(self, medianame, mixes):
+        """One int16 array per mix of the specification `mixes` (resample.normalise_mixes states its spellings): exactly
+        resample.mix_ref(stored, sr, mix), stored and sr from io.decode_source -- the weighted sum of channels in float64,
+        resampled to 16 kHz and quantised (saturating) like load_pcm's downmix --, all of them by ONE decode launch and ONE
+        resample launch; PCM16 whatever the stored format.  ValueError, naming the file, the mix and the reason: a channel outside
+        the file's, a weight that is not finite, a zero or non-finite divisor, an empty mix; an http source; naming the argument
+        with ffmpeg set.  Without resample=True a rate other than 16 kHz is refused as load_pcm refuses it."""
+        self._no_ffmpeg_mixes()
+        return _parts_pcm(self.ctx, iss_io.mix_source(medianame, mixes, self.resample)[1])
+
+    def segment_mixes(self, medianame, mixes, batch_files=None, batch_seconds=None):
+        """Segment every mix of one file on its own -> [[(label, start, stop), ...] per mix].  List k is exactly what
+        segment_signal(load_pcm_mixes(medianame, [mixes[k]])[0]) gives.  All mixes of the file that fit a pass (batch_files /
+        batch_seconds as for segment_channels, a mix counting as a channel does) share one decode launch, one resample launch
+        and one feature pass.  Errors as load_pcm_mixes; a malformed FLAC frame or ADPCM block fails the call."""
+        self._no_ffmpeg_mixes()
+        return self._segment_parts(medianame, *iss_io.mix_source(medianame, mixes, self.resample), batch_files, batch_seconds)
+
+    def load_pcm_mix_excerpts(self, medianame, ranges, mixes, batch_files=None, batch_seconds=None):
+        """load_pcm_mixes for time ranges [(start_sec, stop_sec | None)] of one file -> out[r][k] = the int16 samples [a, b) of
+        load_pcm_mixes(medianame, [mixes[k]])[0], (a, b) as load_pcm_channel_excerpts states them.  Only the bytes, ADPCM blocks
+        and FLAC frames the ranges need are staged, and all (range, mix) pairs that fit a pass take ONE launch per decode kernel
+        and ONE resample launch.  Range errors as segment_excerpts, mix errors as load_pcm_mixes."""
+        self._no_ffmpeg_mixes()
+        ranges = [tuple(r) for r in ranges]
+        sel, sigs = iss_io.mix_excerpts(medianame, ranges, mixes, self.resample)
+        return self._load_pairs(ranges, sel, sigs, batch_files, batch_seconds)
+
+    def segment_mix_excerpts(self, medianame, ranges, mixes, batch_files=None, batch_seconds=None):
+        """Segment time ranges of mixes of one file without ffmpeg -> out[r][k] = exactly what
+        segment_signal(load_pcm_mix_excerpts(...)[r][k], start_sec=ranges[r][0]) gives: segment_channel_excerpts with the mix in
+        place of the channel (passes, short ranges and times as stated there).  Errors as load_pcm_mix_excerpts."""
+        self._no_ffmpeg_mixes()
+        ranges = [tuple(r) for r in ranges]
+        sel, sigs = iss_io.mix_excerpts(medianame, ranges, mixes, self.resample)
+        return self._segment_pairs(medianame, ranges, sel, sigs, batch_files, batch_seconds)
+
     def __call__(self, medianame, start_sec=None, stop_sec=None):
         """segmenter.py:279-294."""
         mspec, loge, difflen = _media2feats(medianame, start_sec, stop_sec, self.ffmpeg, self.ctx, self.resample)
@@ -709,7 +769,7 @@ class Segmenter:
         return self.segment_feats(mspec, loge, difflen, start_sec)
 
     def batch_process(self, linput, loutput, verbose=False, skipifexist=False, nbtry=1, trydelay=2., output_format='csv',
-                      batch_files=None, workers=None, batch_seconds=None, channels=None):
+                      batch_files=None, workers=None, batch_seconds=None, channels=None, mixes=None):
         """segmenter.py:297-335: same arguments, same (t_batch_dur, nb_processed, avg, lmsg) with
         lmsg entries (dst, code, text), code 0 ok / 1 already exists / 2 error, in input order.
         The files run through pipeline.process_files: decode threads, super-batches of at most `batch_files` files /
@@ -721,14 +781,24 @@ class Segmenter:
         writes .ch0 only).  A file's outputs are written in descending channel order, so .ch0 existing means the file is complete:
         skipifexist tests that name.  lmsg then holds one entry per written output, files in input order and channels ascending;
         a file that fails to decode gives one code-2 entry carrying the unsplit dst.  Each channel counts as a file against
-        batch_files, its samples against batch_seconds."""
+        batch_files, its samples against batch_seconds.
+        mixes (an extension, ffmpeg=None only, not with channels='split'): a mix specification (resample.normalise_mixes), the same
+        for every file: every mix of every file is segmented on its own (segment_mixes) and written to <dst stem>.mix<k><ext>,
+        the last mix first, so .mix0 existing means the file is complete: skipifexist tests that name.  lmsg as for
+        channels='split'; a file with too few channels for the specification is a code-2 entry like any file that fails to decode."""
         from . import pipeline
         if channels not in (None, 'split'):
             raise ValueError(f"channels={channels!r}: None or 'split'")
+        part_name = iss_io.channel_name
+        if mixes is not None:
+            if channels is not None:
+                raise ValueError("mixes and channels='split' exclude each other")
+            self._no_ffmpeg_mixes()
+            channels, part_name = resample_mod.normalise_mixes(mixes), iss_io.mix_name
         if channels is not None and self.ffmpeg is not None:
             raise ValueError(f"channels='split' reads files without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={self.ffmpeg!r} "
                              f"downmixes every file with -ac 1")
-        first = (lambda dst: dst) if channels is None else (lambda dst: iss_io.channel_name(dst, 0))
+        first = (lambda dst: dst) if channels is None else (lambda dst: part_name(dst, 0))
         if verbose:
             print('batch_processing %d files' % len(linput))
         if output_format == 'csv':
@@ -757,9 +827,9 @@ class Segmenter:
             elif channels is not None:                         # one segment list per channel: the last channel's output first
                 b = time.time()
                 for k in reversed(range(len(lseg))):
-                    fexport(lseg[k], iss_io.channel_name(dst, k))
+                    fexport(lseg[k], part_name(dst, k))
                 text = 'ok ' + str(secs + (time.time() - b) / len(lseg))
-                msgs[i] = [(iss_io.channel_name(dst, k), 0, text) for k in range(len(lseg))]
+                msgs[i] = [(part_name(dst, k), 0, text) for k in range(len(lseg))]
             else:
                 b = time.time()
                 fexport(lseg, dst)

@@ -31,7 +31,7 @@ from . import _native
 from . import flac
 from . import resample as R
 from .io import _to_float, need_16k_mono
-from .sources import CodedSource, RawSource, host_window
+from .sources import CodedSource, RawSource, host_window, selection
 
 # benchmark switch (tools/bench_sndfmt.py), not a user option: True makes the ffmpeg-free read expand G.711 and ADPCM on
 # the host (numpy table / iss_adpcm_decode_host, iss_msadpcm_decode_host in the decode threads) instead of handing the stored bytes to the device
@@ -593,7 +593,7 @@ class AdpcmExcerpt(AdpcmSource):
 
     def __init__(self, h, kind, a, b, sel=None):
         self.kind, self.size = kind, b - a
-        self.sel = None if sel is None else [int(ch) for ch in sel]
+        self.sel = selection(sel)
         s0, s1 = (a, b) if kind == 'pcm' else (lambda lo, hi: (lo, hi + 1))(*R.input_span(h.sr, h.n, a, b - a))
         self.s, self.first = sub_sound(h, s0, s1)
         self.win = (s0, s1, h.n, a, b - a)

@@ -14,12 +14,19 @@ bytes as stored, which a kernel turns into 16 kHz mono PCM16 inside the resident
     tables(group), launch(ctx, staged, rows, tables, n_signal, **kw)   (of the class) what ONE launch for a group of sources of
                             this class needs besides bytes and rows, and the launch -> the status array (valid after the
                             context's next synchronising call) or None; kw: `windows=`, `splits=` or both, only where some job has one
+                            (`mixes=` in place of `splits=` where some selection holds a mix)
     parts                   how many consecutive signals it writes (default 1): `parts` signals of `size` samples each, signal k at
                             dst_offset + k * `stride`, stride = `size` rounded up to FRAME_HOP
 
 A source made with a channel selection `sel` (RawSource, flac.FlacSource, sndfmt.AdpcmSource and its Microsoft twin) writes one signal per selected
 channel instead of their average: `parts` = len(sel), and its job carries the split row (iss_split) for the split entry point
 -- downmixed and split files of a pass in the same launch.
+
+An entry of `sel` may be a `resample.Mix` in place of a channel index (io.mix_source, io.mix_excerpts): that signal is the
+weighted sum of channels the mix states, staged by the resample kernel's MIX instantiations.  Everything that holds for a
+selected channel holds for a mix -- `parts`, `stride`, `reselect`, `host()` --, and a launch whose jobs carry any mix goes to
+the *_mix entry point (`mixes=`), plain channels beside them as one-term mixes, which are the same samples to the bit.  A launch
+without a mix is the launch it always was.
 
 An excerpt of a file (io.excerpts) is a source too, of a class of its own below its format's: its `size` is the excerpt's, its
 `payload` only the bytes the excerpt needs, and its job carries the window row (iss_window) for the windowed entry point.  A
@@ -47,8 +54,14 @@ from . import resample
 FRAME_HOP = 160
 
 
+def selection(sel):
+    """A channel selection as the sources keep it: None, or a list of channel indices and / or `resample.Mix`."""
+    return None if sel is None else [ch if isinstance(ch, resample.Mix) else int(ch) for ch in sel]
+
+
 class Job(NamedTuple):
-    """What `Source.job` returns: the job row, and the window row or the split `(dst_stride, [channels])` that goes beside it."""
+    """What `Source.job` returns: the job row, and the window row or the split `(dst_stride, [channels or mixes])` that goes
+    beside it."""
     row: tuple
     window: tuple = None
     split: tuple = None
@@ -77,7 +90,7 @@ class Source:
     def reselect(self, sel):
         """This source with another selection of its channels (the file is not read again)."""
         other = copy.copy(self)
-        other.sel = [int(ch) for ch in sel]
+        other.sel = selection(sel)
         return other
 
     def check(self, status):
@@ -123,7 +136,9 @@ class Group:
         kw = {}                                      # (a plain launch: the call every launch made before there were any)
         if any(j.window is not None for j in self.jobs):
             kw['windows'] = [j.window for j in self.jobs]
-        if any(j.split is not None for j in self.jobs):
+        if any(j.split is not None and any(isinstance(ch, resample.Mix) for ch in j.split[1]) for j in self.jobs):
+            kw['mixes'] = [j.split for j in self.jobs]
+        elif any(j.split is not None for j in self.jobs):
             kw['splits'] = [j.split for j in self.jobs]
         self.status = self.cls.launch(self.ctx, self.staged, [j.row for j in self.jobs], self.tables, n_signal, **kw)
         return self
@@ -146,13 +161,13 @@ class Group:
 class RawSource(Source):
     """Samples at another rate or channel count, as stored, for the device resampler (Segmenter(ffmpeg=None, resample=True)).
     `fmt` is the ISS_RS_* format of the stored bytes: the dtype's by default; explicit for signed bytes, G.711 and big-endian
-    samples.  `sel`: the channels to write apart (None: their average)."""
+    samples.  `sel`: the channels (or mixes of them) to write apart (None: their average)."""
     __slots__ = ('x', 'sr', 'size', 'fmt', 'sel')
     pass_order = 0
 
     def __init__(self, x, sr, fmt=None, sel=None):
         self.x, self.sr = np.ascontiguousarray(x), sr
-        self.sel = None if sel is None else [int(ch) for ch in sel]
+        self.sel = selection(sel)
         self.fmt = _native.RS_FORMAT[self.x.dtype] if fmt is None else int(fmt)
         self.size = resample.out_len(x.shape[0], sr)
 
@@ -183,7 +198,7 @@ class RawExcerpt(RawSource):
 
     def __init__(self, sub, x, fmt, a, b, j_lo, frames_total, sel=None):
         self.sub, self.x, self.sr, self.fmt = sub, np.ascontiguousarray(x), sub.sr, int(fmt)
-        self.sel = None if sel is None else [int(ch) for ch in sel]
+        self.sel = selection(sel)
         self.size = b - a
         self.win = (j_lo, j_lo + self.x.shape[0], frames_total, a, b - a)
 
@@ -194,11 +209,13 @@ class RawExcerpt(RawSource):
 
 def host_window(x, sr, win, sel=None):
     """What an excerpt's `host()` gives for x = the stored frames [s_begin, s_end) of its window row `win`: their downmix's
-    outputs, or with a selection one array per selected channel, each resample.resample_ref on that channel's column."""
+    outputs, or with a selection one array per selected channel, each resample.resample_ref on that channel's column
+    (resample.mix_ref for an entry that is a mix)."""
     s0, _, total, a, count = win
     if sel is None:
         return resample.resample_ref(x, sr, a, count, s0, total)
-    return [resample.resample_ref(x[:, ch], sr, a, count, s0, total) for ch in sel]
+    return [resample.mix_ref(x, sr, ch, a, count, s0, total) if isinstance(ch, resample.Mix) else
+            resample.resample_ref(x[:, ch], sr, a, count, s0, total) for ch in sel]
 
 
 class CodedSource(Source):
@@ -209,7 +226,7 @@ class CodedSource(Source):
 
     def __init__(self, parsed, kind, sel=None):
         self.s, self.kind = parsed, kind
-        self.sel = None if sel is None else [int(ch) for ch in sel]
+        self.sel = selection(sel)
         self.size = resample.out_len(parsed.n, parsed.sr) if kind == 'resample' else parsed.n
         self.nbytes = self.payload.nbytes
 

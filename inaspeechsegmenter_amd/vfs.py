@@ -25,6 +25,7 @@ import numpy as np
 from . import _native, keras_model
 from .io import decode_pcm, media2sig16kmono, _to_float
 from . import sndfmt
+from . import io as iss_io
 from .segmenter import Segmenter, locate_model, _parts_pcm
 from .vbx import FeatureExtractor, VBxExtractor, SR, frame_count, pcm16_of, plan_windows
 
@@ -293,6 +294,11 @@ class VoiceFemininityScoring:
         sel, sig = self.vad._channel_sig(fpath, channels)
         if getattr(sig, 'sel', None) is None:                     # a one-channel file
             return [self._alone(fpath, sig, basename)] * len(sel)
+        return self._score_parts(fpath, basename, sel, sig, batch_files, batch_seconds)
+
+    def _score_parts(self, fpath, basename, sel, sig, batch_files, batch_seconds):
+        """score_channels and score_mixes: the signals `sel` (channels, or mixes) of the source `sig`, in passes."""
+        from . import pipeline
         if sig.size < pipeline.MIN_SAMPLES:
             return [self._alone(fpath, one, basename) for one in _parts_pcm(self.ctx, sig)]
         passes = pipeline.cut_passes([sig.reselect([ch]) for ch in sel], batch_files, batch_seconds)
@@ -329,6 +335,11 @@ class VoiceFemininityScoring:
         ranges, sel, sigs = self.vad._channel_excerpt_sigs(fpath, ranges, channels)
         if sigs is None:
             return [[one] * len(sel) for one in self.score_excerpts(fpath, ranges, batch_files, batch_seconds)]
+        return self._score_pairs(fpath, basename, ranges, sel, sigs, batch_files, batch_seconds)
+
+    def _score_pairs(self, fpath, basename, ranges, sel, sigs, batch_files, batch_seconds):
+        """score_channel_excerpts and score_mix_excerpts: the signals `sel` (channels, or mixes) of every range's source."""
+        from . import pipeline
         out, todo = [[None] * len(sel) for _ in ranges], []
         for r, s in enumerate(sigs):
             if s.size < pipeline.MIN_SAMPLES:
@@ -346,6 +357,23 @@ class VoiceFemininityScoring:
                 for k in ks:
                     out[r][k] = next(res)
         return out
+
+    def score_mixes(self, fpath, mixes, batch_files=None, batch_seconds=None):
+        """Score every mix of one file on its own -> [(score, speech_duration, nb_vectors) per mix]: entry k is exactly
+        score_signal(self.vad.load_pcm_mixes(fpath, [mixes[k]])[0]).  Arguments, passes and errors as Segmenter.segment_mixes."""
+        self.vad._no_ffmpeg_mixes()
+        basename = os.path.splitext(os.path.basename(fpath))[0]
+        return self._score_parts(fpath, basename, *iss_io.mix_source(fpath, mixes, self.vad.resample), batch_files, batch_seconds)
+
+    def score_mix_excerpts(self, fpath, ranges, mixes, batch_files=None, batch_seconds=None):
+        """Score time ranges of mixes of one file -> out[r][k] = exactly
+        score_signal(self.vad.load_pcm_mix_excerpts(fpath, [ranges[r]], [mixes[k]])[0][0]).  Arguments, passes and errors as
+        Segmenter.segment_mix_excerpts; window times count from the start of the range."""
+        self.vad._no_ffmpeg_mixes()
+        basename = os.path.splitext(os.path.basename(fpath))[0]
+        ranges = [tuple(r) for r in ranges]
+        sel, sigs = iss_io.mix_excerpts(fpath, ranges, mixes, self.vad.resample)
+        return self._score_pairs(fpath, basename, ranges, sel, sigs, batch_files, batch_seconds)
 
     def _decoded_on_device(self, fpath):
         """Is the file decoded on the device when read without ffmpeg (FLAC, or a file of sndfmt.py)?  Then it is decoded

@@ -402,6 +402,64 @@ int iss_msadpcm_decode_windows_split(iss_ctx* ctx, const void* src, int64_t src_
                                      const iss_window* windows, int32_t njobs, int64_t nblocks_total, int64_t n_signal,
                                      int32_t* status_out, const iss_split* splits, const int32_t* channel_sel, int64_t nsel);
 
+/* Mixes: weighted sums of a file's channels, mixed and resampled in the same launch.  A MIX is K >= 1 terms (c_k, w_k) and a
+ * divisor d: c_k a 0-based channel (channels may repeat and come in any order), w_k a finite float64, d finite and not zero.
+ * For stored frame j, x[j, c] the stored sample scaled as for the plain call (libsndfile's rule):
+ *     m[j] = ( (w_0 * x[j, c_0]) + w_1 * x[j, c_1] + ... + w_{K-1} * x[j, c_{K-1}] ) / d
+ * in float64, every product and every sum rounded on its own (no FMA), terms in ascending k, the division always performed,
+ * once, at the end (d = 1 is exact).  Tap walk, ascending-j sum with separate multiply and add, rint(y * 32768) and saturation
+ * to [-32768, 32767] are those of the plain call, through the identity filter at 16 kHz too: a mix whose sum leaves [-1, 1)
+ * saturates, and the output is PCM16 whatever the stored format (inaspeechsegmenter_amd/resample.py's mix_ref, to the bit).
+ * Two identities: K = 1, w = 1, d = 1 is the split's output for that channel; all C channels in order, every w = 1, d = C is the
+ * plain call's downmix.
+ * Three tables go with a call: a mix-set row beside every job row (mixsets[k] belongs to jobs[k]), the call's mix rows
+ * mixes[0, nmixes) and the call's term rows terms[0, nterms).  A job's mixes are rows [mix_begin, mix_begin + mix_count) of
+ * `mixes`; a mix's terms are rows [term_begin, term_begin + term_count) of `terms`.
+ *   resample rows   mix_count > 0: the job writes mix_count mono outputs of frames_out samples each, output q at dst_offset +
+ *                   q * dst_stride (with a window: outputs i in [out_begin, out_begin + out_count) at dst_offset + q *
+ *                   dst_stride + i - out_begin, frames outside [0, frames_total) zero, as for a windowed split).  Samples between
+ *                   the end of an output and the next stride are not written.
+ *                   mix_count == 0: the job downmixes all its channels exactly as the plain call does, in the same launch.
+ *   decoder rows    only a TO_STAGE job with a filter may carry mix_count > 0: the decode kernel stages the interleaved samples
+ *                   as always and the mix-set row is handed to the resample row that reads them.
+ * `windows` is optional in every *_mix entry point: NULL is the unwindowed call, else a window row beside every job row, with
+ * the contract of the *_windows entry points.  The grid of the resample launch is ragged over (job, mix group, tile); groups and
+ * tile are what iss_resample_split_geometry reports for mix_count rows.  Device table: job rows, (window rows,) mix-set rows,
+ * mix rows, term rows.
+ * ISS_EINVAL (checked before anything is launched or the context changes, the text names the job): mix_count < 0, mix rows
+ * outside [0, nmixes), term_count < 1, term rows outside [0, nterms), a term's channel outside [0, channels), a weight that is
+ * not finite, a divisor that is zero or not finite, dst_stride < frames_out, one of the mix_count destination ranges outside the
+ * signal, any two destination ranges of the call overlapping, a decoder job with mixes that is not TO_STAGE with a filter.
+ * iss_resample_stats counts a mixed job as ONE job whatever its mix_count; launches, status, staging, the signal rule and all
+ * other errors are as for the plain entry point.  The entry points above are unchanged, to the bit and to the launch.          */
+typedef struct {
+    int64_t dst_stride;   /* samples between the outputs of consecutive mixes, >= frames_out                 */
+    int32_t mix_begin;    /* the job's rows of `mixes`: [mix_begin, mix_begin + mix_count)                    */
+    int32_t mix_count;    /* 0: downmix all channels, exactly as the plain call does                         */
+} iss_mixset;
+typedef struct {
+    int32_t term_begin;   /* the mix's rows of `terms`: [term_begin, term_begin + term_count)                 */
+    int32_t term_count;   /* >= 1                                                                            */
+    double divisor;       /* finite, not zero                                                                */
+} iss_mix;
+typedef struct {
+    int32_t channel;      /* 0-based, below the job's channels                                               */
+    int32_t reserved;     /* 0                                                                               */
+    double weight;        /* finite                                                                          */
+} iss_mix_term;
+int iss_resample_pcm16_mix(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
+                           const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_mixset* mixsets,
+                           const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms, int64_t nterms);
+int iss_flac_decode_mix(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_flac_frame* frames, int64_t nframes,
+                        const iss_flac_job* jobs, const iss_window* windows, int32_t njobs, int64_t n_signal, int32_t* status_out,
+                        const iss_mixset* mixsets, const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms, int64_t nterms);
+int iss_adpcm_decode_mix(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, const iss_window* windows,
+                         int32_t njobs, int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_mixset* mixsets,
+                         const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms, int64_t nterms);
+int iss_msadpcm_decode_mix(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_adpcm_job* jobs, const iss_window* windows,
+                           int32_t njobs, int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_mixset* mixsets,
+                           const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms, int64_t nterms);
+
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */
 int iss_host_alloc(iss_ctx* ctx, size_t bytes, void** out);

@@ -45,6 +45,11 @@ def build_parser():
     ap.add_argument('--channels', choices=['mix', 'split'], default='mix',
                     help="with -b None: 'split' segments every channel of a file on its own (two-channel call recordings, multi-track "
                          "broadcast files) and writes <basename>.ch<k>.<format> per channel; 'mix' downmixes as ever")
+    ap.add_argument('--mixes', default=None, metavar='SPEC',
+                    help='with -b None: segment weighted mixes of the channels of every file, each on its own, and write '
+                         '<basename>.mix<k>.<format> per mix.  Mixes are separated by commas, terms joined by "+": "0+1,2+3" is the '
+                         'mean of channels 0 and 1 and the mean of 2 and 3; a mix with any WEIGHT*CHANNEL term is a weighted sum, '
+                         'in which a bare channel has weight 1 and nothing is divided: "0.7*4+0.7*5+1*2"')
     return ap
 
 
@@ -57,6 +62,19 @@ def main(argv=None):
         build_parser().error('--channels split needs -b None (ffmpeg downmixes every file)')
     if args.channels == 'split' and int(os.environ.get('WORLD_SIZE', '1')) != 1:
         build_parser().error('--channels split runs on one GPU')
+    mixes = None
+    if args.mixes is not None:
+        if ffmpeg is not None:
+            build_parser().error('--mixes needs -b None (ffmpeg downmixes every file)')
+        if args.channels == 'split':
+            build_parser().error('--mixes and --channels split exclude each other')
+        if int(os.environ.get('WORLD_SIZE', '1')) != 1:
+            build_parser().error('--mixes runs on one GPU')
+        from inaspeechsegmenter_amd.resample import parse_mixes
+        try:
+            mixes = parse_mixes(args.mixes)
+        except ValueError as exc:
+            build_parser().error(str(exc))
     if ffmpeg is None:
         print('Disabling ffmpeg. WAV (PCM, float, G.711, IMA and Microsoft ADPCM), FLAC, AIFF, AU, CAF, Wave64 and RF64 files are read directly. '
               + ('Files at other rates or with several channels are resampled on the GPU.' if args.resample
@@ -78,7 +96,8 @@ def main(argv=None):
         warnings.simplefilter('ignore')
         if world == 1:
             seg.batch_process(inputs, outputs, verbose=True, output_format=args.export_format,
-                              **({'channels': 'split'} if args.channels == 'split' else {}))
+                              **({'channels': 'split'} if args.channels == 'split' else {}),
+                              **({} if mixes is None else {'mixes': mixes}))
             return 0
         import torch
         import torch.distributed as dist
