@@ -119,8 +119,9 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     }
     unsigned wdst0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(sB_base + w_plane * 2048 + w_half * 1024));     // the wave's piece in tap 0's tile
     auto load_weight_tap = [&](int c0, int v) {      // v: compile-time
-        const uint16_t* src = (w_plane ? p.wl : p.wh) + (v * p.Cin + c0);
-        asm volatile("" : "+s"(wdst0));              // (one scalar add per piece instead of NT hoisted destinations)
+        int cin = p.Cin;
+        asm volatile("" : "+s"(wdst0), "+s"(cin));   // (a few scalar instructions per piece instead of NT hoisted destinations and sources)
+        const uint16_t* src = (w_plane ? p.wl : p.wh) + (v * cin + c0);
         glds16(src, boff_w, wdst0 + (unsigned)(v * F2_BST));
     };
     unsigned bread = sB_base + (unsigned)((2 * li + (lh ^ ((li >> 3) & 1))) * 16);
@@ -135,9 +136,16 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     const int magicW = (65536 + p.W - 1) / p.W;      // x / W == (x * magicW) >> 16 (host-checked range)
     const unsigned cin4 = (unsigned)p.Cin * 4u, cg16 = (unsigned)cg * 16u;
     auto fetch_consts = [&](int c0) {
-        const unsigned o = (unsigned)(c0 + cg * 4);
-        fsw = *reinterpret_cast<const float4*>(p.f_wsum + o);
-        fbw = *reinterpret_cast<const float4*>(p.f_bias + o);
+        // (opaque scalar base + the lane's 32-bit byte offset: no 64-bit address per lane and chunk waits in VGPRs)
+        typedef const char __attribute__((address_space(1)))* GBytes;
+        typedef const f32x4 __attribute__((address_space(1)))* GF4;
+        GBytes ws = (GBytes)(p.f_wsum + c0), bs = (GBytes)(p.f_bias + c0);
+        asm volatile("" : "+s"(ws), "+s"(bs));
+        unsigned o = cg16;
+        asm volatile("" : "+v"(o));                  // (its zero extension in this block: the load takes base and offset as they are)
+        const f32x4 w4 = *(GF4)(ws + o), b4 = *(GF4)(bs + o);
+        fsw = make_float4(w4[0], w4[1], w4[2], w4[3]);
+        fbw = make_float4(b4[0], b4[1], b4[2], b4[3]);
     };
     // fetch of slice q in three pieces: (1) pixel -> (dy, x); (2) window, row, masks; (3) address + load
     int f_x, f_dy, f_row;
@@ -145,8 +153,10 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
         const int qq = 64 * q < u.need ? q : 0;      // unneeded slices re-load slice 0
         int pr = prow;
         if (q == WQ_NFV - 1 && WQ_PIX % 64 != 0) pr = prow < WQ_PIX % 64 ? prow : 0;     // (pixels beyond the buffer: never written)
-        int x = u.fy * p.W + u.fx + pr + 64 * qq;
-        asm volatile("" : "+v"(x));                // (opaque: the same tile is fetched once per chunk, and hipcc would keep all of it)
+        int xs = u.fy * p.W + u.fx + 64 * qq;      // (wave-uniform)
+        asm volatile("" : "+s"(xs));               // (opaque: the same tile is fetched once per chunk, and hipcc would keep all of it --
+                                                   // pinned on the scalar, or the 26 sums xs + pr wait in VGPRs through the chunk loop)
+        const int x = xs + pr;
         f_dy = (x * magicW) >> 16;
         f_x = x - f_dy * p.W;
     };
@@ -255,12 +265,19 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     int rowb = ep.cout * 4;                          // bytes per pooled output row
     float e_x;
     unsigned e_off;
+    // An accumulator value for the VALU, taken from its accumulation register in the piece that needs it: left to hipcc, a block
+    // that drains the other set copies all 128 of its values into VGPRs up front, which pushed this kernel into scratch.
+    auto acc_rd = [&](const floatx16& acc, int i) {  // i: compile-time
+        float t;
+        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(t) : "a"(acc[i]));
+        return t;
+    };
     auto epi_a = [&](const floatx16& acc, int g) {   // window maximum, first half
-        e_x = fmaxf(acc[4 * g], acc[4 * g + 1]);
+        e_x = fmaxf(acc_rd(acc, 4 * g), acc_rd(acc, 4 * g + 1));
         asm volatile("" : "+v"(e_x));
     };
     auto epi_b = [&](const floatx16& acc, int cb, int g) {      // second half, + bias, relu
-        e_x = fmaxf(fmaxf(e_x, acc[4 * g + 2]), acc[4 * g + 3]);
+        e_x = fmaxf(fmaxf(e_x, acc_rd(acc, 4 * g + 2)), acc_rd(acc, 4 * g + 3));
         e_x = fmaxf(e_x + (cb ? ebias1 : ebias0), 0.f);
         asm volatile("" : "+v"(e_x));
     };
@@ -273,10 +290,10 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     int e_lim = 0;                                   // rows of the tile that exist - the lane's first row: unit (rb, g) is stored iff rb * 32 + 8 g < e_lim
     unsigned e_inv = E_INVALID;
     auto epih_a = [&](const floatx16& acc, int g) {
-        asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(e_x) : "v"(acc[4 * g]), "v"(acc[4 * g + 1]), "v"(acc[4 * g + 2]));
+        asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(e_x) : "v"(acc_rd(acc, 4 * g)), "v"(acc_rd(acc, 4 * g + 1)), "v"(acc_rd(acc, 4 * g + 2)));
     };
     auto epih_b = [&](const floatx16& acc, int cb, int g) {
-        asm volatile("v_max_f32 %0, %0, %1" : "+v"(e_x) : "v"(acc[4 * g + 3]));
+        asm volatile("v_max_f32 %0, %0, %1" : "+v"(e_x) : "v"(acc_rd(acc, 4 * g + 3)));
         e_x = fmaxf(e_x + (cb ? ebias1 : ebias0), 0.f);
         asm volatile("" : "+v"(e_x));
     };
