@@ -213,6 +213,7 @@ def lib():
         'iss_prof_get_instance': (C.c_int, [vp, C.c_int, C.c_char_p, i32, pd, pi64, pd]),
         'iss_set_diag': (C.c_int, [vp, C.c_uint32]),
         'iss_scribble': (C.c_int, [vp, C.c_uint32]),
+        'iss_diag_split16': (C.c_int, [vp, pf, i64, i32, i32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
         'iss_viterbi_f64': (C.c_int, [pd, i64, i32, pd, pi32]),
         'iss_viterbi_f32': (C.c_int, [pf, i64, i32, pd, pi32]),
         'iss_energy_viterbi': (C.c_int, [pf, i64, C.c_double, C.c_double, C.c_double, pd, pi32]),
@@ -801,6 +802,16 @@ class Context:
         """Test aid: fill every scratch buffer of the context (capacity, slack included) with the 32-bit `word`; resident
         signal, features, tables and parameters are left alone (include/iss.h iss_scribble)."""
         self._ck(self._L.iss_scribble(self._h, int(word) & 0xFFFFFFFF), 'iss_scribble')
+
+    def diag_split16(self, x, f16, form=0):
+        """Test aid: (hi, lo) uint16 patterns of the conv kernels' operand split of the float32 values `x`, fp16 or bf16 halves;
+        form 0 / 1 = four at a time / one at a time (include/iss.h iss_diag_split16)."""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        hi, lo = np.empty(x.size, np.uint16), np.empty(x.size, np.uint16)
+        p16 = C.POINTER(C.c_uint16)
+        self._ck(self._L.iss_diag_split16(self._h, x.ctypes.data_as(C.POINTER(C.c_float)), x.size, int(bool(f16)), int(form),
+                                          hi.ctypes.data_as(p16), lo.ctypes.data_as(p16)), 'iss_diag_split16')
+        return hi, lo
 
     def synchronize(self):
         self._ck(self._L.iss_synchronize(self._h), 'iss_synchronize')

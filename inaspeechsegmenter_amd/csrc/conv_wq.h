@@ -21,6 +21,10 @@
 //   * TWO footprints of 800 pixels beside the 60 KB of resident weights = exactly 160 KB: tile t of a group lives in
 //     footprint t; the next block's footprint is fetched, converted and stored into the OTHER buffer in pieces of <= 6
 //     instructions spread over the slots of the current block;
+//   * a tile's footprint is built once per 16-channel chunk, and where its slices lie does not depend on the chunk: the
+//     block that builds it for chunk 0 computes, per slice, the lane's byte offset and two flag bits and keeps them (28
+//     VGPRs for the group's two tiles); the blocks that build it for the other chunks fetch a slice with ONE instruction,
+//     global_load_dwordx4 at scalar base + saved offset (profiles/conv2_front_end_ab.md);
 //   * ONE barrier per block, at the start of its last tap (every fragment read of the block has been issued and waited
 //     for, every store into the other footprint is done): behind it the next block's first fragments are read and, every
 //     second block, the next 16-channel chunk's weights are fetched by LDS-DMA, under the last tap's MFMAs;
@@ -130,7 +134,12 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     // ---- footprint slices: thread -> pixel 64 q + (tid >> 2), channels [c0 + 4 (tid & 3), + 4) = k-half cg >> 1, 8-byte half cg & 1
     const int cg = tid & 3, prow = tid >> 2;
     float4 fv[WQ_NFV];
-    unsigned fm[WQ_NFV];                             // per slice: bit 0 = pixel belongs to the second window, bit 1 = it lies on an odd row
+    // Slice geometry, kept per tile of the group: everything the fetch of a slice computes -- pixel -> (row, x), window, row parity,
+    // byte offset -- depends on (tile, slice, lane) only, and a tile's footprint is built once per 16-channel chunk.  The blocks that
+    // build a chunk-0 footprint (the prologue; the t == 0 block of a group's first chunk: tile 1; the t == 1 block of its last
+    // chunk: the next group's tile 0) compute it, every other block loads with the saved offset behind the scalar base p.in + chunk.
+    unsigned go[G][WQ_NFV];                          // per tile and slice: the lane's byte offset behind p.in + c0 (< 2^32, host-checked)
+    unsigned gfl[G];                                 // per tile, two bits per slice q: bit 2 q = pixel belongs to the second window, bit 2 q + 1 = it lies on an odd row
     float4 fsw = make_float4(0.f, 0.f, 0.f, 0.f), fbw = fsw;     // weight sums / bias of this thread's 4 first-layer channels
     Win wx = {}, wpend = {};
     const int magicW = (65536 + p.W - 1) / p.W;      // x / W == (x * magicW) >> 16 (host-checked range)
@@ -154,21 +163,32 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
         int pr = prow;
         if (q == WQ_NFV - 1 && WQ_PIX % 64 != 0) pr = prow < WQ_PIX % 64 ? prow : 0;     // (pixels beyond the buffer: never written)
         int xs = u.fy * p.W + u.fx + 64 * qq;      // (wave-uniform)
-        asm volatile("" : "+s"(xs));               // (opaque: the same tile is fetched once per chunk, and hipcc would keep all of it --
-                                                   // pinned on the scalar, or the 26 sums xs + pr wait in VGPRs through the chunk loop)
+        asm volatile("" : "+s"(xs));               // (opaque, pinned on the scalar: what is worth keeping through the chunk loop is the
+                                                   // finished offset, go[][]; left alone, hipcc also keeps the 26 sums xs + pr in VGPRs)
         const int x = xs + pr;
         f_dy = (x * magicW) >> 16;
         f_x = x - f_dy * p.W;
     };
-    auto fetch_2 = [&](int q) {
+    auto fetch_2 = [&](int bt, int q) {
         int y = f_dy;
         const bool second = y >= p.H;
         y -= second ? p.H : 0;
-        fm[q] = (second ? 1u : 0u) | ((unsigned)(y & 1) << 1);
+        const unsigned bits = (second ? 1u : 0u) | ((unsigned)(y & 1) << 1);
+        gfl[bt] = q == 0 ? bits : (gfl[bt] | (bits << (2 * q)));
         f_row = y + (second ? wx.wr1 : wx.wr0) - p.f_rmin;
     };
-    auto fetch_3 = [&](int c0, int q) {
-        fv[q] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p.in + c0) + ((unsigned)(f_row * p.W + f_x) * cin4 + cg16));
+    auto fetch_3 = [&](int bt, int q) { go[bt][q] = (unsigned)(f_row * p.W + f_x) * cin4 + cg16; };
+    // the load itself: scalar base + the saved 32-bit offset -- all a block that re-builds a tile for another chunk issues per slice
+    typedef const char __attribute__((address_space(1)))* GInBytes;
+    auto fetch_base = [&](int c0) {
+        GInBytes b = (GInBytes)(p.in + c0);
+        asm volatile("" : "+s"(b));                  // (one base per block, not one per slice or hoisted per chunk)
+        return b;
+    };
+    auto fetch_ld = [&](GInBytes base, int bt, int q) {
+        typedef const f32x4 __attribute__((address_space(1)))* GF4;
+        const f32x4 v = *(GF4)(base + go[bt][q]);
+        fv[q] = make_float4(v[0], v[1], v[2], v[3]);
     };
     const float f_lob = p.f_act == 1 ? 0.f : -INFINITY;
     float t0[4] = {0.f, 0.f, 0.f, 0.f}, t1[4] = {0.f, 0.f, 0.f, 0.f}, rs0 = 0.f, rs1 = 0.f;
@@ -191,8 +211,8 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     // conversion of slice q in six pieces of <= 6 instructions; two register sets (steps 12 and 13 convert two slices each)
     typedef unsigned u32x2h __attribute__((ext_vector_type(2)));
     struct Cv { float sc, ta, tb, tc, td; float4 v; bf16x4 h; };
-    auto convert_1 = [&](Cv& c, int q) {             // select the window's scale / shifts
-        const bool second = fm[q] & 1u;
+    auto convert_1 = [&](Cv& c, int bt, int q) {     // select the window's scale / shifts
+        const bool second = (gfl[bt] >> (2 * q)) & 1u;
         c.sc = second ? rs1 : rs0;
         c.ta = second ? t1[0] : t0[0]; c.tb = second ? t1[1] : t0[1]; c.tc = second ? t1[2] : t0[2]; c.td = second ? t1[3] : t0[3];
     };
@@ -214,7 +234,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
             c.v = make_float4(c.v.x - unpk16_lo<true>(hh[0]), c.v.y - unpk16_hi<true>(hh[0]), c.v.z - unpk16_lo<true>(hh[1]), c.v.w - unpk16_hi<true>(hh[1]));
         } else c.v = make_float4(c.v.x - (float)c.h[0], c.v.y - (float)c.h[1], c.v.z - (float)c.h[2], c.v.w - (float)c.h[3]);
     };
-    auto convert_6 = [&](Cv& c, int q, unsigned wbase) {      // lo parts + the two 8-byte stores; wbase = footprint base + wofs
+    auto convert_6 = [&](Cv& c, int bt, int q, unsigned wbase) {     // lo parts + the two 8-byte stores; wbase = footprint base + wofs
         bf16x4 l;
         if constexpr (F16) {
             u32x2h ll;
@@ -223,7 +243,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
         } else {
         l[0] = (__bf16)c.v.x; l[1] = (__bf16)c.v.y; l[2] = (__bf16)c.v.z; l[3] = (__bf16)c.v.w;
         }
-        const unsigned a = wbase + (unsigned)(wsgn * (int)((fm[q] >> 1) & 1u));
+        const unsigned a = wbase + (unsigned)(wsgn * (int)((gfl[bt] >> (2 * q + 1)) & 1u));
         // the last slice is half a slice (32 pixels = the threads of waves 0 and 1): a wave-uniform (scalar) branch
         static_assert(WQ_PIX % 64 == 0 || WQ_PIX % 64 == 32, "");
         if (q == WQ_NFV - 1 && WQ_PIX % 64 != 0 && wv >= 2) return;
@@ -353,12 +373,12 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
     wx = settle(windows_of(ug[0].wb)); wpend = windows_of(ug[1].wb);      // (blocks reload wpend in their step 13)
     fetch_consts(0);
 #pragma unroll
-    for (int q = 0; q < WQ_NFV; ++q) { fetch_1(ug[0], q); fetch_2(q); fetch_3(0, q); }
+    for (int q = 0; q < WQ_NFV; ++q) { fetch_1(ug[0], q); fetch_2(0, q); fetch_3(0, q); fetch_ld(fetch_base(0), 0, q); }
     conv_consts_1(); conv_consts_2(); conv_consts_3();
     Cv cva, cvb;
 #pragma unroll
     for (int q = 0; q < WQ_NFV; ++q) {
-        convert_1(cva, q); convert_2(cva, q); convert_3(cva); convert_4(cva); convert_5(cva); convert_6(cva, q, sF0 + wofs);
+        convert_1(cva, 0, q); convert_2(cva, q); convert_3(cva); convert_4(cva); convert_5(cva); convert_6(cva, 0, q, sF0 + wofs);
     }
 #pragma unroll
     for (int v = 0; v < NT; ++v) load_weight_tap(0, v);
@@ -406,6 +426,10 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
             const TGeo un2 = t == 0 ? (last_chunk ? ug[G] : ug[0]) : (last_chunk ? ug[G + 1] : ug[1]);
             const int nc0 = t == 0 ? c0 : (last_chunk ? 0 : c0 + F2_CH);
             const unsigned wbase = sF0 + (unsigned)((1 - t) * WQ_FB) + wofs;      // the OTHER footprint
+            // it holds tile bt of its group; GEO: this block builds it for chunk 0, so it computes the tile's slice geometry (go, gfl)
+            const int bt = 1 - t;
+            const bool GEO = (t == 0 && ZC) || (t == 1 && last_chunk);
+            const GInBytes fbase = fetch_base(nc0);
             unsigned vb0 = E_INVALID, vb1 = E_INVALID;
             int erows = 0;
             if (EP) { vb0 = epi_base(etile, 0); vb1 = epi_base(etile, 1); erows = tl.rows_of(etile); if (OUT_HL) { e_lim = erows - wrow; e_inv = E_INVALID; asm volatile("" : "+v"(e_inv)); } }
@@ -488,35 +512,35 @@ __global__ __launch_bounds__(256, 1) void conv_x3_wq_kernel(const ConvArgs p) {
                         if (v == 0 && s == 13) fetch_consts(nc0);
                         if (v == 13 && s == 18) wpend = windows_of(un2.wb);
                         if (v <= 10 && s >= 18 && s <= 20) {
-                            if (s == 18) fetch_1(un, v);
-                            if (s == 19) fetch_2(v);
-                            if (s == 20) fetch_3(nc0, v);
+                            if (GEO && s == 18) fetch_1(un, v);
+                            if (GEO && s == 19) fetch_2(bt, v);
+                            if (s == 20) { if (GEO) fetch_3(bt, v); fetch_ld(fbase, bt, v); }
                         }
                         if (v >= 8 && v <= 9 && s >= 21) {
-                            if (s == 21) fetch_1(un, v + 3);
-                            if (s == 22) fetch_2(v + 3);
-                            if (s == 23) fetch_3(nc0, v + 3);
+                            if (GEO && s == 21) fetch_1(un, v + 3);
+                            if (GEO && s == 22) fetch_2(bt, v + 3);
+                            if (s == 23) { if (GEO) fetch_3(bt, v + 3); fetch_ld(fbase, bt, v + 3); }
                         }
                         if (v == 2 && s == 12) conv_consts_1();
                         if (v == 2 && s == 13) conv_consts_2();
                         if (v == 2 && s == 14) conv_consts_3();
                         if (v >= 3 && v <= 13 && s >= 12 && s <= 17) {
                             const int q = v - 3;
-                            if (s == 12) convert_1(cva, q);
+                            if (s == 12) convert_1(cva, bt, q);
                             if (s == 13) convert_2(cva, q);
                             if (s == 14) convert_3(cva);
                             if (s == 15) convert_4(cva);
                             if (s == 16) convert_5(cva);
-                            if (s == 17) convert_6(cva, q, wbase);
+                            if (s == 17) convert_6(cva, bt, q, wbase);
                         }
                         if (v >= 11 && v <= 12 && s >= 18) {
                             const int q = v;
-                            if (s == 18) convert_1(cvb, q);
+                            if (s == 18) convert_1(cvb, bt, q);
                             if (s == 19) convert_2(cvb, q);
                             if (s == 20) convert_3(cvb);
                             if (s == 21) convert_4(cvb);
                             if (s == 22) convert_5(cvb);
-                            if (s == 23) convert_6(cvb, q, wbase);
+                            if (s == 23) convert_6(cvb, bt, q, wbase);
                         }
                     }
                     // ---- epilogue of the other accumulator set: 32 (accumulator, window) units of three pieces; slots 0..8 of the

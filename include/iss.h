@@ -784,6 +784,12 @@ int iss_prof_get_instance(iss_ctx* ctx, int index, char* name_out, int32_t name_
  * FLT_MAX to hold that.  What iss_flac_get_stage / iss_adpcm_get_stage would return is gone.  Not for production.     */
 int iss_scribble(iss_ctx* ctx, uint32_t word);
 
+/* The operand split of the conv kernels over an array: x[i] = hi + lo with hi = rne16(x[i]), lo = rne16(x[i] - hi), the
+ * halves fp16 (f16 != 0) or bf16, as 16-bit patterns in hi_out[i] / lo_out[i] (n values each, host memory like x).
+ * form 0: four values at a time, the way the kernels split an f32 input (split4_pk); form 1: one value at a time, the
+ * way their epilogues split an output.  Not for production.                                                          */
+int iss_diag_split16(iss_ctx* ctx, const float* x, int64_t n, int32_t f16, int32_t form, uint16_t* hi_out, uint16_t* lo_out);
+
 /* ------------------------------------------------------------------ host only
  * Viterbi smoothing, replaces pyannote_viterbi.py:118-224 `viterbi_decoding` on the
  * unconstrained path the segmenter uses (segmenter.py:72-73,176): float64 scores,
