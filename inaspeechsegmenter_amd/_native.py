@@ -47,6 +47,8 @@ SPLIT = np.dtype([('dst_stride', '<i8'), ('sel_begin', '<i4'), ('sel_count', '<i
 MIXSET = np.dtype([('dst_stride', '<i8'), ('mix_begin', '<i4'), ('mix_count', '<i4')])
 MIX = np.dtype([('term_begin', '<i4'), ('term_count', '<i4'), ('divisor', '<f8')])
 MIX_TERM = np.dtype([('channel', '<i4'), ('reserved', '<i4'), ('weight', '<f8')])
+# iss_survey_job (include/iss.h): a row of the survey entry points
+SURVEY_JOB = np.dtype([('src_offset', '<i8'), ('frames_in', '<i8'), ('channels', '<i4'), ('format', '<i4'), ('full', '<f8')])
 # ISS_FLAC_* frame status codes -> reason
 FLAC_STATUS = {1: 'reserved subframe type', 2: 'subframe header padding bit set', 3: 'wasted bits exceed the sample size',
                4: 'reserved residual coding method', 5: 'residual partition order does not fit the block',
@@ -158,6 +160,12 @@ def lib():
         'iss_flac_decode_mix': (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i32, i64, pi32, vp, vp, i64, vp, i64]),
         'iss_adpcm_decode_mix': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64, vp, i64]),
         'iss_msadpcm_decode_mix': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64, vp, i64]),
+        'iss_survey': (C.c_int, [vp, vp, i64, vp, vp, i32, vp]),
+        'iss_flac_survey': (C.c_int, [vp, vp, vp, i32, vp]),
+        'iss_adpcm_survey': (C.c_int, [vp, vp, vp, i32, vp]),
+        'iss_msadpcm_survey': (C.c_int, [vp, vp, vp, i32, vp]),
+        'iss_survey_geometry': (C.c_int, [pi32, pi32, pi32]),
+        'iss_survey_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_get_signal_pcm16': (C.c_int, [vp, pi16, i64, i64]),
         'iss_resample_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_flac_index': (C.c_int, [vp, i64, i64, vp, vp, i64, pi64, pi64, C.c_char_p, i32]),
@@ -600,6 +608,45 @@ class Context:
     def msadpcm_stats(self):
         """(Microsoft ADPCM decode launches, blocks decoded) since the context was created."""
         return self._counters('iss_msadpcm_stats')
+
+    # ---- channel survey (iss_survey*): level figures and cross-products of stored frames, nothing else of the context touched
+    def survey(self, src, jobs, windows=None, coder=None):
+        """iss_survey: src = 1-D uint8 array of the stored bytes of every job, jobs = rows of SURVEY_JOB; one H2D copy, one
+        launch of each survey kernel -> one resample.SurveyFields per job, valid on return.  windows: rows of WINDOW, one
+        beside every job: its bytes hold frames [s_begin, s_end) of the file and frames [out_begin, out_begin + out_count) are
+        surveyed.  coder ('flac', 'adpcm', 'msadpcm'; src is then None): iss_<coder>_survey over what the coder's last decode
+        call staged, src_offset of a row the index of the staged job."""
+        from .resample import SurveyFields, SURVEY_PAIR_CHANNELS
+        jb = np.ascontiguousarray(np.array(jobs, dtype=SURVEY_JOB).reshape(-1))
+        wn = None if windows is None else _window_rows(windows, jb.size)
+        chs = [int(c) for c in jb['channels']]
+        width = [6 * c + (c * (c - 1) // 2 if c <= SURVEY_PAIR_CHANNELS else 0) for c in chs]
+        out = np.zeros(max(sum(width), 1), dtype=np.float64)
+        tail = (C.c_void_p(jb.ctypes.data), None if wn is None else C.c_void_p(wn.ctypes.data), jb.size, C.c_void_p(out.ctypes.data))
+        if coder is None:
+            src = np.ascontiguousarray(src, dtype=np.uint8)
+            self._ck(self._L.iss_survey(self._h, C.c_void_p(src.ctypes.data), src.size, *tail), 'iss_survey')
+        else:
+            self._ck(getattr(self._L, f'iss_{coder}_survey')(self._h, *tail), f'iss_{coder}_survey')
+        res, pos = [], 0
+        for k, (c, w) in enumerate(zip(chs, width)):
+            r = out[pos:pos + w]
+            cnt = r[3 * c:6 * c].view(np.int64)
+            n = int(jb['frames_in'][k] if wn is None else wn['out_count'][k])
+            res.append(SurveyFields(n, r[2 * c:3 * c].copy(), cnt[:c].copy(), cnt[c:2 * c].copy(), cnt[2 * c:].copy(), r[:c].copy(),
+                                    r[c:2 * c].copy(), r[6 * c:].copy() if c <= SURVEY_PAIR_CHANNELS else None))
+            pos += w
+        return res
+
+    def survey_geometry(self):
+        """(frames per chunk, lanes per chunk, channels up to which pairs are computed) of the survey order."""
+        a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self._L.iss_survey_geometry(C.byref(a), C.byref(b), C.byref(c)), 'iss_survey_geometry')
+        return a.value, b.value, c.value
+
+    def survey_stats(self):
+        """(survey launches, jobs surveyed) since the context was created."""
+        return self._counters('iss_survey_stats')
 
     # ---- page-locked host arrays
     def pinned_empty(self, shape, dtype):

@@ -101,6 +101,10 @@ struct iss_ctx {
     // The two ADPCM coders share a kernel template and nothing of their state: a pass with files of both makes two calls
     IssCodec flac{"flac"}, adpcm{"adpcm"}, msadpcm{"msadpcm"};
 
+    // channel survey (survey.hip): uploaded bytes, job rows, per-chunk partial rows, result rows of the last call
+    DevBuf sv_src, sv_jobs, sv_ws, sv_res;
+    IssCounters sv_count;                 // survey_kernel launches, jobs
+
     // resident features
     DevBuf mspec, loge;
     int32_t T = 0;

@@ -1,0 +1,88 @@
+// How a stored sample becomes float64, and how a workgroup stages channels of interleaved frames in LDS: written once for
+// resample.hip (every resample_kernel instantiation) and survey.hip (survey_kernel).  Device code only; not part of the ABI.
+#pragma once
+#include "iss_internal.h"
+
+namespace {
+
+constexpr int RS_THREADS = 256;
+
+__device__ __forceinline__ double to_f64(uint8_t x) { return __ddiv_rn(__dsub_rn((double)x, 128.0), 128.0); }
+__device__ __forceinline__ double to_f64(int8_t x) { return __ddiv_rn((double)x, 128.0); }     // = the u8 twin x + 128
+__device__ __forceinline__ double to_f64(int16_t x) { return __ddiv_rn((double)x, 32768.0); }
+__device__ __forceinline__ double to_f64(int32_t x) { return __ddiv_rn((double)x, 2147483648.0); }
+__device__ __forceinline__ double to_f64(float x) { return (double)x; }
+__device__ __forceinline__ double to_f64(double x) { return x; }
+
+// G.711 expansion (include/iss.h states both): the decoded 16-bit value of a stored byte
+__device__ __forceinline__ int ulaw_value(uint32_t b) {
+    const uint32_t u = ~b & 0xFFu;
+    const int t = (int)((((u & 15u) << 3) + 0x84u) << ((u >> 4) & 7u));
+    return (u & 0x80u) ? 0x84 - t : t - 0x84;
+}
+__device__ __forceinline__ int alaw_value(uint32_t b) {
+    const uint32_t a = (b ^ 0x55u) & 0xFFu;
+    int t = (int)((a & 15u) << 4);
+    const int s = (int)((a >> 4) & 7u);
+    if (s == 0) t += 8;
+    else if (s == 1) t += 0x108;
+    else t = (t + 0x108) << (s - 1);
+    return (a & 0x80u) ? t : -t;
+}
+
+// one stored sample -> float64 with libsndfile's scaling: as stored, G.711, or byte-swapped (big-endian sources)
+template <typename T> struct LdPlain {
+    using type = T;
+    static __device__ __forceinline__ double get(const T* q) { return to_f64(*q); }
+};
+struct LdUlaw {
+    using type = uint8_t;
+    static __device__ __forceinline__ double get(const uint8_t* q) { return to_f64((int16_t)ulaw_value(*q)); }
+};
+struct LdAlaw {
+    using type = uint8_t;
+    static __device__ __forceinline__ double get(const uint8_t* q) { return to_f64((int16_t)alaw_value(*q)); }
+};
+struct LdSwapI16 {
+    using type = uint16_t;
+    static __device__ __forceinline__ double get(const uint16_t* q) { return to_f64((int16_t)__builtin_bswap16(*q)); }
+};
+struct LdSwapI32 {
+    using type = uint32_t;
+    static __device__ __forceinline__ double get(const uint32_t* q) { return to_f64((int32_t)__builtin_bswap32(*q)); }
+};
+struct LdSwapF32 {
+    using type = uint32_t;
+    static __device__ __forceinline__ double get(const uint32_t* q) { return (double)__uint_as_float(__builtin_bswap32(*q)); }
+};
+struct LdSwapF64 {
+    using type = uint64_t;
+    static __device__ __forceinline__ double get(const uint64_t* q) { return __longlong_as_double((long long)__builtin_bswap64(*q)); }
+};
+
+// frames s0 .. s0+len-1 of `gc` selected channels, each on its own: span[k * stride + .] = channel sel[k] (sel == NULL: channel
+// c0 + k).  Thread e takes (frame e / gc, channel e % gc): neighbouring lanes read neighbouring samples of a frame
+// (WIN: stage_span's rule -- s0 + k is the file's own frame, 0 outside [0, W.frames_total), read at W.in_begin less)
+template <typename L, bool WIN>
+__device__ __forceinline__ void stage_channels(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
+                                               double* __restrict__ span, int stride, int c0, int gc,
+                                               const int32_t* __restrict__ sel, const RsWinDev& W) {
+    using T = typename L::type;
+    const T* p = reinterpret_cast<const T*>(src);
+    const int total = len * gc;
+    for (int e = threadIdx.x; e < total; e += RS_THREADS) {
+        const int k = e / gc, kk = e - k * gc;
+        int64_t j = s0 + k;
+        double v = 0.0;
+        bool in = j >= 0 && j < n_in;
+        if constexpr (WIN) {
+            in = j >= 0 && j < W.frames_total;
+            j -= W.in_begin;
+            in = in && j >= 0 && j < n_in;                 // (the planner saw to it that a window reaches no unstaged frame)
+        }
+        if (in) v = L::get(p + j * ch + (sel ? sel[kk] : c0 + kk));
+        span[(int64_t)kk * stride + k] = v;
+    }
+}
+
+}  // namespace

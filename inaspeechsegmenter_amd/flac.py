@@ -125,6 +125,9 @@ class FlacSource(CodedSource):
     'resample'."""
     __slots__ = ()
     pass_order = 1
+    coder = 'flac'                                               # iss_flac_survey surveys what this class's launch staged
+    stage_format = property(lambda self: _native.RS_FORMAT[np.dtype('<i4' if self.s.bps > 16 else '<i2')])
+    full = property(lambda self: R.SURVEY_FULL[{8: 'i8', 16: 'i16', 24: 'i24'}[self.s.bps]])
     batchable = property(lambda self: self.kind != 'float')
     payload = property(lambda self: self.s.audio)
     frames = property(lambda self: self.s.frames)
@@ -159,7 +162,8 @@ class FlacSource(CodedSource):
 
 class FlacExcerpt(FlacSource):
     """Outputs [a, b) of a FLAC file for the windowed decode: the frames that cover the stored-rate samples the excerpt needs
-    ('pcm': [a, b) themselves; 'resample': resample.input_span of them) and their bytes only.  Its `frames` keep the file's sample
+    ('pcm': [a, b) themselves; 'resample': resample.input_span of them) and their bytes only.  kind 'stage' (io.survey_sources):
+    a and b count stored frames, and those are staged for the survey kernel (TO_STAGE, no filter).  Its `frames` keep the file's sample
     numbering; a malformed frame is named by its byte offset in the file.  Frames outside the run are not decoded, so not checked.
     `sel` ('resample' only): the channels to write apart (None: their average)."""
     __slots__ = ('k0', 'rows', 'win', '_payload')
@@ -169,7 +173,7 @@ class FlacExcerpt(FlacSource):
     def __init__(self, stream, kind, a, b, sel=None):
         self.s, self.kind, self.size = stream, kind, b - a
         self.sel = selection(sel)
-        if kind == 'pcm':
+        if kind in ('pcm', 'stage'):
             s0, s1 = a, b
         else:
             j_lo, j_hi = R.input_span(stream.sr, stream.n, a, b - a)

@@ -22,6 +22,8 @@ samples of the 16 kHz mono twin or a windowed source holding only the bytes it n
 `mix_source` and `mix_excerpts` read weighted sums of a file's channels (resample.py states a mix) where the two above read single
 channels: the same sources, an entry of whose selection is a resample.Mix; `decode_mixes` and `decode_mix_excerpts` are the
 host-only twins.
+`survey_sources` reads what a channel survey needs of a file -- per-channel levels and the cross-products between channels of the
+stored frames, measured on the device (Segmenter.survey_channels) --, `survey_channels` is its host-only twin.
 """
 import os
 import struct
@@ -507,3 +509,101 @@ def decode_mix_excerpts(medianame, ranges, mixes, resample=True):
     for range r, by the host builds of the decoders on the frames, blocks and bytes of each excerpt alone and a windowed
     resample.mix_ref per mix."""
     return [s.host() for s in mix_excerpts(medianame, ranges, mixes, resample)[1]]
+
+
+# ---------------------------------------------------------------------------------------------- channel survey
+def survey_bounds(name, frames, sr, start_sec, stop_sec):
+    """-> (a, b): the stored frames of a file of `frames` frames at `sr` Hz that the range (start_sec, stop_sec) means:
+    a = floor(start_sec * sr + 0.5), b = frames for stop_sec None, else min(frames, floor(stop_sec * sr + 0.5)) -- excerpt_bounds'
+    rounding at the file's own rate.  ValueError (naming the file) for a range that holds no frame of the file."""
+    import math
+    _check_range(name, start_sec, stop_sec)
+    a = math.floor(start_sec * sr + 0.5)
+    b = frames if stop_sec is None or math.isinf(stop_sec) else min(frames, math.floor(stop_sec * sr + 0.5))
+    if b - a < 1:
+        raise ValueError(f'{name}: the range ({start_sec!r}, {stop_sec!r}) holds no frame of the file, which lasts '
+                         f'{frames / sr:.3f} s ({frames} frames at {sr} Hz)')
+    return a, b
+
+
+def _wav_bits(buf):
+    """Bits per sample of the `fmt ` chunk of a RIFF/WAVE buffer _parse_wav has read."""
+    pos = 12
+    while pos + 8 <= len(buf):
+        cid, size = buf[pos:pos + 4], struct.unpack_from('<I', buf, pos + 4)[0]
+        if cid == b'fmt ':
+            return struct.unpack_from('<H', buf, pos + 22)[0]
+        pos += 8 + size + (size & 1)
+    return 0
+
+
+def _survey_parsed(medianame, header_ok):
+    """-> (h, full): the file parsed for a survey -- a flac.FlacStream, a sndfmt.Sound, or with header_ok the
+    sndfmt.SoundHeader of a plain RIFF/WAVE file, whose samples are then read by byte ranges -- and the fullscale threshold of
+    its stored format (resample.SURVEY_FULL)."""
+    from . import flac, sndfmt
+    _check_local(medianame)
+    h = sndfmt.read_header(medianame) if header_ok else None
+    if h is None:
+        buf = _read_file(medianame)
+        h = _classify(buf, medianame)
+        if h is None:                                             # what _parse_wav reads (or refuses)
+            x, sr = _parse_wav(buf, medianame)
+            kind = {'uint8': 'u8', 'int16': 'i16', 'int32': 'i32', 'float32': 'f32', 'float64': 'f64'}[x.dtype.name]
+            full = R.SURVEY_FULL['i24' if kind == 'i32' and _wav_bits(buf) == 24 else kind]
+            x = np.ascontiguousarray(x)                           # (24-bit: widened, as the whole-file read stages it)
+            return sndfmt.Sound(medianame, sr, 1 if x.ndim == 1 else x.shape[1], kind, False, x.reshape(-1).view(np.uint8), 0), full
+    if isinstance(h, flac.FlacStream):
+        return h, R.SURVEY_FULL[{8: 'i8', 16: 'i16', 24: 'i24'}[h.bps]]
+    return h, R.SURVEY_FULL[h.kind]
+
+
+def _survey_spans(h, ranges):
+    return [(0, h.n)] if ranges is None else [survey_bounds(h.name, h.n, h.sr, start, stop) for start, stop in ranges]
+
+
+def survey_channels(medianame, ranges=None):
+    """Host-only twin of Segmenter.survey_channels: the file decoded as decode_source decodes it, then resample.survey_ref on
+    its frames -> a survey.ChannelSurvey of the whole file (ranges None), or one per time range (start_sec, stop_sec | None),
+    frames [a, b) by survey_bounds.  ValueError for a range that holds no frame."""
+    from .survey import ChannelSurvey
+    if ranges is not None:
+        ranges = [tuple(r) for r in ranges]
+        for start, stop in ranges:
+            _check_range(medianame, start, stop)
+    h, full = _survey_parsed(medianame, False)
+    spans = _survey_spans(h, ranges)
+    x = h.stored()
+    out = [ChannelSurvey(R.survey_ref(x, full, a, b), h.sr, a) for a, b in spans]
+    return out[0] if ranges is None else out
+
+
+def survey_sources(medianame, ranges=None):
+    """What the device surveys for `medianame` -> (sr, [(source or resample.SurveyFields, first frame) per range]; one entry, the
+    whole file, for ranges None).  A source stages only what its frames [a, b) need: the bytes of a plain RIFF/WAVE file, read by
+    byte ranges (sources.RawSurvey); the covering frames of a FLAC stream or blocks of an ADPCM file, for a decode to the staging
+    buffer without a filter (kind 'stage' of flac.FlacExcerpt, sndfmt.AdpcmExcerpt and its Microsoft twin).  A file without
+    frames is surveyed here (SurveyFields of no samples)."""
+    from . import flac, sndfmt
+    from .sources import RawSurvey
+    if ranges is not None:
+        ranges = [tuple(r) for r in ranges]
+        for start, stop in ranges:
+            _check_range(medianame, start, stop)
+    h, full = _survey_parsed(medianame, True)
+    out = []
+    for a, b in _survey_spans(h, ranges):
+        if b == a:
+            out.append((R.survey_ref(np.zeros((0, h.ch)), full), a))
+            continue
+        if isinstance(h, flac.FlacStream):
+            src = flac.FlacExcerpt(h, 'stage', a, b)
+        elif h.kind in sndfmt._BLOCK:
+            src = sndfmt.block_excerpt(h, 'stage', a, b)
+        else:
+            sub, _ = sndfmt.sub_sound(h, a, b)
+            x, fmt = sub.raw()
+            src = RawSurvey(x, h.sr, fmt, full, a, b, first=a, total=h.n)
+        src.size = -(-(b - a) * R.SR_OUT // h.sr)                 # what packs it into a pass: its length at 16 kHz
+        out.append((src, a))
+    return h.sr, out

@@ -248,3 +248,101 @@ def mixdown(x, mix):
 def mix_ref(x, sr, mix, out_begin=0, out_count=None, in_begin=0, frames_total=None):
     """resample_ref with `mixdown(x, mix)` in place of the downmix -> 16 kHz mono int16 (windows as resample_ref states them)."""
     return quantise(resample_float(mixdown(x, mix), sr, out_begin, out_count, in_begin, frames_total))
+
+
+# ---------------------------------------------------------------------------------------------- channel survey: the reference
+SURVEY_CHUNK, SURVEY_LANES, SURVEY_PAIR_CHANNELS = 1024, 256, 16      # include/iss.h: ISS_SURVEY_CHUNK, four waves of 64, ISS_SURVEY_PAIR_CHANNELS
+
+
+class SurveyFields(NamedTuple):
+    """What a survey measures of stored frames [a, b) (include/iss.h, "Channel survey"): per channel peak, s1, s2 (float64) and
+    zeros, fullscale, nonfinite (int64), and s12 = the sums of products of the pairs (0,1), (0,2), ..., (1,2), ... in that order
+    (float64; None for more than SURVEY_PAIR_CHANNELS channels)."""
+    n: int
+    peak: np.ndarray
+    zeros: np.ndarray
+    fullscale: np.ndarray
+    nonfinite: np.ndarray
+    s1: np.ndarray
+    s2: np.ndarray
+    s12: object
+
+
+# the largest positive value each stored format holds, as the float64 the readers give it (`full` of a job row)
+SURVEY_FULL = {'u8': 127 / 128, 'i8': 127 / 128, 'i16': 32767 / 32768, 'i24': (2 ** 31 - 256) / 2 ** 31, 'i32': (2 ** 31 - 1) / 2 ** 31,
+               'ulaw': 32124 / 32768, 'alaw': 32256 / 32768, 'f32': 1.0, 'f64': 1.0, 'ima': 32767 / 32768, 'ms': 32767 / 32768}
+
+
+def _survey_chunk_sums(terms):
+    """The chunk sums of the rows of `terms` (n, Q), n a multiple of SURVEY_CHUNK but for the last chunk -> (chunks, Q)."""
+    n, nq = terms.shape
+    per = SURVEY_CHUNK // SURVEY_LANES
+    m = -(-n // SURVEY_CHUNK)
+    if n != m * SURVEY_CHUNK:
+        pad = np.zeros((m * SURVEY_CHUNK, nq))
+        pad[:n] = terms
+        terms = pad
+    rows = terms.reshape(m, per, SURVEY_LANES // 64, 64, nq)
+    acc = np.zeros((m, SURVEY_LANES // 64, 64, nq))
+    for r in range(per):
+        acc = acc + rows[:, r]
+    s = 32
+    while s:
+        acc = acc[:, :, :s] + acc[:, :, s:2 * s]
+        s //= 2
+    w = acc[:, :, 0]
+    return ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+
+
+_SURVEY_BLOCK = 256 * SURVEY_CHUNK                   # rows handled at a time: bounds the memory, not the order
+
+
+def survey_sum(terms):
+    """The sums of the columns of `terms` (n, Q) float64 in the SURVEY ORDER, the one order the device and the host twin share:
+    the rows in chunks of SURVEY_CHUNK; within a chunk lane t of 256 starts from +0.0 and adds rows t, t + 256, t + 512, t + 768
+    (a missing row adds nothing: +0.0 here, which changes no partial sum, as none is ever -0.0); each wave's 64 lanes by the
+    tree `lane l += lane l + s`, s = 32 .. 1; the chunk's sum ((wave 0 + wave 1) + wave 2) + wave 3; the chunk sums added in
+    ascending order from +0.0.  Every addition is numpy's float64 addition of two arrays: rounded on its own."""
+    terms = np.asarray(terms, dtype=np.float64)
+    total = np.zeros(terms.shape[1])
+    for r0 in range(0, terms.shape[0], _SURVEY_BLOCK):
+        for chunk in _survey_chunk_sums(terms[r0:r0 + _SURVEY_BLOCK]):
+            total = total + chunk
+    return total
+
+
+def survey_pairs(ch):
+    """The pairs c < d in the order s12 lists them."""
+    return [(c, d) for c in range(ch) for d in range(c + 1, ch)]
+
+
+def survey_ref(x, full, a=0, b=None):
+    """The survey of frames [a, b) of stored samples x ((n,) or (n, C), any io dtype; b None: to the end) against the fullscale
+    threshold `full` -> SurveyFields.  The numpy statement of include/iss.h's definition: samples scaled by io._to_float, a
+    non-finite sample counted and taken as 0.0 everywhere else, peak and counts exact, the three sums by `survey_sum`."""
+    from .io import _to_float
+    x = np.asarray(x)
+    if x.ndim == 1:
+        x = x[:, None]
+    b = x.shape[0] if b is None else min(int(b), x.shape[0])
+    a = int(a)
+    if a < 0 or a > b:
+        raise ValueError(f'frames [{a}, {b}) of {x.shape[0]}')
+    n, ch = b - a, x.shape[1]
+    pairs = survey_pairs(ch) if ch <= SURVEY_PAIR_CHANNELS else None
+    pc, pd = ([c for c, _ in pairs], [d for _, d in pairs]) if pairs else ([], [])
+    peak, sums = np.zeros(ch), np.zeros(2 * ch + len(pc))
+    zeros, fullscale, nonfinite = (np.zeros(ch, dtype=np.int64) for _ in range(3))
+    for r0 in range(a, b, _SURVEY_BLOCK):                        # blocks of whole chunks counted from a
+        v = _to_float(x[r0:min(b, r0 + _SURVEY_BLOCK)], np.float64)
+        bad = ~np.isfinite(v)
+        if bad.any():
+            v = np.where(bad, 0.0, v)
+        mag = np.abs(v)
+        peak = np.maximum(peak, mag.max(axis=0))
+        zeros += (v == 0.0).sum(axis=0)
+        fullscale += (mag >= float(full)).sum(axis=0)
+        nonfinite += bad.sum(axis=0)
+        for chunk in _survey_chunk_sums(np.concatenate([v, v * v] + ([v[:, pc] * v[:, pd]] if pc else []), axis=1)):
+            sums = sums + chunk
+    return SurveyFields(n, peak, zeros, fullscale, nonfinite, sums[:ch], sums[ch:2 * ch], None if pairs is None else sums[2 * ch:])

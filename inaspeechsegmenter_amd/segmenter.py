@@ -761,6 +761,105 @@ class Segmenter:
         sel, sigs = iss_io.mix_excerpts(medianame, ranges, mixes, self.resample)
         return self._segment_pairs(medianame, ranges, sel, sigs, batch_files, batch_seconds)
 
+    # ---- channel survey: what the channels of a file hold, measured on the device (an extension)
+    def _no_ffmpeg_survey(self):
+        if self.ffmpeg is not None:
+            raise ValueError(f'channels are surveyed without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={self.ffmpeg!r} downmixes '
+                             f'every file with -ac 1')
+
+    def _survey_pass(self, items, out, on_error):
+        """One pass of surveys: items = [(index into out, source, sr, first frame)].  All sources of a class share one launch
+        (sources.Group.survey), the classes in pass order.  A malformed file: on_error(index, exception), or raised without it."""
+        from .sources import Group
+        from .survey import ChannelSurvey
+        by_class = {}
+        for it in items:
+            by_class.setdefault(type(it[1]), []).append(it)
+        for cls in sorted(by_class, key=lambda c: c.pass_order):
+            mine = by_class[cls]
+            group = Group(self.ctx, cls, [(src, 0) for _, src, _, _ in mine])
+            fields = group.survey()
+            bad = {}
+            group.check(None if on_error is None else bad.__setitem__)
+            for k, (i, _, sr, first) in enumerate(mine):
+                if k in bad:
+                    on_error(i, bad[k])
+                else:
+                    out[i] = ChannelSurvey(fields[k], sr, first)
+
+    def survey_channels(self, medianame, ranges=None):
+        """What the channels of `medianame` hold, measured on the device in one pass over the stored samples -> a
+        survey.ChannelSurvey of the whole file, or with ranges = [(start_sec, stop_sec | None)] one per range (stored frames
+        [a, b) by io.survey_bounds: the excerpt calls' rounding at the file's own rate).  Per channel: peak, digital zeros,
+        fullscale and non-finite samples, DC and RMS; per pair of channels (files of up to 16) the correlation; and what the
+        default downmix loses (`downmix_loss_db`), which channels carry signal (`active()`, the list to pass as `channels=`)
+        and which pairs are polarity-inverted (`inverted()`).  Equal to the bit, in every field, to io.survey_channels, the
+        host-only twin (include/iss.h states the figures and the order of the sums).  Only the bytes, FLAC frames and ADPCM
+        blocks the ranges need are staged.  ValueError, naming the file: a range that holds no frame, a malformed FLAC frame
+        or ADPCM block among those decoded, an http source; naming the argument with ffmpeg set."""
+        from . import pipeline
+        from .survey import ChannelSurvey
+        self._no_ffmpeg_survey()
+        sr, entries = iss_io.survey_sources(medianame, ranges)
+        out = [None if isinstance(src, Source) else ChannelSurvey(src, sr, first) for src, first in entries]
+        todo = [(k, src, sr, first) for k, (src, first) in enumerate(entries) if isinstance(src, Source)]
+        for idx in pipeline.cut_passes([t[1] for t in todo], None, None):
+            self._survey_pass([todo[k] for k in idx], out, None)
+        return out[0] if ranges is None else out
+
+    def survey_files(self, linput, batch_files=None, batch_seconds=None):
+        """survey_channels for many files -> one entry per file of `linput`: its survey.ChannelSurvey, or for a file that
+        cannot be read the text batch_process reports for it ('error: <class> <message>').  The files are read by four
+        threads and packed into passes as batch_process packs them (at most batch_files files / batch_seconds of audio);
+        all files of a pass that share a source class share ONE survey launch, so a pass costs one launch per class present
+        (stored PCM / float / G.711, FLAC, IMA ADPCM, Microsoft ADPCM), the three decoders with their decode launch in front."""
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+        from . import pipeline
+        from .survey import ChannelSurvey
+        self._no_ffmpeg_survey()
+        linput = list(linput)
+        batch_files, batch_seconds = pipeline._limits(batch_files, batch_seconds)
+        out = [None] * len(linput)
+
+        def failed(i, exc):
+            out[i] = 'error: %s %s' % (type(exc), exc)
+
+        def read(name):
+            try:
+                return iss_io.survey_sources(name)
+            except Exception as exc:                             # this file's error; the others go on
+                return exc
+
+        cur, items = pipeline._Batch(), []
+        with ThreadPoolExecutor(4) as pool:
+            ahead, names = deque(), iter(enumerate(linput))
+            while True:
+                while len(ahead) < 8:                            # a few files read ahead of the pass being packed, not all of them
+                    nxt = next(names, None)
+                    if nxt is None:
+                        break
+                    ahead.append((nxt[0], pool.submit(read, nxt[1])))
+                if not ahead:
+                    break
+                i, fut = ahead.popleft()
+                got = fut.result()
+                if isinstance(got, Exception):
+                    failed(i, got)
+                    continue
+                sr, ((src, first),) = got
+                if not isinstance(src, Source):
+                    out[i] = ChannelSurvey(src, sr, first)
+                    continue
+                cur.sigs.append(src)
+                items.append((i, src, sr, first))
+                if cur.full(batch_files, batch_seconds * 16000):
+                    self._survey_pass(items, out, failed)
+                    cur, items = pipeline._Batch(), []
+        if items:
+            self._survey_pass(items, out, failed)
+        return out
+
     def __call__(self, medianame, start_sec=None, stop_sec=None):
         """segmenter.py:279-294."""
         mspec, loge, difflen = _media2feats(medianame, start_sec, stop_sec, self.ffmpeg, self.ctx, self.resample)

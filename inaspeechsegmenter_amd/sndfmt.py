@@ -563,6 +563,9 @@ class AdpcmSource(CodedSource):
     """An IMA ADPCM file for the device decoder (sources.py states what it answers).  kind: 'pcm' or 'resample'."""
     __slots__ = ()
     pass_order = 2
+    coder = 'adpcm'                                              # iss_adpcm_survey surveys what this class's launch staged
+    stage_format = _native.RS_FORMAT[np.dtype('<i2')]
+    full = R.SURVEY_FULL['ima']
     payload = property(lambda self: self.s.data)
     units = property(lambda self: self.s.nblocks)
 
@@ -571,7 +574,9 @@ class AdpcmSource(CodedSource):
         sample count is the whole file's, also where `s` holds the blocks of an excerpt."""
         s, total = self.s, self.s.n if self.win is None else self.win[2]
         to, fid, nout = _native.ADPCM_TO_SIGNAL, -1, 0
-        if self.kind != 'pcm':
+        if self.kind == 'stage':                                  # (io.survey_sources: staged for the survey kernel, no filter)
+            to = _native.ADPCM_TO_STAGE
+        elif self.kind != 'pcm':
             to, fid, nout = _native.ADPCM_TO_STAGE, ctx.resample_filter(s.sr)[0], self.size
         return (src_offset, block_begin, s.nblocks, total, s.ch, s.block_align, to, fid, dst_offset, nout)
 
@@ -587,14 +592,15 @@ class AdpcmSource(CodedSource):
 class AdpcmExcerpt(AdpcmSource):
     """Outputs [a, b) of an IMA (or, as MsAdpcmExcerpt, Microsoft) ADPCM file for the windowed decode: `s` = the sub_sound of the blocks that hold the
     stored-rate samples the excerpt needs ('pcm': [a, b); 'resample': resample.input_span of them), `first` the file's sample
-    number of its first sample.  A bad block is named by its byte offset in the file (s.base is one).  `sel` ('resample' only):
+    number of its first sample.  kind 'stage' (io.survey_sources): a and b count stored frames, staged for the survey kernel.
+    A bad block is named by its byte offset in the file (s.base is one).  `sel` ('resample' only):
     the channels to write apart (None: their average)."""
     __slots__ = ('first', 'win')
 
     def __init__(self, h, kind, a, b, sel=None):
         self.kind, self.size = kind, b - a
         self.sel = selection(sel)
-        s0, s1 = (a, b) if kind == 'pcm' else (lambda lo, hi: (lo, hi + 1))(*R.input_span(h.sr, h.n, a, b - a))
+        s0, s1 = (a, b) if kind in ('pcm', 'stage') else (lambda lo, hi: (lo, hi + 1))(*R.input_span(h.sr, h.n, a, b - a))
         self.s, self.first = sub_sound(h, s0, s1)
         self.win = (s0, s1, h.n, a, b - a)
         self.nbytes = self.s.data.nbytes
@@ -610,6 +616,7 @@ class MsAdpcmSource(AdpcmSource):
     """A Microsoft ADPCM file for the device decoder: AdpcmSource's rows, its own launch (iss_msadpcm_decode) after IMA's."""
     __slots__ = ()
     pass_order = 3
+    coder = 'msadpcm'
 
     @staticmethod
     def launch(ctx, staged, rows, nblocks, n_signal=-1, **kw):

@@ -38,6 +38,11 @@ selected channel apart -- `parts`, `stride`, `held` and `reselect` as on a whole
 Excerpts with and without a selection share a launch (the downmixed ones with no split beside them), and `host()` of one with
 a selection gives one array per selected channel.
 
+A survey (io.survey_sources, Segmenter.survey_channels / survey_files) measures what the channels of stored frames [a, b) hold
+instead of writing a signal: its sources are `RawSurvey` (stored bytes for iss_survey) and the 'stage' kind of the decoders'
+excerpt classes (decoded to the staging buffer without a filter, then iss_<coder>_survey), and `Group.survey` is their one
+launch per class, the class's `survey(ctx, staged, jobs, tables, sources)` -> (status, one resample.SurveyFields per source).
+
 `Group` is the only place that stages payloads, numbers job rows, launches and hands the status back; `pass_order` places a
 class's launch among the device calls of a pass.  pipeline._Worker.run, Segmenter.load_pcm_excerpts and Source.place (one file
 alone: segmenter._place) are written against this and nothing else: a new format is one class, and one line in io._classify.
@@ -143,6 +148,12 @@ class Group:
         self.status = self.cls.launch(self.ctx, self.staged, [j.row for j in self.jobs], self.tables, n_signal, **kw)
         return self
 
+    def survey(self):
+        """ONE survey launch for the group in place of `launch` (sources of io.survey_sources: every job a TO_STAGE decode
+        without a filter, or stored bytes) -> one resample.SurveyFields per source, valid on return; `check` as after `launch`."""
+        self.status, fields = self.cls.survey(self.ctx, self.staged, self.jobs, self.tables, [s for s, _ in self.placed])
+        return fields
+
     def check(self, on_error=None):
         """Every source checks its slice of the status.  A ValueError goes to on_error(index in `placed`, exception) and the
         others are still checked; without on_error the first is raised."""
@@ -207,6 +218,27 @@ class RawExcerpt(RawSource):
         return host_window(self.sub.stored(), self.sr, self.win, self.sel)
 
 
+class RawSurvey(RawSource):
+    """Stored frames for the survey kernel (io.survey_sources): `x` = frames [first, first + len(x)) of a file of `total`
+    frames, of which frames [a, b) are surveyed against the fullscale threshold `full`.  `size` (what packs it into a pass) is
+    the length of those frames at 16 kHz.  Its job row is a SURVEY_JOB row, its window row says which frames `x` holds."""
+    __slots__ = ('full', 'win')
+
+    def __init__(self, x, sr, fmt, full, a, b, first=0, total=None):
+        self.x, self.sr, self.fmt, self.full, self.sel = np.ascontiguousarray(x), sr, int(fmt), float(full), None
+        n = self.x.shape[0]
+        self.win = (first, first + n, first + n if total is None else total, a, b - a)
+        self.size = -(-(b - a) * resample.SR_OUT // sr)
+
+    def row(self, ctx, src_offset, unit_begin, dst_offset):
+        x = self.x
+        return (src_offset, x.shape[0], 1 if x.ndim == 1 else x.shape[1], self.fmt, self.full)
+
+    @staticmethod
+    def survey(ctx, staged, jobs, tables, srcs):
+        return None, ctx.survey(staged, [j.row for j in jobs], [j.window for j in jobs])
+
+
 def host_window(x, sr, win, sel=None):
     """What an excerpt's `host()` gives for x = the stored frames [s_begin, s_end) of its window row `win`: their downmix's
     outputs, or with a selection one array per selected channel, each resample.resample_ref on that channel's column
@@ -236,6 +268,14 @@ class CodedSource(Source):
 
     def check(self, status):
         self.s.check(status)
+
+    @classmethod
+    def survey(cls, ctx, staged, jobs, tables, srcs):
+        """The decode launch of a group of 'stage' excerpts (every job TO_STAGE without a filter, its window the frames [a, b)
+        it stages), then ONE survey launch over what it staged -> (the decode status, one resample.SurveyFields per source)."""
+        status = cls.launch(ctx, staged, [j.row for j in jobs], tables, 0, windows=[j.window for j in jobs])
+        rows = [(k, s.win[4], s.s.ch, s.stage_format, s.full) for k, s in enumerate(srcs)]
+        return status, ctx.survey(None, rows, coder=cls.coder)
 
 
 def held(sig):

@@ -1,0 +1,135 @@
+"""What the channels of a file hold: the result of a channel survey.
+
+`Segmenter.survey_channels` (the device, csrc/survey.hip) and `io.survey_channels` (the host-only twin) both return a
+`ChannelSurvey`: the measured fields of resample.SurveyFields (include/iss.h, "Channel survey", states them and the order of
+the three sums) and what is derived from them here, in Python float64, from those fields only -- so two surveys whose
+fields are equal are equal in everything.
+"""
+import math
+
+import numpy as np
+
+from . import resample as R
+
+ACTIVE_FLOOR_DB = -60.0          # a definition, not a measurement: a channel whose RMS lies 60 dB below full scale counts as empty
+INVERTED_CORR = -0.5             # likewise: a pair at or below this correlation counts as polarity-inverted
+
+
+class ChannelSurvey:
+    """The survey of stored frames [first, first + n) of a file of `channels` channels at `sr` Hz.
+
+    Measured (numpy arrays, one entry per channel): peak, zeros, fullscale, nonfinite, s1, s2; s12 (one entry per pair c < d in
+    the order of `pairs`; None above resample.SURVEY_PAIR_CHANNELS channels).
+    Derived: dc = s1 / n, rms = sqrt(s2 / n), rms_db = 20 log10(rms) (-inf for 0), corr(c, d), downmix_loss_db, active(),
+    inverted(), rows()."""
+    __slots__ = ('fields', 'sr', 'first')
+
+    def __init__(self, fields, sr, first=0):
+        self.fields, self.sr, self.first = fields, int(sr), int(first)
+
+    n = property(lambda self: self.fields.n)
+    channels = property(lambda self: len(self.fields.peak))
+    peak = property(lambda self: self.fields.peak)
+    zeros = property(lambda self: self.fields.zeros)
+    fullscale = property(lambda self: self.fields.fullscale)
+    nonfinite = property(lambda self: self.fields.nonfinite)
+    s1 = property(lambda self: self.fields.s1)
+    s2 = property(lambda self: self.fields.s2)
+    s12 = property(lambda self: self.fields.s12)
+    pairs = property(lambda self: R.survey_pairs(self.channels))
+
+    def __eq__(self, other):
+        """Equal to the bit in every measured field (and the same frames of a file of the same rate)."""
+        if not isinstance(other, ChannelSurvey):
+            return NotImplemented
+        a, b = self.fields, other.fields
+        return (self.sr, self.first, a.n) == (other.sr, other.first, b.n) and (a.s12 is None) == (b.s12 is None) and all(
+            np.array_equal(np.asarray(x).view(np.int64), np.asarray(y).view(np.int64))
+            for x, y in zip(a[1:7] + ((a.s12,) if a.s12 is not None else ()), b[1:7] + ((b.s12,) if b.s12 is not None else ())))
+
+    __hash__ = None
+
+    @property
+    def dc(self):
+        return [float(v) / self.n if self.n else 0.0 for v in self.s1]
+
+    @property
+    def rms(self):
+        return [math.sqrt(float(v) / self.n) if self.n else 0.0 for v in self.s2]
+
+    @property
+    def rms_db(self):
+        return [20.0 * math.log10(v) if v > 0 else -math.inf for v in self.rms]
+
+    def pair(self, c, d):
+        """s12 of channels c != d."""
+        c, d = min(c, d), max(c, d)
+        return float(self.s12[self.pairs.index((c, d))])
+
+    def corr(self, c, d):
+        """(s12 - s1c s1d / n) / sqrt((s2c - s1c^2 / n) (s2d - s1d^2 / n)); NaN when a factor is not positive (a silent or
+        constant channel) or pairs were not computed."""
+        if self.s12 is None or not self.n:
+            return math.nan
+        n, s1, s2 = self.n, self.s1, self.s2
+        vc, vd = float(s2[c]) - float(s1[c]) ** 2 / n, float(s2[d]) - float(s1[d]) ** 2 / n
+        if not (vc > 0 and vd > 0):
+            return math.nan
+        return (self.pair(c, d) - float(s1[c]) * float(s1[d]) / n) / math.sqrt(vc * vd)
+
+    @property
+    def downmix_loss_db(self):
+        """10 log10(P_mix / P_avg): the power of the default downmix (the mean of all channels) against the mean power of the
+        channels.  0 for identical channels, strongly negative when the downmix cancels them; None when pairs were not computed."""
+        if self.s12 is None:
+            return None
+        ch, n = self.channels, self.n
+        tot = math.fsum(float(v) for v in self.s2)
+        if not n or not tot > 0:
+            return 0.0
+        p_mix = (tot + 2.0 * math.fsum(float(v) for v in self.s12)) / (ch * ch * n)
+        p_avg = tot / (ch * n)
+        return 10.0 * math.log10(p_mix / p_avg) if p_mix > 0 else -math.inf
+
+    def active(self, floor_db=ACTIVE_FLOOR_DB):
+        """The channels, ascending, with peak > 0 and rms_db >= floor_db: the list to pass as `channels=`.  The default floor
+        is a definition, not a measurement."""
+        db = self.rms_db
+        return [c for c in range(self.channels) if self.peak[c] > 0 and db[c] >= floor_db]
+
+    def inverted(self, threshold=INVERTED_CORR):
+        """The pairs (c, d), c < d, with corr <= threshold.  The default threshold is a definition, not a measurement."""
+        if self.s12 is None:
+            return []
+        return [(c, d) for c, d in self.pairs if self.corr(c, d) <= threshold]
+
+    def rows(self, floor_db=ACTIVE_FLOOR_DB):
+        """One tuple per channel for printing: (channel, frames, peak, rms_db, dc, zeros, fullscale, nonfinite, active)."""
+        act, db, dc = set(self.active(floor_db)), self.rms_db, self.dc
+        return [(c, self.n, float(self.peak[c]), db[c], dc[c], int(self.zeros[c]), int(self.fullscale[c]), int(self.nonfinite[c]),
+                 c in act) for c in range(self.channels)]
+
+    def __repr__(self):
+        return f'ChannelSurvey({self.channels} channels, frames [{self.first}, {self.first + self.n}) at {self.sr} Hz)'
+
+
+TSV_COLUMNS = ('path', 'channel', 'frames', 'peak', 'rms_db', 'dc', 'zeros', 'fullscale', 'nonfinite', 'active')
+
+
+def write_tsv(dst, names, surveys):
+    """The table `--survey` of scripts/ina_speech_segmenter_amd.py writes: one row per file and channel under TSV_COLUMNS, then
+    one row per file with channel `*` whose `rms_db` column carries downmix_loss_db and whose `active` column the inverted
+    pairs ("0-1,2-3"; empty for none).  A file that could not be read (an entry of Segmenter.survey_files that is a text) gets
+    one row: channel `!`, the text in the last column."""
+    with open(dst, 'w') as f:
+        f.write('\t'.join(TSV_COLUMNS) + '\n')
+        for name, s in zip(names, surveys):
+            if not isinstance(s, ChannelSurvey):
+                f.write('\t'.join([name, '!'] + [''] * 7 + [str(s).replace('\t', ' ').replace('\n', ' ')]) + '\n')
+                continue
+            for c, n, peak, db, dc, zeros, full, nonf, act in s.rows():
+                f.write('\t'.join([name, str(c), str(n), repr(peak), repr(db), repr(dc), str(zeros), str(full), str(nonf),
+                                   '1' if act else '0']) + '\n')
+            loss = s.downmix_loss_db
+            f.write('\t'.join([name, '*', str(s.n), '', '' if loss is None else repr(loss), '', '', '', '',
+                               ','.join(f'{c}-{d}' for c, d in s.inverted())]) + '\n')

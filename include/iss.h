@@ -460,6 +460,57 @@ int iss_msadpcm_decode_mix(iss_ctx* ctx, const void* src, int64_t src_bytes, con
                            int32_t njobs, int64_t nblocks_total, int64_t n_signal, int32_t* status_out, const iss_mixset* mixsets,
                            const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms, int64_t nterms);
 
+/* Channel survey: per-channel level figures and the cross-products between channels of stored frames [a, b) of a source, in
+ * one pass over the stored samples (survey.hip; inaspeechsegmenter_amd/resample.py `survey_ref` is the same arithmetic in
+ * numpy, to the bit).  Nothing of the resident signal or the features is touched.
+ *
+ * Frames.  The whole file is a = 0, b = frames.  A time range (start_sec, stop_sec) of a file at rate sr is a = floor(start_sec
+ * * sr + 0.5), b = min(frames, floor(stop_sec * sr + 0.5)) (the excerpt calls' rounding, on stored frames); the caller computes
+ * it and refuses an empty range.  n = b - a >= 1 here.
+ * Samples.  x[j, c] is the float64 value the resample kernel gives stored sample (j, c): the ISS_RS_* formats above with
+ * libsndfile's scaling (24-bit PCM widened to x << 8, G.711 expanded, big-endian swapped, decoder output PCM16 or int32).  A
+ * NaN or +-Inf sample of a float format is counted in `nonfinite` and is 0.0 in every other figure (zeros included).
+ * Figures, per channel c:   peak = max_j |x|,  zeros = #{x == 0.0},  fullscale = #{|x| >= full} (`full` from the job row: the
+ * largest positive value the stored format holds),  nonfinite,  s1 = sum_j x,  s2 = sum_j x*x;  and for channels <=
+ * ISS_SURVEY_PAIR_CHANNELS, per pair c < d:  s12 = sum_j x[j,c] * x[j,d].  peak and the counts are exact.
+ * The survey order of the three sums.  Every product and every addition is rounded on its own (no FMA).  The terms of a sum
+ * are numbered k = j - a.  Chunk q holds terms [q * C, min(n, (q+1) * C)), C = ISS_SURVEY_CHUNK = 1024.  Within a chunk, lane
+ * t of 256 starts from +0.0 and adds its terms t, t + 256, t + 512, t + 768 in that order (a missing term adds nothing); the 64
+ * lanes of each of the four waves (lanes 64w .. 64w + 63) are combined by the tree  lane l += lane l + s  for s = 32, 16, 8, 4,
+ * 2, 1; the chunk's sum is ((wave 0 + wave 1) + wave 2) + wave 3.  The job's sum starts from +0.0 and adds its chunk sums in
+ * ascending q.  The order depends on (a, b) alone: not on the grid, on the other jobs of the call, or on where the bytes lie;
+ * no floating-point atomic is used.
+ *
+ * Result row of job k, 8-byte words from results[result_offset_k] on, W = 6 * ch + (ch <= 16 ? ch * (ch - 1) / 2 : 0) of them,
+ * result_offset_k = the sum of W over the jobs before it:   s1[ch], s2[ch], peak[ch] as float64;  zeros[ch], fullscale[ch],
+ * nonfinite[ch] as int64;  then s12 as float64 in the order (0,1), (0,2), ..., (0,ch-1), (1,2), ...
+ *
+ * iss_survey: `src` = the stored bytes of every job (one H2D copy), one launch of survey_kernel over (job, chunk) and one of the
+ * second stage; `results` (the sum of W words) is valid when the call returns.  windows == NULL: job k surveys its frames_in
+ * frames at src_offset.  With windows (one beside every job): the job's bytes hold frames [s_begin, s_end) of the file, and
+ * frames [out_begin, out_begin + out_count) are surveyed (counted in stored frames here, inside [s_begin, s_end): else
+ * ISS_EINVAL) -- the same figures, to the bit, as a job holding those frames alone.
+ * iss_flac_survey / iss_adpcm_survey / iss_msadpcm_survey: the same over what the codec's last decode call staged (TO_STAGE
+ * jobs, with or without a filter): src_offset of a row is the INDEX of the staged job of that call, format ISS_RS_I16 or
+ * ISS_RS_I32 as staged, frames_in * channels samples exactly what the job staged.  Nothing is uploaded but the rows.
+ * Errors: ISS_EINVAL, nothing launched.  channels 1 .. 1024.                                                                 */
+#define ISS_SURVEY_CHUNK          1024
+#define ISS_SURVEY_PAIR_CHANNELS  16
+typedef struct {
+    int64_t src_offset;            /* byte offset of the job's first staged frame (codec entries: index of the staged job)   */
+    int64_t frames_in;             /* frames the job's bytes hold                                                            */
+    int32_t channels, format;      /* ISS_RS_*                                                                               */
+    double  full;                  /* fullscale threshold, > 0                                                               */
+} iss_survey_job;
+int iss_survey(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_survey_job* jobs, const iss_window* windows,
+               int32_t njobs, void* results);
+int iss_flac_survey(iss_ctx* ctx, const iss_survey_job* jobs, const iss_window* windows, int32_t njobs, void* results);
+int iss_adpcm_survey(iss_ctx* ctx, const iss_survey_job* jobs, const iss_window* windows, int32_t njobs, void* results);
+int iss_msadpcm_survey(iss_ctx* ctx, const iss_survey_job* jobs, const iss_window* windows, int32_t njobs, void* results);
+/* the chunk geometry: frames per chunk, lanes per chunk, and the channel count up to which pairs are computed */
+int iss_survey_geometry(int32_t* chunk_out, int32_t* lanes_out, int32_t* pair_channels_out);
+int iss_survey_stats(iss_ctx* ctx, int64_t* launches, int64_t* jobs);     /* survey_kernel launches, jobs surveyed */
+
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */
 int iss_host_alloc(iss_ctx* ctx, size_t bytes, void** out);

@@ -50,6 +50,11 @@ def build_parser():
                          '<basename>.mix<k>.<format> per mix.  Mixes are separated by commas, terms joined by "+": "0+1,2+3" is the '
                          'mean of channels 0 and 1 and the mean of 2 and 3; a mix with any WEIGHT*CHANNEL term is a weighted sum, '
                          'in which a bare channel has weight 1 and nothing is divided: "0.7*4+0.7*5+1*2"')
+    ap.add_argument('--survey', default=None, metavar='OUT.tsv',
+                    help='with -b None: instead of segmenting, measure what the channels of every file hold (peak, RMS, DC, digital '
+                         'zeros, clipped and non-finite samples, which channels carry signal) on the GPU and write one row per file '
+                         "and channel to OUT.tsv; a row with channel '*' per file carries what the default downmix loses in dB and "
+                         'the polarity-inverted channel pairs')
     return ap
 
 
@@ -75,6 +80,10 @@ def main(argv=None):
             mixes = parse_mixes(args.mixes)
         except ValueError as exc:
             build_parser().error(str(exc))
+    if args.survey is not None and ffmpeg is not None:
+        build_parser().error('--survey needs -b None (ffmpeg downmixes every file)')
+    if args.survey is not None and int(os.environ.get('WORLD_SIZE', '1')) != 1:
+        build_parser().error('--survey runs on one GPU')
     if ffmpeg is None:
         print('Disabling ffmpeg. WAV (PCM, float, G.711, IMA and Microsoft ADPCM), FLAC, AIFF, AU, CAF, Wave64 and RF64 files are read directly. '
               + ('Files at other rates or with several channels are resampled on the GPU.' if args.resample
@@ -92,6 +101,10 @@ def main(argv=None):
     from inaspeechsegmenter_amd import Segmenter
     seg = Segmenter(vad_engine=args.vad_engine, detect_gender=args.detect_gender, ffmpeg=ffmpeg, batch_size=args.batch_size,
                     energy_ratio=args.energy_ratio, device=local_rank, models=args.models, resample=args.resample)
+    if args.survey is not None:
+        from inaspeechsegmenter_amd.survey import write_tsv
+        write_tsv(args.survey, inputs, seg.survey_files(inputs))
+        return 0
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         if world == 1:
