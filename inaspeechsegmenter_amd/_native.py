@@ -56,6 +56,9 @@ FLAC_STATUS = {1: 'reserved subframe type', 2: 'subframe header padding bit set'
                9: 'nonzero padding before the footer', 10: 'subframes end before the footer', 11: 'CRC-16 mismatch'}
 
 
+STAGED_ORIGIN = {None: 0, 'flac': 1, 'adpcm': 2, 'msadpcm': 3}      # ISS_STAGED_*: the origins of iss_resample_staged_mix
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -160,6 +163,9 @@ def lib():
         'iss_flac_decode_mix': (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i32, i64, pi32, vp, vp, i64, vp, i64]),
         'iss_adpcm_decode_mix': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64, vp, i64]),
         'iss_msadpcm_decode_mix': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64, vp, i64]),
+        'iss_staged_payload': (C.c_int, [vp, i32, pi64]),
+        'iss_resample_staged_mix': (C.c_int, [vp, i32, i64, vp, vp, i32, i64, vp, vp, i64, vp, i64]),
+        'iss_upload_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_survey': (C.c_int, [vp, vp, i64, vp, vp, i32, vp]),
         'iss_flac_survey': (C.c_int, [vp, vp, vp, i32, vp]),
         'iss_adpcm_survey': (C.c_int, [vp, vp, vp, i32, vp]),
@@ -493,6 +499,30 @@ class Context:
             sp, sel = _split_rows(splits, trail[0])
             name, args = name + '_split', args + (C.c_void_p(sp.ctypes.data), C.c_void_p(sel.ctypes.data), sel.size)
         self._ck(getattr(self._L, name)(self._h, *args), name)
+
+    # ---- resampling what a survey or a decode call left on the device (iss_resample_staged_mix)
+    def staged_payload(self, coder=None):
+        """The id of the payload origin `coder` holds (None: the last survey's upload; 'flac', 'adpcm', 'msadpcm': what the
+        coder's last decode call staged).  NativeError (ISS_ESTATE) when it holds none."""
+        pid = C.c_int64()
+        self._ck(self._L.iss_staged_payload(self._h, STAGED_ORIGIN[coder], C.byref(pid)), 'iss_staged_payload')
+        return pid.value
+
+    def resample_staged(self, coder, payload, jobs, n_signal=-1, windows=None, mixes=None):
+        """iss_resample_staged_mix: the RS_JOB rows `jobs` over the bytes of payload `payload` of origin `coder`, which are on
+        the device already (src_offset of a row: the byte offset of the surveyed job, or for a coder the index of its staged
+        job); nothing is uploaded but rows.  windows, mixes: as for `resample`; mixes None is the plain downmix for every job."""
+        jb = np.ascontiguousarray(np.array(jobs, dtype=RS_JOB).reshape(-1))
+        wn = None if windows is None else _window_rows(windows, jb.size)
+        sets, rows, terms = _mix_rows([None] * jb.size if mixes is None else mixes, jb.size)
+        self._ck(self._L.iss_resample_staged_mix(
+            self._h, STAGED_ORIGIN[coder], int(payload), C.c_void_p(jb.ctypes.data), None if wn is None else C.c_void_p(wn.ctypes.data),
+            jb.size, int(n_signal), C.c_void_p(sets.ctypes.data), C.c_void_p(rows.ctypes.data), rows.size,
+            C.c_void_p(terms.ctypes.data), terms.size), 'iss_resample_staged_mix')
+
+    def upload_stats(self):
+        """(payload H2D copies, their bytes) since the context was created: stored and compressed bytes, not rows or signals."""
+        return self._counters('iss_upload_stats')
 
     def resample_signal(self, x, sr, fmt=None):
         """A single source resampled on its own: the resident signal becomes its 16 kHz mono PCM16 -> its length.  (For arrays in

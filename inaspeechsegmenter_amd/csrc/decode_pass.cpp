@@ -12,6 +12,7 @@ int IssDecodePass::begin(iss_ctx* ctx, const char* name, int64_t n_sig, int32_t 
     }
     stage_off.assign((size_t)njobs, -1);
     stage_bytes.assign((size_t)njobs, 0);
+    stage_esz.assign((size_t)njobs, 0);
     return ISS_OK;
 }
 
@@ -47,6 +48,7 @@ int IssDecodePass::place(int32_t j, const IssJobDst& d, int64_t frames_total, in
         to_sig = false;
         dst_byte = stage_off[(size_t)j] = stage;
         stage_bytes[(size_t)j] = frames_total * channels * esz;
+        stage_esz[(size_t)j] = esz;
         stage += (stage_bytes[(size_t)j] + 15) / 16 * 16;
         if (d.filter >= 0) {
             iss_resample_job r{};
@@ -75,17 +77,23 @@ int IssDecodePass::commit(IssCodec* dec) {
         if (nsig > 0) ISS_HIP(c, hipMemsetAsync(c->sig.p, 0, (size_t)nsig * 2, c->stream));
     }
     iss_set_signal(c, c->sig.p, 1, nsig);                  // (n_signal < 0: what begin() found, written to from here on)
-    if (dec) { dec->stage_off = stage_off; dec->stage_bytes = stage_bytes; }
+    if (dec) { dec->stage_off = stage_off; dec->stage_bytes = stage_bytes; dec->stage_esz = stage_esz; dec->held = 0; }      // (held again once finish() is through)
     return ISS_OK;
 }
 
 int iss_upload_payload(iss_ctx* c, DevBuf& b, const char* name, const void* src, int64_t bytes, size_t cap) {
+    if (&b == &c->sv_src) c->sv_held.id = 0;               // whatever it held is being replaced
     if (int rc = iss_reserve(c, b, cap)) return rc;
     iss_prof_begin(c, ISS_PROF_OTHER, 0.0);
     iss_prof_inst(c, "%s_h2d(%lld B)", name, (long long)bytes);
     if (bytes > 0) ISS_HIP(c, hipMemcpyAsync(b.p, src, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
     iss_prof_end(c);
+    if (bytes > 0) { c->up_count.launches += 1; c->up_count.units += bytes; }
     return ISS_OK;
+}
+
+extern "C" int iss_upload_stats(iss_ctx* c, int64_t* copies, int64_t* bytes) {
+    return iss_get_counters(c ? &c->up_count : nullptr, copies, bytes);
 }
 
 int iss_upload_rows(iss_ctx* c, DevBuf& b, const void* rows, size_t bytes) {
@@ -113,6 +121,7 @@ int IssDecodePass::finish(IssCodec& dec, int32_t* status_out, int64_t units) {
     ISS_HIP(c, hipMemcpyAsync(status_out, dec.status.p, (size_t)units * 4, hipMemcpyDeviceToHost, c->stream));
     dec.count.launches += 1;
     dec.count.units += units;
+    dec.held = ++c->held_seq;
     return iss_resample_launch(c, (const uint8_t*)dec.stage.p, plan);     // (no rows: nothing launched)
 }
 

@@ -129,6 +129,7 @@ extern "C" int iss_scribble(iss_ctx* c, uint32_t word) {
     }
     c->flags_epoch = 0;                    // feat_epoch starts at 1: the row flags are computed again
     c->bad_prefix.clear();
+    c->sv_held.id = c->flac.held = c->adpcm.held = c->msadpcm.held = 0;      // what the origins held is overwritten: ISS_ESTATE from here on
     return ISS_OK;
 }
 

@@ -25,7 +25,9 @@ struct IssCodec {
     const char* name;                                  // "flac": iss_<name>_decode, <name>_h2d
     DevBuf src, rows, status, stage;                   // payload, row table, per-unit status, staging buffer of the last call
     std::vector<int64_t> stage_off, stage_bytes;       // per job of the last call (-1: not staged)
+    std::vector<int32_t> stage_esz;                    // ... and the bytes of a staged sample (2: ISS_RS_I16, 4: ISS_RS_I32)
     IssCounters count;                                 // launches, units (frames / blocks) decoded
+    int64_t held = 0;                                  // id of what `stage` holds for iss_resample_staged_mix (0: nothing whole)
 };
 
 // A network's device parameter arrays once another net shares them (iss_cnn_load_shared): freed with their last user.
@@ -104,6 +106,11 @@ struct iss_ctx {
     // channel survey (survey.hip): uploaded bytes, job rows, per-chunk partial rows, result rows of the last call
     DevBuf sv_src, sv_jobs, sv_ws, sv_res;
     IssCounters sv_count;                 // survey_kernel launches, jobs
+    // what a later call may resample without uploading it again (iss_resample_staged_mix): the payload of the last iss_survey in
+    // sv_src, with the rows that describe it; a codec's is its IssCodec::held.  Ids count up over all origins of the context
+    struct Held { int64_t id = 0, bytes = 0; std::vector<iss_survey_job> jobs; } sv_held;
+    int64_t held_seq = 0;
+    IssCounters up_count;                 // iss_upload_payload: copies, bytes (iss_upload_stats)
 
     // resident features
     DevBuf mspec, loge;

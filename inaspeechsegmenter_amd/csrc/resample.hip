@@ -554,6 +554,88 @@ extern "C" int iss_resample_pcm16_mix(iss_ctx* c, const void* src, int64_t src_b
     return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, windows, nullptr, nullptr, 0, &mix);
 }
 
+// what `origin` holds for iss_resample_staged_mix: its id (0: nothing), and for a codec the codec
+static int64_t staged_held(iss_ctx* c, int32_t origin, IssCodec*& dec) {
+    dec = origin == ISS_STAGED_FLAC ? &c->flac : origin == ISS_STAGED_ADPCM ? &c->adpcm : origin == ISS_STAGED_MSADPCM ? &c->msadpcm
+                                                                                                                           : nullptr;
+    return dec ? dec->held : c->sv_held.id;
+}
+
+static const char* const kStagedOrigin[4] = {"survey", "flac", "adpcm", "msadpcm"};
+
+extern "C" int iss_staged_payload(iss_ctx* c, int32_t origin, int64_t* payload_out) {
+    if (!c || !payload_out || origin < ISS_STAGED_SURVEY || origin > ISS_STAGED_MSADPCM)
+        return iss_fail(c, ISS_EINVAL, "iss_staged_payload: bad argument");
+    IssCodec* dec;
+    const int64_t id = staged_held(c, origin, dec);
+    if (id == 0) return iss_fail(c, ISS_ESTATE, "iss_staged_payload: origin %s holds no payload", kStagedOrigin[origin]);
+    *payload_out = id;
+    return ISS_OK;
+}
+
+// The rows of a *_mix call over bytes a survey call (origin survey) or a decode call (a codec) left on the device: every row is
+// matched against what was uploaded / staged and rewritten to the byte offset it lies at, then planned and launched as
+// resample_pcm16 does -- without its upload.  Everything up to commit() is host work on vectors of this call
+extern "C" int iss_resample_staged_mix(iss_ctx* c, int32_t origin, int64_t payload, const iss_resample_job* jobs,
+                                       const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_mixset* mixsets,
+                                       const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms, int64_t nterms) {
+    const char* who = "iss_resample_staged_mix";
+    if (!c || origin < ISS_STAGED_SURVEY || origin > ISS_STAGED_MSADPCM || njobs < 0 || (njobs > 0 && (!jobs || !mixsets)))
+        return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
+    IssCodec* dec;
+    const int64_t id = staged_held(c, origin, dec);
+    if (id == 0)
+        return iss_fail(c, ISS_ESTATE, "%s: origin %s holds no payload (no %s call went before)", who, kStagedOrigin[origin],
+                        dec ? "decode" : "iss_survey");
+    if (id != payload)
+        return iss_fail(c, ISS_ESTATE, "%s: origin %s: payload %lld has been replaced by a later call (it holds payload %lld)", who,
+                        kStagedOrigin[origin], (long long)payload, (long long)id);
+    std::vector<iss_resample_job> rows(jobs, jobs + njobs);
+    int64_t held_bytes = dec ? 0 : c->sv_held.bytes;
+    if (dec)
+        for (size_t q = 0; q < dec->stage_off.size(); ++q)
+            if (dec->stage_off[q] >= 0) held_bytes = std::max(held_bytes, dec->stage_off[q] + dec->stage_bytes[q]);
+    for (int32_t k = 0; k < njobs; ++k) {
+        iss_resample_job& J = rows[(size_t)k];
+        if (J.channels < 1 || J.channels > 1024 || J.frames_in < 1 || J.frames_in > (int64_t(1) << 40))
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: %lld frames of %d channels", who, k, (long long)J.frames_in, J.channels);
+        if (dec) {
+            const int64_t q = J.src_offset;
+            if (q < 0 || q >= (int64_t)dec->stage_off.size() || dec->stage_off[(size_t)q] < 0)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: job %lld of the last iss_%s_decode did not go to the staging buffer", who,
+                                k, (long long)q, dec->name);
+            const int32_t esz = dec->stage_esz[(size_t)q];
+            if (J.format != (esz == 4 ? ISS_RS_I32 : ISS_RS_I16))
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: format %d: staged job %lld holds %s samples", who, k, J.format,
+                                (long long)q, esz == 4 ? "ISS_RS_I32" : "ISS_RS_I16");
+            const int64_t nbytes = J.frames_in * J.channels * esz;
+            if (dec->stage_bytes[(size_t)q] != nbytes)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: staged job %lld holds %lld bytes, the row states %lld frames of %d "
+                                "channels: %lld", who, k, (long long)q, (long long)dec->stage_bytes[(size_t)q], (long long)J.frames_in,
+                                J.channels, (long long)nbytes);
+            J.src_offset = dec->stage_off[(size_t)q];
+        } else {
+            bool found = false;
+            for (const iss_survey_job& S : c->sv_held.jobs)
+                found = found || (S.src_offset == J.src_offset && S.frames_in == J.frames_in && S.channels == J.channels &&
+                                  S.format == J.format);
+            if (!found)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: no job of the last iss_survey held %lld frames of %d channels in format "
+                                "%d at byte %lld", who, k, (long long)J.frames_in, J.channels, J.format, (long long)J.src_offset);
+        }
+    }
+    const IssMixTables mix{mixsets, mixes, nmixes, terms, nterms};
+    IssDecodePass pass;
+    int rc = pass.begin(c, who, n_signal, 0);
+    pass.jmix = &mix;
+    if (njobs > 0) pass.rmixsets.assign(mixsets, mixsets + njobs);
+    pass.rjobs = rows; pass.stage = held_bytes;
+    if (windows) { pass.rwins.assign(windows, windows + njobs); pass.windowed = true; }
+    if (rc || (rc = pass.commit(nullptr))) return rc;
+    if (njobs == 0) return ISS_OK;
+    return iss_resample_launch(c, (const uint8_t*)(dec ? dec->stage.p : c->sv_src.p), pass.plan);
+}
+
 // (tile, channels per group) the planner gives a job of `nsel` selected channels (or mixes) through filter `filter`
 extern "C" int iss_resample_split_geometry(iss_ctx* c, int32_t filter, int32_t nsel, int32_t* tile_out, int32_t* group_out) {
     if (!c || !tile_out || !group_out || nsel < 1 || filter < 0 || filter >= (int32_t)c->rs_filters.size())

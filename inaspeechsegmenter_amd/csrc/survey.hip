@@ -206,6 +206,11 @@ int survey_call(iss_ctx* c, const char* who, IssCodec* dec, const void* src, int
     ISS_HIP(c, hipStreamSynchronize(c->stream));
     c->sv_count.launches += 1;
     c->sv_count.units += njobs;
+    if (!dec) {                                            // sv_src holds these jobs' bytes until the next upload into it
+        c->sv_held.id = ++c->held_seq;
+        c->sv_held.bytes = src_bytes;
+        c->sv_held.jobs.assign(jobs, jobs + njobs);
+    }
     return ISS_OK;
 }
 

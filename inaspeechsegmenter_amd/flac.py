@@ -14,7 +14,7 @@ import numpy as np
 from . import _native
 from . import resample as R
 from .io import need_16k_mono, source_of
-from .sources import CodedSource, RawSource, host_window, selection
+from .sources import CodedAuto, CodedSource, RawAuto, RawSource, host_window, selection
 
 MAGIC = b'fLaC'
 # benchmark switch (tools/bench_flac.py), not a user option: True makes the ffmpeg-free read decode FLAC on the host
@@ -118,6 +118,14 @@ class FlacStream:
             return RawSource(self.decode_host(), self.sr, sel=sel)
         return FlacSource(self, 'resample', sel)
 
+    def auto_source(self, full):
+        """What Segmenter reads for a multi-channel stream with channels='auto' (io.auto_source)."""
+        if _HOST_DECODE:
+            return RawAuto(self.decode_host(), self.sr, full=full) if self.ch > 1 else source(self, True)
+        if self.ch == 1 and self.sr == R.SR_OUT:                     # (24-bit: the float path, which shares no pass)
+            return FlacSource(self, 'float') if self.bps > 16 else FlacAuto(self, 'pcm')
+        return FlacAuto(self)
+
 
 class FlacSource(CodedSource):
     """A FLAC file for the device decoder (sources.py states what it answers).  kind: 'pcm' (mono 8/16-bit at 16 kHz), 'float'
@@ -158,6 +166,16 @@ class FlacSource(CodedSource):
         x = ctx.flac_get_stage(0, s.n, s.ch, s.bps)
         s.check(st)
         return x
+
+
+class FlacAuto(CodedAuto, FlacSource):
+    """A FLAC file for channels='auto' (sources.CodedAuto): kind 'stage' for two or more channels, and for one channel at
+    another rate; 'pcm' for one 8/16-bit channel at 16 kHz.  `full` as the survey's sources state it."""
+    __slots__ = ('decision',)
+
+    def __init__(self, stream, kind='stage'):
+        FlacSource.__init__(self, stream, kind)
+        self.size, self.decision = stream.n if kind == 'pcm' else R.out_len(stream.n, stream.sr), None
 
 
 class FlacExcerpt(FlacSource):

@@ -24,6 +24,8 @@ channels: the same sources, an entry of whose selection is a resample.Mix; `deco
 host-only twins.
 `survey_sources` reads what a channel survey needs of a file -- per-channel levels and the cross-products between channels of the
 stored frames, measured on the device (Segmenter.survey_channels) --, `survey_channels` is its host-only twin.
+`auto_source` reads a file for channels='auto': a source that is staged once, surveyed and then downmixed by the mix its survey
+suggests (survey.ChannelSurvey.safe_mix); `decode_auto` is the host-only twin.
 """
 import os
 import struct
@@ -576,6 +578,52 @@ def survey_channels(medianame, ranges=None):
     x = h.stored()
     out = [ChannelSurvey(R.survey_ref(x, full, a, b), h.sr, a) for a, b in spans]
     return out[0] if ranges is None else out
+
+
+# ---------------------------------------------------------------------------------------------- survey-guided downmix (channels='auto')
+def _auto_parsed(medianame):
+    """-> (the file parsed as a survey parses it, its fullscale threshold, is it one of two or more channels with frames?)."""
+    _check_no_ffmpeg(medianame, None, None)
+    h, full = _survey_parsed(medianame, False)
+    return h, full, h.ch > 1 and h.n > 0
+
+
+def auto_source(medianame, resample=False):
+    """What Segmenter reads for channels='auto'.  A one-channel file gives the samples the whole-file read gives, from what
+    that read hands on (its array, a RawSource, the float path) -- but a FLAC or ADPCM file that shares passes comes as its
+    coder's two-step class too ('pcm' into the signal as ever, or staged and resampled as it is, with no survey and no
+    decision), so that a pass makes one decode call per coder whatever it holds.  A file of two or more channels gives a source of its class that is staged once,
+    surveyed on the device, told its mix -- survey.ChannelSurvey.safe_mix() of that survey, None being the plain downmix --
+    and resampled from the staged bytes (sources.RawAuto, flac.FlacAuto, sndfmt.AdpcmAuto and its Microsoft twin): `parts` 1,
+    `size` the downmix's length, `decision` = (survey, mix) once launched.  Without `resample` a rate other than 16 kHz is
+    refused as load_pcm_mixes refuses it."""
+    h, full, multi = _auto_parsed(medianame)
+    if h.n == 0:
+        return h.source(resample)
+    if h.ch > 1 or h.sr != R.SR_OUT:
+        if not resample:
+            need_16k_mono(medianame, h.sr, 1) if h.ch == 1 else need_16k(medianame, h.sr)
+        R.check_rate(h.sr)
+    return h.auto_source(full)
+
+
+def decode_auto(medianame, resample=True):
+    """Host-only twin of Segmenter.load_pcm_auto -> (pcm, survey, mix): survey = survey_channels(medianame) and mix =
+    survey.safe_mix() for a file of two or more channels (None, None for one channel); pcm = decode_mixes(medianame, [mix])[0],
+    or for mix None the plain decode: resample.resample_ref of the stored samples (decode_pcm's array for a 16 kHz mono file)."""
+    h, full, multi = _auto_parsed(medianame)
+    x = h.stored()
+    if not multi:
+        if h.sr != R.SR_OUT and resample:
+            return R.resample_ref(x, h.sr), None, None
+        return decode_pcm(medianame, ffmpeg=None), None, None
+    from .survey import ChannelSurvey
+    if not resample:
+        need_16k(medianame, h.sr)
+    R.check_rate(h.sr)
+    survey = ChannelSurvey(R.survey_ref(x, full, 0, h.n), h.sr, 0)
+    mix = survey.safe_mix()
+    return (R.resample_ref(x, h.sr) if mix is None else R.mix_ref(x, h.sr, mix)), survey, mix
 
 
 def survey_sources(medianame, ranges=None):

@@ -294,7 +294,7 @@ DEFAULT_WORKERS = 4               # passes with more contexts in flight overlap 
 
 
 def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch_files=None, batch_seconds=None,
-                  workers=None, decode_threads=4, channels=None):
+                  workers=None, decode_threads=4, channels=None, decided=None):
     """Segment `linput` with the networks of `seg`; on_result(index, src, lseg | None, errtext | None, secs) is called from
     the worker threads (serialised by a lock) as results become available, lseg = [(label, start_sec, stop_sec)], secs =
     this file's share of the processing time of its device pass (the pass's wall time / its files: what the reference's
@@ -302,7 +302,10 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
     skip: set of indices not to process.  Device failures (NativeError) and exceptions raised by on_result (unwritable
     outputs) propagate to the caller: the first one is re-raised here once every stage has drained.
     channels='split': every channel of every file on its own; lseg is then a LIST of segment lists, one per channel of the file.
-    channels = a list of resample.Mix: those mixes of every file, likewise (segmenter._load_source reads either)."""
+    channels = a list of resample.Mix: those mixes of every file, likewise (segmenter._load_source reads either).
+    channels='auto': every file downmixed as its own survey suggests (io.auto_source); lseg is one segment list, as without
+    `channels`, and decided((src, survey, mix)) is called before on_result for every file that was processed."""
+    multi = channels is not None and channels != 'auto'        # on_result gets a list of segment lists
     batch_files, batch_seconds = _limits(batch_files, batch_seconds)
     workers = workers or DEFAULT_WORKERS
     items = [(i, src) for i, src in enumerate(linput) if not (skip and i in skip)]
@@ -381,10 +384,12 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                         with warnings.catch_warnings():
                             warnings.simplefilter('ignore')
                             lseg = one_by_one(seg, w.ctx, sig, src)
-                        res = (lseg if channels is not None else lseg[0], None)
+                        res = (lseg if multi else lseg[0], None)
                     except ValueError as exc:                      # too short to analyse: a per-file error
                         res = (None, 'error: %s %s' % (type(exc), exc))
                     with lock:
+                        if decided is not None and res[0] is not None:
+                            decided((src,) + (getattr(sig, 'decision', None) or (None, None)))
                         on_result(i, src, res[0], res[1], time.time() - t0)
                     continue
                 b = job[1]
@@ -399,7 +404,9 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                             on_result(i, src, None, 'error: %s %s' % (type(b.errs[f]), b.errs[f]), share)
                             continue
                         mine = [[(lab, a * .02, c * .02) for lab, a, c in lseg] for lseg in mine]
-                        on_result(i, src, mine if channels is not None else mine[0], None, share)
+                        if decided is not None:
+                            decided((src,) + (getattr(sig, 'decision', None) or (None, None)))
+                        on_result(i, src, mine if multi else mine[0], None, share)
             except BaseException as exc:                           # noqa: B902  propagate to the caller's thread
                 failure.append(exc)
 

@@ -321,8 +321,11 @@ def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False, channel
     sndfmt.source makes of it (a RawSource with its format, a sndfmt.AdpcmSource, or the twin's array), and a WAV at another
     rate or with several channels a RawSource with `resample` and decode_pcm's refusal without it (io.source_of).
     channels='split' (ffmpeg=None): every channel on its own -- io.split_source's source with all channels selected;
-    channels = a list of resample.Mix: those mixes, each on its own -- io.mix_source's source."""
+    channels = a list of resample.Mix: those mixes, each on its own -- io.mix_source's source.
+    channels='auto' (ffmpeg=None): io.auto_source's source -- one signal, the downmix the file's own survey suggests."""
     if channels is not None:
+        if channels == 'auto':
+            return iss_io.auto_source(medianame, resample)
         if channels != 'split':
             return iss_io.mix_source(medianame, channels, resample)[1]
         return iss_io.split_source(medianame, None, resample)[1]
@@ -761,6 +764,31 @@ class Segmenter:
         sel, sigs = iss_io.mix_excerpts(medianame, ranges, mixes, self.resample)
         return self._segment_pairs(medianame, ranges, sel, sigs, batch_files, batch_seconds)
 
+    # ---- survey-guided downmix (an extension): a file surveyed and downmixed from ONE upload, by the mix its survey suggests
+    def _auto_sig(self, medianame):
+        if self.ffmpeg is not None:
+            raise ValueError(f"channels='auto' reads files without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={self.ffmpeg!r} "
+                             f"downmixes every file with -ac 1")
+        return iss_io.auto_source(medianame, self.resample)
+
+    def load_pcm_auto(self, medianame):
+        """-> (pcm, survey, mix).  A file of two or more channels is uploaded once (a coded one decoded once), surveyed on the
+        device and downmixed from the bytes that are there: survey == survey_channels(medianame) to the bit, mix =
+        survey.safe_mix() (survey.py states the rule), pcm exactly load_pcm(medianame) where mix is None and
+        load_pcm_mixes(medianame, [mix])[0] otherwise.  A one-channel file takes load_pcm's path untouched: survey and mix are
+        None.  ValueError naming the argument with ffmpeg set; without resample=True a rate other than 16 kHz is refused as
+        load_pcm_mixes refuses it; a malformed FLAC frame or ADPCM block is the ValueError load_pcm raises."""
+        sig = self._auto_sig(medianame)
+        pcm = self._mono_pcm(sig)
+        return (pcm,) + (getattr(sig, 'decision', None) or (None, None))
+
+    def segment_auto(self, medianame):
+        """-> (segments, survey, mix): survey and mix as load_pcm_auto gives them, segments exactly segment_signal(pcm) of its pcm,
+        from the same single upload.  Whole files only."""
+        sig = self._auto_sig(medianame)
+        mspec, loge, difflen = _sig2feats(self.ctx, sig, medianame)
+        return (self.segment_feats(mspec, loge, difflen, 0),) + (getattr(sig, 'decision', None) or (None, None))
+
     # ---- channel survey: what the channels of a file hold, measured on the device (an extension)
     def _no_ffmpeg_survey(self):
         if self.ffmpeg is not None:
@@ -868,7 +896,7 @@ class Segmenter:
         return self.segment_feats(mspec, loge, difflen, start_sec)
 
     def batch_process(self, linput, loutput, verbose=False, skipifexist=False, nbtry=1, trydelay=2., output_format='csv',
-                      batch_files=None, workers=None, batch_seconds=None, channels=None, mixes=None):
+                      batch_files=None, workers=None, batch_seconds=None, channels=None, mixes=None, decisions=None):
         """segmenter.py:297-335: same arguments, same (t_batch_dur, nb_processed, avg, lmsg) with
         lmsg entries (dst, code, text), code 0 ok / 1 already exists / 2 error, in input order.
         The files run through pipeline.process_files: decode threads, super-batches of at most `batch_files` files /
@@ -884,11 +912,25 @@ class Segmenter:
         mixes (an extension, ffmpeg=None only, not with channels='split'): a mix specification (resample.normalise_mixes), the same
         for every file: every mix of every file is segmented on its own (segment_mixes) and written to <dst stem>.mix<k><ext>,
         the last mix first, so .mix0 existing means the file is complete: skipifexist tests that name.  lmsg as for
-        channels='split'; a file with too few channels for the specification is a code-2 entry like any file that fails to decode."""
+        channels='split'; a file with too few channels for the specification is a code-2 entry like any file that fails to decode.
+        channels='auto' (an extension, ffmpeg=None only, not with mixes): every file of two or more channels is surveyed on the
+        device and downmixed by the mix its own survey suggests (segment_auto; survey.ChannelSurvey.safe_mix states the rule),
+        from one upload and one decode, all files of a pass and a class in one survey launch and one resample launch.  Outputs,
+        names, skipifexist, lmsg and the return value are the default call's: one output per file, at dst; a healthy or
+        one-channel file writes what the default call writes.  decisions: a list that receives (src, survey, mix) per processed
+        file, in completion order (survey and mix None for a one-channel file)."""
         from . import pipeline
-        if channels not in (None, 'split'):
-            raise ValueError(f"channels={channels!r}: None or 'split'")
+        if channels not in (None, 'split', 'auto'):
+            raise ValueError(f"channels={channels!r}: None, 'split' or 'auto'")
         part_name = iss_io.channel_name
+        auto = channels == 'auto'
+        if auto:
+            if mixes is not None:
+                raise ValueError("mixes and channels='auto' exclude each other: 'auto' derives every file's mix from its survey")
+            if self.ffmpeg is not None:
+                raise ValueError(f"channels='auto' reads files without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={self.ffmpeg!r} "
+                                 f"downmixes every file with -ac 1")
+            channels = None                                    # outputs and messages are the default call's
         if mixes is not None:
             if channels is not None:
                 raise ValueError("mixes and channels='split' exclude each other")
@@ -940,7 +982,9 @@ class Segmenter:
                 print('%d/%d' % (done[0] + len(skip), len(linput)), [msgs[i]])
 
         pipeline.process_files(self, linput, on_result, skip=skip, nbtry=nbtry, trydelay=trydelay,
-                               batch_files=batch_files, workers=workers, batch_seconds=batch_seconds, channels=channels)
+                               batch_files=batch_files, workers=workers, batch_seconds=batch_seconds,
+                               **({'channels': 'auto', 'decided': None if decisions is None else decisions.append} if auto
+                                  else {'channels': channels}))
         lmsg = [m for i in range(len(linput)) for m in (msgs[i] if isinstance(msgs[i], list) else [msgs[i]])]
         t_batch_dur = time.time() - t_batch_start
         nb_processed = len([e for e in lmsg if e[1] == 0])

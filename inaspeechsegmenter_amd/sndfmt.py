@@ -31,7 +31,7 @@ from . import _native
 from . import flac
 from . import resample as R
 from .io import _to_float, need_16k_mono
-from .sources import CodedSource, RawSource, host_window, selection
+from .sources import CodedAuto, CodedSource, RawAuto, RawSource, host_window, selection
 
 # benchmark switch (tools/bench_sndfmt.py), not a user option: True makes the ffmpeg-free read expand G.711 and ADPCM on
 # the host (numpy table / iss_adpcm_decode_host, iss_msadpcm_decode_host in the decode threads) instead of handing the stored bytes to the device
@@ -132,6 +132,18 @@ class Sound:
             return RawSource(self.stored(), self.sr, sel=sel)
         x, fmt = self.raw()
         return RawSource(x, self.sr, fmt, sel)
+
+    def auto_source(self, full):
+        """What Segmenter reads for a multi-channel file with channels='auto' (io.auto_source)."""
+        host = _HOST_DECODE and self.kind in _HOST_KINDS
+        if self.kind in _BLOCK and not host:
+            return _BLOCK[self.kind].auto(self, 'pcm' if self.ch == 1 and self.sr == R.SR_OUT else 'stage')
+        if self.ch == 1:                                          # stored samples of one channel: nothing to survey
+            return source(self, True)
+        if host or self.kind in _BLOCK:
+            return RawAuto(self.stored(), self.sr, full=full)
+        x, fmt = self.raw()
+        return RawAuto(x, self.sr, fmt, full)
 
     def stored(self):
         """The array io._parse_wav returns for the WAV twin: (n,) or (n, ch), uint8 / int16 / int32 / float32 / float64."""
@@ -612,6 +624,16 @@ class AdpcmExcerpt(AdpcmSource):
         return np.ascontiguousarray(x) if self.kind == 'pcm' else host_window(x, self.s.sr, self.win, self.sel)
 
 
+class AdpcmAuto(CodedAuto, AdpcmSource):
+    """An IMA ADPCM file for channels='auto' (sources.CodedAuto): kind 'stage' for two or more channels, and for one channel
+    at another rate; 'pcm' for one channel at 16 kHz."""
+    __slots__ = ('decision',)
+
+    def __init__(self, snd, kind='stage'):
+        AdpcmSource.__init__(self, snd, kind)
+        self.size, self.decision = snd.n if kind == 'pcm' else R.out_len(snd.n, snd.sr), None
+
+
 class MsAdpcmSource(AdpcmSource):
     """A Microsoft ADPCM file for the device decoder: AdpcmSource's rows, its own launch (iss_msadpcm_decode) after IMA's."""
     __slots__ = ()
@@ -628,6 +650,11 @@ class MsAdpcmExcerpt(AdpcmExcerpt, MsAdpcmSource):
     __slots__ = ()
 
 
+class MsAdpcmAuto(AdpcmAuto, MsAdpcmSource):
+    """A Microsoft ADPCM file for channels='auto'."""
+    __slots__ = ()
+
+
 class _BlockKind(NamedTuple):
     """What tells the block-coded kinds apart; every `kind in _BLOCK` branch of this module reads its columns."""
     label: str
@@ -635,12 +662,13 @@ class _BlockKind(NamedTuple):
     host: object           # the host build of the decoder (_native)
     source: type
     excerpt: type
+    auto: type
 
 
 _BLOCK = {'ima': _BlockKind('IMA ADPCM', lambda align, ch: (align // ch - 4) * 2 + 1, _native.adpcm_decode_host,
-                            AdpcmSource, AdpcmExcerpt),
+                            AdpcmSource, AdpcmExcerpt, AdpcmAuto),
           'ms': _BlockKind('MS ADPCM', lambda align, ch: (align - 7 * ch) * 2 // ch + 2, _native.msadpcm_decode_host,
-                           MsAdpcmSource, MsAdpcmExcerpt)}
+                           MsAdpcmSource, MsAdpcmExcerpt, MsAdpcmAuto)}
 _HOST_KINDS = ('ulaw', 'alaw') + tuple(_BLOCK)                   # what _HOST_DECODE expands on the host
 
 

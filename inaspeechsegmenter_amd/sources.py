@@ -43,6 +43,13 @@ instead of writing a signal: its sources are `RawSurvey` (stored bytes for iss_s
 excerpt classes (decoded to the staging buffer without a filter, then iss_<coder>_survey), and `Group.survey` is their one
 launch per class, the class's `survey(ctx, staged, jobs, tables, sources)` -> (status, one resample.SurveyFields per source).
 
+A source of io.auto_source (channels='auto': RawAuto, flac.FlacAuto, sndfmt.AdpcmAuto and its Microsoft twin) is staged once and
+read twice on the device: surveyed, then resampled from the bytes that are there.  Its `parts` is 1 and its `size` the downmix's
+length, so a pass is laid out before any survey is known; its class is `two_step`, and `Group.launch` then runs the class's
+`launch_auto(ctx, staged, jobs, tables, sources, n_signal)`: the decode launch for a coder, ONE survey launch, every source told
+its `decision` = (survey.ChannelSurvey, its safe_mix()), ONE resample launch over the staged bytes -- files with a mix and files
+with the plain downmix in the same launch.  A file whose decode status is not clean decides nothing and writes nothing.
+
 `Group` is the only place that stages payloads, numbers job rows, launches and hands the status back; `pass_order` places a
 class's launch among the device calls of a pass.  pipeline._Worker.run, Segmenter.load_pcm_excerpts and Source.place (one file
 alone: segmenter._place) are written against this and nothing else: a new format is one class, and one line in io._classify.
@@ -70,6 +77,13 @@ class Job(NamedTuple):
     row: tuple
     window: tuple = None
     split: tuple = None
+
+
+class AutoJob(NamedTuple):
+    """What a two-step source's `job` returns: the row of its FIRST step (survey row, or decode-to-stage row) and where its
+    signal goes, for the resample row of the second."""
+    row: tuple
+    dst: int
 
 
 class Source:
@@ -138,6 +152,9 @@ class Group:
         self.tables = cls.tables([s for s, _ in placed])
 
     def launch(self, n_signal=-1):
+        if getattr(self.cls, 'two_step', False):     # survey, decide, resample what is staged (AutoSource)
+            self.status = self.cls.launch_auto(self.ctx, self.staged, self.jobs, self.tables, [s for s, _ in self.placed], n_signal)
+            return self
         kw = {}                                      # (a plain launch: the call every launch made before there were any)
         if any(j.window is not None for j in self.jobs):
             kw['windows'] = [j.window for j in self.jobs]
@@ -199,6 +216,46 @@ class RawSource(Source):
     @staticmethod
     def launch(ctx, staged, rows, tables, n_signal=-1, **kw):
         ctx.resample(staged, rows, n_signal, **kw)
+
+
+class AutoSource:
+    """What the sources of io.auto_source share (a mixin in front of a source class of its format): `full`, the fullscale
+    threshold of the survey; `decision`, None until the launch, then (survey.ChannelSurvey, resample.Mix or None)."""
+    __slots__ = ()
+    two_step = True
+
+    def job(self, ctx, src_offset, unit_begin, dst_offset):
+        return AutoJob(self.row(ctx, src_offset, unit_begin, dst_offset), dst_offset)
+
+    def decide(self, fields, sr):
+        from .survey import ChannelSurvey
+        survey = ChannelSurvey(fields, sr, 0)
+        self.decision = (survey, survey.safe_mix())
+        return None if self.decision[1] is None else (self.stride, [self.decision[1]])
+
+
+class RawAuto(AutoSource, RawSource):
+    """A file of two or more channels as stored, for channels='auto': surveyed by iss_survey, then downmixed -- by the mix its
+    survey suggests, or plainly -- and resampled from the survey's upload (iss_resample_staged_mix)."""
+    __slots__ = ('full', 'decision')
+
+    def __init__(self, x, sr, fmt=None, full=1.0):
+        RawSource.__init__(self, x, sr, fmt)
+        self.full, self.decision = float(full), None
+
+    def row(self, ctx, src_offset, unit_begin, dst_offset):
+        """Its SURVEY_JOB row (the first step); `staged_row` is the RS_JOB row over the same bytes."""
+        return (src_offset, self.x.shape[0], self.x.shape[1], self.fmt, self.full)
+
+    def staged_row(self, ctx, src_offset, dst_offset):
+        return RawSource.row(self, ctx, src_offset, 0, dst_offset)
+
+    @staticmethod
+    def launch_auto(ctx, staged, jobs, tables, srcs, n_signal=-1):
+        fields = ctx.survey(staged, [j.row for j in jobs])            # the one upload; valid on return
+        payload = ctx.staged_payload(None)
+        mixes = [s.decide(f, s.sr) for s, f in zip(srcs, fields)]
+        ctx.resample_staged(None, payload, [s.staged_row(ctx, j.row[0], j.dst) for s, j in zip(srcs, jobs)], n_signal, mixes=mixes)
 
 
 class RawExcerpt(RawSource):
@@ -276,6 +333,39 @@ class CodedSource(Source):
         status = cls.launch(ctx, staged, [j.row for j in jobs], tables, 0, windows=[j.window for j in jobs])
         rows = [(k, s.win[4], s.s.ch, s.stage_format, s.full) for k, s in enumerate(srcs)]
         return status, ctx.survey(None, rows, coder=cls.coder)
+
+
+class CodedAuto(AutoSource):
+    """The mixin of a coder's source for channels='auto' (flac.FlacAuto, sndfmt.AdpcmAuto, sndfmt.MsAdpcmAuto).  kind 'stage':
+    decoded to the staging buffer without a filter, as a survey's sources are, and resampled from there -- a file of two or more
+    channels surveyed there first (iss_<coder>_survey) and told its mix, a one-channel file at another rate resampled as it is.
+    kind 'pcm' (one channel at 16 kHz): PCM16 straight into the signal, as ever.  The one-channel files of a coder are of this
+    class so that a pass makes ONE decode call per coder: a call's status array and staging buffer are the coder's only ones."""
+    __slots__ = ()
+
+    @classmethod
+    def launch_auto(cls, ctx, staged, jobs, tables, srcs, n_signal=-1):
+        status = cls.launch(ctx, staged, [j.row for j in jobs], tables, n_signal)      # the one decode call (n_signal >= 0: a zeroed signal)
+        to_stage = [k for k, s in enumerate(srcs) if s.kind == 'stage']
+        if not to_stage:
+            return status
+        payload = ctx.staged_payload(cls.coder)
+        multi = [k for k in to_stage if srcs[k].s.ch > 1]
+        fields = {}
+        if multi:                                                     # (the survey synchronises: the status is valid after it)
+            rows = [(k, srcs[k].s.n, srcs[k].s.ch, srcs[k].stage_format, srcs[k].full) for k in multi]
+            fields = dict(zip(multi, ctx.survey(None, rows, coder=cls.coder)))
+        ubeg = np.concatenate(([0], np.cumsum([s.units for s in srcs])))
+        rows, mixes = [], []
+        for k in to_stage:
+            s = srcs[k]
+            if multi and np.any(status[ubeg[k]:ubeg[k + 1]]):         # a malformed file decides nothing and writes nothing
+                continue
+            mixes.append(s.decide(fields[k], s.s.sr) if k in fields else None)
+            rows.append((k, s.s.n, s.s.ch, s.stage_format, ctx.resample_filter(s.s.sr)[0], 0, jobs[k].dst, s.size))
+        if rows:
+            ctx.resample_staged(cls.coder, payload, rows, -1, mixes=mixes)
+        return status
 
 
 def held(sig):

@@ -103,6 +103,31 @@ class ChannelSurvey:
             return []
         return [(c, d) for c, d in self.pairs if self.corr(c, d) <= threshold]
 
+    def safe_mix(self):
+        """The downmix this survey suggests in place of the mean of all channels -> a resample.Mix, or None for "the plain
+        downmix".  A definition, as active() and inverted() are, computed from the measured fields only, through active() and
+        corr() with their default floor and threshold:
+          1. A = active().  One channel, or A empty (a silent file has nothing to save): None.
+          2. Signs.  Without pair sums (s12 None: more than resample.SURVEY_PAIR_CHANNELS channels) every sign is +1.  Else r = the
+             channel of A with the largest s2 (ties: the lowest index), and for every other c of A the sign is -1 where
+             corr(r, c) <= INVERTED_CORR, else +1 (NaN: +1).
+          3. A = all channels and every sign +1: None.
+          4. Else Mix(terms = (c, sign[c]) for c of A ascending, divisor = len(A)): the mean of the channels kept, the inverted
+             ones turned back.  It divides by the number of terms, so no mix saturates.
+        None rides as a job without mixes, whose output is the default call's to the bit: a healthy file is read as ever."""
+        act = self.active()
+        if self.channels == 1 or not act:
+            return None
+        sign = {c: 1.0 for c in act}
+        if self.s12 is not None:
+            r = max(act, key=lambda c: (float(self.s2[c]), -c))
+            for c in act:
+                if c != r and self.corr(r, c) <= INVERTED_CORR:      # (NaN compares False)
+                    sign[c] = -1.0
+        if len(act) == self.channels and all(v == 1.0 for v in sign.values()):
+            return None
+        return R.Mix(tuple((c, sign[c]) for c in act), float(len(act)))
+
     def rows(self, floor_db=ACTIVE_FLOOR_DB):
         """One tuple per channel for printing: (channel, frames, peak, rms_db, dc, zeros, fullscale, nonfinite, active)."""
         act, db, dc = set(self.active(floor_db)), self.rms_db, self.dc
@@ -133,3 +158,34 @@ def write_tsv(dst, names, surveys):
             loss = s.downmix_loss_db
             f.write('\t'.join([name, '*', str(s.n), '', '' if loss is None else repr(loss), '', '', '', '',
                                ','.join(f'{c}-{d}' for c, d in s.inverted())]) + '\n')
+
+
+DECISION_COLUMNS = ('path', 'plan', 'kept', 'flipped', 'downmix_loss_db')
+
+
+def write_decisions_tsv(dst, names, decisions, failed=None):
+    """The table `--channels auto --decisions` of scripts/ina_speech_segmenter_amd.py writes: one row per file of `names`, in
+    that order, under DECISION_COLUMNS.  decisions = [(path, survey, mix)] as batch_process(channels='auto', decisions=...)
+    collects them.  plan: `mono` (no survey: a one-channel file), `plain` (the mean of all channels, as ever) or `mix`; kept:
+    the channels of the downmix, comma-joined (all of them for `plain`); flipped: those of them summed with weight -1;
+    downmix_loss_db as the survey states it (empty where it has none).  A file in `failed` (path -> error text), or one without a
+    decision, gets plan `!` and the text in the last column.  A path listed more than once takes its decisions in their order."""
+    by_name = {}                                       # path -> its decisions in the order they came: a path may be listed twice
+    for d in decisions:
+        by_name.setdefault(d[0], []).append(d)
+    failed = failed or {}
+    with open(dst, 'w') as f:
+        f.write('\t'.join(DECISION_COLUMNS) + '\n')
+        for name in names:
+            if name in failed or not by_name.get(name):
+                text = str(failed.get(name, 'not processed')).replace('\t', ' ').replace('\n', ' ')
+                f.write('\t'.join([name, '!', '', '', text]) + '\n')
+                continue
+            _, survey, mix = by_name[name].pop(0)
+            if survey is None:
+                f.write('\t'.join([name, 'mono', '0', '', '']) + '\n')
+                continue
+            loss = survey.downmix_loss_db
+            terms = [(c, 1.0) for c in range(survey.channels)] if mix is None else mix.terms
+            f.write('\t'.join([name, 'plain' if mix is None else 'mix', ','.join(str(c) for c, _ in terms),
+                               ','.join(str(c) for c, w in terms if w < 0), '' if loss is None else repr(loss)]) + '\n')

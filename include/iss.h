@@ -511,6 +511,41 @@ int iss_msadpcm_survey(iss_ctx* ctx, const iss_survey_job* jobs, const iss_windo
 int iss_survey_geometry(int32_t* chunk_out, int32_t* lanes_out, int32_t* pair_channels_out);
 int iss_survey_stats(iss_ctx* ctx, int64_t* launches, int64_t* jobs);     /* survey_kernel launches, jobs surveyed */
 
+/* Resampling what an earlier call left on the device: the rows of a *_mix call over bytes that are already there, so that a survey
+ * of a file and its downmix -- any mix the survey suggests, or the plain one -- cost one upload and one decode.  Nothing is uploaded
+ * but rows and tables; the kernels are the resample_kernel instantiations of iss_resample_pcm16_mix, and so is the arithmetic.
+ * An ORIGIN is one of four device buffers and what its last writer left in it:
+ *   ISS_STAGED_SURVEY    the payload of the context's last iss_survey (`src`, src_bytes of it).  A row must be one of that call's
+ *                        jobs: the same src_offset (a byte offset), frames_in, channels and format.
+ *   ISS_STAGED_FLAC / ISS_STAGED_ADPCM / ISS_STAGED_MSADPCM
+ *                        what the codec's last decode call staged (TO_STAGE jobs, with or without a filter).  src_offset of a row
+ *                        is the INDEX of the staged job of that call, as in iss_survey_job; format is ISS_RS_I16 or ISS_RS_I32 as
+ *                        staged; frames_in * channels samples are exactly what the job staged (a windowed decode job: its
+ *                        s_end - s_begin frames).
+ * A PAYLOAD is what an origin holds, named by an id that counts up over the context's life: every iss_survey that uploads, and
+ * every decode call of a codec that launches, leaves a new one in its origin.  iss_staged_payload gives the id of the payload an
+ * origin holds now (ISS_ESTATE: none -- no such call went before, or the last one failed on its way).  The caller takes it right
+ * after the call that made the payload and hands it to iss_resample_staged_mix, which refuses any other.
+ * iss_resample_staged_mix: filter, dst_offset, frames_out, the optional window rows, mix-set, mix and term rows, mix_count == 0
+ * (the plain downmix, to the bit what iss_resample_pcm16 writes), n_signal, counters and every error of iss_resample_pcm16_mix hold
+ * as written there, with the origin's bytes in the place of `src`.  One launch for all jobs.
+ * ISS_ESTATE (nothing launched, the context unchanged; the text names the entry point and the origin): the origin holds no
+ * payload, or `payload` is not the one it holds -- a later call of that origin (any upload into the survey's source buffer, any
+ * decode call of that codec) has replaced it.  n_signal < 0 without a signal: as iss_resample_pcm16.
+ * ISS_EINVAL (found before anything changes): a row that does not match what was uploaded or staged in frames, channels or
+ * format; a bad origin; everything iss_resample_pcm16_mix refuses.                                                              */
+#define ISS_STAGED_SURVEY   0
+#define ISS_STAGED_FLAC     1
+#define ISS_STAGED_ADPCM    2
+#define ISS_STAGED_MSADPCM  3
+int iss_staged_payload(iss_ctx* ctx, int32_t origin, int64_t* payload_out);
+int iss_resample_staged_mix(iss_ctx* ctx, int32_t origin, int64_t payload, const iss_resample_job* jobs, const iss_window* windows,
+                            int32_t njobs, int64_t n_signal, const iss_mixset* mixsets, const iss_mix* mixes, int64_t nmixes,
+                            const iss_mix_term* terms, int64_t nterms);
+/* Payload H2D copies (stored bytes for the resampler and the survey, compressed bytes for the decoders: not row tables, not
+ * signals) and their bytes since the context was created: what "one upload per file" is counted with.                           */
+int iss_upload_stats(iss_ctx* ctx, int64_t* copies, int64_t* bytes);
+
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */
 int iss_host_alloc(iss_ctx* ctx, size_t bytes, void** out);
@@ -832,7 +867,8 @@ int iss_prof_get_instance(iss_ctx* ctx, int index, char* name_out, int32_t name_
  * dither stream, every table and every network's parameters.  The row flags of the resident features are recomputed at
  * the next call that needs them.  A result of the library is a function of its inputs, parameters, mode and switches
  * only, so no call made afterwards may return anything else than before: the tests use this entry with NaN, -inf, 0 and
- * FLT_MAX to hold that.  What iss_flac_get_stage / iss_adpcm_get_stage would return is gone.  Not for production.     */
+ * FLT_MAX to hold that.  What iss_flac_get_stage / iss_adpcm_get_stage would return is gone, and so is every payload an
+ * origin of iss_resample_staged_mix held: that call is ISS_ESTATE until a new survey or decode call.  Not for production. */
 int iss_scribble(iss_ctx* ctx, uint32_t word);
 
 /* The operand split of the conv kernels over an array: x[i] = hi + lo with hi = rne16(x[i]), lo = rne16(x[i] - hi), the

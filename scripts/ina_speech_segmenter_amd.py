@@ -42,9 +42,15 @@ def build_parser():
     ap.add_argument('--resample', action='store_true',
                     help='with -b None: downmix and resample files of other rates / channel counts (8 kHz G.711 telephony, 44.1 kHz AIFF ...) to '
                          '16 kHz mono on the GPU')
-    ap.add_argument('--channels', choices=['mix', 'split'], default='mix',
+    ap.add_argument('--channels', choices=['mix', 'split', 'auto'], default='mix',
                     help="with -b None: 'split' segments every channel of a file on its own (two-channel call recordings, multi-track "
-                         "broadcast files) and writes <basename>.ch<k>.<format> per channel; 'mix' downmixes as ever")
+                         "broadcast files) and writes <basename>.ch<k>.<format> per channel; 'auto' surveys every multichannel file "
+                         "on the GPU and downmixes it without its dead channels, polarity-inverted channels turned back, from the "
+                         "same upload (a healthy file as ever); 'mix' downmixes as ever")
+    ap.add_argument('--decisions', default=None, metavar='OUT.tsv',
+                    help="with --channels auto: write what was decided per file to OUT.tsv -- path, plan (mono, plain, mix; '!' for "
+                         'a file that failed, with the error text), the channels kept, those of them turned back, and what the '
+                         'default downmix would have lost in dB')
     ap.add_argument('--mixes', default=None, metavar='SPEC',
                     help='with -b None: segment weighted mixes of the channels of every file, each on its own, and write '
                          '<basename>.mix<k>.<format> per mix.  Mixes are separated by commas, terms joined by "+": "0+1,2+3" is the '
@@ -67,6 +73,14 @@ def main(argv=None):
         build_parser().error('--channels split needs -b None (ffmpeg downmixes every file)')
     if args.channels == 'split' and int(os.environ.get('WORLD_SIZE', '1')) != 1:
         build_parser().error('--channels split runs on one GPU')
+    if args.channels == 'auto' and ffmpeg is not None:
+        build_parser().error('--channels auto needs -b None (ffmpeg downmixes every file)')
+    if args.channels == 'auto' and int(os.environ.get('WORLD_SIZE', '1')) != 1:
+        build_parser().error('--channels auto runs on one GPU')
+    if args.channels == 'auto' and args.mixes is not None:
+        build_parser().error('--mixes and --channels auto exclude each other')
+    if args.decisions is not None and args.channels != 'auto':
+        build_parser().error('--decisions goes with --channels auto')
     mixes = None
     if args.mixes is not None:
         if ffmpeg is not None:
@@ -107,6 +121,16 @@ def main(argv=None):
         return 0
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
+        if world == 1 and args.channels == 'auto':
+            decisions = []
+            lmsg = seg.batch_process(inputs, outputs, verbose=True, output_format=args.export_format, channels='auto',
+                                     decisions=decisions)[3]
+            if args.decisions is not None:
+                from inaspeechsegmenter_amd.survey import write_decisions_tsv
+                failed = {dst: text for dst, code, text in lmsg if code == 2}
+                write_decisions_tsv(args.decisions, inputs, decisions, {src: failed[dst] for src, dst in zip(inputs, outputs)
+                                                                        if dst in failed})
+            return 0
         if world == 1:
             seg.batch_process(inputs, outputs, verbose=True, output_format=args.export_format,
                               **({'channels': 'split'} if args.channels == 'split' else {}),
