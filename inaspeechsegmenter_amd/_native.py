@@ -48,6 +48,8 @@ MIXSET = np.dtype([('dst_stride', '<i8'), ('mix_begin', '<i4'), ('mix_count', '<
 MIX = np.dtype([('term_begin', '<i4'), ('term_count', '<i4'), ('divisor', '<f8')])
 MIX_TERM = np.dtype([('channel', '<i4'), ('reserved', '<i4'), ('weight', '<f8')])
 # iss_survey_job (include/iss.h): a row of the survey entry points
+SET = np.dtype([('member_begin', '<i4'), ('member_count', '<i4')])                                       # iss_set, beside every job
+SET_MEMBER = np.dtype([('src_offset', '<i8'), ('frames', '<i8'), ('channels', '<i4'), ('reserved', '<i4')])   # iss_set_member
 SURVEY_JOB = np.dtype([('src_offset', '<i8'), ('frames_in', '<i8'), ('channels', '<i4'), ('format', '<i4'), ('full', '<f8')])
 # ISS_FLAC_* frame status codes -> reason
 FLAC_STATUS = {1: 'reserved subframe type', 2: 'subframe header padding bit set', 3: 'wasted bits exceed the sample size',
@@ -108,6 +110,26 @@ def _mix_rows(mixes, njobs):
     return sets, rows, terms
 
 
+def _set_rows(jb, members):
+    """(job rows, SET rows, SET_MEMBER rows) for a *_set entry point (include/iss.h, "File sets").  members: per job a list of
+    `(byte offset, frames, channels)`, the offset counted from the job row's src_offset -- where the job's payload lies in the
+    source, as a source's `row` states it --, which then becomes the 0 a set job states.  A pair of arrays (SET rows,
+    SET_MEMBER rows) is handed on as given, and so are the job rows."""
+    if isinstance(members, tuple) and len(members) == 2 and isinstance(members[0], np.ndarray):
+        return (np.ascontiguousarray(jb), np.ascontiguousarray(members[0], dtype=SET).reshape(-1),
+                np.ascontiguousarray(members[1], dtype=SET_MEMBER).reshape(-1))
+    if len(members) != jb.size:
+        raise ValueError(f'{len(members)} member lists for {jb.size} jobs')
+    jb = jb.copy()
+    sets, rows = np.zeros(jb.size, dtype=SET), []
+    for k, ms in enumerate(members):
+        sets[k] = (len(rows), len(ms))
+        base = int(jb['src_offset'][k])
+        rows.extend((base + int(off), int(frames), int(ch), 0) for off, frames, ch in ms)
+    jb['src_offset'] = 0
+    return jb, sets, np.array(rows, dtype=SET_MEMBER).reshape(-1)
+
+
 _lib = None
 
 
@@ -166,6 +188,9 @@ def lib():
         'iss_staged_payload': (C.c_int, [vp, i32, pi64]),
         'iss_resample_staged_mix': (C.c_int, [vp, i32, i64, vp, vp, i32, i64, vp, vp, i64, vp, i64]),
         'iss_upload_stats': (C.c_int, [vp, pi64, pi64]),
+        'iss_resample_pcm16_set': (C.c_int, [vp, vp, i64, vp, i32, i64, vp, vp, i64, vp, vp, i64, vp, i64]),
+        'iss_survey_set': (C.c_int, [vp, vp, i64, vp, i32, vp, vp, i64, vp]),
+        'iss_resample_staged_set': (C.c_int, [vp, i32, i64, vp, i32, i64, vp, vp, i64, vp, vp, i64, vp, i64]),
         'iss_survey': (C.c_int, [vp, vp, i64, vp, vp, i32, vp]),
         'iss_flac_survey': (C.c_int, [vp, vp, vp, i32, vp]),
         'iss_adpcm_survey': (C.c_int, [vp, vp, vp, i32, vp]),
@@ -520,6 +545,32 @@ class Context:
             jb.size, int(n_signal), C.c_void_p(sets.ctypes.data), C.c_void_p(rows.ctypes.data), rows.size,
             C.c_void_p(terms.ctypes.data), terms.size), 'iss_resample_staged_mix')
 
+    # ---- file sets (iss_*_set): one file per channel or group of channels, read as the interleaved file they stand for
+    def resample_set(self, src, jobs, members, n_signal=-1, mixes=None):
+        """iss_resample_pcm16_set: `resample` with `mixes` for file sets, whole sources only.  src = the members' stored bytes,
+        jobs = rows of RS_JOB stating each set's frames_in (its longest member's) and channels (all members'), src_offset = where
+        the job's payload lies in src; members: per job [(byte offset in that payload, frames, channels)].  mixes: as for
+        `resample` (a channel index = that channel alone, so a split rides here too); None, or None for a job, is the plain
+        downmix of the set's interleaved twin."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        jb, sets, mem = _set_rows(np.array(jobs, dtype=RS_JOB).reshape(-1), members)
+        ms, rows, terms = _mix_rows([None] * jb.size if mixes is None else mixes, jb.size)
+        self._ck(self._L.iss_resample_pcm16_set(
+            self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data), jb.size, int(n_signal),
+            C.c_void_p(sets.ctypes.data), C.c_void_p(mem.ctypes.data), mem.size, C.c_void_p(ms.ctypes.data),
+            C.c_void_p(rows.ctypes.data), rows.size, C.c_void_p(terms.ctypes.data), terms.size), 'iss_resample_pcm16_set')
+        self._keep_rs = src         # the async H2D copy reads it until the next sync
+
+    def resample_staged_set(self, payload, jobs, members, n_signal=-1, mixes=None):
+        """iss_resample_staged_set: `resample_set` over the bytes the last `survey_set` uploaded (payload = staged_payload(None)
+        right after it); jobs and members as that call's.  Nothing is uploaded but rows."""
+        jb, sets, mem = _set_rows(np.array(jobs, dtype=RS_JOB).reshape(-1), members)
+        ms, rows, terms = _mix_rows([None] * jb.size if mixes is None else mixes, jb.size)
+        self._ck(self._L.iss_resample_staged_set(
+            self._h, STAGED_ORIGIN[None], int(payload), C.c_void_p(jb.ctypes.data), jb.size, int(n_signal),
+            C.c_void_p(sets.ctypes.data), C.c_void_p(mem.ctypes.data), mem.size, C.c_void_p(ms.ctypes.data),
+            C.c_void_p(rows.ctypes.data), rows.size, C.c_void_p(terms.ctypes.data), terms.size), 'iss_resample_staged_set')
+
     def upload_stats(self):
         """(payload H2D copies, their bytes) since the context was created: stored and compressed bytes, not rows or signals."""
         return self._counters('iss_upload_stats')
@@ -646,18 +697,43 @@ class Context:
         beside every job: its bytes hold frames [s_begin, s_end) of the file and frames [out_begin, out_begin + out_count) are
         surveyed.  coder ('flac', 'adpcm', 'msadpcm'; src is then None): iss_<coder>_survey over what the coder's last decode
         call staged, src_offset of a row the index of the staged job."""
-        from .resample import SurveyFields, SURVEY_PAIR_CHANNELS
         jb = np.ascontiguousarray(np.array(jobs, dtype=SURVEY_JOB).reshape(-1))
         wn = None if windows is None else _window_rows(windows, jb.size)
-        chs = [int(c) for c in jb['channels']]
-        width = [6 * c + (c * (c - 1) // 2 if c <= SURVEY_PAIR_CHANNELS else 0) for c in chs]
-        out = np.zeros(max(sum(width), 1), dtype=np.float64)
+        out = self._survey_out(jb)
         tail = (C.c_void_p(jb.ctypes.data), None if wn is None else C.c_void_p(wn.ctypes.data), jb.size, C.c_void_p(out.ctypes.data))
         if coder is None:
             src = np.ascontiguousarray(src, dtype=np.uint8)
             self._ck(self._L.iss_survey(self._h, C.c_void_p(src.ctypes.data), src.size, *tail), 'iss_survey')
         else:
             self._ck(getattr(self._L, f'iss_{coder}_survey')(self._h, *tail), f'iss_{coder}_survey')
+        return self._survey_fields(jb, wn, out)
+
+    def survey_set(self, src, jobs, members):
+        """iss_survey_set: iss_survey (without windows) for file sets.  src = the members' stored bytes, jobs = rows of
+        SURVEY_JOB stating each set's frames (its longest member's) and channels (all members'), src_offset = where the job's
+        payload lies in src; members: per job [(byte offset in that payload, frames, channels)] -> one resample.SurveyFields per
+        job, those of the set's interleaved twin."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        jb, sets, mem = _set_rows(np.array(jobs, dtype=SURVEY_JOB).reshape(-1), members)
+        out = self._survey_out(jb)
+        self._ck(self._L.iss_survey_set(self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data), jb.size,
+                                        C.c_void_p(sets.ctypes.data), C.c_void_p(mem.ctypes.data), mem.size,
+                                        C.c_void_p(out.ctypes.data)), 'iss_survey_set')
+        return self._survey_fields(jb, None, out)
+
+    @staticmethod
+    def _survey_out(jb):
+        """The result words of the survey jobs `jb`, zeroed."""
+        from .resample import SURVEY_PAIR_CHANNELS
+        return np.zeros(max(sum(6 * c + (c * (c - 1) // 2 if c <= SURVEY_PAIR_CHANNELS else 0) for c in map(int, jb['channels'])), 1),
+                        dtype=np.float64)
+
+    @staticmethod
+    def _survey_fields(jb, wn, out):
+        """The result rows `out` of the survey jobs `jb` (windows `wn`) -> one resample.SurveyFields per job."""
+        from .resample import SurveyFields, SURVEY_PAIR_CHANNELS
+        chs = [int(c) for c in jb['channels']]
+        width = [6 * c + (c * (c - 1) // 2 if c <= SURVEY_PAIR_CHANNELS else 0) for c in chs]
         res, pos = [], 0
         for k, (c, w) in enumerate(zip(chs, width)):
             r = out[pos:pos + w]

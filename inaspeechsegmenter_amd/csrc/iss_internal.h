@@ -108,7 +108,8 @@ struct iss_ctx {
     IssCounters sv_count;                 // survey_kernel launches, jobs
     // what a later call may resample without uploading it again (iss_resample_staged_mix): the payload of the last iss_survey in
     // sv_src, with the rows that describe it; a codec's is its IssCodec::held.  Ids count up over all origins of the context
-    struct Held { int64_t id = 0, bytes = 0; std::vector<iss_survey_job> jobs; } sv_held;
+    // (a payload of iss_survey_set: the set row of every job and the call's member rows too; else both empty)
+    struct Held { int64_t id = 0, bytes = 0; std::vector<iss_survey_job> jobs; std::vector<iss_set> sets; std::vector<iss_set_member> members; } sv_held;
     int64_t held_seq = 0;
     IssCounters up_count;                 // iss_upload_payload: copies, bytes (iss_upload_stats)
 
@@ -226,9 +227,15 @@ struct RsSplitDev { int64_t dst_stride, ntiles; int32_t sel_begin, sel_count, gr
 struct RsMixDev { int64_t dst_stride, ntiles; int32_t mix_begin, mix_count, group, stride; };
 struct RsMixRow { int32_t term_begin, term_count; double divisor; };
 struct RsTermDev { int32_t channel, pad; double weight; };
-static_assert(sizeof(RsMixRow) == 16 && sizeof(RsTermDev) == 16, "one array of 16-byte rows");
+// a term row of a set call (include/iss.h, "File sets") in the place of RsTermDev, two 16-byte rows: the term's channel resolved
+// on the host to where it lies -- sample (j, that channel) of its member at byte off + j * step * sample bytes, 0.0 from frame
+// `frames` on
+struct RsSetTermDev { int64_t off, frames; double weight; int32_t step, pad; };
+static_assert(sizeof(RsMixRow) == 16 && sizeof(RsTermDev) == 16 && sizeof(RsSetTermDev) == 32, "one array of 16-byte rows");
 // the three tables of a *_mix entry point (include/iss.h); `sets` one per job
 struct IssMixTables { const iss_mixset* sets; const iss_mix* mixes; int64_t nmixes; const iss_mix_term* terms; int64_t nterms; };
+// the two tables of a *_set entry point; `sets` one per job
+struct IssSetTables { const iss_set* sets; const iss_set_member* members; int64_t nmembers; };
 struct IssRsPlan {
     std::vector<RsJobDev> dj;
     std::vector<RsWinDev> dw;             // empty: no windows, the launch every call made before there were any
@@ -237,15 +244,18 @@ struct IssRsPlan {
     std::vector<RsMixDev> dm;             // empty: no mixes, likewise
     std::vector<RsMixRow> mixes;          // the mix rows the rows of dm point into ...
     std::vector<RsTermDev> terms;         // ... and the term rows those point into
+    std::vector<RsSetTermDev> sterms;     // a set call: its term rows in the place of `terms`, and `set` says so
+    bool set = false;
     int64_t tiles = 0, lds = 0;
 };
 // `ranges`: destination ranges of other writers of the same call, checked for overlap with the jobs' (error texts start with `who`)
 // `wins`: NULL, or a window beside every job (include/iss.h);  `splits`: NULL, or a split beside every job, into sel[0, nsel);
 // `mix`: NULL, or the tables of a mix call with a mix set beside every job (never together with `splits`)
+// `set`: NULL, or the tables of a set call with a set beside every job (with `mix`, without `wins`): the jobs read their members
 int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes, int64_t nsig,
                       std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan,
                       const iss_split* splits = nullptr, const int32_t* sel = nullptr, int64_t nsel = 0,
-                      const IssMixTables* mix = nullptr);
+                      const IssMixTables* mix = nullptr, const IssSetTables* set = nullptr);
 int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& plan);
 
 // implemented in the .hip files

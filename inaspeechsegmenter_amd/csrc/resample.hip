@@ -38,6 +38,13 @@
 // the mixes q of its group ((frame, mix) flattened over the threads, the terms in order, every product, sum and the one
 // division rounded on its own) and runs step 3 once per mix.  Geometry is split_geometry's for mix_count rows; a job without
 // mixes (mix_count 0) is the downmix above, in the same launch.  Table: job rows, (window rows,) mix-set rows, mix rows, terms.
+//
+// File sets (include/iss.h, iss_set): SET = true is one more pair, MIX without windows, for calls whose jobs read the members of a
+// file set -- one file per channel or per group of channels -- as the interleaved file they stand for.  The planner resolves every
+// term of every mix to the member its channel lies in (RsSetTermDev: byte offset, frames, channels of the member) and writes a
+// job without mixes as the mix of all its channels (w = 1, d = their count: the downmix above, to the bit), so the workgroup
+// only stages differently: stage_set_mixes, (mix, frame) flattened over the threads with the frame running fastest -- a wave
+// reads consecutive frames of one member --, a sample past the end of a member 0.0.  Step 3 is the code above.
 #include "decode_pass.h"
 #include "rs_readers.h"      // to_f64, the Ld* readers, stage_channels: shared with survey.hip
 #include <algorithm>
@@ -110,9 +117,13 @@ __device__ __forceinline__ void stage_mixes(const uint8_t* __restrict__ src, int
 // of a MIX launch: the downmix, or the gc mixes from `mix` on (rows of the 16-byte table `rows`, which holds their terms too)
 struct RsGroup { int64_t dst_stride; int stride, c0, gc; const int32_t* sel; const RsMixRow* mix; const RsTermDev* rows; };
 
-template <typename L, bool WIN, bool SPLIT, bool MIX>
+template <typename L, bool WIN, bool SPLIT, bool MIX, bool SET>
 __device__ __forceinline__ void stage(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
                                       double* __restrict__ span, const RsWinDev& W, const RsGroup& G) {
+    if constexpr (SET) {                                   // every job of a set call has mixes: the planner wrote its downmix as one
+        stage_set_mixes<L>(src, n_in, s0, len, span, G.stride, G.gc, G.mix, G.rows);
+        return;
+    }
     if constexpr (SPLIT) {
         if (G.gc > 0) { stage_channels<L, WIN>(src, n_in, ch, s0, len, span, G.stride, G.c0, G.gc, G.sel, W); return; }
     }
@@ -144,11 +155,14 @@ __device__ __forceinline__ void compute_tile(const RsJobDev& J, const double* __
 // switch, and so its code, is what it was before the newer formats existed); EXT = true adds them behind the default case.
 // SPLIT = false is the kernel every call without splits launches; SPLIT = true reads the split table and the channel selections
 // that follow the rows.  MIX = true (never with SPLIT) reads the mix-set table and the mix and term rows that follow it.
-#define RS_STAGE(L) stage<L, WIN, SPLIT, MIX>(s, J.n_in, J.ch, s0, len, span, W, G)
-template <bool EXT, bool WIN, bool SPLIT, bool MIX = false>
+// SET = true (only with MIX, never with WIN; include/iss.h, "File sets") is the pair for calls whose jobs read the members of a
+// file set: the tables are a mix call's, the term rows RsSetTermDev in the place of RsTermDev, and stage_set_mixes reads them.
+#define RS_STAGE(L) stage<L, WIN, SPLIT, MIX, SET>(s, J.n_in, J.ch, s0, len, span, W, G)
+template <bool EXT, bool WIN, bool SPLIT, bool MIX = false, bool SET = false>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __restrict__ src, const RsJobDev* __restrict__ jobs,
                                                               int njobs, int16_t* __restrict__ dst) {
     static_assert(!(SPLIT && MIX), "a call carries split rows or mix-set rows");
+    static_assert(!SET || (MIX && !WIN), "a set call is a mix call over whole sources");
     extern __shared__ __attribute__((aligned(16))) double rs_smem[];
     const int64_t b = blockIdx.x;
     int lo = 0, hi = njobs - 1;                                             // last job whose tile_base <= b
@@ -288,7 +302,7 @@ static int64_t floor_div_host(int64_t a, int64_t b) { return a >= 0 ? a / b : -(
 
 int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes,
                       int64_t nsig, std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan,
-                      const iss_split* splits, const int32_t* sel, int64_t nsel, const IssMixTables* mix) {
+                      const iss_split* splits, const int32_t* sel, int64_t nsel, const IssMixTables* mix, const IssSetTables* set) {
     // validate every job, build the device descriptors and the tile prefix sum
     std::vector<RsJobDev>& dj = plan.dj;
     dj.assign((size_t)njobs, RsJobDev{});
@@ -301,7 +315,17 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
     if (mix && (splits || (njobs > 0 && !mix->sets) || mix->nmixes < 0 || mix->nmixes > 0x3fffffffLL || (mix->nmixes > 0 && !mix->mixes) ||
                 mix->nterms < 0 || mix->nterms > 0x3fffffffLL || (mix->nterms > 0 && !mix->terms)))
         return iss_fail(c, ISS_EINVAL, "%s: bad mix tables", who);
-    if (mix) {                                             // the device's rows: the mixes, then the terms they count from there
+    plan.sterms.clear();
+    plan.set = set != nullptr;
+    if (set && (!mix || wins || (njobs > 0 && !set->sets) || set->nmembers < 0 || (set->nmembers > 0 && !set->members)))
+        return iss_fail(c, ISS_EINVAL, "%s: bad set tables", who);
+    // a set call: the device's rows are written job by job below -- a job's mixes (its downmix: one mix of all its channels), their
+    // terms resolved to the job's members --, the mix rows first: as many as the jobs' mix counts add up to, 1 for a downmix
+    int64_t set_mixes = 0;
+    for (int32_t k = 0; set && k < njobs; ++k) set_mixes += std::max(mix->sets[k].mix_count, 1);
+    if (set_mixes > 0x3fffffffLL) return iss_fail(c, ISS_EINVAL, "%s: %lld mixes in one call", who, (long long)set_mixes);
+    std::vector<SetChanDev> chans;                         // the channels of the job at hand
+    if (mix && !set) {                                     // the device's rows: the mixes, then the terms they count from there
         plan.mixes.resize((size_t)mix->nmixes);
         plan.terms.resize((size_t)mix->nterms);
         for (int64_t q = 0; q < mix->nmixes; ++q)
@@ -327,7 +351,12 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
         if (J.frames_in < 1 || J.frames_in > (int64_t(1) << 40) / (esz * J.channels))
             return iss_fail(c, ISS_EINVAL, "%s: job %d: %lld frames", who, k, (long long)J.frames_in);
         const int64_t nbytes = J.frames_in * J.channels * esz;
-        if (J.src_offset < 0 || J.src_offset % esz != 0 || J.src_offset > src_bytes - nbytes)
+        if (set) {                                         // its members' bytes instead: chans = where each of its channels lies
+            std::string why;
+            chans.clear();
+            if (!set_channels(set->sets[k], set->members, set->nmembers, J.frames_in, J.channels, J.src_offset, esz, src_bytes, chans, why))
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: %s", who, k, why.c_str());
+        } else if (J.src_offset < 0 || J.src_offset % esz != 0 || J.src_offset > src_bytes - nbytes)
             return iss_fail(c, ISS_EINVAL, "%s: job %d: source bytes [%lld, %lld) outside the %lld-byte buffer or "
                             "not aligned to %lld", who, k, (long long)J.src_offset, (long long)(J.src_offset + nbytes),
                             (long long)src_bytes, (long long)esz);
@@ -427,8 +456,37 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
             split_geometry(f, ms.mix_count, tile, group, stride);
             span_b = group * stride * 8;
             groups = (ms.mix_count + group - 1) / group;
-            plan.dm[(size_t)k] = RsMixDev{ms.dst_stride, (nout + tile - 1) / tile, ms.mix_begin, ms.mix_count, (int32_t)group,
+            int32_t mix_begin = ms.mix_begin;
+            if (set) {                                     // the job's own rows: every term resolved to the member it reads
+                mix_begin = (int32_t)plan.mixes.size();
+                for (int32_t q = 0; q < ms.mix_count; ++q) {
+                    const iss_mix& m = mix->mixes[ms.mix_begin + q];
+                    const int64_t at = set_mixes + 2 * (int64_t)plan.sterms.size();
+                    if (at + 2 * (int64_t)m.term_count > 0x7fffffffLL)
+                        return iss_fail(c, ISS_EINVAL, "%s: job %d: too many term rows in one call", who, k);
+                    plan.mixes.push_back(RsMixRow{(int32_t)at, m.term_count, m.divisor});
+                    for (int32_t n = 0; n < m.term_count; ++n) {
+                        const iss_mix_term& t = mix->terms[m.term_begin + n];
+                        const SetChanDev& C = chans[(size_t)t.channel];
+                        plan.sterms.push_back(RsSetTermDev{C.off, C.frames, t.weight, C.step, 0});
+                    }
+                }
+            }
+            plan.dm[(size_t)k] = RsMixDev{ms.dst_stride, (nout + tile - 1) / tile, mix_begin, ms.mix_count, (int32_t)group,
                                           (int32_t)stride};
+        } else if (set) {
+            // the plain downmix of a set: the mix of all its channels in order, every weight 1, divisor = their count -- the
+            // plain call's sums and its one division (one channel: x * 1 / 1), in one output at dst_offset
+            const int64_t at = set_mixes + 2 * (int64_t)plan.sterms.size();
+            if (at + 2 * (int64_t)J.channels > 0x7fffffffLL)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: too many term rows in one call", who, k);
+            const int32_t mix_begin = (int32_t)plan.mixes.size();
+            plan.mixes.push_back(RsMixRow{(int32_t)at, J.channels, (double)J.channels});
+            for (const SetChanDev& C : chans) plan.sterms.push_back(RsSetTermDev{C.off, C.frames, 1.0, C.step, 0});
+            int64_t group, stride;
+            split_geometry(f, 1, tile, group, stride);
+            span_b = group * stride * 8;
+            plan.dm[(size_t)k] = RsMixDev{nout, (nout + tile - 1) / tile, mix_begin, 1, (int32_t)group, (int32_t)stride};
         } else {
             while (tile > RS_THREADS && span_frames(f, tile) * 8 > RS_SPAN_MAX) tile /= 2;
             span_b = span_frames(f, tile) * 8;
@@ -461,13 +519,14 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     int rc;
     if (mix) {                                         // one table: the jobs, (their windows,) their mix sets, the mix rows, the terms
         const size_t nj = dj.size() * sizeof(RsJobDev), nw = win ? dj.size() * sizeof(RsWinDev) : 0, nm = dj.size() * sizeof(RsMixDev);
-        const size_t nr = plan.mixes.size() * sizeof(RsMixRow), nt = plan.terms.size() * sizeof(RsTermDev);
+        const size_t nr = plan.mixes.size() * sizeof(RsMixRow);         // (a set call: its own term rows in the place of `terms`)
+        const size_t nt = plan.set ? plan.sterms.size() * sizeof(RsSetTermDev) : plan.terms.size() * sizeof(RsTermDev);
         std::vector<uint8_t> rows(nj + nw + nm + std::max<size_t>(nr + nt, 16));
         memcpy(rows.data(), dj.data(), nj);
         if (win) memcpy(rows.data() + nj, plan.dw.data(), nw);
         memcpy(rows.data() + nj + nw, plan.dm.data(), nm);
         if (nr) memcpy(rows.data() + nj + nw + nm, plan.mixes.data(), nr);
-        if (nt) memcpy(rows.data() + nj + nw + nm + nr, plan.terms.data(), nt);
+        if (nt) memcpy(rows.data() + nj + nw + nm + nr, plan.set ? (const void*)plan.sterms.data() : (const void*)plan.terms.data(), nt);
         rc = iss_upload_rows(c, c->rs_jobs, rows.data(), rows.size());
     } else if (split) {                                       // one table: the jobs, (their windows,) their splits, the channel selections
         const size_t nj = dj.size() * sizeof(RsJobDev), nw = win ? dj.size() * sizeof(RsWinDev) : 0, ns = dj.size() * sizeof(RsSplitDev);
@@ -488,7 +547,8 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     if (rc) return rc;
     bool ext = false;                                  // a format newer than the WAV five: the instantiation that reads them all
     for (const RsJobDev& d : dj) ext = ext || d.fmt > ISS_RS_F64;
-    auto kernel = mix ? (win ? (ext ? resample_kernel<true, true, false, true> : resample_kernel<false, true, false, true>)
+    auto kernel = plan.set ? (ext ? resample_kernel<true, false, false, true, true> : resample_kernel<false, false, false, true, true>)
+                  : mix ? (win ? (ext ? resample_kernel<true, true, false, true> : resample_kernel<false, true, false, true>)
                              : (ext ? resample_kernel<true, false, false, true> : resample_kernel<false, false, false, true>))
                   : split && win ? (ext ? resample_kernel<true, true, true> : resample_kernel<false, true, true>)
                   : split ? (ext ? resample_kernel<true, false, true> : resample_kernel<false, false, true>)
@@ -616,9 +676,11 @@ extern "C" int iss_resample_staged_mix(iss_ctx* c, int32_t origin, int64_t paylo
             J.src_offset = dec->stage_off[(size_t)q];
         } else {
             bool found = false;
-            for (const iss_survey_job& S : c->sv_held.jobs)
+            for (const iss_survey_job& S : c->sv_held.jobs) {
+                if (!c->sv_held.sets.empty()) break;       // (jobs of iss_survey_set: their rows describe no interleaved bytes)
                 found = found || (S.src_offset == J.src_offset && S.frames_in == J.frames_in && S.channels == J.channels &&
                                   S.format == J.format);
+            }
             if (!found)
                 return iss_fail(c, ISS_EINVAL, "%s: job %d: no job of the last iss_survey held %lld frames of %d channels in format "
                                 "%d at byte %lld", who, k, (long long)J.frames_in, J.channels, J.format, (long long)J.src_offset);
@@ -634,6 +696,79 @@ extern "C" int iss_resample_staged_mix(iss_ctx* c, int32_t origin, int64_t paylo
     if (rc || (rc = pass.commit(nullptr))) return rc;
     if (njobs == 0) return ISS_OK;
     return iss_resample_launch(c, (const uint8_t*)(dec ? dec->stage.p : c->sv_src.p), pass.plan);
+}
+
+// The body of the two set entry points (include/iss.h, "File sets"): the jobs planned over their members' bytes in `src_bytes` of
+// source, then the upload (src != NULL) and the launch over dev_src (NULL: the resampler's own source buffer, uploaded here)
+static int resample_set(iss_ctx* c, const char* who, const uint8_t* dev_src, const void* src, int64_t src_bytes,
+                        const iss_resample_job* jobs, int32_t njobs, int64_t n_signal, const IssSetTables& set, const IssMixTables& mix) {
+    IssDecodePass pass;
+    int rc = pass.begin(c, who, n_signal, 0);
+    pass.jmix = &mix; pass.jset = &set;
+    if (njobs > 0) pass.rmixsets.assign(mix.sets, mix.sets + njobs);
+    pass.rjobs.assign(jobs, jobs + njobs); pass.stage = src_bytes;
+    if (rc || (rc = pass.commit(nullptr))) return rc;
+    if (njobs == 0) return ISS_OK;
+    if (!dev_src) {
+        if ((rc = iss_upload_payload(c, c->rs_src, "resample", src, src_bytes, (size_t)std::max<int64_t>(src_bytes, 16)))) return rc;
+        dev_src = (const uint8_t*)c->rs_src.p;
+    }
+    return iss_resample_launch(c, dev_src, pass.plan);
+}
+
+extern "C" int iss_resample_pcm16_set(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
+                                      int64_t n_signal, const iss_set* sets, const iss_set_member* members, int64_t nmembers,
+                                      const iss_mixset* mixsets, const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms,
+                                      int64_t nterms) {
+    const char* who = "iss_resample_pcm16_set";
+    if (!c || njobs < 0 || (njobs > 0 && (!jobs || !sets || !mixsets)) || src_bytes < 0 || (!src && src_bytes > 0))
+        return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
+    const IssSetTables set{sets, members, nmembers};
+    const IssMixTables mix{mixsets, mixes, nmixes, terms, nterms};
+    return resample_set(c, who, nullptr, src, src_bytes, jobs, njobs, n_signal, set, mix);
+}
+
+// iss_resample_staged_mix for sets: every job is matched against a job of the iss_survey_set whose payload the survey's source
+// buffer holds -- frames, channels, format, and member row for member row --, then planned and launched over those bytes
+extern "C" int iss_resample_staged_set(iss_ctx* c, int32_t origin, int64_t payload, const iss_resample_job* jobs, int32_t njobs,
+                                       int64_t n_signal, const iss_set* sets, const iss_set_member* members, int64_t nmembers,
+                                       const iss_mixset* mixsets, const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms,
+                                       int64_t nterms) {
+    const char* who = "iss_resample_staged_set";
+    if (!c || origin != ISS_STAGED_SURVEY || njobs < 0 || (njobs > 0 && (!jobs || !sets || !mixsets)) || nmembers < 0 ||
+        (nmembers > 0 && !members))
+        return iss_fail(c, ISS_EINVAL, "%s: bad argument (the origin of a set is ISS_STAGED_SURVEY)", who);
+    const iss_ctx::Held& H = c->sv_held;
+    if (H.id == 0)
+        return iss_fail(c, ISS_ESTATE, "%s: origin survey holds no payload (no iss_survey_set went before)", who);
+    if (H.id != payload)
+        return iss_fail(c, ISS_ESTATE, "%s: origin survey: payload %lld has been replaced by a later call (it holds payload %lld)", who,
+                        (long long)payload, (long long)H.id);
+    for (int32_t k = 0; k < njobs; ++k) {
+        const iss_resample_job& J = jobs[k];
+        const iss_set& S = sets[k];
+        bool found = false;
+        if (S.member_count >= 1 && S.member_begin >= 0 && S.member_begin <= nmembers - S.member_count)
+            for (size_t q = 0; q < H.sets.size() && !found; ++q) {
+                const iss_survey_job& V = H.jobs[q];
+                const iss_set& T = H.sets[q];
+                if (V.frames_in != J.frames_in || V.channels != J.channels || V.format != J.format || T.member_count != S.member_count)
+                    continue;
+                found = true;
+                for (int32_t m = 0; m < S.member_count && found; ++m) {
+                    const iss_set_member& A = members[S.member_begin + m];
+                    const iss_set_member& B = H.members[(size_t)(T.member_begin + m)];
+                    found = A.src_offset == B.src_offset && A.frames == B.frames && A.channels == B.channels;
+                }
+            }
+        if (!found)
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: no job of the last iss_survey_set held these members: %lld frames of %d "
+                            "channels in format %d, %d member rows from %d on", who, k, (long long)J.frames_in, J.channels, J.format,
+                            S.member_count, S.member_begin);
+    }
+    const IssSetTables set{sets, members, nmembers};
+    const IssMixTables mix{mixsets, mixes, nmixes, terms, nterms};
+    return resample_set(c, who, (const uint8_t*)c->sv_src.p, nullptr, H.bytes, jobs, njobs, n_signal, set, mix);
 }
 
 // (tile, channels per group) the planner gives a job of `nsel` selected channels (or mixes) through filter `filter`

@@ -2,6 +2,7 @@
 // resample.hip (every resample_kernel instantiation) and survey.hip (survey_kernel).  Device code only; not part of the ABI.
 #pragma once
 #include "iss_internal.h"
+#include "survey_plan.h"     // SetChanDev: a row of the per-channel table of a survey job over a set
 
 namespace {
 
@@ -82,6 +83,55 @@ __device__ __forceinline__ void stage_channels(const uint8_t* __restrict__ src, 
         }
         if (in) v = L::get(p + j * ch + (sel ? sel[kk] : c0 + kk));
         span[(int64_t)kk * stride + k] = v;
+    }
+}
+
+// File sets (include/iss.h): a channel of a job is channel c_local of one MEMBER, which the host resolved once per job to where
+// its first sample lies (`off`, a byte offset into the source), the member's frames and its channels (`step`).  Sample j of the
+// channel is the stored one while the member lasts and 0.0 after it: the zero the interleaved twin stores there.
+// (the planner saw to it that every member's bytes lie inside the source and are aligned to the sample)
+template <typename L>
+__device__ __forceinline__ double set_sample(const uint8_t* __restrict__ src, int64_t off, int64_t frames, int step, int64_t j) {
+    using T = typename L::type;
+    return j < frames ? L::get(reinterpret_cast<const T*>(src + off) + j * step) : 0.0;
+}
+
+// stage_channels for a set (survey.hip), channels `chans[0, gc)`, frames s0 .. s0+len-1 (all inside the job: the survey's chunks
+// are), the same rows at the same places.  Channel-major: row after row, the threads striding over the frames of one -- a wave
+// reads consecutive frames of one member instead of one frame of 64 members, and the row of the channel table is the same for
+// the whole workgroup (scalar loads, no division per sample)
+template <typename L>
+__device__ __forceinline__ void stage_set_channels(const uint8_t* __restrict__ src, const SetChanDev* __restrict__ chans, int64_t s0,
+                                                   int len, double* __restrict__ span, int stride, int gc) {
+    for (int kk = 0; kk < gc; ++kk) {
+        const SetChanDev C = chans[kk];
+        double* row = span + (int64_t)kk * stride;
+        for (int k = threadIdx.x; k < len; k += RS_THREADS) row[k] = set_sample<L>(src, C.off, C.frames, C.step, s0 + k);
+    }
+}
+
+// stage_mixes for a set (resample.hip; whole sources only): frames s0 .. s0+len-1 of `gm` mixes, span[q * stride + .] = mix q of
+// `mixes`, its terms the RsSetTermDev rows of `rows`.  The arithmetic is stage_mixes', term for term: a frame outside the job is
+// 0, a frame past the end of a term's member is w * 0.0 in the sum.  Channel-major, as stage_set_channels: mix after mix
+template <typename L>
+__device__ __forceinline__ void stage_set_mixes(const uint8_t* __restrict__ src, int64_t n_in, int64_t s0, int len,
+                                                double* __restrict__ span, int stride, int gm, const RsMixRow* __restrict__ mixes,
+                                                const RsTermDev* __restrict__ rows) {
+    for (int q = 0; q < gm; ++q) {
+        const RsMixRow M = mixes[q];
+        const RsSetTermDev* t = reinterpret_cast<const RsSetTermDev*>(rows + M.term_begin);
+        double* row = span + (int64_t)q * stride;
+        for (int k = threadIdx.x; k < len; k += RS_THREADS) {
+            const int64_t j = s0 + k;
+            double v = 0.0;
+            if (j >= 0 && j < n_in) {
+                v = __dmul_rn(t[0].weight, set_sample<L>(src, t[0].off, t[0].frames, t[0].step, j));
+                for (int n = 1; n < M.term_count; ++n)
+                    v = __dadd_rn(v, __dmul_rn(t[n].weight, set_sample<L>(src, t[n].off, t[n].frames, t[n].step, j)));
+                v = __ddiv_rn(v, M.divisor);
+            }
+            row[k] = v;
+        }
     }
 }
 

@@ -42,7 +42,15 @@ __device__ __forceinline__ int wave_count(int v) {
     return v;
 }
 
-#define SV_STAGE(L) stage_channels<L, false>(s, J.n, ch, k0, len, span, stride, c0, gc, nullptr, W)
+// SET = false is the kernel every survey of interleaved frames launches.  SET = true (include/iss.h, "File sets") stages the same
+// rows through the per-channel table that follows the job rows, J.src_off being the job's first row of it: steps 2 to 4, and so
+// every figure, are the code below on the same LDS
+#define SV_STAGE(L)                                                                                             \
+    do {                                                                                                        \
+        if constexpr (SET) stage_set_channels<L>(src, chans + c0, k0, len, span, stride, gc);                   \
+        else stage_channels<L, false>(s, J.n, ch, k0, len, span, stride, c0, gc, nullptr, W);                   \
+    } while (0)
+template <bool SET>
 __global__ __launch_bounds__(SV_THREADS) void survey_kernel(const uint8_t* __restrict__ src, const SvJobDev* __restrict__ jobs,
                                                             int njobs, unsigned long long* __restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) double sv_smem[];
@@ -61,6 +69,8 @@ __global__ __launch_bounds__(SV_THREADS) void survey_kernel(const uint8_t* __res
     double* part = sv_smem;                                                 // [wave][SV_PART]: what each wave found for the group
     double* span = sv_smem + 4 * SV_PART;
     const uint8_t* s = src + J.src_off;
+    const SetChanDev* chans = nullptr;                                      // SET: the job's rows of the channel table
+    if constexpr (SET) chans = reinterpret_cast<const SetChanDev*>(jobs + njobs) + J.src_off;
     const RsWinDev W{};
     for (int c0 = 0; c0 < ch; c0 += SV_GROUP) {
         const int gc = min(SV_GROUP, ch - c0);
@@ -166,15 +176,17 @@ __global__ __launch_bounds__(SV_THREADS) void survey_reduce_kernel(const SvJobDe
     res[J.res_off + w] = is_count ? (unsigned long long)cnt : (unsigned long long)__double_as_longlong(acc);
 }
 
-// the body of the four entry points: the rows planned against `src_bytes` of uploaded bytes (dec == NULL) or against what `dec`
-// staged last; both launches; the result rows copied back before it returns
+// the body of the five entry points: the rows planned against `src_bytes` of uploaded bytes (dec == NULL) or against what `dec`
+// staged last; both launches; the result rows copied back before it returns.  `set`: the tables of iss_survey_set (else NULL)
 int survey_call(iss_ctx* c, const char* who, IssCodec* dec, const void* src, int64_t src_bytes, const iss_survey_job* jobs,
-                const iss_window* windows, int32_t njobs, void* results) {
-    if (!c || njobs < 0 || (njobs > 0 && (!jobs || !results)) || src_bytes < 0 || (!dec && !src && src_bytes > 0))
+                const iss_window* windows, int32_t njobs, void* results, const IssSetTables* set = nullptr) {
+    if (!c || njobs < 0 || (njobs > 0 && (!jobs || !results)) || src_bytes < 0 || (!dec && !src && src_bytes > 0) ||
+        (set && njobs > 0 && !set->sets) || (set && (set->nmembers < 0 || (set->nmembers > 0 && !set->members))))
         return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
     SvPlan plan;
     std::string err;
-    if (!sv_plan(jobs, windows, njobs, src_bytes, dec ? &dec->stage_off : nullptr, dec ? &dec->stage_bytes : nullptr, plan, err))
+    if (!sv_plan(jobs, windows, njobs, src_bytes, dec ? &dec->stage_off : nullptr, dec ? &dec->stage_bytes : nullptr, plan, err,
+                 set ? set->sets : nullptr, set ? set->members : nullptr, set ? set->nmembers : 0))
         return iss_fail(c, ISS_EINVAL, "%s: %s", who, err.c_str());
     if (njobs == 0) return ISS_OK;
     ISS_HIP(c, hipSetDevice(c->device));
@@ -186,12 +198,22 @@ int survey_call(iss_ctx* c, const char* who, IssCodec* dec, const void* src, int
     }
     if ((rc = iss_reserve(c, c->sv_ws, (size_t)plan.ws_words * 8))) return rc;
     if ((rc = iss_reserve(c, c->sv_res, (size_t)plan.res_words * 8))) return rc;
-    if ((rc = iss_upload_rows(c, c->sv_jobs, plan.dj.data(), plan.dj.size() * sizeof(SvJobDev)))) return rc;
+    if (set) {                                             // one table: the jobs, then the channels of every one of them
+        const size_t nj = plan.dj.size() * sizeof(SvJobDev), nc = plan.chans.size() * sizeof(SetChanDev);
+        std::vector<uint8_t> rows(nj + nc);
+        memcpy(rows.data(), plan.dj.data(), nj);
+        memcpy(rows.data() + nj, plan.chans.data(), nc);
+        rc = iss_upload_rows(c, c->sv_jobs, rows.data(), rows.size());
+    } else {
+        rc = iss_upload_rows(c, c->sv_jobs, plan.dj.data(), plan.dj.size() * sizeof(SvJobDev));
+    }
+    if (rc) return rc;
+    auto kernel = set ? survey_kernel<true> : survey_kernel<false>;
     if (plan.lds > 64 * 1024)
-        ISS_HIP(c, hipFuncSetAttribute((const void*)survey_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+        ISS_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
     iss_prof_begin(c, ISS_PROF_FRONTEND, 0.0);
     iss_prof_inst(c, "survey_kernel");
-    hipLaunchKernelGGL(survey_kernel, dim3((unsigned)plan.chunks), dim3(SV_THREADS), (size_t)plan.lds, c->stream, dev_src,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)plan.chunks), dim3(SV_THREADS), (size_t)plan.lds, c->stream, dev_src,
                        (const SvJobDev*)c->sv_jobs.p, (int)njobs, (unsigned long long*)c->sv_ws.p);
     ISS_HIP(c, hipGetLastError());
     iss_prof_end(c);
@@ -210,6 +232,12 @@ int survey_call(iss_ctx* c, const char* who, IssCodec* dec, const void* src, int
         c->sv_held.id = ++c->held_seq;
         c->sv_held.bytes = src_bytes;
         c->sv_held.jobs.assign(jobs, jobs + njobs);
+        c->sv_held.sets.clear();
+        c->sv_held.members.clear();
+        if (set) {
+            c->sv_held.sets.assign(set->sets, set->sets + njobs);
+            c->sv_held.members.assign(set->members, set->members + set->nmembers);
+        }
     }
     return ISS_OK;
 }
@@ -219,6 +247,12 @@ int survey_call(iss_ctx* c, const char* who, IssCodec* dec, const void* src, int
 extern "C" int iss_survey(iss_ctx* c, const void* src, int64_t src_bytes, const iss_survey_job* jobs, const iss_window* windows,
                           int32_t njobs, void* results) {
     return survey_call(c, "iss_survey", nullptr, src, src_bytes, jobs, windows, njobs, results);
+}
+
+extern "C" int iss_survey_set(iss_ctx* c, const void* src, int64_t src_bytes, const iss_survey_job* jobs, int32_t njobs,
+                              const iss_set* sets, const iss_set_member* members, int64_t nmembers, void* results) {
+    const IssSetTables set{sets, members, nmembers};
+    return survey_call(c, "iss_survey_set", nullptr, src, src_bytes, jobs, nullptr, njobs, results, &set);
 }
 
 extern "C" int iss_flac_survey(iss_ctx* c, const iss_survey_job* jobs, const iss_window* windows, int32_t njobs, void* results) {

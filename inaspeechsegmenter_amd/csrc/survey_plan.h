@@ -24,8 +24,15 @@ struct SvJobDev {
 };
 static_assert(sizeof(SvJobDev) == 56, "rows are copied to the device as they stand");
 
+// one channel of a job over a file set (include/iss.h, "File sets"): sample (j, this channel) lies at byte off + j * step * sample
+// bytes of the source while j < frames, and is 0.0 from there on.  The rows follow the job rows on the device, a set job's
+// src_off being the index of its first one
+struct SetChanDev { int64_t off, frames; int32_t step, pad; };
+static_assert(sizeof(SetChanDev) == 24 && sizeof(SvJobDev) % 8 == 0, "8-byte aligned behind the job rows");
+
 struct SvPlan {
     std::vector<SvJobDev> dj;
+    std::vector<SetChanDev> chans;                     // a set call: every job's channels, in job order
     int64_t chunks = 0, ws_words = 0, res_words = 0;
     int64_t lds = 0;                                   // bytes of dynamic LDS survey_kernel needs for these jobs
     int32_t max_row = 0;                               // the widest result row, in words
@@ -48,12 +55,51 @@ inline int64_t sv_lds_bytes(int ch) {
     return ((int64_t)4 * SV_PART + (int64_t)gc * sv_stride(gc)) * 8;
 }
 
+// The members of one job of a set call (its set row S, the call's member rows; the job states frames_in frames of `channels`
+// channels of esz-byte samples at src_offset 0 of a buffer of src_bytes) -> one SetChanDev per channel of the job appended to
+// `chans`, or false with `why` (the resample planner and sv_plan put the job in front of it) and `chans` as it was
+inline bool set_channels(const iss_set& S, const iss_set_member* members, int64_t nmembers, int64_t frames_in, int32_t channels,
+                         int64_t src_offset, int64_t esz, int64_t src_bytes, std::vector<SetChanDev>& chans, std::string& why) {
+    char text[224];
+    auto fail = [&](const char* fmt, long long a = 0, long long b = 0, long long c = 0, long long d = 0) {
+        snprintf(text, sizeof text, fmt, a, b, c, d);
+        why = text;
+        return false;
+    };
+    if (S.member_count < 1 || S.member_count > 1024 || S.member_begin < 0 || !members || S.member_begin > nmembers - S.member_count)
+        return fail("member rows [%lld, +%lld) empty, above 1024 or outside the %lld of the call", S.member_begin, S.member_count,
+                    nmembers);
+    if (src_offset != 0) return fail("src_offset %lld: a set job states 0, its members say where the bytes lie", src_offset);
+    int64_t nch = 0, longest = 0;
+    for (int32_t m = 0; m < S.member_count; ++m) {
+        const iss_set_member& M = members[S.member_begin + m];
+        if (M.channels < 1 || M.channels > 1024 || M.frames < 1 || M.frames > (int64_t(1) << 40) / (esz * M.channels))
+            return fail("member %lld: %lld frames of %lld channels", m, M.frames, M.channels);
+        const int64_t nbytes = M.frames * M.channels * esz;
+        if (M.src_offset < 0 || M.src_offset % esz != 0 || M.src_offset > src_bytes - nbytes)
+            return fail("member %lld: source bytes from %lld on (%lld of them) outside the %lld-byte buffer or misaligned", m,
+                        M.src_offset, nbytes, src_bytes);
+        nch += M.channels;
+        if (M.frames > longest) longest = M.frames;
+    }
+    if (nch != channels) return fail("the members hold %lld channels, the job row states %lld", nch, channels);
+    if (longest != frames_in) return fail("the longest member holds %lld frames, the job row states %lld", longest, frames_in);
+    for (int32_t m = 0; m < S.member_count; ++m) {
+        const iss_set_member& M = members[S.member_begin + m];
+        for (int32_t c = 0; c < M.channels; ++c) chans.push_back(SetChanDev{M.src_offset + c * esz, M.frames, M.channels, 0});
+    }
+    return true;
+}
+
+// `sets` (with `members`, nmembers; NULL: not a set call): a set row beside every job, whose channels are those of its members
+// (include/iss.h, "File sets"; never with `wins` or the codec vectors): plan.chans gets a row per channel of every job.
 // `stage_off` / `stage_bytes` NULL: the rows' src_offset are byte offsets into a buffer of src_bytes.  Else (the codec entries):
 // src_offset is an index into the two vectors, what a decode call staged per job (offset -1: not staged).
 // -> true, or false with `err` saying which job and why (plan is then not to be used)
 inline bool sv_plan(const iss_survey_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes,
                     const std::vector<int64_t>* stage_off, const std::vector<int64_t>* stage_bytes, SvPlan& plan,
-                    std::string& err) {
+                    std::string& err, const iss_set* sets = nullptr, const iss_set_member* members = nullptr,
+                    int64_t nmembers = 0) {
     char text[256];
     auto fail = [&](int k, const char* why, long long a = 0, long long b = 0, long long c = 0) {
         char body[192];
@@ -75,7 +121,16 @@ inline bool sv_plan(const iss_survey_job* jobs, const iss_window* wins, int32_t 
         if (J.frames_in < 1 || J.frames_in > (int64_t(1) << 40) / (esz * J.channels)) return fail(k, "%lld frames", J.frames_in);
         const int64_t nbytes = J.frames_in * J.channels * esz;
         int64_t off = J.src_offset;
-        if (stage_off) {
+        if (sets) {
+            std::string why;
+            if (wins || stage_off) return fail(k, "a set call takes no windows and no decoder's staging");
+            off = (int64_t)plan.chans.size();              // the job's rows of the channel table
+            if (!set_channels(sets[k], members, nmembers, J.frames_in, J.channels, J.src_offset, esz, src_bytes, plan.chans, why)) {
+                snprintf(text, sizeof text, "job %d: %s", k, why.c_str());
+                err = text;
+                return false;
+            }
+        } else if (stage_off) {
             if (off < 0 || off >= (int64_t)stage_off->size() || (*stage_off)[(size_t)off] < 0)
                 return fail(k, "job %lld of the last decode call did not go to the staging buffer", off);
             if ((*stage_bytes)[(size_t)off] != nbytes)

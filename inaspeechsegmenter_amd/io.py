@@ -26,6 +26,9 @@ host-only twins.
 stored frames, measured on the device (Segmenter.survey_channels) --, `survey_channels` is its host-only twin.
 `auto_source` reads a file for channels='auto': a source that is staged once, surveyed and then downmixed by the mix its survey
 suggests (survey.ChannelSurvey.safe_mix); `decode_auto` is the host-only twin.
+`FileSet` is a recording stored as one file per channel or group of channels, read as the interleaved file it stands for: every
+whole-file read above takes one (or a tuple or list of member paths) where it takes `medianame`, `set_source` is what the plain
+read gives, `decode_set` the host-only twin -- the interleaved, zero-padded stored samples, which no other call ever builds.
 """
 import os
 import struct
@@ -86,6 +89,161 @@ def _read_file(medianame):
         return f.read()
 
 
+# ---------------------------------------------------------------------------------------------- file sets
+MAX_SET_CHANNELS = 1024
+
+
+class FileSet:
+    """An ordered list of member files that reads as ONE multichannel source (an extension, ffmpeg=None only): a call logger's
+    one mono file per direction, a production system's one mono WAV per track.  It reads exactly like its interleaved twin --
+    the one file holding the members' channels side by side (member 0's first), as many frames as the longest member, a shorter
+    member continued with samples of value 0.0 --, which is never written: the device reads the members where they lie.
+    Members share the sample rate and the stored sample format; they may differ in container and in channel count.  Wherever a
+    call takes `medianame`, a tuple or list of paths means FileSet(paths).  `name` is what error texts and `decisions` carry."""
+    __slots__ = ('members', 'name')
+
+    def __init__(self, members, name=None):
+        if isinstance(members, (str, bytes)) or isinstance(members, FileSet):
+            raise ValueError(f'FileSet({members!r}): members must be a sequence of paths')
+        self.members = tuple(os.fspath(m) for m in members)
+        if name is None:
+            name = f'set({self.members[0]}, +{len(self.members) - 1})' if self.members else 'set()'
+        self.name = str(name)
+
+    def __len__(self):
+        return len(self.members)
+
+    def __iter__(self):
+        return iter(self.members)
+
+    def __str__(self):
+        return self.name
+
+    def __repr__(self):
+        return f'FileSet({list(self.members)!r}, name={self.name!r})'
+
+    def __eq__(self, other):
+        return isinstance(other, FileSet) and (self.members, self.name) == (other.members, other.name)
+
+    def __hash__(self):
+        return hash((self.members, self.name))
+
+
+def as_media(medianame):
+    """`medianame` as the reads below take it: a path as given; a FileSet, tuple or list of one member that member's path (a
+    one-member set is that file); any other tuple or list FileSet(medianame)."""
+    if isinstance(medianame, (tuple, list)):
+        medianame = FileSet(medianame)
+    if isinstance(medianame, FileSet) and len(medianame) == 1:
+        return medianame.members[0]
+    return medianame
+
+
+def _no_set_ranges(medianame, what='time ranges'):
+    if isinstance(as_media(medianame), FileSet):
+        raise ValueError(f'{as_media(medianame)}: {what} of a set are not supported; read the whole set, or cut the members '
+                         f'beforehand')
+
+
+class _SetSound:
+    """A parsed file set, answering what a sndfmt.Sound answers to the reads below: `sr`, `ch` (all members'), `n` (the longest
+    member's frames), `kind`, `stored()` (the interleaved twin's samples, io.decode_set), and the sources the device reads."""
+    __slots__ = ('name', 'sr', 'ch', 'n', 'kind', 'parts', 'fmt', 'full')
+
+    def __init__(self, fs):
+        from . import flac, sndfmt
+        name = self.name = fs.name
+        if len(fs) == 0:
+            raise ValueError(f'{name}: the set is empty')
+        self.parts = []
+        for m in fs.members:
+            _check_local(m)
+            h, full = _survey_parsed(m, False)
+            label = 'FLAC' if isinstance(h, flac.FlacStream) else sndfmt._BLOCK[h.kind].label if h.kind in sndfmt._BLOCK else None
+            if label is not None:
+                raise ValueError(f'{name}: member {m}: {label} is not supported in a file set')
+            if h.n < 1:
+                raise ValueError(f'{name}: member {m} has no frames')
+            self.parts.append((m, h, full) + h.raw()[::-1])      # (..., its ISS_RS_* format, its samples as stored)
+        m0, h0, self.full, self.fmt, _ = self.parts[0]
+        for m, h, full, fmt, _ in self.parts[1:]:
+            if h.sr != h0.sr:
+                raise ValueError(f'{name}: the members differ in sample rate: {m0} is sampled at {h0.sr} Hz, {m} at {h.sr} Hz')
+            if (fmt, full) != (self.fmt, self.full):
+                raise ValueError(f'{name}: the members differ in stored sample format: {m0} holds {_kind_text(h0, self.full)} samples, '
+                                 f'{m} holds {_kind_text(h, full)}')
+        self.sr, self.kind = h0.sr, h0.kind
+        self.ch = sum(p[1].ch for p in self.parts)
+        self.n = max(p[1].n for p in self.parts)
+        if self.ch > MAX_SET_CHANNELS:
+            raise ValueError(f'{name}: {self.ch} channels in all, a set holds at most {MAX_SET_CHANNELS}')
+
+    def _xs(self):
+        return [p[4] for p in self.parts]
+
+    def stored(self):
+        """The samples io._parse_wav would return for the interleaved twin: (n, ch), a shorter member continued with the stored
+        value of 0.0 (128 for unsigned bytes, else 0)."""
+        cols = [p[1].stored() for p in self.parts]
+        out = np.full((self.n, self.ch), 128 if cols[0].dtype == np.uint8 else 0, dtype=cols[0].dtype)
+        c = 0
+        for a in cols:
+            a = a.reshape(a.shape[0], -1)
+            out[:a.shape[0], c:c + a.shape[1]] = a
+            c += a.shape[1]
+        return out
+
+    def source(self, resample=False):
+        from .sources import SetSource
+        if not resample:
+            need_16k_mono(self.name, self.sr, self.ch)
+        R.check_rate(self.sr)
+        return SetSource(self._xs(), self.sr, self.fmt, None, self.name)
+
+    def split_source(self, sel):
+        from .sources import SetSource
+        return SetSource(self._xs(), self.sr, self.fmt, sel, self.name)
+
+    def auto_source(self, full):
+        from .sources import SetAuto
+        return SetAuto(self._xs(), self.sr, self.fmt, full, self.name)
+
+    def survey_source(self, full):
+        from .sources import SetSurvey
+        return SetSurvey(self._xs(), self.sr, self.fmt, full, self.name)
+
+
+def _kind_text(h, full):
+    """A member's stored sample format for a refusal (24-bit PCM of a plain WAV file is parsed as the int32 it is widened to)."""
+    kind = 'i24' if h.kind == 'i32' and full == R.SURVEY_FULL['i24'] else h.kind
+    return f'{"big-endian " if h.big and kind not in ("u8", "i8", "ulaw", "alaw") else ""}{kind}'
+
+
+def decode_set(members):
+    """Host-only twin of a file set -> (the interleaved, zero-padded stored samples (n, C), sr): what decode_source would return
+    for the set's interleaved twin.  They go straight into resample.resample_ref, mix_ref and survey_ref.  ValueError as the
+    device read raises it: an empty set, members that differ in rate or stored format, a coded or empty member, more than 1024
+    channels."""
+    fs = members if isinstance(members, FileSet) else FileSet(members)
+    if len(fs) == 1:
+        x, sr = decode_source(fs.members[0])
+        return x.reshape(x.shape[0], -1), sr
+    h = _SetSound(fs)
+    return h.stored(), h.sr
+
+
+def set_source(members, resample=False):
+    """What Segmenter reads for a file set: a sources.SetSource (the members' bytes as stored; the device downmixes the set as
+    its interleaved twin would be), or for a one-member set what the file's own read gives.  Without `resample` a set is refused
+    as its twin would be (need_16k_mono: the rate first, then the channel count)."""
+    fs = as_media(members if isinstance(members, FileSet) else FileSet(members))
+    if not isinstance(fs, FileSet):
+        buf = _read_file(fs)
+        what = _classify(buf, fs)
+        return what.source(resample) if what is not None else source_of(*_parse_wav(buf, fs), fs, resample)
+    return _SetSound(fs).source(resample)
+
+
 def _read_range(path, offset, size):
     """`size` bytes of the file at `path` from byte `offset` (fewer at its end).  Every read of the excerpt path (`excerpts`)
     goes through here, so what an excerpt costs in disk reads can be counted."""
@@ -144,6 +302,10 @@ def _check_no_ffmpeg(medianame, start_sec, stop_sec):
             f'start_sec={start_sec} and stop_sec={stop_sec} cannot be set '
             f' when running inaSpeechSegmenter without ffmpeg. Please cut '
             f'down your audio files beforehand or use ffmpeg.')
+    if isinstance(medianame, FileSet):
+        for m in medianame.members:
+            _check_no_ffmpeg(m, None, None)
+        return
     if medianame.startswith('http://') or medianame.startswith('https://'):
         raise NotImplementedError(
             f'Without ffmpeg you cannot process media content on http '
@@ -179,6 +341,10 @@ def source_of(x, sr, name, resample=False):
 def decode_pcm(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg'):
     """16 kHz mono samples for the device: int16 when the source is PCM16 (always, through
     ffmpeg), else float32 holding exactly what soundfile's float32 read would return."""
+    medianame = as_media(medianame)
+    if isinstance(medianame, FileSet) and ffmpeg is not None:
+        raise ValueError(f'{medianame}: file sets are read without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={ffmpeg!r} reads one '
+                         f'file per run')
     if ffmpeg is None:
         _check_no_ffmpeg(medianame, start_sec, stop_sec)
         a, sr = decode_source(medianame)
@@ -192,7 +358,10 @@ def decode_pcm(medianame, start_sec=None, stop_sec=None, ffmpeg='ffmpeg'):
 
 def decode_source(medianame):
     """ffmpeg-free read of a WAV, FLAC or sndfmt.py file: -> (samples as stored, (n,) or (n, C), sr).  Nothing is converted:
-    the device downmixes, resamples and quantises (inaspeechsegmenter_amd/resample.py)."""
+    the device downmixes, resamples and quantises (inaspeechsegmenter_amd/resample.py).  A file set: decode_set."""
+    medianame = as_media(medianame)
+    if isinstance(medianame, FileSet):
+        return decode_set(medianame)
     buf = _read_file(medianame)
     return _stored(_classify(buf, medianame), buf, medianame)
 
@@ -227,6 +396,10 @@ def channel_name(dst, k):
 
 
 def _check_local(medianame):
+    if isinstance(medianame, FileSet):
+        for m in medianame.members:
+            _check_local(m)
+        return
     if medianame.startswith('http://') or medianame.startswith('https://'):
         raise ValueError(f'{medianame}: the channels of media on http servers cannot be read; download the file beforehand')
 
@@ -235,8 +408,17 @@ def split_source(medianame, channels=None, resample=False):
     """-> (sel, sig): the selection as a list, and what Segmenter reads for it.  A file of two or more channels gives a source
     of sources.py carrying the selection (RawSource, flac.FlacSource, sndfmt.AdpcmSource: one signal per selected channel, the
     16 kHz twin of that channel alone); a one-channel file gives what the whole-file read gives (sel is then all zeros).
-    Without `resample` a rate other than 16 kHz is refused as the whole-file read refuses it; the channel count is not."""
+    Without `resample` a rate other than 16 kHz is refused as the whole-file read refuses it; the channel count is not.
+    A file set gives a sources.SetSource carrying the selection, channels counted across its members."""
+    medianame = as_media(medianame)
     _check_local(medianame)
+    if isinstance(medianame, FileSet):
+        what = _SetSound(medianame)
+        sel = channel_selection(what.name, channels, what.ch)
+        if not resample:
+            need_16k(what.name, what.sr)
+        R.check_rate(what.sr)
+        return sel, what.split_source(sel)
     buf = _read_file(medianame)
     what = _classify(buf, medianame)
     if what is None:
@@ -258,6 +440,7 @@ def decode_channels(medianame, channels=None, resample=True):
     two or more channels (stored, sr = decode_source(medianame)), [decode_pcm(medianame, ffmpeg=None)] per selected entry for a
     one-channel file.  channels: None (all, ascending) or 0-based indices in the order given.  resample=False refuses a rate
     other than 16 kHz as Segmenter(resample=False) does."""
+    medianame = as_media(medianame)
     _check_local(medianame)
     x, sr = decode_source(medianame)
     nch = 1 if x.ndim == 1 else x.shape[1]
@@ -285,11 +468,15 @@ def mix_source(medianame, mixes, resample=False):
     selection is that list (RawSource, flac.FlacSource, sndfmt.AdpcmSource and its Microsoft twin), one signal per mix,
     resample.mix_ref(stored, sr, mix) of the file's host decode.  A one-channel file is no exception (its mixes name channel 0),
     and the output is PCM16 also where the whole-file read takes the float path.  Without `resample` a rate other than 16 kHz
-    is refused as the whole-file read refuses it."""
+    is refused as the whole-file read refuses it.  A file set gives a sources.SetSource whose selection is the list."""
+    medianame = as_media(medianame)
     _check_local(medianame)
     R.normalise_mixes(mixes, None, medianame)                    # (what can be refused before the file is read)
-    buf = _read_file(medianame)
-    what = _classify(buf, medianame)
+    if isinstance(medianame, FileSet):
+        what, x = _SetSound(medianame), None
+    else:
+        buf = _read_file(medianame)
+        what = _classify(buf, medianame)
     if what is None:
         x, sr = _parse_wav(buf, medianame)
         nch = 1 if x.ndim == 1 else x.shape[1]
@@ -305,6 +492,7 @@ def mix_source(medianame, mixes, resample=False):
 def decode_mixes(medianame, mixes, resample=True):
     """Host-only twin of Segmenter.load_pcm_mixes: [resample.mix_ref(stored, sr, mix) for mix in mixes], stored and sr from
     decode_source(medianame).  resample=False refuses a rate other than 16 kHz as Segmenter(resample=False) does."""
+    medianame = as_media(medianame)
     _check_local(medianame)
     R.normalise_mixes(mixes, None, medianame)
     x, sr = decode_source(medianame)
@@ -389,6 +577,8 @@ def excerpts(medianame, ranges, resample=False):
     Ranges are validated before any sample is read where the header allows it; without `resample` a file that is not 16 kHz
     mono is refused as the whole-file read refuses it (need_16k_mono: the rate first)."""
     from . import flac, sndfmt
+    _no_set_ranges(medianame)
+    medianame = as_media(medianame)
     ranges = [tuple(r) for r in ranges]
     for start, stop in ranges:
         _check_range(medianame, start, stop)
@@ -448,6 +638,8 @@ def _selected_excerpts(medianame, ranges, select, resample, mono_plain):
     one-channel file gives what `excerpts` gives."""
     from . import flac, sndfmt
     from .sources import RawExcerpt
+    _no_set_ranges(medianame)
+    medianame = as_media(medianame)
     ranges = [tuple(r) for r in ranges]
     for start, stop in ranges:
         _check_range(medianame, start, stop)
@@ -542,9 +734,13 @@ def _wav_bits(buf):
 def _survey_parsed(medianame, header_ok):
     """-> (h, full): the file parsed for a survey -- a flac.FlacStream, a sndfmt.Sound, or with header_ok the
     sndfmt.SoundHeader of a plain RIFF/WAVE file, whose samples are then read by byte ranges -- and the fullscale threshold of
-    its stored format (resample.SURVEY_FULL)."""
+    its stored format (resample.SURVEY_FULL).  A file set: its _SetSound, and the threshold its members share."""
     from . import flac, sndfmt
+    medianame = as_media(medianame)
     _check_local(medianame)
+    if isinstance(medianame, FileSet):
+        h = _SetSound(medianame)
+        return h, h.full
     h = sndfmt.read_header(medianame) if header_ok else None
     if h is None:
         buf = _read_file(medianame)
@@ -570,6 +766,7 @@ def survey_channels(medianame, ranges=None):
     frames [a, b) by survey_bounds.  ValueError for a range that holds no frame."""
     from .survey import ChannelSurvey
     if ranges is not None:
+        _no_set_ranges(medianame, 'ranges')
         ranges = [tuple(r) for r in ranges]
         for start, stop in ranges:
             _check_range(medianame, start, stop)
@@ -583,6 +780,7 @@ def survey_channels(medianame, ranges=None):
 # ---------------------------------------------------------------------------------------------- survey-guided downmix (channels='auto')
 def _auto_parsed(medianame):
     """-> (the file parsed as a survey parses it, its fullscale threshold, is it one of two or more channels with frames?)."""
+    medianame = as_media(medianame)
     _check_no_ffmpeg(medianame, None, None)
     h, full = _survey_parsed(medianame, False)
     return h, full, h.ch > 1 and h.n > 0
@@ -596,7 +794,8 @@ def auto_source(medianame, resample=False):
     surveyed on the device, told its mix -- survey.ChannelSurvey.safe_mix() of that survey, None being the plain downmix --
     and resampled from the staged bytes (sources.RawAuto, flac.FlacAuto, sndfmt.AdpcmAuto and its Microsoft twin): `parts` 1,
     `size` the downmix's length, `decision` = (survey, mix) once launched.  Without `resample` a rate other than 16 kHz is
-    refused as load_pcm_mixes refuses it."""
+    refused as load_pcm_mixes refuses it.  A file set gives a sources.SetAuto, the same two steps over its members' bytes."""
+    medianame = as_media(medianame)
     h, full, multi = _auto_parsed(medianame)
     if h.n == 0:
         return h.source(resample)
@@ -611,6 +810,7 @@ def decode_auto(medianame, resample=True):
     """Host-only twin of Segmenter.load_pcm_auto -> (pcm, survey, mix): survey = survey_channels(medianame) and mix =
     survey.safe_mix() for a file of two or more channels (None, None for one channel); pcm = decode_mixes(medianame, [mix])[0],
     or for mix None the plain decode: resample.resample_ref of the stored samples (decode_pcm's array for a 16 kHz mono file)."""
+    medianame = as_media(medianame)
     h, full, multi = _auto_parsed(medianame)
     x = h.stored()
     if not multi:
@@ -635,6 +835,7 @@ def survey_sources(medianame, ranges=None):
     from . import flac, sndfmt
     from .sources import RawSurvey
     if ranges is not None:
+        _no_set_ranges(medianame, 'ranges')
         ranges = [tuple(r) for r in ranges]
         for start, stop in ranges:
             _check_range(medianame, start, stop)
@@ -644,7 +845,9 @@ def survey_sources(medianame, ranges=None):
         if b == a:
             out.append((R.survey_ref(np.zeros((0, h.ch)), full), a))
             continue
-        if isinstance(h, flac.FlacStream):
+        if isinstance(h, _SetSound):
+            src = h.survey_source(full)
+        elif isinstance(h, flac.FlacStream):
             src = flac.FlacExcerpt(h, 'stage', a, b)
         elif h.kind in sndfmt._BLOCK:
             src = sndfmt.block_excerpt(h, 'stage', a, b)

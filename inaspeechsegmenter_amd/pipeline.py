@@ -67,7 +67,13 @@ def _parts(sig):
     return sig.parts if isinstance(sig, sources.Source) else 1
 
 
-_held = sources.held                                 # what a decoded signal holds while it waits, for the audio budget
+def _name(src):
+    """What `decided` carries for an input: a path as given, a file set (io.FileSet, a tuple or list of paths) by its name."""
+    from . import io
+    return src if isinstance(src, str) else str(io.as_media(src))
+
+
+_held = sources.held                                # what a decoded signal holds while it waits, for the audio budget
 
 
 class _AudioBudget:
@@ -110,6 +116,8 @@ def _decode_stage(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None, 
                 except:                                            # noqa: E722  (reference semantics, segmenter.py:364-370)
                     itry += 1
                     err = 'error: ' + str(sys.exc_info()[0])
+                    if not isinstance(src, str):                   # a file set (io.FileSet, a tuple or list): which member, and why
+                        err += ' ' + str(sys.exc_info()[1])
                     if itry != nbtry:
                         time.sleep(random.random() * trydelay)
             if budget is not None and sig is not None:
@@ -389,7 +397,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                         res = (None, 'error: %s %s' % (type(exc), exc))
                     with lock:
                         if decided is not None and res[0] is not None:
-                            decided((src,) + (getattr(sig, 'decision', None) or (None, None)))
+                            decided((_name(src),) + (getattr(sig, 'decision', None) or (None, None)))
                         on_result(i, src, res[0], res[1], time.time() - t0)
                     continue
                 b = job[1]
@@ -405,7 +413,7 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
                             continue
                         mine = [[(lab, a * .02, c * .02) for lab, a, c in lseg] for lseg in mine]
                         if decided is not None:
-                            decided((src,) + (getattr(sig, 'decision', None) or (None, None)))
+                            decided((_name(src),) + (getattr(sig, 'decision', None) or (None, None)))
                         on_result(i, src, mine if multi else mine[0], None, share)
             except BaseException as exc:                           # noqa: B902  propagate to the caller's thread
                 failure.append(exc)

@@ -322,7 +322,19 @@ def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False, channel
     rate or with several channels a RawSource with `resample` and decode_pcm's refusal without it (io.source_of).
     channels='split' (ffmpeg=None): every channel on its own -- io.split_source's source with all channels selected;
     channels = a list of resample.Mix: those mixes, each on its own -- io.mix_source's source.
-    channels='auto' (ffmpeg=None): io.auto_source's source -- one signal, the downmix the file's own survey suggests."""
+    channels='auto' (ffmpeg=None): io.auto_source's source -- one signal, the downmix the file's own survey suggests.
+    A file set (io.FileSet, or a tuple or list of member paths; ffmpeg=None) is read by the same calls: io.set_source's source
+    without `channels`.  Whole sets only."""
+    medianame = iss_io.as_media(medianame)
+    if isinstance(medianame, iss_io.FileSet):
+        if ffmpeg is not None:
+            raise ValueError(f'{medianame}: file sets are read without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={ffmpeg!r} reads '
+                             f'one file per run')
+        if start_sec is not None or stop_sec is not None:
+            iss_io._no_set_ranges(medianame)
+        if channels is None:
+            iss_io._check_no_ffmpeg(medianame, None, None)
+            return iss_io.set_source(medianame, resample)
     if channels is not None:
         if channels == 'auto':
             return iss_io.auto_source(medianame, resample)
@@ -918,7 +930,11 @@ class Segmenter:
         from one upload and one decode, all files of a pass and a class in one survey launch and one resample launch.  Outputs,
         names, skipifexist, lmsg and the return value are the default call's: one output per file, at dst; a healthy or
         one-channel file writes what the default call writes.  decisions: a list that receives (src, survey, mix) per processed
-        file, in completion order (survey and mix None for a one-channel file)."""
+        file, in completion order (survey and mix None for a one-channel file).
+        File sets (an extension, ffmpeg=None only): an entry of linput may be an io.FileSet, or a tuple or list of member paths
+        -- a recording stored as one file per channel or group of channels.  It is read as its interleaved twin would be, by
+        every mode above, the sets of a pass in one launch of their own; its messages and `decisions` carry the set's name, and
+        a set that cannot be read (a coded member, members of different rates or formats) is a code-2 entry naming the member."""
         from . import pipeline
         if channels not in (None, 'split', 'auto'):
             raise ValueError(f"channels={channels!r}: None, 'split' or 'auto'")

@@ -50,6 +50,13 @@ length, so a pass is laid out before any survey is known; its class is `two_step
 its `decision` = (survey.ChannelSurvey, its safe_mix()), ONE resample launch over the staged bytes -- files with a mix and files
 with the plain downmix in the same launch.  A file whose decode status is not clean decides nothing and writes nothing.
 
+A file set (io.FileSet: one file per channel or group of channels; io.set_source and the calls above given a tuple or list of
+paths) is a source of three classes of its own -- `SetSource`, `SetSurvey`, `SetAuto` (two_step) --, which stand to the
+interleaved twin of the set as RawSource, RawSurvey and RawAuto stand to a file: the same rows, selections, mixes and decisions,
+channels counted across the members.  Their payload is the members' bytes end to end (`stage_into` writes them into the staged
+buffer piece by piece: nothing is interleaved or joined on the host), their class's `tables` the member rows, and their launches
+the *_set entry points, whose kernels read every channel where its member lies.  Whole sets only: no window row.
+
 `Group` is the only place that stages payloads, numbers job rows, launches and hands the status back; `pass_order` places a
 class's launch among the device calls of a pass.  pipeline._Worker.run, Segmenter.load_pcm_excerpts and Source.place (one file
 alone: segmenter._place) are written against this and nothing else: a new format is one class, and one line in io._classify.
@@ -115,6 +122,15 @@ class Source:
     def check(self, status):
         pass
 
+    @property
+    def payload_size(self):
+        """Bytes of `payload`; `stage_into(dst)` writes them to dst[:payload_size] (a source whose payload lies in several
+        pieces -- SetSource -- writes them there without joining them first)."""
+        return self.payload.size
+
+    def stage_into(self, dst):
+        dst[:] = self.payload
+
     @staticmethod
     def tables(group):
         return None
@@ -139,15 +155,15 @@ class Group:
             (only, _), = placed
             self.staged = only.payload
         else:
-            nbytes = sum(-(-s.payload.size // 16) * 16 for s, _ in placed)
+            nbytes = sum(-(-s.payload_size // 16) * 16 for s, _ in placed)
             self.staged = np.zeros(nbytes, dtype=np.uint8) if into is None else into(nbytes)[:nbytes]
         bpos = ubeg = 0
         for s, dst in placed:
-            p = s.payload
+            size = s.payload_size
             if not in_place:
-                self.staged[bpos:bpos + p.size] = p
+                s.stage_into(self.staged[bpos:bpos + size])
             self.jobs.append(s.job(ctx, bpos, ubeg, dst))
-            bpos += -(-p.size // 16) * 16
+            bpos += -(-size // 16) * 16
             ubeg += s.units
         self.tables = cls.tables([s for s, _ in placed])
 
@@ -294,6 +310,109 @@ class RawSurvey(RawSource):
     @staticmethod
     def survey(ctx, staged, jobs, tables, srcs):
         return None, ctx.survey(staged, [j.row for j in jobs], [j.window for j in jobs])
+
+
+class SetSource(RawSource):
+    """A file set (io.FileSet: one file per channel or per group of channels) as stored, for the SET instantiations of the
+    resample kernel: `xs` = the members' stored samples, each (n_m,) or (n_m, ch_m), all of the ISS_RS_* format `fmt` at `sr` Hz.
+    It reads like the set's interleaved twin -- the members' channels side by side, a shorter member continued with zeros --,
+    which is never built: `payload` is the members' bytes end to end, each on a 16-byte boundary, and `members` says where.
+    `sel` as for a RawSource, channels counted across the members; sets of a pass share one launch, as a class of their own."""
+    __slots__ = ('xs', 'name', 'frames', 'nch', '_payload')
+
+    def __init__(self, xs, sr, fmt, sel=None, name='<set>'):
+        self.xs, self.sr, self.fmt, self.name = [np.ascontiguousarray(x) for x in xs], sr, int(fmt), name
+        self.sel = selection(sel)
+        self.frames = max(x.shape[0] for x in self.xs)
+        self.nch = sum(1 if x.ndim == 1 else x.shape[1] for x in self.xs)
+        self.size = resample.out_len(self.frames, sr)
+        self._payload = None
+
+    @property
+    def held(self):
+        return max(self.size * self.parts, sum(x.nbytes for x in self.xs) // 2)
+
+    @property
+    def members(self):
+        """[(byte offset in `payload`, frames, channels) per member]."""
+        out, pos = [], 0
+        for x in self.xs:
+            out.append((pos, x.shape[0], 1 if x.ndim == 1 else x.shape[1]))
+            pos += -(-x.nbytes // 16) * 16
+        return out
+
+    @property
+    def payload(self):
+        if self._payload is None:
+            if len(self.xs) == 1:
+                self._payload = self.xs[0].reshape(-1).view(np.uint8)
+            else:
+                self._payload = np.zeros(self.payload_size, dtype=np.uint8)
+                self.stage_into(self._payload)
+        return self._payload
+
+    @property
+    def payload_size(self):
+        return sum(-(-x.nbytes // 16) * 16 for x in self.xs[:-1]) + self.xs[-1].nbytes
+
+    def stage_into(self, dst):
+        for x, (pos, _, _) in zip(self.xs, self.members):
+            dst[pos:pos + x.nbytes] = x.reshape(-1).view(np.uint8)
+
+    def row(self, ctx, src_offset, unit_begin, dst_offset):
+        """Its RS_JOB row, the twin's: src_offset is where its payload lies (the launch hands it on to the member rows)."""
+        fid, _, _ = ctx.resample_filter(self.sr)
+        return (src_offset, self.frames, self.nch, self.fmt, fid, 0, dst_offset, self.size)
+
+    @staticmethod
+    def tables(group):
+        return [s.members for s in group]
+
+    @staticmethod
+    def launch(ctx, staged, rows, tables, n_signal=-1, mixes=None, splits=None):
+        ctx.resample_set(staged, rows, tables, n_signal, mixes if splits is None else splits)      # (a split: one-term mixes)
+
+
+class SetSurvey(SetSource):
+    """A file set for the survey kernel's SET instantiation (io.survey_sources): the whole set, against the fullscale threshold
+    `full`.  Its job row is a SURVEY_JOB row, the twin's."""
+    __slots__ = ('full',)
+
+    def __init__(self, xs, sr, fmt, full, name='<set>'):
+        SetSource.__init__(self, xs, sr, fmt, None, name)
+        self.full = float(full)
+        self.size = -(-self.frames * resample.SR_OUT // sr)
+
+    def row(self, ctx, src_offset, unit_begin, dst_offset):
+        return (src_offset, self.frames, self.nch, self.fmt, self.full)
+
+    @staticmethod
+    def survey(ctx, staged, jobs, tables, srcs):
+        return None, ctx.survey_set(staged, [j.row for j in jobs], tables)
+
+
+class SetAuto(AutoSource, SetSource):
+    """A file set for channels='auto': RawAuto for sets -- surveyed by iss_survey_set, then downmixed by the mix its survey
+    suggests, or plainly, from the survey's upload (iss_resample_staged_set)."""
+    __slots__ = ('full', 'decision')
+
+    def __init__(self, xs, sr, fmt, full=1.0, name='<set>'):
+        SetSource.__init__(self, xs, sr, fmt, None, name)
+        self.full, self.decision = float(full), None
+
+    def row(self, ctx, src_offset, unit_begin, dst_offset):
+        """Its SURVEY_JOB row (the first step); `staged_row` is the RS_JOB row over the same bytes."""
+        return (src_offset, self.frames, self.nch, self.fmt, self.full)
+
+    def staged_row(self, ctx, src_offset, dst_offset):
+        return SetSource.row(self, ctx, src_offset, 0, dst_offset)
+
+    @staticmethod
+    def launch_auto(ctx, staged, jobs, tables, srcs, n_signal=-1):
+        fields = ctx.survey_set(staged, [j.row for j in jobs], tables)      # the one upload; valid on return
+        payload = ctx.staged_payload(None)
+        mixes = [s.decide(f, s.sr) for s, f in zip(srcs, fields)]
+        ctx.resample_staged_set(payload, [s.staged_row(ctx, j.row[0], j.dst) for s, j in zip(srcs, jobs)], tables, n_signal, mixes)
 
 
 def host_window(x, sr, win, sel=None):

@@ -127,6 +127,15 @@ def get_femininity_score(g_preds):
     return sum(seen.values()) / len(seen)
 
 
+def _basename(fpath):
+    """The name x-vector windows are keyed by: the file's name without its directory and extension.  File sets (io.FileSet, or
+    a tuple or list of member paths) are the Segmenter's: scoring them is not supported."""
+    if not isinstance(fpath, (str, bytes, os.PathLike)):
+        raise ValueError(f'{iss_io.as_media(fpath)}: voice femininity scoring of a file set is not supported; score the '
+                         f"members' files, or their interleaved twin")
+    return os.path.splitext(os.path.basename(fpath))[0]
+
+
 def _load_resnet_params(path):
     """final.onnx -- what the reference's live backend loads (OnnxBackendExtractor, vbx_segmenter.py:249-266) -- through the
     package's own protobuf walk (onnx_reader.py); or raw_81.pth, the torch checkpoint behind the reference's commented
@@ -205,7 +214,7 @@ class VoiceFemininityScoring:
 
     def __call__(self, fpath):
         """-> (score, speech_duration, nb_vectors)  (vbx_segmenter.py:147-202)."""
-        basename = os.path.splitext(os.path.basename(fpath))[0]
+        basename = _basename(fpath)
         if self.resample or self._decoded_on_device(fpath):     # one device decode: the VAD and the front end read the same PCM
             a = self.vad.load_pcm(fpath)
             signal = _to_float(a, np.float64) if a.dtype == np.int16 else a.astype(np.float64)   # = media2sig16kmono
@@ -290,7 +299,7 @@ class VoiceFemininityScoring:
         pass are split on the device and scored from the resident signal (_score_passes); a file whose channels are under
         68 frames goes channel by channel through score_signal."""
         from . import pipeline
-        basename = os.path.splitext(os.path.basename(fpath))[0]
+        basename = _basename(fpath)
         sel, sig = self.vad._channel_sig(fpath, channels)
         if getattr(sig, 'sel', None) is None:                     # a one-channel file
             return [self._alone(fpath, sig, basename)] * len(sel)
@@ -312,7 +321,7 @@ class VoiceFemininityScoring:
         Arguments, passes and errors as Segmenter.segment_excerpts; ranges under 68 frames and float media go alone through
         score_signal, the others are cut on the device and scored from the resident signal (_score_passes)."""
         from . import pipeline
-        basename = os.path.splitext(os.path.basename(fpath))[0]
+        basename = _basename(fpath)
         ranges, sigs = self.vad._excerpt_sigs(fpath, ranges)
         out, todo = [None] * len(sigs), []
         for k, s in enumerate(sigs):
@@ -331,7 +340,7 @@ class VoiceFemininityScoring:
         channel k.  Arguments, passes and errors as Segmenter.segment_channel_excerpts (a one-channel file gives
         [score_excerpts(...)[r]] * len(sel) per range); window times count from the start of the range."""
         from . import pipeline
-        basename = os.path.splitext(os.path.basename(fpath))[0]
+        basename = _basename(fpath)
         ranges, sel, sigs = self.vad._channel_excerpt_sigs(fpath, ranges, channels)
         if sigs is None:
             return [[one] * len(sel) for one in self.score_excerpts(fpath, ranges, batch_files, batch_seconds)]
@@ -362,7 +371,7 @@ class VoiceFemininityScoring:
         """Score every mix of one file on its own -> [(score, speech_duration, nb_vectors) per mix]: entry k is exactly
         score_signal(self.vad.load_pcm_mixes(fpath, [mixes[k]])[0]).  Arguments, passes and errors as Segmenter.segment_mixes."""
         self.vad._no_ffmpeg_mixes()
-        basename = os.path.splitext(os.path.basename(fpath))[0]
+        basename = _basename(fpath)
         return self._score_parts(fpath, basename, *iss_io.mix_source(fpath, mixes, self.vad.resample), batch_files, batch_seconds)
 
     def score_mix_excerpts(self, fpath, ranges, mixes, batch_files=None, batch_seconds=None):
@@ -370,7 +379,7 @@ class VoiceFemininityScoring:
         score_signal(self.vad.load_pcm_mix_excerpts(fpath, [ranges[r]], [mixes[k]])[0][0]).  Arguments, passes and errors as
         Segmenter.segment_mix_excerpts; window times count from the start of the range."""
         self.vad._no_ffmpeg_mixes()
-        basename = os.path.splitext(os.path.basename(fpath))[0]
+        basename = _basename(fpath)
         ranges = [tuple(r) for r in ranges]
         sel, sigs = iss_io.mix_excerpts(fpath, ranges, mixes, self.vad.resample)
         return self._score_pairs(fpath, basename, ranges, sel, sigs, batch_files, batch_seconds)
@@ -435,6 +444,9 @@ class VoiceFemininityScoring:
         `path channel score speech_duration nb_vectors`, one row per channel (a failed file: one row, its channel column empty)."""
         if channels not in (None, 'split'):
             raise ValueError(f"channels={channels!r}: None or 'split'")
+        linput = list(linput)
+        for fpath in linput:
+            _basename(fpath)                              # (a file set: ValueError before anything is decoded)
         if channels is not None:
             return self._batch_channels(list(linput), output_csv, batch_seconds, nbtry, trydelay, verbose)
         linput = list(linput)
@@ -465,7 +477,7 @@ class VoiceFemininityScoring:
             if not speech_dur:
                 results[i] = (None, speech_dur, 0)
                 continue
-            basename = os.path.splitext(os.path.basename(fpath))[0]
+            basename = _basename(fpath)
             duration = len(a) / SR
             pcm = pcm16_of(a)
             if pcm is None:                               # samples beyond int16 (float source): the single-file front end

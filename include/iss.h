@@ -546,6 +546,63 @@ int iss_resample_staged_mix(iss_ctx* ctx, int32_t origin, int64_t payload, const
  * signals) and their bytes since the context was created: what "one upload per file" is counted with.                           */
 int iss_upload_stats(iss_ctx* ctx, int64_t* copies, int64_t* bytes);
 
+/* File sets: several files read as ONE multichannel source -- a call logger's one mono file per direction, a production
+ * system's one mono file per track -- without interleaving anything on the host.  A SET is an ordered list of 1 .. 1024 MEMBERS,
+ * each `frames` >= 1 frames of `channels` >= 1 interleaved channels of the job's format at byte `src_offset` of `src`.  It reads
+ * exactly like its INTERLEAVED TWIN, the one source that holds the members' channels side by side (member 0's first, each
+ * member's in order), as many frames as the longest member, a shorter member continued with samples whose value is 0.0:
+ *     x[j, c] = j < frames_m ? (stored sample j * channels_m + c_local of member m, scaled as for the plain call) : 0.0
+ * for channel c = (channels of the members before m) + c_local.  Such a sample is a digital zero to the survey, never fullscale
+ * and never non-finite: what stored zeros of the twin give.  Everything else is the twin's, to the bit: the mix arithmetic of
+ * "Mixes" above, the tap walk and the quantisation of the plain call, the figures and the survey order of "Channel survey".
+ * Two tables go with a call beside those of the entry point it extends: a set row beside every job row (sets[k] belongs to
+ * jobs[k]) and the call's member rows members[0, nmembers); a job's members are rows [member_begin, member_begin +
+ * member_count).  In the job row `channels` is the sum of the members' channels, `frames_in` the largest of their `frames`, and
+ * src_offset is 0: the members say where the bytes lie.  Members of several jobs may share bytes.
+ *   iss_resample_pcm16_set    iss_resample_pcm16_mix without windows, for sets: whole sources only.  mix_count > 0 writes the
+ *                             job's mixes apart (a split is one-term mixes: K = 1, w = 1, d = 1); mix_count == 0 is the plain
+ *                             downmix of the twin, to the bit -- the planner writes it as the mix of all C channels in order,
+ *                             every w = 1, d = C, the second identity of "Mixes".  Geometry: iss_resample_split_geometry for
+ *                             mix_count rows (one row for the downmix).  The kernel is resample_kernel's SET instantiation: a
+ *                             workgroup stages its mixes channel-major (a lane walks consecutive frames of one mix, so a wave
+ *                             reads consecutive frames of one member); the order in which LDS is filled touches no arithmetic.
+ *                             Device table: job rows, mix-set rows, mix rows, then the term rows, each resolved on the host to
+ *                             (byte offset of the member's first sample of that channel, the member's frames and channels).
+ *   iss_survey_set            iss_survey without windows, for sets: the same chunk geometry, partial rows, second stage and
+ *                             result rows; survey_kernel's SET instantiation stages a chunk's rows through a per-channel table
+ *                             (byte offset, frames, channels of the member) that follows the job rows.
+ *   iss_resample_staged_set   iss_resample_pcm16_set over the payload the context's last iss_survey_set left in the survey's
+ *                             source buffer (origin ISS_STAGED_SURVEY, the payload-id rule of iss_resample_staged_mix): a job
+ *                             must be one of that call's, the same frames_in, channels, format and member rows.  Nothing is
+ *                             uploaded but rows.  A payload left by iss_survey is not one of sets, and the other way round.
+ * ISS_EINVAL (checked before anything is launched or the context changes, the text names the job): member_count < 1 or above
+ * 1024, member rows outside [0, nmembers), a member with frames < 1 or channels < 1, the members' channels not adding up to the
+ * job's `channels` or their longest not being its `frames_in`, a job's src_offset not 0, a member's bytes [src_offset, src_offset
+ * + frames * channels * sample bytes) outside `src` or not aligned to the sample, and everything iss_resample_pcm16_mix (without
+ * windows) / iss_survey refuse.  ISS_ESTATE for iss_resample_staged_set as for iss_resample_staged_mix.
+ * Counters: a set job is ONE job of iss_resample_stats / iss_survey_stats whatever its members, and a call's payload one copy of
+ * iss_upload_stats, its bytes `src_bytes`.  Every other entry point is unchanged, to the bit and to the launch.                 */
+typedef struct {
+    int32_t member_begin;  /* the job's rows of `members`: [member_begin, member_begin + member_count)         */
+    int32_t member_count;  /* 1 .. 1024                                                                       */
+} iss_set;
+typedef struct {
+    int64_t src_offset;    /* byte offset of the member's first frame in `src`, aligned to the sample          */
+    int64_t frames;        /* >= 1                                                                            */
+    int32_t channels;      /* >= 1: the member's own interleaved channels                                     */
+    int32_t reserved;      /* 0                                                                               */
+} iss_set_member;
+int iss_resample_pcm16_set(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
+                           int64_t n_signal, const iss_set* sets, const iss_set_member* members, int64_t nmembers,
+                           const iss_mixset* mixsets, const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms,
+                           int64_t nterms);
+int iss_survey_set(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_survey_job* jobs, int32_t njobs, const iss_set* sets,
+                   const iss_set_member* members, int64_t nmembers, void* results);
+int iss_resample_staged_set(iss_ctx* ctx, int32_t origin, int64_t payload, const iss_resample_job* jobs, int32_t njobs,
+                            int64_t n_signal, const iss_set* sets, const iss_set_member* members, int64_t nmembers,
+                            const iss_mixset* mixsets, const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms,
+                            int64_t nterms);
+
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */
 int iss_host_alloc(iss_ctx* ctx, size_t bytes, void** out);

@@ -4,7 +4,8 @@
 Same options as the reference's scripts/ina_speech_segmenter.py (-i -o -s -d -g -b -e -r, :45-53) and the
 same output naming (<basename>.<format> inside the output directory, :80-84).  Extra: --models synthetic
 (seeded stand-in weights, for machines without the Keras release assets), --resample (with -b None: WAV at any rate /
-channel count, downmixed and resampled to 16 kHz on the GPU) and multi-GPU operation: start it
+channel count, downmixed and resampled to 16 kHz on the GPU), --sets (with -b None: recordings stored as one file per channel,
+read as one multichannel file) and multi-GPU operation: start it
 under `python -m torch.distributed.run --nproc-per-node N` and the inputs are dealt to the N GPUs.
 """
 import argparse
@@ -25,11 +26,51 @@ def _truthy(v):
     raise argparse.ArgumentTypeError(f'invalid truth value {v!r}')
 
 
+def read_sets(path):
+    """The list of --sets: one file set per line, `name<TAB>member<TAB>member...` (empty lines and lines starting with # are
+    skipped) -> [io.FileSet].  The name becomes the output's: <output_directory>/<name>.<format>.  ValueError, naming the line:
+    no member, an empty name, a name with a path separator, a name listed twice."""
+    from inaspeechsegmenter_amd.io import FileSet
+    sets, seen = [], set()
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            line = line.rstrip('\r\n')
+            if not line.strip() or line.lstrip().startswith('#'):
+                continue
+            name, *members = [field.strip() for field in line.split('\t')]
+            members = [m for m in members if m]
+            where = f'{path}: line {no}'
+            if not name:
+                raise ValueError(f'{where}: empty name (a line reads name<TAB>member<TAB>member...)')
+            if not members:
+                raise ValueError(f'{where}: no member (a line reads name<TAB>member<TAB>member...)')
+            if '/' in name or os.sep in name:
+                raise ValueError(f'{where}: the name {name!r} holds a path separator; it names the output inside -o')
+            if name in seen:
+                raise ValueError(f'{where}: the name {name!r} is listed twice')
+            seen.add(name)
+            sets.append(FileSet(members, name=name))
+    return sets
+
+
+def output_stem(media):
+    """What an input's outputs are called inside the output directory: a file's name without its extension, a set's name."""
+    return os.path.splitext(os.path.basename(media))[0] if isinstance(media, str) else media.name
+
+
+def parse_args(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if not args.input and args.sets is None:
+        ap.error('one of -i and --sets is required')
+    return args
+
+
 def build_parser():
     ap = argparse.ArgumentParser(
         description="Speech/Music(/Noise) and Male/Female segmentation into CSV or Praat TextGrid files. 'noEnergy' segments "
                     "are excluded from the music / noise / speech / gender analysis.")
-    ap.add_argument('-i', '--input', nargs='+', required=True, help='media paths, glob patterns or http(s) URLs')
+    ap.add_argument('-i', '--input', nargs='+', default=[], help='media paths, glob patterns or http(s) URLs (optional with --sets)')
     ap.add_argument('-o', '--output_directory', required=True, help='directory receiving <basename>.<format>')
     ap.add_argument('-s', '--batch_size', type=int, default=32, help='accepted for compatibility (the engine sizes its own passes)')
     ap.add_argument('-d', '--vad_engine', choices=['sm', 'smn'], default='smn')
@@ -61,11 +102,18 @@ def build_parser():
                          'zeros, clipped and non-finite samples, which channels carry signal) on the GPU and write one row per file '
                          "and channel to OUT.tsv; a row with channel '*' per file carries what the default downmix loses in dB and "
                          'the polarity-inverted channel pairs')
+    ap.add_argument('--sets', default=None, metavar='LIST.tsv',
+                    help='with -b None: recordings stored as one file per channel or group of channels (a call logger\'s X-in.wav / '
+                         'X-out.wav, one mono WAV per track), one per line of LIST.tsv: name<TAB>member<TAB>member...  A set is read '
+                         'as the one file holding its members\' channels side by side, shorter members continued with silence, on the '
+                         'GPU and without writing that file; its output is <name>.<format>.  The sets follow the files of -i; '
+                         '--channels, --mixes, --survey and --decisions treat them as files.  Members share rate and sample format; '
+                         'FLAC and ADPCM members are not supported')
     return ap
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     ffmpeg = None if args.ffmpeg_binary.lower() in ('none', '') else args.ffmpeg_binary
     if args.resample and ffmpeg is not None:
         build_parser().error('--resample needs -b None (ffmpeg already resamples)')
@@ -98,6 +146,16 @@ def main(argv=None):
         build_parser().error('--survey needs -b None (ffmpeg downmixes every file)')
     if args.survey is not None and int(os.environ.get('WORLD_SIZE', '1')) != 1:
         build_parser().error('--survey runs on one GPU')
+    sets = []
+    if args.sets is not None:
+        if ffmpeg is not None:
+            build_parser().error('--sets needs -b None (ffmpeg reads one file per run)')
+        if int(os.environ.get('WORLD_SIZE', '1')) != 1:
+            build_parser().error('--sets runs on one GPU')
+        try:
+            sets = read_sets(args.sets)
+        except ValueError as exc:
+            build_parser().error(str(exc))
     if ffmpeg is None:
         print('Disabling ffmpeg. WAV (PCM, float, G.711, IMA and Microsoft ADPCM), FLAC, AIFF, AU, CAF, Wave64 and RF64 files are read directly. '
               + ('Files at other rates or with several channels are resampled on the GPU.' if args.resample
@@ -105,10 +163,12 @@ def main(argv=None):
     inputs = []
     for pat in args.input:
         inputs += [pat] if pat.startswith('http') else sorted(glob.glob(pat))
-    assert len(inputs) > 0, 'No existing media selected for analysis! Bad values provided to -i (%s)' % args.input
+    assert len(inputs) + len(sets) > 0, 'No existing media selected for analysis! Bad values provided to -i (%s)' % args.input
+    inputs += sets
+    names = [f if isinstance(f, str) else f.name for f in inputs]          # what the tables of --survey and --decisions carry
     odir = args.output_directory.strip(' \t\n\r').rstrip('/')
     assert os.access(odir, os.W_OK), 'Directory %s is not writable!' % odir
-    outputs = [os.path.join(odir, os.path.splitext(os.path.basename(f))[0] + '.' + args.export_format) for f in inputs]
+    outputs = [os.path.join(odir, output_stem(f) + '.' + args.export_format) for f in inputs]
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -117,7 +177,7 @@ def main(argv=None):
                     energy_ratio=args.energy_ratio, device=local_rank, models=args.models, resample=args.resample)
     if args.survey is not None:
         from inaspeechsegmenter_amd.survey import write_tsv
-        write_tsv(args.survey, inputs, seg.survey_files(inputs))
+        write_tsv(args.survey, names, seg.survey_files(inputs))
         return 0
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
@@ -128,7 +188,7 @@ def main(argv=None):
             if args.decisions is not None:
                 from inaspeechsegmenter_amd.survey import write_decisions_tsv
                 failed = {dst: text for dst, code, text in lmsg if code == 2}
-                write_decisions_tsv(args.decisions, inputs, decisions, {src: failed[dst] for src, dst in zip(inputs, outputs)
+                write_decisions_tsv(args.decisions, names, decisions, {src: failed[dst] for src, dst in zip(names, outputs)
                                                                         if dst in failed})
             return 0
         if world == 1:

@@ -104,6 +104,37 @@ int main() {
     st = job(2, 1000, 2, ISS_RS_F32);
     CHECK(!sv_plan(&st, nullptr, 1, 0, &off, &sz, plan, err));            // a decoder stages integers
 
+    // file sets: a job's channels resolved to its members; every refusal names the job and leaves no row behind
+    {
+        const iss_set_member mem[] = {{0, 3000, 1, 0}, {6000, 2000, 2, 0}, {14000, 1, 1, 0}};
+        const iss_set two{0, 2}, three{0, 3};
+        iss_survey_job sj = job(0, 3000, 3, ISS_RS_I16);
+        CHECK(sv_plan(&sj, nullptr, 1, 14000, nullptr, nullptr, plan, err, &two, mem, 3));
+        CHECK(plan.chans.size() == 3 && plan.dj[0].src_off == 0 && plan.dj[0].n == 3000 && plan.chunks == 3);
+        CHECK(plan.chans[0].off == 0 && plan.chans[0].frames == 3000 && plan.chans[0].step == 1);
+        CHECK(plan.chans[1].off == 6000 && plan.chans[2].off == 6002 && plan.chans[2].frames == 2000 && plan.chans[2].step == 2);
+        iss_survey_job both[2] = {sj, job(0, 3000, 4, ISS_RS_I16)};
+        const iss_set rows[2] = {two, three};
+        CHECK(sv_plan(both, nullptr, 2, 14002, nullptr, nullptr, plan, err, rows, mem, 3));
+        CHECK(plan.chans.size() == 7 && plan.dj[1].src_off == 3 && plan.chans[6].off == 14000 && plan.chans[6].frames == 1);
+        CHECK(!sv_plan(both, nullptr, 2, 14001, nullptr, nullptr, plan, err, rows, mem, 3) && err.find("job 1: member 2") == 0);
+        CHECK(!sv_plan(&sj, nullptr, 1, 13999, nullptr, nullptr, plan, err, &two, mem, 3) && err.find("job 0: member 1") == 0);
+        const iss_set none{0, 0}, past{2, 2}, before{-1, 2};
+        CHECK(!sv_plan(&sj, nullptr, 1, 14000, nullptr, nullptr, plan, err, &none, mem, 3) && err.find("job 0: member rows") == 0);
+        CHECK(!sv_plan(&sj, nullptr, 1, 14000, nullptr, nullptr, plan, err, &past, mem, 3));
+        CHECK(!sv_plan(&sj, nullptr, 1, 14000, nullptr, nullptr, plan, err, &before, mem, 3));
+        CHECK(!sv_plan(&sj, nullptr, 1, 14000, nullptr, nullptr, plan, err, &two, nullptr, 0));
+        iss_survey_job off1 = job(2, 3000, 3, ISS_RS_I16), fewer = job(0, 2999, 3, ISS_RS_I16), wider = job(0, 3000, 4, ISS_RS_I16);
+        CHECK(!sv_plan(&off1, nullptr, 1, 14000, nullptr, nullptr, plan, err, &two, mem, 3));
+        CHECK(!sv_plan(&fewer, nullptr, 1, 14000, nullptr, nullptr, plan, err, &two, mem, 3));
+        CHECK(!sv_plan(&wider, nullptr, 1, 14000, nullptr, nullptr, plan, err, &two, mem, 3));
+        const iss_set_member odd[] = {{1, 3000, 1, 0}, {6000, 2000, 2, 0}}, empty[] = {{0, 3000, 1, 0}, {6000, 0, 2, 0}};
+        CHECK(!sv_plan(&sj, nullptr, 1, 14000, nullptr, nullptr, plan, err, &two, odd, 2));      // misaligned
+        CHECK(!sv_plan(&sj, nullptr, 1, 14000, nullptr, nullptr, plan, err, &two, empty, 2));
+        iss_window w0{0, 3000, 3000, 0, 3000};
+        CHECK(!sv_plan(&sj, &w0, 1, 14000, nullptr, nullptr, plan, err, &two, mem, 3));           // whole sets only
+    }
+
     // no jobs; many chunks
     CHECK(sv_plan(nullptr, nullptr, 0, 0, nullptr, nullptr, plan, err) && plan.dj.empty() && plan.chunks == 0);
     iss_survey_job big = job(0, (int64_t(1) << 40) / 2, 1, ISS_RS_I16);
