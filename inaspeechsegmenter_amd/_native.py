@@ -218,6 +218,7 @@ def lib():
         'iss_cnn_probs_async': (C.c_int, [vp, C.c_int, pi32, i32, pf, pu8, pi64]),
         'iss_cnn_dead_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_wait': (C.c_int, [vp, i64]),
+        'iss_wait_slots': (C.c_int, [vp, i64, i32, pi32]),
         'iss_comm_unique_id': (C.c_int, [vp, pu8]),
         'iss_comm_init': (C.c_int, [vp, pu8, i32, i32]),
         'iss_comm_destroy': (C.c_int, [vp]),
@@ -848,6 +849,14 @@ class Context:
 
     def wait(self, ticket=-1):
         self._ck(self._L.iss_wait(self._h, int(ticket)), 'iss_wait')
+
+    def wait_slots(self, ticket, upto):
+        """iss_wait_slots: block until slots [0, upto) of cnn_probs_async call `ticket` are in its output arrays (upto <= 0: do not
+        block) -> how many slots have landed: >= upto, never less than an earlier answer, the call's slot count once it is
+        complete.  A ticket that wait() has retired, or that was never given out, answers 2^31 - 1: everything has landed."""
+        landed = C.c_int32(0)
+        self._ck(self._L.iss_wait_slots(self._h, int(ticket), int(upto), C.byref(landed)), 'iss_wait_slots')
+        return landed.value
 
     # ---- multi-GPU exchange (RCCL)
     def comm_unique_id(self):

@@ -1037,13 +1037,15 @@ __global__ __launch_bounds__(256) void row_flags_kernel(const float* __restrict_
 
 // The rows of one pass over the live windows to the caller's slots: out[map[i]] = res[i], or 0.5 where the window did not
 // normalise to finite values (segmenter.py:175); finite[map[i]] = the device's flag.  The dead slots were filled before.
+// map == nullptr: slot i is row i (a pass of a list without dead windows, stored where it lands).  `out` / `finite` may be
+// page-locked host memory: every element is stored once, by one thread.
 __global__ void scatter_probs_kernel(const float* __restrict__ res, const uint8_t* __restrict__ lfinite, const int32_t* __restrict__ map,
                                      long long n, int C, float* __restrict__ out, uint8_t* __restrict__ finite) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * C) return;
     const long long r = i / C;
     const int k = (int)(i - r * C);
-    const long long m = map[r];
+    const long long m = map ? map[r] : r;
     const uint8_t f = lfinite[r];
     out[m * C + k] = f ? res[i] : 0.5f;
     if (k == 0) finite[m] = f;
@@ -1864,10 +1866,10 @@ static int precision_guard(iss_ctx* c, int id, const int32_t* win_row, int32_t n
     return ISS_OK;
 }
 
-// The row flags of the resident features (row_flags_kernel), on the host: computed at the first call after the features changed,
-// with one short wait -- in every caller the stream then holds only the feature kernels (iss_get_loge has just synchronised).
-static int ensure_row_flags(iss_ctx* c) {
-    if (c->flags_epoch == c->feat_epoch) return ISS_OK;
+// The row flags of the resident features (row_flags_kernel) and their copy to the host, on the stream; no wait.  iss_sidekit puts
+// them right behind its feature kernel, so that the one wait of iss_get_loge brings them along with the log-energy.
+int iss_enqueue_row_flags(iss_ctx* c) {
+    if (c->T <= 0) return ISS_OK;
     int rc;
     if ((rc = iss_reserve(c, c->d_rowflag, (size_t)c->T))) return rc;
     if ((rc = iss_rowflag_host(c, (size_t)c->T))) return rc;
@@ -1877,10 +1879,31 @@ static int ensure_row_flags(iss_ctx* c) {
     iss_prof_end(c);
     ISS_HIP(c, hipGetLastError());
     ISS_HIP(c, hipMemcpyAsync(c->h_rowflag, c->d_rowflag.p, (size_t)c->T, hipMemcpyDeviceToHost, c->stream));
+    return ISS_OK;
+}
+
+// The row flags on the host: already there when the features came from iss_sidekit and iss_get_loge has waited since (or from
+// iss_set_mspec, which scans its argument); else one short wait at the first call after the features changed -- for the flags
+// iss_sidekit queued, when the caller has not waited through iss_get_loge, or for flags computed here.
+static int ensure_row_flags(iss_ctx* c) {
+    if (c->flags_epoch == c->feat_epoch) return ISS_OK;
+    int rc;
+    if (c->flags_queued != c->feat_epoch && (rc = iss_enqueue_row_flags(c))) return rc;
     ISS_HIP(c, hipStreamSynchronize(c->stream));
     c->bad_prefix.clear();
     c->flags_epoch = c->feat_epoch;
     return ISS_OK;
+}
+
+// Are the `bytes` at p page-locked host memory?  A device-to-host hipMemcpyAsync into pageable memory holds the submitting thread
+// until the copy has run, so copies between the passes of a call would serialise its submission with its execution.
+static bool host_pinned(const void* p, size_t bytes) {
+    for (const char* q : {(const char*)p, (const char*)p + (bytes ? bytes - 1 : 0)}) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, q) != hipSuccess) { (void)hipGetLastError(); return false; }
+        if (at.type != hipMemoryTypeHost) return false;
+    }
+    return true;
 }
 
 // P[t] = rows below t with a non-finite value in their first w columns: the window at row r is dead iff P[r + 68] != P[r]
@@ -1961,7 +1984,23 @@ static int cnn_probs_impl(iss_ctx* c, int id, const int32_t* win_row, int32_t ns
     const int32_t* d_map = (const int32_t*)c->d_winrow.p + nlive;
     uint8_t* d_fin = compact ? (uint8_t*)c->d_lfinite.p : (uint8_t*)c->d_finite.p;
     const long long tot = (long long)nslots * n.out_dim;
-    if (compact) {                                   // the dead slots (the live ones are overwritten by the scatter)
+    // Landings (iss_internal.h, iss_ctx::Ticket): an asynchronous call with page-locked outputs stores every pass's rows straight
+    // into the caller's arrays (scatter_probs_kernel; the arrays are device-visible) and records an event behind the pass, so that
+    // the host can start on the front of the result while the later passes run (iss_wait_slots).  No copy follows a pass, and none
+    // the call.  Every other call gathers its result on the device and copies it out once, behind its last pass.
+    float* dev_probs = nullptr;
+    uint8_t* dev_finite = nullptr;
+    const bool per_pass = async && !c->in_guard &&
+                          host_pinned(probs_out, (size_t)tot * 4) && host_pinned(finite_out, (size_t)nslots) &&
+                          hipHostGetDevicePointer((void**)&dev_probs, probs_out, 0) == hipSuccess &&
+                          hipHostGetDevicePointer((void**)&dev_finite, finite_out, 0) == hipSuccess;
+    if (per_pass && compact) {                       // the dead slots, by the host: no kernel stores them
+        for (int i = 0, j = 0; i < nslots; ++i) {
+            if (j < nlive && lm[(size_t)nlive + j] == i) { ++j; continue; }
+            for (int k = 0; k < n.out_dim; ++k) probs_out[(size_t)i * n.out_dim + k] = 0.5f;
+            finite_out[i] = 0;
+        }
+    } else if (compact) {                            // the dead slots (the live ones are overwritten by the scatter)
         iss_prof_begin(c, 2, 0);
         hipLaunchKernelGGL(fill_half_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, (float*)c->d_out.p, tot);
         iss_prof_end(c);
@@ -1983,6 +2022,17 @@ static int cnn_probs_impl(iss_ctx* c, int id, const int32_t* win_row, int32_t ns
         for (int i = 1; i < nlive; ++i) { gmin = std::min(gmin, rows[i]); gmax = std::max(gmax, rows[i]); }
         if ((long long)(gmax - gmin + 68) * 4 > (long long)nlive * 68) share = false;
     }
+    iss_ctx::Ticket ticket;
+    auto landing = [&](int32_t end) -> int {         // an asynchronous call's event: slots [0, end) are in the caller's arrays behind it
+        if (!async) return ISS_OK;
+        hipEvent_t ev;
+        if (!c->ev_pool.empty()) { ev = c->ev_pool.back(); c->ev_pool.pop_back(); }
+        else ISS_HIP(c, hipEventCreate(&ev));
+        ticket.land.push_back({end, ev});            // (owned by the ticket from here on, whatever fails below)
+        ISS_HIP(c, hipEventRecord(ev, c->stream));
+        return ISS_OK;
+    };
+    auto give_back = [&]() { for (auto& l : ticket.land) c->ev_pool.push_back(l.ev); ticket.land.clear(); };
     for (int s0 = 0; s0 < nlive; s0 += bc) {
         const int cur = std::min(bc, nlive - s0);
         float* res = nullptr;
@@ -1990,33 +2040,41 @@ static int cnn_probs_impl(iss_ctx* c, int id, const int32_t* win_row, int32_t ns
         for (int i = s0 + 1; i < s0 + cur; ++i) { rmin = std::min(rmin, rows[i]); rmax = std::max(rmax, rows[i]); }
         rc = run_program(c, n, cur, (const int32_t*)c->d_winrow.p + s0, (const float*)c->d_stats.p + 2 * (size_t)s0,
                          (const uint8_t*)d_fin + s0, nullptr, &res, rmin, rmax, share);
-        if (rc) return rc;
-        if (compact) {
+        if (rc) { give_back(); return rc; }
+        if (compact || per_pass) {
+            // to the caller's slots: through the map of the live windows, or (no dead window) to slots [s0, s0 + cur); 0.5 where
+            // the window did not normalise -- what mask_probs_kernel writes over the gathered result of the other calls
             const long long ct = (long long)cur * n.out_dim;
+            float* out = per_pass ? dev_probs : (float*)c->d_out.p;
+            uint8_t* fin = per_pass ? dev_finite : (uint8_t*)c->d_finite.p;
             iss_prof_begin(c, 2, 0);
             hipLaunchKernelGGL(scatter_probs_kernel, dim3((unsigned)((ct + 255) / 256)), dim3(256), 0, c->stream, (const float*)res,
-                               (const uint8_t*)d_fin + s0, d_map + s0, (long long)cur, n.out_dim, (float*)c->d_out.p, (uint8_t*)c->d_finite.p);
+                               (const uint8_t*)d_fin + s0, compact ? d_map + s0 : (const int32_t*)nullptr, (long long)cur, n.out_dim,
+                               compact ? out : out + (size_t)s0 * n.out_dim, compact ? fin : fin + s0);
             iss_prof_end(c);
-            ISS_HIP(c, hipGetLastError());
+            if (hipGetLastError() != hipSuccess) { give_back(); return iss_fail(c, ISS_EHIP, "scatter_probs_kernel launch failed"); }
         } else {
             ISS_HIP(c, hipMemcpyAsync((float*)c->d_out.p + (size_t)s0 * n.out_dim, res, (size_t)cur * n.out_dim * 4,
                                       hipMemcpyDeviceToDevice, c->stream));
         }
+        // a landing per pass: its own slots, and with dead windows in the list every slot up to the next live window's -- the dead
+        // ones in between hold their 0.5 / 0 already
+        if (per_pass && (rc = landing(s0 + cur >= nlive ? nslots : (compact ? lm[(size_t)nlive + s0 + cur] : s0 + cur)))) { give_back(); return rc; }
     }
-    if (!compact) {
-        hipLaunchKernelGGL(mask_probs_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream,
-                           (float*)c->d_out.p, (const uint8_t*)c->d_finite.p, (long long)nslots, n.out_dim);
-        ISS_HIP(c, hipGetLastError());
+    if (!per_pass) {                                 // gathered on the device: one copy behind the last pass, one landing
+        if (!compact) {
+            hipLaunchKernelGGL(mask_probs_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream,
+                               (float*)c->d_out.p, (const uint8_t*)c->d_finite.p, (long long)nslots, n.out_dim);
+            ISS_HIP(c, hipGetLastError());
+        }
+        ISS_HIP(c, hipMemcpyAsync(probs_out, c->d_out.p, (size_t)tot * 4, hipMemcpyDeviceToHost, c->stream));
+        ISS_HIP(c, hipMemcpyAsync(finite_out, c->d_finite.p, (size_t)nslots, hipMemcpyDeviceToHost, c->stream));
     }
-    ISS_HIP(c, hipMemcpyAsync(probs_out, c->d_out.p, (size_t)tot * 4, hipMemcpyDeviceToHost, c->stream));
-    ISS_HIP(c, hipMemcpyAsync(finite_out, c->d_finite.p, (size_t)nslots, hipMemcpyDeviceToHost, c->stream));
+    // (stored where it lands, and every window dead: no pass has recorded the landing of the slots the host wrote)
+    if ((!per_pass || nlive == 0) && (rc = landing(nslots))) { give_back(); return rc; }
     if (async) {
-        hipEvent_t ev;
-        if (!c->ev_pool.empty()) { ev = c->ev_pool.back(); c->ev_pool.pop_back(); }
-        else ISS_HIP(c, hipEventCreate(&ev));
-        ISS_HIP(c, hipEventRecord(ev, c->stream));
-        c->ticket_ev.push_back(ev);
-        if (ticket_out) *ticket_out = c->ticket_base + (int64_t)c->ticket_ev.size() - 1;
+        c->tickets.push_back(std::move(ticket));
+        if (ticket_out) *ticket_out = c->ticket_base + (int64_t)c->tickets.size() - 1;
         return ISS_OK;
     }
     ISS_HIP(c, hipStreamSynchronize(c->stream));

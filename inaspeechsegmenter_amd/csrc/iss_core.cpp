@@ -86,7 +86,7 @@ extern "C" void iss_destroy(iss_ctx* c) {
     for (auto& f : c->rs_filters) if (f.d_taps) (void)hipFree(f.d_taps);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& e : c->ev_pool) (void)hipEventDestroy(e);
-    for (auto& e : c->ticket_ev) (void)hipEventDestroy(e);
+    for (auto& t : c->tickets) for (auto& l : t.land) (void)hipEventDestroy(l.ev);
     for (auto& s : c->staging) { if (s.p) (void)hipHostFree(s.p); if (s.done) (void)hipEventDestroy(s.done); }
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     if (c->h_rowflag) (void)hipHostFree(c->h_rowflag);
@@ -127,7 +127,7 @@ extern "C" int iss_scribble(iss_ctx* c, uint32_t word) {
         for (size_t i = b->cap & ~(size_t)3; i < b->cap; ++i)      // a capacity need not be a multiple of 4: the word's leading bytes
             ISS_HIP(c, hipMemsetD8Async((hipDeviceptr_t)((char*)b->p + i), (unsigned char)(word >> (8 * (i & 3))), 1, c->stream));
     }
-    c->flags_epoch = 0;                    // feat_epoch starts at 1: the row flags are computed again
+    c->flags_epoch = c->flags_queued = 0;  // feat_epoch starts at 1: the row flags are computed again
     c->bad_prefix.clear();
     c->sv_held.id = c->flac.held = c->adpcm.held = c->msadpcm.held = 0;      // what the origins held is overwritten: ISS_ESTATE from here on
     return ISS_OK;
@@ -284,17 +284,40 @@ void iss_stage_mark(iss_ctx* c, int slot) {
 extern "C" int iss_wait(iss_ctx* c, int64_t ticket) {
     if (!c) return ISS_EINVAL;
     ISS_HIP(c, hipSetDevice(c->device));
-    const int64_t last = c->ticket_base + (int64_t)c->ticket_ev.size() - 1;
+    const int64_t last = c->ticket_base + (int64_t)c->tickets.size() - 1;
     if (ticket < 0 || ticket >= last) {
         ISS_HIP(c, hipStreamSynchronize(c->stream));
-        for (auto e : c->ticket_ev) c->ev_pool.push_back(e);
-        c->ticket_base += (int64_t)c->ticket_ev.size();
-        c->ticket_ev.clear();
+        for (auto& t : c->tickets) for (auto& l : t.land) c->ev_pool.push_back(l.ev);
+        c->ticket_base += (int64_t)c->tickets.size();
+        c->tickets.clear();
         iss_prof_collect(c);
         return ISS_OK;
     }
     if (ticket < c->ticket_base) return ISS_OK;       // already waited for
-    ISS_HIP(c, hipEventSynchronize(c->ticket_ev[(size_t)(ticket - c->ticket_base)]));
+    ISS_HIP(c, hipEventSynchronize(c->tickets[(size_t)(ticket - c->ticket_base)].land.back().ev));
+    return ISS_OK;
+}
+
+extern "C" int iss_wait_slots(iss_ctx* c, int64_t ticket, int32_t upto, int32_t* landed_out) {
+    if (!c || !landed_out) return iss_fail(c, ISS_EINVAL, "iss_wait_slots: NULL argument");
+    *landed_out = 0x7fffffff;
+    if (ticket < c->ticket_base || ticket >= c->ticket_base + (int64_t)c->tickets.size()) return ISS_OK;   // retired, or never given out
+    ISS_HIP(c, hipSetDevice(c->device));
+    auto& t = c->tickets[(size_t)(ticket - c->ticket_base)];
+    const auto& land = t.land;
+    // the landings complete in order (one stream): wait for the first that covers [0, upto), then see how many more are through
+    if (upto > 0 && (t.done == 0 || (land[t.done - 1].slot_end < upto && t.done < land.size()))) {
+        size_t k = t.done;
+        while (k + 1 < land.size() && land[k].slot_end < upto) ++k;
+        ISS_HIP(c, hipEventSynchronize(land[k].ev));
+        t.done = k + 1;
+    }
+    for (; t.done < land.size(); ++t.done) {
+        const hipError_t e = hipEventQuery(land[t.done].ev);
+        if (e == hipErrorNotReady) break;
+        if (e != hipSuccess) return iss_fail(c, ISS_EHIP, "hipEventQuery failed: %s", hipGetErrorString(e));
+    }
+    *landed_out = t.done ? land[t.done - 1].slot_end : 0;
     return ISS_OK;
 }
 
@@ -313,6 +336,14 @@ extern "C" int iss_sidekit(iss_ctx* c, int32_t* T_out) {
     if (rc) return rc;
     if (T > 0) { rc = iss_launch_sidekit(c); if (rc) return rc; }
     c->have_feats = true; ++c->feat_epoch;
+    // the row flags of these features (cnn.hip, dead windows) right behind them: the caller's next wait -- iss_get_loge in every
+    // caller that goes on to the networks -- brings them to the host, and the first CNN call need not wait for them on its own.
+    // A caller that waits some other way gets one more wait in that call (ensure_row_flags), no second launch; one that never
+    // runs a network pays this launch and T bytes of read-back for nothing (about 15 us per audio-hour).
+    if (T > 0) {
+        if ((rc = iss_enqueue_row_flags(c))) return rc;
+        c->flags_queued = c->feat_epoch;
+    }
     if (T_out) *T_out = (int32_t)T;
     return ISS_OK;
 }
@@ -323,6 +354,10 @@ extern "C" int iss_get_loge(iss_ctx* c, float* out) {
     ISS_HIP(c, hipSetDevice(c->device));
     if (c->T > 0) ISS_HIP(c, hipMemcpyAsync(out, c->loge.p, (size_t)c->T * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     ISS_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->flags_queued == c->feat_epoch && c->flags_epoch != c->feat_epoch) {      // iss_sidekit's row flags came with this wait
+        c->bad_prefix.clear();
+        c->flags_epoch = c->feat_epoch;
+    }
     iss_prof_collect(c);
     return ISS_OK;
 }

@@ -122,6 +122,7 @@ struct iss_ctx {
     // dead windows (cnn.hip, cnn_probs_impl): per resident log-mel row the lowest column holding a non-finite value (24: none),
     // read back once per feature set, and per network width w the prefix count of rows whose flag is < w
     uint64_t flags_epoch = 0;             // feat_epoch the row flags belong to
+    uint64_t flags_queued = 0;            // feat_epoch whose flags iss_sidekit has put on the stream (kernel + read-back): they are on the host after the next wait
     DevBuf d_rowflag;
     uint8_t* h_rowflag = nullptr;         // page-locked, grow-only
     size_t h_rowflag_cap = 0;
@@ -154,8 +155,12 @@ struct iss_ctx {
     // pinned staging buffers of the asynchronous entry points (window lists): reused once their copy has completed
     struct Staging { void* p = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool busy = false; };
     std::vector<Staging> staging;
-    // tickets of iss_cnn_probs_async: ticket t <-> ticket_ev[t - ticket_base]
-    std::vector<hipEvent_t> ticket_ev;
+    // tickets of iss_cnn_probs_async: ticket t <-> tickets[t - ticket_base].  A call's result lands in the caller's arrays front
+    // to back, one landing per pass (page-locked outputs) or one in all: slots [0, slot_end) are there once `ev` has completed.
+    // slot_end ascends and the last one is the call's slot count; the last event is what iss_wait waits for
+    struct Landing { int32_t slot_end; hipEvent_t ev; };
+    struct Ticket { std::vector<Landing> land; size_t done = 0; };   // done: landings iss_wait_slots has seen complete
+    std::vector<Ticket> tickets;
     int64_t ticket_base = 1;
     hipEvent_t order_ev = nullptr;        // iss_signal_pcm16_device*: producer stream -> library stream
 
@@ -261,3 +266,4 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
 // implemented in the .hip files
 int iss_launch_sidekit(iss_ctx* c);
 int iss_cnn_free(iss_ctx* c, int net_id);
+int iss_enqueue_row_flags(iss_ctx* c);       // cnn.hip: row_flags_kernel over the resident features and its read-back, no wait

@@ -237,17 +237,16 @@ class DnnSegmenter:
         asynchronously in dense mode and smooths the first while the device evaluates the second)."""
         ctx = ctx or self.ctx
         nframes = _ensure_resident(ctx, mspec)
-        rows = _window_rows(nframes, difflen)
         todo = [(start, stop) for lab, start, stop in lseg if lab == self.inlabel]
         if todo:
             idx = np.concatenate([np.arange(s, e) for s, e in todo])
-            if allpred is not None:
+            if allpred is not None:                            # (whoever computed them built the window list)
                 rawpred = allpred[idx]
             elif dense:
-                allpred, _finite = self.probs(ctx, rows)
+                allpred, _finite = self.probs(ctx, _window_rows(nframes, difflen))
                 rawpred = allpred[idx]
             else:
-                rawpred, _finite = self.probs(ctx, rows[idx])  # non-finite windows already at 0.5 (:175)
+                rawpred, _finite = self.probs(ctx, _window_rows(nframes, difflen)[idx])  # non-finite windows already at 0.5 (:175)
         ret = []
         trans = diag_trans_exp(self.viterbi_arg, len(self.outlabels))
         pos = 0
@@ -262,6 +261,53 @@ class DnnSegmenter:
                 pred = viterbi_decoding(np.log(r), trans)
             for lab2, start2, stop2 in _binidx2seglist(pred):
                 ret.append((self.outlabels[int(lab2)], start2 + start, stop2 + start))
+        return ret
+
+    def smooth_landed(self, ctx, ticket, allpred, lseg):
+        """`__call__(..., allpred=allpred)` for probabilities that are still arriving: `allpred` is the page-locked result of
+        cnn_probs_async `ticket`, whose slots land front to back, pass by pass (include/iss.h, iss_wait_slots).  The `inlabel`
+        spans are walked in order: wait until the next one has landed, take every further span that has landed with it, and
+        smooth them together -- one np.log over their rows, one iss_viterbi_segments_f32 call (each span on its own, the
+        arithmetic of the per-span calls), one run-length encoding.  So only the spans of the last landing are left to do once
+        the device is through.  A context without wait_slots (a test double) lands everything at wait(ticket)."""
+        spans = [(start, stop) for lab, start, stop in lseg if lab == self.inlabel]
+        if not spans:
+            return list(lseg)
+        trans = diag_trans_exp(self.viterbi_arg, len(self.outlabels))
+        wait_slots = getattr(ctx, 'wait_slots', None)
+        runs = [[] for _ in spans]                              # per span: its refined (label, start, stop)
+        i = 0
+        while i < len(spans):
+            if wait_slots is None:
+                ctx.wait(ticket)
+                landed = len(allpred)
+            else:
+                landed = wait_slots(ticket, spans[i][1])
+            j = i + 1
+            while j < len(spans) and spans[j][1] <= landed:
+                j += 1
+            first = np.array([s for s, _ in spans[i:j]], dtype=np.int64)
+            length = np.array([e - s for s, e in spans[i:j]], dtype=np.int64)
+            with np.errstate(divide='ignore'):
+                em = np.log(allpred[spans[i][0]:spans[i][1]] if j == i + 1 else
+                            np.concatenate([allpred[s:e] for s, e in spans[i:j]]))
+            pred = _native.viterbi_segments(em, length, trans)
+            # run-length encode all spans at once: a run starts where the label changes, and where a span starts
+            off = np.concatenate(([0], np.cumsum(length)))      # span k of the batch = rows [off[k], off[k + 1]) of pred
+            a = np.union1d(np.flatnonzero(pred[1:] != pred[:-1]) + 1, off[:-1])
+            b = np.append(a[1:], len(pred))
+            k = np.searchsorted(off, a, side='right') - 1
+            shift = first[k] - off[k]
+            for lab, kk, s, e in zip(pred[a].tolist(), k.tolist(), (a + shift).tolist(), (b + shift).tolist()):
+                runs[i + kk].append((self.outlabels[lab], s, e))
+            i = j
+        ret, k = [], 0
+        for seg in lseg:
+            if seg[0] != self.inlabel:
+                ret.append(seg)
+            else:
+                ret.extend(runs[k])
+                k += 1
         return ret
 
 
@@ -461,11 +507,13 @@ class Segmenter:
             pending = (t1, p1, t2, p2)
         lseg = _energy_segments(loge, self.energy_ratio)
         if pending is not None:
+            # both results land pass by pass: the energy spans are smoothed over the VAD ticket as they arrive, then the speech
+            # spans over the gender ticket, so that after the device's last kernel only the spans of the last pass remain
             t1, p1, t2, p2 = pending
-            self.ctx.wait(t1)
-            lseg = self.vad(mspec, lseg, difflen, allpred=p1)
-            self.ctx.wait(t2)
-            return self.gender(mspec, lseg, difflen, allpred=p2)
+            lseg = self.vad.smooth_landed(self.ctx, t1, p1, lseg)
+            lseg = self.gender.smooth_landed(self.ctx, t2, p2, lseg)
+            self.ctx.wait(t2)                                   # (retires both tickets; all that was waited for has landed)
+            return lseg
         lseg = self.vad(mspec, lseg, difflen, dense=dense)
         if self.detect_gender:
             lseg = self.gender(mspec, lseg, difflen, dense=dense)

@@ -609,7 +609,10 @@ int iss_host_alloc(iss_ctx* ctx, size_t bytes, void** out);
 int iss_host_free(iss_ctx* ctx, void* p);
 
 /* Run the front end on the resident signal.  Results stay in HBM (mspec (T,24),
- * loge (T,)); *T_out = int((n-400)/160)+1 (sidekit_mfcc.py:254), 0 if n < 400. */
+ * loge (T,)); *T_out = int((n-400)/160)+1 (sidekit_mfcc.py:254), 0 if n < 400.
+ * Every call also queues one small kernel over the log-mel rows and a T-byte read-back behind the feature kernel (the row
+ * flags by which iss_cnn_probs* finds dead windows), whether or not a network runs later: iss_get_loge's wait brings them to
+ * the host; after any other wait the first iss_cnn_probs* call waits once more for the stream, without a second launch. */
 int iss_sidekit(iss_ctx* ctx, int32_t* T_out);
 int iss_get_loge(iss_ctx* ctx, float* loge_out /* T */);
 int iss_get_mspec(iss_ctx* ctx, float* mspec_out /* T*24 */);
@@ -707,7 +710,7 @@ int iss_cnn_probs(iss_ctx* ctx, int net_id, const int32_t* win_row, int32_t n,
 /* Asynchronous form: enqueues the same work on the context's stream and returns; win_row
  * is consumed before the call returns, probs_out / finite_out (page-locked memory from
  * iss_host_alloc if the copy is to overlap host work) are valid after iss_wait(ctx, ticket)
- * (or any other call that synchronises the context).  The resident mel spectrogram must not
+ * (or any other call that synchronises the context), and front to back as iss_wait_slots reports.  The resident mel spectrogram must not
  * be replaced before iss_wait.  Lets the host run the Viterbi of one network
  * (segmenter.py:176) while the device already evaluates the next one.
  *
@@ -717,16 +720,29 @@ int iss_cnn_probs(iss_ctx* ctx, int net_id, const int32_t* win_row, int32_t n,
  * the pass size, and the shared-first-layer decision is taken on the live list, so a list with many dead windows may run the
  * per-window first layer where compute-then-mask shares it: the same values to float32 rounding), and a call without a dead window runs exactly as before.  Windows of finite values that do not normalise
  * (std = 0, overflow) stay in the list and are decided on the device as ever.  Which windows are dead is known on the host from
- * one byte per log-mel row (row_flags_kernel; iss_set_mspec scans its argument instead), fetched at the FIRST of these calls
- * after the resident features changed, with ONE wait for the stream: in every caller the stream then holds only the feature
- * kernels (iss_get_loge has just synchronised), so the asynchronous form still returns before its own work runs.  The
+ * one byte per log-mel row (row_flags_kernel; iss_set_mspec scans its argument instead).  iss_sidekit enqueues that kernel and its
+ * read-back behind the feature kernel, and the wait of iss_get_loge brings the bytes along with the log-energy: no further wait.
+ * Features that came another way have them fetched at the FIRST of these calls, with ONE wait for the stream.  The
  * precision guard probes the live list.  ISS_DIAG_NO_SKIP_DEAD restores compute-then-mask.  iss_cnn_dead_stats: windows
  * these calls were given, and how many of them were left out, since the context was created (0 left out under the switch). */
 int iss_cnn_probs_async(iss_ctx* ctx, int net_id, const int32_t* win_row, int32_t n,
                         float* probs_out /* n*out_dim */, uint8_t* finite_out /* n */, int64_t* ticket_out);
 int iss_cnn_dead_stats(iss_ctx* ctx, int64_t* windows, int64_t* dead);
-/* Block until the work of `ticket` (and everything enqueued before it) is complete; ticket < 0 = the whole stream. */
+/* Block until the work of `ticket` (and everything enqueued before it) is complete; ticket < 0 = the whole stream.  A wait for
+ * the newest ticket, or for the whole stream, retires every ticket given out so far. */
 int iss_wait(iss_ctx* ctx, int64_t ticket);
+/* Landings.  The result of an iss_cnn_probs_async call reaches probs_out / finite_out front to back.  When both arrays are
+ * page-locked (iss_host_alloc), every pass of the call (the workspace limit decides how many windows a pass holds) stores its rows
+ * straight into them -- they are device-visible; scatter_probs_kernel writes each element once, 0.5 where the window did not
+ * normalise -- and an event behind the pass says that its slots are there: its own windows' and the dead slots up to the next live
+ * window, which the call itself wrote before it returned.  No copy follows a pass or the call, and the values are those of the
+ * synchronous call.  With a pageable array the call gathers its result on the device and copies it out once, behind the last
+ * pass, one landing: a copy into pageable memory would hold the submitting thread.
+ * iss_wait_slots blocks until slots [0, upto) of call `ticket` are in the caller's arrays and reports in *landed_out how many
+ * slots are: >= min(upto, n), never less than an earlier answer for the ticket, n once the call is complete.  upto <= 0 does not
+ * block (hipEventQuery).  A ticket that iss_wait has retired, or that was never given out, answers 2^31 - 1: everything has
+ * landed.  Tickets are retired by iss_wait alone. */
+int iss_wait_slots(iss_ctx* ctx, int64_t ticket, int32_t upto, int32_t* landed_out);
 
 /* Generic batched forward on caller-supplied host input (n, in_h, in_w, in_c) f32 NHWC:
  * replaces vbx_segmenter.py:262-266 `OnnxBackendExtractor.get_embedding` (ResNet-101
