@@ -18,8 +18,10 @@ import pytest
 from inaspeechsegmenter_amd import keras_model as KM, segmenter as S, _native
 import topologies as TP
 from test_gpu_topologies import _mspec, _oracle_probs
+from test_conv_instantiation_ledger import LI, load_ledger
 
 pytestmark = pytest.mark.gpu
+_LEDGER = load_ledger()
 NNETS = int(os.environ.get('ISS_FUZZ_NNETS', '48'))
 BASE = int(os.environ.get('ISS_FUZZ_BASE', '9000'))
 FRAMES = int(os.environ.get('ISS_FUZZ_T', '700'))
@@ -84,6 +86,10 @@ def test_random_topology(ctx, k):
     probs, fin = ctx.cnn_probs(5, rows)
     insts = [i['kernel'] for i in ctx.prof_instances()]
     ctx.prof_enable(False)
+    # every conv launch reports an instantiation the ledger knows (tests/golden/conv_instantiations.json): a launcher that starts to
+    # report a name the ledger cannot parse, or an instantiation without a float64 case of its own, fails here
+    unknown = [n for n in insts if n.startswith('conv') and LI.canonical_of_profiler_name(n) not in _LEDGER]
+    assert not unknown, (k, unknown)
     err = np.abs(probs - ref).max()
     scat = np.sort(rng.integers(0, T - 68, 48)).astype(np.int32)
     p2, f2 = ctx.cnn_probs(5, scat)

@@ -119,7 +119,9 @@ SPECS = {
                   ('conv', 3, 3, 128), ('bn_relu',), ('maxpool', 2, 1)] + HEAD,
     'gap_head': [('conv', 4, 5, 64), ('bn_relu',), ('conv', 5, 3, 64), ('bn_relu',), ('maxpool', 2, 2),
                  ('conv', 3, 3, 128), ('bn_relu',), ('conv', 3, 3, 128), ('bn_relu',), ('gap',), ('dense', 128)],
-    # ---- round 5: every instantiation of the ring form (> 16 taps) and of the shared zero-padded first layer (FS) at least once
+    # ---- round 5: the ring form (> 16 taps) and the shared zero-padded first layer (FS), each shape at least once (EPI = 1 forms only;
+    # that EVERY compiled instantiation of them runs is enforced by tests/test_gpu_conv_instantiations.py over
+    # tests/golden/conv_instantiations.json)
     'conv1_same_conv2_same': [('conv', 4, 5, 64, 'same'), ('bn_relu',), ('conv', 5, 3, 64, 'same'), ('bn_relu',), ('maxpool', 2, 2),
                               ('conv', 3, 3, 128), ('bn_relu',), ('conv', 3, 3, 128), ('bn_relu',), ('maxpool', 2, 1)] + HEAD,
     'conv1_same3x3_avg': [('conv', 3, 3, 64, 'same'), ('bn_relu',), ('conv', 3, 3, 64), ('bn_relu',), ('avgpool', 2, 2),
