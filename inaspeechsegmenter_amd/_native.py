@@ -47,8 +47,11 @@ SPLIT = np.dtype([('dst_stride', '<i8'), ('sel_begin', '<i4'), ('sel_count', '<i
 MIXSET = np.dtype([('dst_stride', '<i8'), ('mix_begin', '<i4'), ('mix_count', '<i4')])
 MIX = np.dtype([('term_begin', '<i4'), ('term_count', '<i4'), ('divisor', '<f8')])
 MIX_TERM = np.dtype([('channel', '<i4'), ('reserved', '<i4'), ('weight', '<f8')])
+# iss_sched / iss_sched_run (include/iss.h, "Schedules"): the row beside a job row of the *_sched entry points, and the call's run rows
+SCHED = np.dtype([('run_begin', '<i4'), ('run_count', '<i4')])
+SCHED_RUN = np.dtype([('begin_frame', '<i8'), ('mix', '<i4'), ('reserved', '<i4')])
 # iss_survey_job (include/iss.h): a row of the survey entry points
-SET = np.dtype([('member_begin', '<i4'), ('member_count', '<i4')])                                       # iss_set, beside every job
+SET =np.dtype([('member_begin', '<i4'), ('member_count', '<i4')])                                       # iss_set, beside every job
 SET_MEMBER = np.dtype([('src_offset', '<i8'), ('frames', '<i8'), ('channels', '<i4'), ('reserved', '<i4')])   # iss_set_member
 SURVEY_JOB = np.dtype([('src_offset', '<i8'), ('frames_in', '<i8'), ('channels', '<i4'), ('format', '<i4'), ('full', '<f8')])
 # ISS_FLAC_* frame status codes -> reason
@@ -108,6 +111,30 @@ def _mix_rows(mixes, njobs):
     if sets.size != njobs:
         raise ValueError(f'{sets.size} mix sets for {njobs} jobs')
     return sets, rows, terms
+
+
+def _sched_rows(scheds, njobs):
+    """(SCHED rows, SCHED_RUN rows, MIX rows, MIX_TERM rows) for a *_sched entry point from one schedule per job: a
+    resample.Schedule, or a sequence of (begin_frame, mix) with mix a resample.Mix or None (the plain downmix: -1).  Equal mixes of
+    a call share a row.  A 4-tuple of arrays is handed on as given."""
+    if isinstance(scheds, tuple) and len(scheds) == 4 and isinstance(scheds[0], np.ndarray):
+        sc, runs, rows, terms = (np.ascontiguousarray(a, dtype=dt).reshape(-1) for a, dt in zip(scheds, (SCHED, SCHED_RUN, MIX, MIX_TERM)))
+    else:
+        sc, runs, rows, terms, seen = np.zeros(len(scheds), dtype=SCHED), [], [], [], {}
+        for k, s in enumerate(scheds):
+            mine = list(s)
+            sc[k] = (len(runs), len(mine))
+            for begin, m in mine:
+                if m is not None and m not in seen:
+                    seen[m] = len(rows)
+                    rows.append((len(terms), len(m.terms), float(m.divisor)))
+                    terms.extend((int(ch), 0, float(w)) for ch, w in m.terms)
+                runs.append((int(begin), -1 if m is None else seen[m], 0))
+        runs = np.array(runs, dtype=SCHED_RUN).reshape(-1)
+        rows, terms = np.array(rows, dtype=MIX).reshape(-1), np.array(terms, dtype=MIX_TERM).reshape(-1)
+    if sc.size != njobs:
+        raise ValueError(f'{sc.size} schedules for {njobs} jobs')
+    return sc, runs, rows, terms
 
 
 def _set_rows(jb, members):
@@ -187,6 +214,12 @@ def lib():
         'iss_msadpcm_decode_mix': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, i64, pi32, vp, vp, i64, vp, i64]),
         'iss_staged_payload': (C.c_int, [vp, i32, pi64]),
         'iss_resample_staged_mix': (C.c_int, [vp, i32, i64, vp, vp, i32, i64, vp, vp, i64, vp, i64]),
+        'iss_resample_pcm16_sched': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, vp, vp, i64, vp, i64, vp, i64]),
+        'iss_resample_staged_sched': (C.c_int, [vp, i32, i64, vp, vp, i32, i64, vp, vp, i64, vp, i64, vp, i64]),
+        'iss_survey_blocks': (C.c_int, [vp, vp, i64, vp, i32, pi32, vp, vp]),
+        'iss_flac_survey_blocks': (C.c_int, [vp, vp, i32, pi32, vp, vp]),
+        'iss_adpcm_survey_blocks': (C.c_int, [vp, vp, i32, pi32, vp, vp]),
+        'iss_msadpcm_survey_blocks': (C.c_int, [vp, vp, i32, pi32, vp, vp]),
         'iss_upload_stats': (C.c_int, [vp, pi64, pi64]),
         'iss_resample_pcm16_set': (C.c_int, [vp, vp, i64, vp, i32, i64, vp, vp, i64, vp, vp, i64, vp, i64]),
         'iss_survey_set': (C.c_int, [vp, vp, i64, vp, i32, vp, vp, i64, vp]),
@@ -546,6 +579,36 @@ class Context:
             jb.size, int(n_signal), C.c_void_p(sets.ctypes.data), C.c_void_p(rows.ctypes.data), rows.size,
             C.c_void_p(terms.ctypes.data), terms.size), 'iss_resample_staged_mix')
 
+    # ---- schedules (iss_resample_*_sched): a downmix that differs from one stretch of a file to the next
+    @staticmethod
+    def _sched_args(scheds, njobs):
+        sc, runs, rows, terms = tables = _sched_rows(scheds, njobs)
+        return tables, (C.c_void_p(sc.ctypes.data), C.c_void_p(runs.ctypes.data), runs.size, C.c_void_p(rows.ctypes.data), rows.size,
+                        C.c_void_p(terms.ctypes.data), terms.size)
+
+    def resample_sched(self, src, jobs, scheds, n_signal=-1, windows=None):
+        """iss_resample_pcm16_sched: `resample` with one schedule per job (a resample.Schedule, or [(begin_frame, mix or None)]) in
+        place of splits or mixes: every job writes one signal, frame j of its source mixed by the mix of the run that governs it.
+        One H2D copy, one launch.  windows: refused by the library (a schedule governs whole sources)."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        jb = np.ascontiguousarray(np.array(jobs, dtype=RS_JOB).reshape(-1))
+        wn = None if windows is None else _window_rows(windows, jb.size)
+        keep, args = self._sched_args(scheds, jb.size)
+        self._ck(self._L.iss_resample_pcm16_sched(
+            self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data), None if wn is None else C.c_void_p(wn.ctypes.data),
+            jb.size, int(n_signal), *args), 'iss_resample_pcm16_sched')
+        self._keep_rs = src         # the async H2D copy reads it until the next sync
+
+    def resample_staged_sched(self, coder, payload, jobs, scheds, n_signal=-1, windows=None):
+        """iss_resample_staged_sched: `resample_sched` over the bytes of payload `payload` of origin `coder`, as
+        `resample_staged` reads them; nothing is uploaded but rows."""
+        jb = np.ascontiguousarray(np.array(jobs, dtype=RS_JOB).reshape(-1))
+        wn = None if windows is None else _window_rows(windows, jb.size)
+        keep, args = self._sched_args(scheds, jb.size)
+        self._ck(self._L.iss_resample_staged_sched(
+            self._h, STAGED_ORIGIN[coder], int(payload), C.c_void_p(jb.ctypes.data), None if wn is None else C.c_void_p(wn.ctypes.data),
+            jb.size, int(n_signal), *args), 'iss_resample_staged_sched')
+
     # ---- file sets (iss_*_set): one file per channel or group of channels, read as the interleaved file they stand for
     def resample_set(self, src, jobs, members, n_signal=-1, mixes=None):
         """iss_resample_pcm16_set: `resample` with `mixes` for file sets, whole sources only.  src = the members' stored bytes,
@@ -708,6 +771,35 @@ class Context:
         else:
             self._ck(getattr(self._L, f'iss_{coder}_survey')(self._h, *tail), f'iss_{coder}_survey')
         return self._survey_fields(jb, wn, out)
+
+    def survey_blocks(self, src, jobs, block_chunks, coder=None):
+        """iss_survey_blocks (coder: iss_<coder>_survey_blocks, src None): `survey` without windows, and the same figures per
+        block of block_chunks[k] chunks of job k's frames (include/iss.h, "Survey blocks") -> (one resample.SurveyFields per job,
+        per job the list of its blocks' SurveyFields); one H2D copy, one survey launch, valid on return."""
+        from .resample import SURVEY_CHUNK, SURVEY_PAIR_CHANNELS, SurveyFields
+        jb = np.ascontiguousarray(np.array(jobs, dtype=SURVEY_JOB).reshape(-1))
+        ks = np.ascontiguousarray(np.array(block_chunks, dtype=np.int32).reshape(-1))
+        if ks.size != jb.size:
+            raise ValueError(f'{ks.size} block sizes for {jb.size} jobs')
+        out = self._survey_out(jb)
+        chs, ns = [int(c) for c in jb['channels']], [int(n) for n in jb['frames_in']]
+        width = [6 * c + (c * (c - 1) // 2 if c <= SURVEY_PAIR_CHANNELS else 0) for c in chs]
+        nblk = [-(-(-(-n // SURVEY_CHUNK)) // max(int(k), 1)) if n > 0 else 0 for n, k in zip(ns, ks)]
+        blk = np.zeros(max(sum(w * b for w, b in zip(width, nblk)), 1), dtype=np.float64)
+        tail = (C.c_void_p(jb.ctypes.data), jb.size, _ptr(ks, C.c_int32), C.c_void_p(out.ctypes.data), C.c_void_p(blk.ctypes.data))
+        if coder is None:
+            src = np.ascontiguousarray(src, dtype=np.uint8)
+            self._ck(self._L.iss_survey_blocks(self._h, C.c_void_p(src.ctypes.data), src.size, *tail), 'iss_survey_blocks')
+        else:
+            self._ck(getattr(self._L, f'iss_{coder}_survey_blocks')(self._h, *tail), f'iss_{coder}_survey_blocks')
+        blocks, pos = [], 0
+        for c, w, n, k, nb in zip(chs, width, ns, ks, nblk):
+            per = int(k) * SURVEY_CHUNK
+            rows = np.zeros(nb, dtype=SURVEY_JOB)
+            rows['channels'], rows['frames_in'] = c, [min(per, n - b * per) for b in range(nb)]
+            blocks.append(self._survey_fields(rows, None, blk[pos:pos + nb * w]))
+            pos += nb * w
+        return self._survey_fields(jb, None, out), blocks
 
     def survey_set(self, src, jobs, members):
         """iss_survey_set: iss_survey (without windows) for file sets.  src = the members' stored bytes, jobs = rows of

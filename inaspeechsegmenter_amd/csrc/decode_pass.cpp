@@ -70,7 +70,7 @@ int IssDecodePass::commit(IssCodec* dec) {
     IssMixTables rmix{};                                   // the caller's mix and term rows, the sets beside rjobs
     if (jmix) { rmix = *jmix; rmix.sets = rmixsets.data(); }
     int rc = iss_resample_plan(c, rjobs.data(), windowed ? rwins.data() : nullptr, (int32_t)rjobs.size(), stage, nsig, ranges,
-                               who, plan, split ? rsplits.data() : nullptr, sel, nsel, jmix ? &rmix : nullptr, jset);
+                               who, plan, split ? rsplits.data() : nullptr, sel, nsel, jmix ? &rmix : nullptr, jset, jsched);
     if (rc) return rc;
     if (n_signal >= 0) {                                   // a signal of its own, zero wherever no job writes
         if ((rc = iss_reserve(c, c->sig, (size_t)nsig * 2 + 16))) return rc;

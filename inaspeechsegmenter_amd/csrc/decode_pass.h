@@ -25,6 +25,7 @@ struct IssDecodePass {
     const IssMixTables* jmix = nullptr;                       // a mix entry point's tables, `sets` one per JOB (NULL: not one) ...
     std::vector<iss_mixset> rmixsets;                         // ... the sets handed on beside rjobs (no mixes for a job without any)
     const IssSetTables* jset = nullptr;                       // a set entry point's tables, `sets` one per job = per row of rjobs (NULL: not one)
+    const IssSchedTables* jsched = nullptr;                   // a scheduled entry point's tables, `scheds` one per row of rjobs (NULL: not one)
     std::vector<int64_t> stage_off, stage_bytes;              // per job (-1: not staged)
     std::vector<int32_t> stage_esz;                           // per job: bytes of a staged sample
     int64_t stage = 0;                                        // bytes those rows read from: the staging buffer so far

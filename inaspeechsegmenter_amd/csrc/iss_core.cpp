@@ -77,7 +77,7 @@ extern "C" void iss_destroy(iss_ctx* c) {
     void* singles[] = {c->d_window, c->d_melw, c->d_mellim, c->d_tw, c->d_vbx_window, c->d_vbx_melw, c->d_vbx_mellim};
     for (void* p : singles) if (p) (void)hipFree(p);
     DevBuf* bufs[] = {&c->sig, &c->mspec, &c->loge, &c->d_winrow, &c->d_stats, &c->d_finite, &c->d_out, &c->d_in, &c->raw1, &c->d_rowflag, &c->d_lfinite,
-                      &c->vbx_sig, &c->vbx_dither, &c->vbx_fb, &c->vbx_out, &c->vbx_meta, &c->rs_src, &c->rs_jobs, &c->sv_src, &c->sv_jobs, &c->sv_ws, &c->sv_res,
+                      &c->vbx_sig, &c->vbx_dither, &c->vbx_fb, &c->vbx_out, &c->vbx_meta, &c->rs_src, &c->rs_jobs, &c->sv_src, &c->sv_jobs, &c->sv_ws, &c->sv_res, &c->sv_blk,
                       &c->flac.src, &c->flac.rows, &c->flac.status, &c->flac.stage,
                       &c->adpcm.src, &c->adpcm.rows, &c->adpcm.status, &c->adpcm.stage,
                       &c->msadpcm.src, &c->msadpcm.rows, &c->msadpcm.status, &c->msadpcm.stage};
@@ -116,7 +116,7 @@ extern "C" int iss_scribble(iss_ctx* c, uint32_t word) {
     ISS_HIP(c, hipSetDevice(c->device));
     ISS_HIP(c, hipStreamSynchronize(c->stream));
     std::vector<DevBuf*> bufs = {&c->raw1, &c->d_stats, &c->d_finite, &c->d_lfinite, &c->d_out, &c->d_in, &c->d_winrow, &c->d_rowflag,
-                                 &c->vbx_fb, &c->vbx_meta, &c->vbx_sig, &c->rs_src, &c->rs_jobs, &c->sv_src, &c->sv_jobs, &c->sv_ws, &c->sv_res,
+                                 &c->vbx_fb, &c->vbx_meta, &c->vbx_sig, &c->rs_src, &c->rs_jobs, &c->sv_src, &c->sv_jobs, &c->sv_ws, &c->sv_res, &c->sv_blk,
                                  &c->flac.src, &c->flac.rows, &c->flac.status, &c->flac.stage,
                                  &c->adpcm.src, &c->adpcm.rows, &c->adpcm.status, &c->adpcm.stage,
                                  &c->msadpcm.src, &c->msadpcm.rows, &c->msadpcm.status, &c->msadpcm.stage};

@@ -104,7 +104,7 @@ struct iss_ctx {
     IssCodec flac{"flac"}, adpcm{"adpcm"}, msadpcm{"msadpcm"};
 
     // channel survey (survey.hip): uploaded bytes, job rows, per-chunk partial rows, result rows of the last call
-    DevBuf sv_src, sv_jobs, sv_ws, sv_res;
+    DevBuf sv_src, sv_jobs, sv_ws, sv_res, sv_blk;   // sv_blk: the block rows of a *_survey_blocks call
     IssCounters sv_count;                 // survey_kernel launches, jobs
     // what a later call may resample without uploading it again (iss_resample_staged_mix): the payload of the last iss_survey in
     // sv_src, with the rows that describe it; a codec's is its IssCodec::held.  Ids count up over all origins of the context
@@ -237,6 +237,14 @@ struct RsTermDev { int32_t channel, pad; double weight; };
 // `frames` on
 struct RsSetTermDev { int64_t off, frames; double weight; int32_t step, pad; };
 static_assert(sizeof(RsMixRow) == 16 && sizeof(RsTermDev) == 16 && sizeof(RsSetTermDev) == 32, "one array of 16-byte rows");
+// a scheduled call (include/iss.h, "Schedules"): a mix call whose every job writes one row; RsMixDev.mix_begin of job k names its
+// RsSchedDev among the 16-byte rows -- mix rows, term rows, one RsSchedDev per job, then the RsRunDev rows --, every index counted
+// from the first mix row.  run_begin: the job's first RsRunDev; RsRunDev.mix: the RsMixRow the run's frames are mixed by
+struct RsSchedDev { int32_t run_begin, run_count; int64_t pad; };
+struct RsRunDev { int64_t begin; int32_t mix, pad; };
+static_assert(sizeof(RsSchedDev) == 16 && sizeof(RsRunDev) == 16, "one array of 16-byte rows");
+// the two tables of a *_sched entry point; `scheds` one per job
+struct IssSchedTables { const iss_sched* scheds; const iss_sched_run* runs; int64_t nruns; };
 // the three tables of a *_mix entry point (include/iss.h); `sets` one per job
 struct IssMixTables { const iss_mixset* sets; const iss_mix* mixes; int64_t nmixes; const iss_mix_term* terms; int64_t nterms; };
 // the two tables of a *_set entry point; `sets` one per job
@@ -251,16 +259,21 @@ struct IssRsPlan {
     std::vector<RsTermDev> terms;         // ... and the term rows those point into
     std::vector<RsSetTermDev> sterms;     // a set call: its term rows in the place of `terms`, and `set` says so
     bool set = false;
+    std::vector<RsSchedDev> scheds;       // a scheduled call: one per job, and `sched` says so ...
+    std::vector<RsRunDev> runs;           // ... and every job's runs, their mixes resolved to rows of `mixes`
+    bool sched = false;
     int64_t tiles = 0, lds = 0;
 };
 // `ranges`: destination ranges of other writers of the same call, checked for overlap with the jobs' (error texts start with `who`)
 // `wins`: NULL, or a window beside every job (include/iss.h);  `splits`: NULL, or a split beside every job, into sel[0, nsel);
 // `mix`: NULL, or the tables of a mix call with a mix set beside every job (never together with `splits`)
 // `set`: NULL, or the tables of a set call with a set beside every job (with `mix`, without `wins`): the jobs read their members
+// `sched`: NULL, or the tables of a scheduled call with a schedule beside every job (with `mix`, whose sets are not read; without
+// `wins`, `splits`, `set`)
 int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes, int64_t nsig,
                       std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan,
                       const iss_split* splits = nullptr, const int32_t* sel = nullptr, int64_t nsel = 0,
-                      const IssMixTables* mix = nullptr, const IssSetTables* set = nullptr);
+                      const IssMixTables* mix = nullptr, const IssSetTables* set = nullptr, const IssSchedTables* sched = nullptr);
 int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& plan);
 
 // implemented in the .hip files

@@ -45,6 +45,13 @@
 // job without mixes as the mix of all its channels (w = 1, d = their count: the downmix above, to the bit), so the workgroup
 // only stages differently: stage_set_mixes, (mix, frame) flattened over the threads with the frame running fastest -- a wave
 // reads consecutive frames of one member --, a sample past the end of a member 0.0.  Step 3 is the code above.
+//
+// Schedules (include/iss.h, iss_sched): SCHED = true is one more pair, MIX without windows, for calls that carry a schedule beside
+// every job: ONE output row per job, whose staged frame j is mixed by the mix of the run that governs j.  The workgroup finds the
+// runs of the first and the last frame of its span once -- block-uniform values, kept in scalar registers -- and where they are one
+// run stages exactly as stage_mixes stages one mix; else every frame searches its run between those two (stage_sched).  The
+// planner writes a run without a mix as the mix of all the job's channels (w = 1, d = their count), as the set planner does.
+// Table: job rows, mix-set rows (mix_begin: the job's RsSchedDev), then 16-byte rows: mix rows, term rows, RsSchedDev, RsRunDev.
 #include "decode_pass.h"
 #include "rs_readers.h"      // to_f64, the Ld* readers, stage_channels: shared with survey.hip
 #include <algorithm>
@@ -113,13 +120,67 @@ __device__ __forceinline__ void stage_mixes(const uint8_t* __restrict__ src, int
     }
 }
 
+// the last of the run rows runs[lo .. hi] that begins at or before frame j (runs[lo] does)
+__device__ __forceinline__ int run_of(const RsRunDev* __restrict__ runs, int lo, int hi, int64_t j) {
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (runs[mid].begin <= j) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// frames s0 .. s0+len-1 of a scheduled job (include/iss.h, "Schedules"): span[.] = the frame mixed by the mix of its run.  `rows`:
+// the call's 16-byte rows, `sched` the job's row among them.  ra, rb: the runs of the first and the last frame of the file in the
+// span, the same for every lane.  One run: stage_mixes for that mix.  Else each frame finds its run in [ra, rb]
+template <typename L>
+__device__ __forceinline__ void stage_sched(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
+                                            double* __restrict__ span, const RsSchedDev* __restrict__ sched,
+                                            const RsTermDev* __restrict__ rows) {
+    using T = typename L::type;
+    const RsSchedDev S = *sched;
+    const RsRunDev* runs = reinterpret_cast<const RsRunDev*>(rows) + S.run_begin;
+    const RsMixRow* mixes = reinterpret_cast<const RsMixRow*>(rows);
+    const int64_t ja = max(s0, (int64_t)0), jb = min(s0 + len, n_in) - 1;
+    int ra = 0, rb = 0;
+    if (ja <= jb) {
+        ra = run_of(runs, 0, S.run_count - 1, ja);
+        rb = run_of(runs, ra, S.run_count - 1, jb);
+    }
+    ra = __builtin_amdgcn_readfirstlane(ra);
+    rb = __builtin_amdgcn_readfirstlane(rb);
+    if (ra == rb) {
+        stage_mixes<L, false>(src, n_in, ch, s0, len, span, 0, 1, mixes + runs[ra].mix, rows, RsWinDev{});
+        return;
+    }
+    const T* p = reinterpret_cast<const T*>(src);
+    for (int k = threadIdx.x; k < len; k += RS_THREADS) {
+        const int64_t j = s0 + k;
+        double v = 0.0;
+        if (j >= 0 && j < n_in) {
+            const T* f = p + j * ch;
+            const RsMixRow M = mixes[runs[run_of(runs, ra, rb, j)].mix];
+            const RsTermDev* t = rows + M.term_begin;
+            v = __dmul_rn(t[0].weight, L::get(f + t[0].channel));
+            for (int n = 1; n < M.term_count; ++n) v = __dadd_rn(v, __dmul_rn(t[n].weight, L::get(f + t[n].channel)));
+            v = __ddiv_rn(v, M.divisor);
+        }
+        span[k] = v;
+    }
+}
+
 // what a workgroup of a SPLIT launch stages: the downmix (gc == 0), or channels [c0, c0 + gc) of its job's selection;
 // of a MIX launch: the downmix, or the gc mixes from `mix` on (rows of the 16-byte table `rows`, which holds their terms too)
+// of a SCHED launch: one row by the job's schedule, the RsSchedDev `mix` points at (a 16-byte row of `rows`, as the mixes its
+// runs name are)
 struct RsGroup { int64_t dst_stride; int stride, c0, gc; const int32_t* sel; const RsMixRow* mix; const RsTermDev* rows; };
 
-template <typename L, bool WIN, bool SPLIT, bool MIX, bool SET>
+template <typename L, bool WIN, bool SPLIT, bool MIX, bool SET, bool SCHED = false>
 __device__ __forceinline__ void stage(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
                                       double* __restrict__ span, const RsWinDev& W, const RsGroup& G) {
+    if constexpr (SCHED) {                                 // every job of a scheduled call has a schedule
+        stage_sched<L>(src, n_in, ch, s0, len, span, reinterpret_cast<const RsSchedDev*>(G.mix), G.rows);
+        return;
+    }
     if constexpr (SET) {                                   // every job of a set call has mixes: the planner wrote its downmix as one
         stage_set_mixes<L>(src, n_in, s0, len, span, G.stride, G.gc, G.mix, G.rows);
         return;
@@ -157,12 +218,15 @@ __device__ __forceinline__ void compute_tile(const RsJobDev& J, const double* __
 // that follow the rows.  MIX = true (never with SPLIT) reads the mix-set table and the mix and term rows that follow it.
 // SET = true (only with MIX, never with WIN; include/iss.h, "File sets") is the pair for calls whose jobs read the members of a
 // file set: the tables are a mix call's, the term rows RsSetTermDev in the place of RsTermDev, and stage_set_mixes reads them.
-#define RS_STAGE(L) stage<L, WIN, SPLIT, MIX, SET>(s, J.n_in, J.ch, s0, len, span, W, G)
-template <bool EXT, bool WIN, bool SPLIT, bool MIX = false, bool SET = false>
+// SCHED = true (only with MIX, never with WIN or SET; include/iss.h, "Schedules") is the pair for calls whose jobs carry a
+// schedule: the tables are a mix call's with the schedule and run rows behind the term rows, and stage_sched reads them.
+#define RS_STAGE(L) stage<L, WIN, SPLIT, MIX, SET, SCHED>(s, J.n_in, J.ch, s0, len, span, W, G)
+template <bool EXT, bool WIN, bool SPLIT, bool MIX = false, bool SET = false, bool SCHED = false>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __restrict__ src, const RsJobDev* __restrict__ jobs,
                                                               int njobs, int16_t* __restrict__ dst) {
     static_assert(!(SPLIT && MIX), "a call carries split rows or mix-set rows");
     static_assert(!SET || (MIX && !WIN), "a set call is a mix call over whole sources");
+    static_assert(!SCHED || (MIX && !WIN && !SET), "a scheduled call is a mix call over whole interleaved sources");
     extern __shared__ __attribute__((aligned(16))) double rs_smem[];
     const int64_t b = blockIdx.x;
     int lo = 0, hi = njobs - 1;                                             // last job whose tile_base <= b
@@ -195,7 +259,11 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __r
         const RsMixDev* sets = reinterpret_cast<const RsMixDev*>(after);
         const RsMixRow* rows = reinterpret_cast<const RsMixRow*>(sets + njobs);          // the mix rows and the term rows follow that
         const RsMixDev S = sets[lo];
-        if (S.mix_count > 0) {
+        if constexpr (SCHED) {                                                       // one row: mix_begin names the job's schedule row
+            G.dst_stride = S.dst_stride; G.stride = S.stride; G.gc = 1;
+            G.rows = reinterpret_cast<const RsTermDev*>(rows);
+            G.mix = rows + S.mix_begin;
+        } else if (S.mix_count > 0) {
             const int g = (int)(t / S.ntiles);
             t -= g * S.ntiles;
             G.dst_stride = S.dst_stride; G.stride = S.stride; G.c0 = g * S.group; G.gc = min(S.group, S.mix_count - G.c0);
@@ -300,9 +368,27 @@ extern "C" int iss_resample_filter(iss_ctx* c, int32_t up, int32_t down, const d
 
 static int64_t floor_div_host(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }      // b > 0
 
+// mix q of job k (row `m` of the call's mixes) against the call's term rows and the job's channels: ISS_OK, or the refusal
+static int check_mix(iss_ctx* c, const char* who, int32_t k, int32_t q, const iss_mix& m, const IssMixTables& mix, int32_t channels) {
+    if (m.term_count < 1 || m.term_begin < 0 || m.term_begin > mix.nterms - m.term_count)
+        return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: term rows [%d, +%d) outside the %lld of the call, or no "
+                        "term", who, k, q, m.term_begin, m.term_count, (long long)mix.nterms);
+    if (!std::isfinite(m.divisor) || m.divisor == 0.0)
+        return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: divisor %g", who, k, q, m.divisor);
+    for (int32_t n = 0; n < m.term_count; ++n) {
+        const iss_mix_term& t = mix.terms[m.term_begin + n];
+        if (t.channel < 0 || t.channel >= channels)
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: term %d: channel %d of %d", who, k, q, n, t.channel, channels);
+        if (!std::isfinite(t.weight))
+            return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: term %d: weight %g", who, k, q, n, t.weight);
+    }
+    return ISS_OK;
+}
+
 int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes,
                       int64_t nsig, std::vector<std::pair<int64_t, int64_t>> ranges, const char* who, IssRsPlan& plan,
-                      const iss_split* splits, const int32_t* sel, int64_t nsel, const IssMixTables* mix, const IssSetTables* set) {
+                      const iss_split* splits, const int32_t* sel, int64_t nsel, const IssMixTables* mix, const IssSetTables* set,
+                      const IssSchedTables* sched) {
     // validate every job, build the device descriptors and the tile prefix sum
     std::vector<RsJobDev>& dj = plan.dj;
     dj.assign((size_t)njobs, RsJobDev{});
@@ -325,7 +411,16 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
     for (int32_t k = 0; set && k < njobs; ++k) set_mixes += std::max(mix->sets[k].mix_count, 1);
     if (set_mixes > 0x3fffffffLL) return iss_fail(c, ISS_EINVAL, "%s: %lld mixes in one call", who, (long long)set_mixes);
     std::vector<SetChanDev> chans;                         // the channels of the job at hand
-    if (mix && !set) {                                     // the device's rows: the mixes, then the terms they count from there
+    plan.scheds.clear();
+    plan.runs.clear();
+    plan.sched = sched != nullptr;
+    if (sched && (!mix || wins || splits || set || (njobs > 0 && !sched->scheds) || sched->nruns < 0 || sched->nruns > 0x3fffffffLL ||
+                  (sched->nruns > 0 && !sched->runs)))
+        return iss_fail(c, ISS_EINVAL, "%s: bad schedule tables", who);
+    std::vector<int32_t> mix_seen;                         // a scheduled call: the last job whose channels mix q was checked against
+    std::vector<char> has_none;                            // ... and the jobs with a run that names no mix
+    if (sched) { mix_seen.assign((size_t)mix->nmixes, -1); has_none.assign((size_t)njobs, 0); }
+    if (mix && !set && !sched) {                                     // the device's rows: the mixes, then the terms they count from there
         plan.mixes.resize((size_t)mix->nmixes);
         plan.terms.resize((size_t)mix->nterms);
         for (int64_t q = 0; q < mix->nmixes; ++q)
@@ -421,28 +516,40 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
             groups = (sp.sel_count + group - 1) / group;
             plan.ds[(size_t)k] = RsSplitDev{sp.dst_stride, (nout + tile - 1) / tile, sp.sel_begin, sp.sel_count, (int32_t)group,
                                             (int32_t)stride, ident ? 1 : 0, 0};
+        } else if (sched) {
+            // a schedule: its run rows, every mix a run names against this job's channels; one output row
+            const iss_sched& sc = sched->scheds[k];
+            if (sc.run_count < 1 || sc.run_count > (1 << 20) || sc.run_begin < 0 || sc.run_begin > sched->nruns - sc.run_count)
+                return iss_fail(c, ISS_EINVAL, "%s: job %d: run rows [%d, +%d) outside the %lld of the call, or not 1 .. 2^20 of "
+                                "them", who, k, sc.run_begin, sc.run_count, (long long)sched->nruns);
+            for (int32_t q = 0; q < sc.run_count; ++q) {
+                const iss_sched_run& r = sched->runs[sc.run_begin + q];
+                if (q == 0 && r.begin_frame != 0)
+                    return iss_fail(c, ISS_EINVAL, "%s: job %d: run 0 begins at frame %lld, not 0", who, k, (long long)r.begin_frame);
+                if (q > 0 && r.begin_frame <= sched->runs[sc.run_begin + q - 1].begin_frame)
+                    return iss_fail(c, ISS_EINVAL, "%s: job %d: run %d begins at frame %lld, run %d at %lld: begins ascend strictly",
+                                    who, k, q, (long long)r.begin_frame, q - 1, (long long)sched->runs[sc.run_begin + q - 1].begin_frame);
+                if (r.mix < -1 || r.mix >= mix->nmixes)
+                    return iss_fail(c, ISS_EINVAL, "%s: job %d: run %d: mix %d outside [-1, %lld)", who, k, q, r.mix,
+                                    (long long)mix->nmixes);
+                if (r.mix < 0) has_none[(size_t)k] = 1;
+                else if (mix_seen[(size_t)r.mix] != k) {
+                    if (int rc = check_mix(c, who, k, r.mix, mix->mixes[r.mix], *mix, J.channels)) return rc;
+                    mix_seen[(size_t)r.mix] = k;
+                }
+            }
+            int64_t group, stride;
+            split_geometry(f, 1, tile, group, stride);
+            span_b = group * stride * 8;
+            plan.dm[(size_t)k] = RsMixDev{nout, (nout + tile - 1) / tile, 0, 1, (int32_t)group, (int32_t)stride};      // (mix_begin: below)
         } else if (mix && mix->sets[k].mix_count != 0) {
             // mixes: their rows, every term of every one of them, and one destination range per mix
             const iss_mixset& ms = mix->sets[k];
             if (ms.mix_count < 0 || ms.mix_begin < 0 || ms.mix_begin > mix->nmixes - ms.mix_count)
                 return iss_fail(c, ISS_EINVAL, "%s: job %d: mix rows [%d, +%d) outside the %lld of the call", who, k, ms.mix_begin,
                                 ms.mix_count, (long long)mix->nmixes);
-            for (int32_t q = 0; q < ms.mix_count; ++q) {
-                const iss_mix& m = mix->mixes[ms.mix_begin + q];
-                if (m.term_count < 1 || m.term_begin < 0 || m.term_begin > mix->nterms - m.term_count)
-                    return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: term rows [%d, +%d) outside the %lld of the call, or no "
-                                    "term", who, k, q, m.term_begin, m.term_count, (long long)mix->nterms);
-                if (!std::isfinite(m.divisor) || m.divisor == 0.0)
-                    return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: divisor %g", who, k, q, m.divisor);
-                for (int32_t n = 0; n < m.term_count; ++n) {
-                    const iss_mix_term& t = mix->terms[m.term_begin + n];
-                    if (t.channel < 0 || t.channel >= J.channels)
-                        return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: term %d: channel %d of %d", who, k, q, n, t.channel,
-                                        J.channels);
-                    if (!std::isfinite(t.weight))
-                        return iss_fail(c, ISS_EINVAL, "%s: job %d: mix %d: term %d: weight %g", who, k, q, n, t.weight);
-                }
-            }
+            for (int32_t q = 0; q < ms.mix_count; ++q)
+                if (int rc = check_mix(c, who, k, q, mix->mixes[ms.mix_begin + q], *mix, J.channels)) return rc;
             if (ms.dst_stride < nout || ms.dst_stride > (int64_t(1) << 40))
                 return iss_fail(c, ISS_EINVAL, "%s: job %d: dst_stride %lld below the %lld outputs of a mix", who, k,
                                 (long long)ms.dst_stride, (long long)nout);
@@ -507,6 +614,37 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
                             (long long)ranges[k - 1].first, (long long)ranges[k - 1].second, (long long)ranges[k].first,
                             (long long)ranges[k].second);
     if (tiles > 0x7fffffffLL) return iss_fail(c, ISS_EINVAL, "%s: %lld tiles in one call", who, (long long)tiles);
+    if (sched) {
+        // the 16-byte rows: the call's mixes and one all-channel mix per job with a run that names none (w = 1, d = its channels:
+        // the plain downmix, to the bit), their terms, one RsSchedDev per job, every job's runs -- indices from the first mix row
+        int64_t nmix = mix->nmixes, nterm = mix->nterms, nrun = 0;
+        for (int32_t k = 0; k < njobs; ++k) {
+            if (has_none[(size_t)k]) { nmix += 1; nterm += jobs[k].channels; }
+            nrun += sched->scheds[k].run_count;
+        }
+        if (nmix + nterm + njobs + nrun > 0x7fffffffLL)
+            return iss_fail(c, ISS_EINVAL, "%s: %lld rows of mixes, terms and runs in one call", who, (long long)(nmix + nterm + njobs + nrun));
+        plan.mixes.reserve((size_t)nmix); plan.terms.reserve((size_t)nterm); plan.runs.reserve((size_t)nrun);
+        for (int64_t q = 0; q < mix->nmixes; ++q)
+            plan.mixes.push_back(RsMixRow{(int32_t)((int64_t)mix->mixes[q].term_begin + nmix), mix->mixes[q].term_count,
+                                          mix->mixes[q].divisor});        // (a row no run names is never read, nor checked)
+        for (int64_t q = 0; q < mix->nterms; ++q) plan.terms.push_back(RsTermDev{mix->terms[q].channel, 0, mix->terms[q].weight});
+        for (int32_t k = 0; k < njobs; ++k) {
+            const iss_sched& sc = sched->scheds[k];
+            int32_t none = -1;
+            if (has_none[(size_t)k]) {
+                none = (int32_t)plan.mixes.size();
+                plan.mixes.push_back(RsMixRow{(int32_t)(nmix + (int64_t)plan.terms.size()), jobs[k].channels, (double)jobs[k].channels});
+                for (int32_t ch = 0; ch < jobs[k].channels; ++ch) plan.terms.push_back(RsTermDev{ch, 0, 1.0});
+            }
+            plan.scheds.push_back(RsSchedDev{(int32_t)(nmix + nterm + njobs + (int64_t)plan.runs.size()), sc.run_count, 0});
+            for (int32_t q = 0; q < sc.run_count; ++q) {
+                const iss_sched_run& r = sched->runs[sc.run_begin + q];
+                plan.runs.push_back(RsRunDev{r.begin_frame, r.mix < 0 ? none : r.mix, 0});
+            }
+            plan.dm[(size_t)k].mix_begin = (int32_t)(nmix + nterm + k);
+        }
+    }
     plan.tiles = tiles;
     plan.lds = lds;
     return ISS_OK;
@@ -521,12 +659,15 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
         const size_t nj = dj.size() * sizeof(RsJobDev), nw = win ? dj.size() * sizeof(RsWinDev) : 0, nm = dj.size() * sizeof(RsMixDev);
         const size_t nr = plan.mixes.size() * sizeof(RsMixRow);         // (a set call: its own term rows in the place of `terms`)
         const size_t nt = plan.set ? plan.sterms.size() * sizeof(RsSetTermDev) : plan.terms.size() * sizeof(RsTermDev);
-        std::vector<uint8_t> rows(nj + nw + nm + std::max<size_t>(nr + nt, 16));
+        const size_t nc = plan.scheds.size() * sizeof(RsSchedDev), nu = plan.runs.size() * sizeof(RsRunDev);      // (a scheduled call)
+        std::vector<uint8_t> rows(nj + nw + nm + std::max<size_t>(nr + nt, 16) + nc + nu);
         memcpy(rows.data(), dj.data(), nj);
         if (win) memcpy(rows.data() + nj, plan.dw.data(), nw);
         memcpy(rows.data() + nj + nw, plan.dm.data(), nm);
         if (nr) memcpy(rows.data() + nj + nw + nm, plan.mixes.data(), nr);
         if (nt) memcpy(rows.data() + nj + nw + nm + nr, plan.set ? (const void*)plan.sterms.data() : (const void*)plan.terms.data(), nt);
+        if (nc) memcpy(rows.data() + nj + nw + nm + nr + nt, plan.scheds.data(), nc);
+        if (nu) memcpy(rows.data() + nj + nw + nm + nr + nt + nc, plan.runs.data(), nu);
         rc = iss_upload_rows(c, c->rs_jobs, rows.data(), rows.size());
     } else if (split) {                                       // one table: the jobs, (their windows,) their splits, the channel selections
         const size_t nj = dj.size() * sizeof(RsJobDev), nw = win ? dj.size() * sizeof(RsWinDev) : 0, ns = dj.size() * sizeof(RsSplitDev);
@@ -547,7 +688,8 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     if (rc) return rc;
     bool ext = false;                                  // a format newer than the WAV five: the instantiation that reads them all
     for (const RsJobDev& d : dj) ext = ext || d.fmt > ISS_RS_F64;
-    auto kernel = plan.set ? (ext ? resample_kernel<true, false, false, true, true> : resample_kernel<false, false, false, true, true>)
+    auto kernel = plan.sched ? (ext ? resample_kernel<true, false, false, true, false, true> : resample_kernel<false, false, false, true, false, true>)
+                  : plan.set ? (ext ? resample_kernel<true, false, false, true, true> : resample_kernel<false, false, false, true, true>)
                   : mix ? (win ? (ext ? resample_kernel<true, true, false, true> : resample_kernel<false, true, false, true>)
                              : (ext ? resample_kernel<true, false, false, true> : resample_kernel<false, false, false, true>))
                   : split && win ? (ext ? resample_kernel<true, true, true> : resample_kernel<false, true, true>)
@@ -574,14 +716,17 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
 // the tables `mix` of iss_resample_pcm16_mix (with or without windows)
 static int resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
                           int64_t n_signal, const iss_window* windows, const iss_split* splits, const int32_t* channel_sel,
-                          int64_t nsel, const IssMixTables* mix = nullptr) {
-    const char* who = mix ? "iss_resample_pcm16_mix" : splits && windows ? "iss_resample_pcm16_windows_split" : splits ? "iss_resample_pcm16_split"
+                          int64_t nsel, const IssMixTables* mix = nullptr, const IssSchedTables* sched = nullptr) {
+    const char* who = sched ? "iss_resample_pcm16_sched" : mix ? "iss_resample_pcm16_mix" : splits && windows ? "iss_resample_pcm16_windows_split" : splits ? "iss_resample_pcm16_split"
                       : windows ? "iss_resample_pcm16_windows" : "iss_resample_pcm16";
-    if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0) || (mix && njobs > 0 && !mix->sets))
+    if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0) || (mix && !sched && njobs > 0 && !mix->sets) ||
+        (sched && njobs > 0 && !sched->scheds))
         return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
+    if (sched && windows) return iss_fail(c, ISS_EINVAL, "%s: windows passed with a schedule, which governs whole sources", who);
     IssDecodePass pass;
     int rc = pass.begin(c, who, n_signal, 0);
-    if (mix) { pass.jmix = mix; pass.rmixsets.assign(mix->sets, mix->sets + njobs); }
+    if (sched) { pass.jmix = mix; pass.jsched = sched; pass.rmixsets.assign((size_t)njobs, iss_mixset{0, 0, 0}); }      // (no job has a mix set)
+    else if (mix) { pass.jmix = mix; pass.rmixsets.assign(mix->sets, mix->sets + njobs); }
     pass.rjobs.assign(jobs, jobs + njobs); pass.stage = src_bytes;      // no placement: the caller's rows over the caller's bytes
     if (windows) { pass.rwins.assign(windows, windows + njobs); pass.windowed = true; }
     if (splits) { pass.rsplits.assign(splits, splits + njobs); pass.split = true; pass.sel = channel_sel; pass.nsel = nsel; }
@@ -614,6 +759,15 @@ extern "C" int iss_resample_pcm16_mix(iss_ctx* c, const void* src, int64_t src_b
     return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, windows, nullptr, nullptr, 0, &mix);
 }
 
+extern "C" int iss_resample_pcm16_sched(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
+                                        const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_sched* scheds,
+                                        const iss_sched_run* runs, int64_t nruns, const iss_mix* mixes, int64_t nmixes,
+                                        const iss_mix_term* terms, int64_t nterms) {
+    const IssMixTables mix{nullptr, mixes, nmixes, terms, nterms};
+    const IssSchedTables sched{scheds, runs, nruns};
+    return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, windows, nullptr, nullptr, 0, &mix, &sched);
+}
+
 // what `origin` holds for iss_resample_staged_mix: its id (0: nothing), and for a codec the codec
 static int64_t staged_held(iss_ctx* c, int32_t origin, IssCodec*& dec) {
     dec = origin == ISS_STAGED_FLAC ? &c->flac : origin == ISS_STAGED_ADPCM ? &c->adpcm : origin == ISS_STAGED_MSADPCM ? &c->msadpcm
@@ -636,12 +790,15 @@ extern "C" int iss_staged_payload(iss_ctx* c, int32_t origin, int64_t* payload_o
 // The rows of a *_mix call over bytes a survey call (origin survey) or a decode call (a codec) left on the device: every row is
 // matched against what was uploaded / staged and rewritten to the byte offset it lies at, then planned and launched as
 // resample_pcm16 does -- without its upload.  Everything up to commit() is host work on vectors of this call
-extern "C" int iss_resample_staged_mix(iss_ctx* c, int32_t origin, int64_t payload, const iss_resample_job* jobs,
-                                       const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_mixset* mixsets,
-                                       const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms, int64_t nterms) {
-    const char* who = "iss_resample_staged_mix";
-    if (!c || origin < ISS_STAGED_SURVEY || origin > ISS_STAGED_MSADPCM || njobs < 0 || (njobs > 0 && (!jobs || !mixsets)))
+// `sched` (iss_resample_staged_sched; `mixsets` is then NULL): a schedule beside every job in the place of a mix set, no windows
+static int resample_staged(iss_ctx* c, const char* who, int32_t origin, int64_t payload, const iss_resample_job* jobs,
+                           const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_mixset* mixsets,
+                           const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms, int64_t nterms,
+                           const IssSchedTables* sched) {
+    if (!c || origin < ISS_STAGED_SURVEY || origin > ISS_STAGED_MSADPCM || njobs < 0 ||
+        (njobs > 0 && (!jobs || (sched ? !sched->scheds : !mixsets))))
         return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
+    if (sched && windows) return iss_fail(c, ISS_EINVAL, "%s: windows passed with a schedule, which governs whole sources", who);
     IssCodec* dec;
     const int64_t id = staged_held(c, origin, dec);
     if (id == 0)
@@ -690,12 +847,29 @@ extern "C" int iss_resample_staged_mix(iss_ctx* c, int32_t origin, int64_t paylo
     IssDecodePass pass;
     int rc = pass.begin(c, who, n_signal, 0);
     pass.jmix = &mix;
-    if (njobs > 0) pass.rmixsets.assign(mixsets, mixsets + njobs);
+    if (sched) { pass.jsched = sched; pass.rmixsets.assign((size_t)njobs, iss_mixset{0, 0, 0}); }
+    else if (njobs > 0) pass.rmixsets.assign(mixsets, mixsets + njobs);
     pass.rjobs = rows; pass.stage = held_bytes;
     if (windows) { pass.rwins.assign(windows, windows + njobs); pass.windowed = true; }
     if (rc || (rc = pass.commit(nullptr))) return rc;
     if (njobs == 0) return ISS_OK;
     return iss_resample_launch(c, (const uint8_t*)(dec ? dec->stage.p : c->sv_src.p), pass.plan);
+}
+
+extern "C" int iss_resample_staged_mix(iss_ctx* c, int32_t origin, int64_t payload, const iss_resample_job* jobs,
+                                       const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_mixset* mixsets,
+                                       const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms, int64_t nterms) {
+    return resample_staged(c, "iss_resample_staged_mix", origin, payload, jobs, windows, njobs, n_signal, mixsets, mixes, nmixes, terms,
+                           nterms, nullptr);
+}
+
+extern "C" int iss_resample_staged_sched(iss_ctx* c, int32_t origin, int64_t payload, const iss_resample_job* jobs,
+                                         const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_sched* scheds,
+                                         const iss_sched_run* runs, int64_t nruns, const iss_mix* mixes, int64_t nmixes,
+                                         const iss_mix_term* terms, int64_t nterms) {
+    const IssSchedTables sched{scheds, runs, nruns};
+    return resample_staged(c, "iss_resample_staged_sched", origin, payload, jobs, windows, njobs, n_signal, nullptr, mixes, nmixes,
+                           terms, nterms, &sched);
 }
 
 // The body of the two set entry points (include/iss.h, "File sets"): the jobs planned over their members' bytes in `src_bytes` of

@@ -176,17 +176,66 @@ __global__ __launch_bounds__(SV_THREADS) void survey_reduce_kernel(const SvJobDe
     res[J.res_off + w] = is_count ? (unsigned long long)cnt : (unsigned long long)__double_as_longlong(acc);
 }
 
+// Survey blocks (include/iss.h).  Grid: ragged over (job, block, group of SV_THREADS words); job k owns units [unit_base_k,
+// unit_base_k + nblocks_k * wgroups_k) of the SvBlkDev rows that follow the job rows, a prefix sum built on the host, and a
+// workgroup finds its job by binary search.  Thread t adds word w = group * SV_THREADS + t of the block's chunk rows [block * K,
+// min((block + 1) * K, chunks)) in ascending order, exactly as survey_reduce_kernel adds a job's, and stores it: plain stores,
+// every word of every block row written once
+__global__ __launch_bounds__(SV_THREADS) void survey_reduce_blocks_kernel(const SvJobDev* __restrict__ jobs, int njobs,
+                                                                          const unsigned long long* __restrict__ ws,
+                                                                          unsigned long long* __restrict__ res) {
+    const SvBlkDev* blks = reinterpret_cast<const SvBlkDev*>(jobs + njobs);
+    const int64_t b = blockIdx.x;
+    int lo = 0, hi = njobs - 1;                                             // last job whose unit_base <= b
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (blks[mid].unit_base <= b) lo = mid; else hi = mid - 1;
+    }
+    const SvJobDev J = jobs[lo];
+    const SvBlkDev B = blks[lo];
+    const int ch = J.ch;
+    const int64_t width = 6 * (int64_t)ch + (ch <= SV_GROUP ? ch * (ch - 1) / 2 : 0);
+    const int u = (int)(b - B.unit_base), blk = u / B.wgroups;
+    const int64_t w = (int64_t)(u - blk * B.wgroups) * SV_THREADS + threadIdx.x;
+    if (w >= width) return;
+    const int64_t chunks = (J.n + SV_CHUNK - 1) / SV_CHUNK;
+    const int64_t q_begin = (int64_t)blk * B.K, q_end = min(q_begin + B.K, chunks);
+    const unsigned long long* p = ws + J.ws_off + w;
+    const bool is_max = w >= 2 * (int64_t)ch && w < 3 * (int64_t)ch, is_count = w >= 3 * (int64_t)ch && w < 6 * (int64_t)ch;
+    double acc = 0.0;
+    long long cnt = 0;
+    for (int64_t q0 = q_begin; q0 < q_end; q0 += 8) {
+        unsigned long long v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = q0 + k < q_end ? p[(q0 + k) * width] : 0ull;        // (+0.0, or a count of 0)
+        const int m = (int)min((int64_t)8, q_end - q0);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (k < m) {
+                if (is_count) cnt += (long long)v[k];
+                else if (is_max) acc = fmax(acc, __longlong_as_double((long long)v[k]));
+                else acc = __dadd_rn(acc, __longlong_as_double((long long)v[k]));
+            }
+        }
+    }
+    res[B.out_off + (int64_t)blk * width + w] = is_count ? (unsigned long long)cnt : (unsigned long long)__double_as_longlong(acc);
+}
+
 // the body of the five entry points: the rows planned against `src_bytes` of uploaded bytes (dec == NULL) or against what `dec`
-// staged last; both launches; the result rows copied back before it returns.  `set`: the tables of iss_survey_set (else NULL)
+// staged last; both launches; the result rows copied back before it returns.  `set`: the tables of iss_survey_set (else NULL).
+// `blocked`: a *_blocks entry point (include/iss.h, "Survey blocks") with K per job and the block rows' destination: the third
+// launch, and a second copy back
 int survey_call(iss_ctx* c, const char* who, IssCodec* dec, const void* src, int64_t src_bytes, const iss_survey_job* jobs,
-                const iss_window* windows, int32_t njobs, void* results, const IssSetTables* set = nullptr) {
+                const iss_window* windows, int32_t njobs, void* results, const IssSetTables* set = nullptr, bool blocked = false,
+                const int32_t* block_chunks = nullptr, void* block_results = nullptr) {
     if (!c || njobs < 0 || (njobs > 0 && (!jobs || !results)) || src_bytes < 0 || (!dec && !src && src_bytes > 0) ||
-        (set && njobs > 0 && !set->sets) || (set && (set->nmembers < 0 || (set->nmembers > 0 && !set->members))))
+        (set && njobs > 0 && !set->sets) || (set && (set->nmembers < 0 || (set->nmembers > 0 && !set->members))) ||
+        (blocked && njobs > 0 && (!block_chunks || !block_results)))
         return iss_fail(c, ISS_EINVAL, "%s: bad argument", who);
     SvPlan plan;
     std::string err;
     if (!sv_plan(jobs, windows, njobs, src_bytes, dec ? &dec->stage_off : nullptr, dec ? &dec->stage_bytes : nullptr, plan, err,
-                 set ? set->sets : nullptr, set ? set->members : nullptr, set ? set->nmembers : 0))
+                 set ? set->sets : nullptr, set ? set->members : nullptr, set ? set->nmembers : 0, blocked ? block_chunks : nullptr))
         return iss_fail(c, ISS_EINVAL, "%s: %s", who, err.c_str());
     if (njobs == 0) return ISS_OK;
     ISS_HIP(c, hipSetDevice(c->device));
@@ -198,7 +247,14 @@ int survey_call(iss_ctx* c, const char* who, IssCodec* dec, const void* src, int
     }
     if ((rc = iss_reserve(c, c->sv_ws, (size_t)plan.ws_words * 8))) return rc;
     if ((rc = iss_reserve(c, c->sv_res, (size_t)plan.res_words * 8))) return rc;
-    if (set) {                                             // one table: the jobs, then the channels of every one of them
+    if (blocked) {                                         // one table: the jobs, then the block geometry of every one of them
+        if ((rc = iss_reserve(c, c->sv_blk, (size_t)plan.blk_words * 8))) return rc;
+        const size_t nj = plan.dj.size() * sizeof(SvJobDev), nb = plan.blk.size() * sizeof(SvBlkDev);
+        std::vector<uint8_t> rows(nj + nb);
+        memcpy(rows.data(), plan.dj.data(), nj);
+        memcpy(rows.data() + nj, plan.blk.data(), nb);
+        rc = iss_upload_rows(c, c->sv_jobs, rows.data(), rows.size());
+    } else if (set) {                                      // one table: the jobs, then the channels of every one of them
         const size_t nj = plan.dj.size() * sizeof(SvJobDev), nc = plan.chans.size() * sizeof(SetChanDev);
         std::vector<uint8_t> rows(nj + nc);
         memcpy(rows.data(), plan.dj.data(), nj);
@@ -224,6 +280,16 @@ int survey_call(iss_ctx* c, const char* who, IssCodec* dec, const void* src, int
                        (unsigned long long*)c->sv_res.p);
     ISS_HIP(c, hipGetLastError());
     iss_prof_end(c);
+    if (blocked) {
+        iss_prof_begin(c, ISS_PROF_FRONTEND, 0.0);
+        iss_prof_inst(c, "survey_reduce_blocks_kernel");
+        hipLaunchKernelGGL(survey_reduce_blocks_kernel, dim3((unsigned)plan.blk_units), dim3(SV_THREADS), 0, c->stream,
+                           (const SvJobDev*)c->sv_jobs.p, (int)njobs, (const unsigned long long*)c->sv_ws.p,
+                           (unsigned long long*)c->sv_blk.p);
+        ISS_HIP(c, hipGetLastError());
+        iss_prof_end(c);
+        ISS_HIP(c, hipMemcpyAsync(block_results, c->sv_blk.p, (size_t)plan.blk_words * 8, hipMemcpyDeviceToHost, c->stream));
+    }
     ISS_HIP(c, hipMemcpyAsync(results, c->sv_res.p, (size_t)plan.res_words * 8, hipMemcpyDeviceToHost, c->stream));
     ISS_HIP(c, hipStreamSynchronize(c->stream));
     c->sv_count.launches += 1;
@@ -265,6 +331,30 @@ extern "C" int iss_adpcm_survey(iss_ctx* c, const iss_survey_job* jobs, const is
 
 extern "C" int iss_msadpcm_survey(iss_ctx* c, const iss_survey_job* jobs, const iss_window* windows, int32_t njobs, void* results) {
     return survey_call(c, "iss_msadpcm_survey", c ? &c->msadpcm : nullptr, nullptr, 0, jobs, windows, njobs, results);
+}
+
+extern "C" int iss_survey_blocks(iss_ctx* c, const void* src, int64_t src_bytes, const iss_survey_job* jobs, int32_t njobs,
+                                 const int32_t* block_chunks, void* results, void* block_results) {
+    return survey_call(c, "iss_survey_blocks", nullptr, src, src_bytes, jobs, nullptr, njobs, results, nullptr, true, block_chunks,
+                       block_results);
+}
+
+extern "C" int iss_flac_survey_blocks(iss_ctx* c, const iss_survey_job* jobs, int32_t njobs, const int32_t* block_chunks,
+                                      void* results, void* block_results) {
+    return survey_call(c, "iss_flac_survey_blocks", c ? &c->flac : nullptr, nullptr, 0, jobs, nullptr, njobs, results, nullptr, true,
+                       block_chunks, block_results);
+}
+
+extern "C" int iss_adpcm_survey_blocks(iss_ctx* c, const iss_survey_job* jobs, int32_t njobs, const int32_t* block_chunks,
+                                       void* results, void* block_results) {
+    return survey_call(c, "iss_adpcm_survey_blocks", c ? &c->adpcm : nullptr, nullptr, 0, jobs, nullptr, njobs, results, nullptr,
+                       true, block_chunks, block_results);
+}
+
+extern "C" int iss_msadpcm_survey_blocks(iss_ctx* c, const iss_survey_job* jobs, int32_t njobs, const int32_t* block_chunks,
+                                         void* results, void* block_results) {
+    return survey_call(c, "iss_msadpcm_survey_blocks", c ? &c->msadpcm : nullptr, nullptr, 0, jobs, nullptr, njobs, results, nullptr,
+                       true, block_chunks, block_results);
 }
 
 extern "C" int iss_survey_geometry(int32_t* chunk_out, int32_t* lanes_out, int32_t* pair_channels_out) {

@@ -30,8 +30,16 @@ static_assert(sizeof(SvJobDev) == 56, "rows are copied to the device as they sta
 struct SetChanDev { int64_t off, frames; int32_t step, pad; };
 static_assert(sizeof(SetChanDev) == 24 && sizeof(SvJobDev) % 8 == 0, "8-byte aligned behind the job rows");
 
+// beside SvJobDev k of a blocked call (include/iss.h, "Survey blocks"): the job's blocks hold K chunks each (the last fewer), a
+// block's row is cut into `wgroups` groups of SV_THREADS words, the job's (block, word group) units are numbered from unit_base
+// and its block rows start at word out_off of the block results.  The rows follow the job rows on the device
+struct SvBlkDev { int64_t unit_base, out_off; int32_t K, wgroups; };
+static_assert(sizeof(SvBlkDev) == 24, "8-byte aligned behind the job rows");
+
 struct SvPlan {
     std::vector<SvJobDev> dj;
+    std::vector<SvBlkDev> blk;                         // a blocked call: one per job
+    int64_t blk_units = 0, blk_words = 0;              // ... the grid of survey_reduce_blocks_kernel and the words it writes
     std::vector<SetChanDev> chans;                     // a set call: every job's channels, in job order
     int64_t chunks = 0, ws_words = 0, res_words = 0;
     int64_t lds = 0;                                   // bytes of dynamic LDS survey_kernel needs for these jobs
@@ -95,11 +103,12 @@ inline bool set_channels(const iss_set& S, const iss_set_member* members, int64_
 // (include/iss.h, "File sets"; never with `wins` or the codec vectors): plan.chans gets a row per channel of every job.
 // `stage_off` / `stage_bytes` NULL: the rows' src_offset are byte offsets into a buffer of src_bytes.  Else (the codec entries):
 // src_offset is an index into the two vectors, what a decode call staged per job (offset -1: not staged).
+// `block_chunks` (NULL: not a blocked call; never with `wins` or `sets`): K of every job, plan.blk gets a row per job.
 // -> true, or false with `err` saying which job and why (plan is then not to be used)
 inline bool sv_plan(const iss_survey_job* jobs, const iss_window* wins, int32_t njobs, int64_t src_bytes,
                     const std::vector<int64_t>* stage_off, const std::vector<int64_t>* stage_bytes, SvPlan& plan,
                     std::string& err, const iss_set* sets = nullptr, const iss_set_member* members = nullptr,
-                    int64_t nmembers = 0) {
+                    int64_t nmembers = 0, const int32_t* block_chunks = nullptr) {
     char text[256];
     auto fail = [&](int k, const char* why, long long a = 0, long long b = 0, long long c = 0) {
         char body[192];
@@ -159,6 +168,16 @@ inline bool sv_plan(const iss_survey_job* jobs, const iss_window* wins, int32_t 
         if (row > plan.max_row) plan.max_row = (int32_t)row;
         if (sv_lds_bytes(J.channels) > plan.lds) plan.lds = sv_lds_bytes(J.channels);
         if (plan.chunks > 0x7fffffffLL) return fail(k, "%lld chunks in one call", plan.chunks);
+        if (block_chunks) {
+            if (wins || sets) return fail(k, "a blocked call takes no windows and no sets");
+            const int64_t K = block_chunks[k];
+            if (K < 1) return fail(k, "block_chunks %lld: a block holds at least one chunk", K);
+            const int64_t nblocks = (chunks + K - 1) / K, wgroups = (row + SV_THREADS - 1) / SV_THREADS;
+            plan.blk.push_back(SvBlkDev{plan.blk_units, plan.blk_words, (int32_t)K, (int32_t)wgroups});
+            plan.blk_units += nblocks * wgroups;
+            plan.blk_words += nblocks * row;
+            if (plan.blk_units > 0x7fffffffLL) return fail(k, "%lld block units in one call", plan.blk_units);
+        }
     }
     return true;
 }

@@ -14,7 +14,7 @@ import numpy as np
 from . import _native
 from . import resample as R
 from .io import need_16k_mono, source_of
-from .sources import CodedAuto, CodedSource, RawAuto, RawSource, host_window, selection
+from .sources import SCHED_OF, CodedAuto, CodedSched, CodedSource, RawAuto, RawSource, host_window, selection
 
 MAGIC = b'fLaC'
 # benchmark switch (tools/bench_flac.py), not a user option: True makes the ffmpeg-free read decode FLAC on the host
@@ -176,6 +176,14 @@ class FlacAuto(CodedAuto, FlacSource):
     def __init__(self, stream, kind='stage'):
         FlacSource.__init__(self, stream, kind)
         self.size, self.decision = stream.n if kind == 'pcm' else R.out_len(stream.n, stream.sr), None
+
+
+class FlacSched(CodedSched, FlacAuto):
+    """A FLAC file with a schedule, given or decided from its blocked survey (sources.CodedSched)."""
+    __slots__ = ('sched', 'block_chunks')
+
+
+SCHED_OF[FlacAuto] = FlacSched
 
 
 class FlacExcerpt(FlacSource):

@@ -826,6 +826,90 @@ def decode_auto(medianame, resample=True):
     return (R.resample_ref(x, h.sr) if mix is None else R.mix_ref(x, h.sr, mix)), survey, mix
 
 
+# ---------------------------------------------------------------------------------------------- schedules and timelines
+def _sched_parsed(medianame, what, resample):
+    """-> (the file parsed as a survey parses it, its fullscale threshold), for a schedule or a timeline: whole single files
+    without ffmpeg, a rate other than 16 kHz only with `resample`."""
+    medianame = as_media(medianame)
+    _no_set_ranges(medianame, what)
+    h, full, multi = _auto_parsed(medianame)
+    if multi or (h.n > 0 and h.sr != R.SR_OUT):
+        if not resample:
+            need_16k_mono(medianame, h.sr, 1) if h.ch == 1 else need_16k(medianame, h.sr)
+        R.check_rate(h.sr)
+    return h, full
+
+
+def schedule_source(medianame, schedule, resample=False):
+    """What Segmenter reads for load_pcm_schedule -> (the resample.Schedule, the source).  The schedule is normalised against the
+    file's rate and channels (resample.normalise_schedule, the errors naming the file).  The source is io.auto_source's as a
+    scheduled source of its class (sources.scheduled); a one-channel file whose every run is the plain downmix is read as ever."""
+    from . import sources
+    h, full = _sched_parsed(medianame, 'schedules', resample)
+    sched = R.normalise_schedule(schedule, h.sr, h.ch, f'{as_media(medianame)}: schedule')
+    if h.n == 0:
+        return sched, h.source(resample)
+    src = h.auto_source(full)
+    if type(src) not in sources.SCHED_OF or getattr(src, 'kind', 'stage') != 'stage':      # one channel, read as it always was
+        if any(m is not None for _, m in sched.runs):
+            x = h.stored()
+            src = sources.RawAuto(x[:, None] if x.ndim == 1 else x, h.sr, full=full)       # the mixes of one channel: on the device too
+        else:
+            return sched, src
+    return sched, sources.scheduled(src, sched, None)
+
+
+def timeline_source(medianame, block_sec=None, resample=False):
+    """What Segmenter reads for the timeline calls: io.auto_source's source, and for a file of two or more channels that source
+    as a scheduled source that is to decide its schedule from blocks of `block_sec` seconds (survey.block_chunks)."""
+    from . import sources
+    from .survey import DEFAULT_BLOCK_SEC, block_chunks
+    h, full = _sched_parsed(medianame, 'timelines', resample)
+    k = block_chunks(DEFAULT_BLOCK_SEC if block_sec is None else block_sec, h.sr)
+    if h.n == 0:
+        return h.source(resample)
+    src = h.auto_source(full)
+    if type(src) not in sources.SCHED_OF:
+        return src
+    return sources.scheduled(src, None, k)
+
+
+def decode_schedule(medianame, schedule, resample=True):
+    """Host-only twin of Segmenter.load_pcm_schedule: resample.schedule_ref of the stored samples as decode_source decodes them,
+    the schedule normalised against the file's rate and channels."""
+    h, _ = _sched_parsed(medianame, 'schedules', resample)
+    sched = R.normalise_schedule(schedule, h.sr, h.ch, f'{as_media(medianame)}: schedule')
+    x = h.stored()
+    if h.ch == 1 and all(m is None for _, m in sched.runs):
+        return R.resample_ref(x, h.sr) if h.sr != R.SR_OUT else decode_pcm(medianame, ffmpeg=None)
+    return R.schedule_ref(x, h.sr, sched)
+
+
+def survey_timeline(medianame, block_sec=None):
+    """Host-only twin of Segmenter.survey_timeline -> a survey.SurveyTimeline: `whole` = survey_channels(medianame), block b =
+    resample.survey_ref of stored frames [b * B, min((b + 1) * B, n)), B = survey.block_chunks(block_sec, sr) * 1024 (block_sec
+    None: survey.DEFAULT_BLOCK_SEC)."""
+    from .survey import DEFAULT_BLOCK_SEC, ChannelSurvey, SurveyTimeline, block_chunks
+    _no_set_ranges(medianame, 'timelines')
+    h, full = _survey_parsed(medianame, False)
+    per = block_chunks(DEFAULT_BLOCK_SEC if block_sec is None else block_sec, h.sr) * R.SURVEY_CHUNK
+    x = h.stored()
+    blocks = [ChannelSurvey(R.survey_ref(x, full, a, min(a + per, h.n)), h.sr, a) for a in range(0, h.n, per)]
+    return SurveyTimeline(ChannelSurvey(R.survey_ref(x, full, 0, h.n), h.sr, 0), blocks, per)
+
+
+def decode_auto_timeline(medianame, block_sec=None, resample=True):
+    """Host-only twin of Segmenter.load_pcm_auto_timeline -> (pcm, timeline, schedule): timeline = survey_timeline(medianame,
+    block_sec), schedule = timeline.safe_schedule(), pcm = decode_schedule(medianame, schedule); a one-channel file gives
+    decode_auto's pcm and (None, None)."""
+    h, _ = _sched_parsed(medianame, 'timelines', resample)
+    if not (h.ch > 1 and h.n > 0):
+        return decode_auto(medianame, resample)[0], None, None
+    timeline = survey_timeline(medianame, block_sec)
+    schedule = timeline.safe_schedule()
+    return R.schedule_ref(h.stored(), h.sr, schedule), timeline, schedule
+
+
 def survey_sources(medianame, ranges=None):
     """What the device surveys for `medianame` -> (sr, [(source or resample.SurveyFields, first frame) per range]; one entry, the
     whole file, for ranges None).  A source stages only what its frames [a, b) need: the bytes of a plain RIFF/WAVE file, read by

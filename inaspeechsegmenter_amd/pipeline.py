@@ -96,7 +96,7 @@ class _AudioBudget:
             self.cv.notify_all()
 
 
-def _decode_stage(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None, resample=False, channels=None):
+def _decode_stage(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None, resample=False, channels=None, **how):
     """items: [(index, src)].  Puts (index, src, sig | None, errtext | None) on out_q in completion order, then None."""
     import random
     in_q = queue.Queue()
@@ -112,7 +112,7 @@ def _decode_stage(items, ffmpeg, nbtry, trydelay, out_q, nthreads, budget=None, 
             sig, err, itry = None, None, 0
             while sig is None and itry < nbtry:
                 try:
-                    sig = S._load_source(src, None, None, ffmpeg, resample, channels)
+                    sig = S._load_source(src, None, None, ffmpeg, resample, channels, **how)
                 except:                                            # noqa: E722  (reference semantics, segmenter.py:364-370)
                     itry += 1
                     err = 'error: ' + str(sys.exc_info()[0])
@@ -302,7 +302,7 @@ DEFAULT_WORKERS = 4               # passes with more contexts in flight overlap 
 
 
 def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch_files=None, batch_seconds=None,
-                  workers=None, decode_threads=4, channels=None, decided=None):
+                  workers=None, decode_threads=4, channels=None, decided=None, auto_block_sec=None):
     """Segment `linput` with the networks of `seg`; on_result(index, src, lseg | None, errtext | None, secs) is called from
     the worker threads (serialised by a lock) as results become available, lseg = [(label, start_sec, stop_sec)], secs =
     this file's share of the processing time of its device pass (the pass's wall time / its files: what the reference's
@@ -312,7 +312,9 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
     channels='split': every channel of every file on its own; lseg is then a LIST of segment lists, one per channel of the file.
     channels = a list of resample.Mix: those mixes of every file, likewise (segmenter._load_source reads either).
     channels='auto': every file downmixed as its own survey suggests (io.auto_source); lseg is one segment list, as without
-    `channels`, and decided((src, survey, mix)) is called before on_result for every file that was processed."""
+    `channels`, and decided((src, survey, mix)) is called before on_result for every file that was processed.
+    auto_block_sec (with channels='auto'): every file of two or more channels by the schedule its own timeline suggests
+    (io.timeline_source, blocks of that many seconds); decided then gets (src, timeline, schedule)."""
     multi = channels is not None and channels != 'auto'        # on_result gets a list of segment lists
     batch_files, batch_seconds = _limits(batch_files, batch_seconds)
     workers = workers or DEFAULT_WORKERS
@@ -320,7 +322,8 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
     dec_q = queue.Queue(maxsize=4 * batch_files)
     budget = _AudioBudget(2 * batch_seconds * 16000)        # decoded audio waiting for the packer: <= 2 super-batches
     _decode_stage(items, seg.ffmpeg, nbtry, trydelay, dec_q, decode_threads, budget, getattr(seg, 'resample', False),
-                  **({} if channels is None else {'channels': channels}))
+                  **({} if channels is None else {'channels': channels}),
+                  **({} if auto_block_sec is None else {'auto_block_sec': auto_block_sec}))
     batch_q = queue.Queue(maxsize=max(2, workers))
     lock = threading.Lock()
     failure = []

@@ -250,6 +250,109 @@ def mix_ref(x, sr, mix, out_begin=0, out_count=None, in_begin=0, frames_total=No
     return quantise(resample_float(mixdown(x, mix), sr, out_begin, out_count, in_begin, frames_total))
 
 
+# ---------------------------------------------------------------------------------------------- schedules: a mix per stretch of a file
+class Schedule:
+    """A downmix that changes over time (include/iss.h, "Schedules"): `runs` = ((begin, mix), ...), begin in stored frames at
+    the file's own rate -- runs[0] begins at 0, the begins ascend strictly --, mix a `Mix` or None (the plain downmix of all
+    channels).  Run r governs the frames [begin_r, begin_{r+1}), the last run to the end; a run at or past the end of the file
+    governs nothing.  Equal to another, or to a list of (begin, mix) pairs, when the runs are equal."""
+    __slots__ = ('runs',)
+
+    def __init__(self, runs):
+        runs = tuple((int(b), m) for b, m in runs)
+        if not runs or runs[0][0] != 0:
+            raise ValueError(f'schedule: run 0 begins at frame {runs[0][0] if runs else None!r}, not 0')
+        for r in range(1, len(runs)):
+            if runs[r][0] <= runs[r - 1][0]:
+                raise ValueError(f'schedule: run {r} begins at frame {runs[r][0]}, run {r - 1} at {runs[r - 1][0]}: begins ascend strictly')
+        for r, (_, m) in enumerate(runs):
+            if m is not None and not isinstance(m, Mix):
+                raise ValueError(f'schedule: run {r}: its mix is a resample.Mix or None, not {m!r}')
+        self.runs = runs
+
+    def __eq__(self, other):
+        if isinstance(other, Schedule):
+            return self.runs == other.runs
+        if isinstance(other, (list, tuple)):
+            return list(self.runs) == [tuple(r) for r in other]
+        return NotImplemented
+
+    __hash__ = None
+
+    def __len__(self):
+        return len(self.runs)
+
+    def __iter__(self):
+        return iter(self.runs)
+
+    def __repr__(self):
+        return f'Schedule({list(self.runs)!r})'
+
+
+def normalise_schedule(spec, sr, channels=None, name='schedule'):
+    """A schedule specification [(start_sec, mix), ...] for a file at `sr` Hz -> a `Schedule`: begin = floor(start_sec * sr +
+    0.5), the rounding of segment_excerpts; a mix spelt as normalise_mixes states, or None.  A `Schedule` (begins in frames
+    already) has its mixes checked against `channels` and is handed on.  ValueError naming `name`, the run and the reason: an
+    empty specification, a first start that is not 0, two starts that round to one frame, descending starts, a start that is
+    negative or not finite, a channel outside the file's `channels`, and what normalise_mixes refuses of a mix."""
+    def is_num(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+    if isinstance(spec, Schedule):
+        for r, (_, m) in enumerate(spec.runs):
+            if m is not None:
+                _one_mix(0, m, channels, f'{name}: run {r}')
+        return spec
+    if spec is None or isinstance(spec, (str, bytes, Mix)) or hasattr(spec, 'items'):
+        raise ValueError(f'{name}: a schedule is a sequence of (start_sec, mix) runs, not {spec!r}')
+    try:
+        spec = [tuple(run) for run in spec]
+    except TypeError:
+        raise ValueError(f'{name}: a schedule is a sequence of (start_sec, mix) runs, not {spec!r}') from None
+    if not spec:
+        raise ValueError(f'{name}: empty schedule')
+    runs = []
+    for r, run in enumerate(spec):
+        if len(run) != 2 or not is_num(run[0]):
+            raise ValueError(f'{name}: run {r} ({run!r}) is not a (start_sec, mix) pair')
+        start, m = float(run[0]), run[1]
+        if not math.isfinite(start) or start < 0:
+            raise ValueError(f'{name}: run {r}: start {start!r} s is negative or not finite')
+        begin = math.floor(start * sr + 0.5)
+        if r == 0 and begin != 0:
+            raise ValueError(f'{name}: run 0 starts at {start!r} s (frame {begin}): the first run starts at 0')
+        if r > 0 and begin == runs[-1][0]:
+            raise ValueError(f'{name}: run {r}: starts {spec[r - 1][0]!r} s and {start!r} s round to one frame ({begin}) at {sr} Hz')
+        if r > 0 and begin < runs[-1][0]:
+            raise ValueError(f'{name}: run {r}: start {start!r} s lies before run {r - 1} ({spec[r - 1][0]!r} s): starts ascend')
+        runs.append((begin, None if m is None else _one_mix(0, m, channels, f'{name}: run {r}')))
+    return Schedule(runs)
+
+
+def schedule_mixdown(x, schedule):
+    """Stored samples (n,) or (n, C) -> the scheduled float64 mono signal: frame j mixed by `mixdown` with the mix of the run
+    that governs it, None being the mix of all C channels in order with w = 1, d = C (the plain downmix, to the bit)."""
+    x = np.asarray(x)
+    if x.ndim == 1:
+        x = x[:, None]
+    n, ch = x.shape
+    schedule = normalise_schedule(schedule if isinstance(schedule, Schedule) else Schedule(schedule), None, ch)
+    plain = Mix(tuple((c, 1.0) for c in range(ch)), float(ch))
+    out = np.zeros(n)
+    begins = [b for b, _ in schedule.runs] + [n]
+    for r, (_, m) in enumerate(schedule.runs):
+        a, b = min(begins[r], n), min(begins[r + 1], n)
+        if b > a:
+            out[a:b] = mixdown(x[a:b], plain if m is None else m)
+    return out
+
+
+def schedule_ref(x, sr, schedule):
+    """The numpy statement of include/iss.h's "Schedules": resample_ref with `schedule_mixdown(x, schedule)` in place of the
+    downmix -> 16 kHz mono int16.  The taps of outputs near a run boundary see samples of both runs: that is the definition."""
+    return quantise(resample_float(schedule_mixdown(x, schedule), sr))
+
+
 # ---------------------------------------------------------------------------------------------- channel survey: the reference
 SURVEY_CHUNK, SURVEY_LANES, SURVEY_PAIR_CHANNELS = 1024, 256, 16      # include/iss.h: ISS_SURVEY_CHUNK, four waves of 64, ISS_SURVEY_PAIR_CHANNELS
 

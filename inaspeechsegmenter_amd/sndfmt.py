@@ -31,7 +31,7 @@ from . import _native
 from . import flac
 from . import resample as R
 from .io import _to_float, need_16k_mono
-from .sources import CodedAuto, CodedSource, RawAuto, RawSource, host_window, selection
+from .sources import SCHED_OF, CodedAuto, CodedSched, CodedSource, RawAuto, RawSource, host_window, selection
 
 # benchmark switch (tools/bench_sndfmt.py), not a user option: True makes the ffmpeg-free read expand G.711 and ADPCM on
 # the host (numpy table / iss_adpcm_decode_host, iss_msadpcm_decode_host in the decode threads) instead of handing the stored bytes to the device
@@ -653,6 +653,19 @@ class MsAdpcmExcerpt(AdpcmExcerpt, MsAdpcmSource):
 class MsAdpcmAuto(AdpcmAuto, MsAdpcmSource):
     """A Microsoft ADPCM file for channels='auto'."""
     __slots__ = ()
+
+
+class AdpcmSched(CodedSched, AdpcmAuto):
+    """An IMA ADPCM file with a schedule, given or decided from its blocked survey (sources.CodedSched)."""
+    __slots__ = ('sched', 'block_chunks')
+
+
+class MsAdpcmSched(CodedSched, MsAdpcmAuto):
+    """A Microsoft ADPCM file with a schedule."""
+    __slots__ = ('sched', 'block_chunks')
+
+
+SCHED_OF[AdpcmAuto], SCHED_OF[MsAdpcmAuto] = AdpcmSched, MsAdpcmSched
 
 
 class _BlockKind(NamedTuple):

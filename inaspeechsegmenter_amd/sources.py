@@ -50,6 +50,12 @@ length, so a pass is laid out before any survey is known; its class is `two_step
 its `decision` = (survey.ChannelSurvey, its safe_mix()), ONE resample launch over the staged bytes -- files with a mix and files
 with the plain downmix in the same launch.  A file whose decode status is not clean decides nothing and writes nothing.
 
+A scheduled source (io.schedule_source, io.timeline_source: RawSched, flac.FlacSched, sndfmt.AdpcmSched and its Microsoft twin) is
+the two-step source of its format with a downmix that differs from one stretch of the file to the next (include/iss.h,
+"Schedules"): a resample.Schedule the caller gave, or -- `sched` None -- the one its own timeline decides, the file surveyed in
+blocks by ONE iss_*survey_blocks call of its class and resampled by ONE iss_resample_staged_sched launch from the bytes that are
+there.  `parts` 1, `size` the downmix's length, `decision` = (survey.SurveyTimeline or None, the schedule) once launched.
+
 A file set (io.FileSet: one file per channel or group of channels; io.set_source and the calls above given a tuple or list of
 paths) is a source of three classes of its own -- `SetSource`, `SetSurvey`, `SetAuto` (two_step) --, which stand to the
 interleaved twin of the set as RawSource, RawSurvey and RawAuto stand to a file: the same rows, selections, mixes and decisions,
@@ -484,6 +490,105 @@ class CodedAuto(AutoSource):
             rows.append((k, s.s.n, s.s.ch, s.stage_format, ctx.resample_filter(s.s.sr)[0], 0, jobs[k].dst, s.size))
         if rows:
             ctx.resample_staged(cls.coder, payload, rows, -1, mixes=mixes)
+        return status
+
+
+# ---------------------------------------------------------------------------------------------- schedules and timelines
+class SchedSource:
+    """What the scheduled sources share (a mixin in front of a two-step class of its format: RawSched, flac.FlacSched,
+    sndfmt.AdpcmSched and its Microsoft twin; io.schedule_source, io.timeline_source).  `sched`: a resample.Schedule the caller
+    gave, or None for "decide it": the file is then surveyed in blocks of `block_chunks` chunks (include/iss.h, "Survey blocks")
+    and its schedule is survey.SurveyTimeline.safe_schedule().  `decision`: None until the launch, then (timeline, schedule) --
+    (None, schedule) for a schedule that was given."""
+    __slots__ = ()
+
+    def blocks_of(self, frames):
+        """K of this source's job of a blocked survey: its block_chunks, or for a given schedule all its chunks (one block)."""
+        return self.block_chunks if self.sched is None else max(1, -(-frames // resample.SURVEY_CHUNK))
+
+    def decide_blocks(self, whole, blocks, sr):
+        """-> the schedule: the one given, or the one the timeline of these survey fields suggests."""
+        from .survey import ChannelSurvey, SurveyTimeline
+        if self.sched is not None:
+            self.decision = (None, self.sched)
+            return self.sched
+        per = self.block_chunks * resample.SURVEY_CHUNK
+        timeline = SurveyTimeline(ChannelSurvey(whole, sr, 0), [ChannelSurvey(f, sr, b * per) for b, f in enumerate(blocks)], per)
+        self.decision = (timeline, timeline.safe_schedule())
+        return self.decision[1]
+
+
+SCHED_OF = {}                                         # two-step class of channels='auto' -> its scheduled class
+
+
+def scheduled(auto, sched=None, block_chunks=None):
+    """The source `auto` of io.auto_source as a scheduled source of its format: the same file, bytes and rows."""
+    cls = SCHED_OF[type(auto)]
+    other = cls.__new__(cls)
+    for klass in type(auto).__mro__:
+        for name in getattr(klass, '__slots__', ()):
+            if hasattr(auto, name):
+                setattr(other, name, getattr(auto, name))
+    other.sched, other.block_chunks, other.decision = sched, block_chunks, None
+    return other
+
+
+class RawSched(SchedSource, RawAuto):
+    """A file as stored with a schedule: given (iss_resample_pcm16_sched: one upload, one launch), or decided from its blocked
+    survey (iss_survey_blocks, then iss_resample_staged_sched over the survey's upload).  The files of a pass share the launches:
+    where any of them is to be decided, all ride on the survey's upload."""
+    __slots__ = ('sched', 'block_chunks')
+
+    @staticmethod
+    def launch_auto(ctx, staged, jobs, tables, srcs, n_signal=-1):
+        rows = [s.staged_row(ctx, j.row[0], j.dst) for s, j in zip(srcs, jobs)]
+        if all(s.sched is not None for s in srcs):
+            ctx.resample_sched(staged, rows, [s.decide_blocks(None, None, s.sr) for s in srcs], n_signal)
+            return
+        whole, blocks = ctx.survey_blocks(staged, [j.row for j in jobs], [s.blocks_of(s.x.shape[0]) for s in srcs])      # the one upload
+        payload = ctx.staged_payload(None)
+        scheds = [s.decide_blocks(w, b, s.sr) for s, w, b in zip(srcs, whole, blocks)]
+        ctx.resample_staged_sched(None, payload, rows, scheds, n_signal)
+
+
+SCHED_OF[RawAuto] = RawSched
+
+
+class CodedSched(SchedSource, CodedAuto):
+    """The mixin of a coder's scheduled source (flac.FlacSched, sndfmt.AdpcmSched, sndfmt.MsAdpcmSched): CodedAuto's decode call,
+    then for the staged files of two or more channels without a schedule ONE blocked survey (iss_<coder>_survey_blocks), and ONE
+    iss_resample_staged_sched over what the decode call staged -- a one-channel file by the schedule [(0, None)], which is its
+    samples resampled as they are."""
+    __slots__ = ()
+
+    @classmethod
+    def launch_auto(cls, ctx, staged, jobs, tables, srcs, n_signal=-1):
+        status = cls.launch(ctx, staged, [j.row for j in jobs], tables, n_signal)      # the one decode call
+        to_stage = [k for k, s in enumerate(srcs) if s.kind == 'stage']
+        if not to_stage:
+            return status
+        payload = ctx.staged_payload(cls.coder)
+        multi = [k for k in to_stage if srcs[k].s.ch > 1 and srcs[k].sched is None]
+        fields = {}
+        if multi:                                                     # (the survey synchronises: the status is valid after it)
+            rows = [(k, srcs[k].s.n, srcs[k].s.ch, srcs[k].stage_format, srcs[k].full) for k in multi]
+            whole, blocks = ctx.survey_blocks(None, rows, [srcs[k].blocks_of(srcs[k].s.n) for k in multi], coder=cls.coder)
+            fields = dict(zip(multi, zip(whole, blocks)))
+        ubeg = np.concatenate(([0], np.cumsum([s.units for s in srcs])))
+        rows, scheds = [], []
+        for k in to_stage:
+            s = srcs[k]
+            if multi and np.any(status[ubeg[k]:ubeg[k + 1]]):         # a malformed file decides nothing and writes nothing
+                continue
+            if k in fields:
+                scheds.append(s.decide_blocks(*fields[k], s.s.sr))
+            elif s.sched is not None:
+                scheds.append(s.decide_blocks(None, None, s.s.sr))
+            else:
+                scheds.append(resample.Schedule([(0, None)]))         # one channel: nothing to decide
+            rows.append((k, s.s.n, s.s.ch, s.stage_format, ctx.resample_filter(s.s.sr)[0], 0, jobs[k].dst, s.size))
+        if rows:
+            ctx.resample_staged_sched(cls.coder, payload, rows, scheds, -1)
         return status
 
 

@@ -138,6 +138,101 @@ class ChannelSurvey:
         return f'ChannelSurvey({self.channels} channels, frames [{self.first}, {self.first + self.n}) at {self.sr} Hz)'
 
 
+DEFAULT_BLOCK_SEC = 10.0         # a definition: the block length of a timeline where none is given
+
+
+def block_chunks(block_sec, sr):
+    """K of include/iss.h's "Survey blocks": a block holds K = max(1, floor(block_sec * sr / 1024 + 0.5)) chunks of
+    resample.SURVEY_CHUNK frames.  ValueError for a block_sec that is not a finite number above 0."""
+    if isinstance(block_sec, (bool, np.bool_)) or not isinstance(block_sec, (int, float, np.integer, np.floating)) or \
+            not math.isfinite(block_sec) or not block_sec > 0:
+        raise ValueError(f'block_sec={block_sec!r}: a finite number of seconds above 0')
+    return max(1, math.floor(float(block_sec) * sr / R.SURVEY_CHUNK + 0.5))
+
+
+class SurveyTimeline:
+    """A survey resolved in time (include/iss.h, "Survey blocks"): `whole`, the ChannelSurvey of the whole file; `blocks`, one
+    ChannelSurvey per block of `block_frames` = K * resample.SURVEY_CHUNK stored frames counted from frame 0, the last block
+    shorter.  Block b is the survey of frames [b * block_frames, min((b + 1) * block_frames, n)) to the bit.  Equal to another
+    when `whole`, every block and block_frames are equal -- to the bit, as ChannelSurvey.__eq__ is."""
+    __slots__ = ('whole', 'blocks', 'block_frames')
+
+    def __init__(self, whole, blocks, block_frames):
+        self.whole, self.blocks, self.block_frames = whole, list(blocks), int(block_frames)
+
+    sr = property(lambda self: self.whole.sr)
+    n = property(lambda self: self.whole.n)
+    channels = property(lambda self: self.whole.channels)
+
+    def __eq__(self, other):
+        if not isinstance(other, SurveyTimeline):
+            return NotImplemented
+        return self.block_frames == other.block_frames and self.whole == other.whole and len(self.blocks) == len(other.blocks) \
+            and all(a == b for a, b in zip(self.blocks, other.blocks))
+
+    __hash__ = None
+
+    def safe_schedule(self):
+        """The schedule this timeline suggests -> a resample.Schedule.  A definition, as ChannelSurvey.safe_mix() is: block b
+        decides blocks[b].safe_mix() alone, adjacent blocks with equal decisions merge into one run, and run begins are block
+        begins.  Pure Python over measured fields, so timelines equal to the bit decide equally.  Known properties: the
+        reference channel of safe_mix() may change from block to block, so an inverted pair may come out as (L - R)/2 in one
+        run and (R - L)/2 in the next; a run that keeps one of two channels is 6 dB above its (L + R)/2 neighbours; either
+        leaves a discontinuity of one filter length at the boundary.  No hysteresis, crossfade or minimum run length."""
+        return R.Schedule((begin, mix) for begin, _, mix in self.runs())
+
+    def runs(self):
+        """[(begin frame, [block indices], mix or None)] per run of safe_schedule()."""
+        out = []
+        for b, blk in enumerate(self.blocks):
+            mix = blk.safe_mix()
+            if out and out[-1][2] == mix:
+                out[-1][1].append(b)
+            else:
+                out.append((b * self.block_frames, [b], mix))
+        return out or [(0, [], None)]
+
+    def __repr__(self):
+        return f'SurveyTimeline({len(self.blocks)} blocks of {self.block_frames} frames, {self.whole!r})'
+
+
+SCHEDULE_DECISION_COLUMNS = ('path', 'start', 'stop', 'blocks', 'plan', 'kept', 'flipped', 'downmix_loss_db')
+
+
+def write_schedule_decisions_tsv(dst, names, decisions, failed=None):
+    """The table `--channels auto --auto-block SEC --decisions` of scripts/ina_speech_segmenter_amd.py writes: one row per run of
+    every file of `names`, in that order, under SCHEDULE_DECISION_COLUMNS.  decisions = [(path, timeline, schedule)] as
+    batch_process(channels='auto', auto_block_sec=..., decisions=...) collects them.  start, stop: the run's first frame and
+    the next run's (the file's end for the last) / sr, six decimals; blocks: how many blocks the run holds; plan, kept, flipped
+    as write_decisions_tsv states them (`mono`: one row, no timeline); downmix_loss_db: the lowest of the run's blocks (empty
+    where they have none).  A file in `failed` (path -> error text), or one without a decision, gets one row with plan `!` and
+    the text in the last column.  A path listed more than once takes its decisions in their order."""
+    by_name = {}
+    for d in decisions:
+        by_name.setdefault(d[0], []).append(d)
+    failed = failed or {}
+    with open(dst, 'w') as f:
+        f.write('\t'.join(SCHEDULE_DECISION_COLUMNS) + '\n')
+        for name in names:
+            if name in failed or not by_name.get(name):
+                text = str(failed.get(name, 'not processed')).replace('\t', ' ').replace('\n', ' ')
+                f.write('\t'.join([name, '', '', '', '!', '', '', text]) + '\n')
+                continue
+            _, timeline, _ = by_name[name].pop(0)
+            if timeline is None:
+                f.write('\t'.join([name, '', '', '', 'mono', '0', '', '']) + '\n')
+                continue
+            runs, sr, n = timeline.runs(), timeline.sr, timeline.n
+            for k, (begin, blocks, mix) in enumerate(runs):
+                stop = runs[k + 1][0] if k + 1 < len(runs) else n
+                losses = [timeline.blocks[b].downmix_loss_db for b in blocks]
+                losses = [v for v in losses if v is not None]
+                terms = [(c, 1.0) for c in range(timeline.channels)] if mix is None else mix.terms
+                f.write('\t'.join([name, f'{begin / sr:.6f}', f'{stop / sr:.6f}', str(len(blocks)), 'plain' if mix is None else 'mix',
+                                   ','.join(str(c) for c, _ in terms), ','.join(str(c) for c, w in terms if w < 0),
+                                   repr(min(losses)) if losses else '']) + '\n')
+
+
 TSV_COLUMNS = ('path', 'channel', 'frames', 'peak', 'rms_db', 'dc', 'zeros', 'fullscale', 'nonfinite', 'active')
 
 

@@ -603,6 +603,80 @@ int iss_resample_staged_set(iss_ctx* ctx, int32_t origin, int64_t payload, const
                             const iss_mixset* mixsets, const iss_mix* mixes, int64_t nmixes, const iss_mix_term* terms,
                             int64_t nterms);
 
+/* Schedules: a downmix that differs from one stretch of a file to the next.  A SCHEDULE of a file with n stored frames and C
+ * channels is R >= 1 RUNS (begin_r, mix_r): begin_0 = 0 and the begins strictly ascending, in stored frames at the file's own
+ * rate; mix_r a mix of "Mixes" or NONE.  Run r governs the frames [begin_r, begin_{r+1}), the last run to the end; a run that
+ * begins at or past n governs nothing and is allowed.  The scheduled mono signal is m[j] = mixdown(x[j, :], mix_{r(j)}), in
+ * float64 with the arithmetic of "Mixes": terms in order, every product, sum and the one division rounded on its own.  NONE
+ * stands for the mix of all C channels in order with w = 1, d = C: by the second identity of "Mixes" the plain downmix, to the
+ * bit.  Frames outside [0, n) are 0.0.  m is then resampled and quantised exactly as ever, so the FIR taps of outputs near a
+ * boundary see samples of both runs: that is the definition, not an artefact (inaspeechsegmenter_amd/resample.py's
+ * schedule_ref, to the bit).  Two identities: the schedule [(0, NONE)] gives the plain call's output, and [(0, mix)] what a
+ * mix call gives for that one mix.
+ * Tables of a call: a schedule row beside every job row (scheds[k] belongs to jobs[k]), the call's run rows runs[0, nruns) --
+ * a job's runs are rows [run_begin, run_begin + run_count), run_count 1 .. 2^20 -- and the mix and term rows of a mix call; a
+ * run's `mix` is a row of `mixes`, or -1 for NONE.  Every job writes ONE output of frames_out samples at dst_offset.
+ * The kernel is resample_kernel's SCHED instantiation (a pair: the WAV five, and all formats).  Geometry:
+ * iss_resample_split_geometry for one row.  A workgroup finds the runs of the first and the last frame of its span once (the
+ * same for all its lanes); where they are one run -- nearly every tile of a real file -- it stages as a mix call stages one mix,
+ * else each frame finds its run between those two.  Device table, 16-byte rows behind the job rows and the mix-set rows (one per
+ * job, whose mix_begin names the job's schedule row): the call's mix rows and one all-channel mix per job with a NONE run, their
+ * term rows, one {run_begin, run_count} row per job, then run rows {int64 begin_frame; int32 mix; int32 reserved}, every index
+ * counted in 16-byte rows from the first mix row.
+ *   iss_resample_pcm16_sched   the plain call's arguments, `windows` (which must be NULL: a schedule governs whole sources)
+ *                              and the tables above.  One upload, one launch.
+ *   iss_resample_staged_sched  the same over the bytes an origin holds: origins, payload ids and row matching exactly as
+ *                              iss_resample_staged_mix, so FLAC, IMA and Microsoft ADPCM files ride on what their decode call
+ *                              staged and a surveyed file on the survey's upload.
+ * ISS_EINVAL (checked before anything is launched or the context changes, the text names the job): run_count < 1 or above 2^20,
+ * run rows outside [0, nruns), a first begin that is not 0, begins not strictly ascending or negative, a mix index outside
+ * [-1, nmixes), windows passed with a schedule, and for every mix a run names everything iss_resample_pcm16_mix refuses of a
+ * mix (term rows, channels, weights, divisor), as well as everything it refuses of a job.  ISS_ESTATE as for
+ * iss_resample_staged_mix.  iss_resample_stats counts one launch per call and one job per job row.  Every other entry point is
+ * unchanged, to the bit and to the launch.                                                                                      */
+typedef struct {
+    int32_t run_begin;     /* the job's rows of `runs`: [run_begin, run_begin + run_count)                     */
+    int32_t run_count;     /* 1 .. 2^20                                                                       */
+} iss_sched;
+typedef struct {
+    int64_t begin_frame;   /* first stored frame the run governs; 0 for a job's first run, strictly ascending  */
+    int32_t mix;           /* a row of `mixes`, or -1: the plain downmix of all channels                       */
+    int32_t reserved;      /* 0                                                                               */
+} iss_sched_run;
+int iss_resample_pcm16_sched(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
+                             const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_sched* scheds,
+                             const iss_sched_run* runs, int64_t nruns, const iss_mix* mixes, int64_t nmixes,
+                             const iss_mix_term* terms, int64_t nterms);
+int iss_resample_staged_sched(iss_ctx* ctx, int32_t origin, int64_t payload, const iss_resample_job* jobs,
+                              const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_sched* scheds,
+                              const iss_sched_run* runs, int64_t nruns, const iss_mix* mixes, int64_t nmixes,
+                              const iss_mix_term* terms, int64_t nterms);
+
+/* Survey blocks: a survey resolved in time.  A TIMELINE cuts a file's stored frames into BLOCKS of B = K * 1024 frames counted
+ * from frame 0: 1024 is ISS_SURVEY_CHUNK, K = max(1, floor(block_sec * sr / 1024 + 0.5)), the default block_sec = 10.0 a
+ * definition.  The last block is shorter.  Block b's survey is the survey of frames [b * B, min((b + 1) * B, n)) by "Channel
+ * survey", to the bit in every field.  This needs no new first stage: survey_kernel writes one partial row per 1024-frame
+ * chunk and a block is a run of whole chunks, so a block's sums are its chunk rows added in ascending order from +0.0, its peak
+ * their max and its counts their sums -- what the second stage does per job.  survey_reduce_blocks_kernel: grid ragged over
+ * (job, block, group of 256 words), one thread per word of one block's row, plain stores only.  The whole-file survey comes
+ * out of the same launch of survey_kernel and is reduced over ALL chunk rows, not over the block results (the association
+ * differs): `results` is byte for byte what the twin without blocks writes.
+ *   iss_survey_blocks, iss_flac_survey_blocks, iss_adpcm_survey_blocks, iss_msadpcm_survey_blocks
+ *       the arguments of their iss_*survey twins without windows, block_chunks[njobs] (K of each job, >= 1) and
+ *       `block_results`: one row per block with the layout of a result row, the jobs in order, a job's ceil(ceil(n / 1024) / K)
+ *       blocks ascending.  Payload rules are the twin's: iss_survey_blocks uploads, and leaves a payload in origin
+ *       ISS_STAGED_SURVEY; the codec entries read what the codec's last decode call staged.  A call counts as ONE launch of
+ *       iss_survey_stats, its jobs as jobs.
+ * ISS_EINVAL, nothing launched: a block_chunks entry below 1, a NULL table, everything the twin refuses.                        */
+int iss_survey_blocks(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_survey_job* jobs, int32_t njobs,
+                      const int32_t* block_chunks, void* results, void* block_results);
+int iss_flac_survey_blocks(iss_ctx* ctx, const iss_survey_job* jobs, int32_t njobs, const int32_t* block_chunks, void* results,
+                           void* block_results);
+int iss_adpcm_survey_blocks(iss_ctx* ctx, const iss_survey_job* jobs, int32_t njobs, const int32_t* block_chunks, void* results,
+                            void* block_results);
+int iss_msadpcm_survey_blocks(iss_ctx* ctx, const iss_survey_job* jobs, int32_t njobs, const int32_t* block_chunks, void* results,
+                              void* block_results);
+
 /* Page-locked host memory (hipHostMalloc) for decode buffers and result arrays: copies
  * from / to it are truly asynchronous (pageable memory is staged by the runtime).        */
 int iss_host_alloc(iss_ctx* ctx, size_t bytes, void** out);

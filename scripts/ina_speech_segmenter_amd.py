@@ -88,6 +88,11 @@ def build_parser():
                          "broadcast files) and writes <basename>.ch<k>.<format> per channel; 'auto' surveys every multichannel file "
                          "on the GPU and downmixes it without its dead channels, polarity-inverted channels turned back, from the "
                          "same upload (a healthy file as ever); 'mix' downmixes as ever")
+    ap.add_argument('--auto-block', type=float, default=None, metavar='SEC',
+                    help='with --channels auto: decide the downmix block by block instead of once per file -- every multichannel file '
+                         'is surveyed in blocks of SEC seconds on the GPU and each stretch is downmixed as its own blocks suggest '
+                         '(an item recorded out of phase, a leg that is dead for one call); --decisions then writes one row per '
+                         'stretch: path, start, stop, blocks, plan, kept, flipped, downmix_loss_db')
     ap.add_argument('--decisions', default=None, metavar='OUT.tsv',
                     help="with --channels auto: write what was decided per file to OUT.tsv -- path, plan (mono, plain, mix; '!' for "
                          'a file that failed, with the error text), the channels kept, those of them turned back, and what the '
@@ -127,6 +132,10 @@ def main(argv=None):
         build_parser().error('--channels auto runs on one GPU')
     if args.channels == 'auto' and args.mixes is not None:
         build_parser().error('--mixes and --channels auto exclude each other')
+    if args.auto_block is not None and args.channels != 'auto':
+        build_parser().error('--auto-block goes with --channels auto')
+    if args.auto_block is not None and not (args.auto_block > 0 and args.auto_block < float('inf')):
+        build_parser().error('--auto-block takes a number of seconds above 0')
     if args.decisions is not None and args.channels != 'auto':
         build_parser().error('--decisions goes with --channels auto')
     mixes = None
@@ -184,9 +193,11 @@ def main(argv=None):
         if world == 1 and args.channels == 'auto':
             decisions = []
             lmsg = seg.batch_process(inputs, outputs, verbose=True, output_format=args.export_format, channels='auto',
-                                     decisions=decisions)[3]
+                                     decisions=decisions, **({} if args.auto_block is None else {'auto_block_sec': args.auto_block}))[3]
             if args.decisions is not None:
-                from inaspeechsegmenter_amd.survey import write_decisions_tsv
+                from inaspeechsegmenter_amd.survey import write_decisions_tsv, write_schedule_decisions_tsv
+                if args.auto_block is not None:
+                    write_decisions_tsv = write_schedule_decisions_tsv
                 failed = {dst: text for dst, code, text in lmsg if code == 2}
                 write_decisions_tsv(args.decisions, names, decisions, {src: failed[dst] for src, dst in zip(names, outputs)
                                                                         if dst in failed})

@@ -146,6 +146,23 @@ int main() {
     for (auto& b : bigs) { b.frames_in = int64_t(1) << 39; b.format = ISS_RS_U8; b.src_offset = 0; }
     CHECK(!sv_plan(bigs, nullptr, 5, int64_t(1) << 40, nullptr, nullptr, plan, err));      // past 2^31 - 1 blocks in one grid
 
+    // survey blocks (include/iss.h): K chunks a block, the last shorter; units = blocks x groups of SV_THREADS words; rows per job
+    {
+        const iss_survey_job jb[3] = {job(0, 5 * SV_CHUNK + 1, 2, ISS_RS_I16), job(40000, 1, 17, ISS_RS_I16), job(50000, 4 * SV_CHUNK, 1024, ISS_RS_U8)};
+        const int32_t ks[3] = {2, 3, 4}, zero[3] = {2, 0, 4}, neg[3] = {-1, 3, 4};
+        const int64_t nbytes = 50000 + 4 * SV_CHUNK * 1024;
+        CHECK(sv_plan(jb, nullptr, 3, nbytes, nullptr, nullptr, plan, err, nullptr, nullptr, 0, ks) && plan.blk.size() == 3);
+        CHECK(plan.blk[0].K == 2 && plan.blk[0].wgroups == 1 && plan.blk[0].unit_base == 0 && plan.blk[0].out_off == 0);      // 6 chunks: 3 blocks
+        CHECK(plan.blk[1].unit_base == 3 && plan.blk[1].out_off == 3 * 13 && plan.blk[1].wgroups == 1);                          // 1 chunk: 1 block
+        CHECK(plan.blk[2].unit_base == 4 && plan.blk[2].out_off == 3 * 13 + 102 && plan.blk[2].wgroups == 6 * 1024 / SV_THREADS);  // 1 block
+        CHECK(plan.blk_units == 4 + 24 && plan.blk_words == 3 * 13 + 102 + 6 * 1024 && plan.res_words == 13 + 102 + 6 * 1024);
+        CHECK(!sv_plan(jb, nullptr, 3, nbytes, nullptr, nullptr, plan, err, nullptr, nullptr, 0, zero) && err.find("job 1: block_chunks 0") == 0);
+        CHECK(!sv_plan(jb, nullptr, 3, nbytes, nullptr, nullptr, plan, err, nullptr, nullptr, 0, neg) && err.find("job 0: block_chunks -1") == 0);
+        const iss_window w[3] = {{0, 5 * SV_CHUNK + 1, 5 * SV_CHUNK + 1, 0, 10}, {0, 1, 1, 0, 1}, {0, 4 * SV_CHUNK, 4 * SV_CHUNK, 0, 5}};
+        CHECK(!sv_plan(jb, w, 3, nbytes, nullptr, nullptr, plan, err, nullptr, nullptr, 0, ks));      // no windows with blocks
+        CHECK(sv_plan(jb, nullptr, 3, nbytes, nullptr, nullptr, plan, err) && plan.blk.empty() && plan.blk_units == 0);
+    }
+
     printf("survey_plan_check: %d checks passed\n", checks);
     return 0;
 }
