@@ -137,6 +137,21 @@ def _sched_rows(scheds, njobs):
     return sc, runs, rows, terms
 
 
+def _sched_fades(scheds, fades, nruns):
+    """The half-widths of a *_sched_fade entry point (include/iss.h, "Fades"), one int32 per run row, or None where no run
+    fades in: then the *_sched entry point is called.  fades: None -- what the resample.Schedule objects among `scheds` carry --,
+    or the array itself (with schedules given as arrays, or to hand the library rows a Schedule would refuse)."""
+    given = fades is not None
+    if not given:
+        if isinstance(scheds, tuple) and len(scheds) == 4 and isinstance(scheds[0], np.ndarray):
+            return None
+        fades = [h for s in scheds for h in (getattr(s, 'fades', None) or (0,) * len(list(s)))]
+    fades = np.ascontiguousarray(fades, dtype=np.int32).reshape(-1)
+    if fades.size != nruns:
+        raise ValueError(f'{fades.size} fades for {nruns} runs')
+    return fades if given or fades.any() else None      # (an array given goes to the library as it is, all 0 or not)
+
+
 def _set_rows(jb, members):
     """(job rows, SET rows, SET_MEMBER rows) for a *_set entry point (include/iss.h, "File sets").  members: per job a list of
     `(byte offset, frames, channels)`, the offset counted from the job row's src_offset -- where the job's payload lies in the
@@ -216,6 +231,8 @@ def lib():
         'iss_resample_staged_mix': (C.c_int, [vp, i32, i64, vp, vp, i32, i64, vp, vp, i64, vp, i64]),
         'iss_resample_pcm16_sched': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, vp, vp, i64, vp, i64, vp, i64]),
         'iss_resample_staged_sched': (C.c_int, [vp, i32, i64, vp, vp, i32, i64, vp, vp, i64, vp, i64, vp, i64]),
+        'iss_resample_pcm16_sched_fade': (C.c_int, [vp, vp, i64, vp, vp, i32, i64, vp, vp, i64, vp, vp, i64, vp, i64]),
+        'iss_resample_staged_sched_fade': (C.c_int, [vp, i32, i64, vp, vp, i32, i64, vp, vp, i64, vp, vp, i64, vp, i64]),
         'iss_survey_blocks': (C.c_int, [vp, vp, i64, vp, i32, pi32, vp, vp]),
         'iss_flac_survey_blocks': (C.c_int, [vp, vp, i32, pi32, vp, vp]),
         'iss_adpcm_survey_blocks': (C.c_int, [vp, vp, i32, pi32, vp, vp]),
@@ -581,33 +598,40 @@ class Context:
 
     # ---- schedules (iss_resample_*_sched): a downmix that differs from one stretch of a file to the next
     @staticmethod
-    def _sched_args(scheds, njobs):
+    def _sched_args(scheds, njobs, fades=None):
+        """(arrays to keep alive, the entry point's suffix, its arguments from `scheds` on): '_fade' and the half-widths behind the
+        run rows where a run fades in, else '' and the arguments of the call without fades."""
         sc, runs, rows, terms = tables = _sched_rows(scheds, njobs)
-        return tables, (C.c_void_p(sc.ctypes.data), C.c_void_p(runs.ctypes.data), runs.size, C.c_void_p(rows.ctypes.data), rows.size,
-                        C.c_void_p(terms.ctypes.data), terms.size)
+        fd = _sched_fades(scheds, fades, runs.size)
+        mix = (C.c_void_p(rows.ctypes.data), rows.size, C.c_void_p(terms.ctypes.data), terms.size)
+        head = (C.c_void_p(sc.ctypes.data), C.c_void_p(runs.ctypes.data), runs.size)
+        if fd is None:
+            return tables, '', head + mix
+        return tables + (fd,), '_fade', head + (C.c_void_p(fd.ctypes.data),) + mix
 
-    def resample_sched(self, src, jobs, scheds, n_signal=-1, windows=None):
+    def resample_sched(self, src, jobs, scheds, n_signal=-1, windows=None, fades=None):
         """iss_resample_pcm16_sched: `resample` with one schedule per job (a resample.Schedule, or [(begin_frame, mix or None)]) in
         place of splits or mixes: every job writes one signal, frame j of its source mixed by the mix of the run that governs it.
-        One H2D copy, one launch.  windows: refused by the library (a schedule governs whole sources)."""
+        One H2D copy, one launch.  windows: refused by the library (a schedule governs whole sources).  Where a schedule carries
+        a non-zero fade (or `fades`, one half-width per run row of the call, does): iss_resample_pcm16_sched_fade."""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         jb = np.ascontiguousarray(np.array(jobs, dtype=RS_JOB).reshape(-1))
         wn = None if windows is None else _window_rows(windows, jb.size)
-        keep, args = self._sched_args(scheds, jb.size)
-        self._ck(self._L.iss_resample_pcm16_sched(
+        keep, sfx, args = self._sched_args(scheds, jb.size, fades)
+        self._ck(getattr(self._L, 'iss_resample_pcm16_sched' + sfx)(
             self._h, C.c_void_p(src.ctypes.data), src.size, C.c_void_p(jb.ctypes.data), None if wn is None else C.c_void_p(wn.ctypes.data),
-            jb.size, int(n_signal), *args), 'iss_resample_pcm16_sched')
+            jb.size, int(n_signal), *args), 'iss_resample_pcm16_sched' + sfx)
         self._keep_rs = src         # the async H2D copy reads it until the next sync
 
-    def resample_staged_sched(self, coder, payload, jobs, scheds, n_signal=-1, windows=None):
-        """iss_resample_staged_sched: `resample_sched` over the bytes of payload `payload` of origin `coder`, as
-        `resample_staged` reads them; nothing is uploaded but rows."""
+    def resample_staged_sched(self, coder, payload, jobs, scheds, n_signal=-1, windows=None, fades=None):
+        """iss_resample_staged_sched (with fades: iss_resample_staged_sched_fade): `resample_sched` over the bytes of payload
+        `payload` of origin `coder`, as `resample_staged` reads them; nothing is uploaded but rows."""
         jb = np.ascontiguousarray(np.array(jobs, dtype=RS_JOB).reshape(-1))
         wn = None if windows is None else _window_rows(windows, jb.size)
-        keep, args = self._sched_args(scheds, jb.size)
-        self._ck(self._L.iss_resample_staged_sched(
+        keep, sfx, args = self._sched_args(scheds, jb.size, fades)
+        self._ck(getattr(self._L, 'iss_resample_staged_sched' + sfx)(
             self._h, STAGED_ORIGIN[coder], int(payload), C.c_void_p(jb.ctypes.data), None if wn is None else C.c_void_p(wn.ctypes.data),
-            jb.size, int(n_signal), *args), 'iss_resample_staged_sched')
+            jb.size, int(n_signal), *args), 'iss_resample_staged_sched' + sfx)
 
     # ---- file sets (iss_*_set): one file per channel or group of channels, read as the interleaved file they stand for
     def resample_set(self, src, jobs, members, n_signal=-1, mixes=None):

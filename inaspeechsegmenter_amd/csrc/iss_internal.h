@@ -239,12 +239,14 @@ struct RsSetTermDev { int64_t off, frames; double weight; int32_t step, pad; };
 static_assert(sizeof(RsMixRow) == 16 && sizeof(RsTermDev) == 16 && sizeof(RsSetTermDev) == 32, "one array of 16-byte rows");
 // a scheduled call (include/iss.h, "Schedules"): a mix call whose every job writes one row; RsMixDev.mix_begin of job k names its
 // RsSchedDev among the 16-byte rows -- mix rows, term rows, one RsSchedDev per job, then the RsRunDev rows --, every index counted
-// from the first mix row.  run_begin: the job's first RsRunDev; RsRunDev.mix: the RsMixRow the run's frames are mixed by
+// from the first mix row.  run_begin: the job's first RsRunDev; RsRunDev.mix: the RsMixRow the run's frames are mixed by;
+// RsRunDev.half: the half-width of the run's fade zone (include/iss.h, "Fades"; 0 in every call without fades)
 struct RsSchedDev { int32_t run_begin, run_count; int64_t pad; };
-struct RsRunDev { int64_t begin; int32_t mix, pad; };
+struct RsRunDev { int64_t begin; int32_t mix, half; };
 static_assert(sizeof(RsSchedDev) == 16 && sizeof(RsRunDev) == 16, "one array of 16-byte rows");
-// the two tables of a *_sched entry point; `scheds` one per job
-struct IssSchedTables { const iss_sched* scheds; const iss_sched_run* runs; int64_t nruns; };
+// the two tables of a *_sched entry point; `scheds` one per job.  `fades`: the half-widths of a *_sched_fade entry point, one per
+// row of `runs` (NULL: a *_sched entry point, every half-width 0)
+struct IssSchedTables { const iss_sched* scheds; const iss_sched_run* runs; int64_t nruns; const int32_t* fades = nullptr; };
 // the three tables of a *_mix entry point (include/iss.h); `sets` one per job
 struct IssMixTables { const iss_mixset* sets; const iss_mix* mixes; int64_t nmixes; const iss_mix_term* terms; int64_t nterms; };
 // the two tables of a *_set entry point; `sets` one per job
@@ -262,6 +264,7 @@ struct IssRsPlan {
     std::vector<RsSchedDev> scheds;       // a scheduled call: one per job, and `sched` says so ...
     std::vector<RsRunDev> runs;           // ... and every job's runs, their mixes resolved to rows of `mixes`
     bool sched = false;
+    bool fade = false;                    // ... a run of which has a fade zone: the FADE instantiation
     int64_t tiles = 0, lds = 0;
 };
 // `ranges`: destination ranges of other writers of the same call, checked for overlap with the jobs' (error texts start with `who`)

@@ -52,6 +52,11 @@
 // run stages exactly as stage_mixes stages one mix; else every frame searches its run between those two (stage_sched).  The
 // planner writes a run without a mix as the mix of all the job's channels (w = 1, d = their count), as the set planner does.
 // Table: job rows, mix-set rows (mix_begin: the job's RsSchedDev), then 16-byte rows: mix rows, term rows, RsSchedDev, RsRunDev.
+//
+// Fades (include/iss.h, "Fades"): FADE = true is one more pair, SCHED with a half-width in every run row, for scheduled calls in
+// which a run cross-fades in over [begin - half, begin + half).  A workgroup whose span lies in one run and touches neither that
+// run's zone nor the head of the next run's stages as SCHED does; any other blends per frame (stage_sched_fade).  A call whose
+// half-widths are all 0 launches the SCHED pair.
 #include "decode_pass.h"
 #include "rs_readers.h"      // to_f64, the Ld* readers, stage_channels: shared with survey.hip
 #include <algorithm>
@@ -168,15 +173,86 @@ __device__ __forceinline__ void stage_sched(const uint8_t* __restrict__ src, int
     }
 }
 
+// frame `f` of a source mixed by row M: the terms in order, every product, sum and the one division rounded on its own
+template <typename L>
+__device__ __forceinline__ double mix_frame(const typename L::type* __restrict__ f, const RsMixRow M, const RsTermDev* __restrict__ rows) {
+    const RsTermDev* t = rows + M.term_begin;
+    double v = __dmul_rn(t[0].weight, L::get(f + t[0].channel));
+    for (int n = 1; n < M.term_count; ++n) v = __dadd_rn(v, __dmul_rn(t[n].weight, L::get(f + t[n].channel)));
+    return __ddiv_rn(v, M.divisor);
+}
+
+// stage_sched for a job whose runs fade in (include/iss.h, "Fades"): run r's zone is [begin_r - half_r, begin_r + half_r), the
+// zones disjoint and in order (the planner saw to both), so a frame of run r lies in r's own zone, in the head of run r + 1's, or
+// in neither.  One run over the whole span and no zone touched: stage_mixes for that mix, as stage_sched.  Else each frame finds
+// its run and stages p + a * (q - p) inside a zone -- p by the earlier run's mix, q by the later one's, a = (2k + 1) / (4 half)
+// for the zone's k-th frame --, the plain mix outside
+template <typename L>
+__device__ __forceinline__ void stage_sched_fade(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
+                                                 double* __restrict__ span, const RsSchedDev* __restrict__ sched,
+                                                 const RsTermDev* __restrict__ rows) {
+    using T = typename L::type;
+    const RsSchedDev S = *sched;
+    const RsRunDev* runs = reinterpret_cast<const RsRunDev*>(rows) + S.run_begin;
+    const RsMixRow* mixes = reinterpret_cast<const RsMixRow*>(rows);
+    const int64_t ja = max(s0, (int64_t)0), jb = min(s0 + len, n_in) - 1;
+    int ra = 0, rb = 0;
+    if (ja <= jb) {
+        ra = run_of(runs, 0, S.run_count - 1, ja);
+        rb = run_of(runs, ra, S.run_count - 1, jb);
+    }
+    ra = __builtin_amdgcn_readfirstlane(ra);
+    rb = __builtin_amdgcn_readfirstlane(rb);
+    if (ra == rb) {
+        const RsRunDev A = runs[ra];
+        bool clear = ja >= A.begin + A.half;               // past the run's own zone ...
+        if (ra + 1 < S.run_count) {                        // ... and before the next run's
+            const RsRunDev B = runs[ra + 1];
+            clear = clear && jb < B.begin - B.half;
+        }
+        if (clear) {
+            stage_mixes<L, false>(src, n_in, ch, s0, len, span, 0, 1, mixes + A.mix, rows, RsWinDev{});
+            return;
+        }
+    }
+    const T* p = reinterpret_cast<const T*>(src);
+    for (int k = threadIdx.x; k < len; k += RS_THREADS) {
+        const int64_t j = s0 + k;
+        double v = 0.0;
+        if (j >= 0 && j < n_in) {
+            const T* f = p + j * ch;
+            const int r = run_of(runs, ra, rb, j);
+            RsRunDev A = runs[r], B = A;                   // A: the earlier run of a blend, B: the later one, whose zone it is
+            bool blend = j < A.begin + A.half;             // (half > 0 only from run 1 on)
+            if (blend) A = runs[r - 1];
+            else if (r + 1 < S.run_count) {
+                B = runs[r + 1];
+                blend = j >= B.begin - B.half;
+            }
+            v = mix_frame<L>(f, mixes[A.mix], rows);
+            if (blend) {
+                const double q = mix_frame<L>(f, mixes[B.mix], rows);
+                const double a = __ddiv_rn((double)(2 * (j - (B.begin - B.half)) + 1), (double)(4 * (int64_t)B.half));
+                v = __dadd_rn(v, __dmul_rn(a, __dsub_rn(q, v)));
+            }
+        }
+        span[k] = v;
+    }
+}
+
 // what a workgroup of a SPLIT launch stages: the downmix (gc == 0), or channels [c0, c0 + gc) of its job's selection;
 // of a MIX launch: the downmix, or the gc mixes from `mix` on (rows of the 16-byte table `rows`, which holds their terms too)
 // of a SCHED launch: one row by the job's schedule, the RsSchedDev `mix` points at (a 16-byte row of `rows`, as the mixes its
 // runs name are)
 struct RsGroup { int64_t dst_stride; int stride, c0, gc; const int32_t* sel; const RsMixRow* mix; const RsTermDev* rows; };
 
-template <typename L, bool WIN, bool SPLIT, bool MIX, bool SET, bool SCHED = false>
+template <typename L, bool WIN, bool SPLIT, bool MIX, bool SET, bool SCHED = false, bool FADE = false>
 __device__ __forceinline__ void stage(const uint8_t* __restrict__ src, int64_t n_in, int ch, int64_t s0, int len,
                                       double* __restrict__ span, const RsWinDev& W, const RsGroup& G) {
+    if constexpr (FADE) {                                  // a scheduled call, a run of which fades in
+        stage_sched_fade<L>(src, n_in, ch, s0, len, span, reinterpret_cast<const RsSchedDev*>(G.mix), G.rows);
+        return;
+    }
     if constexpr (SCHED) {                                 // every job of a scheduled call has a schedule
         stage_sched<L>(src, n_in, ch, s0, len, span, reinterpret_cast<const RsSchedDev*>(G.mix), G.rows);
         return;
@@ -220,13 +296,16 @@ __device__ __forceinline__ void compute_tile(const RsJobDev& J, const double* __
 // file set: the tables are a mix call's, the term rows RsSetTermDev in the place of RsTermDev, and stage_set_mixes reads them.
 // SCHED = true (only with MIX, never with WIN or SET; include/iss.h, "Schedules") is the pair for calls whose jobs carry a
 // schedule: the tables are a mix call's with the schedule and run rows behind the term rows, and stage_sched reads them.
-#define RS_STAGE(L) stage<L, WIN, SPLIT, MIX, SET, SCHED>(s, J.n_in, J.ch, s0, len, span, W, G)
-template <bool EXT, bool WIN, bool SPLIT, bool MIX = false, bool SET = false, bool SCHED = false>
+// FADE = true (only with SCHED; include/iss.h, "Fades") is the pair for scheduled calls in which a run has a fade zone: the same
+// tables, the run rows' half-widths read as well, and stage_sched_fade stages.
+#define RS_STAGE(L) stage<L, WIN, SPLIT, MIX, SET, SCHED, FADE>(s, J.n_in, J.ch, s0, len, span, W, G)
+template <bool EXT, bool WIN, bool SPLIT, bool MIX = false, bool SET = false, bool SCHED = false, bool FADE = false>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const uint8_t* __restrict__ src, const RsJobDev* __restrict__ jobs,
                                                               int njobs, int16_t* __restrict__ dst) {
     static_assert(!(SPLIT && MIX), "a call carries split rows or mix-set rows");
     static_assert(!SET || (MIX && !WIN), "a set call is a mix call over whole sources");
     static_assert(!SCHED || (MIX && !WIN && !SET), "a scheduled call is a mix call over whole interleaved sources");
+    static_assert(!FADE || SCHED, "fades belong to the runs of a schedule");
     extern __shared__ __attribute__((aligned(16))) double rs_smem[];
     const int64_t b = blockIdx.x;
     int lo = 0, hi = njobs - 1;                                             // last job whose tile_base <= b
@@ -414,8 +493,9 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
     plan.scheds.clear();
     plan.runs.clear();
     plan.sched = sched != nullptr;
+    plan.fade = false;
     if (sched && (!mix || wins || splits || set || (njobs > 0 && !sched->scheds) || sched->nruns < 0 || sched->nruns > 0x3fffffffLL ||
-                  (sched->nruns > 0 && !sched->runs)))
+                  (sched->nruns > 0 && !sched->runs)))      // (a *_sched_fade entry point saw to its `fades` itself)
         return iss_fail(c, ISS_EINVAL, "%s: bad schedule tables", who);
     std::vector<int32_t> mix_seen;                         // a scheduled call: the last job whose channels mix q was checked against
     std::vector<char> has_none;                            // ... and the jobs with a run that names no mix
@@ -532,6 +612,21 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
                 if (r.mix < -1 || r.mix >= mix->nmixes)
                     return iss_fail(c, ISS_EINVAL, "%s: job %d: run %d: mix %d outside [-1, %lld)", who, k, q, r.mix,
                                     (long long)mix->nmixes);
+                if (sched->fades) {                        // zones [begin - half, begin + half): none for run 0, disjoint and in order
+                    const int32_t h = sched->fades[sc.run_begin + q];
+                    if (h < 0)
+                        return iss_fail(c, ISS_EINVAL, "%s: job %d: run %d: fade half-width %d is negative", who, k, q, h);
+                    if (q == 0 && h != 0)
+                        return iss_fail(c, ISS_EINVAL, "%s: job %d: run 0: fade half-width %d: the first run has nothing to fade from",
+                                        who, k, h);
+                    const int64_t pb = q > 0 ? sched->runs[sc.run_begin + q - 1].begin_frame : 0;      // (no sum that could pass 2^63)
+                    const int32_t ph = q > 0 ? sched->fades[sc.run_begin + q - 1] : 0;
+                    if (q > 0 && pb > r.begin_frame - h - ph)
+                        return iss_fail(c, ISS_EINVAL, "%s: job %d: run %d: its fade zone, %d frames either side of frame %lld, overlaps "
+                                        "that of run %d, %d frames either side of frame %lld", who, k, q, h, (long long)r.begin_frame,
+                                        q - 1, ph, (long long)pb);
+                    plan.fade = plan.fade || h != 0;
+                }
                 if (r.mix < 0) has_none[(size_t)k] = 1;
                 else if (mix_seen[(size_t)r.mix] != k) {
                     if (int rc = check_mix(c, who, k, r.mix, mix->mixes[r.mix], *mix, J.channels)) return rc;
@@ -640,7 +735,9 @@ int iss_resample_plan(iss_ctx* c, const iss_resample_job* jobs, const iss_window
             plan.scheds.push_back(RsSchedDev{(int32_t)(nmix + nterm + njobs + (int64_t)plan.runs.size()), sc.run_count, 0});
             for (int32_t q = 0; q < sc.run_count; ++q) {
                 const iss_sched_run& r = sched->runs[sc.run_begin + q];
-                plan.runs.push_back(RsRunDev{r.begin_frame, r.mix < 0 ? none : r.mix, 0});
+                // (a zone wholly past the file blends no frame: written as none, so that begin + half stays far from 2^63)
+                const int32_t h = sched->fades ? sched->fades[sc.run_begin + q] : 0;
+                plan.runs.push_back(RsRunDev{r.begin_frame, r.mix < 0 ? none : r.mix, r.begin_frame - h >= jobs[k].frames_in ? 0 : h});
             }
             plan.dm[(size_t)k].mix_begin = (int32_t)(nmix + nterm + k);
         }
@@ -688,7 +785,8 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
     if (rc) return rc;
     bool ext = false;                                  // a format newer than the WAV five: the instantiation that reads them all
     for (const RsJobDev& d : dj) ext = ext || d.fmt > ISS_RS_F64;
-    auto kernel = plan.sched ? (ext ? resample_kernel<true, false, false, true, false, true> : resample_kernel<false, false, false, true, false, true>)
+    auto kernel = plan.fade ? (ext ? resample_kernel<true, false, false, true, false, true, true> : resample_kernel<false, false, false, true, false, true, true>)
+                  : plan.sched ? (ext ? resample_kernel<true, false, false, true, false, true> : resample_kernel<false, false, false, true, false, true>)
                   : plan.set ? (ext ? resample_kernel<true, false, false, true, true> : resample_kernel<false, false, false, true, true>)
                   : mix ? (win ? (ext ? resample_kernel<true, true, false, true> : resample_kernel<false, true, false, true>)
                              : (ext ? resample_kernel<true, false, false, true> : resample_kernel<false, false, false, true>))
@@ -717,7 +815,7 @@ int iss_resample_launch(iss_ctx* c, const uint8_t* dev_src, const IssRsPlan& pla
 static int resample_pcm16(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs, int32_t njobs,
                           int64_t n_signal, const iss_window* windows, const iss_split* splits, const int32_t* channel_sel,
                           int64_t nsel, const IssMixTables* mix = nullptr, const IssSchedTables* sched = nullptr) {
-    const char* who = sched ? "iss_resample_pcm16_sched" : mix ? "iss_resample_pcm16_mix" : splits && windows ? "iss_resample_pcm16_windows_split" : splits ? "iss_resample_pcm16_split"
+    const char* who = sched && sched->fades ? "iss_resample_pcm16_sched_fade" : sched ? "iss_resample_pcm16_sched" : mix ? "iss_resample_pcm16_mix" : splits && windows ? "iss_resample_pcm16_windows_split" : splits ? "iss_resample_pcm16_split"
                       : windows ? "iss_resample_pcm16_windows" : "iss_resample_pcm16";
     if (!c || njobs < 0 || (njobs > 0 && !jobs) || src_bytes < 0 || (!src && src_bytes > 0) || (mix && !sched && njobs > 0 && !mix->sets) ||
         (sched && njobs > 0 && !sched->scheds))
@@ -765,6 +863,16 @@ extern "C" int iss_resample_pcm16_sched(iss_ctx* c, const void* src, int64_t src
                                         const iss_mix_term* terms, int64_t nterms) {
     const IssMixTables mix{nullptr, mixes, nmixes, terms, nterms};
     const IssSchedTables sched{scheds, runs, nruns};
+    return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, windows, nullptr, nullptr, 0, &mix, &sched);
+}
+
+extern "C" int iss_resample_pcm16_sched_fade(iss_ctx* c, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
+                                             const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_sched* scheds,
+                                             const iss_sched_run* runs, int64_t nruns, const int32_t* fades, const iss_mix* mixes,
+                                             int64_t nmixes, const iss_mix_term* terms, int64_t nterms) {
+    if (!fades && nruns > 0) return iss_fail(c, ISS_EINVAL, "iss_resample_pcm16_sched_fade: bad argument");
+    const IssMixTables mix{nullptr, mixes, nmixes, terms, nterms};
+    const IssSchedTables sched{scheds, runs, nruns, fades};
     return resample_pcm16(c, src, src_bytes, jobs, njobs, n_signal, windows, nullptr, nullptr, 0, &mix, &sched);
 }
 
@@ -869,6 +977,16 @@ extern "C" int iss_resample_staged_sched(iss_ctx* c, int32_t origin, int64_t pay
                                          const iss_mix_term* terms, int64_t nterms) {
     const IssSchedTables sched{scheds, runs, nruns};
     return resample_staged(c, "iss_resample_staged_sched", origin, payload, jobs, windows, njobs, n_signal, nullptr, mixes, nmixes,
+                           terms, nterms, &sched);
+}
+
+extern "C" int iss_resample_staged_sched_fade(iss_ctx* c, int32_t origin, int64_t payload, const iss_resample_job* jobs,
+                                              const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_sched* scheds,
+                                              const iss_sched_run* runs, int64_t nruns, const int32_t* fades, const iss_mix* mixes,
+                                              int64_t nmixes, const iss_mix_term* terms, int64_t nterms) {
+    if (!fades && nruns > 0) return iss_fail(c, ISS_EINVAL, "iss_resample_staged_sched_fade: bad argument");
+    const IssSchedTables sched{scheds, runs, nruns, fades};
+    return resample_staged(c, "iss_resample_staged_sched_fade", origin, payload, jobs, windows, njobs, n_signal, nullptr, mixes, nmixes,
                            terms, nterms, &sched);
 }
 

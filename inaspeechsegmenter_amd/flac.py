@@ -180,7 +180,7 @@ class FlacAuto(CodedAuto, FlacSource):
 
 class FlacSched(CodedSched, FlacAuto):
     """A FLAC file with a schedule, given or decided from its blocked survey (sources.CodedSched)."""
-    __slots__ = ('sched', 'block_chunks')
+    __slots__ = ('sched', 'block_chunks', 'rule', 'fade_sec')
 
 
 SCHED_OF[FlacAuto] = FlacSched

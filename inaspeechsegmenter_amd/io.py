@@ -840,13 +840,19 @@ def _sched_parsed(medianame, what, resample):
     return h, full
 
 
-def schedule_source(medianame, schedule, resample=False):
+def _fade_arg(fade_sec):
+    """fade_sec of the schedule calls -> seconds; ValueError unless it is a finite number, 0 or above (survey.rule_fade's text)."""
+    from .survey import rule_fade
+    return rule_fade('safe', 0.0 if fade_sec is None else fade_sec)
+
+
+def schedule_source(medianame, schedule, resample=False, fade_sec=0.0):
     """What Segmenter reads for load_pcm_schedule -> (the resample.Schedule, the source).  The schedule is normalised against the
-    file's rate and channels (resample.normalise_schedule, the errors naming the file).  The source is io.auto_source's as a
+    file's rate and channels (resample.normalise_schedule, the errors naming the file; fade_sec: its cross-fades).  The source is io.auto_source's as a
     scheduled source of its class (sources.scheduled); a one-channel file whose every run is the plain downmix is read as ever."""
     from . import sources
     h, full = _sched_parsed(medianame, 'schedules', resample)
-    sched = R.normalise_schedule(schedule, h.sr, h.ch, f'{as_media(medianame)}: schedule')
+    sched = R.normalise_schedule(schedule, h.sr, h.ch, f'{as_media(medianame)}: schedule', _fade_arg(fade_sec))
     if h.n == 0:
         return sched, h.source(resample)
     src = h.auto_source(full)
@@ -859,11 +865,13 @@ def schedule_source(medianame, schedule, resample=False):
     return sched, sources.scheduled(src, sched, None)
 
 
-def timeline_source(medianame, block_sec=None, resample=False):
+def timeline_source(medianame, block_sec=None, resample=False, rule='safe', fade_sec=None):
     """What Segmenter reads for the timeline calls: io.auto_source's source, and for a file of two or more channels that source
-    as a scheduled source that is to decide its schedule from blocks of `block_sec` seconds (survey.block_chunks)."""
+    as a scheduled source that is to decide its schedule from blocks of `block_sec` seconds (survey.block_chunks) by `rule`, its
+    run boundaries cross-faded over `fade_sec` seconds (survey.rule_fade states the defaults and the refusals)."""
     from . import sources
-    from .survey import DEFAULT_BLOCK_SEC, block_chunks
+    from .survey import DEFAULT_BLOCK_SEC, block_chunks, rule_fade
+    fade_sec = rule_fade(rule, fade_sec)
     h, full = _sched_parsed(medianame, 'timelines', resample)
     k = block_chunks(DEFAULT_BLOCK_SEC if block_sec is None else block_sec, h.sr)
     if h.n == 0:
@@ -871,14 +879,14 @@ def timeline_source(medianame, block_sec=None, resample=False):
     src = h.auto_source(full)
     if type(src) not in sources.SCHED_OF:
         return src
-    return sources.scheduled(src, None, k)
+    return sources.scheduled(src, None, k, rule, fade_sec)
 
 
-def decode_schedule(medianame, schedule, resample=True):
+def decode_schedule(medianame, schedule, resample=True, fade_sec=0.0):
     """Host-only twin of Segmenter.load_pcm_schedule: resample.schedule_ref of the stored samples as decode_source decodes them,
-    the schedule normalised against the file's rate and channels."""
+    the schedule normalised against the file's rate and channels, its run boundaries cross-faded over `fade_sec` seconds."""
     h, _ = _sched_parsed(medianame, 'schedules', resample)
-    sched = R.normalise_schedule(schedule, h.sr, h.ch, f'{as_media(medianame)}: schedule')
+    sched = R.normalise_schedule(schedule, h.sr, h.ch, f'{as_media(medianame)}: schedule', _fade_arg(fade_sec))
     x = h.stored()
     if h.ch == 1 and all(m is None for _, m in sched.runs):
         return R.resample_ref(x, h.sr) if h.sr != R.SR_OUT else decode_pcm(medianame, ffmpeg=None)
@@ -898,15 +906,17 @@ def survey_timeline(medianame, block_sec=None):
     return SurveyTimeline(ChannelSurvey(R.survey_ref(x, full, 0, h.n), h.sr, 0), blocks, per)
 
 
-def decode_auto_timeline(medianame, block_sec=None, resample=True):
+def decode_auto_timeline(medianame, block_sec=None, resample=True, rule='safe', fade_sec=None):
     """Host-only twin of Segmenter.load_pcm_auto_timeline -> (pcm, timeline, schedule): timeline = survey_timeline(medianame,
-    block_sec), schedule = timeline.safe_schedule(), pcm = decode_schedule(medianame, schedule); a one-channel file gives
-    decode_auto's pcm and (None, None)."""
+    block_sec), schedule = timeline.schedule(rule, fade_sec) -- safe_schedule() by default --, pcm = decode_schedule(medianame,
+    schedule); a one-channel file gives decode_auto's pcm and (None, None)."""
+    from .survey import rule_fade
+    rule_fade(rule, fade_sec)                              # (the refusals, for a one-channel file too)
     h, _ = _sched_parsed(medianame, 'timelines', resample)
     if not (h.ch > 1 and h.n > 0):
         return decode_auto(medianame, resample)[0], None, None
     timeline = survey_timeline(medianame, block_sec)
-    schedule = timeline.safe_schedule()
+    schedule = timeline.schedule(rule, fade_sec)
     return R.schedule_ref(h.stored(), h.sr, schedule), timeline, schedule
 
 

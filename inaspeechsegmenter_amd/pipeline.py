@@ -302,7 +302,8 @@ DEFAULT_WORKERS = 4               # passes with more contexts in flight overlap 
 
 
 def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch_files=None, batch_seconds=None,
-                  workers=None, decode_threads=4, channels=None, decided=None, auto_block_sec=None):
+                  workers=None, decode_threads=4, channels=None, decided=None, auto_block_sec=None, auto_rule='safe',
+                  auto_fade_sec=None):
     """Segment `linput` with the networks of `seg`; on_result(index, src, lseg | None, errtext | None, secs) is called from
     the worker threads (serialised by a lock) as results become available, lseg = [(label, start_sec, stop_sec)], secs =
     this file's share of the processing time of its device pass (the pass's wall time / its files: what the reference's
@@ -314,7 +315,8 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
     channels='auto': every file downmixed as its own survey suggests (io.auto_source); lseg is one segment list, as without
     `channels`, and decided((src, survey, mix)) is called before on_result for every file that was processed.
     auto_block_sec (with channels='auto'): every file of two or more channels by the schedule its own timeline suggests
-    (io.timeline_source, blocks of that many seconds); decided then gets (src, timeline, schedule)."""
+    (io.timeline_source, blocks of that many seconds, decided by auto_rule and cross-faded over auto_fade_sec seconds); decided
+    then gets (src, timeline, schedule)."""
     multi = channels is not None and channels != 'auto'        # on_result gets a list of segment lists
     batch_files, batch_seconds = _limits(batch_files, batch_seconds)
     workers = workers or DEFAULT_WORKERS
@@ -323,7 +325,8 @@ def process_files(seg, linput, on_result, skip=None, nbtry=1, trydelay=2., batch
     budget = _AudioBudget(2 * batch_seconds * 16000)        # decoded audio waiting for the packer: <= 2 super-batches
     _decode_stage(items, seg.ffmpeg, nbtry, trydelay, dec_q, decode_threads, budget, getattr(seg, 'resample', False),
                   **({} if channels is None else {'channels': channels}),
-                  **({} if auto_block_sec is None else {'auto_block_sec': auto_block_sec}))
+                  **({} if auto_block_sec is None else {'auto_block_sec': auto_block_sec, 'auto_rule': auto_rule,
+                                                         'auto_fade_sec': auto_fade_sec}))
     batch_q = queue.Queue(maxsize=max(2, workers))
     lock = threading.Lock()
     failure = []

@@ -255,10 +255,12 @@ class Schedule:
     """A downmix that changes over time (include/iss.h, "Schedules"): `runs` = ((begin, mix), ...), begin in stored frames at
     the file's own rate -- runs[0] begins at 0, the begins ascend strictly --, mix a `Mix` or None (the plain downmix of all
     channels).  Run r governs the frames [begin_r, begin_{r+1}), the last run to the end; a run at or past the end of the file
-    governs nothing.  Equal to another, or to a list of (begin, mix) pairs, when the runs are equal."""
-    __slots__ = ('runs',)
+    governs nothing.  `fades` (include/iss.h, "Fades"): one half-width h_r >= 0 per run in stored frames, None for all 0; run
+    r >= 1 fades in linearly over [begin_r - h_r, begin_r + h_r), h_0 = 0 and the zones disjoint and in order.  Equal to another
+    when runs and fades are equal, to a list of (begin, mix) pairs when the runs are equal and every fade is 0."""
+    __slots__ = ('runs', 'fades')
 
-    def __init__(self, runs):
+    def __init__(self, runs, fades=None):
         runs = tuple((int(b), m) for b, m in runs)
         if not runs or runs[0][0] != 0:
             raise ValueError(f'schedule: run 0 begins at frame {runs[0][0] if runs else None!r}, not 0')
@@ -269,12 +271,17 @@ class Schedule:
             if m is not None and not isinstance(m, Mix):
                 raise ValueError(f'schedule: run {r}: its mix is a resample.Mix or None, not {m!r}')
         self.runs = runs
+        self.fades = _check_fades(runs, fades)
+
+    @property
+    def faded(self):
+        return any(self.fades)
 
     def __eq__(self, other):
         if isinstance(other, Schedule):
-            return self.runs == other.runs
+            return self.runs == other.runs and self.fades == other.fades
         if isinstance(other, (list, tuple)):
-            return list(self.runs) == [tuple(r) for r in other]
+            return list(self.runs) == [tuple(r) for r in other] and not self.faded
         return NotImplemented
 
     __hash__ = None
@@ -286,13 +293,61 @@ class Schedule:
         return iter(self.runs)
 
     def __repr__(self):
+        if self.faded:
+            return f'Schedule({list(self.runs)!r}, fades={list(self.fades)!r})'
         return f'Schedule({list(self.runs)!r})'
 
 
-def normalise_schedule(spec, sr, channels=None, name='schedule'):
+def _check_fades(runs, fades):
+    """The half-widths of a schedule's runs as a tuple of ints, validated as include/iss.h's "Fades" states."""
+    if fades is None:
+        return (0,) * len(runs)
+    try:
+        fades = tuple(fades)
+    except TypeError:
+        raise ValueError(f'schedule: fades are one half-width per run, not {fades!r}') from None
+    if len(fades) != len(runs):
+        raise ValueError(f'schedule: {len(fades)} fades for {len(runs)} runs: one half-width per run')
+    for r, h in enumerate(fades):
+        if isinstance(h, (bool, np.bool_)) or not isinstance(h, (int, np.integer)):
+            raise ValueError(f'schedule: run {r}: its fade is a whole number of frames, not {h!r}')
+        if h < 0:
+            raise ValueError(f'schedule: run {r}: fade half-width {int(h)} is negative')
+    fades = tuple(int(h) for h in fades)
+    if fades[0] != 0:
+        raise ValueError(f'schedule: run 0: fade half-width {fades[0]}: the first run has nothing to fade from')
+    for r in range(1, len(runs)):
+        if runs[r - 1][0] + fades[r - 1] > runs[r][0] - fades[r]:
+            raise ValueError(f'schedule: run {r}: its fade zone [{runs[r][0] - fades[r]}, {runs[r][0] + fades[r]}) overlaps that of '
+                             f'run {r - 1}, which ends at {runs[r - 1][0] + fades[r - 1]}')
+    return fades
+
+
+def fade_halves(begins, fade_sec, sr):
+    """Half-widths for runs that begin at `begins` (stored frames) and cross-fade over `fade_sec` seconds at `sr` Hz: h =
+    floor(fade_sec * sr / 2 + 0.5), and h_r = min(h, (begin_r - begin_{r-1}) // 2, (begin_{r+1} - begin_r) // 2) with no upper
+    term for the last run, h_0 = 0: every run gives at most half its length to each side, so the zones are disjoint by
+    construction.  ValueError: a fade that is negative or not finite."""
+    if isinstance(fade_sec, (bool, np.bool_)) or not isinstance(fade_sec, (int, float, np.integer, np.floating)) or \
+            not math.isfinite(fade_sec) or fade_sec < 0:
+        raise ValueError(f'fade_sec: {fade_sec!r} s is negative, not finite or not a number')
+    begins = [int(b) for b in begins]
+    h = math.floor(float(fade_sec) * sr / 2 + 0.5)
+    out = [0] * len(begins)
+    for r in range(1, len(begins)):
+        hr = min(h, (begins[r] - begins[r - 1]) // 2)
+        if r + 1 < len(begins):
+            hr = min(hr, (begins[r + 1] - begins[r]) // 2)
+        out[r] = hr
+    return out
+
+
+def normalise_schedule(spec, sr, channels=None, name='schedule', fade_sec=0.0):
     """A schedule specification [(start_sec, mix), ...] for a file at `sr` Hz -> a `Schedule`: begin = floor(start_sec * sr +
     0.5), the rounding of segment_excerpts; a mix spelt as normalise_mixes states, or None.  A `Schedule` (begins in frames
-    already) has its mixes checked against `channels` and is handed on.  ValueError naming `name`, the run and the reason: an
+    already) has its mixes checked against `channels` and is handed on.  fade_sec > 0: the result cross-fades at every run
+    boundary over `fade_halves(begins, fade_sec, sr)`; a `Schedule` that carries fades of its own is then refused, one without
+    gets them.  ValueError naming `name`, the run and the reason: an
     empty specification, a first start that is not 0, two starts that round to one frame, descending starts, a start that is
     negative or not finite, a channel outside the file's `channels`, and what normalise_mixes refuses of a mix."""
     def is_num(v):
@@ -302,6 +357,12 @@ def normalise_schedule(spec, sr, channels=None, name='schedule'):
         for r, (_, m) in enumerate(spec.runs):
             if m is not None:
                 _one_mix(0, m, channels, f'{name}: run {r}')
+        if fade_sec:
+            if spec.faded:
+                raise ValueError(f'{name}: fade_sec={fade_sec!r} passed with a Schedule that carries fades of its own')
+            if sr is None:
+                raise ValueError(f'{name}: fade_sec={fade_sec!r} needs the rate of the file')
+            return Schedule(spec.runs, fade_halves([b for b, _ in spec.runs], fade_sec, sr))
         return spec
     if spec is None or isinstance(spec, (str, bytes, Mix)) or hasattr(spec, 'items'):
         raise ValueError(f'{name}: a schedule is a sequence of (start_sec, mix) runs, not {spec!r}')
@@ -326,12 +387,15 @@ def normalise_schedule(spec, sr, channels=None, name='schedule'):
         if r > 0 and begin < runs[-1][0]:
             raise ValueError(f'{name}: run {r}: start {start!r} s lies before run {r - 1} ({spec[r - 1][0]!r} s): starts ascend')
         runs.append((begin, None if m is None else _one_mix(0, m, channels, f'{name}: run {r}')))
-    return Schedule(runs)
+    return Schedule(runs, fade_halves([b for b, _ in runs], fade_sec, sr) if fade_sec else None)
 
 
 def schedule_mixdown(x, schedule):
     """Stored samples (n,) or (n, C) -> the scheduled float64 mono signal: frame j mixed by `mixdown` with the mix of the run
-    that governs it, None being the mix of all C channels in order with w = 1, d = C (the plain downmix, to the bit)."""
+    that governs it, None being the mix of all C channels in order with w = 1, d = C (the plain downmix, to the bit).  A
+    schedule with fades (include/iss.h, "Fades"): frame j of run r's zone [begin_r - h_r, begin_r + h_r), k = j - (begin_r -
+    h_r), is p + a * (q - p) with p and q the frame mixed by the runs r - 1 and r and a = (2k + 1) / (4 h_r) -- one division of
+    two exact integers; the difference, the product and the sum rounded on their own, as numpy rounds them."""
     x = np.asarray(x)
     if x.ndim == 1:
         x = x[:, None]
@@ -344,12 +408,23 @@ def schedule_mixdown(x, schedule):
         a, b = min(begins[r], n), min(begins[r + 1], n)
         if b > a:
             out[a:b] = mixdown(x[a:b], plain if m is None else m)
+    for r, h in enumerate(schedule.fades):
+        a, b = max(schedule.runs[r][0] - h, 0), min(schedule.runs[r][0] + h, n)
+        if h == 0 or b <= a:
+            continue
+        (_, m0), (_, m1) = schedule.runs[r - 1], schedule.runs[r]
+        p = mixdown(x[a:b], plain if m0 is None else m0)
+        q = mixdown(x[a:b], plain if m1 is None else m1)
+        k = np.arange(a, b, dtype=np.int64) - (schedule.runs[r][0] - h)
+        alpha = (2 * k + 1).astype(np.float64) / np.float64(4 * h)
+        out[a:b] = p + alpha * (q - p)
     return out
 
 
 def schedule_ref(x, sr, schedule):
-    """The numpy statement of include/iss.h's "Schedules": resample_ref with `schedule_mixdown(x, schedule)` in place of the
-    downmix -> 16 kHz mono int16.  The taps of outputs near a run boundary see samples of both runs: that is the definition."""
+    """The numpy statement of include/iss.h's "Schedules" and "Fades": resample_ref with `schedule_mixdown(x, schedule)` in
+    place of the downmix -> 16 kHz mono int16.  The taps of outputs near a run boundary see samples of both runs: that is the
+    definition."""
     return quantise(resample_float(schedule_mixdown(x, schedule), sr))
 
 

@@ -360,7 +360,8 @@ def _ensure_resident(ctx, mspec):
     return m.shape[0]
 
 
-def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False, channels=None, auto_block_sec=None):
+def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False, channels=None, auto_block_sec=None, auto_rule='safe',
+                 auto_fade_sec=None):
     """decode_pcm's 16 kHz mono samples (a numpy array), or -- without ffmpeg -- a source of sources.py for the device to
     finish.  The file is read once and what io._classify makes of its bytes says what Segmenter reads: a FLAC stream
     becomes a flac.FlacSource (compressed frames, decoded on the device like its WAV twin reads), a file of sndfmt.py what
@@ -369,7 +370,8 @@ def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False, channel
     channels='split' (ffmpeg=None): every channel on its own -- io.split_source's source with all channels selected;
     channels = a list of resample.Mix: those mixes, each on its own -- io.mix_source's source.
     channels='auto' (ffmpeg=None): io.auto_source's source -- one signal, the downmix the file's own survey suggests; with
-    auto_block_sec io.timeline_source's -- the downmix its survey suggests block by block (whole single files).
+    auto_block_sec io.timeline_source's -- the downmix its survey suggests block by block (whole single files), decided by
+    auto_rule and cross-faded over auto_fade_sec seconds.
     A file set (io.FileSet, or a tuple or list of member paths; ffmpeg=None) is read by the same calls: io.set_source's source
     without `channels`.  Whole sets only."""
     medianame = iss_io.as_media(medianame)
@@ -384,7 +386,7 @@ def _load_source(medianame, start_sec, stop_sec, ffmpeg, resample=False, channel
             return iss_io.set_source(medianame, resample)
     if channels is not None:
         if channels == 'auto' and auto_block_sec is not None:
-            return iss_io.timeline_source(medianame, auto_block_sec, resample)
+            return iss_io.timeline_source(medianame, auto_block_sec, resample, auto_rule, auto_fade_sec)
         if channels == 'auto':
             return iss_io.auto_source(medianame, resample)
         if channels != 'split':
@@ -858,21 +860,24 @@ class Segmenter:
             raise ValueError(f'{what} are read without ffmpeg (Segmenter(ffmpeg=None)); ffmpeg={self.ffmpeg!r} downmixes every '
                              f'file with -ac 1')
 
-    def load_pcm_schedule(self, medianame, schedule):
+    def load_pcm_schedule(self, medianame, schedule, fade_sec=0.0):
         """The 16 kHz mono PCM16 of `medianame` downmixed by `schedule` = [(start_sec, mix), ...] (resample.normalise_schedule
         states the spelling; a resample.Schedule counts in stored frames): exactly resample.schedule_ref(stored, sr, schedule),
         stored and sr from io.decode_source -- frame j mixed by the mix of the run that governs it, None being the plain downmix,
         then resampled and quantised as ever, so outputs near a boundary see both runs.  One upload, one decode launch for a coded
         file, ONE resample launch (resample_kernel's SCHED instantiation).  [(0, None)] is load_pcm to the bit, [(0, mix)] is
-        load_pcm_mixes(medianame, [mix])[0].  ValueError naming the file, the run and the reason for a bad schedule; for a file
-        set (whole single files only); naming the argument with ffmpeg set."""
+        load_pcm_mixes(medianame, [mix])[0].  fade_sec > 0: every run but the first fades in linearly over fade_sec seconds centred
+        on its begin, each run giving at most half its length to either side (resample.fade_halves; include/iss.h, "Fades"), in
+        the same single launch (the FADE instantiation); a resample.Schedule may carry its own half-widths instead.  ValueError
+        naming the file, the run and the reason for a bad schedule; for a fade that is negative or not finite; for a file set
+        (whole single files only); naming the argument with ffmpeg set."""
         self._no_ffmpeg_schedule('schedules')
-        return self._mono_pcm(iss_io.schedule_source(medianame, schedule, self.resample)[1])
+        return self._mono_pcm(iss_io.schedule_source(medianame, schedule, self.resample, fade_sec)[1])
 
-    def segment_schedule(self, medianame, schedule):
-        """-> exactly segment_signal(load_pcm_schedule(medianame, schedule)), the samples never leaving the device."""
+    def segment_schedule(self, medianame, schedule, fade_sec=0.0):
+        """-> exactly segment_signal(load_pcm_schedule(medianame, schedule, fade_sec)), the samples never leaving the device."""
         self._no_ffmpeg_schedule('schedules')
-        mspec, loge, difflen = _sig2feats(self.ctx, iss_io.schedule_source(medianame, schedule, self.resample)[1], medianame)
+        mspec, loge, difflen = _sig2feats(self.ctx, iss_io.schedule_source(medianame, schedule, self.resample, fade_sec)[1], medianame)
         return self.segment_feats(mspec, loge, difflen, 0)
 
     def survey_timeline(self, medianame, block_sec=None):
@@ -890,22 +895,25 @@ class Segmenter:
         group.check()
         return sig.decision[0]
 
-    def load_pcm_auto_timeline(self, medianame, block_sec=None):
+    def load_pcm_auto_timeline(self, medianame, block_sec=None, rule='safe', fade_sec=None):
         """load_pcm_auto with decisions that vary over time -> (pcm, timeline, schedule).  A file of two or more channels is
         uploaded once (a coded one decoded once), surveyed in blocks on the device (ONE survey launch) and downmixed from the
         bytes that are there by ONE resample launch: timeline == survey_timeline(medianame, block_sec) to the bit, schedule =
-        timeline.safe_schedule() (survey.py states the rule), pcm exactly load_pcm_schedule(medianame, schedule).  A one-channel
-        file takes load_pcm's path untouched: timeline and schedule are None.  Errors as load_pcm_auto."""
+        timeline.schedule(rule, fade_sec) (survey.py states the rules), pcm exactly load_pcm_schedule(medianame, schedule).  rule
+        'safe' is safe_schedule(): every block on its own, hard cuts unless fade_sec is given.  rule 'steady' is
+        steady_schedule(): one divisor per file, polarity carried from block to block, and the run boundaries cross-faded over
+        fade_sec seconds (None: survey.DEFAULT_FADE_SEC), still in the one resample launch.  A one-channel file takes load_pcm's
+        path untouched: timeline and schedule are None.  Errors as load_pcm_auto; ValueError for a rule that is neither."""
         self._no_ffmpeg_schedule('timelines')
-        sig = iss_io.timeline_source(medianame, block_sec, self.resample)
+        sig = iss_io.timeline_source(medianame, block_sec, self.resample, rule, fade_sec)
         pcm = self._mono_pcm(sig)
         return (pcm,) + (getattr(sig, 'decision', None) or (None, None))
 
-    def segment_auto_timeline(self, medianame, block_sec=None):
+    def segment_auto_timeline(self, medianame, block_sec=None, rule='safe', fade_sec=None):
         """-> (segments, timeline, schedule): timeline and schedule as load_pcm_auto_timeline gives them, segments exactly
         segment_signal(pcm) of its pcm, from the same single upload.  Whole files only."""
         self._no_ffmpeg_schedule('timelines')
-        sig = iss_io.timeline_source(medianame, block_sec, self.resample)
+        sig = iss_io.timeline_source(medianame, block_sec, self.resample, rule, fade_sec)
         mspec, loge, difflen = _sig2feats(self.ctx, sig, medianame)
         return (self.segment_feats(mspec, loge, difflen, 0),) + (getattr(sig, 'decision', None) or (None, None))
 
@@ -1017,7 +1025,7 @@ class Segmenter:
 
     def batch_process(self, linput, loutput, verbose=False, skipifexist=False, nbtry=1, trydelay=2., output_format='csv',
                       batch_files=None, workers=None, batch_seconds=None, channels=None, mixes=None, decisions=None,
-                      auto_block_sec=None):
+                      auto_block_sec=None, auto_rule=None, auto_fade_sec=None):
         """segmenter.py:297-335: same arguments, same (t_batch_dur, nb_processed, avg, lmsg) with
         lmsg entries (dst, code, text), code 0 ok / 1 already exists / 2 error, in input order.
         The files run through pipeline.process_files: decode threads, super-batches of at most `batch_files` files /
@@ -1045,6 +1053,9 @@ class Segmenter:
         the schedule its timeline suggests, the files of a pass and a class in one survey launch and one resample launch as for
         'auto'.  decisions then receives (src, timeline, schedule).  A healthy file writes what plain 'auto' writes.  File sets
         are code-2 entries on this route (whole single files only).
+        auto_rule, auto_fade_sec (with auto_block_sec only; else ValueError): the rule that decides the schedule, 'safe' (the
+        default) or 'steady', and the cross-fade at its run boundaries in seconds (None: 0 for 'safe', survey.DEFAULT_FADE_SEC
+        for 'steady'), as segment_auto_timeline takes them.
         File sets (an extension, ffmpeg=None only): an entry of linput may be an io.FileSet, or a tuple or list of member paths
         -- a recording stored as one file per channel or group of channels.  It is read as its interleaved twin would be, by
         every mode above, the sets of a pass in one launch of their own; its messages and `decisions` carry the set's name, and
@@ -1057,8 +1068,12 @@ class Segmenter:
         if auto_block_sec is not None:
             if not auto:
                 raise ValueError(f"auto_block_sec={auto_block_sec!r} needs channels='auto': it sets the block length of its decisions")
-            from .survey import block_chunks
+            from .survey import block_chunks, rule_fade
             block_chunks(auto_block_sec, 16000)                # (ValueError for a block length that is none)
+            rule_fade(auto_rule or 'safe', auto_fade_sec)      # (... for a rule or a fade that is none)
+        elif auto_rule is not None or auto_fade_sec is not None:
+            what = f'auto_rule={auto_rule!r}' if auto_rule is not None else f'auto_fade_sec={auto_fade_sec!r}'
+            raise ValueError(f"{what} needs auto_block_sec: it shapes the schedule of a timeline")
         if auto:
             if mixes is not None:
                 raise ValueError("mixes and channels='auto' exclude each other: 'auto' derives every file's mix from its survey")
@@ -1119,7 +1134,9 @@ class Segmenter:
         pipeline.process_files(self, linput, on_result, skip=skip, nbtry=nbtry, trydelay=trydelay,
                                batch_files=batch_files, workers=workers, batch_seconds=batch_seconds,
                                **({'channels': 'auto', 'decided': None if decisions is None else decisions.append,
-                                   **({} if auto_block_sec is None else {'auto_block_sec': auto_block_sec})} if auto
+                                   **({} if auto_block_sec is None else {'auto_block_sec': auto_block_sec}),
+                                   **({} if auto_rule is None and auto_fade_sec is None else
+                                      {'auto_rule': auto_rule or 'safe', 'auto_fade_sec': auto_fade_sec})} if auto
                                   else {'channels': channels}))
         lmsg = [m for i in range(len(linput)) for m in (msgs[i] if isinstance(msgs[i], list) else [msgs[i]])]
         t_batch_dur = time.time() - t_batch_start

@@ -657,12 +657,12 @@ class MsAdpcmAuto(AdpcmAuto, MsAdpcmSource):
 
 class AdpcmSched(CodedSched, AdpcmAuto):
     """An IMA ADPCM file with a schedule, given or decided from its blocked survey (sources.CodedSched)."""
-    __slots__ = ('sched', 'block_chunks')
+    __slots__ = ('sched', 'block_chunks', 'rule', 'fade_sec')
 
 
 class MsAdpcmSched(CodedSched, MsAdpcmAuto):
     """A Microsoft ADPCM file with a schedule."""
-    __slots__ = ('sched', 'block_chunks')
+    __slots__ = ('sched', 'block_chunks', 'rule', 'fade_sec')
 
 
 SCHED_OF[AdpcmAuto], SCHED_OF[MsAdpcmAuto] = AdpcmSched, MsAdpcmSched

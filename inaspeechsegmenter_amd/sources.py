@@ -498,8 +498,9 @@ class SchedSource:
     """What the scheduled sources share (a mixin in front of a two-step class of its format: RawSched, flac.FlacSched,
     sndfmt.AdpcmSched and its Microsoft twin; io.schedule_source, io.timeline_source).  `sched`: a resample.Schedule the caller
     gave, or None for "decide it": the file is then surveyed in blocks of `block_chunks` chunks (include/iss.h, "Survey blocks")
-    and its schedule is survey.SurveyTimeline.safe_schedule().  `decision`: None until the launch, then (timeline, schedule) --
-    (None, schedule) for a schedule that was given."""
+    and its schedule is survey.SurveyTimeline.schedule(rule, fade_sec): safe_schedule() by default, steady_schedule() for rule
+    'steady', the run boundaries cross-faded over fade_sec seconds.  `decision`: None until the launch, then (timeline, schedule)
+    -- (None, schedule) for a schedule that was given."""
     __slots__ = ()
 
     def blocks_of(self, frames):
@@ -514,15 +515,16 @@ class SchedSource:
             return self.sched
         per = self.block_chunks * resample.SURVEY_CHUNK
         timeline = SurveyTimeline(ChannelSurvey(whole, sr, 0), [ChannelSurvey(f, sr, b * per) for b, f in enumerate(blocks)], per)
-        self.decision = (timeline, timeline.safe_schedule())
+        self.decision = (timeline, timeline.schedule(self.rule, self.fade_sec))
         return self.decision[1]
 
 
 SCHED_OF = {}                                         # two-step class of channels='auto' -> its scheduled class
 
 
-def scheduled(auto, sched=None, block_chunks=None):
-    """The source `auto` of io.auto_source as a scheduled source of its format: the same file, bytes and rows."""
+def scheduled(auto, sched=None, block_chunks=None, rule='safe', fade_sec=None):
+    """The source `auto` of io.auto_source as a scheduled source of its format: the same file, bytes and rows.  rule, fade_sec:
+    how a schedule that is to be decided is decided (survey.SurveyTimeline.schedule)."""
     cls = SCHED_OF[type(auto)]
     other = cls.__new__(cls)
     for klass in type(auto).__mro__:
@@ -530,6 +532,7 @@ def scheduled(auto, sched=None, block_chunks=None):
             if hasattr(auto, name):
                 setattr(other, name, getattr(auto, name))
     other.sched, other.block_chunks, other.decision = sched, block_chunks, None
+    other.rule, other.fade_sec = rule, fade_sec
     return other
 
 
@@ -537,7 +540,7 @@ class RawSched(SchedSource, RawAuto):
     """A file as stored with a schedule: given (iss_resample_pcm16_sched: one upload, one launch), or decided from its blocked
     survey (iss_survey_blocks, then iss_resample_staged_sched over the survey's upload).  The files of a pass share the launches:
     where any of them is to be decided, all ride on the survey's upload."""
-    __slots__ = ('sched', 'block_chunks')
+    __slots__ = ('sched', 'block_chunks', 'rule', 'fade_sec')
 
     @staticmethod
     def launch_auto(ctx, staged, jobs, tables, srcs, n_signal=-1):

@@ -139,6 +139,22 @@ class ChannelSurvey:
 
 
 DEFAULT_BLOCK_SEC = 10.0         # a definition: the block length of a timeline where none is given
+DEFAULT_FADE_SEC = 0.05          # likewise: the cross-fade at the run boundaries of a steady schedule
+RULES = ('safe', 'steady')       # the decision rules of a timeline: safe_schedule(), steady_schedule()
+
+
+def rule_fade(rule='safe', fade_sec=None):
+    """The cross-fade a timeline's schedule gets, in seconds: fade_sec, or for None the rule's default -- 0 for 'safe' (hard
+    cuts, as ever), DEFAULT_FADE_SEC for 'steady'.  ValueError for a rule that is none of RULES (hysteresis, a minimum run
+    length and fade curves other than the linear one are not offered) and for a fade that is negative or not finite."""
+    if rule not in RULES:
+        raise ValueError(f"rule={rule!r}: 'safe' or 'steady' (no hysteresis, no minimum run length)")
+    if fade_sec is None:
+        return DEFAULT_FADE_SEC if rule == 'steady' else 0.0
+    if isinstance(fade_sec, (bool, np.bool_)) or not isinstance(fade_sec, (int, float, np.integer, np.floating)) or \
+            not math.isfinite(fade_sec) or fade_sec < 0:
+        raise ValueError(f'fade_sec={fade_sec!r}: a finite number of seconds, 0 or above (the fade is linear)')
+    return float(fade_sec)
 
 
 def block_chunks(block_sec, sr):
@@ -192,6 +208,63 @@ class SurveyTimeline:
                 out.append((b * self.block_frames, [b], mix))
         return out or [(0, [], None)]
 
+    def schedule(self, rule='safe', fade_sec=None):
+        """The schedule `rule` decides, its run boundaries cross-faded over rule_fade(rule, fade_sec) seconds: 'safe' is
+        safe_schedule() (with the defaults exactly that), 'steady' is steady_schedule()."""
+        fade = rule_fade(rule, fade_sec)
+        if rule == 'steady':
+            return self.steady_schedule(fade)
+        sched = self.safe_schedule()
+        return R.Schedule(sched.runs, R.fade_halves([b for b, _ in sched.runs], fade, self.sr)) if fade else sched
+
+    def steady_schedule(self, fade_sec=DEFAULT_FADE_SEC):
+        """A schedule that is steady over time -> a resample.Schedule whose runs cross-fade over `fade_sec` seconds
+        (resample.fade_halves; 0: hard cuts).  A definition, as INVERTED_CORR is; pure Python over measured fields, so timelines
+        equal to the bit decide equally:
+          1. One channel: [(0, None)].
+          2. W = the channels that are active() in at least one block, ascending.  W empty: [(0, None)].
+          3. Carried signs start at sign[c] = +1 for each c of W.
+          4. Blocks in ascending order, A = the block's active().  Where len(A) >= 2 and the block has pair sums: r = the channel of
+             A with the largest s2 (ties: the lowest index); raw[c] = -1 where c != r and corr(r, c) <= INVERTED_CORR, else +1
+             (NaN: +1); g = the sum over A of raw[c] * sign[c]; all of raw is negated when g < 0, and when g == 0 and raw[min(A)]
+             != sign[min(A)]; then sign[c] = raw[c] for c of A.  Any other block leaves the signs as they are.  The block decides
+             None when W is every channel and all signs are +1, else Mix(((c, sign[c]) for c of W), divisor = len(W)).
+          5. Adjacent equal decisions merge; run begins are block begins; fades come from resample.fade_halves.
+        What follows: the divisor is constant over a file, so a leg that falls silent makes no boundary and no level jump; a
+        channel dead throughout is dropped, as safe_mix() drops it; polarity is carried from block to block, so one inverted
+        stretch never comes out as (L - R)/2 here and (R - L)/2 there.  Dual-mono material with one leg dead for a stretch comes
+        out 6 dB low there: safe_schedule() gets that case right and the call-recording case wrong, and no rule that sums
+        channels can have both.  No hysteresis on the correlation threshold, no change-point search inside a block."""
+        runs = self.steady_runs()
+        begins = [begin for begin, _, _ in runs]
+        return R.Schedule(((begin, mix) for begin, _, mix in runs), R.fade_halves(begins, fade_sec, self.sr))
+
+    def steady_runs(self):
+        """[(begin frame, [block indices], mix or None)] per run of steady_schedule()."""
+        if self.channels == 1:
+            return [(0, list(range(len(self.blocks))), None)]
+        active = [blk.active() for blk in self.blocks]
+        keep = sorted(set(c for act in active for c in act))
+        if not keep:
+            return [(0, list(range(len(self.blocks))), None)]
+        sign = {c: 1.0 for c in keep}
+        out = []
+        for b, (blk, act) in enumerate(zip(self.blocks, active)):
+            if len(act) >= 2 and blk.s12 is not None:
+                r = max(act, key=lambda c: (float(blk.s2[c]), -c))
+                raw = {c: -1.0 if c != r and blk.corr(r, c) <= INVERTED_CORR else 1.0 for c in act}      # (NaN compares False)
+                g = sum(raw[c] * sign[c] for c in act)
+                if g < 0 or (g == 0 and raw[act[0]] != sign[act[0]]):
+                    raw = {c: -v for c, v in raw.items()}
+                sign.update(raw)
+            plain = len(keep) == self.channels and all(v == 1.0 for v in sign.values())
+            mix = None if plain else R.Mix(tuple((c, sign[c]) for c in keep), float(len(keep)))
+            if out and out[-1][2] == mix:
+                out[-1][1].append(b)
+            else:
+                out.append((b * self.block_frames, [b], mix))
+        return out or [(0, [], None)]
+
     def __repr__(self):
         return f'SurveyTimeline({len(self.blocks)} blocks of {self.block_frames} frames, {self.whole!r})'
 
@@ -207,6 +280,11 @@ def write_schedule_decisions_tsv(dst, names, decisions, failed=None):
     as write_decisions_tsv states them (`mono`: one row, no timeline); downmix_loss_db: the lowest of the run's blocks (empty
     where they have none).  A file in `failed` (path -> error text), or one without a decision, gets one row with plan `!` and
     the text in the last column.  A path listed more than once takes its decisions in their order."""
+    _write_run_decisions(dst, names, decisions, failed, SurveyTimeline.runs)
+
+
+def _write_run_decisions(dst, names, decisions, failed, runs_of):
+    """The table of write_schedule_decisions_tsv, a timeline's runs being runs_of(timeline)."""
     by_name = {}
     for d in decisions:
         by_name.setdefault(d[0], []).append(d)
@@ -222,7 +300,7 @@ def write_schedule_decisions_tsv(dst, names, decisions, failed=None):
             if timeline is None:
                 f.write('\t'.join([name, '', '', '', 'mono', '0', '', '']) + '\n')
                 continue
-            runs, sr, n = timeline.runs(), timeline.sr, timeline.n
+            runs, sr, n = runs_of(timeline), timeline.sr, timeline.n
             for k, (begin, blocks, mix) in enumerate(runs):
                 stop = runs[k + 1][0] if k + 1 < len(runs) else n
                 losses = [timeline.blocks[b].downmix_loss_db for b in blocks]
@@ -231,6 +309,12 @@ def write_schedule_decisions_tsv(dst, names, decisions, failed=None):
                 f.write('\t'.join([name, f'{begin / sr:.6f}', f'{stop / sr:.6f}', str(len(blocks)), 'plain' if mix is None else 'mix',
                                    ','.join(str(c) for c, _ in terms), ','.join(str(c) for c, w in terms if w < 0),
                                    repr(min(losses)) if losses else '']) + '\n')
+
+
+def write_steady_decisions_tsv(dst, names, decisions, failed=None):
+    """write_schedule_decisions_tsv for `--auto-rule steady`: the same columns, one row per run of every file's
+    steady_schedule(), downmix_loss_db the lowest of the run's blocks."""
+    _write_run_decisions(dst, names, decisions, failed, SurveyTimeline.steady_runs)
 
 
 TSV_COLUMNS = ('path', 'channel', 'frames', 'peak', 'rms_db', 'dc', 'zeros', 'fullscale', 'nonfinite', 'active')

@@ -652,6 +652,39 @@ int iss_resample_staged_sched(iss_ctx* ctx, int32_t origin, int64_t payload, con
                               const iss_sched_run* runs, int64_t nruns, const iss_mix* mixes, int64_t nmixes,
                               const iss_mix_term* terms, int64_t nterms);
 
+/* Fades: a schedule whose runs cross-fade in instead of cutting in.  A schedule of "Schedules" gains one half-width h_r >= 0 per
+ * run, counted in stored frames, h_0 = 0.  Run r >= 1 fades in over the ZONE Z_r = [begin_r - h_r, begin_r + h_r).  Zones are
+ * disjoint and in order: begin_{r-1} + h_{r-1} <= begin_r - h_r for every r >= 1.  The first zone may start at frame 0; a zone
+ * may reach past the file's end or lie past it.
+ * Outside every zone m[j] is what "Schedules" says.  For j in Z_r: k = j - (begin_r - h_r), a = (2k + 1) / (4 h_r) -- both
+ * integers exact in float64, one division --, p = mixdown(x[j, :], mix_{r-1}), q = mixdown(x[j, :], mix_r), each by the
+ * arithmetic of "Mixes", and m[j] = p + a * (q - p): the subtraction, the product and the sum each rounded on its own.  The ramp
+ * is linear and sampled at the centres of the zone's 2 h_r frames, so it never reaches 0 or 1: a passes 1/2 between the two
+ * frames either side of begin_r.  NONE is the all-channel mix, as ever; frames outside [0, n) are 0.0; a run that begins at or
+ * past n still fades in over the part of its zone that lies inside the file.  m is resampled and quantised as ever
+ * (inaspeechsegmenter_amd/resample.py's schedule_ref, to the bit).
+ * Two identities, to the bit: all h_r = 0 is the schedule without fades, and a boundary whose two mixes have equal terms and
+ * divisor leaves m as if there were no boundary (q - p = 0, and p + a * 0 = p).
+ * The kernel is resample_kernel's FADE instantiation (a pair, as SCHED's; FADE only with SCHED).  The half-width rides in the
+ * reserved 32 bits of the device's run row.  A workgroup finds the runs of its span's first and last frame once, as SCHED does,
+ * and stages as a mix call stages one mix only where those are one run AND the span touches neither that run's own zone nor the
+ * head of the next run's; any other workgroup finds each frame's run, tests the run's own zone (blend with the run before) and
+ * the next run's (blend with the run after), and stages the blend or the plain mix.  No LDS beyond SCHED's, no scratch.
+ *   iss_resample_pcm16_sched_fade, iss_resample_staged_sched_fade
+ *       their *_sched twin's arguments and `fades`, one half-width per row of `runs` (fades[i] belongs to runs[i]).  A call
+ *       whose half-widths are all 0 launches the SCHED instantiation: the twin's launch, to the bit.
+ * ISS_EINVAL (before anything is launched or the context changes, the text names job and run): a negative half-width, a
+ * non-zero half-width on a job's first run, overlapping zones, and everything the twin refuses.  ISS_ESTATE as the twin.
+ * iss_resample_stats counts as for the twin.  Every other entry point is unchanged, to the bit and to the launch.               */
+int iss_resample_pcm16_sched_fade(iss_ctx* ctx, const void* src, int64_t src_bytes, const iss_resample_job* jobs,
+                                  const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_sched* scheds,
+                                  const iss_sched_run* runs, int64_t nruns, const int32_t* fades, const iss_mix* mixes,
+                                  int64_t nmixes, const iss_mix_term* terms, int64_t nterms);
+int iss_resample_staged_sched_fade(iss_ctx* ctx, int32_t origin, int64_t payload, const iss_resample_job* jobs,
+                                   const iss_window* windows, int32_t njobs, int64_t n_signal, const iss_sched* scheds,
+                                   const iss_sched_run* runs, int64_t nruns, const int32_t* fades, const iss_mix* mixes,
+                                   int64_t nmixes, const iss_mix_term* terms, int64_t nterms);
+
 /* Survey blocks: a survey resolved in time.  A TIMELINE cuts a file's stored frames into BLOCKS of B = K * 1024 frames counted
  * from frame 0: 1024 is ISS_SURVEY_CHUNK, K = max(1, floor(block_sec * sr / 1024 + 0.5)), the default block_sec = 10.0 a
  * definition.  The last block is shorter.  Block b's survey is the survey of frames [b * B, min((b + 1) * B, n)) by "Channel

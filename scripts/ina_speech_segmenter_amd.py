@@ -93,6 +93,13 @@ def build_parser():
                          'is surveyed in blocks of SEC seconds on the GPU and each stretch is downmixed as its own blocks suggest '
                          '(an item recorded out of phase, a leg that is dead for one call); --decisions then writes one row per '
                          'stretch: path, start, stop, blocks, plan, kept, flipped, downmix_loss_db')
+    ap.add_argument('--auto-rule', choices=['safe', 'steady'], default=None,
+                    help="with --auto-block: how the blocks decide.  'safe' (the default) decides every block on its own; 'steady' "
+                         'keeps one divisor per file, so a leg that falls silent for a while changes no level, carries polarity from '
+                         'block to block, and cross-fades where the downmix changes')
+    ap.add_argument('--auto-fade', type=float, default=None, metavar='SEC',
+                    help="with --auto-block: cross-fade over SEC seconds where the downmix changes (default: 0 for 'safe', 0.05 for "
+                         "'steady'); 0 cuts")
     ap.add_argument('--decisions', default=None, metavar='OUT.tsv',
                     help="with --channels auto: write what was decided per file to OUT.tsv -- path, plan (mono, plain, mix; '!' for "
                          'a file that failed, with the error text), the channels kept, those of them turned back, and what the '
@@ -136,6 +143,10 @@ def main(argv=None):
         build_parser().error('--auto-block goes with --channels auto')
     if args.auto_block is not None and not (args.auto_block > 0 and args.auto_block < float('inf')):
         build_parser().error('--auto-block takes a number of seconds above 0')
+    if args.auto_block is None and (args.auto_rule is not None or args.auto_fade is not None):
+        build_parser().error('--auto-rule and --auto-fade go with --auto-block')
+    if args.auto_fade is not None and not (args.auto_fade >= 0 and args.auto_fade < float('inf')):
+        build_parser().error('--auto-fade takes a number of seconds, 0 or above')
     if args.decisions is not None and args.channels != 'auto':
         build_parser().error('--decisions goes with --channels auto')
     mixes = None
@@ -193,11 +204,13 @@ def main(argv=None):
         if world == 1 and args.channels == 'auto':
             decisions = []
             lmsg = seg.batch_process(inputs, outputs, verbose=True, output_format=args.export_format, channels='auto',
-                                     decisions=decisions, **({} if args.auto_block is None else {'auto_block_sec': args.auto_block}))[3]
+                                     decisions=decisions, **({} if args.auto_block is None else {'auto_block_sec': args.auto_block}),
+                                     **({} if args.auto_rule is None else {'auto_rule': args.auto_rule}),
+                                     **({} if args.auto_fade is None else {'auto_fade_sec': args.auto_fade}))[3]
             if args.decisions is not None:
-                from inaspeechsegmenter_amd.survey import write_decisions_tsv, write_schedule_decisions_tsv
+                from inaspeechsegmenter_amd.survey import write_decisions_tsv, write_schedule_decisions_tsv, write_steady_decisions_tsv
                 if args.auto_block is not None:
-                    write_decisions_tsv = write_schedule_decisions_tsv
+                    write_decisions_tsv = write_steady_decisions_tsv if args.auto_rule == 'steady' else write_schedule_decisions_tsv
                 failed = {dst: text for dst, code, text in lmsg if code == 2}
                 write_decisions_tsv(args.decisions, names, decisions, {src: failed[dst] for src, dst in zip(names, outputs)
                                                                         if dst in failed})

@@ -7,11 +7,14 @@ where it is shorter than five minutes).  Timed per set, `--reps` times a leg, al
   timeline  1: seg.batch_process(files, outs, channels='auto', auto_block_sec=--block)
   route     2: what it replaces: io.decode_auto_timeline on the host, one mono WAV written per file, then batch_process on those
   auto      3: the floor: plain channels='auto', one decision per file, which segments the damaged stretches wrongly
-Every CSV of leg 1 must be byte-identical to leg 2's; how many differ from leg 3's is reported.  Kernel times come from the library
+  steady    4: leg 1 with auto_rule='steady' (one divisor per file, carried polarity, run boundaries cross-faded over 50 ms);
+               its CSVs are compared once, untimed, with its own host route: io.decode_auto_timeline(rule='steady')
+Every CSV of leg 1 must be byte-identical to leg 2's, every one of leg 4 to its host route's; how many differ from leg 3's is reported.  Kernel times come from the library
 profiler over one further pass of leg 1 (survey_reduce_blocks_kernel next to survey_reduce_kernel among them).
 Then, in the same process, the SCHED instantiation of resample_kernel against the MIX instantiation: one file's bytes, the same
 single mix, as a one-run schedule, as a schedule of one run per `--block` seconds (all naming that mix), and as a mix call; 15
-alternated runs a side, kernel time from the profiler; both medians and the MIX side's own spread.
+alternated runs a side, kernel time from the profiler; both medians and the MIX side's own spread.  Likewise the FADE instantiation
+against SCHED: a six-run schedule as it is, and with 50 ms fades at its five boundaries.
 Writes one JSON (default profiles/timeline.json) and prints it.
 """
 import argparse
@@ -76,16 +79,16 @@ def generate(tmp, name, nfiles, minutes):
     return files
 
 
-def leg_timeline(seg, files, odir, block):
+def leg_timeline(seg, files, odir, block, **rule):
     outs, decisions = outputs(odir, files), []
     t = time.perf_counter()
-    _, nb, _, lmsg = seg.batch_process(files, outs, channels='auto', auto_block_sec=block, decisions=decisions)
+    _, nb, _, lmsg = seg.batch_process(files, outs, channels='auto', auto_block_sec=block, decisions=decisions, **rule)
     dt = time.perf_counter() - t
     assert nb == len(files), lmsg
     return dt, outs, decisions
 
 
-def leg_route(seg, files, odir, block):
+def leg_route(seg, files, odir, block, **rule):
     import wavgen
     from inaspeechsegmenter_amd import io as iss_io
     outs = outputs(odir, files)
@@ -93,7 +96,7 @@ def leg_route(seg, files, odir, block):
     monos = []
     for f in files:
         monos.append(os.path.join(odir, os.path.basename(f) + '.mono.wav'))
-        wavgen.write_wav(monos[-1], iss_io.decode_auto_timeline(f, block)[0], 16000, 'i16')
+        wavgen.write_wav(monos[-1], iss_io.decode_auto_timeline(f, block, **rule)[0], 16000, 'i16')
     _, nb, _, lmsg = seg.batch_process(monos, outs)
     dt = time.perf_counter() - t
     assert nb == len(files), lmsg
@@ -162,6 +165,38 @@ def kernel_ab(seg, minutes, block, runs=15):
     return out
 
 
+def fade_ab(seg, minutes, runs=15):
+    """The FADE instantiation against SCHED: six runs over one file, hard cuts against 50 ms fades, kernel ms per launch."""
+    from inaspeechsegmenter_amd.resample import Mix, Schedule, fade_halves
+    ctx = seg.ctx
+    x = stored(minutes, True)
+    src = x.reshape(-1).view(np.uint8)
+    job = ctx.resample_job(x, SR, 0, 0)
+    nout = job[-1]
+    mixes = [None, Mix(((0, 1.0), (1, -1.0)), 2.0)]
+    begins = [k * (x.shape[0] // 6) for k in range(6)]
+    hard = Schedule([(b, mixes[k % 2]) for k, b in enumerate(begins)])
+    faded = Schedule(hard.runs, fade_halves(begins, 0.05, SR))
+    sides = {'sched': lambda: ctx.resample_sched(src, [job], [hard], n_signal=nout),
+             'fade': lambda: ctx.resample_sched(src, [job], [faded], n_signal=nout)}
+    for run in sides.values():
+        run()
+    ms = {name: [] for name in sides}
+    ctx.prof_enable(True)
+    for _ in range(runs):
+        for name, run in sides.items():
+            ctx.prof_reset()
+            run()
+            ctx.synchronize()
+            ms[name].append(sum(i['ms'] for i in ctx.prof_instances() if i['kernel'] == 'resample_kernel'))
+    ctx.prof_enable(False)
+    out = {'frames': int(x.shape[0]), 'runs_a_side': runs, 'schedule_runs': 6, 'fade_half_widths': list(faded.fades)}
+    for name, v in ms.items():
+        out[name] = {'ms_median': float(np.median(v)), 'ms_spread': [float(min(v)), float(max(v))]}
+    out['fade_vs_sched'] = out['fade']['ms_median'] / out['sched']['ms_median']
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--files', type=int, default=32)
@@ -182,9 +217,10 @@ def main(argv=None):
     for name in [s for s in args.sets.split(',') if s]:
         hours = args.files * args.minutes / 60.0
         files = generate(tmp, name, args.files, args.minutes)
-        dirs = {leg: os.path.join(tmp, f'{name}_{leg}') for leg in ('timeline', 'route', 'auto')}
+        dirs = {leg: os.path.join(tmp, f'{name}_{leg}') for leg in ('timeline', 'route', 'auto', 'steady', 'steady_route')}
         legs = {'timeline': lambda: leg_timeline(seg, files, dirs['timeline'], args.block),
-                'route': lambda: leg_route(seg, files, dirs['route'], args.block), 'auto': lambda: leg_auto(seg, files, dirs['auto'], args.block)}
+                'route': lambda: leg_route(seg, files, dirs['route'], args.block), 'auto': lambda: leg_auto(seg, files, dirs['auto'], args.block),
+                'steady': lambda: leg_timeline(seg, files, dirs['steady'], args.block, auto_rule='steady')}
         runs, nbytes, outs, decisions = {leg: [] for leg in legs}, {}, {}, None
         for leg, run in legs.items():                                  # warm-up, the outputs compared, the bytes a leg uploads
             before = uploaded(seg)
@@ -192,6 +228,11 @@ def main(argv=None):
             nbytes[leg], outs[leg] = uploaded(seg) - before, got[1]
             if leg == 'timeline':
                 decisions = got[2]
+            if leg == 'steady':
+                steady = got[2]
+        twin = leg_route(seg, files, dirs['steady_route'], args.block, rule='steady')[1]      # once, untimed: the steady leg's own host route
+        steady_same = all(filecmp.cmp(a, b, shallow=False) for a, b in zip(outs['steady'], twin))
+        ok = ok and steady_same
         same = all(filecmp.cmp(a, b, shallow=False) for a, b in zip(outs['timeline'], outs['route']))
         differ = sum(not filecmp.cmp(a, b, shallow=False) for a, b in zip(outs['timeline'], outs['auto']))
         ok = ok and same
@@ -201,13 +242,17 @@ def main(argv=None):
             print('%-10s %s' % (name, ', '.join('%s %.3f s' % (leg, runs[leg][-1]) for leg in legs)), flush=True)
         entry = {'file_hours_per_leg': hours, 'file_bytes': os.path.getsize(files[0]), 'csv_timeline_equals_route': same,
                  'csv_timeline_differs_from_auto': differ, 'files_with_more_than_one_run': sum(len(d[2]) > 1 for d in decisions),
-                 'schedules': sorted({repr(d[2]) for d in decisions if len(d[2]) > 1})}
+                 'schedules': sorted({repr(d[2]) for d in decisions if len(d[2]) > 1}),
+                 'csv_steady_equals_its_host_route': steady_same,
+                 'csv_steady_differs_from_timeline': sum(not filecmp.cmp(a, b, shallow=False) for a, b in zip(outs['steady'], outs['timeline'])),
+                 'steady_schedules': sorted({repr(d[2]) for d in steady if len(d[2]) > 1})}
         for leg in legs:
             entry[leg] = {'s_runs': runs[leg], 's_median': float(np.median(runs[leg])), 'payload_bytes_uploaded': nbytes[leg],
                           'file_h_per_s_median': hours / float(np.median(runs[leg])),
                           'file_h_per_s_spread': [hours / max(runs[leg]), hours / min(runs[leg])]}
         entry['route_vs_timeline'] = entry['route']['s_median'] / entry['timeline']['s_median']
         entry['timeline_vs_auto'] = entry['timeline']['s_median'] / entry['auto']['s_median']
+        entry['steady_vs_timeline'] = entry['steady']['s_median'] / entry['timeline']['s_median']
         entry['timeline']['kernels'] = profiled(seg, legs['timeline'])
         result['sets'][name] = entry
         print('%-10s %s' % (name, json.dumps(entry)), flush=True)
@@ -216,6 +261,7 @@ def main(argv=None):
         with open(path, 'w') as f:                                     # (after every set: a run cut short leaves what it measured)
             json.dump(result, f, indent=1)
     result['sched_vs_mix_instantiation'] = kernel_ab(seg, args.minutes, args.block)
+    result['fade_vs_sched_instantiation'] = fade_ab(seg, args.minutes)
     with open(path, 'w') as f:
         json.dump(result, f, indent=1)
     seg.close()
